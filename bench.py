@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py — deflate+inflate throughput of the MI355X DEFLATE engine on BASELINE.json's workloads.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
     python bench.py --gpus N --inproc            # ONE process driving N GPUs through the host batch API (row n1)
@@ -15,14 +15,19 @@ all_reduce of the sizes, one exact-length send per rank over xGMI), in flight wh
 kernels run and finished inside the timed region.
 
 Rank 0 prints ONE JSON line.  `value` is GiB/s of uncompressed bytes taken through
-deflate-then-inflate by the whole job (n * N * K / wall).  Every timed loop (exactly K steps between
-barrier + synchronize) runs REPS = 3 times: the line carries the median, and the minimum and maximum
-beside it, so that a slow box and a slow build can be told apart.  `roofline` prices the dominant
-kernel (by HIP-event time on the library's stream) against HBM; `cpu_baseline` is the CPU oracle (a
-port of the reference algorithm) timed on this box's host cores on a bounded sample of the same input.
+deflate-then-inflate by the whole job (n * N * K / wall), `ms_per_step` the wall time of one step.  A
+plain run sets up, checks the result of one untimed step against the reference-run golden (the
+line's `verified_bit_exact`), warms up W steps, times exactly K steps between barrier + synchronize,
+writes the last timed step's results if `--dump-outputs DIR` is given, and prints the line.
 
-The same process then runs the other BASELINE.json configurations as further legs of the same line,
-each with its own golden flag, roofline and cpu_baseline:
+Everything else is measured under `--full` only.  There every timed loop runs REPS = 3 times: the
+line carries the median, and the minimum and maximum beside it, so that a slow box and a slow build
+can be told apart.  `roofline` prices the dominant kernel (by HIP-event time on the library's stream)
+against HBM; `cpu_baseline` is the CPU oracle (a port of the reference algorithm) timed on this box's
+host cores on a bounded sample of the same input.
+
+Under `--full` the same process then runs the other BASELINE.json configurations as further legs of
+the same line, each with its own golden flag, roofline and cpu_baseline:
   "text64"     configs[2]: one 64 MiB text-like buffer per GPU — deflate loop, then the inflate-only hot loop
   "batch1m"    configs[3]: this GPU's 128 of the 1024 x 1 MiB buffers through the batch entry points
   "lowent256"  configs[4]: one of the 8 x 256 MiB low-entropy buffers
@@ -31,6 +36,11 @@ each with its own golden flag, roofline and cpu_baseline:
                (reference src/zlib.ts:11,25): zes_deflate / zes_inflate_alloc on pageable and on pinned host
                arrays, PCIe included, random64 + text64 — and the same through Node when `node` is on the box.
 `--workload X` makes X the only leg.
+
+`--dump-outputs DIR` writes what the timed path computed in its last step (rank 0's buffers) as
+DIR/<name>.npy: the compressed stream and the inflated bytes as float32 (streams longer than
+DUMP_SAMPLE bytes as a fixed, seeded sample), each with its length and its CRC-32 over all of it as
+float64.  The inputs are seeded, so two builds can be compared output for output.
 """
 import argparse
 import hashlib
@@ -44,7 +54,9 @@ sys.path.insert(0, ROOT)
 
 HBM_PEAK_GBS = 8000.0  # MI355X_MICROARCH.md: 8.0 TB/s spec
 GIB = float(1 << 30)
-REPS = 3               # every timed loop runs this often: median reported, min / max beside it
+REPS = 3               # --full: every timed loop runs this often: median reported, min / max beside it
+DUMP_SAMPLE = 1 << 22  # --dump-outputs: bytes per stream written at most (float32: 16 MiB); longer ones are sampled
+DUMP_SEED = 20261015   # the sample's positions: fixed for a given stream length
 
 WORKLOADS = {
     # name: (generator, seed, bytes per buffer[, buffers per GPU])
@@ -76,6 +88,33 @@ def _median(xs):
 def _spread(xs, scale=1.0, nd=4):
     """median / min / max of the repeats of one timed loop"""
     return {"median": round(_median(xs) * scale, nd), "min": round(min(xs) * scale, nd), "max": round(max(xs) * scale, nd)}
+
+
+def dump_outputs(path, outputs):
+    """--dump-outputs DIR: `outputs` maps a name to a uint8 stream (host array) or to a list of lengths.  A stream goes to
+    DIR/<name>.npy as float32 (whole up to DUMP_SAMPLE bytes, else at DUMP_SAMPLE sorted positions drawn with DUMP_SEED),
+    with DIR/<name>_length.npy and DIR/<name>_crc32.npy (float64) over all of it; lengths go to DIR/<name>.npy as
+    float64.  -> {file name: bytes written}"""
+    import zlib as pyzlib
+
+    import numpy as np
+
+    os.makedirs(path, exist_ok=True)
+    written = {}
+    for name, a in outputs.items():
+        if isinstance(a, np.ndarray):
+            a = np.ascontiguousarray(a).view(np.uint8).reshape(-1)
+            sample = a
+            if a.size > DUMP_SAMPLE:
+                sample = a[np.sort(np.random.default_rng(DUMP_SEED).integers(0, a.size, DUMP_SAMPLE))]
+            arrays = {name: sample.astype(np.float32), name + "_length": np.array([a.size], dtype=np.float64),
+                      name + "_crc32": np.array([pyzlib.crc32(a)], dtype=np.float64)}
+        else:
+            arrays = {name: np.array([int(x) for x in a], dtype=np.float64)}
+        for k, v in arrays.items():
+            np.save(os.path.join(path, k + ".npy"), v)
+            written[k + ".npy"] = int(v.nbytes)
+    return written
 
 
 class Leg:
@@ -143,6 +182,22 @@ class Leg:
             return comp, [int(comp.numel())]
         arena = self.d_comp[slot]
         return torch.cat([arena[o:o + l] for o, l in zip(self.c_off, comp)]), [int(x) for x in comp]
+
+    def outputs(self, comp, slot=0):
+        """What a caller of the timed path receives from one step (host copies): the compressed stream(s) of this GPU's
+        buffers (back to back, with their lengths when there are several) and the inflated bytes."""
+        import numpy as np
+
+        out = {}
+        if not self.foreign:
+            if self.nbuf == 1:
+                out["deflate"] = comp.cpu().numpy()
+            else:
+                arena = self.d_comp[slot].cpu().numpy()
+                out["deflate"] = np.concatenate([arena[o:o + l] for o, l in zip(self.c_off, comp)])
+                out["deflate_lengths"] = list(comp)
+        out["inflate"] = self.d_back.cpu().numpy()
+        return out
 
     def note_times(self, direction):
         for name, ms, launches in self.env["z"].last_kernel_times():
@@ -512,8 +567,9 @@ def main_inproc(args):
     for _ in range(args.warmup):
         deflate()
         inflate()
+    reps = REPS if args.full else 1
     td, ti = [], []
-    for _ in range(REPS):
+    for _ in range(reps):
         t0 = time.perf_counter()
         for _ in range(args.steps):
             deflate()
@@ -526,6 +582,9 @@ def main_inproc(args):
     total = cnt * n1
     md, mi = _median(td), _median(ti)
     ctot = int(sum(clen))
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"deflate": np.concatenate([comp[i * cap1:i * cap1 + int(clen[i])] for i in range(cnt)]),
+                                         "deflate_lengths": list(clen), "inflate": back})
     line = {
         "metric": "GiB/s deflate+inflate round trip, 1 MiB buffers through the host batch API of ONE process driving N GPUs (uncompressed bytes / wall, PCIe included), bit-exact vs reference",
         "value": round(total * args.steps / (md + mi) / GIB, 4), "unit": "GiB/s", "n_gpus": got, "steps": args.steps, "warmup": args.warmup,
@@ -537,7 +596,7 @@ def main_inproc(args):
                    "parallelism": "one host process, %d device contexts, buffers partitioned by size (zes_partition), no collective" % got,
                    "buffers_per_context": [owners.count(d) for d in range(got)],
                    "oversubscribed": bool(os.environ.get("ZES_OVERSUBSCRIBE")), "gather": None},
-        "repeats": REPS,
+        "repeats": reps,
         "deflate_gibs": round(total * args.steps / md / GIB, 4), "inflate_gibs": round(total * args.steps / mi / GIB, 4),
         "deflate_ms": _spread([t / args.steps for t in td], 1e3), "inflate_ms": _spread([t / args.steps for t in ti], 1e3),
         "verified_bit_exact": ok, "golden_sha256_checked": golden,
@@ -560,6 +619,11 @@ def main():
     ap.add_argument("--no-gather", action="store_true", help="N > 1: leave the compressed shards where they are")
     ap.add_argument("--no-extra-legs", action="store_true", help="only the main leg and text64")
     ap.add_argument("--inproc", action="store_true", help="one process drives all N GPUs through the host batch API (no RCCL)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline figure: %d repeats of every timed loop, per-kernel times and rooflines, "
+                         "CPU baselines, the further legs and the host-pointer API" % REPS)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's results as DIR/<name>.npy (float32 / float64)")
     args = ap.parse_args()
 
     if args.inproc:
@@ -598,7 +662,8 @@ def main():
     z.init(local_dev)
     env = {"z": z, "dev": dev, "rank": rank, "world": world}
     main_name = args.workload or "random64"
-    extra = [] if args.workload else (["text64"] if args.no_extra_legs else list(EXTRA_LEGS))
+    extra = [] if (args.workload or not args.full) else (["text64"] if args.no_extra_legs else list(EXTRA_LEGS))
+    nrep = REPS if args.full else 1
     shard = None
     if world > 1 and not args.no_gather:
         import importlib.util
@@ -657,8 +722,11 @@ def main():
         if got is not None:
             gathered_bytes[0] += int(sum(got.length))
 
+    last = [None, 0]  # the compressed result of the latest step and its arena slot (--dump-outputs)
+
     def step(k, pending, timed):
         slot = k & 1 if world > 1 else 0
+        timed = timed and args.full  # per-kernel times: --full only
         ta = time.perf_counter()
         comp = leg.run_deflate(slot)
         if timed and not leg.foreign:
@@ -668,6 +736,7 @@ def main():
         if timed:
             leg.note_times("inflate")
         tc = time.perf_counter()
+        last[:] = [comp, slot]
         if shard is not None:
             # the gather of the step before has had this step's kernels to hide behind; its arena is free again
             finish(pending)
@@ -683,9 +752,9 @@ def main():
     finish(pending)
     pending = None
 
-    z.set_profiling(True)
+    z.set_profiling(args.full)
     reps = []  # (elapsed, deflate seconds, inflate seconds) of each repeat of the K timed steps
-    for _ in range(REPS):
+    for _ in range(nrep):
         gathered_bytes[0] = 0
         t_def = t_inf = 0.0
         pending = None
@@ -702,8 +771,11 @@ def main():
         reps.append((elapsed, t_def, t_inf))
     z.set_profiling(False)
     elapsed, t_def, t_inf = sorted(reps)[len(reps) // 2]
-    n_timed = REPS * args.steps  # launches the kernel-time sums cover
+    n_timed = nrep * args.steps  # launches the kernel-time sums cover
     main_pool = z.pool_bytes()
+    if args.dump_outputs and rank == 0 and args.steps > 0:
+        written = dump_outputs(args.dump_outputs, leg.outputs(*last))
+        print("bench.py: %d bytes of the last timed step's results in %s" % (sum(written.values()), args.dump_outputs), file=sys.stderr, flush=True)
     d_lo, d_hi = (0.0, 0.0) if leg.foreign else minmax_over_ranks(leg.n * args.steps / t_def / GIB)
     i_lo, i_hi = minmax_over_ranks(leg.n * args.steps / t_inf / GIB)
 
@@ -796,19 +868,21 @@ def main():
         if both:
             dom = max(both.items(), key=lambda kv: kv[1][0])[0]
             dom_dir = "deflate" if dom in leg.ktimes["deflate"] else "inflate"
-        roofline = leg.roofline(dom_dir, c)
-        cpu = None if (world > 1 or args.no_cpu_baseline) else leg.cpu_baseline()
-        # measured HBM copy bandwidth on this box (report against vendor peak and a measured copy)
-        torch.cuda.synchronize()
-        tcp = time.perf_counter()
-        for _ in range(20):
-            leg.d_back.copy_(leg.d_in)
-        torch.cuda.synchronize()
-        copy_gbs = 2 * n * 20 / (time.perf_counter() - tcp) / 1e9
-        for r in [roofline] + [x for lg in legs.values() if lg for x in (lg["roofline"], lg["roofline_deflate"])]:
-            if r:
-                r["measured_copy_GBs"] = round(copy_gbs, 1)
-                r["frac_of_measured_copy"] = round(r["achieved"] / copy_gbs, 5)
+        roofline = cpu = None
+        if args.full:
+            roofline = leg.roofline(dom_dir, c)
+            cpu = None if (world > 1 or args.no_cpu_baseline) else leg.cpu_baseline()
+            # measured HBM copy bandwidth on this box (report against vendor peak and a measured copy)
+            torch.cuda.synchronize()
+            tcp = time.perf_counter()
+            for _ in range(20):
+                leg.d_back.copy_(leg.d_in)
+            torch.cuda.synchronize()
+            copy_gbs = 2 * n * 20 / (time.perf_counter() - tcp) / 1e9
+            for r in [roofline] + [x for lg in legs.values() if lg for x in (lg["roofline"], lg["roofline_deflate"])]:
+                if r:
+                    r["measured_copy_GBs"] = round(copy_gbs, 1)
+                    r["frac_of_measured_copy"] = round(r["achieved"] / copy_gbs, 5)
         foreign = leg.foreign
         line = {
             "metric": ("GiB/s inflate of a 64 MiB zlib level-6 stream (uncompressed bytes / wall), output identical to the input" if foreign else
@@ -836,8 +910,8 @@ def main():
                                   "before's lengths, sizes all_reduce read behind it), overlapped with the next step, completed inside the timed "
                                   "region: %d result bytes on rank 0 per step"
                                   % (gathered_bytes[0] // max(args.steps, 1)))},
-            # every timed loop ran REPS times (exactly `steps` steps each): value / ms_per_step are the median repeat's
-            "repeats": REPS,
+            # every timed loop ran `repeats` times (exactly `steps` steps each): value / ms_per_step are the median repeat's
+            "repeats": nrep,
             "value_spread": _spread(vals),
             "ms_per_step_spread": _spread([r[0] / args.steps for r in reps], 1e3),
             "deflate_gibs_per_gpu": None if foreign else round(n * args.steps / t_def / GIB, 4),
@@ -855,7 +929,8 @@ def main():
             "roofline": roofline,
             "cpu_baseline": cpu,
             "pool_bytes": main_pool,
-            "kernels_ms_per_step": {k: round(v[0] / n_timed, 4) for k, v in sorted(both.items(), key=lambda kv: -kv[1][0])},
+            "kernels_ms_per_step": ({k: round(v[0] / n_timed, 4) for k, v in sorted(both.items(), key=lambda kv: -kv[1][0])}
+                                    if args.full else None),
         }
         for name in extra:
             line[name] = legs[name]

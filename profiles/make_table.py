@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""The measured table of DESIGN.md §6 from one bench.py line:  python3 profiles/make_table.py <bench json> [--write]
+"""The measured table of DESIGN.md §6 from one `bench.py --full` line:  python3 profiles/make_table.py <bench json> [--write]
 (--write: replaces the text between the MEASURED markers of DESIGN.md)"""
 import json
 import os

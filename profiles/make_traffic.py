@@ -7,7 +7,7 @@ import sys
 
 here = os.path.dirname(os.path.abspath(__file__))
 tag, wls = sys.argv[1], sys.argv[2:]
-out = {"_note": "HBM bytes per launch from rocprofv3 PMC passes (separate --pmc FETCH_SIZE and --pmc WRITE_SIZE runs of `bench.py --steps 2 "
+out = {"_note": "HBM bytes per launch from rocprofv3 PMC passes (separate --pmc FETCH_SIZE and --pmc WRITE_SIZE runs of `bench.py --full --steps 2 "
                 "--workload W`, profiles/collect.sh): (2 x FETCH_SIZE + WRITE_SIZE) KiB x 1024 / launches; FETCH_SIZE doubled per "
                 "MI355X_MICROARCH.md (gfx950 reports half of a wide streaming read; dword-wide and byte loads are uncalibrated, so the read "
                 "side is an upper estimate). Source: profiles/%s_pmc_{%s}.json" % (tag, ",".join(wls))}

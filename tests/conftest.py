@@ -1,6 +1,5 @@
 import json
 import os
-import shutil
 import sys
 
 import pytest
@@ -23,6 +22,11 @@ def golden(name):
 @pytest.fixture(scope="session")
 def z():
     """The product package (zlib.es_amd/ loaded as zlibes_amd); builds the HIP library if missing."""
+    # torch before the library, whichever test asks first: PyTorch ships its own HIP runtime, and libzes_hip.so
+    # (NEEDED libamdhip64.so.7) shares it only if it is already loaded.  The other way round the process gets two HIP
+    # runtimes, and the one that opens the GPU second fails (zes_init: ZES_E_DEVICE in every GPU test after a CPU test).
+    import torch  # noqa: F401
+
     import __graft_entry__ as ge
 
     mod = ge.load()
@@ -48,6 +52,3 @@ def gpu(z):
     z.init(0)
     return torch.device("cuda:0")
 
-
-def have_reference():
-    return os.path.exists("/root/reference/dist/cjs/zlib.js") and shutil.which("node") is not None

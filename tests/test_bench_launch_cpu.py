@@ -53,6 +53,14 @@ def test_gpus_n_starts_the_ranks_as_a_child_and_relays_the_line():
     assert cmd[k + 1:] == ["--gpus", "2", "--steps", "3", "--warmup", "1"]
 
 
+def test_full_and_dump_outputs_reach_the_ranks():
+    line = json.dumps({"metric": "m", "value": 1.0, "n_gpus": 2, "config": {"gather": "x"}})
+    rec, lines = _run(["--gpus", "2", "--steps", "4", "--full", "--dump-outputs", "out"], [[0, line + "\n"]])
+    assert rec["rc"] == 0 and lines == [line]
+    cmd = rec["calls"][0]
+    assert cmd[cmd.index(os.path.join(ROOT, "bench.py")) + 1:] == ["--gpus", "2", "--steps", "4", "--full", "--dump-outputs", "out"]
+
+
 def test_failed_ranks_are_started_once_more_without_the_gather():
     line = json.dumps({"metric": "m", "value": 1.0, "n_gpus": 4, "config": {"gather": None}})
     rec, lines = _run(["--gpus", "4"], [[1, "Traceback ...\n"], [0, line + "\n"]])

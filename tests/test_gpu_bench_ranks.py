@@ -19,7 +19,8 @@ pytestmark = pytest.mark.gpu
 def test_two_ranks_rehearsal_over_gloo(gpu):
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     env["ZES_BENCH_BACKEND"] = "gloo"
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--no-extra-legs"],
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--full", "--no-cpu-baseline",
+                          "--no-extra-legs"],
                          capture_output=True, text=True, timeout=600, env=env)
     assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-3000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
@@ -51,10 +52,10 @@ def test_one_process_two_contexts_inproc_rehearsal(gpu):
 
 
 def test_every_leg_of_the_default_line(gpu):
-    """`python bench.py` (what the driver runs, shortened): the main leg and every further leg — text64, batch1m, lowent256,
+    """`python bench.py --full` (shortened): the main leg and every further leg — text64, batch1m, lowent256,
     zlibtext64, host_api — are in the ONE line, each verified, each with its roofline."""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--no-cpu-baseline"],
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline"],
                          capture_output=True, text=True, timeout=900, env=env)
     assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-3000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
@@ -71,3 +72,37 @@ def test_every_leg_of_the_default_line(gpu):
     for r in h["rows"].values():
         assert r["golden_sha256_checked"] is True and r["deflate_gibs"] > 0 and r["inflate_gibs"] > 0
     assert "failed" not in (h["node"] or {})
+
+
+def test_plain_line_times_k_steps_and_dumps_the_last_one(gpu, z, tmp_path):
+    """`python bench.py --steps K --warmup W --dump-outputs DIR`: the random64 leg alone, ONE timed loop of exactly K steps,
+    verified against the reference-run golden; DIR holds the last timed step's compressed stream and inflated bytes
+    (seeded samples of float32, their lengths and CRC-32s), the inflated ones equal to the seeded input."""
+    import zlib as pyzlib
+
+    import numpy as np
+
+    sys.path.insert(0, ROOT)
+    import bench
+
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--dump-outputs", str(tmp_path)],
+                         capture_output=True, text=True, timeout=600, env=env)
+    assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-3000:]
+    lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1
+    d = json.loads(lines[0])
+    assert d["steps"] == 3 and d["repeats"] == 1 and d["unit"] == "GiB/s" and d["higher_is_better"] is True and d["dtype"] == "u8"
+    assert d["verified_bit_exact"] is True and d["golden_sha256_checked"] is True
+    n = 64 << 20
+    assert abs(d["value"] - n / (d["ms_per_step"] / 1e3) / (1 << 30)) <= 0.01 * d["value"]
+    assert not any(k in d for k in ("text64", "batch1m", "lowent256", "zlibtext64", "host_api"))
+    files = {f: np.load(os.path.join(tmp_path, f)) for f in os.listdir(tmp_path)}
+    assert set(files) == {"%s%s.npy" % (a, b) for a in ("deflate", "inflate") for b in ("", "_length", "_crc32")}
+    assert all(v.dtype in (np.float32, np.float64) for v in files.values())
+    assert sum(os.path.getsize(os.path.join(tmp_path, f)) for f in files) <= 64 * 10**6
+    src = z.gen("xorshift", 12345, n)
+    idx = np.sort(np.random.default_rng(bench.DUMP_SEED).integers(0, n, bench.DUMP_SAMPLE))
+    assert files["inflate_length.npy"][0] == n and files["inflate_crc32.npy"][0] == pyzlib.crc32(src)
+    assert (files["inflate.npy"] == src[idx].astype(np.float32)).all()
+    assert files["deflate_length.npy"][0] == d["config"]["compressed_bytes"] and files["deflate.npy"].size == bench.DUMP_SAMPLE
