@@ -38,7 +38,9 @@ typedef enum zes_status {
   ZES_E_NOSPACE = -16,      /* caller's output capacity too small; *out_len holds the size needed when known */
   ZES_E_DEVICE = -17,       /* HIP runtime error / no gfx950 device */
   ZES_E_ARG = -18,          /* bad argument (null pointer, size overflow) */
-  ZES_E_NOTRANGE = -19      /* zes_inflate_range_dev: the range does not hold a clean chain of reference-made blocks */
+  ZES_E_NOTRANGE = -19,     /* zes_inflate_range_dev: the range does not hold a clean chain of reference-made blocks */
+  ZES_E_GZIP = -20,         /* zes_gunzip*: not a gzip member (magic, CM, reserved flags, a header cut short), c == 0, or a trailer cut short */
+  ZES_E_CHECKSUM = -21      /* a trailer does not match the data: gzip CRC-32 / ISIZE / FHCRC, or zlib Adler-32 with ZES_F_CHECK_ADLER */
 } zes_status;
 
 /* Geometry of the reference format (src/const.ts:7). */
@@ -57,6 +59,9 @@ typedef enum zes_status {
                                  ZES_ALLOC_EARLY in its index argument; the allocator may answer it with NULL ("not now": no block of
                                  that size at hand) and is then asked once, later, for the exact size as without the flag */
 #define ZES_ALLOC_EARLY 0x80000000u
+#define ZES_F_CHECK_ADLER 16u  /* zes_inflate, zes_inflate_dev, zes_inflate_size, zes_inflate_alloc: the 4 bytes behind the stream must
+                                  exist and hold the Adler-32 of the result (big-endian), else ZES_E_CHECKSUM.  Without the flag the
+                                  trailer is ignored, as the reference ignores it (src/zlib.ts:11-23) */
 #define ZES_F_LOOSE_CANDIDATES 2u /* block-start search without the reference's run-length-coding rules: more false
                                   * candidates reach the block decoder (testing aid for that path; same results) */
 
@@ -146,6 +151,54 @@ int zes_deflate_raw_dev(const uint8_t* d_in, uint64_t n, uint8_t* d_out, uint64_
 int zes_inflate_raw(const uint8_t* in, uint64_t c, uint64_t offset, uint8_t* out, uint64_t cap, uint64_t* out_len, uint32_t flags);
 int zes_inflate_raw_dev(const uint8_t* d_in, uint64_t c, uint64_t offset, uint8_t* d_out, uint64_t cap, uint64_t* out_len,
                         uint32_t flags);
+
+/* Where a raw stream ends: zes_inflate_raw* that also report *in_used = the bytes from `offset` up to and including the
+ * byte that holds the final block's last bit (behind its end-of-block code, or its last stored byte) — the count of
+ * len(body) - len(zlib.decompressobj(-15).unused_data).  For containers that put DEFLATE streams back to back (gzip
+ * members, ZIP entries, PDF object streams).  Statuses and results are those of zes_inflate_raw*; *in_used is set
+ * on ZES_OK only.
+ * replaces: nothing (src/inflate.ts:16-40 does not say where it stopped). */
+int zes_inflate_raw_used(const uint8_t* in, uint64_t c, uint64_t offset, uint8_t* out, uint64_t cap, uint64_t* out_len, uint64_t* in_used,
+                         uint32_t flags);
+int zes_inflate_raw_used_dev(const uint8_t* d_in, uint64_t c, uint64_t offset, uint8_t* d_out, uint64_t cap, uint64_t* out_len,
+                             uint64_t* in_used, uint32_t flags);
+
+/* CRC-32 of a buffer: the checksum of gzip, zlib's crc32() and PNG (reflected polynomial 0xEDB88320, initial value and
+ * final XOR 0xFFFFFFFF).  The device form reads d_in at any alignment.
+ * replaces: nothing (the reference has no CRC-32). */
+int zes_crc32(const uint8_t* in, uint64_t n, uint32_t* crc);
+int zes_crc32_dev(const uint8_t* d_in, uint64_t n, uint32_t* crc);
+
+/* gzip (RFC 1952) compress: one member whose
+ *   header  is exactly 1f 8b 08 00 00 00 00 00 00 ff (FLG 0, MTIME 0, XFL 0, OS 255: the output is deterministic),
+ *   body    is exactly the bytes of zes_deflate_raw (the reference's stream), and
+ *   trailer is the CRC-32 of the input, then ISIZE = n mod 2^32, both little-endian.
+ * zes_gzip_bound: a capacity that always suffices (zes_deflate_bound(n) - 6 + 18).
+ * n == 0, n == 1 and n % 131072 == 1 return ZES_E_CORRUPT before the device is touched: the body is the reference's
+ * encoder, which throws on those sizes.  d_out must be 16-byte aligned, as for zes_deflate_dev.
+ * replaces: nothing for the container; the body is `export function deflate(input)` of src/deflate.ts:14-39. */
+int zes_gzip_bound(uint64_t n, uint64_t* cap);
+int zes_gzip(const uint8_t* in, uint64_t n, uint8_t* out, uint64_t cap, uint64_t* out_len);
+int zes_gzip_dev(const uint8_t* d_in, uint64_t n, uint8_t* d_out, uint64_t cap, uint64_t* out_len);
+
+/* gzip (RFC 1952) decompress, as CPython 3.10's gzip.decompress: any number of members back to back, their outputs
+ * concatenated; zero bytes between and after members are skipped.  Header: 1f 8b, CM 8; FEXTRA, FNAME and FCOMMENT are
+ * skipped, FHCRC is checked against the low 16 bits of the header's CRC-32.  Each body is decoded as by
+ * zes_inflate_raw_used (every tier: a reference-made body takes the block-parallel one); the 8 bytes behind it must
+ * hold the CRC-32 and ISIZE of the member's output.
+ *   ZES_E_GZIP      bad magic, CM != 8, reserved FLG bits 5-7 set (CPython ignores them; zlib does not), a header cut
+ *                   short, c == 0 (CPython returns b""), fewer than 8 bytes behind a body, non-zero bytes behind a
+ *                   member that do not start a valid member
+ *   ZES_E_CHECKSUM  CRC-32 or ISIZE mismatch, or a wrong FHCRC (CPython does not check FHCRC)
+ *   an error inside a body: the status zes_inflate_raw returns on those bytes
+ *   ZES_E_NOSPACE   as for zes_inflate: *out_len = the size needed
+ * Header errors of the host forms are decided before the device is touched.  The device form writes whole 16-byte
+ * groups as zes_inflate_dev does (d_out 16-byte aligned; d_in at any alignment).  zes_gunzip_alloc: as
+ * zes_inflate_alloc (one alloc call, index 0, for the exact size).
+ * replaces: nothing (the reference has no gzip container). */
+int zes_gunzip(const uint8_t* in, uint64_t c, uint8_t* out, uint64_t cap, uint64_t* out_len, uint32_t flags);
+int zes_gunzip_dev(const uint8_t* d_in, uint64_t c, uint8_t* d_out, uint64_t cap, uint64_t* out_len, uint32_t flags);
+int zes_gunzip_alloc(const uint8_t* in, uint64_t c, zes_alloc_fn alloc, void* user, uint64_t* out_len, uint32_t flags);
 
 /* Adler-32 of a buffer (standard value as an unsigned 32-bit).
  * replaces: `calcAdler32` src/adler32.ts:1-10 (byte extraction at src/zlib.ts:37-40). */

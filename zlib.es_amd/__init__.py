@@ -41,6 +41,9 @@ ZES_F_PIECES = 4
 ZES_F_ALLOC_BOUND = 8
 ZES_ALLOC_EARLY = 0x80000000  # in the allocator's index argument: an early request for an upper estimate (may be declined with NULL)
 ZES_E_NOTRANGE = -19
+ZES_E_GZIP = -20  # zes_gunzip*: not a valid gzip member (header, or a trailer cut short), or no input at all
+ZES_E_CHECKSUM = -21  # a trailer does not match: gzip CRC-32 / ISIZE / FHCRC, zlib Adler-32 under ZES_F_CHECK_ADLER
+ZES_F_CHECK_ADLER = 16  # zes_inflate*: the Adler-32 trailer behind the stream must be there and match
 
 GEN_KINDS = {"xorshift": 0, "lowent4k": 1, "itext": 2}
 
@@ -99,6 +102,16 @@ def lib():
             getattr(L, name).argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, u64p]
         for name in ("zes_inflate_raw", "zes_inflate_raw_dev"):
             getattr(L, name).argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_uint64, u64p, C.c_uint32]
+        for name in ("zes_inflate_raw_used", "zes_inflate_raw_used_dev"):
+            getattr(L, name).argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_uint64, u64p, u64p, C.c_uint32]
+        for name in ("zes_crc32", "zes_crc32_dev"):
+            getattr(L, name).argtypes = [C.c_void_p, C.c_uint64, u32p]
+        L.zes_gzip_bound.argtypes = [C.c_uint64, u64p]
+        for name in ("zes_gzip", "zes_gzip_dev"):
+            getattr(L, name).argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, u64p]
+        for name in ("zes_gunzip", "zes_gunzip_dev"):
+            getattr(L, name).argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, u64p, C.c_uint32]
+        L.zes_gunzip_alloc.argtypes = [C.c_void_p, C.c_uint64, ALLOC_FN, C.c_void_p, u64p, C.c_uint32]
         L.zes_adler32.argtypes = [C.c_void_p, C.c_uint64, u32p]
         L.zes_adler32_dev.argtypes = [C.c_void_p, C.c_uint64, u32p]
         L.zes_deflate_batch_dev.argtypes = [C.c_void_p, u64p, u64p, C.c_void_p, u64p, u64p, u64p, i32p, C.c_uint32]
@@ -312,6 +325,68 @@ def inflate_raw(data, offset=0, flags=0):
     _raise(ZES_E_DEVICE)
 
 
+def inflate_raw_used(data, offset=0, flags=0):
+    """Raw inflate from byte ``offset`` that also says where the stream ended: ``(out, used)``, ``used`` = bytes from
+    ``offset`` up to and including the one that holds the final block's last bit (zes_inflate_raw_used)."""
+    a = _as_u8(data)
+    cap = max(a.size * 8, 1 << 16)
+    for _ in range(8):
+        out = np.empty(cap, dtype=np.uint8)
+        n, used = C.c_uint64(), C.c_uint64()
+        rc = lib().zes_inflate_raw_used(a.ctypes.data, a.size, offset, out.ctypes.data, cap, C.byref(n), C.byref(used), flags)
+        if rc == ZES_E_NOSPACE and n.value > cap:
+            cap = n.value
+            continue
+        if rc:
+            _raise(rc)
+        return out[: n.value].copy(), used.value
+    _raise(ZES_E_DEVICE)
+
+
+def crc32(data):
+    """CRC-32 of gzip / zlib.crc32 (zes_crc32)."""
+    a = _as_u8(data)
+    out = C.c_uint32()
+    rc = lib().zes_crc32(a.ctypes.data, a.size, C.byref(out))
+    if rc:
+        _raise(rc)
+    return out.value
+
+
+def gzip_bound(n):
+    cap = C.c_uint64()
+    lib().zes_gzip_bound(n, C.byref(cap))
+    return cap.value
+
+
+def gzip(data):
+    """One gzip member: fixed 10-byte header, deflate_raw(data) as the body, CRC-32 and size (zes_gzip)."""
+    a = _as_u8(data)
+    cap = gzip_bound(a.size)
+    out = np.empty(cap, dtype=np.uint8)
+    n = C.c_uint64()
+    rc = lib().zes_gzip(a.ctypes.data, a.size, out.ctypes.data, cap, C.byref(n))
+    if rc:
+        _raise(rc)
+    return out[: n.value].copy()
+
+
+def gunzip(data, flags=0):
+    """gzip.decompress: every member, their outputs concatenated (zes_gunzip_alloc: one decode, an exact-size result)."""
+    a = _as_u8(data)
+    got = []
+
+    def alloc(_user, _index, n):
+        got.append(np.empty(max(int(n), 1), dtype=np.uint8))
+        return got[0].ctypes.data
+
+    n = C.c_uint64()
+    rc = lib().zes_gunzip_alloc(a.ctypes.data, a.size, ALLOC_FN(alloc), None, C.byref(n), flags)
+    if rc:
+        _raise(rc)
+    return got[0][: n.value]
+
+
 def adler32(data):
     a = _as_u8(data)
     out = C.c_uint32()
@@ -374,6 +449,54 @@ def adler32_tensor(t):
     if rc:
         _raise(rc)
     return out.value
+
+
+def crc32_tensor(t):
+    """CRC-32 of a uint8 CUDA tensor at any alignment (zes_crc32_dev)."""
+    import torch
+
+    assert t.is_cuda and t.dtype == torch.uint8 and t.is_contiguous()
+    torch.cuda.current_stream(t.device).synchronize()
+    out = C.c_uint32()
+    rc = lib().zes_crc32_dev(t.data_ptr(), t.numel(), C.byref(out))
+    if rc:
+        _raise(rc)
+    return out.value
+
+
+def gzip_tensor(t, out=None):
+    """gzip of a 1-D uint8 CUDA tensor (zes_gzip_dev); returns a view of ``out`` (allocated if None)."""
+    import torch
+
+    assert t.is_cuda and t.dtype == torch.uint8 and t.is_contiguous()
+    cap = gzip_bound(t.numel())
+    if out is None:
+        out = torch.empty(cap, dtype=torch.uint8, device=t.device)
+    assert out.data_ptr() % 16 == 0, "gzip_tensor: `out` must start on a 16-byte boundary (include/zes.h: device forms)"
+    torch.cuda.current_stream(t.device).synchronize()
+    n = C.c_uint64()
+    rc = lib().zes_gzip_dev(t.data_ptr(), t.numel(), out.data_ptr(), out.numel(), C.byref(n))
+    if rc:
+        _raise(rc)
+    return out[: n.value]
+
+
+def gunzip_tensor(t, out, flags=0):
+    """gunzip of a 1-D uint8 CUDA tensor (any alignment) into ``out`` (zes_gunzip_dev); returns the filled view."""
+    import torch
+
+    assert t.is_cuda and t.dtype == torch.uint8 and t.is_contiguous()
+    assert out.data_ptr() % 16 == 0, "gunzip_tensor: `out` must start on a 16-byte boundary (include/zes.h: device forms)"
+    torch.cuda.current_stream(t.device).synchronize()
+    n = C.c_uint64()
+    rc = lib().zes_gunzip_dev(t.data_ptr(), t.numel(), out.data_ptr(), out.numel(), C.byref(n), flags)
+    if rc == ZES_E_NOSPACE:
+        err = ZlibEsError(rc, "%s (need %d bytes)" % (strerror(rc), n.value))
+        err.need = n.value
+        raise err
+    if rc:
+        _raise(rc)
+    return out[: n.value]
 
 
 def _batch_call(fn, d_in, in_off, in_len, d_out, out_off, out_cap, *extra):

@@ -51,6 +51,10 @@ struct Ctx {
   DevBuf surv, vlong, segfail, symoff, cand, cand_sorted, counters, cres, map, resume, dbg, ibufs, ibufs2, mvlist, scratch, sres, maps, seglist, segprefix, wins, sym16, segorder, segjobs, pw16, gwins, seglive, segouts;
   // staging for the host-pointer API
   DevBuf st_in, st_out;
+  // CRC-32: the kernel's table (x^(8 * 65536 * m) for m < crc_npow) and its two accumulator words; gzip reader: the input
+  // (host forms), the result as it grows (host forms) and one member's output when it cannot go to its place directly
+  DevBuf crctab, crcacc, gz_in, gz_acc, gz_stage;
+  uint32_t crc_npow = 0;
   DevBuf kraft;  // k_inf_scan's table: Kraft contribution of four 3-bit code-length fields at once
   void* pinned = nullptr;  // small pinned area for read-backs
   size_t pinned_cap = 0;
@@ -832,6 +836,9 @@ struct InfJob {
   bool partial = false, final_seen = false;
   uint64_t end_bit = 0;
   int btype0 = -1;  // BTYPE of the block at bit 16, when the block-parallel tier's scan has sent it along (-1: not known)
+  // the caller wants end_bit of the whole stream once it is decoded (zes_inflate_raw_used, the trailer checks): the tiers
+  // that do not have it on the host anyway read it back
+  bool want_end = false;
 };
 
 bool t1_eligible(const InfJob& j, uint32_t flags) { return !(flags & (ZES_F_NO_FASTPATH | ZES_F_PIECES)) && j.c >= 64 && j.c < (1ull << 29); }
@@ -1126,7 +1133,7 @@ int inflate_t1_group(const uint8_t* d_in, uint8_t* d_out, InfJob* jobs, const ui
       if (fast) {
         r.status = 0;
         r.out_len = total;
-        r.aux = 1;
+        r.aux = K + 1;  // (the closing block's candidate, + 1: its end bit is the stream's)
       } else {  // false candidates between the blocks? follow end bit -> next start
         uint32_t j = 0, k = 0;
         total = 0;
@@ -1221,6 +1228,11 @@ int inflate_t1_group(const uint8_t* d_in, uint8_t* d_out, InfJob* jobs, const ui
     std::vector<uint32_t> hmap(K);
     HIPCHK(hipMemcpyAsync(hmap.data(), (const uint32_t*)g.map.p + hb[i].cand_base, (size_t)K * 4, hipMemcpyDeviceToHost, g.stream));
     HIPCHK(hipStreamSynchronize(g.stream));
+    if (j.want_end && K) {
+      ZesCandRes last;
+      HIPCHK(hipMemcpy(&last, (const ZesCandRes*)g.cres.p + hb[i].cand_base + hmap[K - 1], sizeof last, hipMemcpyDeviceToHost));
+      j.end_bit = last.end_bit;
+    }
     std::vector<uint32_t> mv_src, mv_dst, redo;
     for (uint32_t k = 0; k < K; k++) {
       if (hmap[k] == k) continue;
@@ -1285,6 +1297,15 @@ int inflate_t1_group(const uint8_t* d_in, uint8_t* d_out, InfJob* jobs, const ui
     const ZesRes& r = r1[i];
     if (r.status != 0) continue;
     InfJob& j = jobs[ids[i]];
+    if (j.want_end && hres[i].status == 0 && r.aux) {  // (status 2 above has filled it in)
+      if (hostchain) {
+        j.end_bit = ((const ZesCandRes*)g.mirror)[r.aux - 1].end_bit;
+      } else {
+        ZesCandRes last;
+        HIPCHK(hipMemcpy(&last, (const ZesCandRes*)g.cres.p + hb[i].cand_base + r.aux - 1, sizeof last, hipMemcpyDeviceToHost));
+        j.end_bit = last.end_bit;
+      }
+    }
     j.tier = 1;
     j.out_len = r.out_len;
     j.status = r.out_len > j.cap ? ZES_E_NOSPACE : ZES_OK;
@@ -2033,6 +2054,7 @@ int inflate_segments_pieces(const uint8_t* d_in, uint8_t* d_out, InfJob& j) {
       j.tier = 2;
       j.status = (nospace || out_base > j.cap) ? ZES_E_NOSPACE : ZES_OK;
       j.out_len = out_base;
+      j.end_bit = 8 * byte0 + sub[0].end_bit;
       return ZES_OK;
     }
     const uint64_t next_bit = 8 * byte0 + sub[0].end_bit;
@@ -2079,6 +2101,11 @@ int inflate_stored(const uint8_t* d_in, uint8_t* d_out, InfJob& j) {
   j.tier = 2;
   j.out_len = hr.out_len;
   j.status = hr.out_len > j.cap ? ZES_E_NOSPACE : ZES_OK;
+  if (j.want_end && hr.aux) {  // behind the last stored block's last byte
+    ZesStoredBlk last;
+    HIPCHK(hipMemcpy(&last, (const ZesStoredBlk*)g.scratch.p + hr.aux - 1, sizeof last, hipMemcpyDeviceToHost));
+    j.end_bit = 8 * (last.src + last.len);
+  }
   if (j.status == ZES_OK && hr.aux) {
     Timed t("k_inf_stored_copy");
     hipLaunchKernelGGL(k_inf_stored_copy, dim3(hr.aux), dim3(256), 0, g.stream, d_in, j.in_off, d_out, j.out_off, (const ZesStoredBlk*)g.scratch.p);
@@ -2090,7 +2117,7 @@ int inflate_stored(const uint8_t* d_in, uint8_t* d_out, InfJob& j) {
 // T3 then T4 for one buffer the parallel tiers did not settle.
 int inflate_slow(const uint8_t* d_in, uint8_t* d_out, InfJob& j) {
   int rc;
-  if ((rc = ensure(g.res, sizeof(ZesRes)))) return rc;
+  if ((rc = ensure(g.res, 2 * sizeof(ZesRes)))) return rc;  // (k_inf_exact: [1].out_len = where its reader stopped)
   if ((rc = ensure(g.resume, 16))) return rc;
   ZesRes hr;
   bool have_resume = false;
@@ -2128,6 +2155,7 @@ int inflate_slow(const uint8_t* d_in, uint8_t* d_out, InfJob& j) {
       j.tier = 3;
       j.out_len = hr.out_len;
       j.status = hr.out_len > j.cap ? ZES_E_NOSPACE : ZES_OK;
+      if (j.want_end) HIPCHK(hipMemcpy(&j.end_bit, g.resume.p, 8, hipMemcpyDeviceToHost));  // (k_inf_decode puts it there when done)
       return ZES_OK;
     }
     have_resume = true;
@@ -2139,6 +2167,11 @@ int inflate_slow(const uint8_t* d_in, uint8_t* d_out, InfJob& j) {
                        have_resume ? (const uint64_t*)g.resume.p : (const uint64_t*)nullptr, (ZesRes*)g.res.p);
   }
   if ((rc = read_res(&hr))) return rc;
+  if (j.want_end) {
+    ZesRes r2;
+    HIPCHK(hipMemcpy(&r2, (const ZesRes*)g.res.p + 1, sizeof r2, hipMemcpyDeviceToHost));
+    j.end_bit = r2.out_len;
+  }
   j.tier = 4;
   j.out_len = hr.out_len;
   j.status = hr.status;
@@ -2171,6 +2204,7 @@ int inflate_pieces(const uint8_t* d_in, uint8_t* d_out, InfJob& j, uint32_t flag
     if (rr.final_block) {
       j.tier = 1;
       j.out_len = total;
+      j.end_bit = pos_bit;
       j.status = total > j.cap ? ZES_E_NOSPACE : ZES_OK;
       return ZES_OK;
     }
@@ -2336,15 +2370,34 @@ int inflate_jobs(const uint8_t* d_in, uint8_t* d_out, std::vector<InfJob>& jobs,
 
 // One buffer at d_in+in_off (16-byte aligned), result at d_out+out_off (16-byte aligned).
 // Returns the reference-equivalent status; *out_len = bytes produced (or needed on NOSPACE).
+// end_bit (optional): on ZES_OK, the bit behind the stream's final block, relative to d_in + in_off (the raw stream starts at 16)
 int inflate_one(const uint8_t* d_in, uint64_t in_off, uint64_t c, uint8_t* d_out, uint64_t out_off, uint64_t cap,
-                uint64_t* out_len, uint32_t flags, int first_byte /* -1: still on the device */) {
+                uint64_t* out_len, uint32_t flags, int first_byte /* -1: still on the device */, uint64_t* end_bit = nullptr) {
   std::vector<InfJob> jobs(1);
   jobs[0] = InfJob{in_off, c, out_off, cap, 0, ZES_OK, 0};
+  jobs[0].want_end = end_bit != nullptr;
   const uint8_t fb = (uint8_t)first_byte;
-  int rc = inflate_jobs(d_in, d_out, jobs, first_byte < 0 ? nullptr : &fb, flags);
+  int rc = inflate_jobs(d_in, d_out, jobs, first_byte < 0 ? nullptr : &fb, flags & ~ZES_F_CHECK_ADLER);
   if (rc) return rc;
   *out_len = jobs[0].out_len;
+  if (end_bit) *end_bit = jobs[0].end_bit;
   return jobs[0].status;
+}
+
+int adler32_locked(const uint8_t* d_in, uint64_t n, uint32_t* adler_out);
+
+// ZES_F_CHECK_ADLER: the 4 bytes behind the stream (end_bit: relative to the zlib header's first byte) must exist and hold
+// the Adler-32 of the n result bytes at d_res, big-endian.  The stream's bytes are at h_in (host) or d_in (device).
+int check_adler_trailer(const uint8_t* h_in, const uint8_t* d_in, uint64_t c, uint64_t end_bit, const uint8_t* d_res, uint64_t n) {
+  const uint64_t t = (end_bit + 7) / 8;
+  if (end_bit < 16 || t + 4 > c) return ZES_E_CHECKSUM;
+  uint8_t b[4];
+  if (h_in) memcpy(b, h_in + t, 4);
+  else HIPCHK(hipMemcpy(b, d_in + t, 4, hipMemcpyDeviceToHost));
+  uint32_t ad = 0;
+  int rc = adler32_locked(d_res, n, &ad);
+  if (rc) return rc;
+  return ad == ((uint32_t)b[0] << 24 | (uint32_t)b[1] << 16 | (uint32_t)b[2] << 8 | b[3]) ? ZES_OK : ZES_E_CHECKSUM;
 }
 
 }  // namespace
@@ -2366,6 +2419,8 @@ const char* zes_strerror(int status) {
     case ZES_E_DEVICE: return "zes: HIP device error (no gfx950 device or runtime failure)";
     case ZES_E_ARG: return "zes: bad argument";
     case ZES_E_NOTRANGE: return "zes: not a clean chain of reference-made blocks in this range";
+    case ZES_E_GZIP: return "zes: not a valid gzip member (header or trailer)";
+    case ZES_E_CHECKSUM: return "zes: checksum mismatch";
     default: return "zes: unknown status";
   }
 }
@@ -2419,7 +2474,8 @@ int zes_shutdown(void) {
 static void free_scratch_locked() {
   DevBuf* all[] = {&g.bufs, &g.blks, &g.idx_a, &g.idx_b, &g.sdelta, &g.tmask, &g.mlist, &g.hists, &g.codes, &g.hdrs, &g.adler, &g.res, &g.order, &g.surv, &g.vlong, &g.segfail, &g.symoff, &g.cand,
                    &g.cand_sorted, &g.counters, &g.cres, &g.map, &g.resume, &g.dbg, &g.ibufs, &g.ibufs2, &g.mvlist, &g.scratch, &g.st_in, &g.st_out,
-                   &g.sres, &g.maps, &g.seglist, &g.segprefix, &g.wins, &g.sym16, &g.segorder, &g.segjobs, &g.pw16, &g.gwins, &g.seglive, &g.segouts};
+                   &g.sres, &g.maps, &g.seglist, &g.segprefix, &g.wins, &g.sym16, &g.segorder, &g.segjobs, &g.pw16, &g.gwins, &g.seglive, &g.segouts,
+                   &g.crctab, &g.crcacc, &g.gz_in, &g.gz_acc, &g.gz_stage};
   for (DevBuf* b : all) {
     if (b->p) (void)hipFree(b->p);
     b->p = nullptr;
@@ -2681,7 +2737,10 @@ int zes_inflate_dev(const uint8_t* d_in, uint64_t c, uint8_t* d_out, uint64_t ca
   std::lock_guard<std::mutex> lk(g_mu);
   int rc = init_locked(-1);
   if (rc) return rc;
-  return inflate_one(d_in, 0, c, d_out, 0, cap, out_len, flags, -1);
+  if (!(flags & ZES_F_CHECK_ADLER)) return inflate_one(d_in, 0, c, d_out, 0, cap, out_len, flags, -1);
+  uint64_t eb = 0;
+  rc = inflate_one(d_in, 0, c, d_out, 0, cap, out_len, flags, -1, &eb);
+  return rc ? rc : check_adler_trailer(nullptr, d_in, c, eb, d_out, *out_len);
 }
 
 int zes_inflate_batch_dev(const uint8_t* d_in, const uint64_t* in_off, const uint64_t* in_len, uint8_t* d_out,
@@ -2876,7 +2935,7 @@ static int inflate_host(const uint8_t* in, uint64_t c, uint8_t* out, uint64_t ca
   std::lock_guard<std::mutex> lk(g_mu);
   int rc = init_locked(-1);
   if (rc) return rc;
-  if (c >= PIPE_IN_MIN && c < (1ull << 29) && !size_only && (out || alloc) && !(flags & (ZES_F_NO_FASTPATH | ZES_F_PIECES)) &&
+  if (c >= PIPE_IN_MIN && c < (1ull << 29) && !size_only && (out || alloc) && !(flags & (ZES_F_NO_FASTPATH | ZES_F_PIECES | ZES_F_CHECK_ADLER)) &&
       !getenv("ZES_NO_PIPELINE")) {
     bool done = false;
     rc = inflate_host_pipelined(in, c, out, cap, out_len, flags, alloc, user, &done);
@@ -2889,13 +2948,15 @@ static int inflate_host(const uint8_t* in, uint64_t c, uint8_t* out, uint64_t ca
   uint64_t dcap = std::max<uint64_t>((size_only || alloc) ? 0 : cap, std::max<uint64_t>(c * 4, 1 << 20));
   for (int attempt = 0; attempt < 8; attempt++) {
     if ((rc = ensure(g.st_out, dcap + 64))) return rc;
-    uint64_t n = 0;
-    rc = inflate_one((const uint8_t*)g.st_in.p, 0, c, (uint8_t*)g.st_out.p, 0, dcap, &n, flags, c ? in[0] : 0);
+    uint64_t n = 0, eb = 0;
+    rc = inflate_one((const uint8_t*)g.st_in.p, 0, c, (uint8_t*)g.st_out.p, 0, dcap, &n, flags, c ? in[0] : 0,
+                     (flags & ZES_F_CHECK_ADLER) ? &eb : nullptr);
     if (rc == ZES_E_NOSPACE && n > dcap) {
       dcap = n;
       continue;
     }
     if (rc) return rc;
+    if ((flags & ZES_F_CHECK_ADLER) && (rc = check_adler_trailer(in, nullptr, c, eb, (const uint8_t*)g.st_out.p, n))) return rc;
     *out_len = n;
     if (size_only) return ZES_OK;
     if (alloc) {  // the caller allocates the exact result now that its size is known; still under the lock
@@ -3135,7 +3196,8 @@ int zes_inflate_batch_alloc(const uint8_t* const* in, const uint64_t* in_len, ze
   });
 }
 
-static int adler32_locked(const uint8_t* d_in, uint64_t n, uint32_t* adler_out) {
+namespace {
+int adler32_locked(const uint8_t* d_in, uint64_t n, uint32_t* adler_out) {
   int rc;
   if ((rc = ensure(g.adler, 16))) return rc;
   unsigned long long* acc = (unsigned long long*)g.adler.p;
@@ -3154,6 +3216,7 @@ static int adler32_locked(const uint8_t* d_in, uint64_t n, uint32_t* adler_out) 
   *adler_out = (s2 << 16) | s1;
   return ZES_OK;
 }
+}  // namespace
 
 // ---- one buffer over several GPUs: block ranges and their join ----
 int zes_deflate_range_dev(const uint8_t* d_in, uint64_t n, uint64_t n_readable, int final_range, uint8_t* d_out, uint64_t cap,
@@ -3258,27 +3321,47 @@ int zes_adler32_dev(const uint8_t* d_in, uint64_t n, uint32_t* adler_out) {
 // ---- raw DEFLATE (src/deflate.ts:14, src/inflate.ts:16): thin forms over the wrapped pipeline ----
 // The raw stream is decoded as the body of a zlib stream whose two header bytes are supplied here; it is
 // copied device-to-device behind them so that the kernels keep their aligned dword view of the input.
-static int inflate_raw_staged(uint64_t n, uint8_t* d_out, uint64_t cap, uint64_t* out_len, uint32_t flags) {
+// in_used (optional): on ZES_OK, the stream's bytes up to and including the one that holds its last bit
+static int inflate_raw_staged(uint64_t n, uint8_t* d_out, uint64_t cap, uint64_t* out_len, uint32_t flags, uint64_t* in_used = nullptr) {
   HIPCHK(hipMemsetAsync(g.st_in.p, 0x78, 1, g.stream));
   HIPCHK(hipMemsetAsync((uint8_t*)g.st_in.p + 1, 0x9C, 1, g.stream));
-  return inflate_one((const uint8_t*)g.st_in.p, 0, n + 2, d_out, 0, cap, out_len, flags, 0x78);
+  uint64_t eb = 0;
+  const int rc = inflate_one((const uint8_t*)g.st_in.p, 0, n + 2, d_out, 0, cap, out_len, flags & ~ZES_F_CHECK_ADLER, 0x78, in_used ? &eb : nullptr);
+  if (rc == ZES_OK && in_used) *in_used = eb >= 16 ? std::min<uint64_t>((eb - 16 + 7) / 8, n) : 0;
+  return rc;
 }
 
-int zes_inflate_raw_dev(const uint8_t* d_in, uint64_t c, uint64_t offset, uint8_t* d_out, uint64_t cap, uint64_t* out_len,
-                        uint32_t flags) {
+static int inflate_raw_dev_locked(const uint8_t* d_in, uint64_t c, uint64_t offset, uint8_t* d_out, uint64_t cap, uint64_t* out_len,
+                                  uint64_t* in_used, uint32_t flags) {
+  int rc;
+  const uint64_t n = offset < c ? c - offset : 0;
+  if ((rc = ensure(g.st_in, n + 2 + 64))) return rc;
+  if (n) HIPCHK(hipMemcpyAsync((uint8_t*)g.st_in.p + 2, d_in + offset, n, hipMemcpyDeviceToDevice, g.stream));
+  return inflate_raw_staged(n, d_out, cap, out_len, flags, in_used);
+}
+
+int zes_inflate_raw_used_dev(const uint8_t* d_in, uint64_t c, uint64_t offset, uint8_t* d_out, uint64_t cap, uint64_t* out_len,
+                             uint64_t* in_used, uint32_t flags) {
   ROUTE_DEV(d_in, d_out);
   if (!out_len || (!d_in && c)) return ZES_E_ARG;
   if ((((uintptr_t)d_out) & 15u)) return ZES_E_ARG;
   std::lock_guard<std::mutex> lk(g_mu);
   int rc = init_locked(-1);
   if (rc) return rc;
-  const uint64_t n = offset < c ? c - offset : 0;
-  if ((rc = ensure(g.st_in, n + 2 + 64))) return rc;
-  if (n) HIPCHK(hipMemcpyAsync((uint8_t*)g.st_in.p + 2, d_in + offset, n, hipMemcpyDeviceToDevice, g.stream));
-  return inflate_raw_staged(n, d_out, cap, out_len, flags);
+  return inflate_raw_dev_locked(d_in, c, offset, d_out, cap, out_len, in_used, flags);
+}
+
+int zes_inflate_raw_dev(const uint8_t* d_in, uint64_t c, uint64_t offset, uint8_t* d_out, uint64_t cap, uint64_t* out_len,
+                        uint32_t flags) {
+  return zes_inflate_raw_used_dev(d_in, c, offset, d_out, cap, out_len, nullptr, flags);
 }
 
 int zes_inflate_raw(const uint8_t* in, uint64_t c, uint64_t offset, uint8_t* out, uint64_t cap, uint64_t* out_len, uint32_t flags) {
+  return zes_inflate_raw_used(in, c, offset, out, cap, out_len, nullptr, flags);
+}
+
+int zes_inflate_raw_used(const uint8_t* in, uint64_t c, uint64_t offset, uint8_t* out, uint64_t cap, uint64_t* out_len, uint64_t* in_used,
+                         uint32_t flags) {
   UseDev ud(route_host());
   if (!out_len || (!in && c)) return ZES_E_ARG;
   *out_len = 0;
@@ -3293,7 +3376,7 @@ int zes_inflate_raw(const uint8_t* in, uint64_t c, uint64_t offset, uint8_t* out
   for (int attempt = 0; attempt < 8; attempt++) {
     if ((rc = ensure(g.st_out, dcap + 64))) return rc;
     uint64_t m = 0;
-    rc = inflate_raw_staged(n, (uint8_t*)g.st_out.p, dcap, &m, flags);
+    rc = inflate_raw_staged(n, (uint8_t*)g.st_out.p, dcap, &m, flags, in_used);
     if (rc == ZES_E_NOSPACE && m > dcap) {
       dcap = m;
       continue;
@@ -3362,6 +3445,358 @@ int zes_adler32(const uint8_t* in, uint64_t n, uint32_t* adler_out) {
   if ((rc = ensure(g.st_in, n + 64))) return rc;
   if ((rc = upload((uint8_t*)g.st_in.p, in, n))) return rc;
   return adler32_locked((const uint8_t*)g.st_in.p, n, adler_out);
+}
+
+// ---- CRC-32 (zes_crc.hip) ----
+static uint32_t* crc_pin() { return (uint32_t*)((uint8_t*)g.pinned + 240 * 1024); }  // (read-back area, clear of the others)
+
+// the kernel's table, holding the chunk powers an n-byte input needs
+static int crc_ready(uint64_t n) {
+  const uint64_t nch = (n + CRC_CHUNK - 1) / CRC_CHUNK;
+  if (nch >= (1ull << 31)) return ZES_E_ARG;
+  const uint32_t need = (uint32_t)std::max<uint64_t>(nch, 2) - 1;
+  if (g.crctab.p && g.crc_npow >= need) return ZES_OK;
+  uint32_t npow = std::max<uint32_t>(1024, g.crctab.p ? g.crc_npow : 0);
+  while (npow < need) npow *= 2;
+  std::vector<uint32_t> tab(CRC_TAB_POW + npow);
+  zes_crc_tables(tab.data(), npow);
+  HIPCHK(hipStreamSynchronize(g.stream));  // (a launch may still read the table being replaced)
+  HIPCHK(hipStreamSynchronize(g.s_adler));
+  int rc;
+  if ((rc = ensure(g.crctab, tab.size() * 4))) return rc;
+  HIPCHK(hipMemcpy(g.crctab.p, tab.data(), tab.size() * 4, hipMemcpyHostToDevice));
+  g.crc_npow = npow;
+  return ZES_OK;
+}
+
+// k_crc32 over d[0, n) on `st`, the two accumulator words on their way to crc_pin(); crc_finish() once st is synchronised
+static int crc_enqueue(const uint8_t* d, uint64_t n, hipStream_t st) {
+  int rc;
+  if ((rc = crc_ready(n))) return rc;
+  if ((rc = ensure(g.crcacc, 16))) return rc;
+  HIPCHK(hipMemsetAsync(g.crcacc.p, 0, 8, st));
+  if (n) {
+    Timed t("k_crc32", st);
+    hipLaunchKernelGGL(k_crc32, dim3((uint32_t)((n + CRC_CHUNK - 1) / CRC_CHUNK)), dim3(CRC_THREADS), 0, st, d, n, (const uint32_t*)g.crctab.p,
+                       (unsigned int*)g.crcacc.p);
+  }
+  HIPCHK(hipMemcpyAsync(crc_pin(), g.crcacc.p, 8, hipMemcpyDeviceToHost, st));
+  return ZES_OK;
+}
+
+// word 0 holds the chunks before the last one, shifted to the last chunk's start; word 1 the last chunk
+static uint32_t crc_finish(uint64_t n) {
+  const uint32_t* a = crc_pin();
+  const uint64_t last = n ? n - ((n - 1) / CRC_CHUNK) * CRC_CHUNK : 0;
+  const uint32_t raw = zes_crc_shift(a[0], last) ^ a[1];
+  return raw ^ zes_crc_shift(0xFFFFFFFFu, n) ^ 0xFFFFFFFFu;
+}
+
+static int crc32_locked(const uint8_t* d, uint64_t n, uint32_t* crc) {
+  int rc;
+  if ((rc = crc_enqueue(d, n, g.stream))) return rc;
+  HIPCHK(hipStreamSynchronize(g.stream));
+  *crc = crc_finish(n);
+  return ZES_OK;
+}
+
+int zes_crc32_dev(const uint8_t* d_in, uint64_t n, uint32_t* crc) {
+  ROUTE_DEV(d_in);
+  if (!crc || (!d_in && n)) return ZES_E_ARG;
+  std::lock_guard<std::mutex> lk(g_mu);
+  int rc = init_locked(-1);
+  if (rc) return rc;
+  rc = crc32_locked(d_in, n, crc);
+  collect_times();
+  return rc;
+}
+
+int zes_crc32(const uint8_t* in, uint64_t n, uint32_t* crc) {
+  UseDev ud(route_host());
+  if (!crc || (!in && n)) return ZES_E_ARG;
+  std::lock_guard<std::mutex> lk(g_mu);
+  int rc = init_locked(-1);
+  if (rc) return rc;
+  if ((rc = ensure(g.st_in, n + 64))) return rc;
+  if ((rc = upload((uint8_t*)g.st_in.p, in, n))) return rc;
+  rc = crc32_locked((const uint8_t*)g.st_in.p, n, crc);
+  collect_times();
+  return rc;
+}
+
+// ---- gzip writer (RFC 1952): fixed header | zes_deflate_raw's bytes | CRC-32, ISIZE ----
+static const uint8_t kGzHeader[10] = {0x1f, 0x8b, 8, 0, 0, 0, 0, 0, 0, 0xff};  // FLG 0, MTIME 0, XFL 0, OS 255
+static uint64_t gzip_bound(uint64_t n) { return deflate_bound(n) - 6 + 18; }
+static void put_le32(uint8_t* p, uint32_t v) {
+  for (int k = 0; k < 4; k++) p[k] = (uint8_t)(v >> (8 * k));
+}
+static uint32_t get_le32(const uint8_t* p) { return (uint32_t)p[0] | (uint32_t)p[1] << 8 | (uint32_t)p[2] << 16 | (uint32_t)p[3] << 24; }
+
+// the body into g.st_out + 2 (as zes_deflate_raw does); the input's CRC-32 runs on the second stream beside the deflate
+// kernels, as the Adler-32 pass does
+static int gzip_core(const uint8_t* d_in, uint64_t n, uint64_t* raw_len, uint32_t* crc) {
+  int rc;
+  HIPCHK(hipEventRecord(g.ev_a0, g.stream));  // (behind the upload of a host call)
+  HIPCHK(hipStreamWaitEvent(g.s_adler, g.ev_a0, 0));
+  if ((rc = crc_enqueue(d_in, n, g.s_adler))) return rc;
+  rc = deflate_raw_common(d_in, n, raw_len);
+  HIPCHK(hipStreamSynchronize(g.s_adler));
+  if (rc) return rc;
+  *crc = crc_finish(n);
+  return ZES_OK;
+}
+
+int zes_gzip_bound(uint64_t n, uint64_t* cap) {
+  if (!cap) return ZES_E_ARG;
+  *cap = gzip_bound(n);
+  return ZES_OK;
+}
+
+int zes_gzip_dev(const uint8_t* d_in, uint64_t n, uint8_t* d_out, uint64_t cap, uint64_t* out_len) {
+  ROUTE_DEV(d_in, d_out);
+  if (!out_len || !d_out || (!d_in && n)) return ZES_E_ARG;
+  *out_len = 0;
+  if (deflate_throws(n)) return ZES_E_CORRUPT;
+  if (((uintptr_t)d_out) & 15u) return ZES_E_ARG;
+  std::lock_guard<std::mutex> lk(g_mu);
+  int rc = init_locked(-1);
+  if (rc) return rc;
+  uint64_t rl = 0;
+  uint32_t crc = 0;
+  if ((rc = gzip_core(d_in, n, &rl, &crc))) return rc;
+  *out_len = rl + 18;
+  if (rl + 18 > cap) return ZES_E_NOSPACE;
+  uint8_t* hp = (uint8_t*)g.pinned + 248 * 1024;
+  memcpy(hp, kGzHeader, 10);
+  put_le32(hp + 16, crc);
+  put_le32(hp + 20, (uint32_t)n);
+  HIPCHK(hipMemcpyAsync(d_out + 10, (const uint8_t*)g.st_out.p + 2, rl, hipMemcpyDeviceToDevice, g.stream));
+  HIPCHK(hipMemcpyAsync(d_out, hp, 10, hipMemcpyHostToDevice, g.stream));
+  HIPCHK(hipMemcpyAsync(d_out + 10 + rl, hp + 16, 8, hipMemcpyHostToDevice, g.stream));
+  HIPCHK(hipStreamSynchronize(g.stream));
+  return ZES_OK;
+}
+
+int zes_gzip(const uint8_t* in, uint64_t n, uint8_t* out, uint64_t cap, uint64_t* out_len) {
+  UseDev ud(route_host());
+  if (!out_len || (!in && n) || !out) return ZES_E_ARG;
+  *out_len = 0;
+  if (deflate_throws(n)) return ZES_E_CORRUPT;
+  std::lock_guard<std::mutex> lk(g_mu);
+  int rc = init_locked(-1);
+  if (rc) return rc;
+  if ((rc = ensure(g.st_in, n + 64))) return rc;
+  if ((rc = upload((uint8_t*)g.st_in.p, in, n))) return rc;
+  uint64_t rl = 0;
+  uint32_t crc = 0;
+  if ((rc = gzip_core((const uint8_t*)g.st_in.p, n, &rl, &crc))) return rc;
+  *out_len = rl + 18;
+  if (rl + 18 > cap) return ZES_E_NOSPACE;
+  memcpy(out, kGzHeader, 10);
+  if ((rc = download(out + 10, (const uint8_t*)g.st_out.p + 2, rl))) return rc;
+  put_le32(out + 10 + rl, crc);
+  put_le32(out + 14 + rl, (uint32_t)n);
+  return ZES_OK;
+}
+
+// ---- gzip reader (RFC 1952; CPython's gzip.decompress) ----
+// One member's header in h[0, avail) (left = input bytes from its start): ZES_OK and *hlen, ZES_E_GZIP / ZES_E_CHECKSUM,
+// or 1: the header goes on behind `avail` (bring more bytes)
+static int gz_header(const uint8_t* h, uint64_t avail, uint64_t left, uint64_t* hlen) {
+  auto need = [&](uint64_t k) { return k <= avail ? 0 : (avail < left ? 1 : (int)ZES_E_GZIP); };
+  int r;
+  if ((r = need(10))) return r;
+  if (h[0] != 0x1f || h[1] != 0x8b || h[2] != 8 || (h[3] & 0xE0u)) return ZES_E_GZIP;  // (reserved FLG bits: rejected, as zlib does)
+  const uint8_t flg = h[3];
+  uint64_t p = 10;
+  if (flg & 4u) {  // FEXTRA
+    if ((r = need(p + 2))) return r;
+    p += 2 + ((uint64_t)h[p] | (uint64_t)h[p + 1] << 8);
+    if ((r = need(p))) return r;
+  }
+  for (uint32_t f = 8; f <= 16; f <<= 1)  // FNAME, FCOMMENT: zero-terminated
+    if (flg & f)
+      for (;;) {
+        if ((r = need(p + 1))) return r;
+        if (h[p++] == 0) break;
+      }
+  if (flg & 2u) {  // FHCRC: the low 16 bits of the header's CRC-32
+    if ((r = need(p + 2))) return r;
+    if ((zes_crc_host(h, p) & 0xFFFFu) != ((uint32_t)h[p] | (uint32_t)h[p + 1] << 8)) return ZES_E_CHECKSUM;
+    p += 2;
+  }
+  *hlen = p;
+  return ZES_OK;
+}
+
+// the input as the host sees it: the caller's memory (host forms), or pieces copied down from the device
+struct GzSrc {
+  const uint8_t* h;
+  const uint8_t* d;  // the input on the device
+  uint64_t c;
+  std::vector<uint8_t> win;
+  uint64_t win_pos = 0;
+  int get(uint64_t pos, uint64_t k, const uint8_t** out) {  // bytes [pos, pos + k), k <= c - pos
+    if (h) {
+      *out = h + pos;
+      return ZES_OK;
+    }
+    if (pos < win_pos || pos + k > win_pos + win.size()) {
+      const uint64_t len = std::min<uint64_t>(c - pos, std::max<uint64_t>(k, 4096));
+      win.resize(len);
+      if (len) HIPCHK(hipMemcpy(win.data(), d + pos, len, hipMemcpyDeviceToHost));
+      win_pos = pos;
+    }
+    *out = win.data() + (pos - win_pos);
+    return ZES_OK;
+  }
+  int header(uint64_t pos, uint64_t* hlen) {
+    for (uint64_t k = std::min<uint64_t>(c - pos, 4096);; k = std::min<uint64_t>(c - pos, k * 4)) {
+      const uint8_t* p = nullptr;
+      int rc = get(pos, k, &p);
+      if (rc) return rc;
+      rc = gz_header(p, k, c - pos, hlen);
+      if (rc != 1) return rc;
+    }
+  }
+};
+
+// grows b to hold `bytes`, keeping its first `keep` bytes
+static int grow_keep(DevBuf& b, size_t bytes, size_t keep) {
+  if (bytes <= b.cap) return ZES_OK;
+  void* p = nullptr;
+  const size_t want = bytes + bytes / 8 + 4096;
+  HIPCHK(hipMalloc(&p, want));
+  if (keep) HIPCHK(hipMemcpyAsync(p, b.p, keep, hipMemcpyDeviceToDevice, g.stream));
+  HIPCHK(hipStreamSynchronize(g.stream));
+  if (b.p) HIPCHK(hipFree(b.p));
+  b.p = p;
+  b.cap = want;
+  return ZES_OK;
+}
+
+// Members one after the other, the first one's header already read (hlen).  dev: the result goes to d_dst (capacity cap;
+// NOSPACE once it does not fit, the members behind are still measured); else it collects in g.gz_acc.  A member is
+// decoded straight to its place when that is 16-byte aligned and has room, else into g.gz_stage and copied.
+static int gunzip_locked(GzSrc& S, uint64_t hlen, bool dev, uint8_t* d_dst, uint64_t cap, uint64_t* out_len, uint32_t flags) {
+  int rc;
+  uint64_t pos = 0, total = 0;
+  flags &= ~ZES_F_CHECK_ADLER;
+  for (bool first = true;; first = false) {
+    if (!first && (rc = S.header(pos, &hlen))) return rc;
+    const uint64_t body = pos + hlen;
+    uint8_t* base = dev ? d_dst : (uint8_t*)g.gz_acc.p;
+    const uint64_t room = dev ? (cap > total ? cap - total : 0) : (g.gz_acc.cap > total + 64 ? g.gz_acc.cap - total - 64 : 0);
+    bool direct = base && room && (((uintptr_t)(base + total)) & 15u) == 0;
+    uint64_t m = 0, used = 0;
+    if (direct) {
+      rc = inflate_raw_dev_locked(S.d, S.c, body, base + total, room, &m, &used, flags);
+      if (rc == ZES_E_NOSPACE) direct = false;
+      else if (rc) return rc;
+    }
+    const uint8_t* res = base + total;
+    if (!direct) {
+      uint64_t scap = std::max<uint64_t>(m, std::max<uint64_t>((S.c - body) * 4, 1 << 20));
+      for (int attempt = 0;; attempt++) {
+        if ((rc = ensure(g.gz_stage, scap + 64))) return rc;
+        rc = inflate_raw_dev_locked(S.d, S.c, body, (uint8_t*)g.gz_stage.p, scap, &m, &used, flags);
+        if (rc == ZES_E_NOSPACE && m > scap && attempt < 8) {
+          scap = m;
+          continue;
+        }
+        if (rc) return rc;
+        break;
+      }
+      res = (const uint8_t*)g.gz_stage.p;
+    }
+    const uint64_t tpos = body + used;  // the trailer: CRC-32 and ISIZE of this member's output
+    if (tpos + 8 > S.c) return ZES_E_GZIP;
+    const uint8_t* tp = nullptr;
+    if ((rc = S.get(tpos, 8, &tp))) return rc;
+    const uint32_t want_crc = get_le32(tp), want_size = get_le32(tp + 4);
+    uint32_t crc = 0;
+    if ((rc = crc32_locked(res, m, &crc))) return rc;
+    if (crc != want_crc || (uint32_t)m != want_size) return ZES_E_CHECKSUM;
+    if (!direct && m) {
+      if (dev) {
+        if (total + m <= cap) HIPCHK(hipMemcpyAsync(d_dst + total, res, m, hipMemcpyDeviceToDevice, g.stream));
+      } else {
+        if ((rc = grow_keep(g.gz_acc, total + m + 64, total))) return rc;
+        HIPCHK(hipMemcpyAsync((uint8_t*)g.gz_acc.p + total, res, m, hipMemcpyDeviceToDevice, g.stream));
+      }
+      HIPCHK(hipStreamSynchronize(g.stream));  // (the staging buffer is the next member's)
+    }
+    total += m;
+    pos = tpos + 8;
+    while (pos < S.c) {  // zero bytes between and after members
+      const uint64_t k = std::min<uint64_t>(S.c - pos, 4096);
+      const uint8_t* p = nullptr;
+      if ((rc = S.get(pos, k, &p))) return rc;
+      uint64_t i = 0;
+      while (i < k && p[i] == 0) i++;
+      pos += i;
+      if (i < k) break;
+    }
+    if (pos >= S.c) break;
+  }
+  *out_len = total;
+  return (dev && total > cap) ? ZES_E_NOSPACE : ZES_OK;
+}
+
+int zes_gunzip_dev(const uint8_t* d_in, uint64_t c, uint8_t* d_out, uint64_t cap, uint64_t* out_len, uint32_t flags) {
+  ROUTE_DEV(d_in, d_out);
+  if (!out_len || (!d_in && c)) return ZES_E_ARG;
+  *out_len = 0;
+  if (((uintptr_t)d_out) & 15u) return ZES_E_ARG;
+  if (c == 0) return ZES_E_GZIP;
+  std::lock_guard<std::mutex> lk(g_mu);
+  int rc = init_locked(-1);
+  if (rc) return rc;
+  GzSrc S{nullptr, d_in, c};
+  uint64_t hlen = 0;
+  if ((rc = S.header(0, &hlen))) return rc;
+  rc = gunzip_locked(S, hlen, true, d_out, cap, out_len, flags);
+  collect_times();
+  return rc;
+}
+
+static int gunzip_host(const uint8_t* in, uint64_t c, uint8_t* out, uint64_t cap, uint64_t* out_len, uint32_t flags, zes_alloc_fn alloc,
+                       void* user) {
+  if (!out_len || (!in && c)) return ZES_E_ARG;
+  *out_len = 0;
+  if (c == 0) return ZES_E_GZIP;
+  uint64_t hlen = 0;
+  int rc = gz_header(in, c, c, &hlen);  // (decided before the device is touched)
+  if (rc) return rc;
+  std::lock_guard<std::mutex> lk(g_mu);
+  if ((rc = init_locked(-1))) return rc;
+  if ((rc = ensure(g.gz_in, c + 64))) return rc;
+  if ((rc = upload((uint8_t*)g.gz_in.p, in, c))) return rc;
+  if (g.gz_acc.cap < std::max<uint64_t>(c * 4, 1 << 20) && (rc = ensure(g.gz_acc, std::max<uint64_t>(c * 4, 1 << 20) + 64))) return rc;
+  GzSrc S{in, (const uint8_t*)g.gz_in.p, c};
+  uint64_t n = 0;
+  rc = gunzip_locked(S, hlen, false, nullptr, 0, &n, flags);
+  collect_times();
+  if (rc) return rc;
+  *out_len = n;
+  if (alloc) {
+    out = alloc(user, 0, n);
+    if (!out) return ZES_E_ARG;
+    cap = n;
+  }
+  if (n > cap) return ZES_E_NOSPACE;
+  return download(out, (const uint8_t*)g.gz_acc.p, n);
+}
+
+int zes_gunzip(const uint8_t* in, uint64_t c, uint8_t* out, uint64_t cap, uint64_t* out_len, uint32_t flags) {
+  UseDev ud(route_host());
+  return gunzip_host(in, c, out, cap, out_len, flags, nullptr, nullptr);
+}
+
+int zes_gunzip_alloc(const uint8_t* in, uint64_t c, zes_alloc_fn alloc, void* user, uint64_t* out_len, uint32_t flags) {
+  UseDev ud(route_host());
+  if (!alloc) return ZES_E_ARG;
+  return gunzip_host(in, c, nullptr, 0, out_len, flags, alloc, user);
 }
 
 int zes_stage_lz77_dev(const uint8_t* d_in, uint64_t n, uint64_t start, uint32_t len, uint32_t* h_tokens, uint32_t* ntokens) {

@@ -1535,6 +1535,7 @@ __global__ __launch_bounds__(64) void k_inf_decode(const uint8_t* __restrict__ d
       res->out_len = d.o;
       res->status = 0;
       res->aux = 3;  // tier
+      resume[0] = wd_pos(d);  // (done: the bit behind the final block, for callers that need where the stream ends)
     }
   } else {
     // hand the failing block to the exact decoder: everything before it is valid output
@@ -2538,7 +2539,7 @@ __global__ __launch_bounds__(64) void k_inf_seg_decode(const uint8_t* __restrict
 // k_inf_chain: validates the parallel decode.  Success needs: candidate 0 at bit 16, every
 // block ok, every non-final block exactly 131072 bytes, end bit of block k == start of k+1,
 // and the k-th chain member being the k-th candidate (otherwise a remap pass is requested).
-// res->status: 0 done, 2 remap needed (chain in map_out, length in res->aux), 1 give up (T2).
+// res->status: 0 done (res->aux = the closing candidate + 1), 2 remap needed (chain in map_out, length in res->aux), 1 give up (T2).
 // ------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void k_inf_chain(const ZesInfBuf* __restrict__ bufs, const uint32_t* __restrict__ cnt,
                                                    const uint32_t* __restrict__ cand_all, const ZesCandRes* __restrict__ cres_all,
@@ -2604,7 +2605,7 @@ __global__ __launch_bounds__(256) void k_inf_chain(const ZesInfBuf* __restrict__
       if (tid == 0) {
         res->status = 0;
         res->out_len = s_total;
-        res->aux = 1;
+        res->aux = K + 1;  // the closing block's candidate + 1 (its end bit is where the stream ends)
       }
       return;
     }
@@ -2970,6 +2971,7 @@ __global__ void k_inf_exact(const uint8_t* __restrict__ d_in, uint64_t in_off, u
     }
   }
   res->aux = 3;
+  res[1].out_len = (uint64_t)(r.idx + 1) * 8 - (uint64_t)r.now_len;  // the bit behind the last one read (the reader refills eagerly)
   if (rc) {
     res->status = rc;
     res->out_len = 0;

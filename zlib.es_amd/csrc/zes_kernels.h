@@ -18,6 +18,15 @@
 #define HUFF_THREADS_HOST 256
 #define ADLER_THREADS 256
 #define ADLER_CHUNK 65536u
+// k_crc32 (zes_crc.hip): a workgroup per 64 KiB chunk, 16 pieces of 16 bytes per thread, 4096 bytes apart; the table
+// the host builds (zes_crc_tables): piece tables | fold tables | per-thread shifts | x^(8 * 65536 * m) for m = 0, 1, ...
+#define CRC_THREADS 256u
+#define CRC_PIECES 16u
+#define CRC_CHUNK (CRC_THREADS * CRC_PIECES * 16u)
+#define CRC_STRIDE (CRC_THREADS * 16u)
+#define CRC_TAB_FOLD 512u
+#define CRC_TAB_LANE 640u
+#define CRC_TAB_POW (CRC_TAB_LANE + CRC_THREADS)
 #define ZES_PAR_DBG_ROW 32  // u64 slots per work item of k_inf_block_par's ZES_DEBUG_PHASES stamps
 // k_lz_match_lazy -> k_lz_parse, per block: [0] = 1 when the mask is there, [4..] a bit per position of the greedy chain
 #define ZES_TMASK_WORDS (131072 / 32 + 4)
@@ -107,6 +116,11 @@ struct ZesSegOut {
   uint32_t hist;  // bytes of output in front of out_off that exist (a later piece of a long stream: up to 32768)
 };
 
+// CRC-32 host arithmetic (zes_crc.hip): shift(s, k) = s * x^(8k) mod P; the kernel's table with npow powers
+uint32_t zes_crc_shift(uint32_t s, uint64_t k);
+uint32_t zes_crc_host(const uint8_t* p, uint64_t n);  // CRC-32 of a few bytes on the host (gzip header check)
+void zes_crc_tables(uint32_t* tab, uint32_t npow);
+
 #ifdef __HIPCC__
 // inflate direction (zes_inflate.hip)
 __global__ void k_inf_first_bytes(const uint8_t*, const uint64_t*, uint8_t*, uint32_t);
@@ -172,6 +186,7 @@ __global__ void k_huff(ZesBlk*, const uint32_t*, uint32_t*, uint32_t*);
 __global__ void k_huff_lengths_only(const uint32_t*, uint32_t, uint32_t, uint8_t*);
 __global__ void k_selftest_lds_order(unsigned long long*, uint32_t, uint32_t);
 __global__ void k_adler(const uint8_t*, uint64_t, uint64_t, unsigned long long*);
+__global__ void k_crc32(const uint8_t*, uint64_t, const uint32_t*, unsigned int*);
 __global__ void k_adler_blocks(const uint8_t*, const ZesBuf*, const ZesBlk*, unsigned long long*);
 __global__ void k_layout(uint8_t*, const ZesBuf*, ZesBlk*, const unsigned long long*, ZesRes*);
 __global__ void k_emit(uint8_t*, const ZesBuf*, const ZesBlk*, const uint32_t*, const uint32_t*, const uint32_t*);

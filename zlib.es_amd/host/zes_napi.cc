@@ -539,6 +539,62 @@ napi_value InflateRaw(napi_env env, napi_callback_info info) {
   return throw_status(env, ZES_E_DEVICE);
 }
 
+// gzip(input): one gzip member (RFC 1952) whose body is the reference's raw stream (include/zes.h: zes_gzip)
+napi_value Gzip(napi_env env, napi_callback_info info) {
+  size_t argc = 1;
+  napi_value argv[1];
+  napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr);
+  const uint8_t* in = nullptr;
+  size_t n = 0;
+  if (argc < 1 || !get_bytes(env, argv[0], &in, &n)) {
+    napi_throw_type_error(env, nullptr, "gzip(input): input must be a Uint8Array");
+    return nullptr;
+  }
+  uint64_t cap = 0, out_len = 0;
+  zes_gzip_bound(n, &cap);
+  ResultMem tmp = result_alloc(cap);
+  if (!tmp.p) return throw_status(env, ZES_E_ARG);
+  const int rc = zes_gzip(in, n, tmp.p, cap, &out_len);
+  if (rc) {
+    result_free(tmp);
+    return throw_status(env, rc);
+  }
+  return take_u8(env, tmp, out_len);
+}
+
+// gunzip(input): every member of a gzip file, their outputs concatenated; one decode, then the exact-size result
+struct GunzipAlloc {
+  ResultMem m;
+  bool failed = false;
+};
+uint8_t* gunzip_alloc(void* user, uint32_t, uint64_t n) {
+  GunzipAlloc* a = static_cast<GunzipAlloc*>(user);
+  result_free(a->m);
+  a->m = result_alloc((size_t)n, false);  // (inside the library's call: a pooled block or malloc, never zes_host_alloc)
+  if (!a->m.p) a->failed = true;
+  return a->m.p;
+}
+
+napi_value Gunzip(napi_env env, napi_callback_info info) {
+  size_t argc = 1;
+  napi_value argv[1];
+  napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr);
+  const uint8_t* in = nullptr;
+  size_t c = 0;
+  if (argc < 1 || !get_bytes(env, argv[0], &in, &c)) {
+    napi_throw_type_error(env, nullptr, "gunzip(input): input must be a Uint8Array");
+    return nullptr;
+  }
+  GunzipAlloc ga;
+  uint64_t out_len = 0;
+  const int rc = zes_gunzip_alloc(in, c, gunzip_alloc, &ga, &out_len, ZES_F_DEFAULT);
+  if (rc) {
+    result_free(ga.m);
+    return throw_status(env, ga.failed ? ZES_E_ARG : rc);
+  }
+  return take_u8(env, ga.m, out_len);
+}
+
 napi_value Adler32(napi_env env, napi_callback_info info) {
   size_t argc = 1;
   napi_value argv[1];
@@ -911,6 +967,8 @@ napi_value ModuleInit(napi_env env, napi_value exports) {
       {"inflateBatchAsync", nullptr, swept<InflateBatchAsync>, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"allocPinned", nullptr, swept<AllocPinned>, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"adler32", nullptr, swept<Adler32>, nullptr, nullptr, nullptr, napi_default, nullptr},
+      {"gzip", nullptr, swept<Gzip>, nullptr, nullptr, nullptr, napi_default, nullptr},
+      {"gunzip", nullptr, swept<Gunzip>, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"init", nullptr, swept<Init>, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"initDevices", nullptr, swept<InitDevices>, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"trim", nullptr, swept<Trim>, nullptr, nullptr, nullptr, napi_default, nullptr},

@@ -1,4 +1,4 @@
-/** Same declarations as the reference's dist/tsc/zlib.d.ts:4-5, plus the raw, Promise and batch forms and four extras. */
+/** Same declarations as the reference's dist/tsc/zlib.d.ts:4-5, plus the raw, Promise and batch forms and the extras. */
 export declare function inflate(input: Uint8Array): Uint8Array;
 export declare function deflate(input: Uint8Array): Uint8Array;
 export declare function deflateRaw(input: Uint8Array): Uint8Array;
@@ -12,6 +12,8 @@ export declare function deflateBatchAsync(inputs: Uint8Array[]): Promise<BatchRe
 export declare function inflateBatchAsync(inputs: Uint8Array[]): Promise<BatchResult[]>;
 export declare function allocPinned(n: number): Uint8Array;
 export declare function adler32(input: Uint8Array): number;
+export declare function gzip(input: Uint8Array): Uint8Array;
+export declare function gunzip(input: Uint8Array): Uint8Array;
 export declare function init(device: number): void;
 export declare function initDevices(n?: number): number;
 export declare function trim(): void;

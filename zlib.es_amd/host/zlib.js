@@ -78,6 +78,19 @@ function allocPinned(n) {
   return addon.allocPinned(n);
 }
 
+/**
+ * Extra (not in the reference API): gzip files (RFC 1952).  `gzip` writes one member with a fixed 10-byte header
+ * (no name, MTIME 0) around deflateRaw(input); `gunzip` reads every member of a gzip file (CPython's
+ * gzip.decompress) and checks every CRC-32 and size.  Errors are thrown with the library's messages.
+ */
+function gzip(input) {
+  return addon.gzip(input);
+}
+
+function gunzip(input) {
+  return addon.gunzip(input);
+}
+
 /** Extra (not in the reference API): Adler-32 of a buffer, computed on the GPU. */
 function adler32(input) {
   return addon.adler32(input);
@@ -114,6 +127,8 @@ exports.inflateBatch = inflateBatch;
 exports.deflateBatchAsync = deflateBatchAsync;
 exports.inflateBatchAsync = inflateBatchAsync;
 exports.allocPinned = allocPinned;
+exports.gzip = gzip;
+exports.gunzip = gunzip;
 exports.adler32 = adler32;
 exports.init = init;
 exports.initDevices = initDevices;

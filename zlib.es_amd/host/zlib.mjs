@@ -14,6 +14,8 @@ export const deflateBatchAsync = z.deflateBatchAsync;
 export const inflateBatchAsync = z.inflateBatchAsync;
 export const allocPinned = z.allocPinned;
 export const adler32 = z.adler32;
+export const gzip = z.gzip;
+export const gunzip = z.gunzip;
 export const init = z.init;
 export const initDevices = z.initDevices;
 export const trim = z.trim;

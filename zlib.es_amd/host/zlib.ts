@@ -77,6 +77,19 @@ export function allocPinned(n: number): Uint8Array {
   return addon.allocPinned(n);
 }
 
+/**
+ * Extra (not in the reference API): gzip files (RFC 1952).  `gzip` writes one member with a fixed 10-byte header
+ * (no name, MTIME 0) around deflateRaw(input); `gunzip` reads every member of a gzip file (CPython's
+ * gzip.decompress) and checks every CRC-32 and size.  Errors are thrown with the library's messages.
+ */
+export function gzip(input: Uint8Array): Uint8Array {
+  return addon.gzip(input);
+}
+
+export function gunzip(input: Uint8Array): Uint8Array {
+  return addon.gunzip(input);
+}
+
 /** Extra (not in the reference API): Adler-32 of a buffer, computed on the GPU. */
 export function adler32(input: Uint8Array): number {
   return addon.adler32(input);
