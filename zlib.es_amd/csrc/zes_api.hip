@@ -10,11 +10,13 @@
 #include <atomic>
 #include <condition_variable>
 #include <cstdio>
+#include <cstddef>
 #include <cstdlib>
 #include <cstring>
 #include <chrono>
 #include <functional>
 #include <future>
+#include <initializer_list>
 #include <map>
 #include <mutex>
 #include <string>
@@ -34,6 +36,106 @@ struct KTime {
   double ms = 0;
   uint32_t launches = 0;
 };
+
+// ---- the page-locked area of a context ----
+// One block per context, allocated at init and kept until shutdown: the host writes tables into it for the copy engines,
+// read-backs land in it, and a few kernels write into it through its device address (Ctx::pinned_dev).  Every kind of
+// call has its regions in the union, apart from each other; behind the union, each in a place of its own, are what
+// runs beside another call (two range pieces in flight, gzip's CRC words) and the small single read-backs.
+constexpr size_t PINNED_BYTES = 1 << 20;
+constexpr uint32_t INF_GROUP = 4096;             // buffers per T1 group
+constexpr uint32_t SEG_GROUP_BUFS = 512;         // T2: buffers whose candidates are searched before the first read-back (round 3: 64 -> 512: 2048 x 64 KiB of zlib text 7.4 -> 3.8 ms with single-block streams taken by the block decoder)
+constexpr uint32_t DEFLATE_DIRECT_BUFS = 16384;  // k_layout writes the results of a batch up to this size into the area
+constexpr uint32_t DEFLATE_TABLE_BUFS = 14000;   // a larger batch's buffer table goes up from pageable memory
+constexpr uint32_t MIRROR_ITEMS = 8192;          // work items whose results the host mirror holds (a call with a larger launch bound keeps the chain kernel)
+
+constexpr size_t t1_cnt_bytes(size_t nbuf) { return 16 + nbuf * 4 + ((nbuf + 3) & ~(size_t)3); }  // T1: counters[4], cnt[nbuf], first bytes [nbuf]
+
+struct RangeSlot {     // a piece of inflate_host_pipelined in flight: its search's counters and k_inf_chain_range's results
+  uint32_t counters[6];
+  ZesRes res[2];
+};
+
+struct PinnedArea {
+  union {
+    struct {
+      ZesRes res[DEFLATE_DIRECT_BUFS];   // k_layout's results, straight from the kernel when the area is mapped
+      ZesBuf table[DEFLATE_TABLE_BUFS];  // the buffer table of a batch
+    } def;
+    struct {                                           // inflate_t1_group, inflate_t1_range, the serial wavefront batch
+      uint32_t counters[t1_cnt_bytes(INF_GROUP) / 4];  // (one buffer: k_inf_chain or the block decoder's mirror writes them)
+      ZesRes res[INF_GROUP];                           // (one buffer: k_inf_chain writes them)
+      ZesInfBuf table[INF_GROUP + 1];                  // the buffers and the sentinel
+      ZesInfBuf redo[2];                               // one buffer's blocks decoded again into their own slots
+    } t1;
+    struct {                   // inflate_jobs: one byte of every buffer of a group, read on the device
+      uint8_t bytes[INF_GROUP];
+      uint64_t offs[INF_GROUP];
+    } first;
+    struct {                               // inflate_segments and inflate_segments_run, one group
+      ZesInfBuf search[SEG_GROUP_BUFS + 1];  // the candidate search's table
+      uint32_t ncand[SEG_GROUP_BUFS];
+      uint32_t nsurv;                        // the block-parallel tier's survivor count, going back up
+      uint32_t flags[SEG_GROUP_BUFS + 1];    // [0, nb): not-in-store counts, later failure flags; [nb]: declined items
+      uint32_t far;                          // matches behind the short marker ring
+      ZesRes res[2 * SEG_GROUP_BUFS];        // k_inf_seg_chain: the chains, then where they ended
+      ZesSegJob jobs[SEG_GROUP_BUFS];
+      uint32_t live[SEG_GROUP_BUFS + 1];     // the items the wave decoder takes: count, items
+      ZesSegOut out[SEG_GROUP_BUFS];
+    } t2;
+  };
+  RangeSlot range[2];           // pieces k and k + 1 (slot k & 1)
+  ZesRes res1;                  // read_res
+  unsigned long long adler[2];  // adler32_locked
+  uint32_t crc[2];              // the CRC-32 accumulator words (gzip_core: while the deflate results come back)
+  uint8_t head[16], tail[8];    // header and trailer bytes on their way into a device result (gzip, deflate_join)
+};
+
+// k_inf_block_par's copy of a one-buffer T1 call's work items (ZesParMirror), as the host reads it
+struct ParMirror {
+  ZesCandRes cres[MIRROR_ITEMS];
+  uint32_t start[MIRROR_ITEMS];  // the bit a candidate's block starts at, rank order
+};
+
+struct PinSpan {
+  size_t off, len;
+};
+constexpr bool disjoint(std::initializer_list<PinSpan> s) {
+  for (const PinSpan* a = s.begin(); a != s.end(); ++a)
+    for (const PinSpan* b = a + 1; b != s.end(); ++b)
+      if (a->off < b->off + b->len && b->off < a->off + a->len) return false;
+  return true;
+}
+#define PIN_SPAN(m) PinSpan{offsetof(PinnedArea, m), sizeof(PinnedArea::m)}
+#define PIN_HOLDS(m, n) static_assert(sizeof(PinnedArea::m) >= (n), #m " is smaller than its largest user")
+static_assert(sizeof(PinnedArea) <= PINNED_BYTES, "the page-locked area does not fit its allocation");
+PIN_HOLDS(def.res, sizeof(ZesRes) * DEFLATE_DIRECT_BUFS);
+PIN_HOLDS(def.table, sizeof(ZesBuf) * DEFLATE_TABLE_BUFS);
+PIN_HOLDS(t1.counters, t1_cnt_bytes(INF_GROUP));
+PIN_HOLDS(t1.res, sizeof(ZesRes) * INF_GROUP);
+PIN_HOLDS(t1.table, sizeof(ZesInfBuf) * (INF_GROUP + 1));
+PIN_HOLDS(t1.redo, sizeof(ZesInfBuf) * 2);
+PIN_HOLDS(first.bytes, INF_GROUP);
+PIN_HOLDS(first.offs, sizeof(uint64_t) * INF_GROUP);
+PIN_HOLDS(t2.search, sizeof(ZesInfBuf) * (SEG_GROUP_BUFS + 1));
+PIN_HOLDS(t2.ncand, sizeof(uint32_t) * SEG_GROUP_BUFS);
+PIN_HOLDS(t2.flags, sizeof(uint32_t) * (SEG_GROUP_BUFS + 1));
+PIN_HOLDS(t2.res, sizeof(ZesRes) * 2 * SEG_GROUP_BUFS);
+PIN_HOLDS(t2.jobs, sizeof(ZesSegJob) * SEG_GROUP_BUFS);
+PIN_HOLDS(t2.live, sizeof(uint32_t) * (SEG_GROUP_BUFS + 1));
+PIN_HOLDS(t2.out, sizeof(ZesSegOut) * SEG_GROUP_BUFS);
+PIN_HOLDS(range[0].counters, t1_cnt_bytes(1));
+PIN_HOLDS(range[0].res, sizeof(ZesRes) * 2);
+static_assert(sizeof(ParMirror::cres) >= sizeof(ZesCandRes) * MIRROR_ITEMS, "the mirror is smaller than its launch bound");
+static_assert(sizeof(ParMirror::start) >= sizeof(uint32_t) * MIRROR_ITEMS, "the mirror is smaller than its launch bound");
+// what one call uses at the same time
+static_assert(disjoint({PIN_SPAN(range[0]), PIN_SPAN(range[1])}), "the two range slots overlap");
+static_assert(disjoint({PIN_SPAN(def.res), PIN_SPAN(def.table), PIN_SPAN(crc)}), "deflate regions overlap (gzip_core: the CRC words beside the results)");
+static_assert(disjoint({PIN_SPAN(t1.counters), PIN_SPAN(t1.res), PIN_SPAN(t1.table), PIN_SPAN(t1.redo)}), "T1 regions overlap");
+static_assert(disjoint({PIN_SPAN(first.bytes), PIN_SPAN(first.offs)}), "first-byte regions overlap");
+static_assert(disjoint({PIN_SPAN(t2.search), PIN_SPAN(t2.ncand), PIN_SPAN(t2.nsurv), PIN_SPAN(t2.flags), PIN_SPAN(t2.far), PIN_SPAN(t2.res),
+                        PIN_SPAN(t2.jobs), PIN_SPAN(t2.live), PIN_SPAN(t2.out)}),
+              "T2 regions overlap");
 
 struct Ctx {
   bool ready = false;
@@ -56,9 +158,12 @@ struct Ctx {
   DevBuf crctab, crcacc, gz_in, gz_acc, gz_stage;
   uint32_t crc_npow = 0;
   DevBuf kraft;  // k_inf_scan's table: Kraft contribution of four 3-bit code-length fields at once
-  void* pinned = nullptr;  // small pinned area for read-backs
-  size_t pinned_cap = 0;
-  void* mirror = nullptr;  // one-buffer inflate: the block decoder's results as the host reads them (ZesParMirror)
+  PinnedArea* pinned = nullptr;
+  PinnedArea* pinned_dev = nullptr;  // (null: not mapped; results are then copied back)
+  ParMirror* mirror = nullptr;
+  ParMirror* mirror_dev = nullptr;   // (null: not mapped; the chain kernel does the work then)
+  ZesRes* res_more = nullptr;        // page-locked, grows: the results of a deflate batch larger than DEFLATE_DIRECT_BUFS
+  size_t res_more_n = 0;
   // profiling
   bool profiling = false;
   std::vector<std::pair<std::string, std::pair<hipEvent_t, hipEvent_t>>> pending;
@@ -118,10 +223,6 @@ struct UseDev {                  // a call's context for its duration (nested en
     }                                                                                          \
   } while (0)
 
-// pinned staging: [0, PIN_UP) read-back area, [PIN_UP, pinned_cap) upload area for the buffer table
-constexpr size_t PIN_UP = 256 << 10;
-constexpr size_t MIRROR_ITEMS = 8192;  // work items whose results the host mirror holds (a call with a larger launch bound keeps the chain kernel)
-
 int ensure(DevBuf& b, size_t bytes) {
   if (bytes <= b.cap) return ZES_OK;
   if (b.p) HIPCHK(hipFree(b.p));
@@ -160,11 +261,19 @@ int init_locked(int device) {
   HIPCHK(hipStreamCreateWithFlags(&g.s_adler, hipStreamNonBlocking));
   HIPCHK(hipEventCreateWithFlags(&g.ev_a0, hipEventDisableTiming));
   HIPCHK(hipEventCreateWithFlags(&g.ev_a1, hipEventDisableTiming));
-  g.pinned_cap = 1 << 20;
-  HIPCHK(hipHostMalloc(&g.pinned, g.pinned_cap, hipHostMallocDefault));
-  if (hipHostMalloc(&g.mirror, MIRROR_ITEMS * (sizeof(ZesCandRes) + 4), hipHostMallocDefault) != hipSuccess) {
+  auto dev_addr = [](void* h) -> void* {
+    void* d = nullptr;
+    if (hipHostGetDevicePointer(&d, h, 0) == hipSuccess) return d;
     (void)hipGetLastError();
-    g.mirror = nullptr;  // (the chain kernel does the work then)
+    return nullptr;
+  };
+  HIPCHK(hipHostMalloc((void**)&g.pinned, PINNED_BYTES, hipHostMallocDefault));
+  g.pinned_dev = (PinnedArea*)dev_addr(g.pinned);
+  if (hipHostMalloc((void**)&g.mirror, sizeof(ParMirror), hipHostMallocDefault) == hipSuccess) {
+    g.mirror_dev = (ParMirror*)dev_addr(g.mirror);
+  } else {
+    (void)hipGetLastError();
+    g.mirror = nullptr;
   }
   {
     // units of 2^-7, a field of 0 adds nothing; saturated at 200 so that an over-full group can never sum back to exactly 128
@@ -611,9 +720,9 @@ int deflate_batch_core(const uint8_t* d_in, const uint64_t* in_off, const uint64
   uint32_t* idx_b = (uint32_t*)g.idx_b.p;
   unsigned long long* adler = (unsigned long long*)g.adler.p;
   if (nbuf > 1) {
-    if (sizeof(ZesBuf) * nbuf <= g.pinned_cap - PIN_UP) {
-      memcpy((uint8_t*)g.pinned + PIN_UP, hb.data(), sizeof(ZesBuf) * nbuf);
-      HIPCHK(hipMemcpyAsync(g.bufs.p, (uint8_t*)g.pinned + PIN_UP, sizeof(ZesBuf) * nbuf, hipMemcpyHostToDevice, g.stream));
+    if (nbuf <= DEFLATE_TABLE_BUFS) {
+      memcpy(g.pinned->def.table, hb.data(), sizeof(ZesBuf) * nbuf);
+      HIPCHK(hipMemcpyAsync(g.bufs.p, g.pinned->def.table, sizeof(ZesBuf) * nbuf, hipMemcpyHostToDevice, g.stream));
     } else {
       HIPCHK(hipMemcpy(g.bufs.p, hb.data(), sizeof(ZesBuf) * nbuf, hipMemcpyHostToDevice));
     }
@@ -757,12 +866,7 @@ int deflate_batch_core(const uint8_t* d_in, const uint64_t* in_off, const uint64
     HIPCHK(hipStreamSynchronize(g.stream));
     zes_huff_set_dbg((unsigned long long*)g.dbg.p);
   }
-  ZesRes* res_direct = nullptr;  // the read-back area as the device sees it
-  if (sizeof(ZesRes) * nbuf <= PIN_UP) {
-    void* dp = nullptr;
-    if (hipHostGetDevicePointer(&dp, g.pinned, 0) == hipSuccess) res_direct = (ZesRes*)dp;
-    else (void)hipGetLastError();
-  }
+  ZesRes* res_direct = (nbuf <= DEFLATE_DIRECT_BUFS && g.pinned_dev) ? g.pinned_dev->def.res : nullptr;
   {
     Timed t("k_huff");
     hipLaunchKernelGGL(k_huff, dim3(nblk), dim3(HUFF_THREADS_HOST), 0, g.stream, dblks, (const uint32_t*)g.hists.p,
@@ -796,16 +900,21 @@ int deflate_batch_core(const uint8_t* d_in, const uint64_t* in_off, const uint64
                        (const uint32_t*)g.codes.p, (const uint32_t*)g.hdrs.p);
   }
   HIPCHK(hipGetLastError());
-  if (sizeof(ZesRes) * nbuf > g.pinned_cap) {
-    HIPCHK(hipHostFree(g.pinned));
-    g.pinned_cap = sizeof(ZesRes) * nbuf * 2;
-    HIPCHK(hipHostMalloc(&g.pinned, g.pinned_cap, hipHostMallocDefault));
+  ZesRes* r = g.pinned->def.res;
+  if (nbuf > DEFLATE_DIRECT_BUFS) {
+    if (nbuf > g.res_more_n) {
+      if (g.res_more) HIPCHK(hipHostFree(g.res_more));
+      g.res_more = nullptr;
+      g.res_more_n = 0;
+      HIPCHK(hipHostMalloc((void**)&g.res_more, sizeof(ZesRes) * nbuf * 2, hipHostMallocDefault));
+      g.res_more_n = (size_t)nbuf * 2;
+    }
+    r = g.res_more;
   }
-  if (!res_direct) HIPCHK(hipMemcpyAsync(g.pinned, g.res.p, sizeof(ZesRes) * nbuf, hipMemcpyDeviceToHost, g.stream));
-  if (defer) return ZES_OK;  // (one buffer: the caller reads g.pinned after its own synchronisation, deflate_piece_finish)
+  if (!res_direct) HIPCHK(hipMemcpyAsync(r, g.res.p, sizeof(ZesRes) * nbuf, hipMemcpyDeviceToHost, g.stream));
+  if (defer) return ZES_OK;  // (one buffer: the caller reads def.res after its own synchronisation, deflate_host_pipelined)
   HIPCHK(hipStreamSynchronize(g.stream));
   collect_times();
-  const ZesRes* r = (const ZesRes*)g.pinned;
   for (uint32_t k = 0; k < nbuf; k++) {
     out_len[live[k]] = r[k].out_len;
     status[live[k]] = r[k].status;
@@ -816,13 +925,11 @@ int deflate_batch_core(const uint8_t* d_in, const uint64_t* in_off, const uint64
 
 // ---- inflate ----
 int read_res(ZesRes* out) {
-  HIPCHK(hipMemcpyAsync(g.pinned, g.res.p, sizeof(ZesRes), hipMemcpyDeviceToHost, g.stream));
+  HIPCHK(hipMemcpyAsync(&g.pinned->res1, g.res.p, sizeof(ZesRes), hipMemcpyDeviceToHost, g.stream));
   HIPCHK(hipStreamSynchronize(g.stream));
-  *out = *(const ZesRes*)g.pinned;
+  *out = g.pinned->res1;
   return ZES_OK;
 }
-
-constexpr uint32_t INF_GROUP = 4096;  // buffers per T1 group (table and read-backs fit the pinned area)
 
 struct InfJob {
   uint64_t in_off, c, out_off, cap;
@@ -939,7 +1046,7 @@ int print_par_phases(const unsigned long long* dbg, uint64_t work) {
 int inflate_t1_group(const uint8_t* d_in, uint8_t* d_out, InfJob* jobs, const uint32_t* ids, uint32_t nbuf, bool check_first, uint32_t flags) {
   int rc;
   g.sv_ok = false;  // (g.surv is about to be rewritten)
-  ZesInfBuf* hb = (ZesInfBuf*)((uint8_t*)g.pinned + PIN_UP);
+  ZesInfBuf* hb = g.pinned->t1.table;
   uint64_t chunks = 0, cands = 0, total_c = 0;
   for (uint32_t i = 0; i < nbuf; i++) {
     const InfJob& j = jobs[ids[i]];
@@ -972,7 +1079,7 @@ int inflate_t1_group(const uint8_t* d_in, uint8_t* d_out, InfJob* jobs, const ui
     hb[1].cand_cap = hb[0].cand_cap;
   }
   const uint32_t surv_cap = (uint32_t)std::min<uint64_t>(total_c / 4 + 1024ull * nbuf, 1ull << 30);
-  const size_t cnt_bytes = 16 + (size_t)nbuf * 4 + (((size_t)nbuf + 3) & ~(size_t)3);  // counters[4], cnt[nbuf], first bytes [nbuf]
+  const size_t cnt_bytes = t1_cnt_bytes(nbuf);
   if ((rc = ensure(g.ibufs, sizeof(ZesInfBuf) * (nbuf + 1)))) return rc;
   if ((rc = ensure(g.surv, (size_t)surv_cap * 8))) return rc;
   if ((rc = ensure(g.cand, (size_t)cands * 4))) return rc;
@@ -1006,8 +1113,8 @@ int inflate_t1_group(const uint8_t* d_in, uint8_t* d_out, InfJob* jobs, const ui
   // candidate count from device memory (table sentinel ZES_WORK_AUTO) and the host reads counters and
   // result together — one synchronisation per call.  Several buffers: the counts come back first.
   const bool one = nbuf == 1;
-  uint32_t* hc = (uint32_t*)g.pinned;
-  ZesRes* hres = (ZesRes*)((uint8_t*)g.pinned + 128 * 1024);
+  uint32_t* hc = g.pinned->t1.counters;
+  ZesRes* hres = g.pinned->t1.res;
   uint64_t work = 0;
   std::vector<uint32_t> ncand(nbuf);
   if (!one) {
@@ -1062,19 +1169,13 @@ int inflate_t1_group(const uint8_t* d_in, uint8_t* d_out, InfJob* jobs, const ui
     // what k_inf_chain does, on a few hundred 16-byte records: no chain kernel behind this one (11 us + a kernel boundary of
     // a 0.8 ms call).  Only a chain that needs the slots moved (false candidates between the blocks) still runs that kernel,
     // for its map.
-    if (one && work <= MIRROR_ITEMS && g.mirror) {
-      void* dm = nullptr;
-      void* dp0 = nullptr;
-      if (hipHostGetDevicePointer(&dm, g.mirror, 0) == hipSuccess && hipHostGetDevicePointer(&dp0, g.pinned, 0) == hipSuccess) {
-        mir.cres_host = (ZesCandRes*)dm;
-        mir.start_host = (uint32_t*)((uint8_t*)dm + MIRROR_ITEMS * sizeof(ZesCandRes));
-        mir.counters = counters;
-        mir.counters_host = (uint32_t*)dp0;
-        mir.counter_words = (uint32_t)(cnt_bytes / 4);
-        hostchain = true;
-      } else {
-        (void)hipGetLastError();
-      }
+    if (one && work <= MIRROR_ITEMS && g.mirror_dev && g.pinned_dev) {
+      mir.cres_host = g.mirror_dev->cres;
+      mir.start_host = g.mirror_dev->start;
+      mir.counters = counters;
+      mir.counters_host = g.pinned_dev->t1.counters;
+      mir.counter_words = (uint32_t)(cnt_bytes / 4);
+      hostchain = true;
     }
     hipLaunchKernelGGL(kern, dim3((uint32_t)work), dim3(PAR_THREADS), 0, g.stream, d_in, d_out, dbufs, nbuf,
                        (const uint32_t*)cnt, (const uint32_t*)g.cand_sorted.p, (const uint32_t*)nullptr, (ZesCandRes*)g.cres.p, dbg, (const uint32_t*)nullptr,
@@ -1084,16 +1185,11 @@ int inflate_t1_group(const uint8_t* d_in, uint8_t* d_out, InfJob* jobs, const ui
     Timed t("k_inf_chain");
     // one buffer: the kernel puts its result and the counters straight into the page-locked read-back area (no copy
     // commands behind the kernels: ~10 us of a 0.8 ms call)
-    void* dp = nullptr;
-    if (one && hipHostGetDevicePointer(&dp, g.pinned, 0) != hipSuccess) {
-      (void)hipGetLastError();
-      dp = nullptr;
-    }
-    direct = one && dp != nullptr;
+    direct = one && g.pinned_dev;
     hipLaunchKernelGGL(k_inf_chain, dim3(nbuf), dim3(256), 0, g.stream, dbufs, (const uint32_t*)cnt, (const uint32_t*)g.cand_sorted.p,
                        (const ZesCandRes*)g.cres.p, (const uint32_t*)nullptr, (uint32_t*)g.map.p,
-                       direct ? (ZesRes*)((uint8_t*)dp + 128 * 1024) : (ZesRes*)g.res.p, (const uint32_t*)counters, (uint32_t)(cnt_bytes / 4),
-                       direct ? (uint32_t*)dp : (uint32_t*)nullptr);
+                       direct ? g.pinned_dev->t1.res : (ZesRes*)g.res.p, (const uint32_t*)counters, (uint32_t)(cnt_bytes / 4),
+                       direct ? g.pinned_dev->t1.counters : (uint32_t*)nullptr);
     if (!direct) {
       if (one) HIPCHK(hipMemcpyAsync(hc, g.counters.p, cnt_bytes, hipMemcpyDeviceToHost, g.stream));
       HIPCHK(hipMemcpyAsync(hres, g.res.p, sizeof(ZesRes) * nbuf, hipMemcpyDeviceToHost, g.stream));
@@ -1106,8 +1202,8 @@ int inflate_t1_group(const uint8_t* d_in, uint8_t* d_out, InfJob* jobs, const ui
   host_lap("T1: search + decode + chain");
   if (hostchain) {
     // k_inf_chain's walk on the mirror (one buffer; start[k] = the bit candidate k's block starts at, rank order)
-    const ZesCandRes* hcr = (const ZesCandRes*)g.mirror;
-    const uint32_t* hst = (const uint32_t*)((const uint8_t*)g.mirror + MIRROR_ITEMS * sizeof(ZesCandRes));
+    const ZesCandRes* hcr = g.mirror->cres;
+    const uint32_t* hst = g.mirror->start;
     ZesRes r;
     r.status = 1;
     r.out_len = 0;
@@ -1266,7 +1362,7 @@ int inflate_t1_group(const uint8_t* d_in, uint8_t* d_out, InfJob* jobs, const ui
     if (nre) {
       HIPCHK(hipMemcpy(dl + 3 * (size_t)nmv, redo.data(), (size_t)nre * 4, hipMemcpyHostToDevice));
       // a two-entry table for this buffer alone: work item -> slot through redo[], K work items in all
-      ZesInfBuf* one = (ZesInfBuf*)((uint8_t*)g.pinned + PIN_UP) + nbuf + 2;
+      ZesInfBuf* one = g.pinned->t1.redo;
       one[0] = hb[i];
       one[0].work_first = 0;
       one[1] = hb[i];
@@ -1299,7 +1395,7 @@ int inflate_t1_group(const uint8_t* d_in, uint8_t* d_out, InfJob* jobs, const ui
     InfJob& j = jobs[ids[i]];
     if (j.want_end && hres[i].status == 0 && r.aux) {  // (status 2 above has filled it in)
       if (hostchain) {
-        j.end_bit = ((const ZesCandRes*)g.mirror)[r.aux - 1].end_bit;
+        j.end_bit = g.mirror->cres[r.aux - 1].end_bit;
       } else {
         ZesCandRes last;
         HIPCHK(hipMemcpy(&last, (const ZesCandRes*)g.cres.p + hb[i].cand_base + r.aux - 1, sizeof last, hipMemcpyDeviceToHost));
@@ -1337,7 +1433,7 @@ int inflate_t1_range(const uint8_t* d_in, uint64_t in_off, uint64_t c, uint64_t 
     return ZES_OK;
   };
   if (c * 8 < lo_bit + 64) return nothing_here();
-  ZesInfBuf* hb = (ZesInfBuf*)((uint8_t*)g.pinned + PIN_UP);
+  ZesInfBuf* hb = g.pinned->t1.table;
   memset(hb, 0, 2 * sizeof(ZesInfBuf));
   const uint64_t chunks = (c + INF_SCAN_BYTES - 1) / INF_SCAN_BYTES;
   hb[0].in_off = in_off;
@@ -1375,7 +1471,7 @@ int inflate_t1_range(const uint8_t* d_in, uint64_t in_off, uint64_t c, uint64_t 
                        surv_cap, counters, dfirst, (flags & ZES_F_LOOSE_CANDIDATES) ? 1u : 2u, (const uint8_t*)g.kraft.p);
   }
   if ((rc = launch_verify(d_in, dbufs, surv_cap, counters, cnt, (flags & ZES_F_LOOSE_CANDIDATES) ? 1u : 0u, c, 32768))) return rc;
-  uint32_t* hc = (uint32_t*)g.pinned;
+  uint32_t* hc = g.pinned->t1.counters;
   HIPCHK(hipMemcpyAsync(hc, g.counters.p, cnt_bytes, hipMemcpyDeviceToHost, g.stream));
   HIPCHK(hipStreamSynchronize(g.stream));
   const uint32_t nsurv = hc[0], ncand = hc[4];
@@ -1394,7 +1490,7 @@ int inflate_t1_range(const uint8_t* d_in, uint64_t in_off, uint64_t c, uint64_t 
     hipLaunchKernelGGL(k_inf_chain_range, dim3(1), dim3(256), 0, g.stream, dbufs, (const uint32_t*)cnt, (const uint32_t*)g.cand_sorted.p,
                        (const ZesCandRes*)g.cres.p, (ZesRes*)g.res.p, (unsigned long long*)nullptr);
   }
-  ZesRes* hres = (ZesRes*)((uint8_t*)g.pinned + 128 * 1024);
+  ZesRes* hres = g.pinned->t1.res;
   HIPCHK(hipMemcpyAsync(hres, g.res.p, sizeof(ZesRes) * 2, hipMemcpyDeviceToHost, g.stream));
   HIPCHK(hipStreamSynchronize(g.stream));
   if (getenv("ZES_RANGE_DBG")) {
@@ -1429,9 +1525,8 @@ struct RangePend {
   uint64_t lo_bit = 0;
   uint32_t surv_cap = 0, cand_cap = 0, bound = 0;
 };
-static uint32_t* range_hc(int slot) { return (uint32_t*)((uint8_t*)g.pinned + 96 * 1024 + slot * 64); }
-static ZesRes* range_hres(int slot) { return (ZesRes*)((uint8_t*)g.pinned + 96 * 1024 + 256 + slot * 64); }
-static unsigned long long* range_acc() { return (unsigned long long*)((uint8_t*)g.counters.p + 64); }
+constexpr size_t RANGE_ACC_OFF = 64;  // g.counters: the pieces' block count so far, behind the counter words of a piece's search
+static unsigned long long* range_acc() { return (unsigned long long*)((uint8_t*)g.counters.p + RANGE_ACC_OFF); }
 // scratch for pieces of up to cmax bytes, before anything is in flight (growing a buffer frees the old one)
 int range_reserve(uint64_t cmax) {
   int rc;
@@ -1499,8 +1594,9 @@ int range_begin(int slot, RangePend& pd, const uint8_t* d_in, uint64_t in_off, u
       hipLaunchKernelGGL(k_inf_chain_range, dim3(1), dim3(256), 0, g.stream, dbufs, (const uint32_t*)cnt, (const uint32_t*)g.cand_sorted.p,
                          (const ZesCandRes*)g.cres.p, (ZesRes*)g.res.p, range_acc());
     }
-    HIPCHK(hipMemcpyAsync(range_hc(slot), g.counters.p, 24, hipMemcpyDeviceToHost, g.stream));
-    HIPCHK(hipMemcpyAsync(range_hres(slot), g.res.p, sizeof(ZesRes) * 2, hipMemcpyDeviceToHost, g.stream));
+    RangeSlot& hs = g.pinned->range[slot];
+    HIPCHK(hipMemcpyAsync(hs.counters, g.counters.p, sizeof hs.counters, hipMemcpyDeviceToHost, g.stream));
+    HIPCHK(hipMemcpyAsync(hs.res, g.res.p, sizeof hs.res, hipMemcpyDeviceToHost, g.stream));
   }
   HIPCHK(hipEventRecord(g.ev_rng[slot], g.stream));
   return ZES_OK;
@@ -1516,8 +1612,8 @@ int range_finish(int slot, const RangePend& pd, RangeRes* rr) {
     return ZES_OK;
   };
   if (pd.nothing) return nothing_here();
-  const uint32_t* hc = range_hc(slot);
-  const ZesRes* hres = range_hres(slot);
+  const uint32_t* hc = g.pinned->range[slot].counters;
+  const ZesRes* hres = g.pinned->range[slot].res;
   const uint32_t nsurv = hc[0], ncand = hc[4];
   if (nsurv > pd.surv_cap || ncand > pd.cand_cap) return ZES_OK;
   if (nsurv == 0 || ncand == 0) return nothing_here();
@@ -1543,14 +1639,13 @@ constexpr uint64_t SEG_MIN_C = ZES_SEG_MIN_C;  // shorter streams go straight to
 constexpr size_t SERIAL_BATCH_MIN_JOBS = 16;        // this many left-over streams of a call: one serial wavefront each, side by side
 constexpr uint64_t SERIAL_BATCH_MAX_C = 8ull << 10;  // (round 3: 128 KiB -> 8 KiB)  // (longer ones go to the segment-parallel tier: its block decoder is ~15 times a lone wave)
 constexpr uint64_t SEG_PIECES_MIN_C = 48ull << 20;  // streams from this size on go through the tier in pieces of 32 MiB (inflate_segments_pieces)
-constexpr uint32_t SEG_GROUP_BUFS = 512;     // (round 3: 64 -> 512: 2048 x 64 KiB of zlib text 7.4 -> 3.8 ms with single-block streams taken by the block decoder)     // buffers whose candidates are searched before the first read-back
 constexpr uint32_t SEG_GROUP_WORK = 8192;    // work items per segment launch (each owns a 64 KiB map)
 
 // One group: buffers ids[0..nb) with their sorted candidate lists at cand_sorted + cbase[k], ncand[k] entries.
 int inflate_segments_run(const uint8_t* d_in, uint8_t* d_out, InfJob* jobs, const uint32_t* ids, const uint32_t* cbase, const uint32_t* ncand,
                          uint32_t nb, uint32_t* dscratch /* 2 * nb + 1 words: chain segments not in the store, failure flags, far-match counter */) {
   int rc;
-  ZesSegJob* hj = (ZesSegJob*)((uint8_t*)g.pinned + PIN_UP);
+  ZesSegJob* hj = g.pinned->t2.jobs;
   uint32_t work = 0;
   uint64_t csum = 0;
   for (uint32_t k = 0; k < nb; k++) csum += jobs[ids[k]].c + 64;
@@ -1640,8 +1735,8 @@ int inflate_segments_run(const uint8_t* d_in, uint8_t* d_out, InfJob* jobs, cons
               (unsigned long long)sr[w].out_len, sr[w].flags, sr[w].next);
   };
   dump_items("after the block decoder");
-  uint32_t* hs = (uint32_t*)g.pinned;  // [0, nb): not-in-store counts, later failure flags; [nb]: declined items
-  ZesRes* hres = (ZesRes*)((uint8_t*)g.pinned + 128 * 1024);
+  uint32_t* hs = g.pinned->t2.flags;
+  ZesRes* hres = g.pinned->t2.res;
   // the chain of every buffer of the group (work item 0 -> the item that starts where it ended -> ... -> the final block)
   auto run_chains = [&]() -> int {
     HIPCHK(hipMemsetAsync(novf_d, 0, (size_t)nb * 4, g.stream));
@@ -1697,7 +1792,7 @@ int inflate_segments_run(const uint8_t* d_in, uint8_t* d_out, InfJob* jobs, cons
       }
       if (items.empty()) break;
       if ((rc = ensure(g.seglive, ((size_t)nb + 1) * 4))) return rc;
-      uint32_t* hl = (uint32_t*)((uint8_t*)g.pinned + 768 * 1024);  // (upload area, behind the job table)
+      uint32_t* hl = g.pinned->t2.live;
       hl[0] = (uint32_t)items.size();
       memcpy(hl + 1, items.data(), items.size() * 4);
       HIPCHK(hipMemcpyAsync(g.seglive.p, hl, (items.size() + 1) * 4, hipMemcpyHostToDevice, g.stream));
@@ -1707,10 +1802,9 @@ int inflate_segments_run(const uint8_t* d_in, uint8_t* d_out, InfJob* jobs, cons
                            (ZesSegRes*)g.sres.p, (uint32_t*)g.maps.p, (uint32_t*)g.sym16.p, ratio, (const uint32_t*)g.seglive.p + 1, far_d,
                            (const uint32_t*)g.seglive.p, (uint64_t*)g.symoff.p);
       }
-      uint32_t* hf = (uint32_t*)((uint8_t*)g.pinned + 192 * 1024);
-      HIPCHK(hipMemcpyAsync(hf, far_d, 4, hipMemcpyDeviceToHost, g.stream));
+      HIPCHK(hipMemcpyAsync(&g.pinned->t2.far, far_d, 4, hipMemcpyDeviceToHost, g.stream));
       if ((rc = run_chains())) return rc;
-      if (hf[0] != 0) {  // a far match behind the short ring: the full-ring pass below decides
+      if (g.pinned->t2.far != 0) {  // a far match behind the short ring: the full-ring pass below decides
         chained = false;
         break;
       }
@@ -1734,10 +1828,9 @@ int inflate_segments_run(const uint8_t* d_in, uint8_t* d_out, InfJob* jobs, cons
                          (const uint32_t*)fail_list, (uint64_t*)g.symoff.p);
     }
     {
-      uint32_t* hf = (uint32_t*)g.pinned;
-      HIPCHK(hipMemcpyAsync(hf, far_d, 4, hipMemcpyDeviceToHost, g.stream));
+      HIPCHK(hipMemcpyAsync(&g.pinned->t2.far, far_d, 4, hipMemcpyDeviceToHost, g.stream));
       HIPCHK(hipStreamSynchronize(g.stream));
-      if (hf[0] != 0) {
+      if (g.pinned->t2.far != 0) {
         Timed t("k_inf_seg_scan");
         hipLaunchKernelGGL(k_inf_seg_scan, dim3(work), dim3(64), 0, g.stream, d_in, (const ZesSegJob*)g.segjobs.p, nb, cs, (ZesSegRes*)g.sres.p,
                            (uint32_t*)g.maps.p, (uint32_t*)g.sym16.p, ratio, (const uint32_t*)g.segorder.p, far_d, (const uint32_t*)nullptr,
@@ -1781,7 +1874,7 @@ int inflate_segments_run(const uint8_t* d_in, uint8_t* d_out, InfJob* jobs, cons
   HIPCHK(hipMemcpyAsync(g.segjobs.p, hj, sizeof(ZesSegJob) * nb, hipMemcpyHostToDevice, g.stream));
   // where every buffer's bytes go (and how much output exists in front: a later piece of a long stream)
   if ((rc = ensure(g.segouts, sizeof(ZesSegOut) * nb))) return rc;
-  ZesSegOut* ho = (ZesSegOut*)((uint8_t*)g.pinned + 832 * 1024);  // (upload area)
+  ZesSegOut* ho = g.pinned->t2.out;
   uint32_t max_tr = 0, min_tr = 0xFFFFFFFFu;
   for (uint32_t k = 0; k < nb; k++) {
     const InfJob& j = jobs[ids[k]];
@@ -1880,7 +1973,7 @@ int inflate_segments(const uint8_t* d_in, uint8_t* d_out, InfJob* jobs, const st
     // itself, afterwards.  (256 streams of 1 MiB: the searches one after the other were 36 ms of launches.)
     std::vector<char> searched(nb, 0);
     if (nb > 1) {
-      ZesInfBuf* hb = (ZesInfBuf*)((uint8_t*)g.pinned + PIN_UP);
+      ZesInfBuf* hb = g.pinned->t2.search;
       memset(hb, 0, sizeof(ZesInfBuf) * (nb + 1));
       uint64_t chunks = 0, total_c = 0;
       for (uint32_t k = 0; k < nb; k++) {
@@ -1914,7 +2007,7 @@ int inflate_segments(const uint8_t* d_in, uint8_t* d_out, InfJob* jobs, const st
         hipLaunchKernelGGL(k_inf_ranksort, dim3(nb), dim3(1024), 0, g.stream, dbufs, (const uint32_t*)cnt, (const uint32_t*)g.cand.p,
                            (uint32_t*)g.cand_sorted.p, SEG_BUCKETS);
       }
-      uint32_t* hc0 = (uint32_t*)g.pinned;
+      uint32_t* hc0 = g.pinned->t2.ncand;
       HIPCHK(hipMemcpyAsync(hc0, cnt, (size_t)nb * 4, hipMemcpyDeviceToHost, g.stream));
       HIPCHK(hipStreamSynchronize(g.stream));
       for (uint32_t k = 0; k < nb; k++) searched[k] = hc0[k] <= SEG_BUCKETS;  // (the others: thinned below, from a search of their own)
@@ -1948,9 +2041,8 @@ int inflate_segments(const uint8_t* d_in, uint8_t* d_out, InfJob* jobs, const st
       const bool reuse = nb == 1 && g.sv_ok && g.sv_list == g.surv.p && g.sv_din == d_in && g.sv_in_off == j.in_off && g.sv_c == j.c && j.start0 == 16u && g.sv_n <= surv_cap;
       g.sv_ok = false;
       if (reuse) {
-        uint32_t* hv = (uint32_t*)((uint8_t*)g.pinned + 196 * 1024);
-        hv[0] = g.sv_n;
-        HIPCHK(hipMemcpyAsync(counters, hv, 4, hipMemcpyHostToDevice, g.stream));
+        g.pinned->t2.nsurv = g.sv_n;
+        HIPCHK(hipMemcpyAsync(counters, &g.pinned->t2.nsurv, 4, hipMemcpyHostToDevice, g.stream));
       } else {
         Timed t("k_inf_scan");
         // (the BFINAL rule of the scan holds for every encoder's streams: it stays on; only the verify rules are the reference's own)
@@ -1971,7 +2063,7 @@ int inflate_segments(const uint8_t* d_in, uint8_t* d_out, InfJob* jobs, const st
                            (uint32_t*)g.cand_sorted.p + cbase[k], cnt + k);
       }
     }
-    uint32_t* hc = (uint32_t*)g.pinned;
+    uint32_t* hc = g.pinned->t2.ncand;
     HIPCHK(hipMemcpyAsync(hc, cnt, (size_t)nb * 4, hipMemcpyDeviceToHost, g.stream));
     host_lap("(host work since)");
     HIPCHK(hipStreamSynchronize(g.stream));
@@ -2241,15 +2333,15 @@ int inflate_jobs(const uint8_t* d_in, uint8_t* d_out, std::vector<InfJob>& jobs,
   for (size_t g0 = 0; g0 < small.size(); g0 += INF_GROUP) {
     const uint32_t nb = (uint32_t)std::min<size_t>(INF_GROUP, small.size() - g0);
     if ((rc = ensure(g.ibufs, (size_t)INF_GROUP * 8 + INF_GROUP))) return rc;
-    uint64_t* ho = (uint64_t*)((uint8_t*)g.pinned + PIN_UP);
+    uint64_t* ho = g.pinned->first.offs;
     for (uint32_t k = 0; k < nb; k++) ho[k] = jobs[small[g0 + k]].in_off;
     uint8_t* dfirst = (uint8_t*)g.ibufs.p + (size_t)INF_GROUP * 8;
     HIPCHK(hipMemcpyAsync(g.ibufs.p, ho, (size_t)nb * 8, hipMemcpyHostToDevice, g.stream));
     hipLaunchKernelGGL(k_inf_first_bytes, dim3((nb + 255) / 256), dim3(256), 0, g.stream, d_in, (const uint64_t*)g.ibufs.p, dfirst, nb);
-    HIPCHK(hipMemcpyAsync(g.pinned, dfirst, nb, hipMemcpyDeviceToHost, g.stream));
+    HIPCHK(hipMemcpyAsync(g.pinned->first.bytes, dfirst, nb, hipMemcpyDeviceToHost, g.stream));
     HIPCHK(hipStreamSynchronize(g.stream));
     for (uint32_t k = 0; k < nb; k++)
-      if ((((const uint8_t*)g.pinned)[k] & 15u) != 8u) {
+      if ((g.pinned->first.bytes[k] & 15u) != 8u) {
         jobs[small[g0 + k]].status = ZES_E_NOT_DEFLATE;
         jobs[small[g0 + k]].tier = -1;
       }
@@ -2264,11 +2356,9 @@ int inflate_jobs(const uint8_t* d_in, uint8_t* d_out, std::vector<InfJob>& jobs,
     if (j.tier != 0 || j.status != ZES_OK || (flags & ZES_F_NO_FASTPATH)) continue;
     if (!(j.c >= (1ull << 29) || ((flags & ZES_F_PIECES) && j.c >= 64))) continue;
     if (firsts == nullptr) {  // the CM nibble (src/zlib.ts:13-16) was not checked on the way for this one
-      uint8_t fb = 0;
-      HIPCHK(hipMemcpyAsync(g.pinned, d_in + j.in_off, 1, hipMemcpyDeviceToHost, g.stream));
+      HIPCHK(hipMemcpyAsync(g.pinned->first.bytes, d_in + j.in_off, 1, hipMemcpyDeviceToHost, g.stream));
       HIPCHK(hipStreamSynchronize(g.stream));
-      fb = *(const uint8_t*)g.pinned;
-      if ((fb & 15u) != 8u) {
+      if ((g.pinned->first.bytes[0] & 15u) != 8u) {
         j.status = ZES_E_NOT_DEFLATE;
         j.tier = -1;
         continue;
@@ -2286,7 +2376,7 @@ int inflate_jobs(const uint8_t* d_in, uint8_t* d_out, std::vector<InfJob>& jobs,
     if (rest.size() >= SERIAL_BATCH_MIN_JOBS) {
       for (size_t g0 = 0; g0 < rest.size(); g0 += INF_GROUP) {
         const uint32_t nb = (uint32_t)std::min<size_t>(INF_GROUP, rest.size() - g0);
-        ZesInfBuf* hb = (ZesInfBuf*)((uint8_t*)g.pinned + PIN_UP);
+        ZesInfBuf* hb = g.pinned->t1.table;
         memset(hb, 0, sizeof(ZesInfBuf) * nb);
         for (uint32_t k = 0; k < nb; k++) {
           const InfJob& j = jobs[rest[g0 + k]];
@@ -2304,7 +2394,7 @@ int inflate_jobs(const uint8_t* d_in, uint8_t* d_out, std::vector<InfJob>& jobs,
           hipLaunchKernelGGL(k_inf_decode, dim3(nb), dim3(64), 0, g.stream, d_in, d_out, (const ZesInfBuf*)g.ibufs.p, (ZesRes*)g.res.p,
                              (uint64_t*)g.resume.p);
         }
-        ZesRes* hres = (ZesRes*)((uint8_t*)g.pinned + 128 * 1024);
+        ZesRes* hres = g.pinned->t1.res;
         HIPCHK(hipMemcpyAsync(hres, g.res.p, sizeof(ZesRes) * nb, hipMemcpyDeviceToHost, g.stream));
         HIPCHK(hipStreamSynchronize(g.stream));
         for (uint32_t k = 0; k < nb; k++) {
@@ -2330,14 +2420,14 @@ int inflate_jobs(const uint8_t* d_in, uint8_t* d_out, std::vector<InfJob>& jobs,
         for (size_t g0 = 0; g0 < st.size(); g0 += INF_GROUP) {
           const uint32_t nb = (uint32_t)std::min<size_t>(INF_GROUP, st.size() - g0);
           if ((rc = ensure(g.ibufs, (size_t)INF_GROUP * 8 + INF_GROUP))) return rc;
-          uint64_t* ho = (uint64_t*)((uint8_t*)g.pinned + PIN_UP);
+          uint64_t* ho = g.pinned->first.offs;
           for (uint32_t k = 0; k < nb; k++) ho[k] = jobs[st[g0 + k]].in_off + 2u;
           uint8_t* dfirst = (uint8_t*)g.ibufs.p + (size_t)INF_GROUP * 8;
           HIPCHK(hipMemcpyAsync(g.ibufs.p, ho, (size_t)nb * 8, hipMemcpyHostToDevice, g.stream));
           hipLaunchKernelGGL(k_inf_first_bytes, dim3((nb + 255) / 256), dim3(256), 0, g.stream, d_in, (const uint64_t*)g.ibufs.p, dfirst, nb);
-          HIPCHK(hipMemcpyAsync(g.pinned, dfirst, nb, hipMemcpyDeviceToHost, g.stream));
+          HIPCHK(hipMemcpyAsync(g.pinned->first.bytes, dfirst, nb, hipMemcpyDeviceToHost, g.stream));
           HIPCHK(hipStreamSynchronize(g.stream));
-          for (uint32_t k = 0; k < nb; k++) want[g0 + k] = ((((const uint8_t*)g.pinned)[k] >> 1) & 3u) == 0u;
+          for (uint32_t k = 0; k < nb; k++) want[g0 + k] = ((g.pinned->first.bytes[k] >> 1) & 3u) == 0u;
         }
       }
       for (size_t q = 0; q < st.size(); q++)
@@ -2508,9 +2598,12 @@ static int shutdown_one(void) {
   g.kraft.p = nullptr;
   g.kraft.cap = 0;
   if (g.pinned) (void)hipHostFree(g.pinned);
-  g.pinned = nullptr;
   if (g.mirror) (void)hipHostFree(g.mirror);
-  g.mirror = nullptr;
+  if (g.res_more) (void)hipHostFree(g.res_more);
+  g.pinned = g.pinned_dev = nullptr;
+  g.mirror = g.mirror_dev = nullptr;
+  g.res_more = nullptr;
+  g.res_more_n = 0;
   g_side_up.shutdown();
   g_side_down.shutdown();
   g_up.release();
@@ -2671,7 +2764,7 @@ static int deflate_host_pipelined(const uint8_t* in, uint64_t n, uint8_t* out, u
     }
     collect_times();
     stamp("kernels done", k);
-    const ZesRes* r = (const ZesRes*)g.pinned;
+    const ZesRes* r = g.pinned->def.res;
     if (r[0].status) {
       (void)settle(f_up);
       (void)settle(f_down);
@@ -3207,10 +3300,10 @@ int adler32_locked(const uint8_t* d_in, uint64_t n, uint32_t* adler_out) {
     const uint32_t nch = (uint32_t)((n + ADLER_CHUNK - 1) / ADLER_CHUNK);
     hipLaunchKernelGGL(k_adler, dim3(nch), dim3(ADLER_THREADS), 0, g.stream, d_in, (uint64_t)0, n, acc);
   }
-  HIPCHK(hipMemcpyAsync(g.pinned, acc, 16, hipMemcpyDeviceToHost, g.stream));
+  HIPCHK(hipMemcpyAsync(g.pinned->adler, acc, 16, hipMemcpyDeviceToHost, g.stream));
   HIPCHK(hipStreamSynchronize(g.stream));
   collect_times();
-  const unsigned long long* h = (const unsigned long long*)g.pinned;
+  const unsigned long long* h = g.pinned->adler;
   const uint32_t s1 = (uint32_t)((1ull + h[0]) % 65521ull);
   const uint32_t s2 = (uint32_t)((n % 65521ull + h[1]) % 65521ull);
   *adler_out = (s2 << 16) | s1;
@@ -3277,13 +3370,13 @@ int zes_deflate_join_dev(const uint8_t* const* d_piece, const uint64_t* piece_bi
     pos += piece_bits[i];
   }
   HIPCHK(hipGetLastError());
-  uint8_t* hp = (uint8_t*)g.pinned;
-  hp[0] = 0x78;  // src/zlib.ts:29-34
-  hp[1] = 0x9C;
+  uint8_t *head = g.pinned->head, *tail = g.pinned->tail;
+  head[0] = 0x78;  // src/zlib.ts:29-34
+  head[1] = 0x9C;
   const uint32_t ad = (uint32_t)((s2 << 16) | s1);
-  for (int k = 0; k < 4; k++) hp[8 + k] = (uint8_t)(ad >> (24 - 8 * k));  // big-endian trailer (src/zlib.ts:37-40)
-  HIPCHK(hipMemcpyAsync(d_out, hp, 2, hipMemcpyHostToDevice, g.stream));
-  HIPCHK(hipMemcpyAsync(d_out + raw_end, hp + 8, 4, hipMemcpyHostToDevice, g.stream));
+  for (int k = 0; k < 4; k++) tail[k] = (uint8_t)(ad >> (24 - 8 * k));  // big-endian trailer (src/zlib.ts:37-40)
+  HIPCHK(hipMemcpyAsync(d_out, head, 2, hipMemcpyHostToDevice, g.stream));
+  HIPCHK(hipMemcpyAsync(d_out + raw_end, tail, 4, hipMemcpyHostToDevice, g.stream));
   HIPCHK(hipStreamSynchronize(g.stream));
   collect_times();
   return ZES_OK;
@@ -3448,8 +3541,6 @@ int zes_adler32(const uint8_t* in, uint64_t n, uint32_t* adler_out) {
 }
 
 // ---- CRC-32 (zes_crc.hip) ----
-static uint32_t* crc_pin() { return (uint32_t*)((uint8_t*)g.pinned + 240 * 1024); }  // (read-back area, clear of the others)
-
 // the kernel's table, holding the chunk powers an n-byte input needs
 static int crc_ready(uint64_t n) {
   const uint64_t nch = (n + CRC_CHUNK - 1) / CRC_CHUNK;
@@ -3469,7 +3560,7 @@ static int crc_ready(uint64_t n) {
   return ZES_OK;
 }
 
-// k_crc32 over d[0, n) on `st`, the two accumulator words on their way to crc_pin(); crc_finish() once st is synchronised
+// k_crc32 over d[0, n) on `st`, the two accumulator words on their way to the area's crc; crc_finish() once st is synchronised
 static int crc_enqueue(const uint8_t* d, uint64_t n, hipStream_t st) {
   int rc;
   if ((rc = crc_ready(n))) return rc;
@@ -3480,13 +3571,13 @@ static int crc_enqueue(const uint8_t* d, uint64_t n, hipStream_t st) {
     hipLaunchKernelGGL(k_crc32, dim3((uint32_t)((n + CRC_CHUNK - 1) / CRC_CHUNK)), dim3(CRC_THREADS), 0, st, d, n, (const uint32_t*)g.crctab.p,
                        (unsigned int*)g.crcacc.p);
   }
-  HIPCHK(hipMemcpyAsync(crc_pin(), g.crcacc.p, 8, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipMemcpyAsync(g.pinned->crc, g.crcacc.p, 8, hipMemcpyDeviceToHost, st));
   return ZES_OK;
 }
 
 // word 0 holds the chunks before the last one, shifted to the last chunk's start; word 1 the last chunk
 static uint32_t crc_finish(uint64_t n) {
-  const uint32_t* a = crc_pin();
+  const uint32_t* a = g.pinned->crc;
   const uint64_t last = n ? n - ((n - 1) / CRC_CHUNK) * CRC_CHUNK : 0;
   const uint32_t raw = zes_crc_shift(a[0], last) ^ a[1];
   return raw ^ zes_crc_shift(0xFFFFFFFFu, n) ^ 0xFFFFFFFFu;
@@ -3566,13 +3657,12 @@ int zes_gzip_dev(const uint8_t* d_in, uint64_t n, uint8_t* d_out, uint64_t cap, 
   if ((rc = gzip_core(d_in, n, &rl, &crc))) return rc;
   *out_len = rl + 18;
   if (rl + 18 > cap) return ZES_E_NOSPACE;
-  uint8_t* hp = (uint8_t*)g.pinned + 248 * 1024;
-  memcpy(hp, kGzHeader, 10);
-  put_le32(hp + 16, crc);
-  put_le32(hp + 20, (uint32_t)n);
+  memcpy(g.pinned->head, kGzHeader, 10);
+  put_le32(g.pinned->tail, crc);
+  put_le32(g.pinned->tail + 4, (uint32_t)n);
   HIPCHK(hipMemcpyAsync(d_out + 10, (const uint8_t*)g.st_out.p + 2, rl, hipMemcpyDeviceToDevice, g.stream));
-  HIPCHK(hipMemcpyAsync(d_out, hp, 10, hipMemcpyHostToDevice, g.stream));
-  HIPCHK(hipMemcpyAsync(d_out + 10 + rl, hp + 16, 8, hipMemcpyHostToDevice, g.stream));
+  HIPCHK(hipMemcpyAsync(d_out, g.pinned->head, 10, hipMemcpyHostToDevice, g.stream));
+  HIPCHK(hipMemcpyAsync(d_out + 10 + rl, g.pinned->tail, 8, hipMemcpyHostToDevice, g.stream));
   HIPCHK(hipStreamSynchronize(g.stream));
   return ZES_OK;
 }
