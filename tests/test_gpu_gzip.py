@@ -102,6 +102,17 @@ def test_crc32_kernel_is_timed(z, gpu):
     assert "k_crc32" in names
 
 
+def test_pool_bytes_counts_what_trim_gives_back(z, gpu):
+    """zes_pool_bytes is "what zes_trim would give back" (include/zes.h): the CRC-32 pools are freed by trim, so they count."""
+    a = dev(np.arange(1 << 20, dtype=np.uint32).view(np.uint8), gpu)  # 4 MiB
+    z.trim()
+    assert z.pool_bytes() == 0
+    z.crc32_tensor(a)
+    assert z.pool_bytes() > 0
+    z.trim()
+    assert z.pool_bytes() == 0
+
+
 # ---------------------------------------------------------------------------------------------
 # gzip writer
 # ---------------------------------------------------------------------------------------------

@@ -1,14 +1,16 @@
 #!/bin/bash
 # tools/build_variant.sh NAME "-DFLAG ..." — development build of the library with extra flags: zlib.es_amd/libzes_NAME.so
-# (use with ZES_LIB=zlib.es_amd/libzes_NAME.so; *.so is git-ignored but travels with gpurun)
+# (use with ZES_LIB=zlib.es_amd/libzes_NAME.so; *.so is git-ignored)
+# Built by csrc/Makefile itself (its sources, its flags), run in a fresh object directory so that the product build's
+# objects stay as they are; the extra flags ride on the compiler command.
 set -e
-cd "$(dirname "$0")/../zlib.es_amd/csrc"
+root="$(cd "$(dirname "$0")/.." && pwd)"
+src=$root/zlib.es_amd/csrc
 name=$1; shift
-mkdir -p /tmp/zesv_$name
-for f in zes_api zes_deflate zes_index zes_inflate zes_inflate_par; do
-  /opt/rocm/bin/hipcc -O3 -fPIC -std=c++17 --offload-arch=gfx950 -Wall -Wno-unused-function $@ -c $f.hip -o /tmp/zesv_$name/$f.o &
-done
-wait
-gcc -O2 -fPIC -c zes_gen.c -o /tmp/zesv_$name/zes_gen.o
-/opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o ../libzes_$name.so /tmp/zesv_$name/*.o
+obj=$(mktemp -d)
+trap 'rm -rf "$obj"' EXIT
+# (vpath by pattern, sources and headers only: a plain VPATH would also find the product build's objects in csrc/,
+# newer than their sources, and link those without compiling anything)
+make -s -j8 -C "$obj" -f "$src/Makefile" --eval "vpath %.hip $src" --eval "vpath %.c $src" --eval "vpath %.h $src" \
+  HIPCC="/opt/rocm/bin/hipcc $*" OUT="$root/zlib.es_amd/libzes_$name.so"
 echo built zlib.es_amd/libzes_$name.so
