@@ -272,6 +272,19 @@ int zes_stage_lz77_dev(const uint8_t* d_in, uint64_t n, uint64_t start, uint32_t
 /* replaces: the code-length half of generateDeflateHuffmanTable src/huffman.ts:55-115.
  * hist[nsym] symbol counts → lens[nsym] code lengths (0 = unused), limit maxlen (15 or 7). */
 int zes_stage_huff_lengths_dev(const uint32_t* h_hist, uint32_t nsym, uint32_t maxlen, uint8_t* h_lens);
+/* The block-parallel inflate tier's acceptance rule (csrc/zes_chain.h) on one buffer's candidate records
+ * given as host arrays: candidate k's block starts at bit start_bit[k] (>= 16, strictly ascending), ended at end_bit[k],
+ * gave out_len[k] bytes, flags[k] bit 0 = decoded, bit 1 = final.  count: candidates found (the arrays' length); cap: the
+ * entries the buffer's list holds; first_bit: where the stream's first block starts.
+ * on_device = 0: decided by the function a one-buffer call decides with; no device is touched.  != 0: the records go up
+ * and k_inf_chain decides, as for a buffer of a batch.
+ * *status: 0 accepted, 2 accepted with the slots behind a false candidate shifted, 1 declined (count 0 or above cap
+ * included); *total: the chain's bytes; *aux: status 0 the closing candidate + 1, status 2 the chain's length; map[0, *aux)
+ * (room for min(count, cap) entries): the candidate of every chain member.
+ * ZES_E_ARG: a null array with count != 0, start bits out of order, count or cap above 1048576.
+ * replaces: nothing (the reference decodes serially). */
+int zes_stage_chain(const uint32_t* start_bit, const uint64_t* end_bit, const uint32_t* out_len, const uint32_t* flags, uint32_t count,
+                    uint32_t cap, uint32_t first_bit, int on_device, int32_t* status, uint64_t* total, uint32_t* aux, uint32_t* map);
 
 /* Checks, on the device this context drives, the hardware behaviour k_lz_sort's stable ranks rest on: lanes of one
  * wavefront whose returning LDS add (ds_add_rtn_u32) meets in one word receive their old values in ascending lane order.

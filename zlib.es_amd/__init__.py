@@ -123,6 +123,7 @@ def lib():
         L.zes_deflate_join_dev.argtypes = [C.POINTER(C.c_void_p), u64p, u32p, u64p, C.c_uint32, C.c_void_p, C.c_uint64, u64p]
         L.zes_stage_lz77_dev.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint32, C.c_void_p, u32p]
         L.zes_stage_huff_lengths_dev.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]
+        L.zes_stage_chain.argtypes = [u32p, u64p, u32p, u32p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, i32p, u64p, u32p, u32p]
         L.zes_selftest_lds_order.argtypes = [C.c_uint32, C.c_uint32, u64p, u64p]
         L.zes_last_kernel_times.argtypes = [C.POINTER(ZesKTime), C.c_int]
         L.zes_set_profiling.argtypes = [C.c_int]
@@ -625,3 +626,20 @@ def stage_huff_lengths(hist, maxlen):
     if rc:
         _raise(rc)
     return lens
+
+
+def stage_chain(records, cap, first_bit=16, on_device=False):
+    """zes_stage_chain: T1's acceptance rule on candidate records [(start_bit, end_bit, out_len, flags), ...], decided on
+    the host (no GPU needed) or by k_inf_chain.
+    Returns (status, total, aux, chain): 0 accepted / 2 accepted, slots shifted / 1 declined (chain then [])."""
+    n = len(records)
+    cols = [np.ascontiguousarray([r[i] for r in records], dtype=dt) for i, dt in enumerate((np.uint32, np.uint64, np.uint32, np.uint32))]
+    chain = np.zeros(max(n, 1), dtype=np.uint32)
+    status, total, aux = C.c_int32(), C.c_uint64(), C.c_uint32()
+    u64p, u32p = C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)
+    ptr = lambda a, t: a.ctypes.data_as(t) if n else None
+    rc = lib().zes_stage_chain(ptr(cols[0], u32p), ptr(cols[1], u64p), ptr(cols[2], u32p), ptr(cols[3], u32p), n, int(cap), int(first_bit),
+                               1 if on_device else 0, C.byref(status), C.byref(total), C.byref(aux), chain.ctypes.data_as(u32p))
+    if rc:
+        _raise(rc)
+    return int(status.value), int(total.value), int(aux.value), [int(x) for x in chain[: aux.value]] if status.value != 1 else []

@@ -5,6 +5,7 @@
 // No CPU fallback exists here: every compute entry point needs a working gfx950 device and returns ZES_E_DEVICE otherwise.
 #include "../../include/zes.h"
 #include "zes_kernels.h"
+#include "zes_chain.h"
 
 #include <algorithm>
 #include <atomic>
@@ -976,9 +977,8 @@ bool t1_eligible(const InfJob& j, uint32_t flags) { return !(flags & (ZES_F_NO_F
 // code-length symbols: nearly all survivors end there) and k_inf_verify_long (a wave per survivor still alive: the
 // real headers, ~300 symbols each).  `total_c`: compressed bytes behind the survivors (sizes the grids).
 int launch_verify(const uint8_t* d_in, const ZesInfBuf* dbufs, uint32_t surv_cap, uint32_t* counters, uint32_t* cnt, uint32_t loose,
-                  uint64_t total_c, uint32_t div) {
+                  uint64_t total_c) {
   int rc;
-  (void)div;
   // the list of the long pass: one survivor in ~350 bytes of stream, one in eight of them listed; ten times that
   const uint32_t vlong_cap = (uint32_t)std::min<uint64_t>(total_c / 256 + 4096, surv_cap);
   if ((rc = ensure(g.vlong, (size_t)vlong_cap * 24))) return rc;
@@ -1062,373 +1062,406 @@ int print_par_phases(const unsigned long long* dbg, uint64_t work) {
     return ZES_OK;
 }
 
-// T1 over a group of buffers: every launch covers all of them (scan, verify, sort, one decode work
-// item per candidate block, chain check), two host synchronisations for the whole group.  Jobs the
-// tier settles get tier = 1; the others are left for the per-buffer tiers.
-int inflate_t1_group(const uint8_t* d_in, uint8_t* d_out, InfJob* jobs, const uint32_t* ids, uint32_t nbuf, bool check_first, uint32_t flags) {
+// The block-parallel tier's launches, each spelled out once.
+// The search of a table of buffers for block starts: k_inf_scan (the cheap tests at every bit position; the survivors go
+// to g.surv, so whatever a later call knew about that list is void) and the header test.  Which rules the two apply:
+struct SearchMode { uint32_t scan, loose; };
+// T1 looks for the reference's own blocks (ZES_F_LOOSE_CANDIDATES: for headers any encoder writes)
+SearchMode t1_search_mode(uint32_t flags) { return (flags & ZES_F_LOOSE_CANDIDATES) ? SearchMode{1u, 1u} : SearchMode{2u, 0u}; }
+// T2: other encoders do not follow the reference's run-length rules for code lengths: loose candidates (the BFINAL rule
+// of the scan holds for every encoder's streams: it stays on; only the verify rules are the reference's own)
+constexpr SearchMode T2_SEARCH = {0u, 1u};
+int launch_search(const uint8_t* d_in, const ZesInfBuf* dbufs, uint32_t nbuf, uint32_t chunks, uint32_t surv_cap, uint32_t* counters,
+                  uint32_t* cnt, uint8_t* first, SearchMode mode, uint64_t total_c) {
+  {
+    Timed t("k_inf_scan");
+    g.sv_ok = false;
+    hipLaunchKernelGGL(k_inf_scan, dim3(chunks), dim3(INF_SCAN_THREADS), 0, g.stream, d_in, dbufs, nbuf, (unsigned long long*)g.surv.p,
+                       surv_cap, counters, first, mode.scan, (const uint8_t*)g.kraft.p);
+  }
+  return launch_verify(d_in, dbufs, surv_cap, counters, cnt, mode.loose, total_c);
+}
+// The block decoder over `items` work items of the table's buffers (two: the variant whose transfer tables look at two
+// windows, for compressible data).  redo null: the first decode, a work item per candidate — every item finds its own
+// rank in the unsorted list and leaves the sorted one for the chain check.  redo set: chain members decoded again into
+// their own slots, work item -> slot through redo[], slot -> candidate through the chain kernel's map.
+void launch_block_par(const char* name, bool two, uint32_t items, const uint8_t* d_in, uint8_t* d_out, const ZesInfBuf* dbufs, uint32_t nbuf,
+                      const uint32_t* cnt, unsigned long long* dbg, const uint32_t* redo, const ZesParMirror& mir) {
+  Timed t(name);
+  hipLaunchKernelGGL(two ? k_inf_block_par2 : k_inf_block_par, dim3(items), dim3(PAR_THREADS), 0, g.stream, d_in, d_out, dbufs, nbuf, cnt,
+                     (const uint32_t*)g.cand_sorted.p, redo ? (const uint32_t*)g.map.p : nullptr, (ZesCandRes*)g.cres.p, dbg, redo,
+                     redo ? nullptr : (const uint32_t*)g.cand.p, redo ? nullptr : (uint32_t*)g.cand_sorted.p, mir);
+}
+
+// scratch of a T1 search + decode over nbuf buffers with room for `cands` candidates in all
+int t1_pools(uint32_t nbuf, uint32_t surv_cap, uint64_t cands, size_t counter_bytes, uint32_t nres) {
   int rc;
-  g.sv_ok = false;  // (g.surv is about to be rewritten)
-  ZesInfBuf* hb = g.pinned->t1.table;
-  uint64_t chunks = 0, cands = 0, total_c = 0;
-  for (uint32_t i = 0; i < nbuf; i++) {
-    const InfJob& j = jobs[ids[i]];
-    ZesInfBuf& b = hb[i];
-    b.in_off = j.in_off;
-    b.c = j.c;
-    b.out_off = j.out_off;
-    b.cap = j.cap;
-    b.first_chunk = (uint32_t)chunks;
-    b.cand_base = (uint32_t)cands;
-    // a reference-made stream has one block per 131072 bytes of output: more candidates than the caller's capacity
-    // has blocks (plus room for false ones) means another encoder wrote the stream — counted as an overflow, and the
-    // sort never sees more than this many (a zlib stream with 250-byte blocks has 250 000 of them)
-    b.cand_cap = (uint32_t)std::min<uint64_t>(j.c / 64 + 64, j.cap / ZES_BLK + 65);
-    b.work_first = 0;
-    b.start_rel = 0;
-    b.own_rel = 0xFFFFFFFFu;
-    b.range_flags = 0;
-    b.pad = 0;
-    chunks += (j.c + INF_SCAN_BYTES - 1) / INF_SCAN_BYTES;
-    cands += b.cand_cap;
-    total_c += j.c;
-  }
-  if (chunks >= (1ull << 31) || cands >= (1ull << 31)) return ZES_OK;  // leave the jobs to the per-buffer tiers
-  memset(&hb[nbuf], 0, sizeof(ZesInfBuf));
-  hb[nbuf].first_chunk = (uint32_t)chunks;
-  hb[nbuf].cand_base = (uint32_t)cands;
-  if (nbuf == 1) {  // see the single-synchronisation path below
-    hb[1].work_first = ZES_WORK_AUTO;
-    hb[1].cand_cap = hb[0].cand_cap;
-  }
-  const uint32_t surv_cap = (uint32_t)std::min<uint64_t>(total_c / 4 + 1024ull * nbuf, 1ull << 30);
-  const size_t cnt_bytes = t1_cnt_bytes(nbuf);
   if ((rc = ensure(g.ibufs, sizeof(ZesInfBuf) * (nbuf + 1)))) return rc;
   if ((rc = ensure(g.surv, (size_t)surv_cap * 8))) return rc;
   if ((rc = ensure(g.cand, (size_t)cands * 4))) return rc;
   if ((rc = ensure(g.cand_sorted, (size_t)cands * 4))) return rc;
   if ((rc = ensure(g.cres, sizeof(ZesCandRes) * cands))) return rc;
-  if ((rc = ensure(g.map, (size_t)cands * 4))) return rc;
-  if ((rc = ensure(g.counters, cnt_bytes))) return rc;
-  if ((rc = ensure(g.res, sizeof(ZesRes) * nbuf))) return rc;
-  const ZesInfBuf* dbufs = (const ZesInfBuf*)g.ibufs.p;
-  uint32_t* counters = (uint32_t*)g.counters.p;
-  uint32_t* cnt = counters + 4;
-  uint8_t* dfirst = (uint8_t*)(cnt + nbuf);
-  if (nbuf == 1) {  // table and cleared counters straight from kernel arguments
-    hipLaunchKernelGGL(k_inf_set_table1, dim3(1), dim3(64), 0, g.stream, hb[0], hb[1], (ZesInfBuf*)g.ibufs.p, counters,
-                       (uint32_t)(cnt_bytes / 4));
-  } else {
-    HIPCHK(hipMemcpyAsync(g.ibufs.p, hb, sizeof(ZesInfBuf) * (nbuf + 1), hipMemcpyHostToDevice, g.stream));
-    HIPCHK(hipMemsetAsync(g.counters.p, 0, cnt_bytes, g.stream));
-  }
-  {
-    Timed t("k_inf_scan");
-    hipLaunchKernelGGL(k_inf_scan, dim3((uint32_t)chunks), dim3(INF_SCAN_THREADS), 0, g.stream, d_in, dbufs, nbuf,
-                       (unsigned long long*)g.surv.p, surv_cap, counters, dfirst, (flags & ZES_F_LOOSE_CANDIDATES) ? 1u : 2u,
-                       (const uint8_t*)g.kraft.p);
-  }
-  // (k_inf_verify, measured on 64 MiB: 8192 workgroups 0.33 ms, 2048 0.26 ms, 512 0.36 ms — about one survivor in 256 input
-  // bytes, and a lane should get a few of them)
-  if ((rc = launch_verify(d_in, dbufs, surv_cap, counters, cnt, (flags & ZES_F_LOOSE_CANDIDATES) ? 1u : 0u, total_c, 32768))) return rc;
-  // One buffer: nothing has to come back before the decode is launched.  The grid is sized for the most
-  // blocks the caller's capacity can hold (plus room for false candidates); the kernels take the real
-  // candidate count from device memory (table sentinel ZES_WORK_AUTO) and the host reads counters and
-  // result together — one synchronisation per call.  Several buffers: the counts come back first.
-  const bool one = nbuf == 1;
-  uint32_t* hc = g.pinned->t1.counters;
-  ZesRes* hres = g.pinned->t1.res;
-  uint64_t work = 0;
-  std::vector<uint32_t> ncand(nbuf);
-  if (!one) {
-    HIPCHK(hipMemcpyAsync(hc, g.counters.p, cnt_bytes, hipMemcpyDeviceToHost, g.stream));
-    HIPCHK(hipStreamSynchronize(g.stream));  // the table upload has completed too: hb may be rewritten
-    for (uint32_t i = 0; i < nbuf; i++) {
-      const uint8_t fb = ((const uint8_t*)(hc + 4 + nbuf))[i];
-      if (fb & 0x40u) jobs[ids[i]].btype0 = (fb >> 4) & 3;
-    }
-    if (check_first) {  // CM nibble of the first byte (src/zlib.ts:13-16): the scan kernel sent it along
-      const uint8_t* hfirst = (const uint8_t*)(hc + 4 + nbuf);
-      for (uint32_t i = 0; i < nbuf; i++)
-        if ((hfirst[i] & 15u) != 8u) {
-          jobs[ids[i]].status = ZES_E_NOT_DEFLATE;
-          jobs[ids[i]].tier = -1;
-          hc[4 + i] = 0;  // no candidates are looked at
-        }
-    }
-    const uint32_t nsurv0 = hc[0];
-    if (nsurv0 == 0 || nsurv0 > surv_cap) return ZES_OK;  // nothing that looks like this format (or a poisoned count)
-    for (uint32_t i = 0; i < nbuf; i++) {
-      ncand[i] = hc[4 + i];
-      hb[i].work_first = (uint32_t)work;
-      if (ncand[i] > 0 && ncand[i] <= hb[i].cand_cap) work += ncand[i];
-    }
-    hb[nbuf].work_first = (uint32_t)work;
-    if (work == 0) return ZES_OK;
-    HIPCHK(hipMemcpyAsync(g.ibufs.p, hb, sizeof(ZesInfBuf) * (nbuf + 1), hipMemcpyHostToDevice, g.stream));
-  } else {
-    work = hb[1].cand_cap;  // the launch bound written into the sentinel above
-  }
-  bool direct = false, hostchain = false;
-  ZesParMirror mir{};
+  if ((rc = ensure(g.counters, counter_bytes))) return rc;
+  return ensure(g.res, sizeof(ZesRes) * nres);
+}
+
+// T1's verdict on one buffer taken on the host: zes_chain.h's rule — k_inf_chain's — on what the block decoder left in
+// page-locked memory (start[k] = the bit candidate k's block starts at, rank order; hc: the search's counters, survivors
+// in word 0, candidates in word 4; b: the buffer's table entry; work: work items launched).  map: see zes_chain_decide.
+ZesRes t1_host_chain(const uint32_t* start, const ZesCandRes* cres, const uint32_t* hc, uint32_t surv_cap, const ZesInfBuf& b, uint64_t work,
+                     uint32_t* map) {
+  const ZesChainView v = {start, cres, std::min(hc[4], b.cand_cap), 0u};
+  // (no survivors: nothing that looks like this format; more than the list holds: a poisoned count)
+  const uint32_t nwork = hc[0] != 0 && hc[0] <= surv_cap ? (uint32_t)std::min<uint64_t>(v.n, work) : 0u;
+  return zes_chain_decide(v, hc[4], b.cand_cap, nwork, 16u + (uint64_t)b.start_rel, map);
+}
+
+// T1 over a group of buffers: every launch covers all of them (scan, verify, sort, one decode work
+// item per candidate block, chain check), two host synchronisations for the whole group.  Jobs the
+// tier settles get tier = 1; the others are left for the per-buffer tiers.
+struct T1Group {  // the group between the steps of inflate_t1_group
+  const uint8_t* d_in;
+  uint8_t* d_out;
+  InfJob* jobs;
+  const uint32_t* ids;
+  uint32_t nbuf, flags;
+  bool check_first, one;  // one buffer: one synchronisation per call (t1_decode)
+  ZesInfBuf* hb;          // page-locked: the table, ...
+  uint32_t* hc;           // ... the search's counters, ...
+  ZesRes* hres;           // ... the chain results
+  uint64_t chunks = 0, cands = 0, total_c = 0, work = 0;  // work: work items launched
+  uint32_t surv_cap = 0;
+  size_t cnt_bytes = 0;
+  const ZesInfBuf* dbufs = nullptr;
+  uint32_t *counters = nullptr, *cnt = nullptr;
   unsigned long long* dbg = nullptr;
+  bool hostchain = false;  // the host walks the chain (t1_decode decides)
+  std::vector<uint32_t> ncand;
+  std::vector<ZesRes> r1;  // every buffer's verdict
+};
+// a step's answer beside ZES_OK and an error: nothing more for this tier, what it has not settled goes to the per-buffer tiers
+constexpr int T1_OVER = 1;
+
+// what the scan sent along of buffer i's first byte: the BTYPE of the block at bit 16 and the CM nibble (src/zlib.ts:13-16).
+// true: not a deflate stream, the job is settled
+bool t1_first_byte(T1Group& t, uint32_t i, uint8_t fb) {
+  InfJob& j = t.jobs[t.ids[i]];
+  if (fb & 0x40u) j.btype0 = (fb >> 4) & 3;
+  if (!t.check_first || (fb & 15u) == 8u) return false;
+  j.status = ZES_E_NOT_DEFLATE;
+  j.tier = -1;
+  return true;
+}
+
+// step 1: the table of buffers, the pools sized for it, both on their way to the device
+int t1_table(T1Group& t) {
+  int rc;
+  g.sv_ok = false;  // (g.surv is about to be rewritten)
+  ZesInfBuf* hb = t.hb;
+  for (uint32_t i = 0; i < t.nbuf; i++) {
+    const InfJob& j = t.jobs[t.ids[i]];
+    ZesInfBuf& b = hb[i];
+    memset(&b, 0, sizeof b);
+    b.in_off = j.in_off;
+    b.c = j.c;
+    b.out_off = j.out_off;
+    b.cap = j.cap;
+    b.first_chunk = (uint32_t)t.chunks;
+    b.cand_base = (uint32_t)t.cands;
+    // a reference-made stream has one block per 131072 bytes of output: more candidates than the caller's capacity
+    // has blocks (plus room for false ones) means another encoder wrote the stream — counted as an overflow, and the
+    // sort never sees more than this many (a zlib stream with 250-byte blocks has 250 000 of them)
+    b.cand_cap = (uint32_t)std::min<uint64_t>(j.c / 64 + 64, j.cap / ZES_BLK + 65);
+    b.own_rel = 0xFFFFFFFFu;
+    t.chunks += (j.c + INF_SCAN_BYTES - 1) / INF_SCAN_BYTES;
+    t.cands += b.cand_cap;
+    t.total_c += j.c;
+  }
+  if (t.chunks >= (1ull << 31) || t.cands >= (1ull << 31)) return T1_OVER;  // leave the jobs to the per-buffer tiers
+  const uint32_t nbuf = t.nbuf;
+  memset(&hb[nbuf], 0, sizeof(ZesInfBuf));
+  hb[nbuf].first_chunk = (uint32_t)t.chunks;
+  hb[nbuf].cand_base = (uint32_t)t.cands;
+  if (t.one) {  // see t1_decode
+    hb[1].work_first = ZES_WORK_AUTO;
+    hb[1].cand_cap = hb[0].cand_cap;
+  }
+  t.surv_cap = (uint32_t)std::min<uint64_t>(t.total_c / 4 + 1024ull * nbuf, 1ull << 30);
+  t.cnt_bytes = t1_cnt_bytes(nbuf);
+  if ((rc = t1_pools(nbuf, t.surv_cap, t.cands, t.cnt_bytes, nbuf))) return rc;
+  if ((rc = ensure(g.map, (size_t)t.cands * 4))) return rc;
+  t.dbufs = (const ZesInfBuf*)g.ibufs.p;
+  t.counters = (uint32_t*)g.counters.p;
+  t.cnt = t.counters + 4;
+  if (t.one) {  // table and cleared counters straight from kernel arguments
+    hipLaunchKernelGGL(k_inf_set_table1, dim3(1), dim3(64), 0, g.stream, hb[0], hb[1], (ZesInfBuf*)g.ibufs.p, t.counters,
+                       (uint32_t)(t.cnt_bytes / 4));
+  } else {
+    HIPCHK(hipMemcpyAsync(g.ibufs.p, hb, sizeof(ZesInfBuf) * (nbuf + 1), hipMemcpyHostToDevice, g.stream));
+    HIPCHK(hipMemsetAsync(g.counters.p, 0, t.cnt_bytes, g.stream));
+  }
+  return ZES_OK;
+}
+
+// step 3: a decode work item per candidate.
+// One buffer: nothing has to come back before the decode is launched.  The grid is sized for the most
+// blocks the caller's capacity can hold (plus room for false candidates); the kernels take the real
+// candidate count from device memory (table sentinel ZES_WORK_AUTO) and the host reads counters and
+// result together — one synchronisation per call.  Several buffers: the counts come back first.
+int t1_decode(T1Group& t) {
+  int rc;
+  const uint32_t nbuf = t.nbuf;
+  ZesInfBuf* hb = t.hb;
+  uint32_t* hc = t.hc;
+  if (!t.one) {
+    HIPCHK(hipMemcpyAsync(hc, g.counters.p, t.cnt_bytes, hipMemcpyDeviceToHost, g.stream));
+    HIPCHK(hipStreamSynchronize(g.stream));  // the table upload has completed too: hb may be rewritten
+    const uint8_t* hfirst = (const uint8_t*)(hc + 4 + nbuf);
+    for (uint32_t i = 0; i < nbuf; i++)
+      if (t1_first_byte(t, i, hfirst[i])) hc[4 + i] = 0;  // no candidates are looked at
+    const uint32_t nsurv0 = hc[0];
+    if (nsurv0 != 0 && nsurv0 <= t.surv_cap)  // (else: nothing that looks like this format, or a poisoned count)
+      for (uint32_t i = 0; i < nbuf; i++) {
+        t.ncand[i] = hc[4 + i];
+        hb[i].work_first = (uint32_t)t.work;
+        if (t.ncand[i] > 0 && t.ncand[i] <= hb[i].cand_cap) t.work += t.ncand[i];
+      }
+    hb[nbuf].work_first = (uint32_t)t.work;
+    if (t.work == 0) return T1_OVER;
+    HIPCHK(hipMemcpyAsync(g.ibufs.p, hb, sizeof(ZesInfBuf) * (nbuf + 1), hipMemcpyHostToDevice, g.stream));
+  } else {
+    t.work = hb[1].cand_cap;  // the launch bound written into the sentinel
+  }
   if (getenv("ZES_DEBUG_PHASES")) {
-    if ((rc = ensure(g.dbg, (size_t)work * ZES_PAR_DBG_ROW * 8))) return rc;
-    HIPCHK(hipMemsetAsync(g.dbg.p, 0, (size_t)work * ZES_PAR_DBG_ROW * 8, g.stream));
-    dbg = (unsigned long long*)g.dbg.p;
+    if ((rc = ensure(g.dbg, (size_t)t.work * ZES_PAR_DBG_ROW * 8))) return rc;
+    HIPCHK(hipMemsetAsync(g.dbg.p, 0, (size_t)t.work * ZES_PAR_DBG_ROW * 8, g.stream));
+    t.dbg = (unsigned long long*)g.dbg.p;
   }
-  // (the candidates are ranked by the block decoder itself: every work item finds its own rank and the two candidates
-  // behind it in the unsorted list, and leaves the sorted list for the chain check)
-  {
-    // compressible data (the streams are shorter than 0.7 of the room for their outputs): the variant whose transfer
-    // tables look at two windows; incompressible data runs ~4 % faster in the smaller kernel
-    uint64_t total_cap = 0;
-    for (uint32_t i = 0; i < nbuf; i++) total_cap += jobs[ids[i]].cap;
-    const bool two = total_c * 10 < total_cap * 7;
-    Timed t(two ? "k_inf_block_par2" : "k_inf_block_par");
-    auto kern = two ? k_inf_block_par2 : k_inf_block_par;
-    // One buffer and a launch bound the mirror area holds: every work item also puts its result and its block's start bit
-    // into page-locked host memory, work item 0 the counters, and the HOST follows the chain after the one synchronisation —
-    // what k_inf_chain does, on a few hundred 16-byte records: no chain kernel behind this one (11 us + a kernel boundary of
-    // a 0.8 ms call).  Only a chain that needs the slots moved (false candidates between the blocks) still runs that kernel,
-    // for its map.
-    if (one && work <= MIRROR_ITEMS && g.mirror_dev && g.pinned_dev) {
-      mir.cres_host = g.mirror_dev->cres;
-      mir.start_host = g.mirror_dev->start;
-      mir.counters = counters;
-      mir.counters_host = g.pinned_dev->t1.counters;
-      mir.counter_words = (uint32_t)(cnt_bytes / 4);
-      hostchain = true;
-    }
-    hipLaunchKernelGGL(kern, dim3((uint32_t)work), dim3(PAR_THREADS), 0, g.stream, d_in, d_out, dbufs, nbuf,
-                       (const uint32_t*)cnt, (const uint32_t*)g.cand_sorted.p, (const uint32_t*)nullptr, (ZesCandRes*)g.cres.p, dbg, (const uint32_t*)nullptr,
-                       (const uint32_t*)g.cand.p, (uint32_t*)g.cand_sorted.p, mir);
+  // compressible data (the streams are shorter than 0.7 of the room for their outputs): the variant whose transfer
+  // tables look at two windows; incompressible data runs ~4 % faster in the smaller kernel
+  uint64_t total_cap = 0;
+  for (uint32_t i = 0; i < nbuf; i++) total_cap += t.jobs[t.ids[i]].cap;
+  const bool two = t.total_c * 10 < total_cap * 7;
+  // One buffer and a launch bound the mirror area holds: every work item also puts its result and its block's start bit
+  // into page-locked host memory, work item 0 the counters, and the HOST follows the chain after the one synchronisation —
+  // what k_inf_chain does, on a few hundred 16-byte records: no chain kernel behind this one (11 us + a kernel boundary of
+  // a 0.8 ms call).  Only a chain that needs the slots moved (false candidates between the blocks) still runs that kernel,
+  // for its map.
+  ZesParMirror mir{};
+  if (t.one && t.work <= MIRROR_ITEMS && g.mirror_dev && g.pinned_dev) {
+    mir.cres_host = g.mirror_dev->cres;
+    mir.start_host = g.mirror_dev->start;
+    mir.counters = t.counters;
+    mir.counters_host = g.pinned_dev->t1.counters;
+    mir.counter_words = (uint32_t)(t.cnt_bytes / 4);
+    t.hostchain = true;
   }
-  auto device_chain = [&]() -> int {
-    Timed t("k_inf_chain");
-    // one buffer: the kernel puts its result and the counters straight into the page-locked read-back area (no copy
-    // commands behind the kernels: ~10 us of a 0.8 ms call)
-    direct = one && g.pinned_dev;
-    hipLaunchKernelGGL(k_inf_chain, dim3(nbuf), dim3(256), 0, g.stream, dbufs, (const uint32_t*)cnt, (const uint32_t*)g.cand_sorted.p,
-                       (const ZesCandRes*)g.cres.p, (const uint32_t*)nullptr, (uint32_t*)g.map.p,
-                       direct ? g.pinned_dev->t1.res : (ZesRes*)g.res.p, (const uint32_t*)counters, (uint32_t)(cnt_bytes / 4),
-                       direct ? g.pinned_dev->t1.counters : (uint32_t*)nullptr);
-    if (!direct) {
-      if (one) HIPCHK(hipMemcpyAsync(hc, g.counters.p, cnt_bytes, hipMemcpyDeviceToHost, g.stream));
-      HIPCHK(hipMemcpyAsync(hres, g.res.p, sizeof(ZesRes) * nbuf, hipMemcpyDeviceToHost, g.stream));
-    }
-    return ZES_OK;
-  };
-  if (!hostchain && (rc = device_chain())) return rc;
+  launch_block_par(two ? "k_inf_block_par2" : "k_inf_block_par", two, (uint32_t)t.work, t.d_in, t.d_out, t.dbufs, nbuf, t.cnt, t.dbg, nullptr, mir);
+  return ZES_OK;
+}
+
+// k_inf_chain over the group, its results on their way to t.hres
+int t1_device_chain(T1Group& t) {
+  Timed tm("k_inf_chain");
+  // one buffer: the kernel puts its result and the counters straight into the page-locked read-back area (no copy
+  // commands behind the kernels: ~10 us of a 0.8 ms call)
+  const bool direct = t.one && g.pinned_dev;
+  hipLaunchKernelGGL(k_inf_chain, dim3(t.nbuf), dim3(256), 0, g.stream, t.dbufs, (const uint32_t*)t.cnt, (const uint32_t*)g.cand_sorted.p,
+                     (const ZesCandRes*)g.cres.p, (const uint32_t*)nullptr, (uint32_t*)g.map.p,
+                     direct ? g.pinned_dev->t1.res : (ZesRes*)g.res.p, (const uint32_t*)t.counters, (uint32_t)(t.cnt_bytes / 4),
+                     direct ? g.pinned_dev->t1.counters : (uint32_t*)nullptr);
+  if (!direct) {
+    if (t.one) HIPCHK(hipMemcpyAsync(t.hc, g.counters.p, t.cnt_bytes, hipMemcpyDeviceToHost, g.stream));
+    HIPCHK(hipMemcpyAsync(t.hres, g.res.p, sizeof(ZesRes) * t.nbuf, hipMemcpyDeviceToHost, g.stream));
+  }
+  return ZES_OK;
+}
+
+// step 4: every buffer's verdict in t.r1, from k_inf_chain or — one buffer — the host's walk on the mirror; behind it
+// the one-buffer call learns what the several-buffer one read back in t1_decode
+int t1_verdicts(T1Group& t) {
+  int rc;
+  uint32_t* hc = t.hc;
+  if (!t.hostchain && (rc = t1_device_chain(t))) return rc;
   host_lap("(work before the block-parallel tier)");
   HIPCHK(hipStreamSynchronize(g.stream));
   host_lap("T1: search + decode + chain");
-  if (hostchain) {
-    // k_inf_chain's walk on the mirror (one buffer; start[k] = the bit candidate k's block starts at, rank order)
-    const ZesCandRes* hcr = g.mirror->cres;
-    const uint32_t* hst = g.mirror->start;
-    ZesRes r;
-    r.status = 1;
-    r.out_len = 0;
-    r.aux = 0;
-    const uint32_t cnt0 = hc[4];
-    const uint32_t nc = std::min(cnt0, hb[0].cand_cap);
-    const uint32_t nwork = std::min<uint32_t>(nc, (uint32_t)work);
-    if (hc[0] != 0 && hc[0] <= surv_cap && nc != 0 && cnt0 <= hb[0].cand_cap && nc <= nwork && hst[0] == 16u + hb[0].start_rel) {
-      uint32_t K = 0xFFFFFFFFu;
-      for (uint32_t k = 0; k < nwork; k++)
-        if ((hcr[k].flags & 3u) == 3u) {
-          K = k;
-          break;
-        }
-      bool fast = K != 0xFFFFFFFFu;
-      uint64_t total = 0;
-      for (uint32_t k = 0; fast && k <= K; k++) {
-        const ZesCandRes& c = hcr[k];
-        if (!(c.flags & 1u)) fast = false;
-        total += c.out_len;
-        if (k < K && (c.out_len != ZES_BLK || k + 1 >= nc || (uint64_t)hst[k + 1] != c.end_bit)) fast = false;
-      }
-      if (fast) {
-        r.status = 0;
-        r.out_len = total;
-        r.aux = K + 1;  // (the closing block's candidate, + 1: its end bit is the stream's)
-      } else {  // false candidates between the blocks? follow end bit -> next start
-        uint32_t j = 0, k = 0;
-        total = 0;
-        bool ok = false;
-        for (;;) {
-          const ZesCandRes& c = hcr[j];
-          if (!(c.flags & 1u)) break;
-          k++;
-          total += c.out_len;
-          if (c.flags & 2u) {
-            ok = true;
-            break;
-          }
-          if (c.out_len != ZES_BLK) break;
-          const uint32_t* lo = std::lower_bound(hst + j + 1, hst + nc, (uint64_t)c.end_bit, [](uint32_t a, uint64_t b) { return (uint64_t)a < b; });
-          if (lo == hst + nc || (uint64_t)*lo != c.end_bit) break;
-          j = (uint32_t)(lo - hst);
-        }
-        if (ok) {  // the slots are shifted: the chain kernel's map is needed (rare)
-          if ((rc = device_chain())) return rc;
-          HIPCHK(hipStreamSynchronize(g.stream));
-          r = hres[0];
-          (void)k;
-        }
-      }
+  if (t.hostchain) {
+    ZesRes r = t1_host_chain(g.mirror->start, g.mirror->cres, hc, t.surv_cap, t.hb[0], t.work, nullptr);
+    if (r.status == 2) {  // the slots are shifted: the chain kernel's map is needed (rare)
+      if ((rc = t1_device_chain(t))) return rc;
+      HIPCHK(hipStreamSynchronize(g.stream));
+      r = t.hres[0];
+    } else {
+      t.hres[0] = r;
     }
-    if (r.status != 2) hres[0] = r;
     if (getenv("ZES_DEBUG")) {
-      fprintf(stderr, "zes T1 host chain: nsurv %u cnt %u cap %u work %llu -> status %d out_len %llu | start0 %u", hc[0], hc[4], hb[0].cand_cap,
-              (unsigned long long)work, r.status, (unsigned long long)r.out_len, hst[0]);
+      const ZesCandRes* hcr = g.mirror->cres;
+      const uint32_t* hst = g.mirror->start;
+      fprintf(stderr, "zes T1 host chain: nsurv %u cnt %u cap %u work %llu -> status %d out_len %llu | start0 %u", hc[0], hc[4], t.hb[0].cand_cap,
+              (unsigned long long)t.work, r.status, (unsigned long long)r.out_len, hst[0]);
       for (uint32_t k = 0; k < std::min<uint32_t>(hc[4], 10u); k++)
         fprintf(stderr, " [%u: start %u end %llu len %u fl %u]", k, hst[k], (unsigned long long)hcr[k].end_bit, hcr[k].out_len, hcr[k].flags);
       fprintf(stderr, "\n");
     }
   }
   const uint32_t nsurv = hc[0];
-  if (one) {
-    if (((const uint8_t*)(hc + 5))[0] & 0x40u) jobs[ids[0]].btype0 = (((const uint8_t*)(hc + 5))[0] >> 4) & 3;
-    if (check_first && (((const uint8_t*)(hc + 5))[0] & 15u) != 8u) {  // src/zlib.ts:13-16
-      jobs[ids[0]].status = ZES_E_NOT_DEFLATE;
-      jobs[ids[0]].tier = -1;
-      return ZES_OK;
-    }
-    ncand[0] = hc[4];
-    if (nsurv != 0 && nsurv <= surv_cap && !(flags & ZES_F_LOOSE_CANDIDATES)) {  // the scan ran to its end and its list is whole
+  if (t.one) {
+    const InfJob& j = t.jobs[t.ids[0]];
+    if (t1_first_byte(t, 0, ((const uint8_t*)(hc + 5))[0])) return T1_OVER;
+    t.ncand[0] = hc[4];
+    if (nsurv != 0 && nsurv <= t.surv_cap && !(t.flags & ZES_F_LOOSE_CANDIDATES)) {  // the scan ran to its end and its list is whole
       g.sv_ok = true;
-      g.sv_din = d_in;
+      g.sv_din = t.d_in;
       g.sv_list = g.surv.p;
-      g.sv_in_off = jobs[ids[0]].in_off;
-      g.sv_c = jobs[ids[0]].c;
+      g.sv_in_off = j.in_off;
+      g.sv_c = j.c;
       g.sv_n = nsurv;
     }
     // nothing that looks like this format, a poisoned count, or more candidates than were launched
-    if (nsurv == 0 || nsurv > surv_cap || ncand[0] == 0 || ncand[0] > hb[0].cand_cap || ncand[0] > work) return ZES_OK;
-    hb[0].work_first = 0;
-    work = ncand[0];
+    if (nsurv == 0 || nsurv > t.surv_cap || t.ncand[0] == 0 || t.ncand[0] > t.hb[0].cand_cap || t.ncand[0] > t.work) return T1_OVER;
+    t.hb[0].work_first = 0;
+    t.work = t.ncand[0];
   }
-  std::vector<ZesRes> r1(hres, hres + nbuf);
-  if (dbg && (rc = print_par_phases(dbg, work))) return rc;
+  t.r1.assign(t.hres, t.hres + t.nbuf);
+  if (t.dbg && (rc = print_par_phases(t.dbg, t.work))) return rc;
   if (getenv("ZES_DEBUG")) {
-    for (uint32_t i = 0, shown_b = 0; i < nbuf && shown_b < 4; i++) {
-      if (r1[i].status == 0) continue;
+    for (uint32_t i = 0, shown_b = 0; i < t.nbuf && shown_b < 4; i++) {
+      const ZesRes& r = t.r1[i];
+      if (r.status == 0) continue;
       shown_b++;
-      const uint32_t nc = std::min(ncand[i], hb[i].cand_cap);
-      fprintf(stderr, "zes T1: buf %u c=%llu nsurv(all)=%u ncand=%u chain status=%d aux=%u out_len=%llu\n", ids[i],
-              (unsigned long long)hb[i].c, nsurv, ncand[i], r1[i].status, r1[i].aux, (unsigned long long)r1[i].out_len);
-      if (r1[i].status != 1 || nc == 0) continue;
+      const uint32_t nc = std::min(t.ncand[i], t.hb[i].cand_cap);
+      fprintf(stderr, "zes T1: buf %u c=%llu nsurv(all)=%u ncand=%u chain status=%d aux=%u out_len=%llu\n", t.ids[i],
+              (unsigned long long)t.hb[i].c, nsurv, t.ncand[i], r.status, r.aux, (unsigned long long)r.out_len);
+      if (r.status != 1 || nc == 0) continue;
       std::vector<ZesCandRes> hcr(nc);
       std::vector<uint32_t> hcand(nc);
-      HIPCHK(hipMemcpy(hcr.data(), (const ZesCandRes*)g.cres.p + hb[i].cand_base, sizeof(ZesCandRes) * nc, hipMemcpyDeviceToHost));
-      HIPCHK(hipMemcpy(hcand.data(), (const uint32_t*)g.cand_sorted.p + hb[i].cand_base, 4 * (size_t)nc, hipMemcpyDeviceToHost));
+      HIPCHK(hipMemcpy(hcr.data(), (const ZesCandRes*)g.cres.p + t.hb[i].cand_base, sizeof(ZesCandRes) * nc, hipMemcpyDeviceToHost));
+      HIPCHK(hipMemcpy(hcand.data(), (const uint32_t*)g.cand_sorted.p + t.hb[i].cand_base, 4 * (size_t)nc, hipMemcpyDeviceToHost));
+      const ZesChainView v = {hcand.data(), hcr.data(), nc, 16u};
       int shown = 0;
-      for (uint32_t k = 0; k < nc && shown < 6; k++) {
-        const bool chain_ok = (k + 1 == nc) || ((uint64_t)hcand[k + 1] + 16 == hcr[k].end_bit);
-        if (!(hcr[k].flags & 1u) || !chain_ok || (hcr[k].out_len != ZES_BLK && k + 1 != nc)) {
-          fprintf(stderr, "  cand %u start=%u end_bit=%llu next_start=%u out_len=%u flags=%u\n", k, hcand[k] + 16,
-                  (unsigned long long)hcr[k].end_bit, k + 1 < nc ? hcand[k + 1] + 16 : 0, hcr[k].out_len, hcr[k].flags);
-          shown++;
-        }
+      for (uint32_t k = 0; k < nc && shown < 6; k++) {  // candidates that do not link to the next one (the last: not decoded)
+        if (k + 1 < nc ? zes_chain_link(v, hcr[k], k + 1) : (hcr[k].flags & ZES_CAND_OK) != 0) continue;
+        fprintf(stderr, "  cand %u start=%u end_bit=%llu next_start=%u out_len=%u flags=%u\n", k, (uint32_t)zes_chain_start(v, k),
+                (unsigned long long)hcr[k].end_bit, k + 1 < nc ? (uint32_t)zes_chain_start(v, k + 1) : 0, hcr[k].out_len, hcr[k].flags);
+        shown++;
       }
     }
   }
-  // Buffers whose candidate list holds false positives between the blocks: every true block decoded fine, but
-  // the blocks behind a false candidate sit one (or more) slots too far right.  The chain kernel left the true
-  // chain in map[] (true block k = candidate map[k]) and has checked it block by block, so the blocks only
-  // have to move: through a scratch copy, because sources and destinations overlap.  A block whose slot was cut
-  // off by the caller's capacity (typically the last one) is decoded again, straight into its own slot.
-  for (uint32_t i = 0; i < nbuf; i++) {
-    if (r1[i].status != 2) continue;
-    const uint32_t K = r1[i].aux;
-    InfJob& j = jobs[ids[i]];
-    std::vector<uint32_t> hmap(K);
-    HIPCHK(hipMemcpyAsync(hmap.data(), (const uint32_t*)g.map.p + hb[i].cand_base, (size_t)K * 4, hipMemcpyDeviceToHost, g.stream));
+  return ZES_OK;
+}
+
+// the end bit of the block at index idx of the device's result list
+int cand_end_bit(size_t idx, uint64_t* end_bit) {
+  ZesCandRes last;
+  HIPCHK(hipMemcpy(&last, (const ZesCandRes*)g.cres.p + idx, sizeof last, hipMemcpyDeviceToHost));
+  *end_bit = last.end_bit;
+  return ZES_OK;
+}
+
+// step 5, for a buffer whose candidate list holds false positives between the blocks: every true block decoded fine, but
+// the blocks behind a false candidate sit one (or more) slots too far right.  The chain kernel left the true
+// chain in map[] (true block k = candidate map[k]) and has checked it block by block, so the blocks only
+// have to move: through a scratch copy, because sources and destinations overlap.  A block whose slot was cut
+// off by the caller's capacity (typically the last one) is decoded again, straight into its own slot.
+// r: the buffer's verdict, status 2 -> 0 (repaired) or 1; out_len already holds the chain's total.
+int t1_repair_slots(T1Group& t, uint32_t i, ZesRes& r) {
+  int rc;
+  const ZesInfBuf* hb = t.hb;
+  const uint32_t K = r.aux;
+  InfJob& j = t.jobs[t.ids[i]];
+  std::vector<uint32_t> hmap(K);
+  HIPCHK(hipMemcpyAsync(hmap.data(), (const uint32_t*)g.map.p + hb[i].cand_base, (size_t)K * 4, hipMemcpyDeviceToHost, g.stream));
+  HIPCHK(hipStreamSynchronize(g.stream));
+  if (j.want_end && K && (rc = cand_end_bit(hb[i].cand_base + hmap[K - 1], &j.end_bit))) return rc;
+  std::vector<uint32_t> mv_src, mv_dst, redo;
+  for (uint32_t k = 0; k < K; k++) {
+    if (hmap[k] == k) continue;
+    if ((uint64_t)(hmap[k] + 1u) * ZES_BLK <= j.cap) {
+      mv_src.push_back(hmap[k]);
+      mv_dst.push_back(k);
+    } else {
+      redo.push_back(k);
+    }
+  }
+  const uint32_t nmv = (uint32_t)mv_src.size(), nre = (uint32_t)redo.size();
+  if ((rc = ensure(g.mvlist, (size_t)(3 * nmv + nre + 4) * 4))) return rc;
+  uint32_t* dl = (uint32_t*)g.mvlist.p;  // [src slots][dst slots][0..nmv)[redo]
+  if (nmv) {
+    if ((rc = ensure(g.scratch, (size_t)nmv * ZES_BLK))) return rc;
+    std::vector<uint32_t> up(3 * (size_t)nmv);
+    for (uint32_t q = 0; q < nmv; q++) {
+      up[q] = mv_src[q];
+      up[nmv + q] = mv_dst[q];
+      up[2 * (size_t)nmv + q] = q;
+    }
+    HIPCHK(hipMemcpy(dl, up.data(), up.size() * 4, hipMemcpyHostToDevice));
+    Timed tm("k_inf_move_slots");
+    uint8_t* outb = t.d_out + j.out_off;
+    hipLaunchKernelGGL(k_inf_move_slots, dim3(nmv * 32u), dim3(256), 0, g.stream, (uint8_t*)g.scratch.p, (const uint8_t*)outb,
+                       (const uint32_t*)(dl + 2 * (size_t)nmv), (const uint32_t*)dl, nmv);
+    hipLaunchKernelGGL(k_inf_move_slots, dim3(nmv * 32u), dim3(256), 0, g.stream, outb, (const uint8_t*)g.scratch.p,
+                       (const uint32_t*)(dl + nmv), (const uint32_t*)(dl + 2 * (size_t)nmv), nmv);
+  }
+  bool ok = true;
+  if (nre) {
+    HIPCHK(hipMemcpy(dl + 3 * (size_t)nmv, redo.data(), (size_t)nre * 4, hipMemcpyHostToDevice));
+    // a two-entry table for this buffer alone: K work items in all
+    ZesInfBuf* one = g.pinned->t1.redo;
+    one[0] = hb[i];
+    one[0].work_first = 0;
+    one[1] = hb[i];
+    one[1].work_first = K;
+    if ((rc = ensure(g.ibufs2, sizeof(ZesInfBuf) * 2))) return rc;
+    HIPCHK(hipMemcpyAsync(g.ibufs2.p, one, sizeof(ZesInfBuf) * 2, hipMemcpyHostToDevice, g.stream));
+    // cnt / candidates / map / results are indexed from this buffer's region: the table's cand_base does that
+    launch_block_par("k_inf_block_par", false, nre, t.d_in, t.d_out, (const ZesInfBuf*)g.ibufs2.p, 1u, (const uint32_t*)t.cnt + i, nullptr,
+                     (const uint32_t*)(dl + 3 * (size_t)nmv), ZesParMirror{});
+    std::vector<ZesCandRes> hcr(nre);
+    for (uint32_t q = 0; q < nre; q++)
+      HIPCHK(hipMemcpyAsync(&hcr[q], (const ZesCandRes*)g.cres.p + hb[i].cand_base + redo[q], sizeof(ZesCandRes), hipMemcpyDeviceToHost,
+                            g.stream));
     HIPCHK(hipStreamSynchronize(g.stream));
-    if (j.want_end && K) {
-      ZesCandRes last;
-      HIPCHK(hipMemcpy(&last, (const ZesCandRes*)g.cres.p + hb[i].cand_base + hmap[K - 1], sizeof last, hipMemcpyDeviceToHost));
-      j.end_bit = last.end_bit;
-    }
-    std::vector<uint32_t> mv_src, mv_dst, redo;
-    for (uint32_t k = 0; k < K; k++) {
-      if (hmap[k] == k) continue;
-      if ((uint64_t)(hmap[k] + 1u) * ZES_BLK <= j.cap) {
-        mv_src.push_back(hmap[k]);
-        mv_dst.push_back(k);
-      } else {
-        redo.push_back(k);
-      }
-    }
-    const uint32_t nmv = (uint32_t)mv_src.size(), nre = (uint32_t)redo.size();
-    if ((rc = ensure(g.mvlist, (size_t)(3 * nmv + nre + 4) * 4))) return rc;
-    uint32_t* dl = (uint32_t*)g.mvlist.p;  // [src slots][dst slots][0..nmv)[redo]
-    if (nmv) {
-      if ((rc = ensure(g.scratch, (size_t)nmv * ZES_BLK))) return rc;
-      std::vector<uint32_t> up(3 * (size_t)nmv);
-      for (uint32_t q = 0; q < nmv; q++) {
-        up[q] = mv_src[q];
-        up[nmv + q] = mv_dst[q];
-        up[2 * (size_t)nmv + q] = q;
-      }
-      HIPCHK(hipMemcpy(dl, up.data(), up.size() * 4, hipMemcpyHostToDevice));
-      Timed t("k_inf_move_slots");
-      uint8_t* outb = d_out + j.out_off;
-      hipLaunchKernelGGL(k_inf_move_slots, dim3(nmv * 32u), dim3(256), 0, g.stream, (uint8_t*)g.scratch.p, (const uint8_t*)outb,
-                         (const uint32_t*)(dl + 2 * (size_t)nmv), (const uint32_t*)dl, nmv);
-      hipLaunchKernelGGL(k_inf_move_slots, dim3(nmv * 32u), dim3(256), 0, g.stream, outb, (const uint8_t*)g.scratch.p,
-                         (const uint32_t*)(dl + nmv), (const uint32_t*)(dl + 2 * (size_t)nmv), nmv);
-    }
-    bool ok = true;
-    if (nre) {
-      HIPCHK(hipMemcpy(dl + 3 * (size_t)nmv, redo.data(), (size_t)nre * 4, hipMemcpyHostToDevice));
-      // a two-entry table for this buffer alone: work item -> slot through redo[], K work items in all
-      ZesInfBuf* one = g.pinned->t1.redo;
-      one[0] = hb[i];
-      one[0].work_first = 0;
-      one[1] = hb[i];
-      one[1].work_first = K;
-      if ((rc = ensure(g.ibufs2, sizeof(ZesInfBuf) * 2))) return rc;
-      HIPCHK(hipMemcpyAsync(g.ibufs2.p, one, sizeof(ZesInfBuf) * 2, hipMemcpyHostToDevice, g.stream));
-      {
-        Timed t("k_inf_block_par");
-        // cnt / candidates / map / results are indexed from this buffer's region: the table's cand_base does that
-        hipLaunchKernelGGL(k_inf_block_par, dim3(nre), dim3(PAR_THREADS), 0, g.stream, d_in, d_out, (const ZesInfBuf*)g.ibufs2.p, 1u,
-                           (const uint32_t*)cnt + i, (const uint32_t*)g.cand_sorted.p, (const uint32_t*)g.map.p,
-                           (ZesCandRes*)g.cres.p, (unsigned long long*)nullptr, (const uint32_t*)(dl + 3 * (size_t)nmv), (const uint32_t*)nullptr,
-                           (uint32_t*)nullptr, ZesParMirror{});
-      }
-      std::vector<ZesCandRes> hcr(nre);
-      for (uint32_t q = 0; q < nre; q++)
-        HIPCHK(hipMemcpyAsync(&hcr[q], (const ZesCandRes*)g.cres.p + hb[i].cand_base + redo[q], sizeof(ZesCandRes), hipMemcpyDeviceToHost,
-                              g.stream));
-      HIPCHK(hipStreamSynchronize(g.stream));
-      for (uint32_t q = 0; q < nre; q++) {
-        const bool last = redo[q] + 1u == K;
-        ok = ok && (hcr[q].flags & 1u) && (last ? hcr[q].out_len <= ZES_BLK : hcr[q].out_len == ZES_BLK);
-      }
-    }
-    r1[i].status = ok ? 0 : 1;  // out_len already holds the chain's total
+    for (uint32_t q = 0; q < nre; q++) ok = ok && zes_chain_redone(hcr[q], redo[q] + 1u == K);
   }
-  for (uint32_t i = 0; i < nbuf; i++) {
-    const ZesRes& r = r1[i];
+  r.status = ok ? 0 : 1;
+  return ZES_OK;
+}
+
+// step 6: tier, length, status and — where asked for — the stream's end bit of every accepted buffer
+int t1_publish(T1Group& t) {
+  int rc;
+  for (uint32_t i = 0; i < t.nbuf; i++) {
+    const ZesRes& r = t.r1[i];
     if (r.status != 0) continue;
-    InfJob& j = jobs[ids[i]];
-    if (j.want_end && hres[i].status == 0 && r.aux) {  // (status 2 above has filled it in)
-      if (hostchain) {
-        j.end_bit = g.mirror->cres[r.aux - 1].end_bit;
-      } else {
-        ZesCandRes last;
-        HIPCHK(hipMemcpy(&last, (const ZesCandRes*)g.cres.p + hb[i].cand_base + r.aux - 1, sizeof last, hipMemcpyDeviceToHost));
-        j.end_bit = last.end_bit;
-      }
+    InfJob& j = t.jobs[t.ids[i]];
+    if (j.want_end && t.hres[i].status == 0 && r.aux) {  // (t1_repair_slots has filled it in for a status 2)
+      if (t.hostchain) j.end_bit = g.mirror->cres[r.aux - 1].end_bit;
+      else if ((rc = cand_end_bit(t.hb[i].cand_base + r.aux - 1, &j.end_bit))) return rc;
     }
     j.tier = 1;
     j.out_len = r.out_len;
     j.status = r.out_len > j.cap ? ZES_E_NOSPACE : ZES_OK;
   }
   return ZES_OK;
+}
+
+int inflate_t1_group(const uint8_t* d_in, uint8_t* d_out, InfJob* jobs, const uint32_t* ids, uint32_t nbuf, bool check_first, uint32_t flags) {
+  int rc;
+  T1Group t{d_in, d_out, jobs, ids, nbuf, flags, check_first, nbuf == 1, g.pinned->t1.table, g.pinned->t1.counters, g.pinned->t1.res};
+  t.ncand.resize(nbuf);
+  const auto over = [](int r) { return r == T1_OVER ? ZES_OK : r; };
+  if ((rc = t1_table(t))) return over(rc);
+  // (k_inf_verify, measured on 64 MiB: 8192 workgroups 0.33 ms, 2048 0.26 ms, 512 0.36 ms — about one survivor in 256 input
+  // bytes, and a lane should get a few of them)
+  if ((rc = launch_search(d_in, t.dbufs, nbuf, (uint32_t)t.chunks, t.surv_cap, t.counters, t.cnt, (uint8_t*)(t.cnt + nbuf), t1_search_mode(flags),
+                          t.total_c)))
+    return rc;
+  if ((rc = t1_decode(t))) return over(rc);
+  if ((rc = t1_verdicts(t))) return over(rc);
+  for (uint32_t i = 0; i < nbuf; i++)
+    if (t.r1[i].status == 2 && (rc = t1_repair_slots(t, i, t.r1[i]))) return rc;
+  return t1_publish(t);
 }
 
 // T1 over one PIECE of a reference-made stream: the blocks that start inside bits [lo_bit, own_bit) of the piece at
@@ -1476,17 +1509,7 @@ RangePiece range_piece(uint64_t in_off, uint64_t c, uint64_t lo_bit, uint64_t ow
   return pd;
 }
 // scratch for a piece of up to c bytes
-int range_pools(uint64_t c, size_t counter_bytes) {
-  int rc;
-  const uint32_t cands = range_cand_cap(c);
-  if ((rc = ensure(g.ibufs, sizeof(ZesInfBuf) * 2))) return rc;
-  if ((rc = ensure(g.surv, (size_t)range_surv_cap(c) * 8))) return rc;
-  if ((rc = ensure(g.cand, (size_t)cands * 4))) return rc;
-  if ((rc = ensure(g.cand_sorted, (size_t)cands * 4))) return rc;
-  if ((rc = ensure(g.cres, sizeof(ZesCandRes) * cands))) return rc;
-  if ((rc = ensure(g.counters, counter_bytes))) return rc;
-  return ensure(g.res, sizeof(ZesRes) * 2);
-}
+int range_pools(uint64_t c, size_t counter_bytes) { return t1_pools(1, range_surv_cap(c), range_cand_cap(c), counter_bytes, 2); }
 // a range without a block start (a piece in the middle of one block): nothing to decode, and that is an answer
 void range_nothing(const RangePiece& pd, RangeRes* rr) {
   if (pd.exact) return;
@@ -1515,6 +1538,12 @@ void range_result(const ZesRes* hres, RangeRes* rr) {
   rr->first_bit = hres[1].aux;
 }
 
+void launch_chain_range(const ZesInfBuf* dbufs, const uint32_t* cnt, unsigned long long* acc) {
+  Timed t("k_inf_chain");
+  hipLaunchKernelGGL(k_inf_chain_range, dim3(1), dim3(256), 0, g.stream, dbufs, cnt, (const uint32_t*)g.cand_sorted.p, (const ZesCandRes*)g.cres.p,
+                     (ZesRes*)g.res.p, acc);
+}
+
 int inflate_t1_range(const uint8_t* d_in, uint64_t in_off, uint64_t c, uint64_t lo_bit, uint64_t own_bit, bool exact, uint8_t* d_out,
                      uint64_t out_off, uint64_t cap, uint32_t flags, RangeRes* rr) {
   int rc;
@@ -1533,18 +1562,11 @@ int inflate_t1_range(const uint8_t* d_in, uint64_t in_off, uint64_t c, uint64_t 
   const ZesInfBuf* dbufs = (const ZesInfBuf*)g.ibufs.p;
   uint32_t* counters = (uint32_t*)g.counters.p;
   uint32_t* cnt = counters + 4;
-  uint8_t* dfirst = (uint8_t*)(cnt + 1);
   HIPCHK(hipMemcpyAsync(g.ibufs.p, hb, sizeof(ZesInfBuf) * 2, hipMemcpyHostToDevice, g.stream));
   HIPCHK(hipMemsetAsync(g.counters.p, 0, cnt_bytes, g.stream));
-  {
-    Timed t("k_inf_scan");
-    // (the scan's rule that a BFINAL position far from the end is no block start uses the end of the piece: a piece in
-    // the middle of a stream merely keeps a few more survivors near its own end)
-    g.sv_ok = false;
-    hipLaunchKernelGGL(k_inf_scan, dim3(pd.chunks), dim3(INF_SCAN_THREADS), 0, g.stream, d_in, dbufs, 1u, (unsigned long long*)g.surv.p,
-                       pd.surv_cap, counters, dfirst, (flags & ZES_F_LOOSE_CANDIDATES) ? 1u : 2u, (const uint8_t*)g.kraft.p);
-  }
-  if ((rc = launch_verify(d_in, dbufs, pd.surv_cap, counters, cnt, (flags & ZES_F_LOOSE_CANDIDATES) ? 1u : 0u, c, 32768))) return rc;
+  // (the scan's rule that a BFINAL position far from the end is no block start uses the end of the piece: a piece in
+  // the middle of a stream merely keeps a few more survivors near its own end)
+  if ((rc = launch_search(d_in, dbufs, 1u, pd.chunks, pd.surv_cap, counters, cnt, (uint8_t*)(cnt + 1), t1_search_mode(flags), c))) return rc;
   uint32_t* hc = g.pinned->t1.counters;
   HIPCHK(hipMemcpyAsync(hc, g.counters.p, cnt_bytes, hipMemcpyDeviceToHost, g.stream));
   HIPCHK(hipStreamSynchronize(g.stream));
@@ -1552,17 +1574,8 @@ int inflate_t1_range(const uint8_t* d_in, uint64_t in_off, uint64_t c, uint64_t 
   const uint32_t ncand = hc[4];
   hb[1].work_first = ncand;
   HIPCHK(hipMemcpyAsync(g.ibufs.p, hb, sizeof(ZesInfBuf) * 2, hipMemcpyHostToDevice, g.stream));
-  {
-    Timed t("k_inf_block_par");
-    hipLaunchKernelGGL((c * 10 < cap * 7) ? k_inf_block_par2 : k_inf_block_par, dim3(ncand), dim3(PAR_THREADS), 0, g.stream, d_in, d_out, dbufs, 1u, (const uint32_t*)cnt,
-                       (const uint32_t*)g.cand_sorted.p, (const uint32_t*)nullptr, (ZesCandRes*)g.cres.p, (unsigned long long*)nullptr, (const uint32_t*)nullptr,
-                       (const uint32_t*)g.cand.p, (uint32_t*)g.cand_sorted.p, ZesParMirror{});
-  }
-  {
-    Timed t("k_inf_chain");
-    hipLaunchKernelGGL(k_inf_chain_range, dim3(1), dim3(256), 0, g.stream, dbufs, (const uint32_t*)cnt, (const uint32_t*)g.cand_sorted.p,
-                       (const ZesCandRes*)g.cres.p, (ZesRes*)g.res.p, (unsigned long long*)nullptr);
-  }
+  launch_block_par("k_inf_block_par", c * 10 < cap * 7, ncand, d_in, d_out, dbufs, 1u, cnt, nullptr, nullptr, ZesParMirror{});
+  launch_chain_range(dbufs, cnt, nullptr);
   ZesRes* hres = g.pinned->t1.res;
   HIPCHK(hipMemcpyAsync(hres, g.res.p, sizeof(ZesRes) * 2, hipMemcpyDeviceToHost, g.stream));
   HIPCHK(hipStreamSynchronize(g.stream));
@@ -1610,27 +1623,11 @@ int range_begin(int slot, RangePiece& pd, const uint8_t* d_in, uint64_t in_off, 
     const ZesInfBuf* dbufs = (const ZesInfBuf*)g.ibufs.p;
     uint32_t* counters = (uint32_t*)g.counters.p;
     uint32_t* cnt = counters + 4;
-    uint8_t* dfirst = (uint8_t*)(cnt + 1);
     hipLaunchKernelGGL(k_inf_set_table_range, dim3(1), dim3(64), 0, g.stream, b0, b1, (ZesInfBuf*)g.ibufs.p, counters, 6u,
                        (const unsigned long long*)range_acc(), (unsigned long long)dcap);
-    {
-      Timed t("k_inf_scan");
-      g.sv_ok = false;
-      hipLaunchKernelGGL(k_inf_scan, dim3(pd.chunks), dim3(INF_SCAN_THREADS), 0, g.stream, d_in, dbufs, 1u, (unsigned long long*)g.surv.p,
-                         pd.surv_cap, counters, dfirst, (flags & ZES_F_LOOSE_CANDIDATES) ? 1u : 2u, (const uint8_t*)g.kraft.p);
-    }
-    if ((rc = launch_verify(d_in, dbufs, pd.surv_cap, counters, cnt, (flags & ZES_F_LOOSE_CANDIDATES) ? 1u : 0u, c, 32768))) return rc;
-    {
-      Timed t("k_inf_block_par");
-      hipLaunchKernelGGL(two ? k_inf_block_par2 : k_inf_block_par, dim3(pd.bound), dim3(PAR_THREADS), 0, g.stream, d_in, d_out, dbufs, 1u,
-                         (const uint32_t*)cnt, (const uint32_t*)g.cand_sorted.p, (const uint32_t*)nullptr, (ZesCandRes*)g.cres.p,
-                         (unsigned long long*)nullptr, (const uint32_t*)nullptr, (const uint32_t*)g.cand.p, (uint32_t*)g.cand_sorted.p, ZesParMirror{});
-    }
-    {
-      Timed t("k_inf_chain");
-      hipLaunchKernelGGL(k_inf_chain_range, dim3(1), dim3(256), 0, g.stream, dbufs, (const uint32_t*)cnt, (const uint32_t*)g.cand_sorted.p,
-                         (const ZesCandRes*)g.cres.p, (ZesRes*)g.res.p, range_acc());
-    }
+    if ((rc = launch_search(d_in, dbufs, 1u, pd.chunks, pd.surv_cap, counters, cnt, (uint8_t*)(cnt + 1), t1_search_mode(flags), c))) return rc;
+    launch_block_par("k_inf_block_par", two, pd.bound, d_in, d_out, dbufs, 1u, cnt, nullptr, nullptr, ZesParMirror{});
+    launch_chain_range(dbufs, cnt, range_acc());
     RangeSlot& hs = g.pinned->range[slot];
     HIPCHK(hipMemcpyAsync(hs.counters, g.counters.p, sizeof hs.counters, hipMemcpyDeviceToHost, g.stream));
     HIPCHK(hipMemcpyAsync(hs.res, g.res.p, sizeof hs.res, hipMemcpyDeviceToHost, g.stream));
@@ -2014,13 +2011,7 @@ int inflate_segments(const uint8_t* d_in, uint8_t* d_out, InfJob* jobs, const st
       if ((rc = ensure(g.surv, (size_t)surv_all * 8))) return rc;
       dbufs = (const ZesInfBuf*)g.ibufs.p;
       HIPCHK(hipMemcpyAsync(g.ibufs.p, hb, sizeof(ZesInfBuf) * (nb + 1), hipMemcpyHostToDevice, g.stream));
-      {
-        Timed t("k_inf_scan");
-        g.sv_ok = false;
-        hipLaunchKernelGGL(k_inf_scan, dim3((uint32_t)chunks), dim3(INF_SCAN_THREADS), 0, g.stream, d_in, dbufs, nb, (unsigned long long*)g.surv.p,
-                           surv_all, counters, sink, 0u, (const uint8_t*)g.kraft.p);
-      }
-      if ((rc = launch_verify(d_in, dbufs, surv_all, counters, cnt, 1u, total_c, 16384))) return rc;
+      if ((rc = launch_search(d_in, dbufs, nb, (uint32_t)chunks, surv_all, counters, cnt, sink, T2_SEARCH, total_c))) return rc;
       {
         Timed t("k_inf_ranksort");
         hipLaunchKernelGGL(k_inf_ranksort, dim3(nb), dim3(1024), 0, g.stream, dbufs, (const uint32_t*)cnt, (const uint32_t*)g.cand.p,
@@ -2059,18 +2050,14 @@ int inflate_segments(const uint8_t* d_in, uint8_t* d_out, InfJob* jobs, const st
       // verify kernels' — so only their count goes back into place (0.06 of the 1.65 ms of 64 MiB of zlib text).
       const bool reuse = nb == 1 && g.sv_ok && g.sv_list == g.surv.p && g.sv_din == d_in && g.sv_in_off == j.in_off && g.sv_c == j.c && j.start0 == 16u && g.sv_n <= surv_cap;
       g.sv_ok = false;
-      if (reuse) {
+      if (reuse) {  // the header test alone
         g.pinned->t2.nsurv = g.sv_n;
         HIPCHK(hipMemcpyAsync(counters, &g.pinned->t2.nsurv, 4, hipMemcpyHostToDevice, g.stream));
+        rc = launch_verify(d_in, dbufs, surv_cap, counters, cnt + k, T2_SEARCH.loose, j.c);
       } else {
-        Timed t("k_inf_scan");
-        // (the BFINAL rule of the scan holds for every encoder's streams: it stays on; only the verify rules are the reference's own)
-        g.sv_ok = false;
-        hipLaunchKernelGGL(k_inf_scan, dim3(chunks), dim3(INF_SCAN_THREADS), 0, g.stream, d_in, dbufs, 1u, (unsigned long long*)g.surv.p,
-                           surv_cap, counters, sink, 0u, (const uint8_t*)g.kraft.p);
+        rc = launch_search(d_in, dbufs, 1u, chunks, surv_cap, counters, cnt + k, sink, T2_SEARCH, j.c);
       }
-      // other encoders do not follow the reference's run-length rules for code lengths: loose candidates
-      if ((rc = launch_verify(d_in, dbufs, surv_cap, counters, cnt + k, 1u, j.c, 16384))) return rc;
+      if (rc) return rc;
       {
         // one candidate per bucket of the stream, in order (at most SEG_BUCKETS segments whatever the block size)
         Timed t("k_inf_cand_thin");
@@ -3882,6 +3869,54 @@ int zes_stage_huff_lengths_dev(const uint32_t* h_hist, uint32_t nsym, uint32_t m
   HIPCHK(hipGetLastError());
   HIPCHK(hipMemcpyAsync(h_lens, g.codes.p, nsym, hipMemcpyDeviceToHost, g.stream));
   HIPCHK(hipStreamSynchronize(g.stream));
+  return ZES_OK;
+}
+
+// (records beyond this many: not a case, ZES_E_ARG — T1's own cap for a stream of 2^29 bytes is 2^23 + 64)
+constexpr uint32_t STAGE_CHAIN_MAX = 1u << 20;
+int zes_stage_chain(const uint32_t* start_bit, const uint64_t* end_bit, const uint32_t* out_len, const uint32_t* flags, uint32_t count, uint32_t cap,
+                    uint32_t first_bit, int on_device, int32_t* status, uint64_t* total, uint32_t* aux, uint32_t* map) {
+  if (!status || !total || !aux || count > STAGE_CHAIN_MAX || cap > STAGE_CHAIN_MAX || first_bit < 16) return ZES_E_ARG;
+  if (count && (!start_bit || !end_bit || !out_len || !flags || !map)) return ZES_E_ARG;
+  const uint32_t n = std::min(count, cap);  // the records a list of `cap` entries holds
+  std::vector<ZesCandRes> cres(n);
+  std::vector<uint32_t> rel(n);  // the device's form of the start bits
+  for (uint32_t k = 0; k < count; k++) {
+    if (start_bit[k] < 16 || (k && start_bit[k] <= start_bit[k - 1])) return ZES_E_ARG;
+    if (k >= n) continue;
+    cres[k] = ZesCandRes{end_bit[k], out_len[k], flags[k]};
+    rel[k] = start_bit[k] - 16u;
+  }
+  ZesInfBuf tab[2] = {};
+  tab[0].cand_cap = cap;
+  tab[0].start_rel = first_bit - 16u;
+  const uint32_t hc[5] = {1u, 0u, 0u, 0u, count};  // the search found something; `count` candidates
+  ZesRes r;
+  if (!on_device) {  // as a one-buffer call: the launch bound is the cap
+    r = t1_host_chain(start_bit, cres.data(), hc, 1u, tab[0], cap, map);
+  } else {  // as a buffer of a batch: a work item per candidate of a list that is whole
+    LOCK_READY();
+    tab[1].work_first = count <= cap ? count : 0u;
+    // every list has cap + 1 entries, and the kernel reads min(count, cap) of them
+    if ((rc = t1_pools(1, 0, (uint64_t)cap + 1, sizeof hc, 1))) return rc;
+    if ((rc = ensure(g.map, (size_t)cap * 4 + 4))) return rc;
+    uint32_t* counters = (uint32_t*)g.counters.p;
+    HIPCHK(hipMemcpyAsync(g.ibufs.p, tab, sizeof tab, hipMemcpyHostToDevice, g.stream));
+    HIPCHK(hipMemcpyAsync(counters, hc, sizeof hc, hipMemcpyHostToDevice, g.stream));
+    if (n) {
+      HIPCHK(hipMemcpyAsync(g.cand_sorted.p, rel.data(), (size_t)n * 4, hipMemcpyHostToDevice, g.stream));
+      HIPCHK(hipMemcpyAsync(g.cres.p, cres.data(), sizeof(ZesCandRes) * n, hipMemcpyHostToDevice, g.stream));
+    }
+    hipLaunchKernelGGL(k_inf_chain, dim3(1), dim3(256), 0, g.stream, (const ZesInfBuf*)g.ibufs.p, (const uint32_t*)(counters + 4),
+                       (const uint32_t*)g.cand_sorted.p, (const ZesCandRes*)g.cres.p, (const uint32_t*)nullptr, (uint32_t*)g.map.p, (ZesRes*)g.res.p,
+                       (const uint32_t*)counters, 0u, (uint32_t*)nullptr);
+    HIPCHK(hipGetLastError());
+    if ((rc = read_res(&r))) return rc;
+    if (r.status != 1 && r.aux <= n) HIPCHK(hipMemcpy(map, g.map.p, (size_t)r.aux * 4, hipMemcpyDeviceToHost));
+  }
+  *status = r.status;
+  *total = r.out_len;
+  *aux = r.aux;
   return ZES_OK;
 }
 

@@ -23,6 +23,7 @@
 //      up — reproduces the reference's result on malformed streams (which error, or which bytes).
 #include "zes_common.h"
 #include "zes_kernels.h"
+#include "zes_chain.h"
 
 #define ZES_E_NOT_DEFLATE (-1)
 #define ZES_E_BTYPE3 (-2)
@@ -2538,7 +2539,8 @@ __global__ __launch_bounds__(64) void k_inf_seg_decode(const uint8_t* __restrict
 // ------------------------------------------------------------------------------------------
 // k_inf_chain: validates the parallel decode.  Success needs: candidate 0 at bit 16, every
 // block ok, every non-final block exactly 131072 bytes, end bit of block k == start of k+1,
-// and the k-th chain member being the k-th candidate (otherwise a remap pass is requested).
+// and the k-th chain member being the k-th candidate (otherwise a remap pass is requested).  Every one of these tests is
+// zes_chain.h's (the host takes the same decision from them: zes_chain_decide); here the fast check runs over 256 threads.
 // res->status: 0 done (res->aux = the closing candidate + 1), 2 remap needed (chain in map_out, length in res->aux), 1 give up (T2).
 // ------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void k_inf_chain(const ZesInfBuf* __restrict__ bufs, const uint32_t* __restrict__ cnt,
@@ -2572,13 +2574,12 @@ __global__ __launch_bounds__(256) void k_inf_chain(const ZesInfBuf* __restrict__
     res->aux = 0;
   }
   __syncthreads();
-  if (ncand == 0 || nwork == 0 || cand[0] != bf.start_rel || cnt[blockIdx.x] > bf.cand_cap) return;  // (no work items: the buffer was left out, results would be stale)
-  if (autow && ncand > nwork) return;  // more candidates than work items were launched: the host falls back
-  // Fast check, all work items in parallel: item k is ok, non-final items give exactly one slot
-  // and end where item k+1 starts, the first final item closes the chain.
+  const ZesChainView v = {cand, cres, ncand, 16u};
+  if (!zes_chain_enter(v, cnt[blockIdx.x], bf.cand_cap, nwork, (uint64_t)bf.start_rel + 16)) return;
+  // Fast check, all work items in parallel: chain member k is candidate k, the first closing one closes the chain.
   uint32_t first_final = 0xFFFFFFFFu;
   for (uint32_t k = tid; k < nwork; k += 256)
-    if ((cres[k].flags & 3u) == 3u) {
+    if (zes_chain_closes(cres[k])) {
       first_final = k;
       break;
     }
@@ -2590,12 +2591,8 @@ __global__ __launch_bounds__(256) void k_inf_chain(const ZesInfBuf* __restrict__
     uint32_t bad = 0;
     for (uint32_t k = tid; k <= K; k += 256) {
       const ZesCandRes r = cres[k];
-      if (!(r.flags & 1u)) bad = 1;
       part += r.out_len;
-      if (k < K) {
-        const uint32_t nxt = map_in ? map_in[k + 1] : k + 1;
-        if (r.out_len != ZES_BLK || nxt >= ncand || (uint64_t)cand[nxt] + 16 != r.end_bit) bad = 1;
-      }
+      if (k < K && !zes_chain_link(v, r, map_in ? map_in[k + 1] : k + 1)) bad = 1;
       if (map_in == nullptr) map_out[k] = k;
     }
     if (bad) atomicOr(&s_bad, 1u);
@@ -2612,27 +2609,11 @@ __global__ __launch_bounds__(256) void k_inf_chain(const ZesInfBuf* __restrict__
   }
   if (map_in || tid != 0) return;  // a remapped pass that still fails goes to T2
   // Slow path (false candidates between the blocks): follow end bit -> next start serially.
-  uint32_t j = 0, k = 0;
-  uint64_t total = 0;
-  for (;;) {
-    const ZesCandRes r = cres[j];
-    if (!(r.flags & 1u)) return;
-    map_out[k] = j;
-    k++;
-    total += r.out_len;
-    if (r.flags & 2u) break;
-    if (r.out_len != ZES_BLK) return;
-    const uint64_t want = r.end_bit - 16;
-    uint32_t lo = j + 1, hi = ncand;
-    while (lo < hi) {
-      const uint32_t mid = (lo + hi) >> 1;
-      if ((uint64_t)cand[mid] < want) lo = mid + 1; else hi = mid;
-    }
-    if (lo >= ncand || (uint64_t)cand[lo] != want) return;
-    j = lo;
-  }
+  uint64_t total;
+  uint32_t len;
+  if (!zes_chain_walk(v, map_out, &total, &len)) return;
   res->out_len = total;
-  res->aux = k;
+  res->aux = len;
   res->status = 2;  // the slots are shifted: decode the chain again in order
 }
 
@@ -2655,6 +2636,7 @@ __global__ __launch_bounds__(256) void k_inf_chain_range(const ZesInfBuf* __rest
   const uint32_t ncand = min(cnt[0], bf.cand_cap);
   const uint32_t* cand = cand_all + bf.cand_base;
   const ZesCandRes* cres = cres_all + bf.cand_base;
+  const ZesChainView v = {cand, cres, ncand, 16u};
   if (tid == 0) {
     s_bad = 0;
     s_final = 0;
@@ -2684,12 +2666,11 @@ __global__ __launch_bounds__(256) void k_inf_chain_range(const ZesInfBuf* __rest
   uint32_t bad = 0, fin = 0;
   for (uint32_t k = tid; k < nown; k += 256) {
     const ZesCandRes r = cres[k];
-    if (!(r.flags & 1u)) bad = 1;
     part += r.out_len;
-    if (r.flags & 2u) {  // the stream's final block: must be the last own one
-      if (k + 1 != nown) bad = 1;
+    if (r.flags & ZES_CAND_FINAL) {  // the stream's final block: must be the last own one
+      if (!zes_chain_closes(r) || k + 1 != nown) bad = 1;
       fin = 1;
-    } else if (r.out_len != ZES_BLK || k + 1 >= ncand || (uint64_t)cand[k + 1] + 16 != r.end_bit) {
+    } else if (!zes_chain_link(v, r, k + 1)) {
       bad = 1;  // (k + 1 == nown: the candidate behind the last own block is the next piece's first block)
     }
   }

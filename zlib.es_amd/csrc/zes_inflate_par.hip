@@ -27,6 +27,7 @@
 // the data) marks the block not-ok; the chain check then sends the stream to T2/T3.
 #include "zes_common.h"
 #include "zes_kernels.h"
+#include "zes_chain.h"
 
 #define PL_ROOT 10u
 #define PD_ROOT 9u
@@ -2414,7 +2415,7 @@ __device__ __forceinline__ static void par_body(ParSmem& S, const ParItem& it, u
         ZesCandRes r;
         r.end_bit = end_bit;
         r.out_len = total;
-        r.flags = 1u | (S.bfinal ? 2u : 0u);
+        r.flags = ZES_CAND_OK | (S.bfinal ? ZES_CAND_FINAL : 0u);
         *it.cres = r;
         if (it.cres_host) {
           *it.cres_host = r;
