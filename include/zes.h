@@ -62,6 +62,8 @@ typedef enum zes_status {
 #define ZES_F_CHECK_ADLER 16u  /* zes_inflate, zes_inflate_dev, zes_inflate_size, zes_inflate_alloc: the 4 bytes behind the stream must
                                   exist and hold the Adler-32 of the result (big-endian), else ZES_E_CHECKSUM.  Without the flag the
                                   trailer is ignored, as the reference ignores it (src/zlib.ts:11-23) */
+#define ZES_F_GZIP_SERIAL 32u   /* zes_gunzip*: decode the members one after the other even where they could go as one batch:
+                                  testing aid, same results */
 #define ZES_F_LOOSE_CANDIDATES 2u /* block-start search without the reference's run-length-coding rules: more false
                                   * candidates reach the block decoder (testing aid for that path; same results) */
 
@@ -168,6 +170,10 @@ int zes_inflate_raw_used_dev(const uint8_t* d_in, uint64_t c, uint64_t offset, u
  * replaces: nothing (the reference has no CRC-32). */
 int zes_crc32(const uint8_t* in, uint64_t n, uint32_t* crc);
 int zes_crc32_dev(const uint8_t* d_in, uint64_t n, uint32_t* crc);
+/* CRC-32 of many buffers of device memory in one launch: crc[i] = the CRC-32 of d_in[off[i], off[i] + len[i]), i < count.
+ * Any alignment, any length (0 gives 0), buffers may overlap; off, len and crc are host arrays.  count == 0 is ZES_OK.
+ * Made for many short, unaligned buffers (the members of a BGZF file), which zes_crc32_dev would take one launch each. */
+int zes_crc32_batch_dev(const uint8_t* d_in, const uint64_t* off, const uint64_t* len, uint32_t* crc, uint32_t count);
 
 /* gzip (RFC 1952) compress: one member whose
  *   header  is exactly 1f 8b 08 00 00 00 00 00 00 ff (FLG 0, MTIME 0, XFL 0, OS 255: the output is deterministic),
@@ -195,6 +201,18 @@ int zes_gzip_dev(const uint8_t* d_in, uint64_t n, uint8_t* d_out, uint64_t cap, 
  * Header errors of the host forms are decided before the device is touched.  The device form writes whole 16-byte
  * groups as zes_inflate_dev does (d_out 16-byte aligned; d_in at any alignment).  zes_gunzip_alloc: as
  * zes_inflate_alloc (one alloc call, index 0, for the exact size).
+ *
+ * Member-parallel reading.  A file whose members all state their own size (BGZF, the format of bgzip / htslib) is decoded
+ * as one batch: its members are found without decoding, all bodies go through the inflate tiers in one call, and one
+ * segmented CRC-32 launch checks all outputs.  A member qualifies when its header is 1f 8b 08 with FLG exactly 04
+ * (FEXTRA only) and at most 256 bytes long, its extra field, walked subfield by subfield, ends exactly with a subfield and
+ * holds a subfield 'B','C' of SLEN 2 (others before or after it are fine), and with size = BSIZE + 1: hlen + 8 <= size and
+ * the member lies inside the input.  The batch is tried when members follow each other directly from byte 0 to the
+ * input's last byte, every one of them qualifies and there are at least two.  It answers only with ZES_OK: when every
+ * member decodes to exactly its ISIZE bytes, its stream ends in the last byte in front of its trailer and its CRC-32
+ * matches.  Anything else (padding, a plain member, a BSIZE that lies, any error, a result beyond the device form's cap)
+ * is decided by the member-by-member path run from the start, so results and statuses are the same either way, and the
+ * allocator of zes_gunzip_alloc is still called exactly once.  ZES_F_GZIP_SERIAL forces the member-by-member path.
  * replaces: nothing (the reference has no gzip container). */
 int zes_gunzip(const uint8_t* in, uint64_t c, uint8_t* out, uint64_t cap, uint64_t* out_len, uint32_t flags);
 int zes_gunzip_dev(const uint8_t* d_in, uint64_t c, uint8_t* d_out, uint64_t cap, uint64_t* out_len, uint32_t flags);
@@ -301,7 +319,10 @@ int zes_last_kernel_times(zes_ktime* out, int cap);
  * 2 segment-parallel (any valid stream), 3 sequential wavefront, 4 exact single-lane restatement
  * (DESIGN.md §4); 0 if the call failed before decoding. */
 int zes_last_inflate_tier(void);
-/* (After zes_init_devices: zes_last_inflate_tier / zes_last_kernel_times report on the context that served the calling
+/* Members the member-parallel path decoded in the calling thread's last zes_gunzip* call; 0 when the member-by-member
+ * path answered. */
+int zes_last_gunzip_members(void);
+/* (After zes_init_devices: zes_last_inflate_tier / zes_last_gunzip_members / zes_last_kernel_times report on the context that served the calling
  * thread's last call; zes_set_profiling switches every context.) */
 int zes_set_profiling(int on);
 

@@ -43,6 +43,7 @@ ZES_ALLOC_EARLY = 0x80000000  # in the allocator's index argument: an early requ
 ZES_E_NOTRANGE = -19
 ZES_E_GZIP = -20  # zes_gunzip*: not a valid gzip member (header, or a trailer cut short), or no input at all
 ZES_E_CHECKSUM = -21  # a trailer does not match: gzip CRC-32 / ISIZE / FHCRC, zlib Adler-32 under ZES_F_CHECK_ADLER
+ZES_F_GZIP_SERIAL = 32  # zes_gunzip*: the members one after the other even where they could go as one batch (testing aid)
 ZES_F_CHECK_ADLER = 16  # zes_inflate*: the Adler-32 trailer behind the stream must be there and match
 
 GEN_KINDS = {"xorshift": 0, "lowent4k": 1, "itext": 2}
@@ -106,6 +107,8 @@ def lib():
             getattr(L, name).argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_uint64, u64p, u64p, C.c_uint32]
         for name in ("zes_crc32", "zes_crc32_dev"):
             getattr(L, name).argtypes = [C.c_void_p, C.c_uint64, u32p]
+        L.zes_crc32_batch_dev.argtypes = [C.c_void_p, u64p, u64p, u32p, C.c_uint32]
+        L.zes_last_gunzip_members.argtypes = []
         L.zes_gzip_bound.argtypes = [C.c_uint64, u64p]
         for name in ("zes_gzip", "zes_gzip_dev"):
             getattr(L, name).argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, u64p]
@@ -465,6 +468,26 @@ def crc32_tensor(t):
     return out.value
 
 
+_len = len  # (crc32_batch_tensor has a parameter of that name, after the C entry point)
+
+
+def crc32_batch_tensor(d_in, off, len):
+    """CRC-32 of every d_in[off[i] : off[i] + len[i]] of a uint8 CUDA tensor, any alignment and length, in one launch
+    (zes_crc32_batch_dev); returns a list of ints."""
+    import torch
+
+    assert d_in.is_cuda and d_in.dtype == torch.uint8 and d_in.is_contiguous()
+    cnt = _len(off)
+    assert _len(len) == cnt
+    assert all(int(o) + int(n) <= d_in.numel() for o, n in zip(off, len)), "crc32_batch_tensor: a buffer reaches beyond d_in"
+    torch.cuda.current_stream(d_in.device).synchronize()
+    out = (C.c_uint32 * cnt)()
+    rc = lib().zes_crc32_batch_dev(d_in.data_ptr(), (C.c_uint64 * cnt)(*[int(x) for x in off]), (C.c_uint64 * cnt)(*[int(x) for x in len]), out, cnt)
+    if rc:
+        _raise(rc)
+    return list(out)
+
+
 def gzip_tensor(t, out=None):
     """gzip of a 1-D uint8 CUDA tensor (zes_gzip_dev); returns a view of ``out`` (allocated if None)."""
     import torch
@@ -590,13 +613,18 @@ def last_inflate_tier():
     return int(lib().zes_last_inflate_tier())
 
 
+def last_gunzip_members():
+    """Members the member-parallel path decoded in this thread's last gunzip call (0: the member-by-member path answered)."""
+    return int(lib().zes_last_gunzip_members())
+
+
 def set_profiling(on):
     lib().zes_set_profiling(1 if on else 0)
 
 
 def last_kernel_times():
-    arr = (ZesKTime * 32)()
-    n = lib().zes_last_kernel_times(arr, 32)
+    arr = (ZesKTime * 64)()
+    n = lib().zes_last_kernel_times(arr, 64)
     return [(arr[i].name.decode(), float(arr[i].ms), int(arr[i].launches)) for i in range(n)]
 
 

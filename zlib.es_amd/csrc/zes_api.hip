@@ -68,6 +68,7 @@ struct PinnedArea {
       ZesRes res[INF_GROUP];                           // (one buffer: k_inf_chain writes them)
       ZesInfBuf table[INF_GROUP + 1];                  // the buffers and the sentinel
       ZesInfBuf redo[2];                               // one buffer's blocks decoded again into their own slots
+      uint64_t ends[2 * INF_GROUP];                    // the serial wavefront batch: k_inf_decode's two words per stream ([0]: where it ended)
     } t1;
     struct {                   // inflate_jobs: one byte of every buffer of a group, read on the device
       uint8_t bytes[INF_GROUP];
@@ -116,6 +117,7 @@ PIN_HOLDS(t1.counters, t1_cnt_bytes(INF_GROUP));
 PIN_HOLDS(t1.res, sizeof(ZesRes) * INF_GROUP);
 PIN_HOLDS(t1.table, sizeof(ZesInfBuf) * (INF_GROUP + 1));
 PIN_HOLDS(t1.redo, sizeof(ZesInfBuf) * 2);
+PIN_HOLDS(t1.ends, sizeof(uint64_t) * 2 * INF_GROUP);
 PIN_HOLDS(first.bytes, INF_GROUP);
 PIN_HOLDS(first.offs, sizeof(uint64_t) * INF_GROUP);
 PIN_HOLDS(t2.search, sizeof(ZesInfBuf) * (SEG_GROUP_BUFS + 1));
@@ -132,7 +134,7 @@ static_assert(sizeof(ParMirror::start) >= sizeof(uint32_t) * MIRROR_ITEMS, "the 
 // what one call uses at the same time
 static_assert(disjoint({PIN_SPAN(range[0]), PIN_SPAN(range[1])}), "the two range slots overlap");
 static_assert(disjoint({PIN_SPAN(def.res), PIN_SPAN(def.table), PIN_SPAN(crc)}), "deflate regions overlap (gzip_core: the CRC words beside the results)");
-static_assert(disjoint({PIN_SPAN(t1.counters), PIN_SPAN(t1.res), PIN_SPAN(t1.table), PIN_SPAN(t1.redo)}), "T1 regions overlap");
+static_assert(disjoint({PIN_SPAN(t1.counters), PIN_SPAN(t1.res), PIN_SPAN(t1.table), PIN_SPAN(t1.redo), PIN_SPAN(t1.ends)}), "T1 regions overlap");
 static_assert(disjoint({PIN_SPAN(first.bytes), PIN_SPAN(first.offs)}), "first-byte regions overlap");
 static_assert(disjoint({PIN_SPAN(t2.search), PIN_SPAN(t2.ncand), PIN_SPAN(t2.nsurv), PIN_SPAN(t2.flags), PIN_SPAN(t2.far), PIN_SPAN(t2.res),
                         PIN_SPAN(t2.jobs), PIN_SPAN(t2.live), PIN_SPAN(t2.out)}),
@@ -151,7 +153,9 @@ static_assert(disjoint({PIN_SPAN(t2.search), PIN_SPAN(t2.ncand), PIN_SPAN(t2.nsu
   X(st_in) X(st_out)                                                                                                              \
   /* CRC-32: the kernel's table (x^(8 * 65536 * m) for m < crc_npow) and its two accumulator words; gzip reader: the input  */    \
   /* (host forms), the result as it grows (host forms) and one member's output when it cannot go to its place directly */         \
-  X(crctab) X(crcacc) X(gz_in) X(gz_acc) X(gz_stage)
+  /* member-parallel gzip reader: the bodies behind their 78 9C, the outputs that cannot go to their places directly, the    */    \
+  /* device tables (members, segments); segmented CRC-32: its buffers, work items and accumulator words */                        \
+  X(crctab) X(crcacc) X(gz_in) X(gz_acc) X(gz_stage) X(gz_bodies) X(gz_outs) X(gz_tab) X(crcseg)
 
 struct Ctx {
   bool ready = false;
@@ -179,8 +183,10 @@ struct Ctx {
   std::vector<std::pair<std::string, std::pair<hipEvent_t, hipEvent_t>>> pending;
   std::vector<hipEvent_t> event_pool;
   std::vector<std::pair<std::string, KTime>> last_times;
+  std::vector<std::pair<std::string, KTime>> carry;  // times collected in the middle of a call (a nested inflate_jobs) that its last collect_times puts in front of its own
   std::vector<std::string> name_pool;
   int last_tier = 0;
+  int last_members = 0;  // members the member-parallel gzip reader decoded in the last gunzip call (0: the serial path answered)
   // the survivor list of the block-start search as the block-parallel tier's scan left it (one buffer): the segment-parallel
   // tier's search of the same stream starts from it instead of scanning again
   bool sv_ok = false;
@@ -694,7 +700,18 @@ void collect_times() {
   }
   g.pending.clear();
   g.last_times.clear();
-  for (auto& n : order) g.last_times.push_back({n, acc[n]});
+  for (auto& e : g.carry) {
+    auto it = acc.find(e.first);
+    if (it != acc.end()) {
+      e.second.ms += it->second.ms;
+      e.second.launches += it->second.launches;
+      acc.erase(it);
+    }
+    g.last_times.push_back(e);
+  }
+  g.carry.clear();
+  for (auto& n : order)
+    if (acc.count(n)) g.last_times.push_back({n, acc[n]});
 }
 
 // ---- deflate ----
@@ -1431,17 +1448,42 @@ int t1_repair_slots(T1Group& t, uint32_t i, ZesRes& r) {
 // step 6: tier, length, status and — where asked for — the stream's end bit of every accepted buffer
 int t1_publish(T1Group& t) {
   int rc;
+  // end bits that are still on the device (a group's chains were judged there): one segmented copy (k_gz_gather, 8 bytes a
+  // buffer out of its closing block's record) and one read-back for all of them, not a copy command per buffer
+  std::vector<ZesGzSeg> segs;
+  std::vector<uint32_t> who;
   for (uint32_t i = 0; i < t.nbuf; i++) {
     const ZesRes& r = t.r1[i];
     if (r.status != 0) continue;
     InfJob& j = t.jobs[t.ids[i]];
     if (j.want_end && t.hres[i].status == 0 && r.aux) {  // (t1_repair_slots has filled it in for a status 2)
-      if (t.hostchain) j.end_bit = g.mirror->cres[r.aux - 1].end_bit;
-      else if ((rc = cand_end_bit(t.hb[i].cand_base + r.aux - 1, &j.end_bit))) return rc;
+      if (t.hostchain) {
+        j.end_bit = g.mirror->cres[r.aux - 1].end_bit;
+      } else {
+        segs.push_back(ZesGzSeg{sizeof(ZesCandRes) * ((uint64_t)t.hb[i].cand_base + r.aux - 1) + offsetof(ZesCandRes, end_bit), 0, 8, 0u, 0u});
+        who.push_back(t.ids[i]);
+      }
     }
     j.tier = 1;
     j.out_len = r.out_len;
     j.status = r.out_len > j.cap ? ZES_E_NOSPACE : ZES_OK;
+  }
+  if (segs.size() == 1) return cand_end_bit(segs[0].src_off / sizeof(ZesCandRes), &t.jobs[who[0]].end_bit);
+  if (!segs.empty()) {
+    const size_t o_dst = (sizeof(ZesGzSeg) * segs.size() + 15) & ~(size_t)15;
+    for (size_t k = 0; k < segs.size(); k++) segs[k].dst_off = o_dst + 8 * k;
+    if ((rc = ensure(g.crcseg, o_dst + 8 * segs.size()))) return rc;
+    HIPCHK(hipMemcpyAsync(g.crcseg.p, segs.data(), sizeof(ZesGzSeg) * segs.size(), hipMemcpyHostToDevice, g.stream));
+    {
+      Timed tm("k_gz_gather");
+      hipLaunchKernelGGL(k_gz_gather, dim3((uint32_t)segs.size(), 1), dim3(GZ_GATHER_THREADS), 0, g.stream, (const uint8_t*)g.cres.p,
+                         (uint8_t*)g.crcseg.p, (const ZesGzSeg*)g.crcseg.p);
+    }
+    HIPCHK(hipGetLastError());
+    std::vector<uint64_t> ends(segs.size());
+    HIPCHK(hipMemcpyAsync(ends.data(), (const uint8_t*)g.crcseg.p + o_dst, 8 * ends.size(), hipMemcpyDeviceToHost, g.stream));
+    HIPCHK(hipStreamSynchronize(g.stream));
+    for (size_t k = 0; k < who.size(); k++) t.jobs[who[k]].end_bit = ends[k];
   }
   return ZES_OK;
 }
@@ -2412,6 +2454,10 @@ int inflate_jobs(const uint8_t* d_in, uint8_t* d_out, std::vector<InfJob>& jobs,
         }
         ZesRes* hres = g.pinned->t1.res;
         HIPCHK(hipMemcpyAsync(hres, g.res.p, sizeof(ZesRes) * nb, hipMemcpyDeviceToHost, g.stream));
+        bool want_end = false;  // (k_inf_decode leaves the bit behind a stream it finished in the first of its two words)
+        for (uint32_t k = 0; k < nb; k++) want_end = want_end || jobs[rest[g0 + k]].want_end;
+        const uint64_t* hend = g.pinned->t1.ends;
+        if (want_end) HIPCHK(hipMemcpyAsync(g.pinned->t1.ends, g.resume.p, (size_t)16 * nb, hipMemcpyDeviceToHost, g.stream));
         HIPCHK(hipStreamSynchronize(g.stream));
         for (uint32_t k = 0; k < nb; k++) {
           if (hres[k].status != 0) continue;
@@ -2419,6 +2465,7 @@ int inflate_jobs(const uint8_t* d_in, uint8_t* d_out, std::vector<InfJob>& jobs,
           j.tier = 3;
           j.out_len = hres[k].out_len;
           j.status = hres[k].out_len > j.cap ? ZES_E_NOSPACE : ZES_OK;
+          if (j.want_end) j.end_bit = hend[2 * k];
         }
       }
     }
@@ -3546,6 +3593,75 @@ int zes_crc32(const uint8_t* in, uint64_t n, uint32_t* crc) {
   return rc;
 }
 
+// Segmented CRC-32 (k_crc32_seg): crc[i] of d[segs[i].off, + segs[i].len) for all i in one launch.  The work items are
+// (buffer, 64 KiB chunk of memory) pairs, listed here from the lengths exactly as the kernel cuts a buffer; the kernel
+// leaves two words per buffer, finished here (two GF(2) multiplies per buffer; the powers are kept per length, a batch
+// of BGZF members has two or three different ones).
+static int crc32_batch_locked(const uint8_t* d, const ZesCrcSeg* segs, uint32_t count, uint32_t* crc) {
+  int rc;
+  struct Item {
+    uint32_t buf, chunk;
+  };
+  std::vector<Item> work;
+  std::vector<uint64_t> last(count);  // bytes of a buffer's last work item
+  work.reserve(count);
+  uint64_t maxlen = 0;
+  for (uint32_t i = 0; i < count; i++) {
+    if (!segs[i].len) continue;
+    const uint64_t a = (uint64_t)(uintptr_t)d + segs[i].off, end = a + segs[i].len;
+    const uint64_t A = a & ~(uint64_t)15, E = std::max<uint64_t>(end & ~(uint64_t)15, a);
+    const uint64_t nch = E > a ? (E - A + CRC_CHUNK - 1) / CRC_CHUNK : 1;
+    if (work.size() + nch >= (1ull << 31)) return ZES_E_ARG;
+    for (uint64_t j = 0; j < nch; j++) work.push_back({i, (uint32_t)j});
+    last[i] = end - std::max<uint64_t>(a, A + (nch - 1) * CRC_CHUNK);
+    maxlen = std::max(maxlen, segs[i].len);
+  }
+  for (uint32_t i = 0; i < count; i++) crc[i] = 0;  // (of no bytes)
+  if (work.empty()) return ZES_OK;
+  if ((rc = crc_ready(maxlen + 2 * CRC_CHUNK))) return rc;
+  const size_t o_work = sizeof(ZesCrcSeg) * (size_t)count, o_acc = o_work + sizeof(Item) * work.size();
+  if ((rc = ensure(g.crcseg, o_acc + 8 * (size_t)count))) return rc;
+  uint8_t* base = (uint8_t*)g.crcseg.p;
+  HIPCHK(hipMemcpyAsync(base, segs, o_work, hipMemcpyHostToDevice, g.stream));
+  HIPCHK(hipMemcpyAsync(base + o_work, work.data(), sizeof(Item) * work.size(), hipMemcpyHostToDevice, g.stream));
+  HIPCHK(hipMemsetAsync(base + o_acc, 0, 8 * (size_t)count, g.stream));
+  {
+    Timed t("k_crc32_seg");
+    hipLaunchKernelGGL(k_crc32_seg, dim3((uint32_t)work.size()), dim3(CRC_THREADS), 0, g.stream, d, (const ZesCrcSeg*)base, (const uint2*)(base + o_work),
+                       (const uint32_t*)g.crctab.p, (unsigned int*)(base + o_acc));
+  }
+  HIPCHK(hipGetLastError());
+  std::vector<uint32_t> acc(2 * (size_t)count);
+  HIPCHK(hipMemcpyAsync(acc.data(), base + o_acc, 8 * (size_t)count, hipMemcpyDeviceToHost, g.stream));
+  HIPCHK(hipStreamSynchronize(g.stream));
+  std::map<uint64_t, uint32_t> pw;  // x^(8k)
+  auto shift = [&](uint32_t v, uint64_t k) {
+    auto it = pw.find(k);
+    if (it == pw.end()) it = pw.emplace(k, zes_crc_shift(0x80000000u, k)).first;
+    return zes_crc_mul(it->second, v);
+  };
+  for (uint32_t i = 0; i < count; i++) {
+    if (!segs[i].len) continue;
+    const uint32_t raw = shift(acc[2 * (size_t)i], last[i]) ^ acc[2 * (size_t)i + 1];
+    crc[i] = raw ^ shift(0xFFFFFFFFu, segs[i].len) ^ 0xFFFFFFFFu;
+  }
+  return ZES_OK;
+}
+
+int zes_crc32_batch_dev(const uint8_t* d_in, const uint64_t* off, const uint64_t* len, uint32_t* crc, uint32_t count) {
+  ROUTE_DEV(d_in);
+  if (count && (!off || !len || !crc)) return ZES_E_ARG;
+  LOCK_READY();
+  std::vector<ZesCrcSeg> segs(count);
+  for (uint32_t i = 0; i < count; i++) {
+    if (len[i] && !d_in) return ZES_E_ARG;
+    segs[i] = ZesCrcSeg{off[i], len[i]};
+  }
+  rc = crc32_batch_locked(d_in, segs.data(), count, crc);
+  collect_times();
+  return rc;
+}
+
 // ---- gzip writer (RFC 1952): fixed header | zes_deflate_raw's bytes | CRC-32, ISIZE ----
 static const uint8_t kGzHeader[10] = {0x1f, 0x8b, 8, 0, 0, 0, 0, 0, 0, 0xff};  // FLG 0, MTIME 0, XFL 0, OS 255
 static uint64_t gzip_bound(uint64_t n) { return deflate_bound(n) - 6 + 18; }
@@ -3697,7 +3813,7 @@ static int grow_keep(DevBuf& b, size_t bytes, size_t keep) {
 static int gunzip_locked(GzSrc& S, uint64_t hlen, bool dev, uint8_t* d_dst, uint64_t cap, uint64_t* out_len, uint32_t flags) {
   int rc;
   uint64_t pos = 0, total = 0;
-  flags &= ~ZES_F_CHECK_ADLER;
+  flags &= ~(ZES_F_CHECK_ADLER | ZES_F_GZIP_SERIAL);
   for (bool first = true;; first = false) {
     if (!first && (rc = S.header(pos, &hlen))) return rc;
     const uint64_t body = pos + hlen;
@@ -3752,6 +3868,190 @@ static int gunzip_locked(GzSrc& S, uint64_t hlen, bool dev, uint8_t* d_dst, uint
   return (dev && total > cap) ? ZES_E_NOSPACE : ZES_OK;
 }
 
+// ---- the member-parallel reader (include/zes.h: "Member-parallel reading") ----
+// One member at h[0, avail) of a file with `left` bytes from its start on: does it qualify, and what does it say
+// (the rule of k_gz_walk, which does the same on the device)
+static bool gz_member(const uint8_t* h, uint64_t avail, uint64_t left, ZesGzMember* m) {
+  if (avail < 12 || h[0] != 0x1f || h[1] != 0x8b || h[2] != 8 || h[3] != 4) return false;
+  const uint32_t hlen = 12 + ((uint32_t)h[10] | (uint32_t)h[11] << 8);
+  if (hlen > ZES_GZ_HLEN_MAX || hlen > avail) return false;
+  uint32_t p = 12, size = 0;
+  while (p + 4 <= hlen) {
+    const uint32_t sl = (uint32_t)h[p + 2] | (uint32_t)h[p + 3] << 8;
+    if (p + 4 + sl > hlen) break;
+    if (!size && h[p] == 'B' && h[p + 1] == 'C' && sl == 2) size = ((uint32_t)h[p + 4] | (uint32_t)h[p + 5] << 8) + 1;
+    p += 4 + sl;
+  }
+  if (p != hlen || !size || hlen + 8 > size || size > left) return false;
+  m->size = size;
+  m->hlen = hlen;
+  return true;
+}
+
+// the members of the input when it is such a file from its first byte to its last (*ok), else nothing
+static int gz_walk(GzSrc& S, std::vector<ZesGzMember>& tab, bool* ok) {
+  *ok = false;
+  tab.clear();
+  if (S.h) {  // the caller's memory
+    for (uint64_t pos = 0; pos < S.c;) {
+      ZesGzMember m;
+      if (!gz_member(S.h + pos, S.c - pos, S.c - pos, &m)) return ZES_OK;
+      m.crc = get_le32(S.h + pos + m.size - 8);
+      m.isize = get_le32(S.h + pos + m.size - 4);
+      tab.push_back(m);
+      pos += m.size;
+    }
+    *ok = tab.size() >= 2;
+    return ZES_OK;
+  }
+  int rc;
+  const uint8_t* p = nullptr;
+  const uint64_t k = std::min<uint64_t>(S.c, 4096);  // (the bytes the header check has brought down already)
+  if ((rc = S.get(0, k, &p))) return rc;
+  ZesGzMember m0;
+  if (!gz_member(p, k, S.c, &m0) || m0.size >= S.c) return ZES_OK;  // an ordinary gzip file: no launch, no table
+  // the table's size: members as long as the first one, four times over (a file of shorter ones goes member by member)
+  const uint32_t cap = (uint32_t)std::min<uint64_t>({S.c / 28 + 1, 4 * (S.c / m0.size) + 1024, (uint64_t)1 << 28});
+  if (ensure(g.gz_tab, sizeof(ZesGzWalk) + sizeof(ZesGzMember) * (size_t)cap)) return ZES_OK;
+  ZesGzWalk* d_head = (ZesGzWalk*)g.gz_tab.p;
+  {
+    Timed t("k_gz_walk");
+    hipLaunchKernelGGL(k_gz_walk, dim3(1), dim3(64), 0, g.stream, S.d, S.c, d_head, (ZesGzMember*)(d_head + 1), cap);
+  }
+  HIPCHK(hipGetLastError());
+  ZesGzWalk head;
+  HIPCHK(hipMemcpyAsync(&head, d_head, sizeof head, hipMemcpyDeviceToHost, g.stream));
+  HIPCHK(hipStreamSynchronize(g.stream));
+  if (!head.ok || head.count < 2 || head.count > cap) return ZES_OK;
+  tab.resize(head.count);
+  HIPCHK(hipMemcpyAsync(tab.data(), d_head + 1, sizeof(ZesGzMember) * tab.size(), hipMemcpyDeviceToHost, g.stream));
+  HIPCHK(hipStreamSynchronize(g.stream));
+  *ok = true;
+  return ZES_OK;
+}
+
+static int gz_gather(const uint8_t* src, uint8_t* dst, const std::vector<ZesGzSeg>& segs) {
+  if (segs.empty()) return ZES_OK;
+  int rc;
+  uint64_t longest = 0;
+  for (const ZesGzSeg& s : segs) longest = std::max(longest, s.len);
+  if ((rc = ensure(g.gz_tab, sizeof(ZesGzSeg) * segs.size()))) return rc;
+  HIPCHK(hipMemcpyAsync(g.gz_tab.p, segs.data(), sizeof(ZesGzSeg) * segs.size(), hipMemcpyHostToDevice, g.stream));
+  const uint32_t ny = (uint32_t)std::min<uint64_t>(std::max<uint64_t>((longest + GZ_GATHER_PIECE - 1) / GZ_GATHER_PIECE, 1), 256);
+  Timed t("k_gz_gather");
+  hipLaunchKernelGGL(k_gz_gather, dim3((uint32_t)segs.size(), ny), dim3(GZ_GATHER_THREADS), 0, g.stream, src, dst, (const ZesGzSeg*)g.gz_tab.p);
+  HIPCHK(hipGetLastError());
+  return ZES_OK;
+}
+
+// All members as one batch: one gather of the bodies behind a 78 9C each, one inflate_jobs call, one gather of the outputs
+// that could not be decoded in place, one segmented CRC-32 launch.  *done only when every member checks out; in every
+// other case nothing has been decided (the result's memory may have been written to) and the serial path runs.
+// dev: the result goes to d_dst (capacity cap), else to g.gz_acc.
+static int gunzip_parallel(GzSrc& S, bool dev, uint8_t* d_dst, uint64_t cap, uint64_t* out_len, uint32_t flags, bool* done) {
+  *done = false;
+  int rc;
+  std::vector<ZesGzMember> tab;
+  bool ok = false;
+  // ZES_DEBUG: where the call's wall time goes
+  static const bool dbg = getenv("ZES_DEBUG") != nullptr;
+  auto now = [] { return std::chrono::steady_clock::now(); };
+  auto ms = [](std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
+  const auto t0 = now();
+  if ((rc = gz_walk(S, tab, &ok))) return rc;
+  const auto t1 = now();
+  if (!ok || tab.size() >= (1u << 28)) return ZES_OK;
+  const uint32_t n = (uint32_t)tab.size();
+  std::vector<uint64_t> pos(n), ooff(n + 1);
+  uint64_t total = 0, at = 0;
+  int64_t last_out = -1;  // the last member with output
+  for (uint32_t k = 0; k < n; k++) {
+    pos[k] = at;
+    at += tab[k].size;
+    ooff[k] = total;
+    total += tab[k].isize;
+    if (tab[k].isize) last_out = k;
+  }
+  ooff[n] = total;
+  if (dev && total > cap) return ZES_OK;
+  if (!dev && ensure(g.gz_acc, total + 64)) return ZES_OK;
+  uint8_t* dst = dev ? d_dst : (uint8_t*)g.gz_acc.p;
+  const uint64_t dst_cap = dev ? cap : g.gz_acc.cap;
+  // A member is decoded in place when the 16-byte groups the decoders write stay inside its own range; the others get a
+  // slot of their own (the members run side by side: a group that reaches into a neighbour's range would race with it)
+  auto up16 = [](uint64_t v) { return (v + 15) & ~15ull; };
+  std::vector<char> direct(n);
+  std::vector<uint64_t> islot(n), oslot(n);
+  std::vector<ZesGzSeg> segs(n);
+  uint64_t ipos = 0, opos = 0;
+  for (uint32_t k = 0; k < n; k++) {
+    const uint64_t dlen = tab[k].size - tab[k].hlen - 8, m = tab[k].isize;
+    islot[k] = ipos;
+    ipos += up16(2 + dlen) + 64;
+    segs[k] = ZesGzSeg{pos[k] + tab[k].hlen, islot[k] + 2, dlen, 1u, 0u};
+    direct[k] = dst && m && (ooff[k] & 15u) == 0 && ((m & 15u) == 0 || ((int64_t)k == last_out && up16(ooff[k] + m) <= dst_cap));
+    if (!direct[k]) {
+      oslot[k] = opos;
+      opos += std::max<uint64_t>(up16(m), 16) + 16;
+    }
+  }
+  if (ensure(g.gz_bodies, ipos + 64) || ensure(g.gz_outs, opos + 64)) return ZES_OK;
+  if ((rc = gz_gather(S.d, (uint8_t*)g.gz_bodies.p, segs))) return rc;
+  // one base for both kinds of destination (inflate_jobs takes one pointer and an offset per job): the lower of the two
+  uint8_t* outs = (uint8_t*)g.gz_outs.p;
+  uint8_t* base = dst && dst < outs ? dst : outs;
+  std::vector<InfJob> jobs(n);
+  for (uint32_t k = 0; k < n; k++) {
+    const uint64_t dlen = tab[k].size - tab[k].hlen - 8, m = tab[k].isize;
+    uint8_t* to = direct[k] ? dst + ooff[k] : outs + oslot[k];
+    jobs[k] = InfJob{islot[k], 2 + dlen, (uint64_t)(to - base), direct[k] ? m : std::max<uint64_t>(up16(m), 16), 0, ZES_OK, 0};
+    jobs[k].want_end = true;
+  }
+  const std::vector<uint8_t> firsts(n, 0x78);
+  const auto t2 = now();
+  if ((rc = inflate_jobs((const uint8_t*)g.gz_bodies.p, base, jobs, firsts.data(), flags & ~(ZES_F_CHECK_ADLER | ZES_F_GZIP_SERIAL)))) return rc;
+  if (g.profiling) g.carry = g.last_times;  // (inflate_jobs has collected what ran so far: the call's last collect_times keeps it)
+  const auto t3 = now();
+  for (uint32_t k = 0; k < n; k++) {
+    const uint64_t dlen = tab[k].size - tab[k].hlen - 8;
+    if (jobs[k].status != ZES_OK || jobs[k].out_len != tab[k].isize || jobs[k].end_bit < 16 || (jobs[k].end_bit - 16 + 7) / 8 != dlen) return ZES_OK;
+  }
+  segs.clear();
+  std::vector<ZesCrcSeg> csegs(n);
+  for (uint32_t k = 0; k < n; k++) {
+    if (!direct[k] && tab[k].isize) segs.push_back(ZesGzSeg{oslot[k], ooff[k], tab[k].isize, 0u, 0u});
+    csegs[k] = ZesCrcSeg{ooff[k], tab[k].isize};
+  }
+  if ((rc = gz_gather(outs, dst, segs))) return rc;
+  std::vector<uint32_t> crc(n);
+  if ((rc = crc32_batch_locked(dst, csegs.data(), n, crc.data()))) return rc;
+  for (uint32_t k = 0; k < n; k++)
+    if (crc[k] != tab[k].crc) return ZES_OK;
+  if (dbg)
+    fprintf(stderr, "zes gunzip, %u members as one batch: walk %.3f ms, plan + gather %.3f, inflate_jobs %.3f, gather + CRC-32 %.3f\n", n, ms(t0, t1),
+            ms(t1, t2), ms(t2, t3), ms(t3, now()));
+  *out_len = total;
+  g.last_members = (int)n;
+  *done = true;
+  return ZES_OK;
+}
+
+// the parallel path where it applies and succeeds, else the members one after the other
+static int gunzip_any(GzSrc& S, uint64_t hlen, bool dev, uint8_t* d_dst, uint64_t cap, uint64_t* out_len, uint32_t flags) {
+  g.last_members = 0;
+  if (!(flags & ZES_F_GZIP_SERIAL)) {
+    bool done = false;
+    uint64_t n = 0;
+    if (gunzip_parallel(S, dev, d_dst, cap, &n, flags, &done) == ZES_OK && done) {
+      *out_len = n;
+      return ZES_OK;
+    }
+    (void)hipGetLastError();
+    g.carry.clear();
+  }
+  return gunzip_locked(S, hlen, dev, d_dst, cap, out_len, flags);
+}
+
 int zes_gunzip_dev(const uint8_t* d_in, uint64_t c, uint8_t* d_out, uint64_t cap, uint64_t* out_len, uint32_t flags) {
   ROUTE_DEV(d_in, d_out);
   if (!out_len || (!d_in && c)) return ZES_E_ARG;
@@ -3762,7 +4062,7 @@ int zes_gunzip_dev(const uint8_t* d_in, uint64_t c, uint8_t* d_out, uint64_t cap
   GzSrc S{nullptr, d_in, c};
   uint64_t hlen = 0;
   if ((rc = S.header(0, &hlen))) return rc;
-  rc = gunzip_locked(S, hlen, true, d_out, cap, out_len, flags);
+  rc = gunzip_any(S, hlen, true, d_out, cap, out_len, flags);
   collect_times();
   return rc;
 }
@@ -3779,7 +4079,7 @@ static int gunzip_host(const uint8_t* in, uint64_t c, uint8_t* out, uint64_t cap
   if (g.gz_acc.cap < std::max<uint64_t>(c * 4, 1 << 20) && (rc = ensure(g.gz_acc, std::max<uint64_t>(c * 4, 1 << 20) + 64))) return rc;
   GzSrc S{in, (const uint8_t*)g.gz_in.p, c};
   uint64_t n = 0;
-  rc = gunzip_locked(S, hlen, false, nullptr, 0, &n, flags);
+  rc = gunzip_any(S, hlen, false, nullptr, 0, &n, flags);
   collect_times();
   if (rc) return rc;
   *out_len = n;
@@ -3939,6 +4239,12 @@ int zes_last_inflate_tier(void) {
   UseDev ud(t_last);  // the context that served this thread's last call (single host calls go round robin over the contexts)
   std::lock_guard<std::mutex> lk(g_mu);
   return g.last_tier;
+}
+
+int zes_last_gunzip_members(void) {
+  UseDev ud(t_last);
+  std::lock_guard<std::mutex> lk(g_mu);
+  return g.last_members;
 }
 
 int zes_set_profiling(int on) {

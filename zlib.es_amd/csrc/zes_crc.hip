@@ -20,6 +20,14 @@
 //             bytewise, laid out against the chunk's END: the missing bytes count as leading zeros, which leave a raw
 //             CRC unchanged, so the same per-thread constants apply.  The last chunk XORs into a second word, which
 //             the host shifts by the last chunk's length (it is the only shift that is not a multiple of 64 KiB).
+//   k_crc32_seg  many buffers at any alignment in one launch; a work item is (buffer, 64 KiB chunk).  The chunks of a buffer
+//             are cut at 64 KiB steps of MEMORY counted from the 16-byte boundary at or below its first byte, so every piece
+//             of every chunk is an aligned 16-byte load whatever the buffer's start.  A short chunk (the first one of an
+//             unaligned buffer, the last one) lays its bytes against the chunk's end as the tail above does, so the same
+//             per-thread constants apply; rows of pieces that lie wholly in front of the data are skipped.  What goes
+//             bytewise: the piece the buffer starts inside (under 16 bytes) and the bytes behind the buffer's last 16-byte
+//             boundary (under 16), which the last chunk's first thread runs through the CRC register behind the chunk's
+//             state.  Two accumulator words per buffer, as above; the host shifts word 0 by the last work item's bytes.
 #include "zes_common.h"
 #include "zes_kernels.h"
 
@@ -55,6 +63,7 @@ static uint32_t crc_x8n(uint64_t k) {
 }
 
 uint32_t zes_crc_shift(uint32_t s, uint64_t k) { return crc_mulmod(crc_x8n(k), s); }
+uint32_t zes_crc_mul(uint32_t a, uint32_t b) { return crc_mulmod(a, b); }
 
 // raw CRC of n bytes, bit by bit (host: table construction only)
 static uint32_t crc_raw_bits(const uint8_t* p, uint32_t n) {
@@ -159,5 +168,75 @@ __global__ __launch_bounds__(CRC_THREADS) void k_crc32(const uint8_t* __restrict
     for (uint32_t w = 0; w < CRC_THREADS / 64; w++) r ^= s_w[w];
     if (j + 1 == nch) atomicXor(&acc[1], r);
     else atomicXor(&acc[0], crc_mulmod(r, tab[CRC_TAB_POW + (nch - 2 - j)]));
+  }
+}
+
+// Work item w = (buffer, chunk) of segs[]; acc[2b] / acc[2b + 1] as k_crc32's two words, for buffer b.  With a = the address
+// of the buffer's first byte, A = a rounded down to 16, E = its end rounded down to 16 (a, when that lies in front of a):
+// chunk j holds [max(a, A + 64Ki * j), min(E, A + 64Ki * (j + 1))), the last one also the bytes [E, end).
+__global__ __launch_bounds__(CRC_THREADS) void k_crc32_seg(const uint8_t* __restrict__ d_in, const ZesCrcSeg* __restrict__ segs,
+                                                          const uint2* __restrict__ work, const uint32_t* __restrict__ tab,
+                                                          unsigned int* __restrict__ acc) {
+  __shared__ uint32_t s_t[CRC_TAB_LANE];
+  __shared__ uint32_t s_w[CRC_THREADS / 64];
+  const uint32_t tid = threadIdx.x;
+  for (uint32_t i = tid; i < CRC_TAB_LANE; i += CRC_THREADS) s_t[i] = tab[i];
+  const uint2 w = work[blockIdx.x];
+  const ZesCrcSeg sg = segs[w.x];
+  // (signed: virtual offset 0 of a short chunk may stand for an address below zero)
+  const int64_t a = (int64_t)(uintptr_t)d_in + (int64_t)sg.off, end = a + (int64_t)sg.len;
+  const int64_t A = a & ~15ll, E = max(end & ~15ll, a), CH = CRC_CHUNK;
+  const int64_t nch = E > a ? (E - A + CH - 1) / CH : 1, j = w.y;
+  const int64_t lo = max(a, A + j * CH);
+  const int64_t hi = max(lo, min(E, A + (j + 1) * CH));
+  const uint32_t len = (uint32_t)(hi - lo);
+  const int64_t v0 = hi - CH;  // the address virtual offset 0 stands for (16-byte aligned whenever len != 0)
+  uint32_t st = 0;
+  __syncthreads();
+  if (len == CRC_CHUNK) {
+    uint4 v[CRC_PIECES];
+#pragma unroll
+    for (uint32_t i = 0; i < CRC_PIECES; i++) v[i] = reinterpret_cast<const uint4*>((uintptr_t)lo)[i * CRC_THREADS + tid];
+#pragma unroll
+    for (uint32_t i = 0; i < CRC_PIECES; i++) st = crc_piece(s_t, v[i].x ^ (i ? crc_fold(s_t, st) : 0u), v[i].y, v[i].z, v[i].w);
+  } else if (len) {
+    const uint32_t row0 = (CRC_CHUNK - len) / CRC_STRIDE;  // the first row of pieces that holds data
+    uint4 v[CRC_PIECES];
+#pragma unroll
+    for (uint32_t i = 0; i < CRC_PIECES; i++) {
+      v[i] = make_uint4(0, 0, 0, 0);
+      if (i < row0) continue;
+      const int64_t m = v0 + (int64_t)(i * CRC_THREADS + tid) * 16;
+      if (m >= lo) {
+        v[i] = *reinterpret_cast<const uint4*>((uintptr_t)m);
+      } else if (m + 16 > lo) {  // the piece the buffer starts inside
+        uint32_t d[4] = {0, 0, 0, 0};
+#pragma unroll
+        for (uint32_t b = 0; b < 16; b++)
+          if (m + b >= lo) d[b >> 2] |= (uint32_t)(*reinterpret_cast<const uint8_t*>((uintptr_t)(m + b))) << (8 * (b & 3));
+        v[i] = make_uint4(d[0], d[1], d[2], d[3]);
+      }
+    }
+#pragma unroll
+    for (uint32_t i = 0; i < CRC_PIECES; i++)
+      if (i >= row0) st = crc_piece(s_t, v[i].x ^ crc_fold(s_t, st), v[i].y, v[i].z, v[i].w);
+  }
+  st = crc_mulmod(st, tab[CRC_TAB_LANE + tid]);
+#pragma unroll
+  for (int m = 32; m >= 1; m >>= 1) st ^= (uint32_t)__shfl_xor((int)st, m, 64);
+  if ((tid & 63u) == 0) s_w[tid >> 6] = st;
+  __syncthreads();
+  if (tid == 0) {
+    uint32_t r = 0;
+    for (uint32_t k = 0; k < CRC_THREADS / 64; k++) r ^= s_w[k];
+    if (j + 1 == nch) {
+      for (int64_t q = E; q < end; q++) {  // behind the last 16-byte boundary: through the register, bit by bit
+        r ^= *reinterpret_cast<const uint8_t*>((uintptr_t)q);
+        for (int b = 0; b < 8; b++) r = (r >> 1) ^ (CRC_POLY & (0u - (r & 1u)));
+      }
+      atomicXor(&acc[2 * (size_t)w.x + 1], r);
+    } else {
+      atomicXor(&acc[2 * (size_t)w.x], crc_mulmod(r, tab[CRC_TAB_POW + (nch - 2 - j)]));
+    }
   }
 }

@@ -1,0 +1,113 @@
+// zes_gzip.hip — device pieces of the member-parallel gzip reader (zes_api.hip: gunzip_parallel).
+//
+// A file whose members all state their own size — BGZF, the format of bgzip / htslib: every member's extra field holds a
+// subfield 'B','C' with BSIZE = member size - 1 — can be cut into its members without decoding anything.
+//
+//   k_gz_walk    one wavefront follows the chain of members from byte 0.  The chain is serial (a member's position is the
+//                sum of the sizes before it), so a hop costs one memory round trip: the 64 lanes fetch the 256 bytes at the
+//                member's start as one coalesced access, a dword per lane, and the header is then parsed from the lanes'
+//                registers with uniform lane reads.  The member's trailer (CRC-32, ISIZE) is fetched by eight lanes once
+//                its size is known and stored while the next header is on its way, so it adds no round trip of its own.
+//   k_gz_gather  a segmented copy, {src_off, dst_off, len} per segment at any alignment on both sides: workgroup (s, y)
+//                takes the 64 KiB pieces y, y + gridDim.y, ... of segment s.  The destination's whole 16-byte groups are
+//                written as 16-byte stores; a group's bytes come from the two aligned 16-byte groups of the source that hold
+//                them (one, when both sides are aligned alike), shifted into place.  Only groups that hold bytes of the
+//                segment are read, and only the segment's bytes are written; the under-16-byte head and tail go bytewise.
+#include "zes_common.h"
+#include "zes_kernels.h"
+
+__global__ __launch_bounds__(64) void k_gz_walk(const uint8_t* __restrict__ d_in, uint64_t c, ZesGzWalk* __restrict__ head,
+                                               ZesGzMember* __restrict__ tab, uint32_t cap) {
+  const uint32_t lane = threadIdx.x;
+  uint64_t pos = 0;
+  uint32_t k = 0, tb = 0;
+  bool ok = true;
+  while (pos < c) {
+    if (k >= cap) {
+      ok = false;
+      break;
+    }
+    uint32_t w = 0;
+#pragma unroll
+    for (uint32_t b = 0; b < 4; b++) {
+      const uint64_t o = pos + lane * 4 + b;
+      if (o < c) w |= (uint32_t)d_in[o] << (8 * b);
+    }
+    if (k && lane < 8) reinterpret_cast<uint8_t*>(&tab[k - 1])[8 + lane] = (uint8_t)tb;  // the member before: its trailer has arrived
+    // byte i of the window, the same value in every lane
+    auto B = [&](uint32_t i) -> uint32_t { return ((uint32_t)__builtin_amdgcn_readlane((int)w, (int)(i >> 2)) >> (8 * (i & 3u))) & 255u; };
+    const uint64_t left = c - pos;
+    const uint32_t hlen = 12 + (B(10) | B(11) << 8);
+    bool q = B(0) == 0x1f && B(1) == 0x8b && B(2) == 8 && B(3) == 4 && hlen <= ZES_GZ_HLEN_MAX && hlen <= left;
+    uint32_t p = 12, size = 0;
+    while (q && p + 4 <= hlen) {  // the extra field, subfield by subfield
+      const uint32_t sl = B(p + 2) | B(p + 3) << 8;
+      if (p + 4 + sl > hlen) break;
+      if (!size && B(p) == 'B' && B(p + 1) == 'C' && sl == 2) size = (B(p + 4) | B(p + 5) << 8) + 1;
+      p += 4 + sl;
+    }
+    q = q && p == hlen && size && hlen + 8 <= size && size <= left;
+    if (!q) {
+      ok = false;
+      break;
+    }
+    if (lane == 0) {
+      tab[k].size = size;
+      tab[k].hlen = hlen;
+    }
+    pos += size;
+    tb = lane < 8 ? d_in[pos - 8 + lane] : 0u;
+    k++;
+  }
+  if (k && lane < 8) reinterpret_cast<uint8_t*>(&tab[k - 1])[8 + lane] = (uint8_t)tb;
+  if (lane == 0) {
+    head->count = k;
+    head->ok = ok && k >= 2 && pos == c;
+    head->end = pos;
+  }
+}
+
+__global__ __launch_bounds__(GZ_GATHER_THREADS) void k_gz_gather(const uint8_t* __restrict__ src, uint8_t* __restrict__ dst,
+                                                                const ZesGzSeg* __restrict__ segs) {
+  const ZesGzSeg sg = segs[blockIdx.x];
+  const uint32_t tid = threadIdx.x;
+  const uint8_t* s = src + sg.src_off;
+  uint8_t* d = dst + sg.dst_off;
+  if (sg.zhdr && blockIdx.y == 0 && tid < 2) d[(int)tid - 2] = tid ? 0x9C : 0x78;
+  // [0, head): in front of the destination's first 16-byte boundary; [head, head + 16 * groups): whole groups; the rest: tail
+  const uint64_t head = min(sg.len, (uint64_t)((0 - (uintptr_t)d) & 15u));
+  const uint64_t groups = (sg.len - head) / 16;
+  if (blockIdx.y == 0) {
+    if (tid < head) d[tid] = s[tid];
+    const uint64_t t0 = head + groups * 16;
+    if (t0 + tid < sg.len) d[t0 + tid] = s[t0 + tid];
+  }
+  const uint8_t* sa = s + head;                     // the source of group 0
+  const uint32_t sh = (uint32_t)((uintptr_t)sa & 15u);  // (the same for every group of the segment)
+  const uint4* s16 = reinterpret_cast<const uint4*>(sa - sh);
+  uint4* d16 = reinterpret_cast<uint4*>(d + head);
+  const uint32_t qd = sh >> 2, rb = 8 * (sh & 3u);
+  constexpr uint64_t PIECE_GROUPS = GZ_GATHER_PIECE / 16;
+  for (uint64_t g0 = (uint64_t)blockIdx.y * PIECE_GROUPS; g0 < groups; g0 += (uint64_t)gridDim.y * PIECE_GROUPS) {
+    const uint64_t g1 = min(groups, g0 + PIECE_GROUPS);
+#pragma unroll 4
+    for (uint64_t gi = g0 + tid; gi < g1; gi += GZ_GATHER_THREADS) {
+      const uint4 lo = s16[gi];
+      if (sh == 0) {
+        d16[gi] = lo;
+        continue;
+      }
+      const uint4 hi = s16[gi + 1];  // (sh != 0: the group's last bytes lie in it)
+      const uint32_t v[8] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
+      uint32_t e[5];
+#pragma unroll
+      for (uint32_t k = 0; k < 5; k++) e[k] = qd == 0 ? v[k] : qd == 1 ? v[k + 1] : qd == 2 ? v[k + 2] : v[k + 3];
+      uint4 o;
+      o.x = (uint32_t)((((uint64_t)e[1] << 32) | e[0]) >> rb);
+      o.y = (uint32_t)((((uint64_t)e[2] << 32) | e[1]) >> rb);
+      o.z = (uint32_t)((((uint64_t)e[3] << 32) | e[2]) >> rb);
+      o.w = (uint32_t)((((uint64_t)e[4] << 32) | e[3]) >> rb);
+      d16[gi] = o;
+    }
+  }
+}

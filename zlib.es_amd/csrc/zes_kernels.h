@@ -116,8 +116,37 @@ struct ZesSegOut {
   uint32_t hist;  // bytes of output in front of out_off that exist (a later piece of a long stream: up to 32768)
 };
 
+// k_crc32_seg (zes_crc.hip): one buffer of a batch, bytes [off, off + len) of the input
+struct ZesCrcSeg {
+  uint64_t off, len;
+};
+
+// k_gz_walk (zes_gzip.hip): one member of a file whose members all state their size (BGZF); a member's position is the sum
+// of the sizes before it
+struct ZesGzMember {
+  uint32_t size;   // the whole member, header to ISIZE (BSIZE + 1)
+  uint32_t hlen;   // its header
+  uint32_t crc;    // its trailer: CRC-32 ...
+  uint32_t isize;  // ... and length of its output
+};
+struct ZesGzWalk {
+  uint32_t count;  // members written to the table
+  uint32_t ok;     // 1: at least two members, all of them qualify, the last one ends with the input
+  uint64_t end;    // where the walk stopped
+};
+#define ZES_GZ_HLEN_MAX 256u  // a member with a longer header does not qualify (the walk reads a header as one window)
+// k_gz_gather: one segment of a segmented copy
+struct ZesGzSeg {
+  uint64_t src_off, dst_off, len;
+  uint32_t zhdr;  // 1: the two bytes in front of the destination become 78 9C
+  uint32_t pad;
+};
+#define GZ_GATHER_THREADS 256u
+#define GZ_GATHER_PIECE 65536u  // a workgroup's share of a segment
+
 // CRC-32 host arithmetic (zes_crc.hip): shift(s, k) = s * x^(8k) mod P; the kernel's table with npow powers
 uint32_t zes_crc_shift(uint32_t s, uint64_t k);
+uint32_t zes_crc_mul(uint32_t a, uint32_t b);  // a * b mod P (zes_crc_shift(0x80000000, k) is x^(8k): a shift kept for many uses)
 uint32_t zes_crc_host(const uint8_t* p, uint64_t n);  // CRC-32 of a few bytes on the host (gzip header check)
 void zes_crc_tables(uint32_t* tab, uint32_t npow);
 
@@ -187,6 +216,10 @@ __global__ void k_huff_lengths_only(const uint32_t*, uint32_t, uint32_t, uint8_t
 __global__ void k_selftest_lds_order(unsigned long long*, uint32_t, uint32_t);
 __global__ void k_adler(const uint8_t*, uint64_t, uint64_t, unsigned long long*);
 __global__ void k_crc32(const uint8_t*, uint64_t, const uint32_t*, unsigned int*);
+__global__ void k_crc32_seg(const uint8_t*, const ZesCrcSeg*, const uint2*, const uint32_t*, unsigned int*);
+// gzip reader (zes_gzip.hip)
+__global__ void k_gz_walk(const uint8_t*, uint64_t, ZesGzWalk*, ZesGzMember*, uint32_t);
+__global__ void k_gz_gather(const uint8_t*, uint8_t*, const ZesGzSeg*);
 __global__ void k_adler_blocks(const uint8_t*, const ZesBuf*, const ZesBlk*, unsigned long long*);
 __global__ void k_layout(uint8_t*, const ZesBuf*, ZesBlk*, const unsigned long long*, ZesRes*);
 __global__ void k_emit(uint8_t*, const ZesBuf*, const ZesBlk*, const uint32_t*, const uint32_t*, const uint32_t*);

@@ -641,6 +641,13 @@ napi_value InitDevices(napi_env env, napi_callback_info info) {
   return v;
 }
 
+// lastGunzipMembers(): members the member-parallel path decoded in this thread's last gunzip() (zes_last_gunzip_members)
+napi_value LastGunzipMembers(napi_env env, napi_callback_info) {
+  napi_value v;
+  napi_create_int32(env, zes_last_gunzip_members(), &v);
+  return v;
+}
+
 // trim(): the library's pooled device scratch goes back to the driver (zes_trim); the next call allocates again
 napi_value Trim(napi_env env, napi_callback_info) {
   g_big.clear();
@@ -969,6 +976,7 @@ napi_value ModuleInit(napi_env env, napi_value exports) {
       {"adler32", nullptr, swept<Adler32>, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"gzip", nullptr, swept<Gzip>, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"gunzip", nullptr, swept<Gunzip>, nullptr, nullptr, nullptr, napi_default, nullptr},
+      {"lastGunzipMembers", nullptr, swept<LastGunzipMembers>, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"init", nullptr, swept<Init>, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"initDevices", nullptr, swept<InitDevices>, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"trim", nullptr, swept<Trim>, nullptr, nullptr, nullptr, napi_default, nullptr},

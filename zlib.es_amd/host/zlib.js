@@ -91,6 +91,14 @@ function gunzip(input) {
   return addon.gunzip(input);
 }
 
+/**
+ * Extra: how many members the last gunzip() of this thread decoded as one batch (a BGZF file: all of them, the
+ * end-of-file marker included); 0 when the members went one after the other.
+ */
+function lastGunzipMembers() {
+  return addon.lastGunzipMembers();
+}
+
 /** Extra (not in the reference API): Adler-32 of a buffer, computed on the GPU. */
 function adler32(input) {
   return addon.adler32(input);
@@ -129,6 +137,7 @@ exports.inflateBatchAsync = inflateBatchAsync;
 exports.allocPinned = allocPinned;
 exports.gzip = gzip;
 exports.gunzip = gunzip;
+exports.lastGunzipMembers = lastGunzipMembers;
 exports.adler32 = adler32;
 exports.init = init;
 exports.initDevices = initDevices;

@@ -16,6 +16,7 @@ export const allocPinned = z.allocPinned;
 export const adler32 = z.adler32;
 export const gzip = z.gzip;
 export const gunzip = z.gunzip;
+export const lastGunzipMembers = z.lastGunzipMembers;
 export const init = z.init;
 export const initDevices = z.initDevices;
 export const trim = z.trim;

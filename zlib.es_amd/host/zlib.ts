@@ -90,6 +90,14 @@ export function gunzip(input: Uint8Array): Uint8Array {
   return addon.gunzip(input);
 }
 
+/**
+ * Extra: how many members the last gunzip() of this thread decoded as one batch (a BGZF file: all of them, the
+ * end-of-file marker included); 0 when the members went one after the other.
+ */
+export function lastGunzipMembers(): number {
+  return addon.lastGunzipMembers();
+}
+
 /** Extra (not in the reference API): Adler-32 of a buffer, computed on the GPU. */
 export function adler32(input: Uint8Array): number {
   return addon.adler32(input);
