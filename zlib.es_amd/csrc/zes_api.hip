@@ -31,6 +31,7 @@ namespace {
 struct DevBuf {
   void* p = nullptr;
   size_t cap = 0;
+  uint32_t gen = 0;  // how often its memory has been given back (release): what a note about its contents records (SurvList)
 };
 
 struct KTime {
@@ -157,6 +158,24 @@ static_assert(disjoint({PIN_SPAN(t2.search), PIN_SPAN(t2.ncand), PIN_SPAN(t2.nsu
   /* device tables (members, segments); segmented CRC-32: its buffers, work items and accumulator words */                        \
   X(crctab) X(crcacc) X(gz_in) X(gz_acc) X(gz_stage) X(gz_bodies) X(gz_outs) X(gz_tab) X(crcseg)
 
+// The survivor list of the block-start search as the block-parallel tier's scan left it in a pool (one buffer): the
+// segment-parallel tier's search of the same stream starts from it instead of scanning again.  The note holds until it
+// is dropped (the list is about to be rewritten, or another call begins: the bytes behind a pointer may have changed) or
+// the pool's memory is given back (ensure, zes_trim, shutdown) - a new block may come back at the old address.
+struct SurvList {
+  bool ok = false;
+  const uint8_t* d_in = nullptr;
+  uint64_t in_off = 0, c = 0;
+  uint32_t n = 0, gen = 0;
+  void note(const DevBuf& list, const uint8_t* din, uint64_t off, uint64_t len, uint32_t nsurv) {
+    ok = true, d_in = din, in_off = off, c = len, n = nsurv, gen = list.gen;
+  }
+  bool holds(const DevBuf& list, const uint8_t* din, uint64_t off, uint64_t len) const {  // this stream's list, whole, still in `list`
+    return ok && gen == list.gen && list.p != nullptr && d_in == din && in_off == off && c == len;
+  }
+  void drop() { ok = false; }
+};
+
 struct Ctx {
   bool ready = false;
   int device = -1;
@@ -187,13 +206,7 @@ struct Ctx {
   std::vector<std::string> name_pool;
   int last_tier = 0;
   int last_members = 0;  // members the member-parallel gzip reader decoded in the last gunzip call (0: the serial path answered)
-  // the survivor list of the block-start search as the block-parallel tier's scan left it (one buffer): the segment-parallel
-  // tier's search of the same stream starts from it instead of scanning again
-  bool sv_ok = false;
-  const uint8_t* sv_din = nullptr;
-  const void* sv_list = nullptr;  // (g.surv.p when the list was made: a pool that has grown since holds something else)
-  uint64_t sv_in_off = 0, sv_c = 0;
-  uint32_t sv_n = 0;
+  SurvList sv;  // (of `surv`)
   char arch[64] = {0};
   int cus = 0;
   uint64_t hbm = 0;
@@ -245,11 +258,19 @@ struct UseDev {                  // a call's context for its duration (nested en
     }                                                                                          \
   } while (0)
 
-int ensure(DevBuf& b, size_t bytes) {
-  if (bytes <= b.cap) return ZES_OK;
-  if (b.p) HIPCHK(hipFree(b.p));
+// gives a buffer's memory back: every place that frees one goes through here, so that a note about what the buffer held
+// (SurvList) can tell
+hipError_t release(DevBuf& b) {
+  const hipError_t e = b.p ? hipFree(b.p) : hipSuccess;
   b.p = nullptr;
   b.cap = 0;
+  b.gen++;
+  return e;
+}
+
+int ensure(DevBuf& b, size_t bytes) {
+  if (bytes <= b.cap) return ZES_OK;
+  HIPCHK(release(b));
   size_t want = bytes + bytes / 8 + 4096;
   HIPCHK(hipMalloc(&b.p, want));
   b.cap = want;
@@ -988,6 +1009,17 @@ struct InfJob {
   bool want_end = false;
 };
 
+// a job's entry of a table of buffers: where its stream and its output are; the rest is zero, and each caller's own
+ZesInfBuf inf_buf(const InfJob& j) {
+  ZesInfBuf b;
+  memset(&b, 0, sizeof b);
+  b.in_off = j.in_off;
+  b.c = j.c;
+  b.out_off = j.out_off;
+  b.cap = j.cap;
+  return b;
+}
+
 bool t1_eligible(const InfJob& j, uint32_t flags) { return !(flags & (ZES_F_NO_FASTPATH | ZES_F_PIECES)) && j.c >= 64 && j.c < (1ull << 29); }
 
 // The header test of the block-start search, two launches: k_inf_verify (a lane per survivor, the first VERIFY_STEPS
@@ -1092,7 +1124,7 @@ int launch_search(const uint8_t* d_in, const ZesInfBuf* dbufs, uint32_t nbuf, ui
                   uint32_t* cnt, uint8_t* first, SearchMode mode, uint64_t total_c) {
   {
     Timed t("k_inf_scan");
-    g.sv_ok = false;
+    g.sv.drop();
     hipLaunchKernelGGL(k_inf_scan, dim3(chunks), dim3(INF_SCAN_THREADS), 0, g.stream, d_in, dbufs, nbuf, (unsigned long long*)g.surv.p,
                        surv_cap, counters, first, mode.scan, (const uint8_t*)g.kraft.p);
   }
@@ -1173,16 +1205,11 @@ bool t1_first_byte(T1Group& t, uint32_t i, uint8_t fb) {
 // step 1: the table of buffers, the pools sized for it, both on their way to the device
 int t1_table(T1Group& t) {
   int rc;
-  g.sv_ok = false;  // (g.surv is about to be rewritten)
+  g.sv.drop();  // (g.surv is about to be rewritten)
   ZesInfBuf* hb = t.hb;
   for (uint32_t i = 0; i < t.nbuf; i++) {
     const InfJob& j = t.jobs[t.ids[i]];
-    ZesInfBuf& b = hb[i];
-    memset(&b, 0, sizeof b);
-    b.in_off = j.in_off;
-    b.c = j.c;
-    b.out_off = j.out_off;
-    b.cap = j.cap;
+    ZesInfBuf& b = hb[i] = inf_buf(j);
     b.first_chunk = (uint32_t)t.chunks;
     b.cand_base = (uint32_t)t.cands;
     // a reference-made stream has one block per 131072 bytes of output: more candidates than the caller's capacity
@@ -1327,14 +1354,8 @@ int t1_verdicts(T1Group& t) {
     const InfJob& j = t.jobs[t.ids[0]];
     if (t1_first_byte(t, 0, ((const uint8_t*)(hc + 5))[0])) return T1_OVER;
     t.ncand[0] = hc[4];
-    if (nsurv != 0 && nsurv <= t.surv_cap && !(t.flags & ZES_F_LOOSE_CANDIDATES)) {  // the scan ran to its end and its list is whole
-      g.sv_ok = true;
-      g.sv_din = t.d_in;
-      g.sv_list = g.surv.p;
-      g.sv_in_off = j.in_off;
-      g.sv_c = j.c;
-      g.sv_n = nsurv;
-    }
+    if (nsurv != 0 && nsurv <= t.surv_cap && !(t.flags & ZES_F_LOOSE_CANDIDATES))  // the scan ran to its end and its list is whole
+      g.sv.note(g.surv, t.d_in, j.in_off, j.c, nsurv);
     // nothing that looks like this format, a poisoned count, or more candidates than were launched
     if (nsurv == 0 || nsurv > t.surv_cap || t.ncand[0] == 0 || t.ncand[0] > t.hb[0].cand_cap || t.ncand[0] > t.work) return T1_OVER;
     t.hb[0].work_first = 0;
@@ -1699,38 +1720,90 @@ constexpr uint64_t SERIAL_BATCH_MAX_C = 8ull << 10;  // (round 3: 128 KiB -> 8 K
 constexpr uint64_t SEG_PIECES_MIN_C = 48ull << 20;  // streams from this size on go through the tier in pieces of 32 MiB (inflate_segments_pieces)
 constexpr uint32_t SEG_GROUP_WORK = 8192;    // work items per segment launch (each owns a 64 KiB map)
 
-// One group: buffers ids[0..nb) with their sorted candidate lists at cand_sorted + cbase[k], ncand[k] entries.
-int inflate_segments_run(const uint8_t* d_in, uint8_t* d_out, InfJob* jobs, const uint32_t* ids, const uint32_t* cbase, const uint32_t* ncand,
-                         uint32_t nb, uint32_t* dscratch /* 2 * nb + 1 words: chain segments not in the store, failure flags, far-match counter */) {
+// The device words of one group of nb buffers, as word offsets into g.counters: the search's scan/verify words and its
+// candidate count per buffer; then what a segment run over nr <= nb of the buffers keeps (chain segments that are not in
+// the symbol store, per buffer; failure flags, per buffer; the counter of matches behind the short marker ring); the
+// first-byte sink of the search (a byte per buffer).
+struct SegWords {
+  size_t scan, cnt, novf, fail, far, sink, sink_words, total;  // (novf .. far: one piece, cleared before a run starts)
+};
+constexpr SegWords seg_words(size_t nb, size_t nr) {
+  SegWords w{};
+  w.scan = 0;
+  w.cnt = 4;
+  w.novf = w.cnt + nb;
+  w.fail = w.novf + nr;
+  w.far = w.fail + nr;
+  w.sink = w.novf + 2 * nb + 4;
+  w.sink_words = (nb + 3) / 4;
+  w.total = w.sink + 4 + w.sink_words;
+  return w;
+}
+constexpr bool seg_words_apart(size_t nb, size_t nr) {
+  const SegWords w = seg_words(nb, nr);
+  return disjoint({PinSpan{w.scan, 4}, PinSpan{w.cnt, nb}, PinSpan{w.novf, nr}, PinSpan{w.fail, nr}, PinSpan{w.far, 1}, PinSpan{w.sink, w.sink_words}}) && w.far + 1 <= w.sink &&
+         w.sink + w.sink_words <= w.total && w.fail == w.novf + nr && w.far == w.fail + nr;
+}
+static_assert(seg_words_apart(SEG_GROUP_BUFS, SEG_GROUP_BUFS) && seg_words_apart(SEG_GROUP_BUFS, 1) && seg_words_apart(1, 1), "T2 device words overlap");
+static_assert(seg_words(SEG_GROUP_BUFS, 1).total == 4 + SEG_GROUP_BUFS + 2 * SEG_GROUP_BUFS + 4 + 4 + (SEG_GROUP_BUFS + 3) / 4,
+              "the group's counter scratch is not the size inflate_segments has always asked for");
+
+// One segment run between the steps of inflate_segments_run: buffers ids[0..nb) with their sorted candidate lists at
+// cand_sorted + cbase[k], ncand[k] entries.
+struct T2Run {
+  const uint8_t* d_in;
+  uint8_t* d_out;
+  InfJob* jobs;
+  const uint32_t *ids, *cbase, *ncand;
+  uint32_t nb;
+  ZesSegJob* hj;   // page-locked: the job table, ...
+  uint32_t* hs;    // ... [0, nb): not-in-store counts, later failure flags; [nb]: declined items, ...
+  ZesRes* hres;    // ... the chains, then where they ended
+  uint32_t *novf_d, *fail_d, *far_d;  // device words (SegWords)
+  uint32_t work = 0, ratio = 0;       // work items; 16-bit symbols per compressed byte in the symbol store (0: no store)
+  uint64_t share_syms = 0, bump_syms = 0;
+  bool blockpar = false;              // the block decoder goes first
+  uint32_t* fail_list = nullptr;      // what it declined: count, items
+  std::vector<uint32_t> last_stuck;   // per buffer: the item its chain stood in front of when that item went to the wave decoder
+  std::vector<uint32_t> novf;         // verdicts: hs and hres, copied out of the page-locked area before it is used again
+  std::vector<ZesRes> hr;
+  std::vector<char> go;               // the buffer's bytes are to be written
+};
+constexpr int T2_OVER = 1;  // a step's answer beside ZES_OK and an error: nothing more for this run
+constexpr uint32_t T2_NONE = 0xFFFFFFFFu;
+
+// step 1: the symbol store's size, the job table, the pools, table and cleared words on their way, the items' order
+int t2_plan(T2Run& t) {
   int rc;
-  ZesSegJob* hj = g.pinned->t2.jobs;
-  uint32_t work = 0;
+  const uint32_t nb = t.nb;
+  ZesSegJob* hj = t.hj;
   uint64_t csum = 0;
-  for (uint32_t k = 0; k < nb; k++) csum += jobs[ids[k]].c + 64;
+  for (uint32_t k = 0; k < nb; k++) csum += t.jobs[t.ids[k]].c + 64;
   // symbol store: `ratio` 16-bit symbols per compressed byte (a segment that inflates further is decoded twice);
   // as many as a 2 GiB store holds, up to DEFLATE's own limit of 1032 bytes per compressed byte
-  uint32_t ratio = (uint32_t)std::min<uint64_t>(1032, (2ull << 30) / (2 * csum)) & ~1u;
-  if (ratio < 4) ratio = 0;
+  t.ratio = (uint32_t)std::min<uint64_t>(1032, (2ull << 30) / (2 * csum)) & ~1u;
+  if (t.ratio < 4) t.ratio = 0;
   // behind the shares: a common area of a quarter of their size (at least 64 MiB), handed out by need to blocks whose
   // share is too small for them (a false candidate inside the block has cut it short, or the block inflates further)
-  const uint64_t share_syms = (uint64_t)csum * ratio;
-  const uint64_t bump_syms = ratio ? std::max<uint64_t>(share_syms / 4, 32ull << 20) & ~7ull : 0;
-  if (ratio && ensure(g.sym16, (size_t)(share_syms + bump_syms) * 2 + 64)) ratio = 0;  // no memory for it: two decodes
+  t.share_syms = (uint64_t)csum * t.ratio;
+  t.bump_syms = t.ratio ? std::max<uint64_t>(t.share_syms / 4, 32ull << 20) & ~7ull : 0;
+  if (t.ratio && ensure(g.sym16, (size_t)(t.share_syms + t.bump_syms) * 2 + 64)) t.ratio = 0;  // no memory for it: two decodes
   uint64_t sym_base = 0;
   for (uint32_t k = 0; k < nb; k++) {
-    const InfJob& j = jobs[ids[k]];
+    const InfJob& j = t.jobs[t.ids[k]];
     hj[k].in_off = j.in_off;
     hj[k].c = j.c;
     hj[k].sym_base = sym_base;
-    hj[k].cand_base = cbase[k];
-    hj[k].ncand = ncand[k];
-    hj[k].work_first = work;
+    hj[k].cand_base = t.cbase[k];
+    hj[k].ncand = t.ncand[k];
+    hj[k].work_first = t.work;
     hj[k].nseg = 0;
     hj[k].start0 = j.start0;
     hj[k].flags = j.partial ? ZES_SEG_PARTIAL : 0u;
-    work += ncand[k] + 1;
-    sym_base += (j.c + 64) * ratio / 2;
+    t.work += t.ncand[k] + 1;
+    sym_base += (j.c + 64) * t.ratio / 2;
   }
+  const uint32_t work = t.work;
   if ((rc = ensure(g.segjobs, sizeof(ZesSegJob) * nb))) return rc;
   if ((rc = ensure(g.sres, sizeof(ZesSegRes) * work))) return rc;
   if ((rc = ensure(g.maps, (size_t)work * ZES_WINDOW * 2))) return rc;
@@ -1740,26 +1813,34 @@ int inflate_segments_run(const uint8_t* d_in, uint8_t* d_out, InfJob* jobs, cons
   if ((rc = ensure(g.symoff, (size_t)work * 8 + 8))) return rc;  // per work item: where its symbols are; behind them: the common area's fill
   if ((rc = ensure(g.res, sizeof(ZesRes) * nb * 2))) return rc;  // (second half: where a chain ended, k_inf_seg_chain)
   HIPCHK(hipMemcpyAsync(g.segjobs.p, hj, sizeof(ZesSegJob) * nb, hipMemcpyHostToDevice, g.stream));
-  HIPCHK(hipMemsetAsync(dscratch, 0, (size_t)nb * 8 + 4, g.stream));
-  uint32_t* novf_d = dscratch;
-  uint32_t* fail_d = dscratch + nb;
-  const uint32_t* cs = (const uint32_t*)g.cand_sorted.p;
-  hipLaunchKernelGGL(k_inf_seg_order, dim3(nb), dim3(1024), 0, g.stream, (const ZesSegJob*)g.segjobs.p, cs, (uint32_t*)g.segorder.p);
-  // The decoders run with the short marker ring first (three per CU instead of two); a match that reaches behind the
-  // ring takes its symbols from the symbol store, so a segment that has outgrown its share of the store and then meets
-  // such a match cannot go on: far_d counts those, and the whole group runs again with the full ring (rare: streams
-  // that inflate by more than the store's symbols per compressed byte).
-  uint32_t* far_d = dscratch + 2 * nb;
-  // Every work item first goes to the block decoder of the block-parallel tier in its any-encoder form
-  // (k_inf_seg_block_par: a workgroup per block, 1024 lanes decoding 1024 bit segments of it) — a wave that decodes a
-  // block token by token gets through ~13 MB/s.  What it declines (an item whose block is stored or fixed, is followed
-  // by a block that is not on the list, or is longer than 128 KiB) is listed, and the wave decoder runs for the list.
-  const bool blockpar = ratio != 0 && !getenv("ZES_NO_SEG_PAR");
-  uint32_t* fail_list = nullptr;
-  if (blockpar) {
+  HIPCHK(hipMemsetAsync(t.novf_d, 0, (size_t)(t.far_d + 1 - t.novf_d) * 4, g.stream));  // (not-in-store counts, failure flags, far-match counter)
+  hipLaunchKernelGGL(k_inf_seg_order, dim3(nb), dim3(1024), 0, g.stream, (const ZesSegJob*)g.segjobs.p, (const uint32_t*)g.cand_sorted.p,
+                     (uint32_t*)g.segorder.p);
+  return ZES_OK;
+}
+
+// ZES_T2_DBG: what work items first .. first + count have come to so far (numbered from 0)
+int t2_dump_items(uint32_t first, uint32_t count) {
+  std::vector<ZesSegRes> sr(count);
+  HIPCHK(hipMemcpy(sr.data(), (const ZesSegRes*)g.sres.p + first, sr.size() * sizeof(ZesSegRes), hipMemcpyDeviceToHost));
+  for (size_t w = 0; w < sr.size(); w++)
+    fprintf(stderr, "   item %zu: end_bit %llu out_len %llu flags %u next %u\n", w, (unsigned long long)sr[w].end_bit,
+            (unsigned long long)sr[w].out_len, sr[w].flags, sr[w].next);
+  return ZES_OK;
+}
+
+// step 2: every work item first goes to the block decoder of the block-parallel tier in its any-encoder form
+// (k_inf_seg_block_par: a workgroup per block, 1024 lanes decoding 1024 bit segments of it) — a wave that decodes a
+// block token by token gets through ~13 MB/s.  What it declines (an item whose block is stored or fixed, is followed
+// by a block that is not on the list, or is longer than 128 KiB) is listed, and the wave decoder runs for the list.
+int t2_block_decoder(T2Run& t) {
+  int rc;
+  const uint32_t work = t.work;
+  t.blockpar = t.ratio != 0 && !getenv("ZES_NO_SEG_PAR");
+  if (t.blockpar) {
     if ((rc = ensure(g.segfail, ((size_t)work + 1) * 4))) return rc;
-    fail_list = (uint32_t*)g.segfail.p;
-    HIPCHK(hipMemsetAsync(fail_list, 0, 4, g.stream));
+    t.fail_list = (uint32_t*)g.segfail.p;
+    HIPCHK(hipMemsetAsync(t.fail_list, 0, 4, g.stream));
     HIPCHK(hipMemsetAsync((uint64_t*)g.symoff.p + work, 0, 8, g.stream));
     unsigned long long* pdbg = nullptr;
     if (getenv("ZES_DEBUG_PHASES")) {
@@ -1768,166 +1849,174 @@ int inflate_segments_run(const uint8_t* d_in, uint8_t* d_out, InfJob* jobs, cons
       pdbg = (unsigned long long*)g.dbg.p;
     }
     {
-      Timed t("k_inf_seg_block_par");
-      hipLaunchKernelGGL(k_inf_seg_block_par, dim3(work), dim3(PAR_THREADS), 0, g.stream, d_in, (const ZesSegJob*)g.segjobs.p, nb, cs, (ZesSegRes*)g.sres.p,
-                         (uint32_t*)g.maps.p, (uint32_t*)g.sym16.p, ratio, fail_list, (unsigned long long*)((uint64_t*)g.symoff.p + work),
-                         (uint64_t)((share_syms / 2 + 3) & ~3ull), bump_syms, (uint64_t*)g.symoff.p, pdbg);
+      Timed tm("k_inf_seg_block_par");
+      hipLaunchKernelGGL(k_inf_seg_block_par, dim3(work), dim3(PAR_THREADS), 0, g.stream, t.d_in, (const ZesSegJob*)g.segjobs.p, t.nb,
+                         (const uint32_t*)g.cand_sorted.p, (ZesSegRes*)g.sres.p, (uint32_t*)g.maps.p, (uint32_t*)g.sym16.p, t.ratio, t.fail_list,
+                         (unsigned long long*)((uint64_t*)g.symoff.p + work), (uint64_t)((t.share_syms / 2 + 3) & ~3ull), t.bump_syms,
+                         (uint64_t*)g.symoff.p, pdbg);
     }
     if (pdbg) {
       HIPCHK(hipStreamSynchronize(g.stream));
       if ((rc = print_par_phases(pdbg, work))) return rc;
     }
   }
-  auto dump_items = [&](const char* tag) {  // ZES_T2_DBG: what every work item has come to so far
-    if (!getenv("ZES_T2_DBG")) return;
+  if (getenv("ZES_T2_DBG")) {
     (void)hipStreamSynchronize(g.stream);
-    std::vector<ZesSegRes> sr(work);
     std::vector<uint32_t> fl(work + 1, 0);
-    (void)hipMemcpy(sr.data(), g.sres.p, sr.size() * sizeof(ZesSegRes), hipMemcpyDeviceToHost);
-    if (fail_list) (void)hipMemcpy(fl.data(), fail_list, fl.size() * 4, hipMemcpyDeviceToHost);
-    fprintf(stderr, "zes T2 items %s (fail list: %u:", tag, fl[0]);
+    if (t.fail_list) (void)hipMemcpy(fl.data(), t.fail_list, fl.size() * 4, hipMemcpyDeviceToHost);
+    fprintf(stderr, "zes T2 items after the block decoder (fail list: %u:", fl[0]);
     for (uint32_t i = 0; i < fl[0] && i < 16; i++) fprintf(stderr, " %u", fl[1 + i]);
     fprintf(stderr, ")\n");
-    for (size_t w = 0; w < sr.size(); w++)
-      fprintf(stderr, "   item %zu: end_bit %llu out_len %llu flags %u next %u\n", w, (unsigned long long)sr[w].end_bit,
-              (unsigned long long)sr[w].out_len, sr[w].flags, sr[w].next);
-  };
-  dump_items("after the block decoder");
-  uint32_t* hs = g.pinned->t2.flags;
-  ZesRes* hres = g.pinned->t2.res;
-  // the chain of every buffer of the group (work item 0 -> the item that starts where it ended -> ... -> the final block)
-  auto run_chains = [&]() -> int {
-    HIPCHK(hipMemsetAsync(novf_d, 0, (size_t)nb * 4, g.stream));
-    {
-      Timed t("k_inf_seg_chain");  // (one launch: a workgroup per buffer of the group)
-      hipLaunchKernelGGL(k_inf_seg_chain, dim3(nb), dim3(256), 0, g.stream, (const ZesSegJob*)g.segjobs.p, (const ZesSegRes*)g.sres.p,
-                         (uint32_t*)g.seglist.p, (uint64_t*)g.segprefix.p, (ZesRes*)g.res.p, novf_d);
-    }
-    HIPCHK(hipMemcpyAsync(hs, novf_d, (size_t)nb * 4, hipMemcpyDeviceToHost, g.stream));
-    HIPCHK(hipMemcpyAsync(hres, g.res.p, sizeof(ZesRes) * nb * 2, hipMemcpyDeviceToHost, g.stream));
-    if (blockpar) HIPCHK(hipMemcpyAsync(hs + nb, fail_list, 4, hipMemcpyDeviceToHost, g.stream));
-    host_lap("(host work since)");
-    HIPCHK(hipStreamSynchronize(g.stream));  // (the job table upload has completed too: hj may be rewritten)
-    host_lap("T2: decode / chains");
-    return ZES_OK;
-  };
-  // Round 3: the chains are tried on what the block decoder left BEFORE the wave decoder gets the declined items.  An
-  // item that starts on a false candidate is declined (its "block" is garbage) and nobody's chain leads to it — but
-  // the lone wave that decodes it on may take milliseconds to find that out (256 x 1 MiB of zlib text: 6.9 of 32 ms).
-  // Only when a chain does run into a declined item (a stored or fixed block, a block behind an unlisted start) do the
-  // declined items go to the wave decoder, and the chains are followed again.
-  bool chained = false;
-  if (blockpar) {
-    if ((rc = run_chains())) return rc;
-    chained = true;
-    const uint32_t ndecl = hs[nb];
-    if (getenv("ZES_DEBUG")) fprintf(stderr, "zes T2: %u work items, %u declined by the block decoder\n", work, ndecl);
-    // Chains that stand in front of an undecoded item: exactly those items go to the wave decoder (a zlib stream's
-    // last block is often a fixed one: one small item per stream, where the declined list of 256 streams of 1 MiB also
-    // held ~200 false candidates that cost the lone waves 6.8 ms), and the chains are followed again; a few rounds,
-    // then — streams with many stored or fixed blocks — everything that was declined.
-    std::vector<uint32_t> last_stuck(nb, 0xFFFFFFFFu);
-    // the item a buffer's chain stands in front of (status 1: no chain; 3: the chain of a piece, as far as it got)
-    auto stuck_of = [&](uint32_t k) -> uint32_t {
-      if (hres[k].status == 1 && hres[k].out_len != 0) return (uint32_t)(hres[k].out_len - 1);
-      if (hres[k].status == 3 && hres[nb + k].aux != 0) return hres[nb + k].aux - 1u;
-      return 0xFFFFFFFFu;
-    };
-    // (Not when an eighth of all items were declined: a stream of blocks of a few hundred bytes — zlib with memLevel 1 —
-    // is thinned to 2048 items of a dozen blocks each, every one of them handed over behind its first block: four
-    // rounds of one lone wave each were 16 of that stream's 31 ms before the launch that takes them all.)
-    const bool many = ndecl >= 16 && (uint64_t)ndecl * 8 >= work;
-    for (int round = 0; ndecl && !many && round < 4; round++) {
-      std::vector<uint32_t> items;
-      for (uint32_t k = 0; k < nb; k++) {
-        const uint32_t w = stuck_of(k);
-        if (w == 0xFFFFFFFFu || w == last_stuck[k]) continue;  // (the same item again: it has been to the wave decoder — the stream is not for this tier)
-        // a piece of a longer stream whose chain got through half the piece: what it stands in front of is, as a rule,
-        // the block the piece's end cuts — the next piece starts there
-        if (hres[k].status == 3 && hres[nb + k].out_len >= jobs[ids[k]].c * 4) continue;
-        last_stuck[k] = w;
-        items.push_back(hj[k].work_first + w);
-      }
-      if (items.empty()) break;
-      if ((rc = ensure(g.seglive, ((size_t)nb + 1) * 4))) return rc;
-      uint32_t* hl = g.pinned->t2.live;
-      hl[0] = (uint32_t)items.size();
-      memcpy(hl + 1, items.data(), items.size() * 4);
-      HIPCHK(hipMemcpyAsync(g.seglive.p, hl, (items.size() + 1) * 4, hipMemcpyHostToDevice, g.stream));
-      {
-        Timed t("k_inf_seg_scan");
-        hipLaunchKernelGGL(k_inf_seg_scan_short, dim3((uint32_t)items.size()), dim3(64), 0, g.stream, d_in, (const ZesSegJob*)g.segjobs.p, nb, cs,
-                           (ZesSegRes*)g.sres.p, (uint32_t*)g.maps.p, (uint32_t*)g.sym16.p, ratio, (const uint32_t*)g.seglive.p + 1, far_d,
-                           (const uint32_t*)g.seglive.p, (uint64_t*)g.symoff.p);
-      }
-      HIPCHK(hipMemcpyAsync(&g.pinned->t2.far, far_d, 4, hipMemcpyDeviceToHost, g.stream));
-      if ((rc = run_chains())) return rc;
-      if (g.pinned->t2.far != 0) {  // a far match behind the short ring: the full-ring pass below decides
-        chained = false;
-        break;
-      }
-    }
-    if (chained && ndecl)
-      for (uint32_t k = 0; k < nb; k++) {
-        const uint32_t w = stuck_of(k);
-        if (w == 0xFFFFFFFFu || w == last_stuck[k]) continue;
-        // rounds used up with a chain still in front of an undecoded item (a stream whose blocks mostly follow blocks
-        // that are not on the thinned list): everything that was declined goes to the wave decoder in one launch —
-        // unless it is a piece's chain that got through half the piece (see above)
-        if (hres[k].status == 3 && hres[nb + k].out_len >= jobs[ids[k]].c * 4) continue;
-        chained = false;
-      }
+    (void)t2_dump_items(0, work);
   }
-  if (!chained) {
-    {
-      Timed t("k_inf_seg_scan");
-      hipLaunchKernelGGL(k_inf_seg_scan_short, dim3(work), dim3(64), 0, g.stream, d_in, (const ZesSegJob*)g.segjobs.p, nb, cs, (ZesSegRes*)g.sres.p,
-                         (uint32_t*)g.maps.p, (uint32_t*)g.sym16.p, ratio, blockpar ? (const uint32_t*)fail_list + 1 : (const uint32_t*)g.segorder.p, far_d,
-                         (const uint32_t*)fail_list, (uint64_t*)g.symoff.p);
-    }
-    {
-      HIPCHK(hipMemcpyAsync(&g.pinned->t2.far, far_d, 4, hipMemcpyDeviceToHost, g.stream));
-      HIPCHK(hipStreamSynchronize(g.stream));
-      if (g.pinned->t2.far != 0) {
-        Timed t("k_inf_seg_scan");
-        hipLaunchKernelGGL(k_inf_seg_scan, dim3(work), dim3(64), 0, g.stream, d_in, (const ZesSegJob*)g.segjobs.p, nb, cs, (ZesSegRes*)g.sres.p,
-                           (uint32_t*)g.maps.p, (uint32_t*)g.sym16.p, ratio, (const uint32_t*)g.segorder.p, far_d, (const uint32_t*)nullptr,
-                           (uint64_t*)g.symoff.p);
-      }
-    }
-    if ((rc = run_chains())) return rc;
+  return ZES_OK;
+}
+
+// the chain of every buffer of the run (work item 0 -> the item that starts where it ended -> ... -> the final block),
+// read back with the not-in-store counts and the block decoder's declined count
+int t2_chains(T2Run& t) {
+  const uint32_t nb = t.nb;
+  HIPCHK(hipMemsetAsync(t.novf_d, 0, (size_t)nb * 4, g.stream));
+  {
+    Timed tm("k_inf_seg_chain");  // (one launch: a workgroup per buffer of the group)
+    hipLaunchKernelGGL(k_inf_seg_chain, dim3(nb), dim3(256), 0, g.stream, (const ZesSegJob*)g.segjobs.p, (const ZesSegRes*)g.sres.p,
+                       (uint32_t*)g.seglist.p, (uint64_t*)g.segprefix.p, (ZesRes*)g.res.p, t.novf_d);
   }
-  std::vector<uint32_t> novf(hs, hs + nb);
-  std::vector<ZesRes> hr(hres, hres + 2 * nb);
-  std::vector<char> go(nb, 0);
+  HIPCHK(hipMemcpyAsync(t.hs, t.novf_d, (size_t)nb * 4, hipMemcpyDeviceToHost, g.stream));
+  HIPCHK(hipMemcpyAsync(t.hres, g.res.p, sizeof(ZesRes) * nb * 2, hipMemcpyDeviceToHost, g.stream));
+  if (t.blockpar) HIPCHK(hipMemcpyAsync(t.hs + nb, t.fail_list, 4, hipMemcpyDeviceToHost, g.stream));
+  host_lap("(host work since)");
+  HIPCHK(hipStreamSynchronize(g.stream));  // (the job table upload has completed too: hj may be rewritten)
+  host_lap("T2: decode / chains");
+  return ZES_OK;
+}
+
+// The wave decoder, a wave per work item: `items` of them from `list`, fewer if *count (device) says so.  It runs with the
+// short marker ring (three waves per CU instead of two); a match that reaches behind the ring takes its symbols from the
+// symbol store, so a segment that has outgrown its share of the store and then meets such a match cannot go on: far_d
+// counts those, and the whole run goes through the full ring (rare: streams that inflate by more than the store's
+// symbols per compressed byte).
+void t2_launch_waves(const T2Run& t, bool short_ring, uint32_t items, const uint32_t* list, const uint32_t* count) {
+  Timed tm("k_inf_seg_scan");
+  hipLaunchKernelGGL(short_ring ? k_inf_seg_scan_short : k_inf_seg_scan, dim3(items), dim3(64), 0, g.stream, t.d_in, (const ZesSegJob*)g.segjobs.p,
+                     t.nb, (const uint32_t*)g.cand_sorted.p, (ZesSegRes*)g.sres.p, (uint32_t*)g.maps.p, (uint32_t*)g.sym16.p, t.ratio, list, t.far_d,
+                     count, (uint64_t*)g.symoff.p);
+}
+
+// The undecoded item buffer k's chain stands in front of (status 1: no chain; 3: the chain of a piece, as far as it got)
+// and has not stood in front of before; T2_NONE: none, or the same item again (it has been to the wave decoder — the
+// stream is not for this tier), or a piece of a longer stream whose chain got through half the piece: what that stands
+// in front of is, as a rule, the block the piece's end cuts — the next piece starts there.
+uint32_t t2_stuck_at(const T2Run& t, uint32_t k) {
+  const ZesRes &chain = t.hres[k], &end = t.hres[t.nb + k];
+  uint32_t w = T2_NONE;
+  if (chain.status == 1 && chain.out_len != 0) w = (uint32_t)(chain.out_len - 1);
+  else if (chain.status == 3 && end.aux != 0) w = end.aux - 1u;
+  if (w == T2_NONE || w == t.last_stuck[k]) return T2_NONE;
+  if (chain.status == 3 && end.out_len >= t.jobs[t.ids[k]].c * 4) return T2_NONE;
+  return w;
+}
+
+// step 3 behind the block decoder.  The chains are tried on what it left BEFORE the wave decoder gets the declined items:
+// an item that starts on a false candidate is declined (its "block" is garbage) and nobody's chain leads to it — but
+// the lone wave that decodes it on may take milliseconds to find that out (256 x 1 MiB of zlib text: 6.9 of 32 ms).
+// Chains that stand in front of an undecoded item (a stored or fixed block, a block behind an unlisted start): exactly
+// those items go to the wave decoder (a zlib stream's last block is often a fixed one: one small item per stream, where
+// the declined list of 256 streams of 1 MiB also held ~200 false candidates that cost the lone waves 6.8 ms), and the
+// chains are followed again; a few rounds.  *everything: the wave decoder is to take all that was declined — a far
+// match behind the short ring, or the rounds are used up (or were not tried) with a chain still in front of an
+// undecoded item: streams with many stored or fixed blocks, or whose blocks mostly follow blocks that are not on the
+// thinned list.
+int t2_handover(T2Run& t, bool* everything) {
+  int rc;
+  const uint32_t nb = t.nb;
+  *everything = false;
+  if ((rc = t2_chains(t))) return rc;
+  const uint32_t ndecl = t.hs[nb];
+  if (getenv("ZES_DEBUG")) fprintf(stderr, "zes T2: %u work items, %u declined by the block decoder\n", t.work, ndecl);
+  if (!ndecl) return ZES_OK;
+  t.last_stuck.assign(nb, T2_NONE);
+  // (No rounds when an eighth of all items were declined: a stream of blocks of a few hundred bytes — zlib with memLevel 1 —
+  // is thinned to 2048 items of a dozen blocks each, every one of them handed over behind its first block: four
+  // rounds of one lone wave each were 16 of that stream's 31 ms before the launch that takes them all.)
+  const bool many = ndecl >= 16 && (uint64_t)ndecl * 8 >= t.work;
+  for (int round = 0; !many && round < 4; round++) {
+    uint32_t* hl = g.pinned->t2.live;
+    uint32_t n = 0;
+    for (uint32_t k = 0; k < nb; k++) {
+      const uint32_t w = t2_stuck_at(t, k);
+      if (w == T2_NONE) continue;
+      t.last_stuck[k] = w;
+      hl[++n] = t.hj[k].work_first + w;
+    }
+    if (!n) break;
+    hl[0] = n;
+    if ((rc = ensure(g.seglive, ((size_t)nb + 1) * 4))) return rc;
+    HIPCHK(hipMemcpyAsync(g.seglive.p, hl, ((size_t)n + 1) * 4, hipMemcpyHostToDevice, g.stream));
+    t2_launch_waves(t, true, n, (const uint32_t*)g.seglive.p + 1, (const uint32_t*)g.seglive.p);
+    HIPCHK(hipMemcpyAsync(&g.pinned->t2.far, t.far_d, 4, hipMemcpyDeviceToHost, g.stream));
+    if ((rc = t2_chains(t))) return rc;
+    if (g.pinned->t2.far != 0) {  // a far match behind the short ring: the full-ring pass decides
+      *everything = true;
+      return ZES_OK;
+    }
+  }
+  for (uint32_t k = 0; k < nb; k++)
+    if (t2_stuck_at(t, k) != T2_NONE) *everything = true;
+  return ZES_OK;
+}
+
+// step 3 without the block decoder, or when the handover has not settled the run: everything that was declined (no
+// block decoder: every item, in k_inf_seg_order's order) goes to the wave decoder in one launch, after a far match
+// every item again with the full ring, and the chains are followed again
+int t2_everything(T2Run& t) {
+  t2_launch_waves(t, true, t.work, t.blockpar ? (const uint32_t*)t.fail_list + 1 : (const uint32_t*)g.segorder.p, t.fail_list);
+  HIPCHK(hipMemcpyAsync(&g.pinned->t2.far, t.far_d, 4, hipMemcpyDeviceToHost, g.stream));
+  HIPCHK(hipStreamSynchronize(g.stream));
+  if (g.pinned->t2.far != 0) t2_launch_waves(t, false, t.work, (const uint32_t*)g.segorder.p, nullptr);
+  return t2_chains(t);
+}
+
+// step 4: every buffer's verdict.  A chain to the final block (a piece: as far as it got) that fits the output: go; one
+// that does not fit: the caller learns the size without the output passes; anything else is left to the serial tiers.
+int t2_verdicts(T2Run& t) {
+  const uint32_t nb = t.nb;
+  t.novf.assign(t.hs, t.hs + nb);  // (the page-locked area is used again by the output passes)
+  t.hr.assign(t.hres, t.hres + 2 * nb);
+  t.go.assign(nb, 0);
+  int rc;
   bool any = false;
   for (uint32_t k = 0; k < nb; k++) {
-    InfJob& j = jobs[ids[k]];
+    InfJob& j = t.jobs[t.ids[k]];
+    ZesRes& r = t.hr[k];
     if (getenv("ZES_DEBUG"))
       fprintf(stderr, "zes T2: c=%llu candidates=%u chain status=%d segments=%u (%u decoded twice) out_len=%llu\n", (unsigned long long)j.c,
-              ncand[k], hr[k].status, hr[k].aux, novf[k], (unsigned long long)hr[k].out_len);
-    if (getenv("ZES_T2_DBG")) {  // what every work item came to
-      std::vector<ZesSegRes> sr(ncand[k] + 1);
-      HIPCHK(hipMemcpy(sr.data(), (const ZesSegRes*)g.sres.p + hj[k].work_first, sr.size() * sizeof(ZesSegRes), hipMemcpyDeviceToHost));
-      for (size_t w = 0; w < sr.size(); w++)
-        fprintf(stderr, "   item %zu: end_bit %llu out_len %llu flags %u next %u\n", w, (unsigned long long)sr[w].end_bit,
-                (unsigned long long)sr[w].out_len, sr[w].flags, sr[w].next);
-    }
-    if (hr[k].status == 3 && j.partial) hr[k].status = 0;  // a piece's chain, as far as it got
-    if (hr[k].status != 0 || hr[k].aux == 0) continue;
-    j.end_bit = hr[nb + k].out_len;
-    j.final_seen = hr[nb + k].status != 0;
-    if (hr[k].out_len > j.cap) {  // the caller learns the size without the output passes
+              t.ncand[k], r.status, r.aux, t.novf[k], (unsigned long long)r.out_len);
+    if (getenv("ZES_T2_DBG") && (rc = t2_dump_items(t.hj[k].work_first, t.ncand[k] + 1))) return rc;  // what every work item came to
+    if (r.status == 3 && j.partial) r.status = 0;  // a piece's chain, as far as it got
+    if (r.status != 0 || r.aux == 0) continue;
+    j.end_bit = t.hr[nb + k].out_len;
+    j.final_seen = t.hr[nb + k].status != 0;
+    if (r.out_len > j.cap) {
       j.tier = 2;
-      j.out_len = hr[k].out_len;
+      j.out_len = r.out_len;
       j.status = ZES_E_NOSPACE;
       continue;
     }
-    go[k] = 1;
+    t.go[k] = 1;
     any = true;
-    hj[k].nseg = hr[k].aux;
+    t.hj[k].nseg = r.aux;
   }
-  if (!any) return ZES_OK;
+  return any ? ZES_OK : T2_OVER;
+}
+
+// step 5: the output passes — the 32 KiB window in front of every segment, the symbols translated into bytes, and the
+// segments that are not in the symbol store decoded again, buffer by buffer
+int t2_output(T2Run& t) {
+  int rc;
+  const uint32_t nb = t.nb, work = t.work;
+  ZesSegJob* hj = t.hj;
+  const uint32_t* cs = (const uint32_t*)g.cand_sorted.p;
   if ((rc = ensure(g.wins, (size_t)work * ZES_WINDOW))) return rc;
   HIPCHK(hipMemcpyAsync(g.segjobs.p, hj, sizeof(ZesSegJob) * nb, hipMemcpyHostToDevice, g.stream));
   // where every buffer's bytes go (and how much output exists in front: a later piece of a long stream)
@@ -1935,10 +2024,10 @@ int inflate_segments_run(const uint8_t* d_in, uint8_t* d_out, InfJob* jobs, cons
   ZesSegOut* ho = g.pinned->t2.out;
   uint32_t max_tr = 0, min_tr = 0xFFFFFFFFu;
   for (uint32_t k = 0; k < nb; k++) {
-    const InfJob& j = jobs[ids[k]];
+    const InfJob& j = t.jobs[t.ids[k]];
     ho[k].out_off = j.out_off;
     ho[k].cap = j.cap;
-    ho[k].nseg = (go[k] && novf[k] < hr[k].aux) ? hr[k].aux : 0u;
+    ho[k].nseg = (t.go[k] && t.novf[k] < t.hr[k].aux) ? t.hr[k].aux : 0u;
     ho[k].hist = j.hist;
     if (ho[k].nseg) {
       max_tr = std::max(max_tr, ho[k].nseg);
@@ -1953,46 +2042,245 @@ int inflate_segments_run(const uint8_t* d_in, uint8_t* d_out, InfJob* jobs, cons
     const uint32_t max_groups = (max_nseg + SEGWIN_GROUP - 1) / SEGWIN_GROUP;
     if ((rc = ensure(g.pw16, (size_t)work * ZES_WINDOW * 2))) return rc;
     if ((rc = ensure(g.gwins, ((size_t)work / SEGWIN_GROUP + nb + 1) * ZES_WINDOW))) return rc;  // (work_first / group) + buffer index + group
-    Timed t("k_inf_seg_windows");
+    Timed tm("k_inf_seg_windows");
     hipLaunchKernelGGL(k_inf_seg_win_group, dim3(max_groups, nb), dim3(1024), 0, g.stream, (const uint32_t*)g.maps.p,
                        (const uint32_t*)g.seglist.p, (const ZesSegJob*)g.segjobs.p, (uint32_t*)g.pw16.p);
     hipLaunchKernelGGL(k_inf_seg_win_top, dim3(nb), dim3(1024), 0, g.stream, (const uint32_t*)g.pw16.p, (const ZesSegJob*)g.segjobs.p,
-                       (uint8_t*)g.gwins.p, (const uint8_t*)d_out, (const ZesSegOut*)g.segouts.p);
+                       (uint8_t*)g.gwins.p, (const uint8_t*)t.d_out, (const ZesSegOut*)g.segouts.p);
     hipLaunchKernelGGL(k_inf_seg_win_fin, dim3(max_nseg, nb), dim3(1024), 0, g.stream, (const uint32_t*)g.pw16.p,
                        (const ZesSegJob*)g.segjobs.p, (const uint8_t*)g.gwins.p, (uint8_t*)g.wins.p);
   }
-  {
+  if (max_tr) {
     // symbols -> bytes: one launch over (segments, workgroups per segment, buffers)
-    if (max_tr) {
-      Timed t("k_inf_seg_translate");
-      // few long segments: split each over several workgroups (by the buffer with the fewest)
-      const uint32_t ny = std::max(1u, std::min(16u, 2048u / std::max(1u, min_tr * std::min(nb, 8u))));
-      hipLaunchKernelGGL(k_inf_seg_translate, dim3(max_tr, ny, nb), dim3(256), 0, g.stream, d_out, (const ZesSegJob*)g.segjobs.p,
-                         (const ZesSegOut*)g.segouts.p, cs, (const ZesSegRes*)g.sres.p, (const uint32_t*)g.seglist.p,
-                         (const uint64_t*)g.segprefix.p, (const uint8_t*)g.wins.p, (const uint32_t*)g.sym16.p, (const uint64_t*)g.symoff.p, fail_d);
-    }
+    Timed tm("k_inf_seg_translate");
+    // few long segments: split each over several workgroups (by the buffer with the fewest)
+    const uint32_t ny = std::max(1u, std::min(16u, 2048u / std::max(1u, min_tr * std::min(nb, 8u))));
+    hipLaunchKernelGGL(k_inf_seg_translate, dim3(max_tr, ny, nb), dim3(256), 0, g.stream, t.d_out, (const ZesSegJob*)g.segjobs.p,
+                       (const ZesSegOut*)g.segouts.p, cs, (const ZesSegRes*)g.sres.p, (const uint32_t*)g.seglist.p,
+                       (const uint64_t*)g.segprefix.p, (const uint8_t*)g.wins.p, (const uint32_t*)g.sym16.p, (const uint64_t*)g.symoff.p, t.fail_d);
   }
   for (uint32_t k = 0; k < nb; k++) {
-    if (!go[k]) continue;
-    const InfJob& j = jobs[ids[k]];
-    const uint32_t nseg = hr[k].aux, wf = hj[k].work_first;
-    if (novf[k] > 0) {
-      Timed t("k_inf_seg_decode");
-      hipLaunchKernelGGL(k_inf_seg_decode, dim3(nseg), dim3(64), 0, g.stream, d_in, j.in_off, j.c, d_out, j.out_off, j.cap, cs + cbase[k],
-                         (const ZesSegRes*)g.sres.p + wf, (const uint32_t*)g.seglist.p + wf, (const uint64_t*)g.segprefix.p + wf,
-                         (const uint8_t*)g.wins.p + (size_t)wf * ZES_WINDOW, fail_d + k, novf[k] < nseg ? 1u : 0u, j.start0, j.hist);
-    }
+    if (!t.go[k] || t.novf[k] == 0) continue;
+    const InfJob& j = t.jobs[t.ids[k]];
+    const uint32_t nseg = t.hr[k].aux, wf = hj[k].work_first;
+    Timed tm("k_inf_seg_decode");
+    hipLaunchKernelGGL(k_inf_seg_decode, dim3(nseg), dim3(64), 0, g.stream, t.d_in, j.in_off, j.c, t.d_out, j.out_off, j.cap, cs + t.cbase[k],
+                       (const ZesSegRes*)g.sres.p + wf, (const uint32_t*)g.seglist.p + wf, (const uint64_t*)g.segprefix.p + wf,
+                       (const uint8_t*)g.wins.p + (size_t)wf * ZES_WINDOW, t.fail_d + k, t.novf[k] < nseg ? 1u : 0u, j.start0, j.hist);
   }
-  HIPCHK(hipMemcpyAsync(hs, fail_d, (size_t)nb * 4, hipMemcpyDeviceToHost, g.stream));
+  HIPCHK(hipMemcpyAsync(t.hs, t.fail_d, (size_t)nb * 4, hipMemcpyDeviceToHost, g.stream));
   host_lap("(host work since)");
   HIPCHK(hipStreamSynchronize(g.stream));
   host_lap("T2: windows + translate");
-  for (uint32_t k = 0; k < nb; k++) {
-    if (!go[k] || hs[k] != 0) continue;  // (a match behind the first byte of the stream: the serial tiers decide)
-    InfJob& j = jobs[ids[k]];
+  return ZES_OK;
+}
+
+// step 6: the jobs this run has settled
+int t2_publish(T2Run& t) {
+  for (uint32_t k = 0; k < t.nb; k++) {
+    if (!t.go[k] || t.hs[k] != 0) continue;  // (a match behind the first byte of the stream: the serial tiers decide)
+    InfJob& j = t.jobs[t.ids[k]];
     j.tier = 2;
-    j.out_len = hr[k].out_len;
+    j.out_len = t.hr[k].out_len;
     j.status = ZES_OK;
+  }
+  return ZES_OK;
+}
+
+// `w`: the run's device words (seg_words(buffers of the group, nb))
+int inflate_segments_run(const uint8_t* d_in, uint8_t* d_out, InfJob* jobs, const uint32_t* ids, const uint32_t* cbase, const uint32_t* ncand,
+                         uint32_t nb, const SegWords& w) {
+  int rc;
+  uint32_t* words = (uint32_t*)g.counters.p;
+  T2Run t{d_in, d_out, jobs, ids, cbase, ncand, nb, g.pinned->t2.jobs, g.pinned->t2.flags, g.pinned->t2.res, words + w.novf, words + w.fail, words + w.far};
+  if ((rc = t2_plan(t))) return rc;
+  if ((rc = t2_block_decoder(t))) return rc;
+  bool everything = true;  // (no block decoder: the wave decoder takes every item)
+  if (t.blockpar && (rc = t2_handover(t, &everything))) return rc;
+  if (everything && (rc = t2_everything(t))) return rc;
+  if ((rc = t2_verdicts(t))) return rc == T2_OVER ? ZES_OK : rc;
+  if ((rc = t2_output(t))) return rc;
+  return t2_publish(t);
+}
+
+// One group of the tier between the steps of inflate_segments: buffers ids[0..nb), their candidate lists side by side in
+// g.cand / g.cand_sorted (buffer k's at cbase[k], room for ccap[k]).
+struct T2Group {
+  const uint8_t* d_in;
+  uint8_t* d_out;
+  InfJob* jobs;
+  const uint32_t* ids;
+  uint32_t nb;
+  SegWords w;
+  std::vector<uint32_t> cbase, ccap;
+  uint32_t surv_cap = 0;  // of a buffer searched by itself
+  uint32_t *counters = nullptr, *cnt = nullptr;
+  uint8_t* sink = nullptr;
+  const ZesInfBuf* dbufs = nullptr;  // the table of the search that is running
+  std::vector<char> searched;        // the several-buffer search has settled this buffer's list
+  std::vector<uint32_t> nc;          // candidates per buffer, read back
+};
+
+// step 1: where every buffer's candidates go, the pools, the cleared device words.
+// (range_cand_cap / range_surv_cap are c / 64 + 64 and c / 4 + 1024 below their upper bounds of 2^23 and 2^30: so for
+// every c this tier is given — streams below SEG_PIECES_MIN_C, pieces of up to 448 MiB: 448 MiB / 64 + 64 < 2^23.)
+int t2_group_table(T2Group& G) {
+  int rc;
+  const uint32_t nb = G.nb;
+  G.cbase.resize(nb);
+  G.ccap.resize(nb);
+  G.searched.assign(nb, 0);
+  uint64_t cands = 0, max_c = 0;
+  for (uint32_t k = 0; k < nb; k++) {
+    const InfJob& j = G.jobs[G.ids[k]];
+    G.cbase[k] = (uint32_t)cands;
+    G.ccap[k] = range_cand_cap(j.c);
+    cands += G.ccap[k];
+    max_c = std::max(max_c, j.c);
+  }
+  G.surv_cap = range_surv_cap(max_c);
+  G.w = seg_words(nb, nb);
+  if ((rc = ensure(g.ibufs, sizeof(ZesInfBuf) * 2))) return rc;
+  if ((rc = ensure(g.surv, (size_t)G.surv_cap * 8))) return rc;
+  if ((rc = ensure(g.cand, (size_t)cands * 4))) return rc;
+  if ((rc = ensure(g.cand_sorted, (size_t)cands * 4))) return rc;
+  if ((rc = ensure(g.counters, G.w.total * 4))) return rc;
+  if ((rc = ensure(g.mvlist, SEG_BUCKETS * 4))) return rc;
+  G.counters = (uint32_t*)g.counters.p + G.w.scan;
+  G.cnt = (uint32_t*)g.counters.p + G.w.cnt;
+  G.sink = (uint8_t*)((uint32_t*)g.counters.p + G.w.sink);
+  HIPCHK(hipMemsetAsync(g.counters.p, 0, G.w.total * 4, g.stream));
+  G.dbufs = (const ZesInfBuf*)g.ibufs.p;
+  return ZES_OK;
+}
+
+// a buffer's entry of a search table of this tier
+ZesInfBuf t2_search_buf(const T2Group& G, uint32_t k) {
+  const InfJob& j = G.jobs[G.ids[k]];
+  ZesInfBuf b = inf_buf(j);
+  b.cand_base = G.cbase[k];
+  b.cand_cap = G.ccap[k];
+  b.start_rel = j.start0 - 16u;  // (a piece of a longer stream: nothing in front of its first block is searched)
+  return b;
+}
+
+// step 2, several buffers (a batch of another encoder's streams): one scan and one header test over all of them, the lists
+// sorted by one launch; only a buffer with more candidates than a segment run takes (tiny blocks) is thinned, by
+// itself, afterwards.  (256 streams of 1 MiB: the searches one after the other were 36 ms of launches.)
+int t2_search_group(T2Group& G) {
+  int rc;
+  const uint32_t nb = G.nb;
+  ZesInfBuf* hb = g.pinned->t2.search;
+  uint64_t chunks = 0, total_c = 0;
+  for (uint32_t k = 0; k < nb; k++) {
+    hb[k] = t2_search_buf(G, k);
+    hb[k].first_chunk = (uint32_t)chunks;
+    chunks += (hb[k].c + INF_SCAN_BYTES - 1) / INF_SCAN_BYTES;
+    total_c += hb[k].c;
+  }
+  memset(&hb[nb], 0, sizeof(ZesInfBuf));
+  hb[nb].first_chunk = (uint32_t)chunks;
+  const uint32_t surv_all = (uint32_t)std::min<uint64_t>(total_c / 4 + 1024ull * nb, 1ull << 30);
+  if ((rc = ensure(g.ibufs, sizeof(ZesInfBuf) * (nb + 1)))) return rc;
+  if ((rc = ensure(g.surv, (size_t)surv_all * 8))) return rc;
+  G.dbufs = (const ZesInfBuf*)g.ibufs.p;
+  HIPCHK(hipMemcpyAsync(g.ibufs.p, hb, sizeof(ZesInfBuf) * (nb + 1), hipMemcpyHostToDevice, g.stream));
+  if ((rc = launch_search(G.d_in, G.dbufs, nb, (uint32_t)chunks, surv_all, G.counters, G.cnt, G.sink, T2_SEARCH, total_c))) return rc;
+  {
+    Timed t("k_inf_ranksort");
+    hipLaunchKernelGGL(k_inf_ranksort, dim3(nb), dim3(1024), 0, g.stream, G.dbufs, (const uint32_t*)G.cnt, (const uint32_t*)g.cand.p,
+                       (uint32_t*)g.cand_sorted.p, SEG_BUCKETS);
+  }
+  uint32_t* hc0 = g.pinned->t2.ncand;
+  HIPCHK(hipMemcpyAsync(hc0, G.cnt, (size_t)nb * 4, hipMemcpyDeviceToHost, g.stream));
+  HIPCHK(hipStreamSynchronize(g.stream));
+  bool redo = false;
+  for (uint32_t k = 0; k < nb; k++) {
+    G.searched[k] = hc0[k] <= SEG_BUCKETS;  // (the others: thinned, from a search of their own)
+    redo = redo || !G.searched[k];
+  }
+  if (redo) {  // a table of its own for those searches: the one the sort used stays as it is
+    if ((rc = ensure(g.ibufs2, sizeof(ZesInfBuf) * 2))) return rc;
+    G.dbufs = (const ZesInfBuf*)g.ibufs2.p;
+  }
+  return ZES_OK;
+}
+
+// step 2, one buffer by itself (the search has the chip to itself), and its list thinned
+int t2_search_one(T2Group& G, uint32_t k) {
+  int rc;
+  uint32_t* cntk = G.cnt + k;
+  HIPCHK(hipMemsetAsync(cntk, 0, 4, g.stream));
+  const ZesInfBuf b0 = t2_search_buf(G, k);
+  const uint32_t chunks = (uint32_t)((b0.c + INF_SCAN_BYTES - 1) / INF_SCAN_BYTES);
+  ZesInfBuf b1;
+  memset(&b1, 0, sizeof b1);
+  b1.first_chunk = chunks;
+  hipLaunchKernelGGL(k_inf_set_table1, dim3(1), dim3(64), 0, g.stream, b0, b1, const_cast<ZesInfBuf*>(G.dbufs), G.counters, 4u);
+  // The block-parallel tier has just searched this very stream and declined it (another encoder's): its scan's
+  // survivors are still in g.surv — the scan applies the same tests for both tiers, the reference's own rules are the
+  // verify kernels' — so only their count goes back into place (0.06 of the 1.65 ms of 64 MiB of zlib text).
+  const bool reuse = G.nb == 1 && g.sv.holds(g.surv, G.d_in, b0.in_off, b0.c) && b0.start_rel == 0u && g.sv.n <= G.surv_cap;
+  g.sv.drop();
+  if (reuse) {  // the header test alone
+    g.pinned->t2.nsurv = g.sv.n;
+    HIPCHK(hipMemcpyAsync(G.counters, &g.pinned->t2.nsurv, 4, hipMemcpyHostToDevice, g.stream));
+    rc = launch_verify(G.d_in, G.dbufs, G.surv_cap, G.counters, cntk, T2_SEARCH.loose, b0.c);
+  } else {
+    rc = launch_search(G.d_in, G.dbufs, 1u, chunks, G.surv_cap, G.counters, cntk, G.sink, T2_SEARCH, b0.c);
+  }
+  if (rc) return rc;
+  // one candidate per bucket of the stream, in order (at most SEG_BUCKETS segments whatever the block size)
+  Timed t("k_inf_cand_thin");
+  const uint32_t bucket_bits = (uint32_t)((b0.c * 8 + SEG_BUCKETS - 1) / SEG_BUCKETS);
+  HIPCHK(hipMemsetAsync(g.mvlist.p, 0xFF, SEG_BUCKETS * 4, g.stream));
+  hipLaunchKernelGGL(k_inf_cand_bucket, dim3((uint32_t)std::min<uint64_t>(b0.cand_cap / 256 + 1, 1024)), dim3(256), 0, g.stream,
+                     (const uint32_t*)g.cand.p + b0.cand_base, (const uint32_t*)cntk, b0.cand_cap, bucket_bits, (uint32_t*)g.mvlist.p);
+  hipLaunchKernelGGL(k_inf_cand_compact, dim3(1), dim3(1024), 0, g.stream, (const uint32_t*)g.mvlist.p,
+                     (uint32_t*)g.cand_sorted.p + b0.cand_base, cntk);
+  return ZES_OK;
+}
+
+// step 3: the candidate counts, back on the host
+int t2_group_counts(T2Group& G) {
+  const uint32_t nb = G.nb;
+  uint32_t* hc = g.pinned->t2.ncand;
+  HIPCHK(hipMemcpyAsync(hc, G.cnt, (size_t)nb * 4, hipMemcpyDeviceToHost, g.stream));
+  host_lap("(host work since)");
+  HIPCHK(hipStreamSynchronize(g.stream));
+  host_lap("T2: search (verify, thinning)");
+  G.nc.assign(hc, hc + nb);
+  if (getenv("ZES_T2_DBG")) {  // the candidate lists, for a comparison with a map of the stream (tools/gpu_t2_candidates.py)
+    for (uint32_t k = 0; k < nb; k++) {
+      std::vector<uint32_t> hcand(std::min<uint32_t>(G.nc[k], SEG_BUCKETS));
+      if (!hcand.empty()) HIPCHK(hipMemcpy(hcand.data(), (const uint32_t*)g.cand_sorted.p + G.cbase[k], hcand.size() * 4, hipMemcpyDeviceToHost));
+      fprintf(stderr, "zes T2 candidates buf %u (%zu):", k, hcand.size());
+      for (uint32_t v : hcand) fprintf(stderr, " %u", v + 16u);
+      fprintf(stderr, "\n");
+    }
+  }
+  return ZES_OK;
+}
+
+// step 4: segment runs, as many buffers as fit the work-item budget at a time
+int t2_group_runs(T2Group& G) {
+  int rc;
+  std::vector<uint32_t> rid, rbase, rn;
+  for (uint32_t k = 0; k < G.nb;) {
+    uint32_t work = 0;
+    rid.clear();
+    rbase.clear();
+    rn.clear();
+    for (; k < G.nb; k++) {
+      if (G.nc[k] > SEG_BUCKETS) continue;  // (a poisoned count; a stream without a second block start is still one block for the block decoder)
+      if (!rid.empty() && work + G.nc[k] + 1 > SEG_GROUP_WORK) break;
+      rid.push_back(G.ids[k]);
+      rbase.push_back(G.cbase[k]);
+      rn.push_back(G.nc[k]);
+      work += G.nc[k] + 1;
+    }
+    const uint32_t nr = (uint32_t)rid.size();
+    if (nr && (rc = inflate_segments_run(G.d_in, G.d_out, G.jobs, rid.data(), rbase.data(), rn.data(), nr, seg_words(G.nb, nr)))) return rc;
   }
   return ZES_OK;
 }
@@ -2000,153 +2288,13 @@ int inflate_segments_run(const uint8_t* d_in, uint8_t* d_out, InfJob* jobs, cons
 int inflate_segments(const uint8_t* d_in, uint8_t* d_out, InfJob* jobs, const std::vector<uint32_t>& all) {
   int rc;
   for (size_t g0 = 0; g0 < all.size(); g0 += SEG_GROUP_BUFS) {
-    const uint32_t nb = (uint32_t)std::min<size_t>(SEG_GROUP_BUFS, all.size() - g0);
-    const uint32_t* ids = all.data() + g0;
-    // ---- candidates, buffer by buffer (each search has the chip to itself) ----
-    std::vector<uint32_t> cbase(nb), ccap(nb);
-    uint64_t cands = 0, max_c = 0;
-    for (uint32_t k = 0; k < nb; k++) {
-      const InfJob& j = jobs[ids[k]];
-      cbase[k] = (uint32_t)cands;
-      ccap[k] = (uint32_t)(j.c / 64 + 64);
-      cands += ccap[k];
-      max_c = std::max(max_c, j.c);
-    }
-    const uint32_t surv_cap = (uint32_t)std::min<uint64_t>(max_c / 4 + 1024ull, 1ull << 30);
-    const size_t cnt_words = 4 + (size_t)nb + 2 * (size_t)nb + 4 + 4 + ((size_t)nb + 3) / 4;  // scan/verify scratch, counts, run scratch (+ far-match counter), first-byte sink (a byte per buffer)
-    if ((rc = ensure(g.ibufs, sizeof(ZesInfBuf) * 2))) return rc;
-    if ((rc = ensure(g.surv, (size_t)surv_cap * 8))) return rc;
-    if ((rc = ensure(g.cand, (size_t)cands * 4))) return rc;
-    if ((rc = ensure(g.cand_sorted, (size_t)cands * 4))) return rc;
-    if ((rc = ensure(g.counters, cnt_words * 4))) return rc;
-    if ((rc = ensure(g.mvlist, SEG_BUCKETS * 4))) return rc;
-    uint32_t* counters = (uint32_t*)g.counters.p;
-    uint32_t* cnt = counters + 4;
-    uint32_t* dscratch = cnt + nb;
-    uint8_t* sink = (uint8_t*)(dscratch + 2 * nb + 4);
-    HIPCHK(hipMemsetAsync(counters, 0, cnt_words * 4, g.stream));
-    const ZesInfBuf* dbufs = (const ZesInfBuf*)g.ibufs.p;
-    // Several buffers (a batch of another encoder's streams): one scan and one header test over all of them, the lists
-    // sorted by one launch; only a buffer with more candidates than a segment run takes (tiny blocks) is thinned, by
-    // itself, afterwards.  (256 streams of 1 MiB: the searches one after the other were 36 ms of launches.)
-    std::vector<char> searched(nb, 0);
-    if (nb > 1) {
-      ZesInfBuf* hb = g.pinned->t2.search;
-      memset(hb, 0, sizeof(ZesInfBuf) * (nb + 1));
-      uint64_t chunks = 0, total_c = 0;
-      for (uint32_t k = 0; k < nb; k++) {
-        const InfJob& j = jobs[ids[k]];
-        hb[k].in_off = j.in_off;
-        hb[k].c = j.c;
-        hb[k].out_off = j.out_off;
-        hb[k].cap = j.cap;
-        hb[k].first_chunk = (uint32_t)chunks;
-        hb[k].cand_base = cbase[k];
-        hb[k].cand_cap = ccap[k];
-        hb[k].start_rel = j.start0 - 16u;  // (a piece of a longer stream: nothing in front of its first block is searched)
-        chunks += (j.c + INF_SCAN_BYTES - 1) / INF_SCAN_BYTES;
-        total_c += j.c;
-      }
-      hb[nb].first_chunk = (uint32_t)chunks;
-      const uint32_t surv_all = (uint32_t)std::min<uint64_t>(total_c / 4 + 1024ull * nb, 1ull << 30);
-      if ((rc = ensure(g.ibufs, sizeof(ZesInfBuf) * (nb + 1)))) return rc;
-      if ((rc = ensure(g.surv, (size_t)surv_all * 8))) return rc;
-      dbufs = (const ZesInfBuf*)g.ibufs.p;
-      HIPCHK(hipMemcpyAsync(g.ibufs.p, hb, sizeof(ZesInfBuf) * (nb + 1), hipMemcpyHostToDevice, g.stream));
-      if ((rc = launch_search(d_in, dbufs, nb, (uint32_t)chunks, surv_all, counters, cnt, sink, T2_SEARCH, total_c))) return rc;
-      {
-        Timed t("k_inf_ranksort");
-        hipLaunchKernelGGL(k_inf_ranksort, dim3(nb), dim3(1024), 0, g.stream, dbufs, (const uint32_t*)cnt, (const uint32_t*)g.cand.p,
-                           (uint32_t*)g.cand_sorted.p, SEG_BUCKETS);
-      }
-      uint32_t* hc0 = g.pinned->t2.ncand;
-      HIPCHK(hipMemcpyAsync(hc0, cnt, (size_t)nb * 4, hipMemcpyDeviceToHost, g.stream));
-      HIPCHK(hipStreamSynchronize(g.stream));
-      for (uint32_t k = 0; k < nb; k++) searched[k] = hc0[k] <= SEG_BUCKETS;  // (the others: thinned below, from a search of their own)
-      bool redo = false;
-      for (uint32_t k = 0; k < nb; k++) redo = redo || !searched[k];
-      if (redo) {
-        if ((rc = ensure(g.ibufs2, sizeof(ZesInfBuf) * 2))) return rc;
-        dbufs = (const ZesInfBuf*)g.ibufs2.p;
-      }
-    }
-    for (uint32_t k = 0; k < nb; k++) {
-      if (searched[k]) continue;
-      HIPCHK(hipMemsetAsync(cnt + k, 0, 4, g.stream));
-      const InfJob& j = jobs[ids[k]];
-      ZesInfBuf b0, b1;
-      memset(&b0, 0, sizeof b0);
-      memset(&b1, 0, sizeof b1);
-      b0.in_off = j.in_off;
-      b0.c = j.c;
-      b0.out_off = j.out_off;
-      b0.cap = j.cap;
-      b0.cand_base = cbase[k];
-      b0.cand_cap = ccap[k];
-      b0.start_rel = j.start0 - 16u;
-      const uint32_t chunks = (uint32_t)((j.c + INF_SCAN_BYTES - 1) / INF_SCAN_BYTES);
-      b1.first_chunk = chunks;
-      hipLaunchKernelGGL(k_inf_set_table1, dim3(1), dim3(64), 0, g.stream, b0, b1, const_cast<ZesInfBuf*>(dbufs), counters, 4u);
-      // The block-parallel tier has just searched this very stream and declined it (another encoder's): its scan's
-      // survivors are still in g.surv — the scan applies the same tests for both tiers, the reference's own rules are the
-      // verify kernels' — so only their count goes back into place (0.06 of the 1.65 ms of 64 MiB of zlib text).
-      const bool reuse = nb == 1 && g.sv_ok && g.sv_list == g.surv.p && g.sv_din == d_in && g.sv_in_off == j.in_off && g.sv_c == j.c && j.start0 == 16u && g.sv_n <= surv_cap;
-      g.sv_ok = false;
-      if (reuse) {  // the header test alone
-        g.pinned->t2.nsurv = g.sv_n;
-        HIPCHK(hipMemcpyAsync(counters, &g.pinned->t2.nsurv, 4, hipMemcpyHostToDevice, g.stream));
-        rc = launch_verify(d_in, dbufs, surv_cap, counters, cnt + k, T2_SEARCH.loose, j.c);
-      } else {
-        rc = launch_search(d_in, dbufs, 1u, chunks, surv_cap, counters, cnt + k, sink, T2_SEARCH, j.c);
-      }
-      if (rc) return rc;
-      {
-        // one candidate per bucket of the stream, in order (at most SEG_BUCKETS segments whatever the block size)
-        Timed t("k_inf_cand_thin");
-        const uint32_t bucket_bits = (uint32_t)((j.c * 8 + SEG_BUCKETS - 1) / SEG_BUCKETS);
-        HIPCHK(hipMemsetAsync(g.mvlist.p, 0xFF, SEG_BUCKETS * 4, g.stream));
-        hipLaunchKernelGGL(k_inf_cand_bucket, dim3((uint32_t)std::min<uint64_t>(ccap[k] / 256 + 1, 1024)), dim3(256), 0, g.stream,
-                           (const uint32_t*)g.cand.p + cbase[k], (const uint32_t*)(cnt + k), ccap[k], bucket_bits, (uint32_t*)g.mvlist.p);
-        hipLaunchKernelGGL(k_inf_cand_compact, dim3(1), dim3(1024), 0, g.stream, (const uint32_t*)g.mvlist.p,
-                           (uint32_t*)g.cand_sorted.p + cbase[k], cnt + k);
-      }
-    }
-    uint32_t* hc = g.pinned->t2.ncand;
-    HIPCHK(hipMemcpyAsync(hc, cnt, (size_t)nb * 4, hipMemcpyDeviceToHost, g.stream));
-    host_lap("(host work since)");
-    HIPCHK(hipStreamSynchronize(g.stream));
-    host_lap("T2: search (verify, thinning)");
-    std::vector<uint32_t> nc(hc, hc + nb);
-    if (getenv("ZES_T2_DBG")) {  // the candidate lists, for a comparison with a map of the stream (tools/gpu_t2_candidates.py)
-      for (uint32_t k = 0; k < nb; k++) {
-        std::vector<uint32_t> hcand(std::min<uint32_t>(nc[k], SEG_BUCKETS));
-        if (!hcand.empty()) HIPCHK(hipMemcpy(hcand.data(), (const uint32_t*)g.cand_sorted.p + cbase[k], hcand.size() * 4, hipMemcpyDeviceToHost));
-        fprintf(stderr, "zes T2 candidates buf %u (%zu):", k, hcand.size());
-        for (uint32_t v : hcand) fprintf(stderr, " %u", v + 16u);
-        fprintf(stderr, "\n");
-      }
-    }
-    // ---- segment runs: as many buffers as fit the work-item budget at a time ----
-    std::vector<uint32_t> rid, rbase, rn;
-    uint32_t work = 0;
-    auto flush = [&]() -> int {
-      if (rid.empty()) return ZES_OK;
-      const int r = inflate_segments_run(d_in, d_out, jobs, rid.data(), rbase.data(), rn.data(), (uint32_t)rid.size(), dscratch);
-      rid.clear();
-      rbase.clear();
-      rn.clear();
-      work = 0;
-      return r;
-    };
-    for (uint32_t k = 0; k < nb; k++) {
-      if (nc[k] > SEG_BUCKETS) continue;  // (a poisoned count; a stream without a second block start is still one block for the block decoder)
-      if (work + nc[k] + 1 > SEG_GROUP_WORK && (rc = flush())) return rc;
-      rid.push_back(ids[k]);
-      rbase.push_back(cbase[k]);
-      rn.push_back(nc[k]);
-      work += nc[k] + 1;
-    }
-    if ((rc = flush())) return rc;
+    T2Group G{d_in, d_out, jobs, all.data() + g0, (uint32_t)std::min<size_t>(SEG_GROUP_BUFS, all.size() - g0)};
+    if ((rc = t2_group_table(G))) return rc;
+    if (G.nb > 1 && (rc = t2_search_group(G))) return rc;
+    for (uint32_t k = 0; k < G.nb; k++)
+      if (!G.searched[k] && (rc = t2_search_one(G, k))) return rc;
+    if ((rc = t2_group_counts(G))) return rc;
+    if ((rc = t2_group_runs(G))) return rc;
   }
   return ZES_OK;
 }
@@ -2269,12 +2417,7 @@ int inflate_slow(const uint8_t* d_in, uint8_t* d_out, InfJob& j) {
     zes_wd_set_dbg((unsigned long long*)g.dbg.p);
 #endif
     {
-      ZesInfBuf b0;
-      memset(&b0, 0, sizeof b0);
-      b0.in_off = j.in_off;
-      b0.c = j.c;
-      b0.out_off = j.out_off;
-      b0.cap = j.cap;
+      const ZesInfBuf b0 = inf_buf(j);
       if ((rc = ensure(g.ibufs, sizeof(ZesInfBuf) * 2))) return rc;
       hipLaunchKernelGGL(k_inf_set_table1, dim3(1), dim3(64), 0, g.stream, b0, b0, (ZesInfBuf*)g.ibufs.p, (uint32_t*)nullptr, 0u);
       Timed t("k_inf_decode_seq");
@@ -2373,7 +2516,7 @@ int gather_bytes(const uint8_t* d_in, const std::vector<InfJob>& jobs, const uin
 // for the buffers to decode (anything else is left untouched).  firsts[i] = first byte of buffer i.
 int inflate_jobs(const uint8_t* d_in, uint8_t* d_out, std::vector<InfJob>& jobs, const uint8_t* firsts, uint32_t flags) {
   g.last_tier = 0;
-  g.sv_ok = false;  // (a survivor list serves the call that made it: the bytes behind a pointer may have changed since)
+  g.sv.drop();  // (a survivor list serves the call that made it: the bytes behind a pointer may have changed since)
   std::vector<uint32_t> ids;
   std::vector<uint32_t> todo;
   std::vector<uint32_t> small;  // buffers T1 does not take and whose first byte is still on the device
@@ -2435,14 +2578,7 @@ int inflate_jobs(const uint8_t* d_in, uint8_t* d_out, std::vector<InfJob>& jobs,
       for (size_t g0 = 0; g0 < rest.size(); g0 += INF_GROUP) {
         const uint32_t nb = (uint32_t)std::min<size_t>(INF_GROUP, rest.size() - g0);
         ZesInfBuf* hb = g.pinned->t1.table;
-        memset(hb, 0, sizeof(ZesInfBuf) * nb);
-        for (uint32_t k = 0; k < nb; k++) {
-          const InfJob& j = jobs[rest[g0 + k]];
-          hb[k].in_off = j.in_off;
-          hb[k].c = j.c;
-          hb[k].out_off = j.out_off;
-          hb[k].cap = j.cap;
-        }
+        for (uint32_t k = 0; k < nb; k++) hb[k] = inf_buf(jobs[rest[g0 + k]]);
         if ((rc = ensure(g.ibufs, sizeof(ZesInfBuf) * nb))) return rc;
         if ((rc = ensure(g.res, sizeof(ZesRes) * nb))) return rc;
         if ((rc = ensure(g.resume, (size_t)16 * nb))) return rc;
@@ -2617,11 +2753,7 @@ int zes_shutdown(void) {
 
 // every pooled device buffer of the current context
 static void free_scratch_locked() {
-  for_each_pool(g, [](DevBuf& b) {
-    if (b.p) (void)hipFree(b.p);
-    b.p = nullptr;
-    b.cap = 0;
-  });
+  for_each_pool(g, [](DevBuf& b) { (void)release(b); });
 }
 
 int zes_trim(void) {
@@ -2645,9 +2777,7 @@ static int shutdown_one(void) {
   (void)hipSetDevice(g.device);
   (void)hipStreamSynchronize(g.stream);
   free_scratch_locked();
-  if (g.kraft.p) (void)hipFree(g.kraft.p);
-  g.kraft.p = nullptr;
-  g.kraft.cap = 0;
+  (void)release(g.kraft);
   if (g.pinned) (void)hipHostFree(g.pinned);
   if (g.mirror) (void)hipHostFree(g.mirror);
   if (g.res_more) (void)hipHostFree(g.res_more);
@@ -3801,7 +3931,7 @@ static int grow_keep(DevBuf& b, size_t bytes, size_t keep) {
   HIPCHK(hipMalloc(&p, want));
   if (keep) HIPCHK(hipMemcpyAsync(p, b.p, keep, hipMemcpyDeviceToDevice, g.stream));
   HIPCHK(hipStreamSynchronize(g.stream));
-  if (b.p) HIPCHK(hipFree(b.p));
+  HIPCHK(release(b));
   b.p = p;
   b.cap = want;
   return ZES_OK;
