@@ -287,6 +287,21 @@ int zes_inflate_range_dev(const uint8_t* d_in, uint64_t c, uint64_t lo_bit, uint
  * tokens[i] = literal byte, or 0x80000000 | (len-3) << 16 | (dist-1) for a match. */
 int zes_stage_lz77_dev(const uint8_t* d_in, uint64_t n, uint64_t start, uint32_t len,
                        uint32_t* h_tokens, uint32_t* ntokens);
+/* The route record of the calling thread's last zes_stage_lz77_dev call: which of the encoder's data-dependent paths that
+ * block took.  For tests: the pipeline entry points record nothing.  Nine words (cap >= 9, else ZES_E_ARG):
+ *   [0] [1] [2]  the block's flag word (kept positions | 0x80000000 lazy | 0x40000000 left to k_lz_index | 0x20000000 handed
+ *                back) behind the first k_lz_sort launch, k_lz_index and the second k_lz_sort launch; [1] and [2] are 0 for
+ *                a block k_lz_sort did not leave to k_lz_index
+ *   [3]          k_lz_sort, a block it kept: 1 two filter levels | 2 dense (no filter: every position sorted); 0 one level
+ *   [4]          k_lz_index: words of its largest class | 0x40000000 a group above 16384 words | 0x80000000 a sixteenth of
+ *                the positions in heavy classes
+ *   [5]          head of the match list: matches k_lz_match found, or 0xFFFFFFFF for a block of k_lz_match_lazy
+ *   [6]          head of the chain mask (lazy blocks: 1 the mask is there; else 0)
+ *   [7]          k_lz_match_lazy: 1 guarded loop | 2 probed | 4 found periodic | 8 phase 3 ran out of its budget |
+ *                16 words cleared late after a second chain gave up | 32 phase 3 walked the true chain; else 0
+ *   [8]          tokens
+ * replaces: nothing (the reference has one path). */
+int zes_stage_lz77_route(uint32_t* words, uint32_t cap);
 /* replaces: the code-length half of generateDeflateHuffmanTable src/huffman.ts:55-115.
  * hist[nsym] symbol counts → lens[nsym] code lengths (0 = unused), limit maxlen (15 or 7). */
 int zes_stage_huff_lengths_dev(const uint32_t* h_hist, uint32_t nsym, uint32_t maxlen, uint8_t* h_lens);

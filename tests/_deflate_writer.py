@@ -49,10 +49,16 @@ def fields_to_bits(values, widths):
     total = int(widths.sum())
     if total == 0:
         return np.zeros(0, dtype=np.uint8)
-    idx = np.repeat(np.arange(widths.size), widths)
-    starts = np.cumsum(widths) - widths
-    pos = (np.arange(total) - starts[idx]).astype(np.uint64)
-    return ((values[idx] >> pos) & np.uint64(1)).astype(np.uint8)
+    # every field lands in the 64-bit word its first bit falls into (the part that does not fit: in the next one); the
+    # fields are in order, so the words are sums over runs of fields, and fields never share a bit: sum = or
+    values = values & (~np.uint64(0) >> (64 - np.minimum(widths, 64)).astype(np.uint64)) * (widths > 0)
+    off = np.cumsum(widths) - widths
+    wi, sh = off >> 6, (off & 63).astype(np.uint64)
+    first = np.flatnonzero(np.concatenate([[True], wi[1:] != wi[:-1]]))
+    words = np.zeros((total + 63) // 64 + 1, dtype=np.uint64)
+    words[wi[first]] = np.add.reduceat(values << sh, first)
+    words[wi[first] + 1] |= np.add.reduceat((values >> np.uint64(1)) >> (np.uint64(63) - sh), first)
+    return np.unpackbits(words.astype("<u8").view(np.uint8), bitorder="little")[:total]
 
 
 class BitWriter:
@@ -244,8 +250,9 @@ def encode_tokens(tok, llens, dlens, fixed_dist=False):
         return np.zeros(0, dtype=np.uint8)
     lcodes, dcodes = canonical(llens), canonical(dlens)
     assert (llens[tok.sym] > 0).all(), "a symbol without a code"
+    # (codes are reversed per symbol, not per token)
     lw = llens[tok.sym]
-    lv = _rev(lcodes[tok.sym], lw)
+    lv = _rev(lcodes, llens)[tok.sym]
     hasd = tok.dsym >= 0
     ds = np.where(hasd, tok.dsym, 0)
     if fixed_dist:
@@ -254,7 +261,7 @@ def encode_tokens(tok, llens, dlens, fixed_dist=False):
     else:
         assert (dlens[ds[hasd]] > 0).all(), "a distance without a code"
         dw = np.where(hasd, dlens[ds], 0)
-        dv = _rev(dcodes[ds], dw)
+        dv = np.where(hasd, _rev(dcodes, dlens)[ds], np.uint64(0))
     # one field of at most 15 + 5 + 15 + 13 bits per token
     v = lv.copy()
     w = lw.copy()
@@ -370,10 +377,10 @@ def dynamic(w, tok, llens, dlens, final=False, cl_syms=None, hlit=None, hdist=No
     return w
 
 
-def ref_dynamic(w, tok, final=False):
-    """A dynamic block the way the reference writes one (src/deflate.ts:56-227): histograms with EOB counted once,
-    lengths by its Huffman builder at 15 bits, HLIT / HDIST up to the largest symbol used, its run-length rule,
-    the code-length code at 7 bits, HCLEN up to its last non-zero length."""
+def ref_header(tok):
+    """What the reference puts into a dynamic block's header for these tokens (src/deflate.ts:56-148): histograms with
+    EOB counted once, lengths by its Huffman builder at 15 bits, HLIT / HDIST up to the largest symbol used, its
+    run-length rule, the code-length code at 7 bits -> (llens, dlens, hlit, hdist, cl_syms, clens)."""
     import _oracle
 
     lhist = np.bincount(tok.sym, minlength=286)[:286].astype(np.uint32)
@@ -403,7 +410,14 @@ def ref_dynamic(w, tok, final=False):
         i += 1
     chist = np.bincount([s for s, _ in cl_syms], minlength=19).astype(np.uint32)
     clens = _oracle.huff_lengths(chist, 7).astype(np.int64)
-    return dynamic(w, tok, llens, dlens, final, cl_syms=cl_syms, hlit=lmax + 1, hdist=dmax + 1, clens=clens)
+    return llens, dlens, lmax + 1, dmax + 1, cl_syms, clens
+
+
+def ref_dynamic(w, tok, final=False):
+    """A dynamic block the way the reference writes one (src/deflate.ts:56-227): ref_header's header (HCLEN up to the
+    code-length code's last non-zero length), then the tokens."""
+    llens, dlens, hlit, hdist, cl_syms, clens = ref_header(tok)
+    return dynamic(w, tok, llens, dlens, final, cl_syms=cl_syms, hlit=hlit, hdist=hdist, clens=clens)
 
 
 def ref_block(w, data, start, length, final=False):

@@ -125,6 +125,7 @@ def lib():
                                             u32p, i32p]
         L.zes_deflate_join_dev.argtypes = [C.POINTER(C.c_void_p), u64p, u32p, u64p, C.c_uint32, C.c_void_p, C.c_uint64, u64p]
         L.zes_stage_lz77_dev.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint32, C.c_void_p, u32p]
+        L.zes_stage_lz77_route.argtypes = [C.c_void_p, C.c_uint32]
         L.zes_stage_huff_lengths_dev.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]
         L.zes_stage_chain.argtypes = [u32p, u64p, u32p, u32p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, i32p, u64p, u32p, u32p]
         L.zes_selftest_lds_order.argtypes = [C.c_uint32, C.c_uint32, u64p, u64p]
@@ -636,6 +637,15 @@ def stage_lz77_tensor(t, start, length):
     if rc:
         _raise(rc)
     return tok[: nt.value].copy()
+
+
+def stage_lz77_route():
+    """zes_stage_lz77_route: the nine route words of this thread's last stage_lz77_tensor call (include/zes.h)."""
+    w = np.zeros(9, dtype=np.uint32)
+    rc = lib().zes_stage_lz77_route(w.ctypes.data, w.size)
+    if rc:
+        _raise(rc)
+    return w
 
 
 def selftest_lds_order(iters=200, seed=1):

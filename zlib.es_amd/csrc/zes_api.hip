@@ -206,6 +206,7 @@ struct Ctx {
   std::vector<std::string> name_pool;
   int last_tier = 0;
   int last_members = 0;  // members the member-parallel gzip reader decoded in the last gunzip call (0: the serial path answered)
+  uint32_t route[ZES_ROUTE_WORDS] = {0};  // zes_stage_lz77_dev's last block: what its kernels did (zes_stage_lz77_route)
   SurvList sv;  // (of `surv`)
   char arch[64] = {0};
   int cus = 0;
@@ -775,8 +776,10 @@ int phases_print(PhaseSetter set, uint32_t nblk, int ran, const char* fmt) {
 // stand-in, both launch through here.  after_index() runs between the index and the match launches.
 // heaviest_first: a batch of unlike buffers, the lazy matcher takes the blocks in k_lz_order's order.
 // phases: ZES_DEBUG_PHASES stamps of the lazy matcher (printed here) and the parser (armed here: the caller prints them).
+// route: null in the pipeline.  The stage entry's one block: behind each index launch its flag word is copied to
+// route[0..2], and the word the launch left in idx_b's last slot to route[3] (first sort) and route[4] (k_lz_index).
 template <class F>
-int launch_lz77(const uint8_t* d_in, uint32_t grid, bool use_index, bool heaviest_first, bool phases, F after_index) {
+int launch_lz77(const uint8_t* d_in, uint32_t grid, bool use_index, bool heaviest_first, bool phases, F after_index, uint32_t* route = nullptr) {
   int rc;
   const ZesBuf* dbufs = (const ZesBuf*)g.bufs.p;
   ZesBlk* dblks = (ZesBlk*)g.blks.p;
@@ -789,14 +792,24 @@ int launch_lz77(const uint8_t* d_in, uint32_t grid, bool use_index, bool heavies
     hipLaunchKernelGGL(k_lz_sort, dim3(grid), dim3(SORT_THREADS), 0, g.stream, d_in, dbufs, dblks, idx_a, idx_b, idx_a, (uint16_t*)g.sdelta.p,
                        ZES_SORT_MODE_FIRST | (use_index ? ZES_SORT_USE_INDEX : 0u));
   }
+  auto note = [&](uint32_t* flag_to, uint32_t* word_to) -> int {  // (copies on the stream, behind the launch they report on)
+    HIPCHK(hipMemcpyAsync(flag_to, idx_a + ZES_BLK - 1, 4, hipMemcpyDeviceToHost, g.stream));
+    if (word_to) HIPCHK(hipMemcpyAsync(word_to, idx_b + ZES_BLK - 1, 4, hipMemcpyDeviceToHost, g.stream));
+    return ZES_OK;
+  };
+  if (route && (rc = note(&route[0], &route[3]))) return rc;
   if (use_index) {
     {
       Timed t("k_lz_index");
       hipLaunchKernelGGL(k_lz_index, dim3(grid), dim3(IDX_THREADS), 0, g.stream, d_in, dbufs, dblks, idx_a, idx_b, idx_a, (uint16_t*)g.sdelta.p);
     }
-    Timed t("k_lz_sort_redo");
-    hipLaunchKernelGGL(k_lz_sort, dim3(grid), dim3(SORT_THREADS), 0, g.stream, d_in, dbufs, dblks, idx_a, idx_b, idx_a, (uint16_t*)g.sdelta.p,
-                       ZES_SORT_MODE_REDO);
+    if (route && (rc = note(&route[1], &route[4]))) return rc;
+    {
+      Timed t("k_lz_sort_redo");
+      hipLaunchKernelGGL(k_lz_sort, dim3(grid), dim3(SORT_THREADS), 0, g.stream, d_in, dbufs, dblks, idx_a, idx_b, idx_a, (uint16_t*)g.sdelta.p,
+                         ZES_SORT_MODE_REDO);
+    }
+    if (route && (rc = note(&route[2], nullptr))) return rc;
   }
   if ((rc = after_index())) return rc;
   {
@@ -4258,6 +4271,10 @@ int zes_stage_lz77_dev(const uint8_t* d_in, uint64_t n, uint64_t start, uint32_t
   if ((rc = ensure(g.mlist, ZES_MLIST_WORDS * 4))) return rc;
   HIPCHK(hipMemcpyAsync(g.bufs.p, &b, sizeof b, hipMemcpyHostToDevice, g.stream));
   HIPCHK(hipMemcpyAsync(g.blks.p, &z, sizeof z, hipMemcpyHostToDevice, g.stream));
+  // the route record: a kernel that leaves before its word (a block without keys, a dense block left to k_lz_index) reports 0
+  uint32_t route[ZES_ROUTE_WORDS] = {0};
+  memset(g.route, 0, sizeof g.route);
+  HIPCHK(hipMemsetAsync((uint32_t*)g.idx_b.p + ZES_BLK - 1, 0, 4, g.stream));
   rc = launch_lz77(d_in, 1, getenv("ZES_NO_INDEX") == nullptr, false, false, [&]() -> int {
     if (const char* dump = getenv("ZES_DUMP_INDEX")) {  // development: the block's index as the match finders will see it
       HIPCHK(hipStreamSynchronize(g.stream));
@@ -4274,17 +4291,38 @@ int zes_stage_lz77_dev(const uint8_t* d_in, uint64_t n, uint64_t start, uint32_t
       }
     }
     return ZES_OK;
-  });
+  }, route);
   if (rc) return rc;
   HIPCHK(hipGetLastError());
   HIPCHK(hipMemcpyAsync(&z, g.blks.p, sizeof z, hipMemcpyDeviceToHost, g.stream));
+  uint32_t thead[2] = {0, 0};
+  HIPCHK(hipMemcpyAsync(&route[5], g.mlist.p, 4, hipMemcpyDeviceToHost, g.stream));
+  HIPCHK(hipMemcpyAsync(thead, g.tmask.p, sizeof thead, hipMemcpyDeviceToHost, g.stream));
   HIPCHK(hipStreamSynchronize(g.stream));
+  {
+    // words of launches the block did not take part in say 0, not what an earlier call left in the pools
+    const bool to_index = (route[0] & ZES_SORT_INDEX) != 0u, lazy = route[5] == 0xFFFFFFFFu;
+    if (!to_index) route[1] = route[2] = route[4] = 0;
+    else route[3] = 0;
+    route[6] = lazy ? thead[0] : 0u;
+    route[7] = lazy ? thead[1] : 0u;
+    route[8] = z.ntok;
+    memcpy(g.route, route, sizeof route);
+  }
   // (with profiling on the sequence's Timed scopes have recorded: their events go back to the pool; what
   // zes_last_kernel_times reports stays the last pipeline call's)
   for (auto& p : g.pending) g.event_pool.insert(g.event_pool.end(), {p.second.first, p.second.second});
   g.pending.clear();
   *ntokens = z.ntok;
   HIPCHK(hipMemcpy(h_tokens, g.idx_a.p, (size_t)z.ntok * 4, hipMemcpyDeviceToHost));
+  return ZES_OK;
+}
+
+int zes_stage_lz77_route(uint32_t* words, uint32_t cap) {
+  if (!words || cap < ZES_ROUTE_WORDS) return ZES_E_ARG;
+  UseDev ud(t_last);  // the context that served this thread's last call
+  std::lock_guard<std::mutex> lk(g_mu);
+  memcpy(words, g.route, sizeof g.route);
   return ZES_OK;
 }
 

@@ -240,6 +240,7 @@ __global__ __launch_bounds__(SORT_THREADS) void k_lz_sort(const uint8_t* __restr
   // filter level over the kept ones with another hash leaves ~2 % of the positions, and the three sorting passes —
   // two thirds of this kernel on such data — have a twelfth of the elements.
   const bool two = !redo && (S.nsat & 0xFFFFu) * 5u < (S.nsat >> 16) * 2u;
+  if (tid == 0) B[ZES_BLK - 1] = (two ? ZES_ROUTE_SORT_TWO : 0u) | (dense ? ZES_ROUTE_SORT_DENSE : 0u);  // route record (zes_stage_lz77_route): no list, bucket or match word of a block reaches this slot before k_lz_match
   uint32_t ns = cnt;
   if (!dense) {
   // pass 2: keep the positions whose counter reached two; 128 flags per thread
@@ -926,6 +927,7 @@ struct LazySmem {
   uint32_t unmerged;                              // a second chain gave up: the true chain may hold unevaluated positions
   uint32_t ngave;                                 // how many gave up (the probe of a block that may be periodic counts them)
   uint32_t abort3;                                // phase 3 ran out of its budget of single evaluations: the block is not periodic after all
+  uint32_t route;                                 // ZES_ROUTE_* bits of what this block did (thread 0 alone reads and writes it): the route record
   uint32_t mp[LAZY_NWIN];                         // where the second chain from window w's exit met a window chain (LAZY_NOMERGE: it ran to the block's end)
   uint32_t tfrom[LAZY_NWIN];                      // true chain: the first position of window w's own chain that is on it (LAZY_NOMERGE: none)
   uint8_t titem[LAZY_NWIN];                       // true chain: it leaves window w at that window's exit
@@ -1493,6 +1495,7 @@ __global__ __launch_bounds__(MATCH_THREADS) void k_lz_match_lazy(const uint8_t* 
   bool probe = guarded && nwin >= 4u * LAZY_PROBE_STRIDE;
   const uint32_t tbase = cnt > LAZY_TAIL ? cnt - LAZY_TAIL : 0u;  // first pre-evaluated position
   uint32_t* tm = tmask_all + (uint64_t)g * ZES_TMASK_WORDS;
+  if (tid == 0) S.route = (guarded ? ZES_ROUTE_GUARDED : 0u) | (probe ? ZES_ROUTE_PROBED : 0u);
   for (;;) {
     if (cleared) {
       uint4* mo4 = reinterpret_cast<uint4*>(mo);
@@ -1532,7 +1535,10 @@ __global__ __launch_bounds__(MATCH_THREADS) void k_lz_match_lazy(const uint8_t* 
       __syncthreads();
       if (periodic) {
         budget3 = 64u + T / 1024u;  // (periodic data: one single evaluation per 64 maximal matches, ~10 a block)
-        if (tid == 0) S.unmerged = 1u;
+        if (tid == 0) {
+          S.unmerged = 1u;
+          S.route |= ZES_ROUTE_PERIODIC;
+        }
       } else {
         if (tid == 0) {
           S.wq = 0;
@@ -1567,6 +1573,7 @@ __global__ __launch_bounds__(MATCH_THREADS) void k_lz_match_lazy(const uint8_t* 
     }
     if (S.unmerged && !cleared) {  // (uniform) phase 3 asks "has anybody evaluated this position?": the words are cleared first, and everything is evaluated once more
       cleared = true;
+      if (tid == 0) S.route |= ZES_ROUTE_LATE_CLEAR;
       __syncthreads();  // everybody has read the flag before it is reset
       continue;
     }
@@ -1645,7 +1652,10 @@ __global__ __launch_bounds__(MATCH_THREADS) void k_lz_match_lazy(const uint8_t* 
     __syncthreads();
     for (uint32_t i = tid; i < ZES_BLK / 32; i += MATCH_THREADS) tm[4u + i] = S.v1[i];
   }
-  if (tid == 0) tm[0] = S.unmerged ? 0u : 1u;
+  if (tid == 0) {
+    tm[0] = S.unmerged ? 0u : 1u;
+    if (S.unmerged) S.route |= ZES_ROUTE_WALK3;
+  }
 
   // ---- phase 3 (periodic data only): the true chain, by one wavefront (which also notes the chain's positions
   // for k_lz_parse: V1 starts over) ----
@@ -1752,6 +1762,7 @@ __global__ __launch_bounds__(MATCH_THREADS) void k_lz_match_lazy(const uint8_t* 
     __syncthreads();
     if (S.abort3) {  // (uniform) the probe was wrong about this block: once more, every window with its chain
       probe = false;
+      if (tid == 0) S.route |= ZES_ROUTE_ABORT3;
       __syncthreads();
       continue;
     }
@@ -1761,6 +1772,7 @@ __global__ __launch_bounds__(MATCH_THREADS) void k_lz_match_lazy(const uint8_t* 
   }
   break;
   }
+  if (tid == 0) tm[1] = S.route;  // (words 1 to 3 of the mask's head are nobody's: k_lz_parse reads [0] and [4..])
   LSTAMP(5);
 }
 

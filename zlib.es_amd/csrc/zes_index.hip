@@ -373,6 +373,8 @@ __global__ __launch_bounds__(IDX_THREADS) void k_lz_index(const uint8_t* __restr
     // (uniform) a class or a group the LDS cannot hold — or a block with much of its weight in a few heavy keys (text: " th",
     // "he " ... a fifth of the positions sit in classes that need the radix passes, and k_lz_sort is the faster one there):
     // the block goes back to k_lz_sort
+    // route record (zes_stage_lz77_route): the largest class and which of the three reasons hold; the block's words in E end below this slot
+    if (tid == 0) E[ZES_BLK - 1] = S.maxc | (gmax > IDX_GCAP ? ZES_ROUTE_IDX_GROUP : 0u) | (S.nheavy * 16u > cnt ? ZES_ROUTE_IDX_HEAVY : 0u);
     if (S.maxc > IDX_BIGCAP || gmax > IDX_GCAP || S.nheavy * 16u > cnt) {
       if (tid == 0) A[ZES_BLK - 1] = cnt | ZES_SORT_REDO;
       return;

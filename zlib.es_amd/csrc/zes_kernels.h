@@ -13,6 +13,21 @@
 #define ZES_SORT_INDEX 0x40000000u  // a dense block k_lz_sort left to k_lz_index
 #define ZES_SORT_REDO 0x20000000u   // k_lz_index handed the block back (a class too large for its LDS): k_lz_sort, second launch
 #define ZES_INV_NONE 0xFFFFFFFFu    // inv entry of a position without a candidate
+// The route record (zes_stage_lz77_route, tests only): what the data made a block's kernels do.  k_lz_sort and k_lz_index
+// leave one word each in idx_b[g][ZES_BLK-1] (free until the match finders: lists, buckets and k_lz_index's words end below
+// it), k_lz_match_lazy one in word 1 of the block's chain mask head; nothing in the pipeline reads them.
+#define ZES_ROUTE_WORDS 9u             // words of a record (include/zes.h)
+#define ZES_ROUTE_SORT_TWO 1u          // k_lz_sort: two filter levels
+#define ZES_ROUTE_SORT_DENSE 2u        // k_lz_sort: a dense block it kept (no filter: every position is sorted)
+#define ZES_ROUTE_IDX_MAXC 0x3FFFFu    // k_lz_index: words of its largest class ...
+#define ZES_ROUTE_IDX_GROUP 0x40000000u  // ... a group above the LDS's share
+#define ZES_ROUTE_IDX_HEAVY 0x80000000u  // ... a sixteenth of the positions in heavy classes
+#define ZES_ROUTE_GUARDED 1u           // k_lz_match_lazy: the guarded form of the loop (a block of k_lz_index)
+#define ZES_ROUTE_PROBED 2u            // the block was probed (64 windows and more)
+#define ZES_ROUTE_PERIODIC 4u          // the probe's verdict: periodic
+#define ZES_ROUTE_ABORT3 8u            // phase 3 ran out of its budget: every window got its chain after all
+#define ZES_ROUTE_LATE_CLEAR 16u       // an unguarded block whose second chain gave up: words cleared, evaluated once more
+#define ZES_ROUTE_WALK3 32u            // phase 3 walked the true chain
 #define PARSE_THREADS 1024
 #define EMIT_THREADS 1024
 #define HUFF_THREADS_HOST 256
