@@ -256,7 +256,8 @@ int zes_inflate_batch_alloc(const uint8_t* const* in, const uint64_t* in_len, ze
  * zes_deflate_join_dev: 78 9C | the pieces, bit-concatenated | zero pad | Adler-32 of the whole (combined from the
  *   pieces' values and lengths: src/adler32.ts:1-10 is associative in that sense), into d_out.  The pieces are device
  *   pointers on this GPU (4-byte aligned), in order; they are read, and d_out is written, in whole dwords: piece i
- *   must be readable up to the dword that holds its last bit (zes_deflate_range_dev's own output is), and
+ *   must be readable up to the dword that holds its last bit (zes_deflate_range_dev's own output is; bits behind the
+ *   piece's last one may hold anything; the pointer of a piece of no bits is not looked at and may be null), and
  *   cap >= the result's length rounded up to 4 — otherwise ZES_E_NOSPACE with *out_len = the result's length.
  * replaces: the block loop of src/deflate.ts:20-34 and the wrapper of src/zlib.ts:25-49, split at block boundaries. */
 int zes_deflate_range_dev(const uint8_t* d_in, uint64_t n, uint64_t n_readable, int final_range, uint8_t* d_out, uint64_t cap,
@@ -273,9 +274,11 @@ int zes_deflate_join_dev(const uint8_t* const* d_piece, const uint64_t* piece_bi
  *   lo_bit, own_bit      blocks that start at bit lo_bit <= s < own_bit (relative to d_in; lo_bit >= 16) belong to the call
  *   exact_start          != 0: a block starts exactly at lo_bit (the end bit of the piece before); 0: the first block
  *                        start found at or behind lo_bit begins the chain (a GPU that takes a middle part of the stream)
- *   d_out, cap           block k of the range goes to d_out + k * 131072
+ *   d_out, cap           block k of the range goes to d_out + k * 131072; nothing is written behind the range's last block
  *   *first_bit, *end_bit bit positions (relative to d_in) of the range's first block and behind its last one: consecutive
  *                        ranges fit when one's end is the next one's first; *nblocks, *final_block (BFINAL seen)
+ * A range without exact_start that holds no block start (a piece in the middle of one block) is ZES_OK with *nblocks == 0,
+ * *out_len == 0, nothing written, and *first_bit == *end_bit == lo_bit.
  * ZES_E_NOTRANGE: not a clean chain (another encoder's stream, a false block start): decode the stream with zes_inflate_dev.
  * replaces: the block loop of src/inflate.ts:22-37, split at block boundaries. */
 int zes_inflate_range_dev(const uint8_t* d_in, uint64_t c, uint64_t lo_bit, uint64_t own_bit, int exact_start, uint8_t* d_out,

@@ -1579,7 +1579,7 @@ RangePiece range_piece(uint64_t in_off, uint64_t c, uint64_t lo_bit, uint64_t ow
   b0->cand_cap = pd.cand_cap;
   b0->start_rel = (uint32_t)(lo_bit - 16);
   b0->own_rel = (uint32_t)std::min<uint64_t>(own_bit >= 16 ? own_bit - 16 : 0, 0xFFFFFFFEull);
-  b0->range_flags = exact ? 0u : ZES_START_ANY;
+  b0->range_flags = (exact ? 0u : ZES_START_ANY) | ZES_OWN_ONLY;
   b1->first_chunk = pd.chunks;
   b1->cand_base = pd.cand_cap;
   return pd;

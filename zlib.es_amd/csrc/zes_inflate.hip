@@ -377,7 +377,7 @@ __global__ __launch_bounds__(64) void k_inf_verify(const uint8_t* __restrict__ d
       if (have) {
         // ---- one code-length symbol; no branch in it: a step of a lone lane is a dependent chain, and every exec-mask
         // region the compiler builds for an `if` adds to it (the branchy form took ~1400 cycles per step) ----
-        uint32_t ok = (uint32_t)(pos + 14u <= limit);
+        uint32_t ok = 1u;
         {
           const uint32_t need = (uint32_t)(nb <= 32u);
           if (__ballot(need && wi == WIN)) {  // only a lane that found no room on the list gets here: the next window
@@ -410,6 +410,7 @@ __global__ __launch_bounds__(64) void k_inf_verify(const uint8_t* __restrict__ d
         bb >>= adv;
         nb -= adv;
         pos += adv;
+        ok &= (uint32_t)(pos <= limit);  // the symbol's own bits lie inside the data (a final block may end with the buffer)
         ok &= (uint32_t)(k + rep <= total);
         {
           // rep entries of length val starting at index k: split at the lit/len | distance border (val = 0 adds nothing)
@@ -625,7 +626,7 @@ __global__ __launch_bounds__(64) void k_inf_verify_long(const uint8_t* __restric
       const uint32_t ndd = rep - nl;
       const uint32_t kl = c_kl + wave_scan_add(nl * c), kd = c_kd + wave_scan_add(ndd * c);
       const uint32_t dd = val ? ndd : 0u;
-      uint32_t ok = (uint32_t)(P + off + 14u <= limit);
+      uint32_t ok = (uint32_t)(P + off + ((t >> 12) & 15u) <= limit);  // the symbol's own bits lie inside the data
       ok &= (uint32_t)!(is16 & (uint32_t)(k == 0u));
       ok &= (verify_rule_break(psym, sy, xv, is16, is17, is18) & strict) ^ 1u;
       ok &= (uint32_t)(k + rep <= total) & (uint32_t)(kl <= 32768u) & (uint32_t)(kd <= 32768u);
@@ -2659,7 +2660,11 @@ __global__ __launch_bounds__(256) void k_inf_chain_range(const ZesInfBuf* __rest
   }
   const uint32_t nown = lo;
   if (nown == 0) {  // no block starts in this piece (possible for a piece in the middle of one block)
-    if (tid == 0) res[0].status = 0;
+    if (tid == 0) {
+      res[0].status = 0;
+      res[1].out_len = (uint64_t)bf.start_rel + 16u;  // first bit == end bit == the range's lo_bit, as the host says of a
+      res[1].aux = bf.start_rel + 16u;                // piece too short to hold a start (range_nothing)
+    }
     return;
   }
   unsigned long long part = 0;

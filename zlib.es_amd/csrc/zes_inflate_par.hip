@@ -2582,6 +2582,9 @@ __device__ __forceinline__ static void block_par_t1(ParSmem& S, const uint8_t* _
   const uint64_t c = bufs[bi].c;
   if (ranked) w = w_rank;
   const uint32_t ci = map ? map[w] : w;
+  // a piece of a longer stream: a candidate at or behind own_rel is the next piece's block — here it only marks where the
+  // last own block has to end, so it is not decoded and the output behind the own blocks stays as it was
+  if ((bufs[bi].range_flags & ZES_OWN_ONLY) && (ranked ? raw_mine : cand[ci]) >= bufs[bi].own_rel) return;
   ParItem it;
   it.g32 = reinterpret_cast<const uint32_t*>(d_in + bufs[bi].in_off);
   it.lastdw = (uint32_t)((c - 1) >> 2);

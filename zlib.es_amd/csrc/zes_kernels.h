@@ -68,10 +68,11 @@ struct ZesInfBuf {
   // or behind it; candidates at or behind own_rel only serve as end estimates and are left to the next piece
   uint32_t start_rel;
   uint32_t own_rel;      // 0xFFFFFFFF: the whole buffer
-  uint32_t range_flags;  // ZES_START_ANY
+  uint32_t range_flags;  // ZES_START_ANY, ZES_OWN_ONLY
   uint32_t pad;
 };
 #define ZES_START_ANY 1u
+#define ZES_OWN_ONLY 2u  // range form: candidates at or behind own_rel are not decoded (nothing is written for them)
 
 // work_first of the table's sentinel entry in one-buffer calls: the decode kernels take the number of work
 // items from the candidate counter on the device (the sentinel's cand_cap holds the launch bound)

@@ -328,7 +328,10 @@ def join_host(pieces, bits: Sequence[int], adlers: Sequence[int], lens: Sequence
         p = np.asarray(p, dtype=np.uint8)
         nb = (nbits + 7) // 8
         sh, byte0 = pos & 7, pos >> 3
-        w = p[:nb].astype(np.uint16) << sh  # the piece's bit k lands on bit pos + k: shift-merge at the seam
+        w = p[:nb].astype(np.uint16)
+        if nbits & 7:
+            w[-1] &= (1 << (nbits & 7)) - 1  # bits of the last byte beyond nbits are not part of the stream (as k_bits_place masks them)
+        w <<= sh  # the piece's bit k lands on bit pos + k: shift-merge at the seam
         body[byte0: byte0 + nb] |= (w & 0xFF).astype(np.uint8)
         hi8 = (w >> 8).astype(np.uint8)
         m = min(nb, len(body) - (byte0 + 1))
