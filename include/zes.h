@@ -50,7 +50,9 @@ typedef enum zes_status {
 #define ZES_F_DEFAULT 0u
 #define ZES_F_NO_FASTPATH 1u   /* force the general (serial, any-stream) decoder: testing aid */
 #define ZES_F_PIECES 4u        /* decode a reference-made stream piece by piece (1 MiB pieces) as streams of 512 MiB and more are
-                                  * (256 MiB pieces): testing aid for that path; same results */
+                                  * (256 MiB pieces): testing aid for that path; same results.  zes_bgzip*: encode the members in
+                                  * groups of 4 instead of 1024, as inputs of more than 1024 chunks are encoded group by group:
+                                  * testing aid for the seams between groups; same bytes */
 #define ZES_F_ALLOC_BOUND 8u   /* zes_inflate_alloc: the allocator may be asked EARLY for an upper estimate of the result's size (the
                                  result is then a prefix of what it returned: *out_len says how long), and a second time for the exact
                                  size if the estimate fell short — the last pointer it returned holds the result.  For callers whose
@@ -186,6 +188,39 @@ int zes_crc32_batch_dev(const uint8_t* d_in, const uint64_t* off, const uint64_t
 int zes_gzip_bound(uint64_t n, uint64_t* cap);
 int zes_gzip(const uint8_t* in, uint64_t n, uint8_t* out, uint64_t cap, uint64_t* out_len);
 int zes_gzip_dev(const uint8_t* d_in, uint64_t n, uint8_t* d_out, uint64_t cap, uint64_t* out_len);
+
+/* BGZF compress (the blocked gzip of bgzip / htslib): valid gzip whose members state their own size, so that htslib can
+ * index the file and zes_gunzip* decodes it as one batch.  The format is fixed, so the output is deterministic:
+ *   chunks   the input is cut into chunks of ZES_BGZF_CHUNK = 65280 bytes (htslib's BGZF_BLOCK_SIZE), the last one may be
+ *            shorter; each chunk becomes one member, member k holding input bytes [k * 65280, ...)
+ *   header   18 bytes, exactly 1f 8b 08 04 00 00 00 00 00 ff 06 00 42 43 02 00 | BSIZE (LE16), BSIZE = member size - 1
+ *   body     exactly the bytes of zes_deflate_raw of that chunk alone (an independent buffer: no match reaches into the
+ *            next chunk) — unless that stream is longer than len + 5 bytes or the chunk is 1 byte long (the reference's
+ *            encoder throws on it): then one stored block, 01 | LEN | NLEN | the chunk's bytes (BFINAL 1, BTYPE 00), len + 5
+ *            bytes.  A stream of exactly len + 5 bytes is kept.  So a member has at most 65311 bytes and BSIZE fits its
+ *            16 bits (the reference's encoder has no stored blocks: its output on incompressible data has no usable bound)
+ *   trailer  the CRC-32 of the chunk, then ISIZE = len, both little-endian
+ *   marker   behind the last member the 28-byte end-of-file marker
+ *            1f 8b 08 04 00 00 00 00 00 ff 06 00 42 43 02 00 1b 00 03 00 00 00 00 00 00 00 00 00
+ * Every n is valid; n == 0 gives the marker alone.
+ * zes_bgzip_members: ceil(n / 65280) + 1 (the marker); zes_bgzip_bound: full chunks * 65311 + (tail ? tail + 31 : 0) + 28, a
+ * capacity that always suffices and is exact for incompressible input.  Neither touches a device.
+ * member_off: NULL, or a host array with room for zes_bgzip_members(n) entries that receives the byte position of every
+ * member in the output, the marker's last — what BGZF virtual offsets and a .gzi index are made of.
+ * The device form takes d_in and d_out at ANY alignment and writes exactly *out_len bytes and no byte behind them (the other
+ * device forms write whole 16-byte groups); the caller's input is read only inside the aligned 16-byte groups that hold
+ * its bytes.  The host form stages through the library's buffers as zes_gzip does.
+ *   ZES_E_NOSPACE  cap is too small: *out_len = the size needed; bytes at and behind d_out + cap are untouched, what lies
+ *                  below cap is unspecified
+ *   ZES_E_ARG      a null pointer with n != 0, a null out_len, flag bits other than ZES_F_PIECES
+ * Members are encoded in groups (1024; ZES_F_PIECES: 4 — same bytes) so that the pooled scratch stays bounded whatever n
+ * is: what zes_deflate_dev pools for 128 MiB.
+ * replaces: nothing (the reference has no gzip container); the bodies are `deflate` of src/deflate.ts:14-39 per chunk. */
+#define ZES_BGZF_CHUNK 65280u
+int zes_bgzip_members(uint64_t n, uint64_t* members);
+int zes_bgzip_bound(uint64_t n, uint64_t* cap);
+int zes_bgzip(const uint8_t* in, uint64_t n, uint8_t* out, uint64_t cap, uint64_t* out_len, uint64_t* member_off, uint32_t flags);
+int zes_bgzip_dev(const uint8_t* d_in, uint64_t n, uint8_t* d_out, uint64_t cap, uint64_t* out_len, uint64_t* member_off, uint32_t flags);
 
 /* gzip (RFC 1952) decompress, as CPython 3.10's gzip.decompress: any number of members back to back, their outputs
  * concatenated; zero bytes between and after members are skipped.  Header: 1f 8b, CM 8; FEXTRA, FNAME and FCOMMENT are

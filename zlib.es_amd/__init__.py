@@ -114,6 +114,10 @@ def lib():
             getattr(L, name).argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, u64p]
         for name in ("zes_gunzip", "zes_gunzip_dev"):
             getattr(L, name).argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, u64p, C.c_uint32]
+        for name in ("zes_bgzip_members", "zes_bgzip_bound"):
+            getattr(L, name).argtypes = [C.c_uint64, u64p]
+        for name in ("zes_bgzip", "zes_bgzip_dev"):
+            getattr(L, name).argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, u64p, u64p, C.c_uint32]
         L.zes_gunzip_alloc.argtypes = [C.c_void_p, C.c_uint64, ALLOC_FN, C.c_void_p, u64p, C.c_uint32]
         L.zes_adler32.argtypes = [C.c_void_p, C.c_uint64, u32p]
         L.zes_adler32_dev.argtypes = [C.c_void_p, C.c_uint64, u32p]
@@ -376,6 +380,39 @@ def gzip(data):
     return out[: n.value].copy()
 
 
+def bgzip_members(n):
+    """Members of bgzip() of n bytes: one per 65280-byte chunk and the end-of-file marker (zes_bgzip_members; no GPU needed)."""
+    m = C.c_uint64()
+    rc = lib().zes_bgzip_members(n, C.byref(m))
+    if rc:
+        _raise(rc)
+    return m.value
+
+
+def bgzip_bound(n):
+    """A capacity that always suffices for bgzip() of n bytes, exact for incompressible input (zes_bgzip_bound; no GPU needed)."""
+    cap = C.c_uint64()
+    rc = lib().zes_bgzip_bound(n, C.byref(cap))
+    if rc:
+        _raise(rc)
+    return cap.value
+
+
+def bgzip(data, flags=0, index=False):
+    """A BGZF file (bgzip / htslib): a gzip member per 65280-byte chunk and the end-of-file marker (zes_bgzip).
+    index=True: ``(bytes, offsets)``, ``offsets[k]`` the position of member k in the result, the marker's last."""
+    a = _as_u8(data)
+    cap = bgzip_bound(a.size)
+    out = np.empty(cap, dtype=np.uint8)
+    off = (C.c_uint64 * bgzip_members(a.size))()
+    n = C.c_uint64()
+    rc = lib().zes_bgzip(a.ctypes.data, a.size, out.ctypes.data, cap, C.byref(n), off, flags)
+    if rc:
+        _raise(rc)
+    res = out[: n.value].copy()
+    return (res, list(off)) if index else res
+
+
 def gunzip(data, flags=0):
     """gzip.decompress: every member, their outputs concatenated (zes_gunzip_alloc: one decode, an exact-size result)."""
     a = _as_u8(data)
@@ -504,6 +541,28 @@ def gzip_tensor(t, out=None):
     if rc:
         _raise(rc)
     return out[: n.value]
+
+
+def bgzip_tensor(t, out=None, flags=0, index=False):
+    """BGZF file of a 1-D uint8 CUDA tensor (zes_bgzip_dev); returns a view of ``out`` (allocated if None), or with
+    index=True ``(view, offsets)``.  ``t`` and ``out`` may start at any byte; only the result's bytes are written."""
+    import torch
+
+    assert t.is_cuda and t.dtype == torch.uint8 and t.is_contiguous()
+    if out is None:
+        out = torch.empty(bgzip_bound(t.numel()), dtype=torch.uint8, device=t.device)
+    assert out.is_cuda and out.dtype == torch.uint8 and out.is_contiguous()
+    torch.cuda.current_stream(t.device).synchronize()
+    off = (C.c_uint64 * bgzip_members(t.numel()))()
+    n = C.c_uint64()
+    rc = lib().zes_bgzip_dev(t.data_ptr() if t.numel() else None, t.numel(), out.data_ptr(), out.numel(), C.byref(n), off, flags)
+    if rc == ZES_E_NOSPACE:
+        err = ZlibEsError(rc, "%s (need %d bytes)" % (strerror(rc), n.value))
+        err.need = n.value
+        raise err
+    if rc:
+        _raise(rc)
+    return (out[: n.value], list(off)) if index else out[: n.value]
 
 
 def gunzip_tensor(t, out, flags=0):

@@ -155,7 +155,9 @@ static_assert(disjoint({PIN_SPAN(t2.search), PIN_SPAN(t2.ncand), PIN_SPAN(t2.nsu
   /* CRC-32: the kernel's table (x^(8 * 65536 * m) for m < crc_npow) and its two accumulator words; gzip reader: the input  */    \
   /* (host forms), the result as it grows (host forms) and one member's output when it cannot go to its place directly */         \
   /* member-parallel gzip reader: the bodies behind their 78 9C, the outputs that cannot go to their places directly, the    */    \
-  /* device tables (members, segments); segmented CRC-32: its buffers, work items and accumulator words */                        \
+  /* device tables (members, segments); segmented CRC-32: its buffers, work items and accumulator words.  The BGZF writer   */    \
+  /* uses the same: gz_in and gz_acc for a host call's input and result, gz_bodies for a group's encoder slots, gz_tab for   */    \
+  /* its member records                                                                                                       */    \
   X(crctab) X(crcacc) X(gz_in) X(gz_acc) X(gz_stage) X(gz_bodies) X(gz_outs) X(gz_tab) X(crcseg)
 
 // The survivor list of the block-start search as the block-parallel tier's scan left it in a pool (one buffer): the
@@ -3872,6 +3874,140 @@ int zes_gzip(const uint8_t* in, uint64_t n, uint8_t* out, uint64_t cap, uint64_t
   put_le32(out + 10 + rl, crc);
   put_le32(out + 14 + rl, (uint32_t)n);
   return ZES_OK;
+}
+
+// ---- BGZF writer: the input in chunks of ZES_BGZF_CHUNK bytes, a gzip member each, and the end-of-file marker ----
+static const uint8_t kBgzfEof[28] = {0x1f, 0x8b, 8, 4, 0, 0, 0, 0, 0, 0xff, 6, 0, 'B', 'C', 2, 0, 0x1b, 0, 3, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+constexpr uint32_t BGZF_GROUP = 1024;       // members encoded at once: a block's scratch each, what zes_deflate_dev pools for 128 MiB
+constexpr uint32_t BGZF_GROUP_PIECES = 4;   // ... under ZES_F_PIECES
+constexpr uint64_t BGZF_MEMBER_MAX = ZES_BGZF_HLEN + 5 + ZES_BGZF_CHUNK + 8;  // a full chunk as a stored block: 65311
+constexpr uint64_t BGZF_N_MAX = 1ull << 62;  // (the bound of a longer input does not fit 64 bits)
+static_assert(BGZF_MEMBER_MAX <= 65536, "BSIZE has 16 bits");
+static_assert(BGZF_GROUP <= DEFLATE_TABLE_BUFS && BGZF_GROUP <= DEFLATE_DIRECT_BUFS, "a group's buffer table and results go through the page-locked area");
+static uint64_t bgzip_members(uint64_t n) { return (n + ZES_BGZF_CHUNK - 1) / ZES_BGZF_CHUNK + 1; }
+static uint64_t bgzip_bound(uint64_t n) {
+  const uint64_t tail = n % ZES_BGZF_CHUNK;
+  return n / ZES_BGZF_CHUNK * BGZF_MEMBER_MAX + (tail ? tail + ZES_BGZF_HLEN + 5 + 8 : 0) + sizeof kBgzfEof;
+}
+
+// The members of d_in[0, n) and the marker into d_out[0, cap), group by group: the group's chunks are checksummed by one
+// segmented CRC-32 launch and encoded as independent buffers into 16-byte aligned slots of g.gz_bodies (a chunk of one byte,
+// which the encoder refuses, is left out), their sizes come back, the host chooses stream or stored block per member and
+// k_bgzf_pack puts the members in their places.  The marker is the last launch's last record.  A result beyond cap:
+// every group is still encoded (the size needed is the answer), and from the first group that does not fit whole no
+// member is written.  member_off: null, or where every member starts, the marker's last.
+static int bgzip_core(const uint8_t* d_in, uint64_t n, uint8_t* d_out, uint64_t cap, uint64_t* out_len, uint64_t* member_off, uint32_t flags) {
+  int rc;
+  g.carry.clear();
+  const uint64_t nm = bgzip_members(n) - 1;  // (without the marker)
+  const uint64_t group = (flags & ZES_F_PIECES) ? BGZF_GROUP_PIECES : BGZF_GROUP;
+  const uint64_t slot = (deflate_bound(ZES_BGZF_CHUNK) + 15) & ~(uint64_t)15;
+  std::vector<ZesBgzfRec> recs((size_t)nm + 1);  // (of the whole call: uploads read it until the last synchronisation)
+  const size_t gmax = (size_t)std::min(group, nm);
+  std::vector<uint64_t> in_off(gmax), in_len(gmax), o_off(gmax), o_cap(gmax), o_len(gmax);
+  std::vector<int32_t> status(gmax);
+  std::vector<ZesCrcSeg> csegs(gmax);
+  std::vector<uint32_t> crc(gmax);
+  uint64_t total = 0;
+  bool fits = true;
+  for (uint64_t m0 = 0;; m0 += group) {
+    const uint32_t cnt = (uint32_t)std::min(group, nm - m0);
+    const bool last = m0 + cnt == nm;
+    if (cnt) {
+      for (uint32_t k = 0; k < cnt; k++) {
+        in_off[k] = (m0 + k) * ZES_BGZF_CHUNK;
+        in_len[k] = std::min<uint64_t>(ZES_BGZF_CHUNK, n - in_off[k]);
+        o_off[k] = k * slot;
+        o_cap[k] = slot;
+        csegs[k] = ZesCrcSeg{in_off[k], in_len[k]};
+      }
+      if ((rc = ensure(g.gz_bodies, (size_t)cnt * slot))) return rc;
+      if ((rc = crc32_batch_locked(d_in, csegs.data(), cnt, crc.data()))) return rc;
+      if ((rc = deflate_batch_core(d_in, in_off.data(), in_len.data(), (uint8_t*)g.gz_bodies.p, o_off.data(), o_cap.data(), o_len.data(), status.data(), cnt)))
+        return rc;
+      if (g.profiling) g.carry = g.last_times;  // (deflate_batch_core has collected what ran so far: the call's last collect_times keeps it)
+    }
+    for (uint32_t k = 0; k < cnt; k++) {
+      const uint32_t len = (uint32_t)in_len[k];
+      if (len > 1 && (status[k] != ZES_OK || o_len[k] < 6)) return status[k] ? status[k] : ZES_E_DEVICE;
+      const uint64_t raw = len > 1 ? o_len[k] - 6 : 0;  // without 78 9C and the Adler-32
+      const bool stored = len == 1 || raw > (uint64_t)len + 5;
+      ZesBgzfRec& r = recs[(size_t)(m0 + k)];
+      r.src_off = stored ? in_off[k] : o_off[k] + 2;
+      r.dst_off = total;
+      r.body_len = stored ? len + 5 : (uint32_t)raw;
+      r.len = len;
+      r.crc = crc[k];
+      r.kind = stored ? ZES_BGZF_STORED : ZES_BGZF_STREAM;
+      total += ZES_BGZF_HLEN + r.body_len + 8;
+    }
+    if (last) {
+      recs[(size_t)nm] = ZesBgzfRec{0, total, 2, 0, 0, ZES_BGZF_EOF};
+      total += sizeof kBgzfEof;
+    }
+    const uint32_t nrec = cnt + (last ? 1u : 0u);
+    fits = fits && total <= cap && d_out != nullptr;
+    if (fits) {
+      if ((rc = ensure(g.gz_tab, sizeof(ZesBgzfRec) * (size_t)nrec))) return rc;
+      HIPCHK(hipMemcpyAsync(g.gz_tab.p, &recs[(size_t)m0], sizeof(ZesBgzfRec) * (size_t)nrec, hipMemcpyHostToDevice, g.stream));
+      Timed t("k_bgzf_pack");
+      hipLaunchKernelGGL(k_bgzf_pack, dim3(nrec), dim3(GZ_GATHER_THREADS), 0, g.stream, d_in, (const uint8_t*)g.gz_bodies.p, d_out,
+                         (const ZesBgzfRec*)g.gz_tab.p);
+    }
+    HIPCHK(hipGetLastError());
+    if (last) break;
+  }
+  HIPCHK(hipStreamSynchronize(g.stream));
+  if (member_off)
+    for (uint64_t k = 0; k <= nm; k++) member_off[k] = recs[(size_t)k].dst_off;
+  *out_len = total;
+  return fits ? ZES_OK : ZES_E_NOSPACE;
+}
+
+int zes_bgzip_members(uint64_t n, uint64_t* members) {
+  if (!members) return ZES_E_ARG;
+  *members = bgzip_members(n);
+  return ZES_OK;
+}
+
+int zes_bgzip_bound(uint64_t n, uint64_t* cap) {
+  if (!cap || n > BGZF_N_MAX) return ZES_E_ARG;
+  *cap = bgzip_bound(n);
+  return ZES_OK;
+}
+
+int zes_bgzip_dev(const uint8_t* d_in, uint64_t n, uint8_t* d_out, uint64_t cap, uint64_t* out_len, uint64_t* member_off, uint32_t flags) {
+  ROUTE_DEV(d_out, d_in);
+  if (!out_len || (n && (!d_in || !d_out)) || (!d_out && cap) || (flags & ~ZES_F_PIECES) || n > BGZF_N_MAX) return ZES_E_ARG;
+  *out_len = 0;
+  LOCK_READY();
+  rc = bgzip_core(d_in, n, d_out, cap, out_len, member_off, flags);
+  collect_times();
+  return rc;
+}
+
+int zes_bgzip(const uint8_t* in, uint64_t n, uint8_t* out, uint64_t cap, uint64_t* out_len, uint64_t* member_off, uint32_t flags) {
+  UseDev ud(route_host());
+  if (!out_len || (n && (!in || !out)) || (!out && cap) || (flags & ~ZES_F_PIECES) || n > BGZF_N_MAX) return ZES_E_ARG;
+  *out_len = 0;
+  if (n == 0) {  // the marker alone: nothing to compute
+    *out_len = sizeof kBgzfEof;
+    if (member_off) member_off[0] = 0;
+    if (cap < sizeof kBgzfEof) return ZES_E_NOSPACE;
+    memcpy(out, kBgzfEof, sizeof kBgzfEof);
+    return ZES_OK;
+  }
+  LOCK_READY();
+  if ((rc = stage_in(g.gz_in, in, n))) return rc;
+  const uint64_t bound = bgzip_bound(n);
+  if ((rc = ensure(g.gz_acc, bound + 64))) return rc;
+  uint64_t total = 0;
+  rc = bgzip_core((const uint8_t*)g.gz_in.p, n, (uint8_t*)g.gz_acc.p, bound, &total, member_off, flags);
+  collect_times();
+  if (rc) return rc;
+  *out_len = total;
+  if (total > cap) return ZES_E_NOSPACE;
+  return download(out, (const uint8_t*)g.gz_acc.p, total);
 }
 
 // ---- gzip reader (RFC 1952; CPython's gzip.decompress) ----

@@ -1,4 +1,5 @@
-// zes_gzip.hip — device pieces of the member-parallel gzip reader (zes_api.hip: gunzip_parallel).
+// zes_gzip.hip — device pieces of the member-parallel gzip reader (zes_api.hip: gunzip_parallel) and of the BGZF writer
+// (zes_api.hip: bgzip_core).
 //
 // A file whose members all state their own size — BGZF, the format of bgzip / htslib: every member's extra field holds a
 // subfield 'B','C' with BSIZE = member size - 1 — can be cut into its members without decoding anything.
@@ -13,6 +14,11 @@
 //                written as 16-byte stores; a group's bytes come from the two aligned 16-byte groups of the source that hold
 //                them (one, when both sides are aligned alike), shifted into place.  Only groups that hold bytes of the
 //                segment are read, and only the segment's bytes are written; the under-16-byte head and tail go bytewise.
+//                (The copy itself is gz_copy, which k_bgzf_pack calls too.)
+//   k_bgzf_pack  a workgroup per member of a BGZF file being written (a member is at most 64 KiB): the 18 header bytes, the
+//                body at whatever alignment its place has — the encoder's stream out of its scratch slot, or a stored block:
+//                five bytes and the chunk out of the caller's input — and the 8 trailer bytes.  Only the member's own bytes
+//                are written, and the input is read only inside the aligned 16-byte groups that hold the chunk's bytes.
 #include "zes_common.h"
 #include "zes_kernels.h"
 
@@ -67,28 +73,25 @@ __global__ __launch_bounds__(64) void k_gz_walk(const uint8_t* __restrict__ d_in
   }
 }
 
-__global__ __launch_bounds__(GZ_GATHER_THREADS) void k_gz_gather(const uint8_t* __restrict__ src, uint8_t* __restrict__ dst,
-                                                                const ZesGzSeg* __restrict__ segs) {
-  const ZesGzSeg sg = segs[blockIdx.x];
-  const uint32_t tid = threadIdx.x;
-  const uint8_t* s = src + sg.src_off;
-  uint8_t* d = dst + sg.dst_off;
-  if (sg.zhdr && blockIdx.y == 0 && tid < 2) d[(int)tid - 2] = tid ? 0x9C : 0x78;
+// Bytes [0, len) of s to d, any alignment on both sides, by the GZ_GATHER_THREADS threads of a workgroup that is share y of
+// the ny that copy this range: share 0 writes the bytes in front of d's first 16-byte boundary and behind its last one,
+// the whole 16-byte groups between go in pieces of GZ_GATHER_PIECE bytes, piece y, y + ny, ... to share y.
+__device__ __forceinline__ void gz_copy(const uint8_t* __restrict__ s, uint8_t* __restrict__ d, uint64_t len, uint32_t tid, uint32_t y, uint32_t ny) {
   // [0, head): in front of the destination's first 16-byte boundary; [head, head + 16 * groups): whole groups; the rest: tail
-  const uint64_t head = min(sg.len, (uint64_t)((0 - (uintptr_t)d) & 15u));
-  const uint64_t groups = (sg.len - head) / 16;
-  if (blockIdx.y == 0) {
+  const uint64_t head = min(len, (uint64_t)((0 - (uintptr_t)d) & 15u));
+  const uint64_t groups = (len - head) / 16;
+  if (y == 0) {
     if (tid < head) d[tid] = s[tid];
     const uint64_t t0 = head + groups * 16;
-    if (t0 + tid < sg.len) d[t0 + tid] = s[t0 + tid];
+    if (t0 + tid < len) d[t0 + tid] = s[t0 + tid];
   }
   const uint8_t* sa = s + head;                     // the source of group 0
-  const uint32_t sh = (uint32_t)((uintptr_t)sa & 15u);  // (the same for every group of the segment)
+  const uint32_t sh = (uint32_t)((uintptr_t)sa & 15u);  // (the same for every group of the range)
   const uint4* s16 = reinterpret_cast<const uint4*>(sa - sh);
   uint4* d16 = reinterpret_cast<uint4*>(d + head);
   const uint32_t qd = sh >> 2, rb = 8 * (sh & 3u);
   constexpr uint64_t PIECE_GROUPS = GZ_GATHER_PIECE / 16;
-  for (uint64_t g0 = (uint64_t)blockIdx.y * PIECE_GROUPS; g0 < groups; g0 += (uint64_t)gridDim.y * PIECE_GROUPS) {
+  for (uint64_t g0 = (uint64_t)y * PIECE_GROUPS; g0 < groups; g0 += (uint64_t)ny * PIECE_GROUPS) {
     const uint64_t g1 = min(groups, g0 + PIECE_GROUPS);
 #pragma unroll 4
     for (uint64_t gi = g0 + tid; gi < g1; gi += GZ_GATHER_THREADS) {
@@ -109,5 +112,42 @@ __global__ __launch_bounds__(GZ_GATHER_THREADS) void k_gz_gather(const uint8_t* 
       o.w = (uint32_t)((((uint64_t)e[4] << 32) | e[3]) >> rb);
       d16[gi] = o;
     }
+  }
+}
+
+__global__ __launch_bounds__(GZ_GATHER_THREADS) void k_gz_gather(const uint8_t* __restrict__ src, uint8_t* __restrict__ dst,
+                                                                const ZesGzSeg* __restrict__ segs) {
+  const ZesGzSeg sg = segs[blockIdx.x];
+  const uint32_t tid = threadIdx.x;
+  uint8_t* d = dst + sg.dst_off;
+  if (sg.zhdr && blockIdx.y == 0 && tid < 2) d[(int)tid - 2] = tid ? 0x9C : 0x78;
+  gz_copy(src + sg.src_off, d, sg.len, tid, blockIdx.y, gridDim.y);
+}
+
+// a member's header in front of BSIZE: FLG 4 (FEXTRA), MTIME 0, XFL 0, OS 255, XLEN 6, subfield 'B','C' of SLEN 2
+__device__ __constant__ static const uint8_t kBgzfHead[16] = {0x1f, 0x8b, 8, 4, 0, 0, 0, 0, 0, 0xff, 6, 0, 'B', 'C', 2, 0};
+
+__global__ __launch_bounds__(GZ_GATHER_THREADS) void k_bgzf_pack(const uint8_t* __restrict__ in, const uint8_t* __restrict__ slots,
+                                                                uint8_t* __restrict__ out, const ZesBgzfRec* __restrict__ recs) {
+  const ZesBgzfRec r = recs[blockIdx.x];
+  const uint32_t tid = threadIdx.x;
+  uint8_t* m = out + r.dst_off;
+  const uint32_t bsize = ZES_BGZF_HLEN + r.body_len + 8 - 1;
+  if (tid < ZES_BGZF_HLEN) m[tid] = tid < 16 ? kBgzfHead[tid] : (uint8_t)(bsize >> (8 * (tid - 16)));
+  if (tid >= 32 && tid < 40) {
+    const uint32_t k = tid - 32;
+    m[ZES_BGZF_HLEN + r.body_len + k] = (uint8_t)((k < 4 ? r.crc : r.len) >> (8 * (k & 3u)));
+  }
+  uint8_t* body = m + ZES_BGZF_HLEN;
+  if (r.kind == ZES_BGZF_STREAM) {
+    gz_copy(slots + r.src_off, body, r.body_len, tid, 0, 1);
+  } else if (r.kind == ZES_BGZF_STORED) {  // 01 | LEN | NLEN | the chunk
+    if (tid >= 64 && tid < 69) {
+      const uint32_t k = tid - 64, v = r.len | (~r.len << 16);
+      body[k] = k ? (uint8_t)(v >> (8 * (k - 1))) : 1;
+    }
+    gz_copy(in + r.src_off, body + 5, r.len, tid, 0, 1);
+  } else if (tid < 2) {  // the end-of-file marker's body: an empty fixed-Huffman block
+    body[tid] = tid ? 0 : 3;
   }
 }

@@ -159,6 +159,19 @@ struct ZesGzSeg {
 };
 #define GZ_GATHER_THREADS 256u
 #define GZ_GATHER_PIECE 65536u  // a workgroup's share of a segment
+// k_bgzf_pack: one member of a BGZF file being written
+struct ZesBgzfRec {
+  uint64_t src_off;   // the body's source: ZES_BGZF_STREAM the raw stream's first byte in the slots, ZES_BGZF_STORED the chunk in the input
+  uint64_t dst_off;   // the member's first byte in the output
+  uint32_t body_len;  // bytes between header and trailer (the member is 18 + body_len + 8 bytes long)
+  uint32_t len;       // the chunk's bytes (ISIZE)
+  uint32_t crc;       // the chunk's CRC-32
+  uint32_t kind;      // ZES_BGZF_*
+};
+#define ZES_BGZF_STREAM 0u  // the body is the encoder's stream
+#define ZES_BGZF_STORED 1u  // the body is one stored block: 01 | LEN | NLEN | the chunk
+#define ZES_BGZF_EOF 2u     // the end-of-file marker: no chunk, the body is 03 00
+#define ZES_BGZF_HLEN 18u   // a member's header
 
 // CRC-32 host arithmetic (zes_crc.hip): shift(s, k) = s * x^(8k) mod P; the kernel's table with npow powers
 uint32_t zes_crc_shift(uint32_t s, uint64_t k);
@@ -233,9 +246,10 @@ __global__ void k_selftest_lds_order(unsigned long long*, uint32_t, uint32_t);
 __global__ void k_adler(const uint8_t*, uint64_t, uint64_t, unsigned long long*);
 __global__ void k_crc32(const uint8_t*, uint64_t, const uint32_t*, unsigned int*);
 __global__ void k_crc32_seg(const uint8_t*, const ZesCrcSeg*, const uint2*, const uint32_t*, unsigned int*);
-// gzip reader (zes_gzip.hip)
+// gzip reader and BGZF writer (zes_gzip.hip)
 __global__ void k_gz_walk(const uint8_t*, uint64_t, ZesGzWalk*, ZesGzMember*, uint32_t);
 __global__ void k_gz_gather(const uint8_t*, uint8_t*, const ZesGzSeg*);
+__global__ void k_bgzf_pack(const uint8_t*, const uint8_t*, uint8_t*, const ZesBgzfRec*);
 __global__ void k_adler_blocks(const uint8_t*, const ZesBuf*, const ZesBlk*, unsigned long long*);
 __global__ void k_layout(uint8_t*, const ZesBuf*, ZesBlk*, const unsigned long long*, ZesRes*);
 __global__ void k_emit(uint8_t*, const ZesBuf*, const ZesBlk*, const uint32_t*, const uint32_t*, const uint32_t*);

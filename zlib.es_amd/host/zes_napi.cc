@@ -562,6 +562,44 @@ napi_value Gzip(napi_env env, napi_callback_info info) {
   return take_u8(env, tmp, out_len);
 }
 
+// bgzip(input) / bgzipIndex(input): a BGZF file, a gzip member per 65280-byte chunk and the end-of-file marker
+// (include/zes.h: zes_bgzip); with_index: { data, offsets } with the position of every member, the marker's last
+napi_value bgzip_common(napi_env env, napi_callback_info info, bool with_index) {
+  size_t argc = 1;
+  napi_value argv[1];
+  napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr);
+  const uint8_t* in = nullptr;
+  size_t n = 0;
+  if (argc < 1 || !get_bytes(env, argv[0], &in, &n)) {
+    napi_throw_type_error(env, nullptr, with_index ? "bgzipIndex(input): input must be a Uint8Array" : "bgzip(input): input must be a Uint8Array");
+    return nullptr;
+  }
+  uint64_t cap = 0, out_len = 0, members = 0;
+  if (zes_bgzip_bound(n, &cap) || zes_bgzip_members(n, &members)) return throw_status(env, ZES_E_ARG);
+  std::vector<uint64_t> off(with_index ? (size_t)members : 0);
+  ResultMem tmp = result_alloc(cap);
+  if (!tmp.p) return throw_status(env, ZES_E_ARG);
+  const int rc = zes_bgzip(in, n, tmp.p, cap, &out_len, with_index ? off.data() : nullptr, ZES_F_DEFAULT);
+  if (rc) {
+    result_free(tmp);
+    return throw_status(env, rc);
+  }
+  napi_value data = take_u8(env, tmp, out_len);
+  if (!with_index || !data) return data;
+  napi_value res, arr;
+  if (napi_create_object(env, &res) != napi_ok || napi_create_array_with_length(env, off.size(), &arr) != napi_ok) return nullptr;
+  for (size_t i = 0; i < off.size(); i++) {
+    napi_value v;
+    if (napi_create_double(env, (double)off[i], &v) != napi_ok) return nullptr;  // (far below 2^53)
+    napi_set_element(env, arr, (uint32_t)i, v);
+  }
+  napi_set_named_property(env, res, "data", data);
+  napi_set_named_property(env, res, "offsets", arr);
+  return res;
+}
+napi_value Bgzip(napi_env env, napi_callback_info info) { return bgzip_common(env, info, false); }
+napi_value BgzipIndex(napi_env env, napi_callback_info info) { return bgzip_common(env, info, true); }
+
 // gunzip(input): every member of a gzip file, their outputs concatenated; one decode, then the exact-size result
 struct GunzipAlloc {
   ResultMem m;
@@ -976,6 +1014,8 @@ napi_value ModuleInit(napi_env env, napi_value exports) {
       {"adler32", nullptr, swept<Adler32>, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"gzip", nullptr, swept<Gzip>, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"gunzip", nullptr, swept<Gunzip>, nullptr, nullptr, nullptr, napi_default, nullptr},
+      {"bgzip", nullptr, swept<Bgzip>, nullptr, nullptr, nullptr, napi_default, nullptr},
+      {"bgzipIndex", nullptr, swept<BgzipIndex>, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"lastGunzipMembers", nullptr, swept<LastGunzipMembers>, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"init", nullptr, swept<Init>, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"initDevices", nullptr, swept<InitDevices>, nullptr, nullptr, nullptr, napi_default, nullptr},

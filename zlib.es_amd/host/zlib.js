@@ -92,6 +92,20 @@ function gunzip(input) {
 }
 
 /**
+ * Extra (not in the reference API): BGZF files, the blocked gzip of bgzip / htslib.  `bgzip` writes one gzip member per
+ * 65280-byte chunk of the input, each stating its own size, and the 28-byte end-of-file marker: a file htslib can index
+ * and gunzip() decodes as one batch.  Every input length is valid.  `bgzipIndex` also returns the byte position of every
+ * member in the result, the marker's last (member k holds input bytes from k * 65280): what virtual offsets are made of.
+ */
+function bgzip(input) {
+  return addon.bgzip(input);
+}
+
+function bgzipIndex(input) {
+  return addon.bgzipIndex(input);
+}
+
+/**
  * Extra: how many members the last gunzip() of this thread decoded as one batch (a BGZF file: all of them, the
  * end-of-file marker included); 0 when the members went one after the other.
  */
@@ -137,6 +151,8 @@ exports.inflateBatchAsync = inflateBatchAsync;
 exports.allocPinned = allocPinned;
 exports.gzip = gzip;
 exports.gunzip = gunzip;
+exports.bgzip = bgzip;
+exports.bgzipIndex = bgzipIndex;
 exports.lastGunzipMembers = lastGunzipMembers;
 exports.adler32 = adler32;
 exports.init = init;

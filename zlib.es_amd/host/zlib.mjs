@@ -17,6 +17,8 @@ export const adler32 = z.adler32;
 export const gzip = z.gzip;
 export const gunzip = z.gunzip;
 export const lastGunzipMembers = z.lastGunzipMembers;
+export const bgzip = z.bgzip;
+export const bgzipIndex = z.bgzipIndex;
 export const init = z.init;
 export const initDevices = z.initDevices;
 export const trim = z.trim;

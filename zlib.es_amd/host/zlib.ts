@@ -12,6 +12,7 @@
 const addon = require('./build/zes_napi.node');
 
 type BatchResult = Uint8Array | Error;
+type BgzipIndexed = { data: Uint8Array, offsets: number[] };
 
 export function inflate(input: Uint8Array): Uint8Array {
   return addon.inflate(input);
@@ -88,6 +89,20 @@ export function gzip(input: Uint8Array): Uint8Array {
 
 export function gunzip(input: Uint8Array): Uint8Array {
   return addon.gunzip(input);
+}
+
+/**
+ * Extra (not in the reference API): BGZF files, the blocked gzip of bgzip / htslib.  `bgzip` writes one gzip member per
+ * 65280-byte chunk of the input, each stating its own size, and the 28-byte end-of-file marker: a file htslib can index
+ * and gunzip() decodes as one batch.  Every input length is valid.  `bgzipIndex` also returns the byte position of every
+ * member in the result, the marker's last (member k holds input bytes from k * 65280): what virtual offsets are made of.
+ */
+export function bgzip(input: Uint8Array): Uint8Array {
+  return addon.bgzip(input);
+}
+
+export function bgzipIndex(input: Uint8Array): BgzipIndexed {
+  return addon.bgzipIndex(input);
 }
 
 /**
