@@ -66,6 +66,8 @@ typedef enum zes_status {
                                   trailer is ignored, as the reference ignores it (src/zlib.ts:11-23) */
 #define ZES_F_GZIP_SERIAL 32u   /* zes_gunzip*: decode the members one after the other even where they could go as one batch:
                                   testing aid, same results */
+#define ZES_F_INDEX_WALK 64u    /* zes_bgzf_index_dev: find the members with k_gz_walk's serial chain instead of the
+                                  parallel finder: testing aid and the baseline of the measurement; same results */
 #define ZES_F_LOOSE_CANDIDATES 2u /* block-start search without the reference's run-length-coding rules: more false
                                   * candidates reach the block decoder (testing aid for that path; same results) */
 
@@ -253,6 +255,56 @@ int zes_gunzip(const uint8_t* in, uint64_t c, uint8_t* out, uint64_t cap, uint64
 int zes_gunzip_dev(const uint8_t* d_in, uint64_t c, uint8_t* d_out, uint64_t cap, uint64_t* out_len, uint32_t flags);
 int zes_gunzip_alloc(const uint8_t* in, uint64_t c, zes_alloc_fn alloc, void* user, uint64_t* out_len, uint32_t flags);
 
+/* BGZF random access: the member index of a BGZF file, and reads of any range of its uncompressed data that decode only
+ * the members holding that range (what htslib does with a .gzi index).
+ *
+ * zes_bgzf_index*: the file must be BGZF from its first byte to its last: members follow each other directly from byte 0
+ * to byte c, and every one qualifies under the rule of "Member-parallel reading" above (1f 8b 08, FLG exactly 04, a header
+ * of at most 256 bytes, an extra field that walks to its exact end and holds a 'B','C' subfield of SLEN 2, hlen + 8 <= size
+ * <= the bytes left).  One member is enough.  On ZES_OK *members is the member count (the end-of-file marker included when
+ * there is one) and members + 1 entries are written to each host array: coff[k] = member k's byte position, uoff[k] = the
+ * sum of the ISIZE fields in front of it, and the closing entry coff[members] = c, uoff[members] = the uncompressed size.
+ * Nothing is decoded: a wrong CRC-32 or a damaged body does not concern the index.
+ *   ZES_E_GZIP     c == 0, or not such a chain to its last byte: padding, a plain member, a BSIZE that lies, a header or
+ *                  trailer cut short, garbage behind the file
+ *   ZES_E_NOSPACE  cap < members + 1: *members is set, nothing is written to coff or uoff (coff == uoff == NULL with
+ *                  cap == 0 asks for the count)
+ *   ZES_E_ARG      a null members, a null in with c != 0, flag bits other than ZES_F_INDEX_WALK, only one of coff / uoff
+ *                  null, both null with cap != 0
+ * The host form walks the caller's memory on the host and touches no device (it works without one, and ignores
+ * ZES_F_INDEX_WALK).  The device form takes d_in at any alignment and reads only inside the aligned 16-byte groups that
+ * hold its bytes: k_bgzf_mark tests every byte position for a member's first four bytes and judges each hit by the rule
+ * above, and the host follows the chain from byte 0 through the list of those that qualify (at most c / 256 + 1024 of
+ * them; with more, or with ZES_F_INDEX_WALK, k_gz_walk's serial chain answers — the same result by the same rule).
+ *
+ * zes_bgzf_read*: bytes [pos, pos + n) of the uncompressed data, n = min(len, total - pos), total = uoff[members], through
+ * an index as zes_bgzf_index* writes it (coff, uoff: host arrays of members + 1 entries).  The members whose output
+ * overlaps the range are found by binary search in uoff (members inside the range whose ISIZE is 0 are skipped), and only
+ * their index entries are looked at: a call costs O(log members + touched).  Every touched member is decoded whole and
+ * checked as the member-parallel reader checks it; members the range does not touch are never looked at.
+ *   ZES_E_ARG       a null pointer, members == 0, pos > total, flag bits other than ZES_F_PIECES (passed on to the inflate
+ *                   tiers)
+ *   ZES_E_NOSPACE   n > cap: *out_len = n; decided from the index alone, nothing is decoded or written
+ *   ZES_OK with *out_len = 0 when len == 0 or pos == total: no device work
+ *   ZES_E_GZIP      a stale or foreign index: a touched member does not lie inside [0, c) with coff[k] < coff[k + 1], its
+ *                   header, read again from the file, does not qualify, its size is not coff[k + 1] - coff[k], or its
+ *                   ISIZE is not uoff[k + 1] - uoff[k]
+ *   an error inside a touched body: the status zes_inflate_raw returns on it (the first such member in file order decides)
+ *   ZES_E_CHECKSUM  a touched member's output is not ISIZE bytes long (one that would outgrow its slot included), its
+ *                   stream does not end in the last byte in front of the trailer, or its CRC-32 does not match
+ * The device form takes d_in and d_out at any alignment and writes exactly *out_len bytes and no byte in front of or behind
+ * them, as zes_bgzip_dev does; after an error the bytes below cap are unspecified.  The host form uploads only the file
+ * bytes [coff[first touched], coff[last touched + 1]) and downloads n bytes.  Scratch grows with the range (the touched
+ * bodies and the outputs that cannot be decoded in place), as it does with the file for zes_gunzip_dev.
+ * zes_last_gunzip_members() reports the members the call decoded.
+ * replaces: nothing (the reference has no gzip container). */
+int zes_bgzf_index(const uint8_t* in, uint64_t c, uint64_t* coff, uint64_t* uoff, uint64_t cap, uint64_t* members, uint32_t flags);
+int zes_bgzf_index_dev(const uint8_t* d_in, uint64_t c, uint64_t* coff, uint64_t* uoff, uint64_t cap, uint64_t* members, uint32_t flags);
+int zes_bgzf_read(const uint8_t* in, uint64_t c, const uint64_t* coff, const uint64_t* uoff, uint64_t members, uint64_t pos, uint64_t len,
+                  uint8_t* out, uint64_t cap, uint64_t* out_len, uint32_t flags);
+int zes_bgzf_read_dev(const uint8_t* d_in, uint64_t c, const uint64_t* coff, const uint64_t* uoff, uint64_t members, uint64_t pos, uint64_t len,
+                      uint8_t* d_out, uint64_t cap, uint64_t* out_len, uint32_t flags);
+
 /* Adler-32 of a buffer (standard value as an unsigned 32-bit).
  * replaces: `calcAdler32` src/adler32.ts:1-10 (byte extraction at src/zlib.ts:37-40). */
 int zes_adler32(const uint8_t* in, uint64_t n, uint32_t* adler);
@@ -373,7 +425,8 @@ int zes_last_kernel_times(zes_ktime* out, int cap);
  * (DESIGN.md §4); 0 if the call failed before decoding. */
 int zes_last_inflate_tier(void);
 /* Members the member-parallel path decoded in the calling thread's last zes_gunzip* call; 0 when the member-by-member
- * path answered. */
+ * path answered.  After a zes_bgzf_read* call: the members that call decoded (those with output in the range); 0 when it
+ * decoded nothing (an empty range) or returned an error. */
 int zes_last_gunzip_members(void);
 /* (After zes_init_devices: zes_last_inflate_tier / zes_last_gunzip_members / zes_last_kernel_times report on the context that served the calling
  * thread's last call; zes_set_profiling switches every context.) */

@@ -44,6 +44,7 @@ ZES_E_NOTRANGE = -19
 ZES_E_GZIP = -20  # zes_gunzip*: not a valid gzip member (header, or a trailer cut short), or no input at all
 ZES_E_CHECKSUM = -21  # a trailer does not match: gzip CRC-32 / ISIZE / FHCRC, zlib Adler-32 under ZES_F_CHECK_ADLER
 ZES_F_GZIP_SERIAL = 32  # zes_gunzip*: the members one after the other even where they could go as one batch (testing aid)
+ZES_F_INDEX_WALK = 64  # zes_bgzf_index_dev: the members by k_gz_walk's serial chain instead of the parallel finder (testing aid, baseline)
 ZES_F_CHECK_ADLER = 16  # zes_inflate*: the Adler-32 trailer behind the stream must be there and match
 
 GEN_KINDS = {"xorshift": 0, "lowent4k": 1, "itext": 2}
@@ -118,6 +119,11 @@ def lib():
             getattr(L, name).argtypes = [C.c_uint64, u64p]
         for name in ("zes_bgzip", "zes_bgzip_dev"):
             getattr(L, name).argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, u64p, u64p, C.c_uint32]
+        for name in ("zes_bgzf_index", "zes_bgzf_index_dev"):
+            getattr(L, name).argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, u64p, C.c_uint32]
+        for name in ("zes_bgzf_read", "zes_bgzf_read_dev"):
+            getattr(L, name).argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_void_p, C.c_uint64,
+                                         u64p, C.c_uint32]
         L.zes_gunzip_alloc.argtypes = [C.c_void_p, C.c_uint64, ALLOC_FN, C.c_void_p, u64p, C.c_uint32]
         L.zes_adler32.argtypes = [C.c_void_p, C.c_uint64, u32p]
         L.zes_adler32_dev.argtypes = [C.c_void_p, C.c_uint64, u32p]
@@ -413,6 +419,50 @@ def bgzip(data, flags=0, index=False):
     return (res, list(off)) if index else res
 
 
+def _bgzf_index_call(fn, ptr, c, flags):
+    """(coff, uoff) of a BGZF file through zes_bgzf_index / zes_bgzf_index_dev: the count first, then the arrays."""
+    m = C.c_uint64()
+    rc = fn(ptr, c, None, None, 0, C.byref(m), flags)
+    if rc != ZES_E_NOSPACE:
+        _raise(rc if rc else ZES_E_ARG)
+    coff = np.empty(m.value + 1, dtype=np.uint64)
+    uoff = np.empty(m.value + 1, dtype=np.uint64)
+    rc = fn(ptr, c, coff.ctypes.data, uoff.ctypes.data, coff.size, C.byref(m), flags)
+    if rc:
+        _raise(rc)
+    return coff, uoff
+
+
+def _bgzf_index_arrays(index):
+    coff = np.ascontiguousarray(index[0], dtype=np.uint64)
+    uoff = np.ascontiguousarray(index[1], dtype=np.uint64)
+    assert coff.ndim == 1 and coff.size == uoff.size and coff.size >= 1, "a BGZF index is (coff, uoff): two arrays of members + 1 entries"
+    return coff, uoff
+
+
+def bgzf_index(data):
+    """The member index of a BGZF file (zes_bgzf_index; no GPU needed): ``(coff, uoff)``, numpy uint64 arrays of
+    members + 1 entries — member k starts at byte ``coff[k]`` and its output at byte ``uoff[k]`` of the uncompressed data;
+    the closing entries are the file's length and the uncompressed size."""
+    a = _as_u8(data)
+    return _bgzf_index_call(lib().zes_bgzf_index, a.ctypes.data, a.size, 0)
+
+
+def bgzf_read(data, index, pos, length):
+    """Bytes ``[pos, pos + length)`` of the uncompressed data of a BGZF file, clipped at its end, through ``index`` =
+    ``bgzf_index(data)``: only the members that hold the range are uploaded and decoded (zes_bgzf_read)."""
+    a = _as_u8(data)
+    coff, uoff = _bgzf_index_arrays(index)
+    total = int(uoff[-1])
+    cap = max(min(int(length), max(total - int(pos), 0)), 0)
+    out = np.empty(max(cap, 1), dtype=np.uint8)
+    n = C.c_uint64()
+    rc = lib().zes_bgzf_read(a.ctypes.data, a.size, coff.ctypes.data, uoff.ctypes.data, coff.size - 1, pos, length, out.ctypes.data, cap, C.byref(n), 0)
+    if rc:
+        _raise(rc)
+    return out[: n.value]
+
+
 def gunzip(data, flags=0):
     """gzip.decompress: every member, their outputs concatenated (zes_gunzip_alloc: one decode, an exact-size result)."""
     a = _as_u8(data)
@@ -583,6 +633,37 @@ def gunzip_tensor(t, out, flags=0):
     return out[: n.value]
 
 
+def bgzf_index_tensor(t, flags=0):
+    """bgzf_index of a 1-D uint8 CUDA tensor (any alignment; zes_bgzf_index_dev): the members are found on the device by
+    the parallel finder, or with ZES_F_INDEX_WALK by the serial walk."""
+    import torch
+
+    assert t.is_cuda and t.dtype == torch.uint8 and t.is_contiguous()
+    torch.cuda.current_stream(t.device).synchronize()
+    return _bgzf_index_call(lib().zes_bgzf_index_dev, t.data_ptr() if t.numel() else None, t.numel(), flags)
+
+
+def bgzf_read_tensor(t, index, pos, length, out, flags=0):
+    """bgzf_read of a 1-D uint8 CUDA tensor into ``out`` (zes_bgzf_read_dev); returns the filled view.  ``t`` and ``out`` may
+    start at any byte; only the result's bytes are written."""
+    import torch
+
+    assert t.is_cuda and t.dtype == torch.uint8 and t.is_contiguous()
+    assert out.is_cuda and out.dtype == torch.uint8 and out.is_contiguous()
+    coff, uoff = _bgzf_index_arrays(index)
+    torch.cuda.current_stream(t.device).synchronize()
+    n = C.c_uint64()
+    rc = lib().zes_bgzf_read_dev(t.data_ptr(), t.numel(), coff.ctypes.data, uoff.ctypes.data, coff.size - 1, pos, length, out.data_ptr(), out.numel(),
+                                 C.byref(n), flags)
+    if rc == ZES_E_NOSPACE:
+        err = ZlibEsError(rc, "%s (need %d bytes)" % (strerror(rc), n.value))
+        err.need = n.value
+        raise err
+    if rc:
+        _raise(rc)
+    return out[: n.value]
+
+
 def _batch_call(fn, d_in, in_off, in_len, d_out, out_off, out_cap, *extra):
     import torch
 
@@ -674,7 +755,8 @@ def last_inflate_tier():
 
 
 def last_gunzip_members():
-    """Members the member-parallel path decoded in this thread's last gunzip call (0: the member-by-member path answered)."""
+    """Members the member-parallel path decoded in this thread's last gunzip call (0: the member-by-member path answered),
+    or the members the last bgzf_read decoded."""
     return int(lib().zes_last_gunzip_members())
 
 

@@ -4223,9 +4223,103 @@ static int gz_gather(const uint8_t* src, uint8_t* dst, const std::vector<ZesGzSe
   return ZES_OK;
 }
 
-// All members as one batch: one gather of the bodies behind a 78 9C each, one inflate_jobs call, one gather of the outputs
-// that could not be decoded in place, one segmented CRC-32 launch.  *done only when every member checks out; in every
-// other case nothing has been decided (the result's memory may have been written to) and the serial path runs.
+// One member of a batch of gz_decode_batch: where it lies in the source, what its header and trailer say, and the part of its
+// output that is wanted: bytes [skip, skip + take) of it go to dst + dst_off (a whole member: skip 0, take = its ISIZE)
+struct GzPart {
+  uint64_t pos;
+  ZesGzMember m;
+  uint64_t dst_off;
+  uint32_t skip, take;
+};
+
+// Members as one batch (gunzip_parallel: a whole file; bgzf_read_core: the members a range touches): one gather of the
+// bodies behind a 78 9C each, one inflate_jobs call, one gather of the outputs that could not be decoded in place, one
+// segmented CRC-32 launch.  Every member is decoded whole and must check out: *verdict is ZES_OK when all do, else what
+// the first member in file order that does not is guilty of — its body's inflate status, or ZES_E_CHECKSUM: an output
+// that is not ISIZE bytes long (one that would outgrow its slot included), a stream that does not end in the last byte in
+// front of the trailer, a CRC-32 mismatch — or the status of a scratch buffer that could not grow.  With a verdict the
+// result's memory may have been written to.
+// A member is decoded in place when the 16-byte groups the decoders write stay inside its own part of dst; the others get a
+// slot of their own (the members run side by side: a group that reaches into a neighbour's range would race with it).
+// exact: no byte of dst outside the parts is written; else the last member with output may be decoded in place up to the
+// next 16-byte boundary below dst_cap.  stamps: the time in front of and behind inflate_jobs.
+static int gz_decode_batch(const uint8_t* d_src, const std::vector<GzPart>& ps, uint8_t* dst, uint64_t dst_cap, bool exact, uint32_t flags, int* verdict,
+                           std::chrono::steady_clock::time_point* stamps) {
+  *verdict = ZES_OK;
+  int rc;
+  const uint32_t n = (uint32_t)ps.size();
+  int64_t last_out = -1;  // the last member with output
+  if (!exact)
+    for (uint32_t k = 0; k < n; k++)
+      if (ps[k].m.isize) last_out = k;
+  auto up16 = [](uint64_t v) { return (v + 15) & ~15ull; };
+  auto whole = [&](uint32_t k) { return ps[k].skip == 0 && ps[k].take == ps[k].m.isize; };
+  std::vector<char> direct(n);
+  std::vector<uint64_t> islot(n), oslot(n);
+  std::vector<ZesGzSeg> segs(n);
+  uint64_t ipos = 0, opos = 0;
+  for (uint32_t k = 0; k < n; k++) {
+    const uint64_t dlen = ps[k].m.size - ps[k].m.hlen - 8, m = ps[k].m.isize;
+    islot[k] = ipos;
+    ipos += up16(2 + dlen) + 64;
+    segs[k] = ZesGzSeg{ps[k].pos + ps[k].m.hlen, islot[k] + 2, dlen, 1u, 0u};
+    direct[k] = dst && m && whole(k) && ((uintptr_t)(dst + ps[k].dst_off) & 15u) == 0 &&
+                ((m & 15u) == 0 || ((int64_t)k == last_out && up16(ps[k].dst_off + m) <= dst_cap));
+    if (!direct[k]) {
+      oslot[k] = opos;
+      opos += std::max<uint64_t>(up16(m), 16) + 16;
+    }
+  }
+  if ((rc = ensure(g.gz_bodies, ipos + 64)) || (rc = ensure(g.gz_outs, opos + 64))) {
+    *verdict = rc;
+    return ZES_OK;
+  }
+  if ((rc = gz_gather(d_src, (uint8_t*)g.gz_bodies.p, segs))) return rc;
+  // one base for both kinds of destination (inflate_jobs takes one pointer and an offset per job): the lower of the two
+  uint8_t* outs = (uint8_t*)g.gz_outs.p;
+  uint8_t* base = dst && dst < outs ? dst : outs;
+  std::vector<InfJob> jobs(n);
+  for (uint32_t k = 0; k < n; k++) {
+    const uint64_t dlen = ps[k].m.size - ps[k].m.hlen - 8, m = ps[k].m.isize;
+    uint8_t* to = direct[k] ? dst + ps[k].dst_off : outs + oslot[k];
+    jobs[k] = InfJob{islot[k], 2 + dlen, (uint64_t)(to - base), direct[k] ? m : std::max<uint64_t>(up16(m), 16), 0, ZES_OK, 0};
+    jobs[k].want_end = true;
+  }
+  const std::vector<uint8_t> firsts(n, 0x78);
+  if (stamps) stamps[0] = std::chrono::steady_clock::now();
+  if ((rc = inflate_jobs((const uint8_t*)g.gz_bodies.p, base, jobs, firsts.data(), flags & ~(ZES_F_CHECK_ADLER | ZES_F_GZIP_SERIAL)))) return rc;
+  if (g.profiling) g.carry = g.last_times;  // (inflate_jobs has collected what ran so far: the call's last collect_times keeps it)
+  if (stamps) stamps[1] = std::chrono::steady_clock::now();
+  for (uint32_t k = 0; k < n; k++) {
+    const uint64_t dlen = ps[k].m.size - ps[k].m.hlen - 8;
+    if (jobs[k].status != ZES_OK && jobs[k].status != ZES_E_NOSPACE)
+      *verdict = jobs[k].status;
+    else if (jobs[k].status != ZES_OK || jobs[k].out_len != ps[k].m.isize || jobs[k].end_bit < 16 || (jobs[k].end_bit - 16 + 7) / 8 != dlen)
+      *verdict = ZES_E_CHECKSUM;
+    if (*verdict) return ZES_OK;
+  }
+  // a whole member's output is checked where it ends up, a trimmed one's in its slot
+  segs.clear();
+  std::vector<ZesCrcSeg> csegs(n);
+  const uint8_t* cbase = base;
+  for (uint32_t k = 0; k < n; k++) {
+    if (!direct[k] && ps[k].take) segs.push_back(ZesGzSeg{oslot[k] + ps[k].skip, ps[k].dst_off, ps[k].take, 0u, 0u});
+    const uint8_t* at = whole(k) ? dst + ps[k].dst_off : outs + oslot[k];
+    csegs[k] = ZesCrcSeg{ps[k].m.isize ? (uint64_t)(at - cbase) : 0, ps[k].m.isize};
+  }
+  if ((rc = gz_gather(outs, dst, segs))) return rc;
+  std::vector<uint32_t> crc(n);
+  if ((rc = crc32_batch_locked(cbase, csegs.data(), n, crc.data()))) return rc;
+  for (uint32_t k = 0; k < n; k++)
+    if (crc[k] != ps[k].m.crc) {
+      *verdict = ZES_E_CHECKSUM;
+      return ZES_OK;
+    }
+  return ZES_OK;
+}
+
+// All members of a file as one batch (gz_decode_batch).  *done only when every member checks out; in every other case
+// nothing has been decided (the result's memory may have been written to) and the serial path runs.
 // dev: the result goes to d_dst (capacity cap), else to g.gz_acc.
 static int gunzip_parallel(GzSrc& S, bool dev, uint8_t* d_dst, uint64_t cap, uint64_t* out_len, uint32_t flags, bool* done) {
   *done = false;
@@ -4241,74 +4335,22 @@ static int gunzip_parallel(GzSrc& S, bool dev, uint8_t* d_dst, uint64_t cap, uin
   const auto t1 = now();
   if (!ok || tab.size() >= (1u << 28)) return ZES_OK;
   const uint32_t n = (uint32_t)tab.size();
-  std::vector<uint64_t> pos(n), ooff(n + 1);
+  std::vector<GzPart> ps(n);
   uint64_t total = 0, at = 0;
-  int64_t last_out = -1;  // the last member with output
   for (uint32_t k = 0; k < n; k++) {
-    pos[k] = at;
+    ps[k] = GzPart{at, tab[k], total, 0u, tab[k].isize};
     at += tab[k].size;
-    ooff[k] = total;
     total += tab[k].isize;
-    if (tab[k].isize) last_out = k;
   }
-  ooff[n] = total;
   if (dev && total > cap) return ZES_OK;
   if (!dev && ensure(g.gz_acc, total + 64)) return ZES_OK;
-  uint8_t* dst = dev ? d_dst : (uint8_t*)g.gz_acc.p;
-  const uint64_t dst_cap = dev ? cap : g.gz_acc.cap;
-  // A member is decoded in place when the 16-byte groups the decoders write stay inside its own range; the others get a
-  // slot of their own (the members run side by side: a group that reaches into a neighbour's range would race with it)
-  auto up16 = [](uint64_t v) { return (v + 15) & ~15ull; };
-  std::vector<char> direct(n);
-  std::vector<uint64_t> islot(n), oslot(n);
-  std::vector<ZesGzSeg> segs(n);
-  uint64_t ipos = 0, opos = 0;
-  for (uint32_t k = 0; k < n; k++) {
-    const uint64_t dlen = tab[k].size - tab[k].hlen - 8, m = tab[k].isize;
-    islot[k] = ipos;
-    ipos += up16(2 + dlen) + 64;
-    segs[k] = ZesGzSeg{pos[k] + tab[k].hlen, islot[k] + 2, dlen, 1u, 0u};
-    direct[k] = dst && m && (ooff[k] & 15u) == 0 && ((m & 15u) == 0 || ((int64_t)k == last_out && up16(ooff[k] + m) <= dst_cap));
-    if (!direct[k]) {
-      oslot[k] = opos;
-      opos += std::max<uint64_t>(up16(m), 16) + 16;
-    }
-  }
-  if (ensure(g.gz_bodies, ipos + 64) || ensure(g.gz_outs, opos + 64)) return ZES_OK;
-  if ((rc = gz_gather(S.d, (uint8_t*)g.gz_bodies.p, segs))) return rc;
-  // one base for both kinds of destination (inflate_jobs takes one pointer and an offset per job): the lower of the two
-  uint8_t* outs = (uint8_t*)g.gz_outs.p;
-  uint8_t* base = dst && dst < outs ? dst : outs;
-  std::vector<InfJob> jobs(n);
-  for (uint32_t k = 0; k < n; k++) {
-    const uint64_t dlen = tab[k].size - tab[k].hlen - 8, m = tab[k].isize;
-    uint8_t* to = direct[k] ? dst + ooff[k] : outs + oslot[k];
-    jobs[k] = InfJob{islot[k], 2 + dlen, (uint64_t)(to - base), direct[k] ? m : std::max<uint64_t>(up16(m), 16), 0, ZES_OK, 0};
-    jobs[k].want_end = true;
-  }
-  const std::vector<uint8_t> firsts(n, 0x78);
-  const auto t2 = now();
-  if ((rc = inflate_jobs((const uint8_t*)g.gz_bodies.p, base, jobs, firsts.data(), flags & ~(ZES_F_CHECK_ADLER | ZES_F_GZIP_SERIAL)))) return rc;
-  if (g.profiling) g.carry = g.last_times;  // (inflate_jobs has collected what ran so far: the call's last collect_times keeps it)
-  const auto t3 = now();
-  for (uint32_t k = 0; k < n; k++) {
-    const uint64_t dlen = tab[k].size - tab[k].hlen - 8;
-    if (jobs[k].status != ZES_OK || jobs[k].out_len != tab[k].isize || jobs[k].end_bit < 16 || (jobs[k].end_bit - 16 + 7) / 8 != dlen) return ZES_OK;
-  }
-  segs.clear();
-  std::vector<ZesCrcSeg> csegs(n);
-  for (uint32_t k = 0; k < n; k++) {
-    if (!direct[k] && tab[k].isize) segs.push_back(ZesGzSeg{oslot[k], ooff[k], tab[k].isize, 0u, 0u});
-    csegs[k] = ZesCrcSeg{ooff[k], tab[k].isize};
-  }
-  if ((rc = gz_gather(outs, dst, segs))) return rc;
-  std::vector<uint32_t> crc(n);
-  if ((rc = crc32_batch_locked(dst, csegs.data(), n, crc.data()))) return rc;
-  for (uint32_t k = 0; k < n; k++)
-    if (crc[k] != tab[k].crc) return ZES_OK;
+  int verdict = ZES_OK;
+  std::chrono::steady_clock::time_point st[2];
+  if ((rc = gz_decode_batch(S.d, ps, dev ? d_dst : (uint8_t*)g.gz_acc.p, dev ? cap : g.gz_acc.cap, false, flags, &verdict, st))) return rc;
+  if (verdict) return ZES_OK;
   if (dbg)
     fprintf(stderr, "zes gunzip, %u members as one batch: walk %.3f ms, plan + gather %.3f, inflate_jobs %.3f, gather + CRC-32 %.3f\n", n, ms(t0, t1),
-            ms(t1, t2), ms(t2, t3), ms(t3, now()));
+            ms(t1, st[0]), ms(st[0], st[1]), ms(st[1], now()));
   *out_len = total;
   g.last_members = (int)n;
   *done = true;
@@ -4380,6 +4422,258 @@ int zes_gunzip_alloc(const uint8_t* in, uint64_t c, zes_alloc_fn alloc, void* us
   UseDev ud(route_host());
   if (!alloc) return ZES_E_ARG;
   return gunzip_host(in, c, nullptr, 0, out_len, flags, alloc, user);
+}
+
+// ---- BGZF random access (include/zes.h: "BGZF random access"): the member index and range reads through it ----
+struct BgzfEntry {  // a member of the chain from byte 0: where it starts, how long its output is
+  uint64_t pos;
+  uint32_t isize;
+};
+
+static int bgzf_index_args(const uint8_t* in, uint64_t c, const uint64_t* coff, const uint64_t* uoff, uint64_t cap, uint64_t* members, uint32_t flags) {
+  if (!members || (!in && c) || (flags & ~ZES_F_INDEX_WALK) || (!coff) != (!uoff) || (!coff && cap)) return ZES_E_ARG;
+  *members = 0;
+  return c ? ZES_OK : ZES_E_GZIP;
+}
+
+// the index of a chain: members + 1 entries, the last one the file's end and the total of the ISIZE fields
+static int bgzf_index_out(const std::vector<BgzfEntry>& ch, uint64_t c, uint64_t* coff, uint64_t* uoff, uint64_t cap, uint64_t* members) {
+  *members = ch.size();
+  if (cap < ch.size() + 1) return ZES_E_NOSPACE;
+  uint64_t u = 0;
+  for (size_t k = 0; k < ch.size(); k++) {
+    coff[k] = ch[k].pos;
+    uoff[k] = u;
+    u += ch[k].isize;
+  }
+  coff[ch.size()] = c;
+  uoff[ch.size()] = u;
+  return ZES_OK;
+}
+
+int zes_bgzf_index(const uint8_t* in, uint64_t c, uint64_t* coff, uint64_t* uoff, uint64_t cap, uint64_t* members, uint32_t flags) {
+  if (const int arc = bgzf_index_args(in, c, coff, uoff, cap, members, flags)) return arc;
+  std::vector<BgzfEntry> ch;
+  for (uint64_t pos = 0; pos < c;) {
+    ZesGzMember m;
+    if (!gz_member(in + pos, c - pos, c - pos, &m)) return ZES_E_GZIP;
+    ch.push_back(BgzfEntry{pos, get_le32(in + pos + m.size - 4)});
+    pos += m.size;
+  }
+  return bgzf_index_out(ch, c, coff, uoff, cap, members);
+}
+
+constexpr uint64_t BGZF_MARK_FIRST = 4096;  // candidates that come down together with the counter
+
+// The chain of members of the device-resident file d_in[0, c), c != 0 (*ok: it is BGZF from its first byte to its last).
+// The parallel finder: k_bgzf_mark lists every position whose member qualifies, one read-back brings the counter and the
+// first BGZF_MARK_FIRST records down (a second one the rest, when a file has more), and the chain from 0 is followed through
+// the list sorted by position; candidates the chain does not reach (headers inside stored payloads) play no part.
+// With more candidates than the list holds (c / 256 + 1024), or with `walk`, k_gz_walk answers, its table sized for the
+// worst case: as many members as there were candidates, or c / 28 + 1 when nothing has been counted.
+static int bgzf_find_dev(const uint8_t* d_in, uint64_t c, bool walk, std::vector<BgzfEntry>& ch, bool* ok) {
+  *ok = false;
+  ch.clear();
+  int rc;
+  uint64_t counted = 0;
+  if (!walk) {
+    const uint64_t lcap = c / 256 + 1024;
+    const uint64_t tiles = (((uintptr_t)d_in & 15u) + c + ZES_BGZF_MARK_TILE - 1) / ZES_BGZF_MARK_TILE;
+    if (lcap >= (1ull << 31) || tiles >= (1ull << 31)) return ZES_E_ARG;
+    if ((rc = ensure(g.gz_tab, sizeof(ZesBgzfMark) + sizeof(ZesBgzfCand) * (size_t)lcap))) return rc;
+    ZesBgzfMark* d_head = (ZesBgzfMark*)g.gz_tab.p;
+    const ZesBgzfCand* d_list = (const ZesBgzfCand*)(d_head + 1);
+    HIPCHK(hipMemsetAsync(d_head, 0, sizeof *d_head, g.stream));
+    {
+      Timed t("k_bgzf_mark");
+      hipLaunchKernelGGL(k_bgzf_mark, dim3((uint32_t)tiles), dim3(ZES_BGZF_MARK_THREADS), 0, g.stream, d_in, c, d_head, (ZesBgzfCand*)(d_head + 1),
+                         (uint32_t)lcap);
+    }
+    HIPCHK(hipGetLastError());
+    const size_t first = (size_t)std::min<uint64_t>(lcap, BGZF_MARK_FIRST);
+    std::vector<uint8_t> down(sizeof(ZesBgzfMark) + sizeof(ZesBgzfCand) * first);
+    HIPCHK(hipMemcpyAsync(down.data(), d_head, down.size(), hipMemcpyDeviceToHost, g.stream));
+    HIPCHK(hipStreamSynchronize(g.stream));
+    ZesBgzfMark head;
+    memcpy(&head, down.data(), sizeof head);
+    counted = head.count;
+    if (counted <= lcap) {
+      std::vector<ZesBgzfCand> list((size_t)counted);
+      const size_t got = std::min<size_t>(first, list.size());
+      if (got) memcpy(list.data(), down.data() + sizeof head, sizeof(ZesBgzfCand) * got);
+      if (list.size() > got) {
+        HIPCHK(hipMemcpyAsync(list.data() + got, d_list + got, sizeof(ZesBgzfCand) * (list.size() - got), hipMemcpyDeviceToHost, g.stream));
+        HIPCHK(hipStreamSynchronize(g.stream));
+      }
+      std::sort(list.begin(), list.end(), [](const ZesBgzfCand& a, const ZesBgzfCand& b) { return a.pos < b.pos; });
+      uint64_t pos = 0;
+      while (pos < c) {  // (a candidate's size keeps it inside the file: pos never passes c)
+        auto it = std::lower_bound(list.begin(), list.end(), pos, [](const ZesBgzfCand& a, uint64_t p) { return a.pos < p; });
+        if (it == list.end() || it->pos != pos) return ZES_OK;
+        ch.push_back(BgzfEntry{pos, it->isize});
+        pos += it->size;
+      }
+      *ok = true;
+      return ZES_OK;
+    }
+  }
+  const uint64_t cap = std::min<uint64_t>(counted ? counted : c / 28 + 1, 0xFFFFFFFFull);
+  if ((rc = ensure(g.gz_tab, sizeof(ZesGzWalk) + sizeof(ZesGzMember) * (size_t)cap))) return rc;
+  ZesGzWalk* d_head = (ZesGzWalk*)g.gz_tab.p;
+  {
+    Timed t("k_gz_walk");
+    hipLaunchKernelGGL(k_gz_walk, dim3(1), dim3(64), 0, g.stream, d_in, c, d_head, (ZesGzMember*)(d_head + 1), (uint32_t)cap);
+  }
+  HIPCHK(hipGetLastError());
+  ZesGzWalk head;
+  HIPCHK(hipMemcpyAsync(&head, d_head, sizeof head, hipMemcpyDeviceToHost, g.stream));
+  HIPCHK(hipStreamSynchronize(g.stream));
+  // (head.ok asks for two members, as zes_gunzip's batch does; one is enough here: the walk got to the file's end)
+  if (!head.count || head.count > cap || head.end != c) return ZES_OK;
+  std::vector<ZesGzMember> tab(head.count);
+  HIPCHK(hipMemcpyAsync(tab.data(), d_head + 1, sizeof(ZesGzMember) * tab.size(), hipMemcpyDeviceToHost, g.stream));
+  HIPCHK(hipStreamSynchronize(g.stream));
+  uint64_t pos = 0;
+  for (const ZesGzMember& m : tab) {
+    ch.push_back(BgzfEntry{pos, m.isize});
+    pos += m.size;
+  }
+  *ok = true;
+  return ZES_OK;
+}
+
+int zes_bgzf_index_dev(const uint8_t* d_in, uint64_t c, uint64_t* coff, uint64_t* uoff, uint64_t cap, uint64_t* members, uint32_t flags) {
+  ROUTE_DEV(d_in);
+  if (const int arc = bgzf_index_args(d_in, c, coff, uoff, cap, members, flags)) return arc;
+  LOCK_READY();
+  std::vector<BgzfEntry> ch;
+  bool ok = false;
+  rc = bgzf_find_dev(d_in, c, (flags & ZES_F_INDEX_WALK) != 0, ch, &ok);
+  collect_times();
+  if (rc) return rc;
+  if (!ok) return ZES_E_GZIP;
+  return bgzf_index_out(ch, c, coff, uoff, cap, members);
+}
+
+// What the index says about a read of [pos, pos + len): *out_len = n, the bytes it yields, and the members with output in
+// that range (`touched`; none when n == 0).  Only their entries are looked at: O(log members + members in the range).
+static int bgzf_read_plan(uint64_t c, const uint64_t* coff, const uint64_t* uoff, uint64_t members, uint64_t pos, uint64_t len, uint64_t cap,
+                          uint64_t* out_len, std::vector<uint64_t>& touched) {
+  const uint64_t total = uoff[members];
+  if (pos > total) return ZES_E_ARG;
+  const uint64_t n = std::min(len, total - pos);
+  *out_len = n;
+  if (n > cap) return ZES_E_NOSPACE;
+  if (!n) return ZES_OK;
+  const uint64_t end = pos + n;
+  const uint64_t* ue = uoff + members + 1;
+  const uint64_t a = (uint64_t)(std::upper_bound(uoff, ue, pos) - uoff), b = (uint64_t)(std::lower_bound(uoff, ue, end) - uoff);
+  // member k0 holds byte pos, member k1 byte end - 1 (an index whose entries are out of order can send the searches anywhere)
+  if (!a || !b || b > members || a > b) return ZES_E_GZIP;
+  const uint64_t k0 = a - 1, k1 = b - 1;
+  if (uoff[k0] > pos || uoff[k0 + 1] <= pos || uoff[k1] >= end || uoff[k1 + 1] < end) return ZES_E_GZIP;
+  for (uint64_t k = k0; k <= k1; k++) {
+    if (uoff[k + 1] < uoff[k]) return ZES_E_GZIP;
+    if (uoff[k + 1] == uoff[k]) continue;  // no output: skipped
+    if (coff[k] >= coff[k + 1] || coff[k + 1] > c || coff[k + 1] - coff[k] > 65536 || coff[k + 1] - coff[k] < 20) return ZES_E_GZIP;
+    touched.push_back(k);
+  }
+  return ZES_OK;
+}
+
+constexpr uint64_t BGZF_PEEK = ZES_GZ_HLEN_MAX + 16;  // a touched member's first 256 bytes and its trailer, as the device form brings them down
+
+// The touched members decoded and the range's bytes put at dst[0, n).  d_src holds the file from byte `src_at` on; h: the
+// file in the caller's memory (host form), or null: the members' headers and trailers come down from d_src in one gather.
+// A member that is not what the index says (a stale or foreign index) is ZES_E_GZIP; the rest is gz_decode_batch's verdict.
+static int bgzf_read_core(const uint8_t* h, const uint8_t* d_src, uint64_t src_at, uint64_t c, const uint64_t* coff, const uint64_t* uoff, uint64_t pos,
+                          uint64_t n, const std::vector<uint64_t>& touched, uint8_t* dst, uint32_t flags) {
+  int rc;
+  const size_t nt = touched.size();
+  std::vector<uint8_t> peek;
+  if (!h) {
+    std::vector<ZesGzSeg> segs;
+    for (size_t i = 0; i < nt; i++) {
+      const uint64_t at = coff[touched[i]], size = coff[touched[i] + 1] - at;
+      segs.push_back(ZesGzSeg{at - src_at, i * BGZF_PEEK, std::min<uint64_t>(size, ZES_GZ_HLEN_MAX), 0u, 0u});
+      segs.push_back(ZesGzSeg{at - src_at + size - 8, i * BGZF_PEEK + ZES_GZ_HLEN_MAX, 8, 0u, 0u});
+    }
+    if ((rc = ensure(g.gz_stage, nt * BGZF_PEEK))) return rc;
+    if ((rc = gz_gather(d_src, (uint8_t*)g.gz_stage.p, segs))) return rc;
+    peek.resize(nt * BGZF_PEEK);
+    HIPCHK(hipMemcpyAsync(peek.data(), g.gz_stage.p, peek.size(), hipMemcpyDeviceToHost, g.stream));
+    HIPCHK(hipStreamSynchronize(g.stream));
+  }
+  std::vector<GzPart> ps(nt);
+  for (size_t i = 0; i < nt; i++) {
+    const uint64_t k = touched[i], at = coff[k], size = coff[k + 1] - at, u0 = uoff[k], u1 = uoff[k + 1];
+    const uint8_t* hd = h ? h + at : peek.data() + i * BGZF_PEEK;
+    const uint8_t* tr = h ? h + at + size - 8 : hd + ZES_GZ_HLEN_MAX;
+    ZesGzMember m;
+    if (!gz_member(hd, std::min<uint64_t>(size, ZES_GZ_HLEN_MAX), c - at, &m) || m.size != size) return ZES_E_GZIP;
+    m.crc = get_le32(tr);
+    m.isize = get_le32(tr + 4);
+    if (m.isize != u1 - u0) return ZES_E_GZIP;
+    const uint64_t lo = std::max(pos, u0), hi = std::min(pos + n, u1);
+    ps[i] = GzPart{at - src_at, m, lo - pos, (uint32_t)(lo - u0), (uint32_t)(hi - lo)};
+  }
+  int verdict = ZES_OK;
+  if ((rc = gz_decode_batch(d_src, ps, dst, n, true, flags, &verdict, nullptr))) return rc;
+  if (verdict) return verdict;
+  g.last_members = (int)nt;
+  return ZES_OK;
+}
+
+static int bgzf_read_args(const uint8_t* in, const uint64_t* coff, const uint64_t* uoff, uint64_t members, const uint8_t* out, uint64_t* out_len,
+                          uint32_t flags) {
+  if (!in || !coff || !uoff || !out || !out_len || !members || (flags & ~ZES_F_PIECES)) return ZES_E_ARG;
+  *out_len = 0;
+  return ZES_OK;
+}
+
+// a call that decodes nothing: zes_last_gunzip_members reports 0 after it
+static void bgzf_read_none() {
+  std::lock_guard<std::mutex> lk(g_mu);
+  g.last_members = 0;
+}
+
+int zes_bgzf_read_dev(const uint8_t* d_in, uint64_t c, const uint64_t* coff, const uint64_t* uoff, uint64_t members, uint64_t pos, uint64_t len,
+                      uint8_t* d_out, uint64_t cap, uint64_t* out_len, uint32_t flags) {
+  ROUTE_DEV(d_in, d_out);
+  if (const int arc = bgzf_read_args(d_in, coff, uoff, members, d_out, out_len, flags)) return arc;
+  std::vector<uint64_t> touched;
+  if (const int prc = bgzf_read_plan(c, coff, uoff, members, pos, len, cap, out_len, touched); prc || touched.empty()) {
+    bgzf_read_none();
+    return prc;
+  }
+  LOCK_READY();
+  g.last_members = 0;
+  rc = bgzf_read_core(nullptr, d_in, 0, c, coff, uoff, pos, *out_len, touched, d_out, flags);
+  if (rc) (void)hipGetLastError();
+  collect_times();
+  return rc;
+}
+
+int zes_bgzf_read(const uint8_t* in, uint64_t c, const uint64_t* coff, const uint64_t* uoff, uint64_t members, uint64_t pos, uint64_t len, uint8_t* out,
+                  uint64_t cap, uint64_t* out_len, uint32_t flags) {
+  UseDev ud(route_host());
+  if (const int arc = bgzf_read_args(in, coff, uoff, members, out, out_len, flags)) return arc;
+  std::vector<uint64_t> touched;
+  if (const int prc = bgzf_read_plan(c, coff, uoff, members, pos, len, cap, out_len, touched); prc || touched.empty()) {
+    bgzf_read_none();
+    return prc;
+  }
+  LOCK_READY();
+  g.last_members = 0;
+  // only the file bytes of the touched members cross to the device
+  const uint64_t lo = coff[touched.front()], hi = coff[touched.back() + 1], n = *out_len;
+  if ((rc = stage_in(g.gz_in, in + lo, hi - lo))) return rc;
+  if ((rc = ensure(g.gz_acc, n + 64))) return rc;
+  rc = bgzf_read_core(in, (const uint8_t*)g.gz_in.p, lo, c, coff, uoff, pos, n, touched, (uint8_t*)g.gz_acc.p, flags);
+  if (rc) (void)hipGetLastError();
+  collect_times();
+  if (rc) return rc;
+  return download(out, (const uint8_t*)g.gz_acc.p, n);
 }
 
 int zes_stage_lz77_dev(const uint8_t* d_in, uint64_t n, uint64_t start, uint32_t len, uint32_t* h_tokens, uint32_t* ntokens) {

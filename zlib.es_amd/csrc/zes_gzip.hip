@@ -9,6 +9,9 @@
 //                member's start as one coalesced access, a dword per lane, and the header is then parsed from the lanes'
 //                registers with uniform lane reads.  The member's trailer (CRC-32, ISIZE) is fetched by eight lanes once
 //                its size is known and stored while the next header is on its way, so it adds no round trip of its own.
+//   k_bgzf_mark  the same members found in parallel (zes_api.hip: bgzf_index_dev): every byte position is tested for a
+//                member's first four bytes, and each hit is judged by the walk's rule by the thread that holds it; the host
+//                follows the chain through the list of those that qualify.
 //   k_gz_gather  a segmented copy, {src_off, dst_off, len} per segment at any alignment on both sides: workgroup (s, y)
 //                takes the 64 KiB pieces y, y + gridDim.y, ... of segment s.  The destination's whole 16-byte groups are
 //                written as 16-byte stores; a group's bytes come from the two aligned 16-byte groups of the source that hold
@@ -70,6 +73,68 @@ __global__ __launch_bounds__(64) void k_gz_walk(const uint8_t* __restrict__ d_in
     head->count = k;
     head->ok = ok && k >= 2 && pos == c;
     head->end = pos;
+  }
+}
+
+// The member that may start at pos, judged by k_gz_walk's rule from global memory (no byte at or behind c is read); one that
+// qualifies is appended to the list with its trailer.
+__device__ __forceinline__ void bgzf_candidate(const uint8_t* __restrict__ d_in, uint64_t c, uint64_t pos, ZesBgzfMark* __restrict__ head,
+                                               ZesBgzfCand* __restrict__ list, uint32_t cap) {
+  const uint64_t left = c - pos;
+  if (left < 12) return;
+  const uint8_t* h = d_in + pos;
+  auto le16 = [&](uint32_t i) -> uint32_t { return (uint32_t)h[i] | (uint32_t)h[i + 1] << 8; };
+  const uint32_t hlen = 12 + le16(10);
+  if (hlen > ZES_GZ_HLEN_MAX || hlen > left) return;
+  uint32_t p = 12, size = 0;
+  while (p + 4 <= hlen) {  // the extra field, subfield by subfield
+    const uint32_t sl = le16(p + 2);
+    if (p + 4 + sl > hlen) break;
+    if (!size && h[p] == 'B' && h[p + 1] == 'C' && sl == 2) size = le16(p + 4) + 1;
+    p += 4 + sl;
+  }
+  if (p != hlen || !size || hlen + 8 > size || size > left) return;
+  const uint8_t* t = h + size - 8;
+  ZesBgzfCand r;
+  r.pos = pos;
+  r.size = size;
+  r.hlen = hlen;
+  r.crc = (uint32_t)t[0] | (uint32_t)t[1] << 8 | (uint32_t)t[2] << 16 | (uint32_t)t[3] << 24;
+  r.isize = (uint32_t)t[4] | (uint32_t)t[5] << 8 | (uint32_t)t[6] << 16 | (uint32_t)t[7] << 24;
+  const uint32_t at = atomicAdd(&head->count, 1u);
+  if (at < cap) list[at] = r;
+}
+
+// The parallel member finder: every byte position of d_in[0, c) is tested for 1f 8b 08 04, and the thread that holds a hit
+// judges the member there.  Tiles start at the 16-byte boundary at or below d_in and are read as aligned 16-byte groups, a
+// thread taking every ZES_BGZF_MARK_THREADS-th group of its tile together with the first dword of the group behind it (the
+// three bytes a signature may reach into it, across a tile's end as well); only groups that hold bytes of [0, c) are read,
+// and a position counts only when its four bytes lie inside [0, c).
+__global__ __launch_bounds__(ZES_BGZF_MARK_THREADS) void k_bgzf_mark(const uint8_t* __restrict__ d_in, uint64_t c, ZesBgzfMark* __restrict__ head,
+                                                                    ZesBgzfCand* __restrict__ list, uint32_t cap) {
+  const uint32_t sh = (uint32_t)((uintptr_t)d_in & 15u);
+  const uint4* p16 = reinterpret_cast<const uint4*>(d_in - sh);
+  const uint64_t ngroups = (sh + c + 15) / 16;  // the groups that hold bytes of the input
+  constexpr uint32_t TILE_GROUPS = ZES_BGZF_MARK_TILE / 16;
+  const uint64_t g0 = (uint64_t)blockIdx.x * TILE_GROUPS + threadIdx.x;
+#pragma unroll
+  for (uint32_t i = 0; i < TILE_GROUPS / ZES_BGZF_MARK_THREADS; i++) {
+    const uint64_t gi = g0 + (uint64_t)i * ZES_BGZF_MARK_THREADS;
+    if (gi >= ngroups) break;
+    const uint4 v = p16[gi];
+    const uint32_t nx = gi + 1 < ngroups ? reinterpret_cast<const uint32_t*>(p16 + gi + 1)[0] : 0u;
+    const uint32_t w[5] = {v.x, v.y, v.z, v.w, nx};
+    uint32_t hits = 0;
+#pragma unroll
+    for (uint32_t b = 0; b < 16; b++) {
+      const uint32_t sig = (uint32_t)((((uint64_t)w[b / 4 + 1] << 32) | w[b / 4]) >> (8 * (b & 3u)));
+      hits |= (sig == 0x04088b1fu ? 1u : 0u) << b;
+    }
+    while (hits) {
+      const uint64_t x = gi * 16 + (uint32_t)(__ffs((int)hits) - 1);  // the hit's distance from the first group's start
+      hits &= hits - 1;
+      if (x >= sh && x - sh + 4 <= c) bgzf_candidate(d_in, c, x - sh, head, list, cap);
+    }
   }
 }
 

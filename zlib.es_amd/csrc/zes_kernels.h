@@ -151,6 +151,21 @@ struct ZesGzWalk {
   uint64_t end;    // where the walk stopped
 };
 #define ZES_GZ_HLEN_MAX 256u  // a member with a longer header does not qualify (the walk reads a header as one window)
+// k_bgzf_mark (zes_gzip.hip): a workgroup tests every byte position of a tile of this many bytes for a member's first four
+// bytes; a position whose member qualifies becomes one record of the candidate list
+#define ZES_BGZF_MARK_TILE 16384u
+#define ZES_BGZF_MARK_THREADS 256u
+struct ZesBgzfCand {
+  uint64_t pos;    // where the member starts
+  uint32_t size;   // as ZesGzMember
+  uint32_t hlen;
+  uint32_t crc;
+  uint32_t isize;
+};
+struct ZesBgzfMark {
+  uint32_t count;  // candidates found (those beyond the list's capacity are counted and not stored)
+  uint32_t pad[3];
+};
 // k_gz_gather: one segment of a segmented copy
 struct ZesGzSeg {
   uint64_t src_off, dst_off, len;
@@ -248,6 +263,7 @@ __global__ void k_crc32(const uint8_t*, uint64_t, const uint32_t*, unsigned int*
 __global__ void k_crc32_seg(const uint8_t*, const ZesCrcSeg*, const uint2*, const uint32_t*, unsigned int*);
 // gzip reader and BGZF writer (zes_gzip.hip)
 __global__ void k_gz_walk(const uint8_t*, uint64_t, ZesGzWalk*, ZesGzMember*, uint32_t);
+__global__ void k_bgzf_mark(const uint8_t*, uint64_t, ZesBgzfMark*, ZesBgzfCand*, uint32_t);
 __global__ void k_gz_gather(const uint8_t*, uint8_t*, const ZesGzSeg*);
 __global__ void k_bgzf_pack(const uint8_t*, const uint8_t*, uint8_t*, const ZesBgzfRec*);
 __global__ void k_adler_blocks(const uint8_t*, const ZesBuf*, const ZesBlk*, unsigned long long*);

@@ -600,6 +600,99 @@ napi_value bgzip_common(napi_env env, napi_callback_info info, bool with_index) 
 napi_value Bgzip(napi_env env, napi_callback_info info) { return bgzip_common(env, info, false); }
 napi_value BgzipIndex(napi_env env, napi_callback_info info) { return bgzip_common(env, info, true); }
 
+// bgzfIndex(file): the member index of a BGZF file, { compressed, uncompressed }: two BigUint64Arrays of members + 1 entries
+// (include/zes.h: zes_bgzf_index, the host form: no device is touched)
+napi_value BgzfIndex(napi_env env, napi_callback_info info) {
+  size_t argc = 1;
+  napi_value argv[1];
+  napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr);
+  const uint8_t* in = nullptr;
+  size_t c = 0;
+  if (argc < 1 || !get_bytes(env, argv[0], &in, &c)) {
+    napi_throw_type_error(env, nullptr, "bgzfIndex(file): file must be a Uint8Array");
+    return nullptr;
+  }
+  uint64_t members = 0;
+  int rc = zes_bgzf_index(in, c, nullptr, nullptr, 0, &members, ZES_F_DEFAULT);  // (the count: ZES_E_NOSPACE on a valid file)
+  if (rc != ZES_E_NOSPACE) return throw_status(env, rc ? rc : ZES_E_ARG);
+  napi_value res, ab[2], ta[2];
+  void* mem[2] = {nullptr, nullptr};
+  const size_t entries = (size_t)members + 1;
+  for (int k = 0; k < 2; k++)
+    if (napi_create_arraybuffer(env, entries * 8, &mem[k], &ab[k]) != napi_ok || napi_create_typedarray(env, napi_biguint64_array, entries, ab[k], 0, &ta[k]) != napi_ok)
+      return nullptr;
+  rc = zes_bgzf_index(in, c, static_cast<uint64_t*>(mem[0]), static_cast<uint64_t*>(mem[1]), entries, &members, ZES_F_DEFAULT);
+  if (rc) return throw_status(env, rc);
+  if (napi_create_object(env, &res) != napi_ok) return nullptr;
+  napi_set_named_property(env, res, "compressed", ta[0]);
+  napi_set_named_property(env, res, "uncompressed", ta[1]);
+  return res;
+}
+
+// a position or length: a non-negative safe integer as a number, or a bigint below 2^64
+bool get_offset(napi_env env, napi_value v, uint64_t* out) {
+  napi_valuetype vt;
+  if (napi_typeof(env, v, &vt) != napi_ok) return false;
+  if (vt == napi_bigint) {
+    bool lossless = false;
+    return napi_get_value_bigint_uint64(env, v, out, &lossless) == napi_ok && lossless;
+  }
+  double d = 0;
+  if (vt != napi_number || napi_get_value_double(env, v, &d) != napi_ok || !(d >= 0) || d > 9007199254740991.0 || d != (double)(uint64_t)d) return false;
+  *out = (uint64_t)d;
+  return true;
+}
+
+bool get_u64_array(napi_env env, napi_value v, const uint64_t** data, size_t* len) {
+  bool is_ta = false;
+  if (napi_is_typedarray(env, v, &is_ta) != napi_ok || !is_ta) return false;
+  napi_typedarray_type type;
+  void* p = nullptr;
+  napi_value ab;
+  size_t off;
+  if (napi_get_typedarray_info(env, v, &type, len, &p, &ab, &off) != napi_ok || type != napi_biguint64_array) return false;
+  *data = static_cast<const uint64_t*>(p);
+  return true;
+}
+
+// bgzfRead(file, index, pos, len): bytes [pos, pos + len) of the uncompressed data, clipped at its end, through the index
+// bgzfIndex(file) returned; only the members that hold the range are uploaded and decoded (include/zes.h: zes_bgzf_read)
+napi_value BgzfRead(napi_env env, napi_callback_info info) {
+  size_t argc = 4;
+  napi_value argv[4];
+  napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr);
+  const uint8_t* in = nullptr;
+  size_t c = 0;
+  if (argc < 4 || !get_bytes(env, argv[0], &in, &c)) {
+    napi_throw_type_error(env, nullptr, "bgzfRead(file, index, pos, len): file must be a Uint8Array");
+    return nullptr;
+  }
+  const uint64_t *coff = nullptr, *uoff = nullptr;
+  size_t nc = 0, nu = 0;
+  napi_value vc, vu;
+  if (napi_get_named_property(env, argv[1], "compressed", &vc) != napi_ok || napi_get_named_property(env, argv[1], "uncompressed", &vu) != napi_ok ||
+      !get_u64_array(env, vc, &coff, &nc) || !get_u64_array(env, vu, &uoff, &nu) || nc != nu || nc < 2) {
+    napi_throw_type_error(env, nullptr, "bgzfRead(file, index, pos, len): index must be what bgzfIndex(file) returned");
+    return nullptr;
+  }
+  uint64_t pos = 0, len = 0;
+  if (!get_offset(env, argv[2], &pos) || !get_offset(env, argv[3], &len)) {
+    napi_throw_type_error(env, nullptr, "bgzfRead(file, index, pos, len): pos and len must be non-negative safe integers or bigints");
+    return nullptr;
+  }
+  const uint64_t total = uoff[nu - 1];
+  const uint64_t cap = pos <= total ? std::min<uint64_t>(len, total - pos) : 0;  // (pos > total: the library answers ZES_E_ARG)
+  ResultMem tmp = result_alloc((size_t)cap);
+  if (!tmp.p) return throw_status(env, ZES_E_ARG);
+  uint64_t out_len = 0;
+  const int rc = zes_bgzf_read(in, c, coff, uoff, nu - 1, pos, len, tmp.p, cap, &out_len, ZES_F_DEFAULT);
+  if (rc) {
+    result_free(tmp);
+    return throw_status(env, rc);
+  }
+  return take_u8(env, tmp, out_len);
+}
+
 // gunzip(input): every member of a gzip file, their outputs concatenated; one decode, then the exact-size result
 struct GunzipAlloc {
   ResultMem m;
@@ -1016,6 +1109,8 @@ napi_value ModuleInit(napi_env env, napi_value exports) {
       {"gunzip", nullptr, swept<Gunzip>, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"bgzip", nullptr, swept<Bgzip>, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"bgzipIndex", nullptr, swept<BgzipIndex>, nullptr, nullptr, nullptr, napi_default, nullptr},
+      {"bgzfIndex", nullptr, swept<BgzfIndex>, nullptr, nullptr, nullptr, napi_default, nullptr},
+      {"bgzfRead", nullptr, swept<BgzfRead>, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"lastGunzipMembers", nullptr, swept<LastGunzipMembers>, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"init", nullptr, swept<Init>, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"initDevices", nullptr, swept<InitDevices>, nullptr, nullptr, nullptr, napi_default, nullptr},

@@ -106,6 +106,21 @@ function bgzipIndex(input) {
 }
 
 /**
+ * Extra: random access into a BGZF file.  `bgzfIndex` walks the file's members on the host (no device is touched) and
+ * returns their byte positions (`compressed`) and the positions of their outputs in the uncompressed data
+ * (`uncompressed`), members + 1 entries each, the last one the file's length and the uncompressed size.  `bgzfRead` returns
+ * bytes [pos, pos + len) of the uncompressed data, clipped at its end: only the members that hold the range are uploaded
+ * and decoded.  Virtual offsets and .gzi files are not handled.
+ */
+function bgzfIndex(file) {
+  return addon.bgzfIndex(file);
+}
+
+function bgzfRead(file, index, pos, len) {
+  return addon.bgzfRead(file, index, pos, len);
+}
+
+/**
  * Extra: how many members the last gunzip() of this thread decoded as one batch (a BGZF file: all of them, the
  * end-of-file marker included); 0 when the members went one after the other.
  */
@@ -153,6 +168,8 @@ exports.gzip = gzip;
 exports.gunzip = gunzip;
 exports.bgzip = bgzip;
 exports.bgzipIndex = bgzipIndex;
+exports.bgzfIndex = bgzfIndex;
+exports.bgzfRead = bgzfRead;
 exports.lastGunzipMembers = lastGunzipMembers;
 exports.adler32 = adler32;
 exports.init = init;

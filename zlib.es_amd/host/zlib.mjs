@@ -19,6 +19,8 @@ export const gunzip = z.gunzip;
 export const lastGunzipMembers = z.lastGunzipMembers;
 export const bgzip = z.bgzip;
 export const bgzipIndex = z.bgzipIndex;
+export const bgzfIndex = z.bgzfIndex;
+export const bgzfRead = z.bgzfRead;
 export const init = z.init;
 export const initDevices = z.initDevices;
 export const trim = z.trim;

@@ -13,6 +13,8 @@ const addon = require('./build/zes_napi.node');
 
 type BatchResult = Uint8Array | Error;
 type BgzipIndexed = { data: Uint8Array, offsets: number[] };
+type BgzfIndex = { compressed: BigUint64Array, uncompressed: BigUint64Array };
+type Offset = number | bigint;
 
 export function inflate(input: Uint8Array): Uint8Array {
   return addon.inflate(input);
@@ -103,6 +105,21 @@ export function bgzip(input: Uint8Array): Uint8Array {
 
 export function bgzipIndex(input: Uint8Array): BgzipIndexed {
   return addon.bgzipIndex(input);
+}
+
+/**
+ * Extra: random access into a BGZF file.  `bgzfIndex` walks the file's members on the host (no device is touched) and
+ * returns their byte positions (`compressed`) and the positions of their outputs in the uncompressed data
+ * (`uncompressed`), members + 1 entries each, the last one the file's length and the uncompressed size.  `bgzfRead` returns
+ * bytes [pos, pos + len) of the uncompressed data, clipped at its end: only the members that hold the range are uploaded
+ * and decoded.  Virtual offsets and .gzi files are not handled.
+ */
+export function bgzfIndex(file: Uint8Array): BgzfIndex {
+  return addon.bgzfIndex(file);
+}
+
+export function bgzfRead(file: Uint8Array, index: BgzfIndex, pos: Offset, len: Offset): Uint8Array {
+  return addon.bgzfRead(file, index, pos, len);
 }
 
 /**
