@@ -61,8 +61,12 @@ typedef enum zes_status {
                                  ZES_ALLOC_EARLY in its index argument; the allocator may answer it with NULL ("not now": no block of
                                  that size at hand) and is then asked once, later, for the exact size as without the flag */
 #define ZES_ALLOC_EARLY 0x80000000u
-#define ZES_F_CHECK_ADLER 16u  /* zes_inflate, zes_inflate_dev, zes_inflate_size, zes_inflate_alloc: the 4 bytes behind the stream must
-                                  exist and hold the Adler-32 of the result (big-endian), else ZES_E_CHECKSUM.  Without the flag the
+#define ZES_F_CHECK_ADLER 16u  /* zes_inflate, zes_inflate_dev, zes_inflate_size, zes_inflate_alloc, zes_inflate_batch_dev,
+                                  zes_inflate_batch_alloc: the 4 bytes behind the stream must exist and hold the Adler-32 of the
+                                  result (big-endian), else ZES_E_CHECKSUM.  In the batch forms that is the status of the buffer
+                                  alone: its out_len stays the decoded length, a buffer with any other status keeps it, and
+                                  zes_inflate_batch_alloc does not ask for memory for a buffer that fails.  All trailers of a batch
+                                  are checked by one segmented launch (zes_adler32_batch_dev's kernel).  Without the flag the
                                   trailer is ignored, as the reference ignores it (src/zlib.ts:11-23) */
 #define ZES_F_GZIP_SERIAL 32u   /* zes_gunzip*: decode the members one after the other even where they could go as one batch:
                                   testing aid, same results */
@@ -309,6 +313,13 @@ int zes_bgzf_read_dev(const uint8_t* d_in, uint64_t c, const uint64_t* coff, con
  * replaces: `calcAdler32` src/adler32.ts:1-10 (byte extraction at src/zlib.ts:37-40). */
 int zes_adler32(const uint8_t* in, uint64_t n, uint32_t* adler);
 int zes_adler32_dev(const uint8_t* d_in, uint64_t n, uint32_t* adler);
+/* Adler-32 of many buffers of device memory in one launch: adler[i] = the Adler-32 of d_in[off[i], off[i] + len[i]), i < count.
+ * Any alignment, any length (0 gives 1), buffers may overlap; off, len and adler are host arrays.  count == 0 is ZES_OK.
+ * ZES_E_ARG: a null array with count != 0, a null d_in with a non-zero length, more than 2^31 work items (a work item is
+ * 64 KiB of a buffer).  Made for many short, unaligned buffers (the outputs of an inflate batch), which zes_adler32_dev
+ * would take one launch, one copy and one synchronisation each.
+ * replaces: `calcAdler32` src/adler32.ts:1-10, once per buffer. */
+int zes_adler32_batch_dev(const uint8_t* d_in, const uint64_t* off, const uint64_t* len, uint32_t* adler, uint32_t count);
 
 /* Batch forms over independent buffers (configs 4/5 of BASELINE.json): count buffers, the
  * i-th at d_in + in_off[i] with in_len[i] bytes, written to d_out + out_off[i] (capacity

@@ -45,7 +45,7 @@ ZES_E_GZIP = -20  # zes_gunzip*: not a valid gzip member (header, or a trailer c
 ZES_E_CHECKSUM = -21  # a trailer does not match: gzip CRC-32 / ISIZE / FHCRC, zlib Adler-32 under ZES_F_CHECK_ADLER
 ZES_F_GZIP_SERIAL = 32  # zes_gunzip*: the members one after the other even where they could go as one batch (testing aid)
 ZES_F_INDEX_WALK = 64  # zes_bgzf_index_dev: the members by k_gz_walk's serial chain instead of the parallel finder (testing aid, baseline)
-ZES_F_CHECK_ADLER = 16  # zes_inflate*: the Adler-32 trailer behind the stream must be there and match
+ZES_F_CHECK_ADLER = 16  # zes_inflate*, the batch forms included: the Adler-32 trailer behind the stream must be there and match
 
 GEN_KINDS = {"xorshift": 0, "lowent4k": 1, "itext": 2}
 
@@ -127,6 +127,7 @@ def lib():
         L.zes_gunzip_alloc.argtypes = [C.c_void_p, C.c_uint64, ALLOC_FN, C.c_void_p, u64p, C.c_uint32]
         L.zes_adler32.argtypes = [C.c_void_p, C.c_uint64, u32p]
         L.zes_adler32_dev.argtypes = [C.c_void_p, C.c_uint64, u32p]
+        L.zes_adler32_batch_dev.argtypes = [C.c_void_p, u64p, u64p, u32p, C.c_uint32]
         L.zes_deflate_batch_dev.argtypes = [C.c_void_p, u64p, u64p, C.c_void_p, u64p, u64p, u64p, i32p, C.c_uint32]
         L.zes_inflate_batch_dev.argtypes = [C.c_void_p, u64p, u64p, C.c_void_p, u64p, u64p, u64p, i32p, C.c_uint32,
                                             C.c_uint32]
@@ -278,6 +279,9 @@ def deflate_batch(buffers):
 
 
 def inflate_batch(buffers, flags=0):
+    """Inflate independent zlib streams in one call (zes_inflate_batch_alloc); returns one uint8 array or one ZlibEsError
+    per buffer.  With ZES_F_CHECK_ADLER in ``flags`` every stream's Adler-32 trailer must be there and match its result:
+    a buffer that fails is a ZlibEsError(ZES_E_CHECKSUM) and no memory is asked for it."""
     arrs = [_as_u8(b) for b in buffers]
     cnt = len(arrs)
     got = {}
@@ -559,6 +563,23 @@ def crc32_tensor(t):
 _len = len  # (crc32_batch_tensor has a parameter of that name, after the C entry point)
 
 
+def adler32_batch_tensor(d_in, off, len):
+    """Adler-32 of every d_in[off[i] : off[i] + len[i]] of a uint8 CUDA tensor, any alignment and length, in one launch
+    (zes_adler32_batch_dev); returns a list of ints."""
+    import torch
+
+    assert d_in.is_cuda and d_in.dtype == torch.uint8 and d_in.is_contiguous()
+    cnt = _len(off)
+    assert _len(len) == cnt
+    assert all(int(o) + int(n) <= d_in.numel() for o, n in zip(off, len)), "adler32_batch_tensor: a buffer reaches beyond d_in"
+    torch.cuda.current_stream(d_in.device).synchronize()
+    out = (C.c_uint32 * cnt)()
+    rc = lib().zes_adler32_batch_dev(d_in.data_ptr(), (C.c_uint64 * cnt)(*[int(x) for x in off]), (C.c_uint64 * cnt)(*[int(x) for x in len]), out, cnt)
+    if rc:
+        _raise(rc)
+    return list(out)
+
+
 def crc32_batch_tensor(d_in, off, len):
     """CRC-32 of every d_in[off[i] : off[i] + len[i]] of a uint8 CUDA tensor, any alignment and length, in one launch
     (zes_crc32_batch_dev); returns a list of ints."""
@@ -684,6 +705,9 @@ def deflate_batch_tensor(d_in, in_off, in_len, d_out, out_off, out_cap):
 
 
 def inflate_batch_tensor(d_in, in_off, in_len, d_out, out_off, out_cap, flags=0):
+    """Independent zlib streams inside one arena (offsets 16-byte aligned); returns (out_len[], status[]).  With
+    ZES_F_CHECK_ADLER in ``flags`` a stream whose Adler-32 trailer is missing or does not match its result gets the status
+    ZES_E_CHECKSUM; its out_len stays the decoded length and its bytes stay written."""
     return _batch_call(lib().zes_inflate_batch_dev, d_in, in_off, in_len, d_out, out_off, out_cap, flags)
 
 

@@ -158,7 +158,9 @@ static_assert(disjoint({PIN_SPAN(t2.search), PIN_SPAN(t2.ncand), PIN_SPAN(t2.nsu
   /* device tables (members, segments); segmented CRC-32: its buffers, work items and accumulator words.  The BGZF writer   */    \
   /* uses the same: gz_in and gz_acc for a host call's input and result, gz_bodies for a group's encoder slots, gz_tab for   */    \
   /* its member records                                                                                                       */    \
-  X(crctab) X(crcacc) X(gz_in) X(gz_acc) X(gz_stage) X(gz_bodies) X(gz_outs) X(gz_tab) X(crcseg)
+  X(crctab) X(crcacc) X(gz_in) X(gz_acc) X(gz_stage) X(gz_bodies) X(gz_outs) X(gz_tab) X(crcseg)                                  \
+  /* segmented Adler-32: its buffers, work items and accumulator words; the trailers of a checked inflate batch */                \
+  X(adlerseg)
 
 // The survivor list of the block-start search as the block-parallel tier's scan left it in a pool (one buffer): the
 // segment-parallel tier's search of the same stream starts from it instead of scanning again.  The note holds until it
@@ -2698,6 +2700,99 @@ int check_adler_trailer(const uint8_t* h_in, const uint8_t* d_in, uint64_t c, ui
   return ad == ((uint32_t)b[0] << 24 | (uint32_t)b[1] << 16 | (uint32_t)b[2] << 8 | b[3]) ? ZES_OK : ZES_E_CHECKSUM;
 }
 
+// Segmented Adler-32 (k_adler_seg): adler[i] of d[segs[i].off, + segs[i].len) for all i in one launch and one read-back.
+// The work items are (buffer, 64 KiB chunk of memory) pairs, listed here from the lengths exactly as the kernel cuts a
+// buffer; the kernel leaves two sums per buffer, finished here as k_layout finishes k_adler's.
+int adler32_batch_locked(const uint8_t* d, const ZesCrcSeg* segs, uint32_t count, uint32_t* adler) {
+  int rc;
+  struct Item {
+    uint32_t buf, chunk;
+  };
+  std::vector<Item> work;
+  work.reserve(count);
+  for (uint32_t i = 0; i < count; i++) {
+    adler[i] = 1;  // (of no bytes)
+    if (!segs[i].len) continue;
+    const uint64_t a = (uint64_t)(uintptr_t)d + segs[i].off, end = a + segs[i].len;
+    const uint64_t nch = (((end + 15) & ~(uint64_t)15) - (a & ~(uint64_t)15) + ADLER_CHUNK - 1) / ADLER_CHUNK;
+    if (work.size() + nch >= (1ull << 31)) return ZES_E_ARG;
+    for (uint64_t j = 0; j < nch; j++) work.push_back({i, (uint32_t)j});
+  }
+  if (work.empty()) return ZES_OK;
+  const size_t o_work = sizeof(ZesCrcSeg) * (size_t)count, o_acc = o_work + sizeof(Item) * work.size();
+  if ((rc = ensure(g.adlerseg, o_acc + 16 * (size_t)count))) return rc;
+  uint8_t* base = (uint8_t*)g.adlerseg.p;
+  HIPCHK(hipMemcpyAsync(base, segs, o_work, hipMemcpyHostToDevice, g.stream));
+  HIPCHK(hipMemcpyAsync(base + o_work, work.data(), sizeof(Item) * work.size(), hipMemcpyHostToDevice, g.stream));
+  HIPCHK(hipMemsetAsync(base + o_acc, 0, 16 * (size_t)count, g.stream));
+  {
+    Timed t("k_adler_seg");
+    hipLaunchKernelGGL(k_adler_seg, dim3((uint32_t)work.size()), dim3(ADLER_THREADS), 0, g.stream, d, (const ZesCrcSeg*)base, (const uint2*)(base + o_work),
+                       (unsigned long long*)(base + o_acc));
+  }
+  HIPCHK(hipGetLastError());
+  std::vector<unsigned long long> acc(2 * (size_t)count);
+  HIPCHK(hipMemcpyAsync(acc.data(), base + o_acc, 16 * (size_t)count, hipMemcpyDeviceToHost, g.stream));
+  HIPCHK(hipStreamSynchronize(g.stream));
+  for (uint32_t i = 0; i < count; i++) {
+    const uint32_t s1 = (uint32_t)((1ull + acc[2 * (size_t)i]) % 65521ull);
+    const uint32_t s2 = (uint32_t)((segs[i].len % 65521ull + acc[2 * (size_t)i + 1]) % 65521ull);
+    adler[i] = (s2 << 16) | s1;
+  }
+  return ZES_OK;
+}
+
+// ZES_F_CHECK_ADLER for the jobs of one inflate_jobs call that had want_end set: every job that ended ZES_OK must have its
+// 4 trailer bytes and they must hold the Adler-32 of its output (big-endian), else its status becomes ZES_E_CHECKSUM.  Two
+// steps: the trailers of all such jobs come back in one go (h_in[k], the job's stream in the caller's memory, when
+// given; else one k_gz_gather launch of 4-byte segments out of d_in and one read-back), then one k_adler_seg launch runs
+// over their outputs.  A job with any other status keeps it, and a job whose trailer is cut short costs no launch.
+int check_adler_jobs(const uint8_t* d_in, const uint8_t* const* h_in, const uint8_t* d_out, std::vector<InfJob>& jobs) {
+  int rc;
+  std::vector<uint32_t> who;
+  std::vector<uint64_t> at;  // the trailer's place in the job's stream
+  for (uint32_t k = 0; k < jobs.size(); k++) {
+    InfJob& j = jobs[k];
+    if (j.status != ZES_OK) continue;
+    const uint64_t t = (j.end_bit + 7) / 8;
+    if (j.end_bit < 16 || t + 4 > j.c) {
+      j.status = ZES_E_CHECKSUM;
+      continue;
+    }
+    who.push_back(k);
+    at.push_back(t);
+  }
+  if (who.empty()) return ZES_OK;
+  const size_t n = who.size();
+  std::vector<uint8_t> trail(4 * n);
+  if (h_in) {
+    for (size_t q = 0; q < n; q++) memcpy(&trail[4 * q], h_in[who[q]] + at[q], 4);
+  } else {
+    std::vector<ZesGzSeg> segs(n);
+    const size_t o_dst = (sizeof(ZesGzSeg) * n + 15) & ~(size_t)15;
+    for (size_t q = 0; q < n; q++) segs[q] = ZesGzSeg{jobs[who[q]].in_off + at[q], o_dst + 4 * q, 4, 0u, 0u};
+    if ((rc = ensure(g.adlerseg, o_dst + 4 * n))) return rc;
+    HIPCHK(hipMemcpyAsync(g.adlerseg.p, segs.data(), sizeof(ZesGzSeg) * n, hipMemcpyHostToDevice, g.stream));
+    {
+      Timed tm("k_gz_gather");
+      hipLaunchKernelGGL(k_gz_gather, dim3((uint32_t)n, 1), dim3(GZ_GATHER_THREADS), 0, g.stream, d_in, (uint8_t*)g.adlerseg.p,
+                         (const ZesGzSeg*)g.adlerseg.p);
+    }
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(trail.data(), (const uint8_t*)g.adlerseg.p + o_dst, 4 * n, hipMemcpyDeviceToHost, g.stream));
+    HIPCHK(hipStreamSynchronize(g.stream));
+  }
+  std::vector<ZesCrcSeg> csegs(n);
+  for (size_t q = 0; q < n; q++) csegs[q] = ZesCrcSeg{jobs[who[q]].out_len ? jobs[who[q]].out_off : 0, jobs[who[q]].out_len};
+  std::vector<uint32_t> ad(n);
+  if ((rc = adler32_batch_locked(d_out, csegs.data(), (uint32_t)n, ad.data()))) return rc;
+  for (size_t q = 0; q < n; q++) {
+    const uint8_t* b = &trail[4 * q];
+    if (ad[q] != ((uint32_t)b[0] << 24 | (uint32_t)b[1] << 16 | (uint32_t)b[2] << 8 | b[3])) jobs[who[q]].status = ZES_E_CHECKSUM;
+  }
+  return ZES_OK;
+}
+
 }  // namespace
 
 // ------------------------------------------------------------------------------------------
@@ -3031,8 +3126,17 @@ int zes_inflate_batch_dev(const uint8_t* d_in, const uint64_t* in_off, const uin
   for (uint32_t i = 0; i < count; i++) status[i] = ((in_off[i] & 15u) || (out_off[i] & 15u)) ? ZES_E_ARG : ZES_OK;
   std::vector<InfJob> jobs(count);
   for (uint32_t i = 0; i < count; i++) jobs[i] = InfJob{in_off[i], in_len[i], out_off[i], out_cap[i], 0, status[i], 0};
-  rc = inflate_jobs(d_in, d_out, jobs, nullptr, flags);  // the first bytes (CM nibble, src/zlib.ts:13) are read on the way
+  const bool check = (flags & ZES_F_CHECK_ADLER) != 0;
+  if (check)
+    for (InfJob& j : jobs) j.want_end = true;
+  rc = inflate_jobs(d_in, d_out, jobs, nullptr, flags & ~ZES_F_CHECK_ADLER);  // the first bytes (CM nibble, src/zlib.ts:13) are read on the way
   if (rc) return rc;
+  if (check) {
+    if (g.profiling) g.carry = g.last_times;  // (inflate_jobs has collected what ran so far: the call's last collect_times keeps it)
+    rc = check_adler_jobs(d_in, nullptr, d_out, jobs);
+    collect_times();
+    if (rc) return rc;
+  }
   for (uint32_t i = 0; i < count; i++) {
     status[i] = jobs[i].status;
     out_len[i] = jobs[i].out_len;
@@ -3285,6 +3389,7 @@ static int inflate_batch_alloc_one(const uint8_t* const* in, const uint64_t* in_
   LOCK_READY();
   std::vector<uint64_t> in_off(count), o_off(count), o_cap(count);
   std::vector<uint8_t> firsts(count);
+  const bool check = (flags & ZES_F_CHECK_ADLER) != 0;
   uint64_t tin = 0;
   for (uint32_t i = 0; i < count; i++) {
     if (!in[i] && in_len[i]) return ZES_E_ARG;
@@ -3305,15 +3410,24 @@ static int inflate_batch_alloc_one(const uint8_t* const* in, const uint64_t* in_
     uint64_t tout = 0;
     std::vector<InfJob> jobs(todo.size());
     std::vector<uint8_t> fb(todo.size());
+    std::vector<const uint8_t*> hin(todo.size());
     for (size_t k = 0; k < todo.size(); k++) {
       const uint32_t i = todo[k];
       o_off[i] = tout;
       tout += (o_cap[i] + 15) & ~15ull;
       jobs[k] = InfJob{in_off[i], in_len[i], o_off[i], o_cap[i], 0, ZES_OK, 0};
+      jobs[k].want_end = check;
       fb[k] = firsts[i];
+      hin[k] = in[i];
     }
     if ((rc = ensure(g.st_out, tout + 64))) return rc;
-    if ((rc = inflate_jobs((const uint8_t*)g.st_in.p, (uint8_t*)g.st_out.p, jobs, fb.data(), flags))) return rc;
+    if ((rc = inflate_jobs((const uint8_t*)g.st_in.p, (uint8_t*)g.st_out.p, jobs, fb.data(), flags & ~ZES_F_CHECK_ADLER))) return rc;
+    if (check) {  // the buffers that finished in this attempt, before any of them is handed out
+      if (g.profiling) g.carry = g.last_times;  // (inflate_jobs has collected what ran so far)
+      rc = check_adler_jobs(nullptr, hin.data(), (const uint8_t*)g.st_out.p, jobs);
+      collect_times();
+      if (rc) return rc;
+    }
     std::vector<uint32_t> again;
     for (size_t k = 0; k < todo.size(); k++) {
       const uint32_t i = todo[k];
@@ -3803,6 +3917,20 @@ int zes_crc32_batch_dev(const uint8_t* d_in, const uint64_t* off, const uint64_t
     segs[i] = ZesCrcSeg{off[i], len[i]};
   }
   rc = crc32_batch_locked(d_in, segs.data(), count, crc);
+  collect_times();
+  return rc;
+}
+
+int zes_adler32_batch_dev(const uint8_t* d_in, const uint64_t* off, const uint64_t* len, uint32_t* adler, uint32_t count) {
+  ROUTE_DEV(d_in);
+  if (count && (!off || !len || !adler)) return ZES_E_ARG;
+  LOCK_READY();
+  std::vector<ZesCrcSeg> segs(count);
+  for (uint32_t i = 0; i < count; i++) {
+    if (len[i] && !d_in) return ZES_E_ARG;
+    segs[i] = ZesCrcSeg{off[i], len[i]};
+  }
+  rc = adler32_batch_locked(d_in, segs.data(), count, adler);
   collect_times();
   return rc;
 }

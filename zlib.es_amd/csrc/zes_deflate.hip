@@ -2775,6 +2775,103 @@ __global__ __launch_bounds__(ADLER_THREADS) void k_adler_blocks(const uint8_t* _
 }
 
 // ------------------------------------------------------------------------------------------
+// k_adler_seg: the Adler-32 of many unrelated segments at any alignment in one launch.  Work item w = (segment, chunk) of
+// segs[]; a segment's chunks are cut at 64 KiB steps of MEMORY counted from the 16-byte boundary at or below its first
+// byte, so every load is an aligned 16-byte one inside a group that holds bytes of the segment.  The bytes of the first
+// and the last group that lie outside the segment are masked to zero behind the load: a zero byte adds nothing to either
+// sum, so nothing goes bytewise.  With a = the address of the segment's first byte and G = a rounded down to 16, chunk j
+// holds the bytes of [a, end) inside [G + 64Ki * j, G + 64Ki * (j + 1)): segment offsets [s, e).  It adds
+// A_c = sum b[i] to acc[2 * seg] and B_c + A_c * (len - e), B_c = sum (e - i) * b[i], to acc[2 * seg + 1], both mod 65521
+// (k_adler's closed form; the host finishes as k_layout does).
+// ------------------------------------------------------------------------------------------
+// the low n bytes (n <= 16) of a 16-byte group, as a mask over its four dwords
+__device__ __forceinline__ static uint4 adler_low_bytes(uint32_t n) {
+  const uint64_t lo = n >= 8u ? ~0ull : (1ull << (8u * n)) - 1ull;
+  const uint64_t hi = n <= 8u ? 0ull : (n >= 16u ? ~0ull : (1ull << (8u * (n - 8u))) - 1ull);
+  return make_uint4((uint32_t)lo, (uint32_t)(lo >> 32), (uint32_t)hi, (uint32_t)(hi >> 32));
+}
+
+// one group's share: v = its 16 bytes at chunk offset o, of which only [keep_lo, keep_hi) belong to the segment;
+// `behind` = chunk end - o - 16 (as in adler_chunk, it may wrap where the zeroed bytes behind the end stand)
+__device__ __forceinline__ static void adler_seg_group(uint4 v, uint32_t o, uint32_t keep_lo, uint32_t keep_hi, uint64_t behind, uint64_t& A,
+                                                       uint64_t& B) {
+  if (o < keep_lo || o + 16u > keep_hi) {  // the group the segment starts inside, the group it ends inside
+    const uint4 ml = adler_low_bytes(keep_lo > o ? keep_lo - o : 0u);
+    const uint4 mh = adler_low_bytes(keep_hi > o ? min(keep_hi - o, 16u) : 0u);
+    v.x &= mh.x & ~ml.x;
+    v.y &= mh.y & ~ml.y;
+    v.z &= mh.z & ~ml.z;
+    v.w &= mh.w & ~ml.w;
+  }
+  uint32_t a = __builtin_amdgcn_udot4(v.x, 0x01010101u, 0u, false);
+  a = __builtin_amdgcn_udot4(v.y, 0x01010101u, a, false);
+  a = __builtin_amdgcn_udot4(v.z, 0x01010101u, a, false);
+  a = __builtin_amdgcn_udot4(v.w, 0x01010101u, a, false);
+  uint32_t w = __builtin_amdgcn_udot4(v.x, 0x0D0E0F10u, 0u, false);  // byte k of the 16 weighs 16 - k
+  w = __builtin_amdgcn_udot4(v.y, 0x090A0B0Cu, w, false);
+  w = __builtin_amdgcn_udot4(v.z, 0x05060708u, w, false);
+  w = __builtin_amdgcn_udot4(v.w, 0x01020304u, w, false);
+  A += a;
+  B += (uint64_t)w + (uint64_t)a * behind;
+}
+
+__global__ __launch_bounds__(ADLER_THREADS) void k_adler_seg(const uint8_t* __restrict__ d_in, const ZesCrcSeg* __restrict__ segs,
+                                                             const uint2* __restrict__ work, unsigned long long* __restrict__ acc) {
+  __shared__ uint64_t sa[ADLER_THREADS / 64], sb[ADLER_THREADS / 64];
+  const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+  const uint2 wk = work[blockIdx.x];
+  const ZesCrcSeg sg = segs[wk.x];
+  const uint64_t a = (uint64_t)(uintptr_t)d_in + sg.off, end = a + sg.len;
+  const uint64_t lo = (a & ~15ull) + (uint64_t)wk.y * ADLER_CHUNK;       // the chunk's groups: [lo, hi)
+  const uint64_t hi = min(lo + ADLER_CHUNK, (end + 15ull) & ~15ull);
+  const uint32_t span = (uint32_t)(hi - lo);                             // (a multiple of 16, at most 64 Ki)
+  const uint32_t keep_lo = a > lo ? (uint32_t)(a - lo) : 0u;             // chunk offsets of the segment's bytes: [keep_lo, keep_hi)
+  const uint32_t keep_hi = (uint32_t)(min(end, hi) - lo);
+  const uint4* __restrict__ p = reinterpret_cast<const uint4*>((uintptr_t)lo);
+  // a byte at chunk offset q weighs keep_hi - q = (keep_hi - o - 16) + (16 - k) for q = o + k
+  uint64_t A = 0, B = 0;
+  // whole rounds first, four 16-byte loads in flight per thread (adler_chunk: one at a time ran at 1.6 TB/s)
+  constexpr uint32_t ROUND = ADLER_THREADS * 16u * 4u;
+  const uint32_t nround = span / ROUND;
+  for (uint32_t r = 0; r < nround; r++) {
+    uint4 v[4];
+#pragma unroll
+    for (uint32_t q = 0; q < 4; q++) v[q] = p[(r * ROUND + q * ADLER_THREADS * 16u) / 16u + tid];
+#pragma unroll
+    for (uint32_t q = 0; q < 4; q++) {
+      const uint32_t o = r * ROUND + q * ADLER_THREADS * 16u + tid * 16u;
+      adler_seg_group(v[q], o, keep_lo, keep_hi, (uint64_t)keep_hi - o - 16u, A, B);
+    }
+  }
+  for (uint32_t o = nround * ROUND + tid * 16u; o < span; o += ADLER_THREADS * 16u)
+    adler_seg_group(p[o / 16u], o, keep_lo, keep_hi, (uint64_t)keep_hi - o - 16u, A, B);
+  // note: where o + 16 > keep_hi the factor keep_hi - o - 16 wraps modulo 2^64, and so does the over-count inside w for
+  // the zeroed bytes: together they are still exact modulo 2^64, because keep_hi - o - k >= 1 for every byte that counts
+  for (int d = 32; d >= 1; d >>= 1) {
+    A += __shfl_down(A, d);
+    B += __shfl_down(B, d);
+  }
+  if (lane == 0) {
+    sa[wave] = A;
+    sb[wave] = B;
+  }
+  __syncthreads();
+  if (tid == 0) {
+    uint64_t ta = 0, tb = 0;
+    for (uint32_t w = 0; w < ADLER_THREADS / 64; w++) {
+      ta += sa[w];
+      tb += sb[w];
+    }
+    const uint64_t after = end - min(end, hi);  // len - e
+    ta %= 65521u;
+    tb %= 65521u;
+    const uint64_t share = (tb + ta * (after % 65521u)) % 65521u;
+    atomicAdd(&acc[2 * (size_t)wk.x], (unsigned long long)ta);
+    atomicAdd(&acc[2 * (size_t)wk.x + 1], (unsigned long long)share);
+  }
+}
+
+// ------------------------------------------------------------------------------------------
 // k_layout: one workgroup per buffer.  Exclusive scan of the block bit counts (blocks are
 // bit-concatenated, src/deflate.ts:20-34), final zero pad (:35-37), zlib header and Adler-32
 // trailer (src/zlib.ts:28-46).  Boundary dwords of every block are zeroed here because k_emit

@@ -132,7 +132,7 @@ struct ZesSegOut {
   uint32_t hist;  // bytes of output in front of out_off that exist (a later piece of a long stream: up to 32768)
 };
 
-// k_crc32_seg (zes_crc.hip): one buffer of a batch, bytes [off, off + len) of the input
+// k_crc32_seg (zes_crc.hip), k_adler_seg (zes_deflate.hip): one buffer of a batch, bytes [off, off + len) of the input
 struct ZesCrcSeg {
   uint64_t off, len;
 };
@@ -267,6 +267,7 @@ __global__ void k_bgzf_mark(const uint8_t*, uint64_t, ZesBgzfMark*, ZesBgzfCand*
 __global__ void k_gz_gather(const uint8_t*, uint8_t*, const ZesGzSeg*);
 __global__ void k_bgzf_pack(const uint8_t*, const uint8_t*, uint8_t*, const ZesBgzfRec*);
 __global__ void k_adler_blocks(const uint8_t*, const ZesBuf*, const ZesBlk*, unsigned long long*);
+__global__ void k_adler_seg(const uint8_t*, const ZesCrcSeg*, const uint2*, unsigned long long*);
 __global__ void k_layout(uint8_t*, const ZesBuf*, ZesBlk*, const unsigned long long*, ZesRes*);
 __global__ void k_emit(uint8_t*, const ZesBuf*, const ZesBlk*, const uint32_t*, const uint32_t*, const uint32_t*);
 __global__ void k_zero_u64(unsigned long long*, uint32_t);

@@ -428,9 +428,21 @@ napi_value Deflate(napi_env env, napi_callback_info info) {
   return take_u8(env, tmp, out_len);
 }
 
+// the optional `options` argument of the inflate forms, { verify?: boolean }: ZES_F_CHECK_ADLER when verify is true, else
+// nothing (no second argument, undefined, null, an object without the property: the call is the one-argument call)
+uint32_t verify_flag(napi_env env, size_t argc, const napi_value* argv, size_t at) {
+  if (argc <= at) return 0;
+  napi_valuetype t = napi_undefined;
+  if (napi_typeof(env, argv[at], &t) != napi_ok || t != napi_object) return 0;
+  napi_value v;
+  bool on = false;
+  if (napi_get_named_property(env, argv[at], "verify", &v) != napi_ok || napi_typeof(env, v, &t) != napi_ok || t != napi_boolean) return 0;
+  return napi_get_value_bool(env, v, &on) == napi_ok && on ? ZES_F_CHECK_ADLER : 0;
+}
+
 napi_value Inflate(napi_env env, napi_callback_info info) {
-  size_t argc = 1;
-  napi_value argv[1];
+  size_t argc = 2;
+  napi_value argv[2];
   napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr);
   const uint8_t* in = nullptr;
   size_t c = 0;
@@ -453,7 +465,8 @@ napi_value Inflate(napi_env env, napi_callback_info info) {
   }
   // (the pooled block is longer than the ArrayBuffer shows of it anyway: the library may ask early for an upper estimate and
   // send the bytes down while it is still decoding)
-  const int rc = zes_inflate_alloc(in, c, sync_alloc, &sa, &out_len, ZES_F_ALLOC_BOUND);
+  // (with ZES_F_CHECK_ADLER the library takes its one-pass path, where ZES_F_ALLOC_BOUND asks for nothing early)
+  const int rc = zes_inflate_alloc(in, c, sync_alloc, &sa, &out_len, ZES_F_ALLOC_BOUND | verify_flag(env, argc, argv, 1));
   if (!sa.in_scratch) g_big.top_up();
   if (rc) {
     if (!sa.in_scratch) result_free(sa.m);
@@ -798,6 +811,7 @@ struct AsyncJob {
   const uint8_t* in = nullptr;
   size_t n = 0;
   bool inflate = false;
+  uint32_t flags = 0;  // inflate: ZES_F_CHECK_ADLER when the caller asked for { verify: true }
   ResultMem out;
   uint64_t out_len = 0;
   int rc = 0;
@@ -824,7 +838,7 @@ void async_execute(napi_env, void* data) {  // worker thread: no N-API calls her
     return;
   }
   // one call: the library decodes, then asks for memory of the exact size (no state is kept in the library between calls)
-  j->rc = zes_inflate_alloc(j->in, j->n, async_alloc, j, &j->out_len, ZES_F_ALLOC_BOUND);
+  j->rc = zes_inflate_alloc(j->in, j->n, async_alloc, j, &j->out_len, ZES_F_ALLOC_BOUND | j->flags);
   g_big.top_up();
 }
 
@@ -857,8 +871,8 @@ void async_complete(napi_env env, napi_status, void* data) {  // JS thread again
 }
 
 napi_value start_async(napi_env env, napi_callback_info info, bool inflate) {
-  size_t argc = 1;
-  napi_value argv[1];
+  size_t argc = 2;
+  napi_value argv[2];
   napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr);
   const uint8_t* in = nullptr;
   size_t n = 0;
@@ -870,6 +884,7 @@ napi_value start_async(napi_env env, napi_callback_info info, bool inflate) {
   j->in = in;
   j->n = n;
   j->inflate = inflate;
+  if (inflate) j->flags = verify_flag(env, argc, argv, 1);
   napi_value promise, name;
   if (napi_create_promise(env, &j->deferred, &promise) != napi_ok) {
     delete j;
@@ -906,6 +921,7 @@ struct BatchJob {
   napi_deferred deferred = nullptr;  // null: synchronous call
   napi_ref input_ref = nullptr;
   bool inflate = false;
+  uint32_t flags = 0;  // inflate: ZES_F_CHECK_ADLER when the caller asked for { verify: true }
   uint32_t count = 0;
   const uint8_t** in = nullptr;
   uint64_t* in_len = nullptr;
@@ -944,7 +960,7 @@ uint8_t* batch_alloc(void* user, uint32_t i, uint64_t n) {  // any thread: plain
 void batch_execute(napi_env, void* data) {
   BatchJob* j = static_cast<BatchJob*>(data);
   if (j->inflate) {
-    j->rc = zes_inflate_batch_alloc(j->in, j->in_len, batch_alloc, j, j->out_len, j->status, j->count, ZES_F_DEFAULT);
+    j->rc = zes_inflate_batch_alloc(j->in, j->in_len, batch_alloc, j, j->out_len, j->status, j->count, ZES_F_DEFAULT | j->flags);
     return;
   }
   for (uint32_t i = 0; i < j->count; i++) {
@@ -1002,8 +1018,8 @@ void batch_complete(napi_env env, napi_status, void* data) {
 }
 
 napi_value start_batch(napi_env env, napi_callback_info info, bool inflate, bool async) {
-  size_t argc = 1;
-  napi_value argv[1];
+  size_t argc = 2;
+  napi_value argv[2];
   napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr);
   bool is_arr = false;
   uint32_t count = 0;
@@ -1013,6 +1029,7 @@ napi_value start_batch(napi_env env, napi_callback_info info, bool inflate, bool
   }
   BatchJob* j = new BatchJob();
   j->inflate = inflate;
+  if (inflate) j->flags = verify_flag(env, argc, argv, 1);
   j->count = count;
   j->in = new const uint8_t*[count + 1]();
   j->in_len = new uint64_t[count + 1]();

@@ -13,9 +13,15 @@
  */
 const addon = require('./build/zes_napi.node');
 
+/**
+ * Extra (not in the reference API): `verify: true` makes an inflate form check the stream's Adler-32 trailer against its
+ * result; a trailer that is missing or does not match is the Error "zes: checksum mismatch".  The reference ignores the
+ * trailer (src/zlib.ts:11-23), and so does every call without the option.  (A rest parameter below, not
+ * `options?`: inflate.length stays 1, as the reference's; zlib.d.ts declares one optional argument.)
+ */
 
-function inflate(input) {
-  return addon.inflate(input);
+function inflate(input, ...options) {
+  return addon.inflate(input, options[0]);
 }
 
 function deflate(input) {
@@ -44,30 +50,32 @@ function deflateAsync(input) {
   return addon.deflateAsync(input);
 }
 
-function inflateAsync(input) {
-  return addon.inflateAsync(input);
+function inflateAsync(input, ...options) {
+  return addon.inflateAsync(input, options[0]);
 }
 
 /**
  * Batch forms (not in the reference API; SURVEY §7 step 3): an array of independent buffers in one call — what a
  * caller's loop over deflate()/inflate() (reference README.md:28-42) becomes when small buffers should share the GPU.
  * Element i of the result is the Uint8Array deflate(inputs[i]) / inflate(inputs[i]) would return, or — instead of a
- * throw — the `Error` it would have thrown (same message).  The Async forms run on a libuv worker thread.
+ * throw — the `Error` it would have thrown (same message).  The Async forms run on a libuv worker thread.  With
+ * `{ verify: true }` the inflate forms check every stream's Adler-32 trailer in one launch over all results; a buffer
+ * that fails is the Error "zes: checksum mismatch" in its element.
  */
 function deflateBatch(inputs) {
   return addon.deflateBatch(inputs);
 }
 
-function inflateBatch(inputs) {
-  return addon.inflateBatch(inputs);
+function inflateBatch(inputs, ...options) {
+  return addon.inflateBatch(inputs, options[0]);
 }
 
 function deflateBatchAsync(inputs) {
   return addon.deflateBatchAsync(inputs);
 }
 
-function inflateBatchAsync(inputs) {
-  return addon.inflateBatchAsync(inputs);
+function inflateBatchAsync(inputs, ...options) {
+  return addon.inflateBatchAsync(inputs, options[0]);
 }
 
 /**

@@ -15,9 +15,16 @@ type BatchResult = Uint8Array | Error;
 type BgzipIndexed = { data: Uint8Array, offsets: number[] };
 type BgzfIndex = { compressed: BigUint64Array, uncompressed: BigUint64Array };
 type Offset = number | bigint;
+/**
+ * Extra (not in the reference API): `verify: true` makes an inflate form check the stream's Adler-32 trailer against its
+ * result; a trailer that is missing or does not match is the Error "zes: checksum mismatch".  The reference ignores the
+ * trailer (src/zlib.ts:11-23), and so does every call without the option.  (A rest parameter below, not
+ * `options?`: inflate.length stays 1, as the reference's; zlib.d.ts declares one optional argument.)
+ */
+type InflateOptions = { verify?: boolean };
 
-export function inflate(input: Uint8Array): Uint8Array {
-  return addon.inflate(input);
+export function inflate(input: Uint8Array, ...options: InflateOptions[]): Uint8Array {
+  return addon.inflate(input, options[0]);
 }
 
 export function deflate(input: Uint8Array): Uint8Array {
@@ -46,30 +53,32 @@ export function deflateAsync(input: Uint8Array): Promise<Uint8Array> {
   return addon.deflateAsync(input);
 }
 
-export function inflateAsync(input: Uint8Array): Promise<Uint8Array> {
-  return addon.inflateAsync(input);
+export function inflateAsync(input: Uint8Array, ...options: InflateOptions[]): Promise<Uint8Array> {
+  return addon.inflateAsync(input, options[0]);
 }
 
 /**
  * Batch forms (not in the reference API; SURVEY §7 step 3): an array of independent buffers in one call — what a
  * caller's loop over deflate()/inflate() (reference README.md:28-42) becomes when small buffers should share the GPU.
  * Element i of the result is the Uint8Array deflate(inputs[i]) / inflate(inputs[i]) would return, or — instead of a
- * throw — the `Error` it would have thrown (same message).  The Async forms run on a libuv worker thread.
+ * throw — the `Error` it would have thrown (same message).  The Async forms run on a libuv worker thread.  With
+ * `{ verify: true }` the inflate forms check every stream's Adler-32 trailer in one launch over all results; a buffer
+ * that fails is the Error "zes: checksum mismatch" in its element.
  */
 export function deflateBatch(inputs: Uint8Array[]): BatchResult[] {
   return addon.deflateBatch(inputs);
 }
 
-export function inflateBatch(inputs: Uint8Array[]): BatchResult[] {
-  return addon.inflateBatch(inputs);
+export function inflateBatch(inputs: Uint8Array[], ...options: InflateOptions[]): BatchResult[] {
+  return addon.inflateBatch(inputs, options[0]);
 }
 
 export function deflateBatchAsync(inputs: Uint8Array[]): Promise<BatchResult[]> {
   return addon.deflateBatchAsync(inputs);
 }
 
-export function inflateBatchAsync(inputs: Uint8Array[]): Promise<BatchResult[]> {
-  return addon.inflateBatchAsync(inputs);
+export function inflateBatchAsync(inputs: Uint8Array[], ...options: InflateOptions[]): Promise<BatchResult[]> {
+  return addon.inflateBatchAsync(inputs, options[0]);
 }
 
 /**
