@@ -1,0 +1,230 @@
+"""The checksum / gzip / BGZF layer's launches: a case per seam of the layer, each at the smallest shape that reaches it, and
+a runner that records what a call came to — status, result, and the launches per profiled name (zes_last_kernel_times).
+tests/test_gpu_container_launches.py compares the records with tests/golden/container_launches.json.
+
+    python -m tests._container_cases      writes tests/golden/container_launches.json (ZES_LIB selects the library)
+
+The launch counts are kept for this layer's kernels (LAYER); of a call's inflate and deflate kernels only the set of names.
+Every input is the library's own (its generators, its encoders): nothing depends on the zlib build beside it.
+"""
+import functools
+import gzip as pygzip
+import hashlib
+import json
+import os
+import sys
+import zlib as pz
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+GOLDEN = os.path.join(ROOT, "tests", "golden", "container_launches.json")
+LAYER = ("k_crc32", "k_crc32_seg", "k_adler", "k_adler_seg", "k_gz_walk", "k_gz_gather", "k_bgzf_mark", "k_bgzf_pack")
+CHUNK = 65280  # ZES_BGZF_CHUNK
+
+# (alignment, length) of the checksum cases' buffers: a start inside a 16-byte piece, a tail behind the last 16-byte boundary,
+# one and two 64 KiB work items, a buffer of no bytes between two others and one in last place
+SEGMENTS = [(15, 0), (15, 1), (0, 0), (15, 17), (0, 65536), (1, 65537), (7, 131075), (0, 0)]
+
+CASES = ["crc32 batch", "adler32 batch", "crc32 batch, every length 0", "adler32 batch, every length 0", "crc32 batch, count 0",
+         "adler32 batch, count 0", "gunzip_tensor bgzf", "gunzip bgzf", "gunzip two members", "bgzip_tensor", "bgzip_tensor pieces",
+         "bgzf_index_tensor", "bgzf_index_tensor walk", "bgzf_read_tensor", "bgzf_read", "inflate_batch_tensor checked",
+         "inflate_batch checked"]
+
+
+def _pkg():
+    import torch  # noqa: F401  (before the library: tests/conftest.py says why)
+
+    if ROOT not in sys.path:
+        sys.path.insert(0, ROOT)
+    import __graft_entry__ as ge
+
+    return ge.load()
+
+
+def _itext(n, seed=7):
+    return _pkg().gen("itext", seed, n)
+
+
+@functools.lru_cache(maxsize=None)
+def arena():
+    """(bytes, off[], len[]) of the checksum cases."""
+    off, length, pos = [], [], 0
+    for align, n in SEGMENTS:
+        off.append(pos + align)
+        length.append(n)
+        pos += (align + n + 15) // 16 * 16 + 16
+    return _itext(pos), off, length
+
+
+@functools.lru_cache(maxsize=None)
+def bgzf_file(n):
+    """(the library's bgzip of n bytes, the bytes)."""
+    plain = _itext(n, 11)
+    blob = _pkg().bgzip(plain)
+    assert pygzip.decompress(blob.tobytes()) == plain.tobytes()
+    return blob, plain.tobytes()
+
+
+@functools.lru_cache(maxsize=None)
+def checked_streams():
+    """Three zlib streams of a few KiB and their bytes: a good one, one with a wrong trailer, one cut inside its trailer."""
+    z = _pkg()
+    plains = [_itext(n, 20 + k) for k, n in enumerate((3000, 5000, 4000))]
+    streams = [z.deflate(p).copy() for p in plains]
+    streams[1][-1] ^= 1
+    streams[2] = streams[2][:-2].copy()
+    return streams, [p.tobytes() for p in plains]
+
+
+def _dev(a, gpu, lead=0):
+    """`a` on the device, `lead` bytes behind a 16-byte boundary."""
+    import torch
+
+    t = torch.zeros(lead + a.size, dtype=torch.uint8, device=gpu)
+    assert t.data_ptr() % 16 == 0
+    t[lead:] = torch.from_numpy(np.ascontiguousarray(a)).to(gpu)
+    return t[lead:]
+
+
+def _call(z, fn):
+    """status, what fn returns (None with a status), the NOSPACE size."""
+    try:
+        return 0, fn(), 0
+    except z.ZlibEsError as e:
+        return e.code, None, getattr(e, "need", 0)
+
+
+def _record(z, status, **what):
+    names = {name: n for name, _, n in z.last_kernel_times()}
+    rec = {"status": status, "launches": {k: v for k, v in names.items() if k in LAYER}, "others": sorted(k for k in names if k not in LAYER)}
+    rec.update(what)
+    return rec
+
+
+def _checksums(z, gpu, which, lengths=None, count=None):
+    data, off, length = arena()
+    if lengths is not None:
+        length = lengths
+    off, length = off[:count], length[:count]
+    fn, ref = (z.crc32_batch_tensor, pz.crc32) if which == "crc32" else (z.adler32_batch_tensor, pz.adler32)
+    status, got, _ = _call(z, lambda: fn(_dev(data, gpu), off, length))
+    want = [ref(data[o:o + n].tobytes()) for o, n in zip(off, length)]
+    return _record(z, status, values=got, values_equal=got == want)
+
+
+def _gunzip(z, gpu, blob, plain, on_device):
+    import torch
+
+    if on_device:
+        out = torch.zeros(len(plain), dtype=torch.uint8, device=gpu)
+        status, got, _ = _call(z, lambda: z.gunzip_tensor(_dev(blob, gpu), out).cpu().numpy())
+    else:
+        status, got, _ = _call(z, lambda: z.gunzip(blob))
+    return _record(z, status, out_len=None if got is None else int(got.size), bytes_equal=None if got is None else got.tobytes() == plain,
+                   members=z.last_gunzip_members())
+
+
+def _bgzip(z, gpu, n, flags):
+    plain = _itext(n, 11)
+    status, got, _ = _call(z, lambda: z.bgzip_tensor(_dev(plain, gpu), flags=flags, index=True))
+    blob = got[0].cpu().numpy().tobytes()
+    return _record(z, status, out_len=len(blob), sha256=hashlib.sha256(blob).hexdigest(), member_off=[int(v) for v in got[1]],
+                   bytes_equal=pygzip.decompress(blob) == plain.tobytes())
+
+
+def _index(z, gpu, flags):
+    blob, _ = bgzf_file(4 * CHUNK + 1)
+    status, got, _ = _call(z, lambda: z.bgzf_index_tensor(_dev(blob, gpu), flags))
+    same = [a.tolist() for a in got] == [a.tolist() for a in z.bgzf_index(blob)]
+    return _record(z, status, coff=got[0].tolist(), uoff=got[1].tolist(), same_as_host_index=same)
+
+
+def _read(z, gpu, on_device):
+    import torch
+
+    blob, plain = bgzf_file(70000)
+    index = z.bgzf_index(blob)
+    pos, length = 30000, CHUNK + 2000 - 30000  # the middle of member 0 to the middle of member 1
+    if on_device:
+        out = torch.zeros(3 + length, dtype=torch.uint8, device=gpu)[3:]
+        assert out.data_ptr() % 16 == 3
+        status, got, _ = _call(z, lambda: z.bgzf_read_tensor(_dev(blob, gpu), index, pos, length, out).cpu().numpy())
+    else:
+        status, got, _ = _call(z, lambda: z.bgzf_read(blob, index, pos, length))
+    return _record(z, status, out_len=int(got.size), bytes_equal=got.tobytes() == plain[pos:pos + length], members=z.last_gunzip_members())
+
+
+def _checked(z, gpu, on_device):
+    import torch
+
+    streams, plains = checked_streams()
+    if not on_device:
+        res = z.inflate_batch(streams, z.ZES_F_CHECK_ADLER)
+        st = [r.code if isinstance(r, z.ZlibEsError) else 0 for r in res]
+        return _record(z, 0, statuses=st, bytes_equal=[r.tobytes() == p if s == 0 else None for r, s, p in zip(res, st, plains)])
+    up = lambda n: (n + 15) // 16 * 16
+    in_off, out_off = np.cumsum([0] + [up(s.size) for s in streams]).tolist(), np.cumsum([0] + [up(len(p)) for p in plains]).tolist()
+    h_in = np.zeros(in_off[-1] + 64, dtype=np.uint8)
+    for s, o in zip(streams, in_off):
+        h_in[o:o + s.size] = s
+    out = torch.zeros(out_off[-1], dtype=torch.uint8, device=gpu)
+    status, got, _ = _call(z, lambda: z.inflate_batch_tensor(_dev(h_in, gpu), in_off[:-1], [s.size for s in streams], out, out_off[:-1],
+                                                             [len(p) for p in plains], z.ZES_F_CHECK_ADLER))
+    host = out.cpu().numpy()
+    olen, st = got
+    return _record(z, status, statuses=[int(s) for s in st], out_len=[int(n) for n in olen],
+                   bytes_equal=[host[o:o + len(p)].tobytes() == p for o, p in zip(out_off, plains)])
+
+
+def run_case(z, gpu, name):
+    """A case's record; profiling is on for the call and off again behind it."""
+    z.set_profiling(True)
+    try:
+        if name.endswith("batch"):
+            return _checksums(z, gpu, name.split()[0])
+        if name.endswith("every length 0"):
+            return _checksums(z, gpu, name.split()[0], lengths=[0] * len(SEGMENTS))
+        if name.endswith("count 0"):
+            return _checksums(z, gpu, name.split()[0], count=0)
+        if name in ("gunzip_tensor bgzf", "gunzip bgzf"):
+            return _gunzip(z, gpu, *bgzf_file(70000), on_device=name.startswith("gunzip_tensor"))
+        if name == "gunzip two members":
+            a, b = _itext(3000, 31), _itext(70000, 32)
+            return _gunzip(z, gpu, np.concatenate([z.gzip(a), z.gzip(b)]), a.tobytes() + b.tobytes(), on_device=False)
+        if name == "bgzip_tensor":
+            return _bgzip(z, gpu, 70000, 0)
+        if name == "bgzip_tensor pieces":
+            return _bgzip(z, gpu, 4 * CHUNK + 1, z.ZES_F_PIECES)  # five members: two groups of BGZF_GROUP_PIECES
+        if name.startswith("bgzf_index_tensor"):
+            return _index(z, gpu, z.ZES_F_INDEX_WALK if name.endswith("walk") else 0)
+        if name in ("bgzf_read_tensor", "bgzf_read"):
+            return _read(z, gpu, name == "bgzf_read_tensor")
+        if name in ("inflate_batch_tensor checked", "inflate_batch checked"):
+            return _checked(z, gpu, name.startswith("inflate_batch_tensor"))
+        raise KeyError(name)
+    finally:
+        z.set_profiling(False)
+
+
+def main():
+    import torch
+
+    z = _pkg()
+    assert torch.cuda.is_available(), "the launches are recorded on a GPU"
+    z.init(0)
+    gpu = torch.device("cuda:0")
+    rec = {}
+    for name in CASES:
+        first, second = run_case(z, gpu, name), run_case(z, gpu, name)
+        assert first == second, "%s: the second run differs from the first: %r / %r" % (name, first, second)
+        rec[name] = first
+        print(name, first, file=sys.stderr)
+    with open(GOLDEN, "w") as f:
+        json.dump(rec, f, indent=1, sort_keys=True)
+        f.write("\n")
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

@@ -157,6 +157,16 @@ def _raise(code):
     raise ZlibEsError(code, strerror(code))
 
 
+def _raise_need(rc, n):
+    """A device form's status: ZES_E_NOSPACE carries the size the result needs (``.need``, from the call's out_len ``n``)."""
+    if rc == ZES_E_NOSPACE:
+        err = ZlibEsError(rc, "%s (need %d bytes)" % (strerror(rc), n.value))
+        err.need = n.value
+        raise err
+    if rc:
+        _raise(rc)
+
+
 def init(device=0):
     rc = lib().zes_init(int(device))
     if rc:
@@ -527,12 +537,7 @@ def inflate_tensor(t, out, flags=0):
     torch.cuda.current_stream(t.device).synchronize()
     n = C.c_uint64()
     rc = lib().zes_inflate_dev(t.data_ptr(), t.numel(), out.data_ptr(), out.numel(), C.byref(n), flags)
-    if rc == ZES_E_NOSPACE:
-        err = ZlibEsError(rc, "%s (need %d bytes)" % (strerror(rc), n.value))
-        err.need = n.value
-        raise err
-    if rc:
-        _raise(rc)
+    _raise_need(rc, n)
     return out[: n.value]
 
 
@@ -560,41 +565,34 @@ def crc32_tensor(t):
     return out.value
 
 
-_len = len  # (crc32_batch_tensor has a parameter of that name, after the C entry point)
+_len = len  # (the batch checksums have a parameter of that name, after the C entry points)
+
+
+def _checksum_batch_tensor(fn, who, d_in, off, len):
+    import torch
+
+    assert d_in.is_cuda and d_in.dtype == torch.uint8 and d_in.is_contiguous()
+    cnt = _len(off)
+    assert _len(len) == cnt
+    assert all(int(o) + int(n) <= d_in.numel() for o, n in zip(off, len)), "%s: a buffer reaches beyond d_in" % who
+    torch.cuda.current_stream(d_in.device).synchronize()
+    out = (C.c_uint32 * cnt)()
+    rc = fn(d_in.data_ptr(), (C.c_uint64 * cnt)(*[int(x) for x in off]), (C.c_uint64 * cnt)(*[int(x) for x in len]), out, cnt)
+    if rc:
+        _raise(rc)
+    return list(out)
 
 
 def adler32_batch_tensor(d_in, off, len):
     """Adler-32 of every d_in[off[i] : off[i] + len[i]] of a uint8 CUDA tensor, any alignment and length, in one launch
     (zes_adler32_batch_dev); returns a list of ints."""
-    import torch
-
-    assert d_in.is_cuda and d_in.dtype == torch.uint8 and d_in.is_contiguous()
-    cnt = _len(off)
-    assert _len(len) == cnt
-    assert all(int(o) + int(n) <= d_in.numel() for o, n in zip(off, len)), "adler32_batch_tensor: a buffer reaches beyond d_in"
-    torch.cuda.current_stream(d_in.device).synchronize()
-    out = (C.c_uint32 * cnt)()
-    rc = lib().zes_adler32_batch_dev(d_in.data_ptr(), (C.c_uint64 * cnt)(*[int(x) for x in off]), (C.c_uint64 * cnt)(*[int(x) for x in len]), out, cnt)
-    if rc:
-        _raise(rc)
-    return list(out)
+    return _checksum_batch_tensor(lib().zes_adler32_batch_dev, "adler32_batch_tensor", d_in, off, len)
 
 
 def crc32_batch_tensor(d_in, off, len):
     """CRC-32 of every d_in[off[i] : off[i] + len[i]] of a uint8 CUDA tensor, any alignment and length, in one launch
     (zes_crc32_batch_dev); returns a list of ints."""
-    import torch
-
-    assert d_in.is_cuda and d_in.dtype == torch.uint8 and d_in.is_contiguous()
-    cnt = _len(off)
-    assert _len(len) == cnt
-    assert all(int(o) + int(n) <= d_in.numel() for o, n in zip(off, len)), "crc32_batch_tensor: a buffer reaches beyond d_in"
-    torch.cuda.current_stream(d_in.device).synchronize()
-    out = (C.c_uint32 * cnt)()
-    rc = lib().zes_crc32_batch_dev(d_in.data_ptr(), (C.c_uint64 * cnt)(*[int(x) for x in off]), (C.c_uint64 * cnt)(*[int(x) for x in len]), out, cnt)
-    if rc:
-        _raise(rc)
-    return list(out)
+    return _checksum_batch_tensor(lib().zes_crc32_batch_dev, "crc32_batch_tensor", d_in, off, len)
 
 
 def gzip_tensor(t, out=None):
@@ -627,12 +625,7 @@ def bgzip_tensor(t, out=None, flags=0, index=False):
     off = (C.c_uint64 * bgzip_members(t.numel()))()
     n = C.c_uint64()
     rc = lib().zes_bgzip_dev(t.data_ptr() if t.numel() else None, t.numel(), out.data_ptr(), out.numel(), C.byref(n), off, flags)
-    if rc == ZES_E_NOSPACE:
-        err = ZlibEsError(rc, "%s (need %d bytes)" % (strerror(rc), n.value))
-        err.need = n.value
-        raise err
-    if rc:
-        _raise(rc)
+    _raise_need(rc, n)
     return (out[: n.value], list(off)) if index else out[: n.value]
 
 
@@ -645,12 +638,7 @@ def gunzip_tensor(t, out, flags=0):
     torch.cuda.current_stream(t.device).synchronize()
     n = C.c_uint64()
     rc = lib().zes_gunzip_dev(t.data_ptr(), t.numel(), out.data_ptr(), out.numel(), C.byref(n), flags)
-    if rc == ZES_E_NOSPACE:
-        err = ZlibEsError(rc, "%s (need %d bytes)" % (strerror(rc), n.value))
-        err.need = n.value
-        raise err
-    if rc:
-        _raise(rc)
+    _raise_need(rc, n)
     return out[: n.value]
 
 
@@ -676,12 +664,7 @@ def bgzf_read_tensor(t, index, pos, length, out, flags=0):
     n = C.c_uint64()
     rc = lib().zes_bgzf_read_dev(t.data_ptr(), t.numel(), coff.ctypes.data, uoff.ctypes.data, coff.size - 1, pos, length, out.data_ptr(), out.numel(),
                                  C.byref(n), flags)
-    if rc == ZES_E_NOSPACE:
-        err = ZlibEsError(rc, "%s (need %d bytes)" % (strerror(rc), n.value))
-        err.need = n.value
-        raise err
-    if rc:
-        _raise(rc)
+    _raise_need(rc, n)
     return out[: n.value]
 
 

@@ -152,14 +152,14 @@ static_assert(disjoint({PIN_SPAN(t2.search), PIN_SPAN(t2.ncand), PIN_SPAN(t2.nsu
   X(seglive) X(segouts)                                                                                                           \
   /* staging for the host-pointer API */                                                                                          \
   X(st_in) X(st_out)                                                                                                              \
-  /* CRC-32: the kernel's table (x^(8 * 65536 * m) for m < crc_npow) and its two accumulator words; gzip reader: the input  */    \
-  /* (host forms), the result as it grows (host forms) and one member's output when it cannot go to its place directly */         \
-  /* member-parallel gzip reader: the bodies behind their 78 9C, the outputs that cannot go to their places directly, the    */    \
-  /* device tables (members, segments); segmented CRC-32: its buffers, work items and accumulator words.  The BGZF writer   */    \
-  /* uses the same: gz_in and gz_acc for a host call's input and result, gz_bodies for a group's encoder slots, gz_tab for   */    \
-  /* its member records                                                                                                       */    \
+  /* CRC-32: the kernel's table (x^(8 * 65536 * m) for m < crc_npow) and its two accumulator words; gzip reader: the input */     \
+  /* (host forms), the result as it grows (host forms) and one member's output when it cannot go to its place directly; */        \
+  /* member-parallel gzip reader: the bodies behind their 78 9C, the outputs that cannot go to their places directly, the */      \
+  /* device tables (gz_walk_dev's members, gz_gather's segments); crcseg: seg_checksum_locked's segs | work | acc for */          \
+  /* the CRC-32.  The BGZF writer uses the same: gz_in and gz_acc for a host call's input and result, gz_bodies for a */          \
+  /* group's encoder slots, gz_tab for its member records */                                                                      \
   X(crctab) X(crcacc) X(gz_in) X(gz_acc) X(gz_stage) X(gz_bodies) X(gz_outs) X(gz_tab) X(crcseg)                                  \
-  /* segmented Adler-32: its buffers, work items and accumulator words; the trailers of a checked inflate batch */                \
+  /* seg_checksum_locked's segs | work | acc for the Adler-32; the gathered trailers of a checked inflate batch */                \
   X(adlerseg)
 
 // The survivor list of the block-start search as the block-parallel tier's scan left it in a pool (one buffer): the
@@ -738,6 +738,12 @@ void collect_times() {
   g.carry.clear();
   for (auto& n : order)
     if (acc.count(n)) g.last_times.push_back({n, acc[n]});
+}
+
+// The call's report keeps what a driver in front (inflate_jobs, deflate_batch_core) has collected already: the call's last
+// collect_times puts it in front of the launches that follow
+void keep_times() {
+  if (g.profiling) g.carry = g.last_times;
 }
 
 // ---- deflate ----
@@ -2685,112 +2691,151 @@ int inflate_one(const uint8_t* d_in, uint64_t in_off, uint64_t c, uint8_t* d_out
 }
 
 int adler32_locked(const uint8_t* d_in, uint64_t n, uint32_t* adler_out);
+int adler32_batch_locked(const uint8_t* d, const ZesCrcSeg* segs, uint32_t count, uint32_t* adler);
 
-// ZES_F_CHECK_ADLER: the 4 bytes behind the stream (end_bit: relative to the zlib header's first byte) must exist and hold
-// the Adler-32 of the n result bytes at d_res, big-endian.  The stream's bytes are at h_in (host) or d_in (device).
+uint32_t get_le32(const uint8_t* p) { return (uint32_t)p[0] | (uint32_t)p[1] << 8 | (uint32_t)p[2] << 16 | (uint32_t)p[3] << 24; }
+uint32_t get_be32(const uint8_t* p) { return (uint32_t)p[0] << 24 | (uint32_t)p[1] << 16 | (uint32_t)p[2] << 8 | p[3]; }
+
+// segs[i].len bytes from src + src_off to dst + dst_off for every i, in one launch (k_gz_gather); the table goes through g.gz_tab
+int gz_gather(const uint8_t* src, uint8_t* dst, const std::vector<ZesGzSeg>& segs) {
+  if (segs.empty()) return ZES_OK;
+  int rc;
+  uint64_t longest = 0;
+  for (const ZesGzSeg& s : segs) longest = std::max(longest, s.len);
+  if ((rc = ensure(g.gz_tab, sizeof(ZesGzSeg) * segs.size()))) return rc;
+  HIPCHK(hipMemcpyAsync(g.gz_tab.p, segs.data(), sizeof(ZesGzSeg) * segs.size(), hipMemcpyHostToDevice, g.stream));
+  const uint32_t ny = (uint32_t)std::min<uint64_t>(std::max<uint64_t>((longest + GZ_GATHER_PIECE - 1) / GZ_GATHER_PIECE, 1), 256);
+  Timed t("k_gz_gather");
+  hipLaunchKernelGGL(k_gz_gather, dim3((uint32_t)segs.size(), ny), dim3(GZ_GATHER_THREADS), 0, g.stream, src, dst, (const ZesGzSeg*)g.gz_tab.p);
+  HIPCHK(hipGetLastError());
+  return ZES_OK;
+}
+
+// ---- BGZF members: the rule, and the walk over a file on the host and on the device ----
+// One member at h[0, avail) of a file with `left` bytes from its start on: does it qualify, and what does it say
+// (the rule of k_gz_walk, which does the same on the device)
+bool gz_member(const uint8_t* h, uint64_t avail, uint64_t left, ZesGzMember* m) {
+  if (avail < 12 || h[0] != 0x1f || h[1] != 0x8b || h[2] != 8 || h[3] != 4) return false;
+  const uint32_t hlen = 12 + ((uint32_t)h[10] | (uint32_t)h[11] << 8);
+  if (hlen > ZES_GZ_HLEN_MAX || hlen > avail) return false;
+  uint32_t p = 12, size = 0;
+  while (p + 4 <= hlen) {
+    const uint32_t sl = (uint32_t)h[p + 2] | (uint32_t)h[p + 3] << 8;
+    if (p + 4 + sl > hlen) break;
+    if (!size && h[p] == 'B' && h[p + 1] == 'C' && sl == 2) size = ((uint32_t)h[p + 4] | (uint32_t)h[p + 5] << 8) + 1;
+    p += 4 + sl;
+  }
+  if (p != hlen || !size || hlen + 8 > size || size > left) return false;
+  m->size = size;
+  m->hlen = hlen;
+  return true;
+}
+
+// The members of the file h[0, c) from byte 0 on, each one to each(pos, member); true when they reach the file's end
+template <class F>
+bool gz_walk_host(const uint8_t* h, uint64_t c, F each) {
+  for (uint64_t pos = 0; pos < c;) {
+    ZesGzMember m;
+    if (!gz_member(h + pos, c - pos, c - pos, &m)) return false;
+    each(pos, m);
+    pos += m.size;
+  }
+  return true;
+}
+
+// The same on the device (k_gz_walk, one wave).  Precondition: gz_walk_room(cap) has succeeded, so that g.gz_tab holds the head
+// and a table of `cap` members (sizing is the caller's statement: a table that cannot be sized means "not applicable" to
+// one caller and an error to the other).  The head comes down, and the table (head.count members) when accept(head) says
+// so; else tab stays empty.
+int gz_walk_room(uint64_t cap) { return ensure(g.gz_tab, sizeof(ZesGzWalk) + sizeof(ZesGzMember) * (size_t)cap); }
+template <class F>
+int gz_walk_dev(const uint8_t* d, uint64_t c, uint32_t cap, F accept, std::vector<ZesGzMember>& tab) {
+  tab.clear();
+  ZesGzWalk head;
+  ZesGzWalk* d_head = (ZesGzWalk*)g.gz_tab.p;
+  {
+    Timed t("k_gz_walk");
+    hipLaunchKernelGGL(k_gz_walk, dim3(1), dim3(64), 0, g.stream, d, c, d_head, (ZesGzMember*)(d_head + 1), cap);
+  }
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipMemcpyAsync(&head, d_head, sizeof head, hipMemcpyDeviceToHost, g.stream));
+  HIPCHK(hipStreamSynchronize(g.stream));
+  if (!accept(head)) return ZES_OK;
+  tab.resize(head.count);
+  HIPCHK(hipMemcpyAsync(tab.data(), d_head + 1, sizeof(ZesGzMember) * tab.size(), hipMemcpyDeviceToHost, g.stream));
+  HIPCHK(hipStreamSynchronize(g.stream));
+  return ZES_OK;
+}
+
+// the segments gathered into `pool` and brought down: `bytes` in all at h_dst (no segments: nothing happens)
+int gather_down(DevBuf& pool, const uint8_t* src, const std::vector<ZesGzSeg>& segs, uint8_t* h_dst, size_t bytes) {
+  if (segs.empty()) return ZES_OK;
+  int rc;
+  if ((rc = ensure(pool, bytes))) return rc;
+  if ((rc = gz_gather(src, (uint8_t*)pool.p, segs))) return rc;
+  HIPCHK(hipMemcpyAsync(h_dst, pool.p, bytes, hipMemcpyDeviceToHost, g.stream));
+  HIPCHK(hipStreamSynchronize(g.stream));
+  return ZES_OK;
+}
+
+// ZES_F_CHECK_ADLER: the Adler-32 trailer of a zlib stream of c bytes whose final block ends at bit end_bit (relative to the
+// header's first byte) is the 4 bytes from *t on, big-endian; false when they are not all there
+bool adler_trailer_at(uint64_t end_bit, uint64_t c, uint64_t* t) {
+  *t = (end_bit + 7) / 8;
+  return end_bit >= 16 && *t + 4 <= c;
+}
+
+// ZES_F_CHECK_ADLER of one stream: its trailer must exist and hold the Adler-32 of the n result bytes at d_res.  The
+// stream's bytes are at h_in (host) or d_in (device).
 int check_adler_trailer(const uint8_t* h_in, const uint8_t* d_in, uint64_t c, uint64_t end_bit, const uint8_t* d_res, uint64_t n) {
-  const uint64_t t = (end_bit + 7) / 8;
-  if (end_bit < 16 || t + 4 > c) return ZES_E_CHECKSUM;
+  uint64_t t;
+  if (!adler_trailer_at(end_bit, c, &t)) return ZES_E_CHECKSUM;
   uint8_t b[4];
   if (h_in) memcpy(b, h_in + t, 4);
   else HIPCHK(hipMemcpy(b, d_in + t, 4, hipMemcpyDeviceToHost));
   uint32_t ad = 0;
   int rc = adler32_locked(d_res, n, &ad);
   if (rc) return rc;
-  return ad == ((uint32_t)b[0] << 24 | (uint32_t)b[1] << 16 | (uint32_t)b[2] << 8 | b[3]) ? ZES_OK : ZES_E_CHECKSUM;
+  return ad == get_be32(b) ? ZES_OK : ZES_E_CHECKSUM;
 }
 
-// Segmented Adler-32 (k_adler_seg): adler[i] of d[segs[i].off, + segs[i].len) for all i in one launch and one read-back.
-// The work items are (buffer, 64 KiB chunk of memory) pairs, listed here from the lengths exactly as the kernel cuts a
-// buffer; the kernel leaves two sums per buffer, finished here as k_layout finishes k_adler's.
-int adler32_batch_locked(const uint8_t* d, const ZesCrcSeg* segs, uint32_t count, uint32_t* adler) {
-  int rc;
-  struct Item {
-    uint32_t buf, chunk;
-  };
-  std::vector<Item> work;
-  work.reserve(count);
-  for (uint32_t i = 0; i < count; i++) {
-    adler[i] = 1;  // (of no bytes)
-    if (!segs[i].len) continue;
-    const uint64_t a = (uint64_t)(uintptr_t)d + segs[i].off, end = a + segs[i].len;
-    const uint64_t nch = (((end + 15) & ~(uint64_t)15) - (a & ~(uint64_t)15) + ADLER_CHUNK - 1) / ADLER_CHUNK;
-    if (work.size() + nch >= (1ull << 31)) return ZES_E_ARG;
-    for (uint64_t j = 0; j < nch; j++) work.push_back({i, (uint32_t)j});
-  }
-  if (work.empty()) return ZES_OK;
-  const size_t o_work = sizeof(ZesCrcSeg) * (size_t)count, o_acc = o_work + sizeof(Item) * work.size();
-  if ((rc = ensure(g.adlerseg, o_acc + 16 * (size_t)count))) return rc;
-  uint8_t* base = (uint8_t*)g.adlerseg.p;
-  HIPCHK(hipMemcpyAsync(base, segs, o_work, hipMemcpyHostToDevice, g.stream));
-  HIPCHK(hipMemcpyAsync(base + o_work, work.data(), sizeof(Item) * work.size(), hipMemcpyHostToDevice, g.stream));
-  HIPCHK(hipMemsetAsync(base + o_acc, 0, 16 * (size_t)count, g.stream));
-  {
-    Timed t("k_adler_seg");
-    hipLaunchKernelGGL(k_adler_seg, dim3((uint32_t)work.size()), dim3(ADLER_THREADS), 0, g.stream, d, (const ZesCrcSeg*)base, (const uint2*)(base + o_work),
-                       (unsigned long long*)(base + o_acc));
-  }
-  HIPCHK(hipGetLastError());
-  std::vector<unsigned long long> acc(2 * (size_t)count);
-  HIPCHK(hipMemcpyAsync(acc.data(), base + o_acc, 16 * (size_t)count, hipMemcpyDeviceToHost, g.stream));
-  HIPCHK(hipStreamSynchronize(g.stream));
-  for (uint32_t i = 0; i < count; i++) {
-    const uint32_t s1 = (uint32_t)((1ull + acc[2 * (size_t)i]) % 65521ull);
-    const uint32_t s2 = (uint32_t)((segs[i].len % 65521ull + acc[2 * (size_t)i + 1]) % 65521ull);
-    adler[i] = (s2 << 16) | s1;
-  }
-  return ZES_OK;
-}
-
-// ZES_F_CHECK_ADLER for the jobs of one inflate_jobs call that had want_end set: every job that ended ZES_OK must have its
-// 4 trailer bytes and they must hold the Adler-32 of its output (big-endian), else its status becomes ZES_E_CHECKSUM.  Two
-// steps: the trailers of all such jobs come back in one go (h_in[k], the job's stream in the caller's memory, when
-// given; else one k_gz_gather launch of 4-byte segments out of d_in and one read-back), then one k_adler_seg launch runs
-// over their outputs.  A job with any other status keeps it, and a job whose trailer is cut short costs no launch.
+// ZES_F_CHECK_ADLER for the jobs of the inflate_jobs call in front that had want_end set.  Of those that ended ZES_OK: their
+// trailers (the streams in the caller's memory at h_in[k] when given, else inside d_in: one gather of 4-byte segments into
+// g.adlerseg and one read-back) against the Adler-32 of their outputs (one k_adler_seg launch).  A job that fails gets
+// ZES_E_CHECKSUM; any other status stays, and a job whose trailer is cut short costs no launch.  The launches of both
+// calls show in the call's times.
 int check_adler_jobs(const uint8_t* d_in, const uint8_t* const* h_in, const uint8_t* d_out, std::vector<InfJob>& jobs) {
-  int rc;
+  keep_times();
   std::vector<uint32_t> who;
-  std::vector<uint64_t> at;  // the trailer's place in the job's stream
+  std::vector<ZesGzSeg> segs;  // the trailers: from the job's stream to 4 bytes each, in the order of `who`
   for (uint32_t k = 0; k < jobs.size(); k++) {
     InfJob& j = jobs[k];
     if (j.status != ZES_OK) continue;
-    const uint64_t t = (j.end_bit + 7) / 8;
-    if (j.end_bit < 16 || t + 4 > j.c) {
+    uint64_t t;
+    if (!adler_trailer_at(j.end_bit, j.c, &t)) {
       j.status = ZES_E_CHECKSUM;
       continue;
     }
+    segs.push_back(ZesGzSeg{t, 4 * who.size(), 4, 0u, 0u});
     who.push_back(k);
-    at.push_back(t);
   }
-  if (who.empty()) return ZES_OK;
   const size_t n = who.size();
   std::vector<uint8_t> trail(4 * n);
+  int rc = ZES_OK;
   if (h_in) {
-    for (size_t q = 0; q < n; q++) memcpy(&trail[4 * q], h_in[who[q]] + at[q], 4);
+    for (size_t q = 0; q < n; q++) memcpy(&trail[4 * q], h_in[who[q]] + segs[q].src_off, 4);
   } else {
-    std::vector<ZesGzSeg> segs(n);
-    const size_t o_dst = (sizeof(ZesGzSeg) * n + 15) & ~(size_t)15;
-    for (size_t q = 0; q < n; q++) segs[q] = ZesGzSeg{jobs[who[q]].in_off + at[q], o_dst + 4 * q, 4, 0u, 0u};
-    if ((rc = ensure(g.adlerseg, o_dst + 4 * n))) return rc;
-    HIPCHK(hipMemcpyAsync(g.adlerseg.p, segs.data(), sizeof(ZesGzSeg) * n, hipMemcpyHostToDevice, g.stream));
-    {
-      Timed tm("k_gz_gather");
-      hipLaunchKernelGGL(k_gz_gather, dim3((uint32_t)n, 1), dim3(GZ_GATHER_THREADS), 0, g.stream, d_in, (uint8_t*)g.adlerseg.p,
-                         (const ZesGzSeg*)g.adlerseg.p);
-    }
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(trail.data(), (const uint8_t*)g.adlerseg.p + o_dst, 4 * n, hipMemcpyDeviceToHost, g.stream));
-    HIPCHK(hipStreamSynchronize(g.stream));
+    for (size_t q = 0; q < n; q++) segs[q].src_off += jobs[who[q]].in_off;
+    rc = gather_down(g.adlerseg, d_in, segs, trail.data(), trail.size());
   }
   std::vector<ZesCrcSeg> csegs(n);
   for (size_t q = 0; q < n; q++) csegs[q] = ZesCrcSeg{jobs[who[q]].out_len ? jobs[who[q]].out_off : 0, jobs[who[q]].out_len};
   std::vector<uint32_t> ad(n);
-  if ((rc = adler32_batch_locked(d_out, csegs.data(), (uint32_t)n, ad.data()))) return rc;
-  for (size_t q = 0; q < n; q++) {
-    const uint8_t* b = &trail[4 * q];
-    if (ad[q] != ((uint32_t)b[0] << 24 | (uint32_t)b[1] << 16 | (uint32_t)b[2] << 8 | b[3])) jobs[who[q]].status = ZES_E_CHECKSUM;
-  }
-  return ZES_OK;
+  if (!rc && !(rc = adler32_batch_locked(d_out, csegs.data(), (uint32_t)n, ad.data())))
+    for (size_t q = 0; q < n; q++)
+      if (ad[q] != get_be32(&trail[4 * q])) jobs[who[q]].status = ZES_E_CHECKSUM;
+  collect_times();
+  return rc;
 }
 
 }  // namespace
@@ -3132,10 +3177,7 @@ int zes_inflate_batch_dev(const uint8_t* d_in, const uint64_t* in_off, const uin
   rc = inflate_jobs(d_in, d_out, jobs, nullptr, flags & ~ZES_F_CHECK_ADLER);  // the first bytes (CM nibble, src/zlib.ts:13) are read on the way
   if (rc) return rc;
   if (check) {
-    if (g.profiling) g.carry = g.last_times;  // (inflate_jobs has collected what ran so far: the call's last collect_times keeps it)
-    rc = check_adler_jobs(d_in, nullptr, d_out, jobs);
-    collect_times();
-    if (rc) return rc;
+    if ((rc = check_adler_jobs(d_in, nullptr, d_out, jobs))) return rc;
   }
   for (uint32_t i = 0; i < count; i++) {
     status[i] = jobs[i].status;
@@ -3423,10 +3465,7 @@ static int inflate_batch_alloc_one(const uint8_t* const* in, const uint64_t* in_
     if ((rc = ensure(g.st_out, tout + 64))) return rc;
     if ((rc = inflate_jobs((const uint8_t*)g.st_in.p, (uint8_t*)g.st_out.p, jobs, fb.data(), flags & ~ZES_F_CHECK_ADLER))) return rc;
     if (check) {  // the buffers that finished in this attempt, before any of them is handed out
-      if (g.profiling) g.carry = g.last_times;  // (inflate_jobs has collected what ran so far)
-      rc = check_adler_jobs(nullptr, hin.data(), (const uint8_t*)g.st_out.p, jobs);
-      collect_times();
-      if (rc) return rc;
+      if ((rc = check_adler_jobs(nullptr, hin.data(), (const uint8_t*)g.st_out.p, jobs))) return rc;
     }
     std::vector<uint32_t> again;
     for (size_t k = 0; k < todo.size(); k++) {
@@ -3852,87 +3891,137 @@ int zes_crc32(const uint8_t* in, uint64_t n, uint32_t* crc) {
   return rc;
 }
 
-// Segmented CRC-32 (k_crc32_seg): crc[i] of d[segs[i].off, + segs[i].len) for all i in one launch.  The work items are
-// (buffer, 64 KiB chunk of memory) pairs, listed here from the lengths exactly as the kernel cuts a buffer; the kernel
-// leaves two words per buffer, finished here (two GF(2) multiplies per buffer; the powers are kept per length, a batch
-// of BGZF members has two or three different ones).
-static int crc32_batch_locked(const uint8_t* d, const ZesCrcSeg* segs, uint32_t count, uint32_t* crc) {
+}  // extern "C" (a template has C++ linkage)
+// ---- segmented checksums (k_crc32_seg, k_adler_seg) ----
+// out[i] = the checksum of d[segs[i].off, + segs[i].len) for all i, in one launch and one read-back.  The work items are
+// (buffer, 64 KiB chunk of memory) pairs, listed here from the lengths exactly as the kernel cuts a buffer; the kernel leaves
+// two accumulator words per buffer, finished here.  The pool holds segs | work | acc.  What differs between the checksums
+// is in the description S:
+//   Word, EMPTY, NAME  an accumulator word, the checksum of no bytes, the launch's name in the times
+//   pool()             the pool
+//   chunks(a, end)     the work items of a buffer at the addresses [a, end), a < end
+//   ready(maxlen)      what the launch needs beside the pool, for buffers of up to maxlen bytes
+//   launch(...)        the kernel over `items` work items
+//   finish(a, end, w)  the buffer's checksum from its two words
+namespace {
+template <class S>
+int seg_checksum_locked(S ck, const uint8_t* d, const ZesCrcSeg* segs, uint32_t count, uint32_t* out) {
+  using Word = typename S::Word;
   int rc;
-  struct Item {
-    uint32_t buf, chunk;
-  };
-  std::vector<Item> work;
-  std::vector<uint64_t> last(count);  // bytes of a buffer's last work item
+  std::vector<uint2> work;  // (buffer, chunk)
   work.reserve(count);
   uint64_t maxlen = 0;
   for (uint32_t i = 0; i < count; i++) {
+    out[i] = S::EMPTY;
     if (!segs[i].len) continue;
-    const uint64_t a = (uint64_t)(uintptr_t)d + segs[i].off, end = a + segs[i].len;
-    const uint64_t A = a & ~(uint64_t)15, E = std::max<uint64_t>(end & ~(uint64_t)15, a);
-    const uint64_t nch = E > a ? (E - A + CRC_CHUNK - 1) / CRC_CHUNK : 1;
+    const uint64_t a = (uint64_t)(uintptr_t)d + segs[i].off, nch = S::chunks(a, a + segs[i].len);
     if (work.size() + nch >= (1ull << 31)) return ZES_E_ARG;
-    for (uint64_t j = 0; j < nch; j++) work.push_back({i, (uint32_t)j});
-    last[i] = end - std::max<uint64_t>(a, A + (nch - 1) * CRC_CHUNK);
+    for (uint64_t j = 0; j < nch; j++) work.push_back(make_uint2(i, (uint32_t)j));
     maxlen = std::max(maxlen, segs[i].len);
   }
-  for (uint32_t i = 0; i < count; i++) crc[i] = 0;  // (of no bytes)
   if (work.empty()) return ZES_OK;
-  if ((rc = crc_ready(maxlen + 2 * CRC_CHUNK))) return rc;
-  const size_t o_work = sizeof(ZesCrcSeg) * (size_t)count, o_acc = o_work + sizeof(Item) * work.size();
-  if ((rc = ensure(g.crcseg, o_acc + 8 * (size_t)count))) return rc;
-  uint8_t* base = (uint8_t*)g.crcseg.p;
+  if ((rc = ck.ready(maxlen))) return rc;
+  const size_t o_work = sizeof(ZesCrcSeg) * (size_t)count, o_acc = o_work + sizeof(uint2) * work.size(), n_acc = 2 * sizeof(Word) * (size_t)count;
+  if ((rc = ensure(S::pool(), o_acc + n_acc))) return rc;
+  uint8_t* base = (uint8_t*)S::pool().p;
   HIPCHK(hipMemcpyAsync(base, segs, o_work, hipMemcpyHostToDevice, g.stream));
-  HIPCHK(hipMemcpyAsync(base + o_work, work.data(), sizeof(Item) * work.size(), hipMemcpyHostToDevice, g.stream));
-  HIPCHK(hipMemsetAsync(base + o_acc, 0, 8 * (size_t)count, g.stream));
+  HIPCHK(hipMemcpyAsync(base + o_work, work.data(), sizeof(uint2) * work.size(), hipMemcpyHostToDevice, g.stream));
+  HIPCHK(hipMemsetAsync(base + o_acc, 0, n_acc, g.stream));
   {
-    Timed t("k_crc32_seg");
-    hipLaunchKernelGGL(k_crc32_seg, dim3((uint32_t)work.size()), dim3(CRC_THREADS), 0, g.stream, d, (const ZesCrcSeg*)base, (const uint2*)(base + o_work),
-                       (const uint32_t*)g.crctab.p, (unsigned int*)(base + o_acc));
+    Timed t(S::NAME);
+    ck.launch((uint32_t)work.size(), d, (const ZesCrcSeg*)base, (const uint2*)(base + o_work), (Word*)(base + o_acc));
   }
   HIPCHK(hipGetLastError());
-  std::vector<uint32_t> acc(2 * (size_t)count);
-  HIPCHK(hipMemcpyAsync(acc.data(), base + o_acc, 8 * (size_t)count, hipMemcpyDeviceToHost, g.stream));
+  std::vector<Word> acc(2 * (size_t)count);
+  HIPCHK(hipMemcpyAsync(acc.data(), base + o_acc, n_acc, hipMemcpyDeviceToHost, g.stream));
   HIPCHK(hipStreamSynchronize(g.stream));
-  std::map<uint64_t, uint32_t> pw;  // x^(8k)
-  auto shift = [&](uint32_t v, uint64_t k) {
-    auto it = pw.find(k);
-    if (it == pw.end()) it = pw.emplace(k, zes_crc_shift(0x80000000u, k)).first;
-    return zes_crc_mul(it->second, v);
-  };
   for (uint32_t i = 0; i < count; i++) {
     if (!segs[i].len) continue;
-    const uint32_t raw = shift(acc[2 * (size_t)i], last[i]) ^ acc[2 * (size_t)i + 1];
-    crc[i] = raw ^ shift(0xFFFFFFFFu, segs[i].len) ^ 0xFFFFFFFFu;
+    const uint64_t a = (uint64_t)(uintptr_t)d + segs[i].off;
+    out[i] = ck.finish(a, a + segs[i].len, &acc[2 * (size_t)i]);
   }
   return ZES_OK;
 }
 
-int zes_crc32_batch_dev(const uint8_t* d_in, const uint64_t* off, const uint64_t* len, uint32_t* crc, uint32_t count) {
+// CRC-32: chunk j of a buffer holds [max(a, A + 64Ki * j), min(E, A + 64Ki * (j + 1))), A = a rounded down to 16, E = the end
+// rounded down to 16 (a, when that lies in front of a), the last one also [E, end): at least one item.  Word 0 is shifted
+// by the last item's bytes (two GF(2) multiplies per buffer; the powers are kept per length, a batch of BGZF members has
+// two or three different ones).
+struct CrcSeg {
+  using Word = unsigned int;
+  static constexpr uint32_t EMPTY = 0;
+  static constexpr const char* NAME = "k_crc32_seg";
+  static DevBuf& pool() { return g.crcseg; }
+  static uint64_t chunks(uint64_t a, uint64_t end) {
+    const uint64_t A = a & ~(uint64_t)15, E = std::max<uint64_t>(end & ~(uint64_t)15, a);
+    return E > a ? (E - A + CRC_CHUNK - 1) / CRC_CHUNK : 1;
+  }
+  int ready(uint64_t maxlen) { return crc_ready(maxlen + 2 * CRC_CHUNK); }
+  void launch(uint32_t items, const uint8_t* d, const ZesCrcSeg* segs, const uint2* work, Word* acc) {
+    hipLaunchKernelGGL(k_crc32_seg, dim3(items), dim3(CRC_THREADS), 0, g.stream, d, segs, work, (const uint32_t*)g.crctab.p, acc);
+  }
+  std::map<uint64_t, uint32_t> pw;  // x^(8k)
+  uint32_t shift(uint32_t v, uint64_t k) {
+    auto it = pw.find(k);
+    if (it == pw.end()) it = pw.emplace(k, zes_crc_shift(0x80000000u, k)).first;
+    return zes_crc_mul(it->second, v);
+  }
+  uint32_t finish(uint64_t a, uint64_t end, const Word* w) {
+    const uint64_t last = end - std::max<uint64_t>(a, (a & ~(uint64_t)15) + (chunks(a, end) - 1) * CRC_CHUNK);
+    return shift(w[0], last) ^ w[1] ^ shift(0xFFFFFFFFu, end - a) ^ 0xFFFFFFFFu;
+  }
+};
+
+// Adler-32: chunk j holds the bytes of [a, end) inside [G + 64Ki * j, G + 64Ki * (j + 1)), G = a rounded down to 16; the two
+// sums are finished as k_layout finishes k_adler's.
+struct AdlerSeg {
+  using Word = unsigned long long;
+  static constexpr uint32_t EMPTY = 1;
+  static constexpr const char* NAME = "k_adler_seg";
+  static DevBuf& pool() { return g.adlerseg; }
+  static uint64_t chunks(uint64_t a, uint64_t end) { return (((end + 15) & ~(uint64_t)15) - (a & ~(uint64_t)15) + ADLER_CHUNK - 1) / ADLER_CHUNK; }
+  int ready(uint64_t) { return ZES_OK; }
+  void launch(uint32_t items, const uint8_t* d, const ZesCrcSeg* segs, const uint2* work, Word* acc) {
+    hipLaunchKernelGGL(k_adler_seg, dim3(items), dim3(ADLER_THREADS), 0, g.stream, d, segs, work, acc);
+  }
+  uint32_t finish(uint64_t a, uint64_t end, const Word* w) {
+    const uint32_t s1 = (uint32_t)((1ull + w[0]) % 65521ull), s2 = (uint32_t)(((end - a) % 65521ull + w[1]) % 65521ull);
+    return (s2 << 16) | s1;
+  }
+};
+
+int crc32_batch_locked(const uint8_t* d, const ZesCrcSeg* segs, uint32_t count, uint32_t* crc) {
+  return seg_checksum_locked(CrcSeg(), d, segs, count, crc);
+}
+
+int adler32_batch_locked(const uint8_t* d, const ZesCrcSeg* segs, uint32_t count, uint32_t* adler) {
+  return seg_checksum_locked(AdlerSeg(), d, segs, count, adler);
+}
+}  // namespace
+extern "C" {
+
+// zes_crc32_batch_dev, zes_adler32_batch_dev: the argument checks, the buffers as ZesCrcSeg, the call's times
+static int checksum_batch_dev(int (*batch)(const uint8_t*, const ZesCrcSeg*, uint32_t, uint32_t*), const uint8_t* d_in, const uint64_t* off,
+                              const uint64_t* len, uint32_t* out, uint32_t count) {
   ROUTE_DEV(d_in);
-  if (count && (!off || !len || !crc)) return ZES_E_ARG;
+  if (count && (!off || !len || !out)) return ZES_E_ARG;
   LOCK_READY();
   std::vector<ZesCrcSeg> segs(count);
   for (uint32_t i = 0; i < count; i++) {
     if (len[i] && !d_in) return ZES_E_ARG;
     segs[i] = ZesCrcSeg{off[i], len[i]};
   }
-  rc = crc32_batch_locked(d_in, segs.data(), count, crc);
+  rc = batch(d_in, segs.data(), count, out);
   collect_times();
   return rc;
 }
 
+int zes_crc32_batch_dev(const uint8_t* d_in, const uint64_t* off, const uint64_t* len, uint32_t* crc, uint32_t count) {
+  return checksum_batch_dev(crc32_batch_locked, d_in, off, len, crc, count);
+}
+
 int zes_adler32_batch_dev(const uint8_t* d_in, const uint64_t* off, const uint64_t* len, uint32_t* adler, uint32_t count) {
-  ROUTE_DEV(d_in);
-  if (count && (!off || !len || !adler)) return ZES_E_ARG;
-  LOCK_READY();
-  std::vector<ZesCrcSeg> segs(count);
-  for (uint32_t i = 0; i < count; i++) {
-    if (len[i] && !d_in) return ZES_E_ARG;
-    segs[i] = ZesCrcSeg{off[i], len[i]};
-  }
-  rc = adler32_batch_locked(d_in, segs.data(), count, adler);
-  collect_times();
-  return rc;
+  return checksum_batch_dev(adler32_batch_locked, d_in, off, len, adler, count);
 }
 
 // ---- gzip writer (RFC 1952): fixed header | zes_deflate_raw's bytes | CRC-32, ISIZE ----
@@ -3941,7 +4030,6 @@ static uint64_t gzip_bound(uint64_t n) { return deflate_bound(n) - 6 + 18; }
 static void put_le32(uint8_t* p, uint32_t v) {
   for (int k = 0; k < 4; k++) p[k] = (uint8_t)(v >> (8 * k));
 }
-static uint32_t get_le32(const uint8_t* p) { return (uint32_t)p[0] | (uint32_t)p[1] << 8 | (uint32_t)p[2] << 16 | (uint32_t)p[3] << 24; }
 
 // the body into g.st_out + 2 (as zes_deflate_raw does); the input's CRC-32 runs on the second stream beside the deflate
 // kernels, as the Adler-32 pass does
@@ -4053,7 +4141,7 @@ static int bgzip_core(const uint8_t* d_in, uint64_t n, uint8_t* d_out, uint64_t 
       if ((rc = crc32_batch_locked(d_in, csegs.data(), cnt, crc.data()))) return rc;
       if ((rc = deflate_batch_core(d_in, in_off.data(), in_len.data(), (uint8_t*)g.gz_bodies.p, o_off.data(), o_cap.data(), o_len.data(), status.data(), cnt)))
         return rc;
-      if (g.profiling) g.carry = g.last_times;  // (deflate_batch_core has collected what ran so far: the call's last collect_times keeps it)
+      keep_times();
     }
     for (uint32_t k = 0; k < cnt; k++) {
       const uint32_t len = (uint32_t)in_len[k];
@@ -4276,39 +4364,17 @@ static int gunzip_locked(GzSrc& S, uint64_t hlen, bool dev, uint8_t* d_dst, uint
 }
 
 // ---- the member-parallel reader (include/zes.h: "Member-parallel reading") ----
-// One member at h[0, avail) of a file with `left` bytes from its start on: does it qualify, and what does it say
-// (the rule of k_gz_walk, which does the same on the device)
-static bool gz_member(const uint8_t* h, uint64_t avail, uint64_t left, ZesGzMember* m) {
-  if (avail < 12 || h[0] != 0x1f || h[1] != 0x8b || h[2] != 8 || h[3] != 4) return false;
-  const uint32_t hlen = 12 + ((uint32_t)h[10] | (uint32_t)h[11] << 8);
-  if (hlen > ZES_GZ_HLEN_MAX || hlen > avail) return false;
-  uint32_t p = 12, size = 0;
-  while (p + 4 <= hlen) {
-    const uint32_t sl = (uint32_t)h[p + 2] | (uint32_t)h[p + 3] << 8;
-    if (p + 4 + sl > hlen) break;
-    if (!size && h[p] == 'B' && h[p + 1] == 'C' && sl == 2) size = ((uint32_t)h[p + 4] | (uint32_t)h[p + 5] << 8) + 1;
-    p += 4 + sl;
-  }
-  if (p != hlen || !size || hlen + 8 > size || size > left) return false;
-  m->size = size;
-  m->hlen = hlen;
-  return true;
-}
-
 // the members of the input when it is such a file from its first byte to its last (*ok), else nothing
 static int gz_walk(GzSrc& S, std::vector<ZesGzMember>& tab, bool* ok) {
   *ok = false;
   tab.clear();
   if (S.h) {  // the caller's memory
-    for (uint64_t pos = 0; pos < S.c;) {
-      ZesGzMember m;
-      if (!gz_member(S.h + pos, S.c - pos, S.c - pos, &m)) return ZES_OK;
+    const bool whole = gz_walk_host(S.h, S.c, [&](uint64_t pos, ZesGzMember m) {
       m.crc = get_le32(S.h + pos + m.size - 8);
       m.isize = get_le32(S.h + pos + m.size - 4);
       tab.push_back(m);
-      pos += m.size;
-    }
-    *ok = tab.size() >= 2;
+    });
+    *ok = whole && tab.size() >= 2;
     return ZES_OK;
   }
   int rc;
@@ -4319,35 +4385,9 @@ static int gz_walk(GzSrc& S, std::vector<ZesGzMember>& tab, bool* ok) {
   if (!gz_member(p, k, S.c, &m0) || m0.size >= S.c) return ZES_OK;  // an ordinary gzip file: no launch, no table
   // the table's size: members as long as the first one, four times over (a file of shorter ones goes member by member)
   const uint32_t cap = (uint32_t)std::min<uint64_t>({S.c / 28 + 1, 4 * (S.c / m0.size) + 1024, (uint64_t)1 << 28});
-  if (ensure(g.gz_tab, sizeof(ZesGzWalk) + sizeof(ZesGzMember) * (size_t)cap)) return ZES_OK;
-  ZesGzWalk* d_head = (ZesGzWalk*)g.gz_tab.p;
-  {
-    Timed t("k_gz_walk");
-    hipLaunchKernelGGL(k_gz_walk, dim3(1), dim3(64), 0, g.stream, S.d, S.c, d_head, (ZesGzMember*)(d_head + 1), cap);
-  }
-  HIPCHK(hipGetLastError());
-  ZesGzWalk head;
-  HIPCHK(hipMemcpyAsync(&head, d_head, sizeof head, hipMemcpyDeviceToHost, g.stream));
-  HIPCHK(hipStreamSynchronize(g.stream));
-  if (!head.ok || head.count < 2 || head.count > cap) return ZES_OK;
-  tab.resize(head.count);
-  HIPCHK(hipMemcpyAsync(tab.data(), d_head + 1, sizeof(ZesGzMember) * tab.size(), hipMemcpyDeviceToHost, g.stream));
-  HIPCHK(hipStreamSynchronize(g.stream));
-  *ok = true;
-  return ZES_OK;
-}
-
-static int gz_gather(const uint8_t* src, uint8_t* dst, const std::vector<ZesGzSeg>& segs) {
-  if (segs.empty()) return ZES_OK;
-  int rc;
-  uint64_t longest = 0;
-  for (const ZesGzSeg& s : segs) longest = std::max(longest, s.len);
-  if ((rc = ensure(g.gz_tab, sizeof(ZesGzSeg) * segs.size()))) return rc;
-  HIPCHK(hipMemcpyAsync(g.gz_tab.p, segs.data(), sizeof(ZesGzSeg) * segs.size(), hipMemcpyHostToDevice, g.stream));
-  const uint32_t ny = (uint32_t)std::min<uint64_t>(std::max<uint64_t>((longest + GZ_GATHER_PIECE - 1) / GZ_GATHER_PIECE, 1), 256);
-  Timed t("k_gz_gather");
-  hipLaunchKernelGGL(k_gz_gather, dim3((uint32_t)segs.size(), ny), dim3(GZ_GATHER_THREADS), 0, g.stream, src, dst, (const ZesGzSeg*)g.gz_tab.p);
-  HIPCHK(hipGetLastError());
+  if (gz_walk_room(cap)) return ZES_OK;
+  if ((rc = gz_walk_dev(S.d, S.c, cap, [&](const ZesGzWalk& w) { return w.ok && w.count >= 2 && w.count <= cap; }, tab))) return rc;
+  *ok = !tab.empty();
   return ZES_OK;
 }
 
@@ -4416,7 +4456,7 @@ static int gz_decode_batch(const uint8_t* d_src, const std::vector<GzPart>& ps, 
   const std::vector<uint8_t> firsts(n, 0x78);
   if (stamps) stamps[0] = std::chrono::steady_clock::now();
   if ((rc = inflate_jobs((const uint8_t*)g.gz_bodies.p, base, jobs, firsts.data(), flags & ~(ZES_F_CHECK_ADLER | ZES_F_GZIP_SERIAL)))) return rc;
-  if (g.profiling) g.carry = g.last_times;  // (inflate_jobs has collected what ran so far: the call's last collect_times keeps it)
+  keep_times();
   if (stamps) stamps[1] = std::chrono::steady_clock::now();
   for (uint32_t k = 0; k < n; k++) {
     const uint64_t dlen = ps[k].m.size - ps[k].m.hlen - 8;
@@ -4582,12 +4622,7 @@ static int bgzf_index_out(const std::vector<BgzfEntry>& ch, uint64_t c, uint64_t
 int zes_bgzf_index(const uint8_t* in, uint64_t c, uint64_t* coff, uint64_t* uoff, uint64_t cap, uint64_t* members, uint32_t flags) {
   if (const int arc = bgzf_index_args(in, c, coff, uoff, cap, members, flags)) return arc;
   std::vector<BgzfEntry> ch;
-  for (uint64_t pos = 0; pos < c;) {
-    ZesGzMember m;
-    if (!gz_member(in + pos, c - pos, c - pos, &m)) return ZES_E_GZIP;
-    ch.push_back(BgzfEntry{pos, get_le32(in + pos + m.size - 4)});
-    pos += m.size;
-  }
+  if (!gz_walk_host(in, c, [&](uint64_t pos, const ZesGzMember& m) { ch.push_back(BgzfEntry{pos, get_le32(in + pos + m.size - 4)}); })) return ZES_E_GZIP;
   return bgzf_index_out(ch, c, coff, uoff, cap, members);
 }
 
@@ -4646,21 +4681,11 @@ static int bgzf_find_dev(const uint8_t* d_in, uint64_t c, bool walk, std::vector
     }
   }
   const uint64_t cap = std::min<uint64_t>(counted ? counted : c / 28 + 1, 0xFFFFFFFFull);
-  if ((rc = ensure(g.gz_tab, sizeof(ZesGzWalk) + sizeof(ZesGzMember) * (size_t)cap))) return rc;
-  ZesGzWalk* d_head = (ZesGzWalk*)g.gz_tab.p;
-  {
-    Timed t("k_gz_walk");
-    hipLaunchKernelGGL(k_gz_walk, dim3(1), dim3(64), 0, g.stream, d_in, c, d_head, (ZesGzMember*)(d_head + 1), (uint32_t)cap);
-  }
-  HIPCHK(hipGetLastError());
-  ZesGzWalk head;
-  HIPCHK(hipMemcpyAsync(&head, d_head, sizeof head, hipMemcpyDeviceToHost, g.stream));
-  HIPCHK(hipStreamSynchronize(g.stream));
+  if ((rc = gz_walk_room(cap))) return rc;
+  std::vector<ZesGzMember> tab;
   // (head.ok asks for two members, as zes_gunzip's batch does; one is enough here: the walk got to the file's end)
-  if (!head.count || head.count > cap || head.end != c) return ZES_OK;
-  std::vector<ZesGzMember> tab(head.count);
-  HIPCHK(hipMemcpyAsync(tab.data(), d_head + 1, sizeof(ZesGzMember) * tab.size(), hipMemcpyDeviceToHost, g.stream));
-  HIPCHK(hipStreamSynchronize(g.stream));
+  if ((rc = gz_walk_dev(d_in, c, (uint32_t)cap, [&](const ZesGzWalk& w) { return w.count && w.count <= cap && w.end == c; }, tab))) return rc;
+  if (tab.empty()) return ZES_OK;
   uint64_t pos = 0;
   for (const ZesGzMember& m : tab) {
     ch.push_back(BgzfEntry{pos, m.isize});
@@ -4726,11 +4751,8 @@ static int bgzf_read_core(const uint8_t* h, const uint8_t* d_src, uint64_t src_a
       segs.push_back(ZesGzSeg{at - src_at, i * BGZF_PEEK, std::min<uint64_t>(size, ZES_GZ_HLEN_MAX), 0u, 0u});
       segs.push_back(ZesGzSeg{at - src_at + size - 8, i * BGZF_PEEK + ZES_GZ_HLEN_MAX, 8, 0u, 0u});
     }
-    if ((rc = ensure(g.gz_stage, nt * BGZF_PEEK))) return rc;
-    if ((rc = gz_gather(d_src, (uint8_t*)g.gz_stage.p, segs))) return rc;
     peek.resize(nt * BGZF_PEEK);
-    HIPCHK(hipMemcpyAsync(peek.data(), g.gz_stage.p, peek.size(), hipMemcpyDeviceToHost, g.stream));
-    HIPCHK(hipStreamSynchronize(g.stream));
+    if ((rc = gather_down(g.gz_stage, d_src, segs, peek.data(), peek.size()))) return rc;
   }
   std::vector<GzPart> ps(nt);
   for (size_t i = 0; i < nt; i++) {

@@ -2676,6 +2676,18 @@ __global__ void k_make_blks(ZesBuf b0, uint32_t nbuf, ZesBuf* __restrict__ bufs,
 // k_adler: each workgroup reduces one 64 KiB chunk to (A, B) and adds its closed-form share
 //  to two u64 accumulators per buffer: acc[0] += A, acc[1] += B + A * bytesAfter.
 // ------------------------------------------------------------------------------------------
+// the sums of a 16-byte group by dot-product instructions: a = sum b[k], w = sum (16 - k) * b[k]
+__device__ __forceinline__ static void adler_group_sums(uint4 v, uint32_t& a, uint32_t& w) {
+  a = __builtin_amdgcn_udot4(v.x, 0x01010101u, 0u, false);
+  a = __builtin_amdgcn_udot4(v.y, 0x01010101u, a, false);
+  a = __builtin_amdgcn_udot4(v.z, 0x01010101u, a, false);
+  a = __builtin_amdgcn_udot4(v.w, 0x01010101u, a, false);
+  w = __builtin_amdgcn_udot4(v.x, 0x0D0E0F10u, 0u, false);  // byte k of the 16 weighs 16 - k
+  w = __builtin_amdgcn_udot4(v.y, 0x090A0B0Cu, w, false);
+  w = __builtin_amdgcn_udot4(v.z, 0x05060708u, w, false);
+  w = __builtin_amdgcn_udot4(v.w, 0x01020304u, w, false);
+}
+
 // one chunk [c0, c0 + clen) of an n-byte buffer at p0
 __device__ __forceinline__ static void adler_chunk(const uint8_t* __restrict__ p0, uint64_t n, uint64_t c0, uint64_t clen,
                                                    unsigned long long* __restrict__ acc) {
@@ -2699,14 +2711,8 @@ __device__ __forceinline__ static void adler_chunk(const uint8_t* __restrict__ p
 #pragma unroll
       for (uint32_t q = 0; q < 4; q++) {
         const uint64_t o = r * ROUND + (uint64_t)q * ADLER_THREADS * 16 + (uint64_t)tid * 16;
-        uint32_t a = __builtin_amdgcn_udot4(v[q].x, 0x01010101u, 0u, false);
-        a = __builtin_amdgcn_udot4(v[q].y, 0x01010101u, a, false);
-        a = __builtin_amdgcn_udot4(v[q].z, 0x01010101u, a, false);
-        a = __builtin_amdgcn_udot4(v[q].w, 0x01010101u, a, false);
-        uint32_t w = __builtin_amdgcn_udot4(v[q].x, 0x0D0E0F10u, 0u, false);  // byte k of the 16 weighs 16 - k
-        w = __builtin_amdgcn_udot4(v[q].y, 0x090A0B0Cu, w, false);
-        w = __builtin_amdgcn_udot4(v[q].z, 0x05060708u, w, false);
-        w = __builtin_amdgcn_udot4(v[q].w, 0x01020304u, w, false);
+        uint32_t a, w;
+        adler_group_sums(v[q], a, w);
         A += a;
         B += (uint64_t)w + (uint64_t)a * (clen - o - 16);
       }
@@ -2803,14 +2809,8 @@ __device__ __forceinline__ static void adler_seg_group(uint4 v, uint32_t o, uint
     v.z &= mh.z & ~ml.z;
     v.w &= mh.w & ~ml.w;
   }
-  uint32_t a = __builtin_amdgcn_udot4(v.x, 0x01010101u, 0u, false);
-  a = __builtin_amdgcn_udot4(v.y, 0x01010101u, a, false);
-  a = __builtin_amdgcn_udot4(v.z, 0x01010101u, a, false);
-  a = __builtin_amdgcn_udot4(v.w, 0x01010101u, a, false);
-  uint32_t w = __builtin_amdgcn_udot4(v.x, 0x0D0E0F10u, 0u, false);  // byte k of the 16 weighs 16 - k
-  w = __builtin_amdgcn_udot4(v.y, 0x090A0B0Cu, w, false);
-  w = __builtin_amdgcn_udot4(v.z, 0x05060708u, w, false);
-  w = __builtin_amdgcn_udot4(v.w, 0x01020304u, w, false);
+  uint32_t a, w;
+  adler_group_sums(v, a, w);
   A += a;
   B += (uint64_t)w + (uint64_t)a * behind;
 }
