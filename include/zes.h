@@ -420,6 +420,19 @@ int zes_stage_huff_lengths_dev(const uint32_t* h_hist, uint32_t nsym, uint32_t m
 int zes_stage_chain(const uint32_t* start_bit, const uint64_t* end_bit, const uint32_t* out_len, const uint32_t* flags, uint32_t count,
                     uint32_t cap, uint32_t first_bit, int on_device, int32_t* status, uint64_t* total, uint32_t* aux, uint32_t* map);
 
+/* Fills the pooled scratch with a chosen word, for tests/test_gpu_poison.py: every context that is ready, under its own
+ * lock, has its streams synchronised, then every pool (its whole capacity, in whole 32-bit words: a tail of up to 3 bytes
+ * stays as it is), the page-locked read-back area, the block decoder's host mirror and the large deflate batch's result
+ * array (when there is one) set to `word`, and its streams synchronised again.  Notes about what a pool holds do not
+ * outlive the fill: the survivor list's note is dropped and the CRC-32 table counts as absent (the next call that needs
+ * it builds it again).  The scan's constant table (not a pool), the staging rings, the profiling state and the route
+ * record stay.  *bytes (may be null): the bytes filled, over all contexts — the pools' whole words and the three
+ * page-locked areas; right after zes_trim that is the page-locked areas alone.  zes_pool_bytes is unchanged.
+ * The rule it tests: the library never clears its scratch between calls, so a call may read only words that the same call
+ * wrote; with every word nobody wrote set to a value that would do harm, every call must still give its known answer.
+ * replaces: nothing. */
+int zes_stage_poison(uint32_t word, uint64_t* bytes);
+
 /* Checks, on the device this context drives, the hardware behaviour k_lz_sort's stable ranks rest on: lanes of one
  * wavefront whose returning LDS add (ds_add_rtn_u32) meets in one word receive their old values in ascending lane order.
  * 256 workgroups x 16 wavefronts x iters rounds x 4 adds over six digit patterns; *bad = values that differ from the rank

@@ -139,6 +139,7 @@ def lib():
         L.zes_stage_lz77_route.argtypes = [C.c_void_p, C.c_uint32]
         L.zes_stage_huff_lengths_dev.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]
         L.zes_stage_chain.argtypes = [u32p, u64p, u32p, u32p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, i32p, u64p, u32p, u32p]
+        L.zes_stage_poison.argtypes = [C.c_uint32, u64p]
         L.zes_selftest_lds_order.argtypes = [C.c_uint32, C.c_uint32, u64p, u64p]
         L.zes_last_kernel_times.argtypes = [C.POINTER(ZesKTime), C.c_int]
         L.zes_set_profiling.argtypes = [C.c_int]
@@ -794,6 +795,16 @@ def stage_lz77_route():
     if rc:
         _raise(rc)
     return w
+
+
+def stage_poison(word):
+    """zes_stage_poison: every pool, the page-locked areas and the mirror of every ready context filled with the 32-bit
+    ``word`` (include/zes.h); returns the bytes filled."""
+    n = C.c_uint64(0)
+    rc = lib().zes_stage_poison(int(word) & 0xFFFFFFFF, C.byref(n))
+    if rc:
+        _raise(rc)
+    return int(n.value)
 
 
 def selftest_lds_order(iters=200, seed=1):

@@ -4968,6 +4968,48 @@ int zes_stage_chain(const uint32_t* start_bit, const uint64_t* end_bit, const ui
   return ZES_OK;
 }
 
+// one context, its lock held: everything a call could find from an earlier one becomes `word`
+static int poison_locked(Ctx& c, uint32_t word, uint64_t* filled) {
+  HIPCHK(hipSetDevice(c.device));
+  const hipStream_t streams[] = {c.stream, c.cs_in, c.cs_out, c.s_adler};
+  for (hipStream_t s : streams) HIPCHK(hipStreamSynchronize(s));
+  hipError_t e = hipSuccess;
+  for_each_pool(c, [&](DevBuf& b) {
+    const size_t words = b.p ? b.cap / 4 : 0;
+    if (!words || e != hipSuccess) return;
+    e = hipMemsetD32Async((hipDeviceptr_t)b.p, (int)word, words, c.stream);
+    *filled += (uint64_t)words * 4;
+  });
+  HIPCHK(e);
+  // the page-locked areas are host memory: no launch is in flight, so the host fills them
+  auto fill = [&](void* p, size_t bytes) {
+    if (!p) return;
+    std::fill((uint32_t*)p, (uint32_t*)p + bytes / 4, word);
+    *filled += bytes / 4 * 4;
+  };
+  fill(c.pinned, PINNED_BYTES);
+  fill(c.mirror, sizeof(ParMirror));
+  fill(c.res_more, sizeof(ZesRes) * c.res_more_n);
+  c.sv.drop();     // (of `surv`)
+  c.crc_npow = 0;  // (of `crctab`: crc_ready builds the table again)
+  HIPCHK(hipStreamSynchronize(c.stream));
+  return ZES_OK;
+}
+
+int zes_stage_poison(uint32_t word, uint64_t* bytes) {
+  std::lock_guard<std::mutex> cfg(g_cfg_mu);
+  uint64_t filled = 0;
+  int rc = ZES_OK;
+  for (int i = 0; i < ZES_MAX_DEV; i++) {
+    std::lock_guard<std::mutex> lk(g_mus[i]);
+    if (!g_ctx[i].ready) continue;
+    const int r = poison_locked(g_ctx[i], word, &filled);
+    if (r && !rc) rc = r;
+  }
+  if (bytes) *bytes = filled;
+  return rc;
+}
+
 int zes_selftest_lds_order(uint32_t iters, uint32_t seed, uint64_t* bad, uint64_t* checked) {
   if (!bad || !checked || iters == 0 || iters > 100000u) return ZES_E_ARG;
   LOCK_READY();
