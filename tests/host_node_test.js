@@ -129,6 +129,8 @@ it('malformed-stream cases (every 7th)', () => {
       assert.ok(ab[2] instanceof Error && ab[2].message === 'Data is corrupted');
       assert.ok(Buffer.from(abk[1]).equals(Buffer.from(RAW_BIN)));
     });
+    const none = [zlibes.deflateBatch([]), zlibes.inflateBatch([]), await zlibes.deflateBatchAsync([]), await zlibes.inflateBatchAsync([])];
+    it('an empty batch is []', () => { for (const r of none) assert.ok(Array.isArray(r) && r.length === 0); });
     it('batch argument checks', () => assert.throws(() => zlibes.deflateBatch([RAW, 5]), TypeError));
     it('inflateRaw offset checks', () => {
       assert.throws(() => zlibes.inflateRaw(RAW, -1), TypeError);

@@ -25,6 +25,16 @@ def test_napi_addon_loads_and_mirrors_the_reference_api(z):
     assert out.returncode == 0 and "ok" in out.stdout, (out.returncode, out.stderr)
 
 
+@pytest.mark.skipif(shutil.which("node") is None, reason="node not installed")
+def test_argument_errors_on_the_main_thread_and_in_a_worker(z):
+    """Every TypeError and host-side Error of the façade, constructor and exact message, in two N-API environments
+    (tests/host_node_args_test.js); no device is touched."""
+    subprocess.check_call(["make", "-s", "-C", os.path.join(ROOT, "zlib.es_amd", "host")])
+    out = subprocess.run(["node", os.path.join(ROOT, "tests", "host_node_args_test.js")], capture_output=True, text=True, timeout=60)
+    assert out.returncode == 0, out.stdout[-3000:] + out.stderr[-3000:]
+    assert "argument checks passed on both threads" in out.stdout
+
+
 def test_generated_js_is_in_sync_with_ts():
     host = os.path.join(ROOT, "zlib.es_amd", "host")
     before = open(os.path.join(host, "zlib.js")).read()

@@ -9,11 +9,14 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <algorithm>
 #include <atomic>
 #include <csignal>
 #include <execinfo.h>
 #include <unistd.h>
+#include <memory>
 #include <mutex>
+#include <string>
 #include <thread>
 #include <vector>
 
@@ -25,6 +28,23 @@ napi_value throw_status(napi_env env, int status) {
   // plain `Error` with the reference's exact message (src/zlib.ts:15, src/inflate.ts:32,35,50,...)
   napi_throw_error(env, nullptr, zes_strerror(status));
   return nullptr;
+}
+napi_value throw_type(napi_env env, const std::string& text) {
+  napi_throw_type_error(env, nullptr, text.c_str());
+  return nullptr;
+}
+// the same plain `Error` as an object: what a promise is rejected with and what stands for a failed buffer of a batch
+napi_value make_error(napi_env env, const char* text) {
+  napi_value msg, err = nullptr;
+  napi_create_string_utf8(env, text, NAPI_AUTO_LENGTH, &msg);
+  napi_create_error(env, nullptr, msg, &err);
+  return err;
+}
+napi_value undefined_unless(napi_env env, int rc) {
+  if (rc) return throw_status(env, rc);
+  napi_value v;
+  napi_get_undefined(env, &v);
+  return v;
 }
 
 bool get_bytes(napi_env env, napi_value v, const uint8_t** data, size_t* len) {
@@ -65,7 +85,7 @@ bool get_bytes(napi_env env, napi_value v, const uint8_t** data, size_t* len) {
 // Set when the last environment (or the process) goes down: from then on nothing here calls into the library or the HIP
 // runtime any more — page-locked blocks are left to the process's end.
 std::atomic<bool> g_exiting{false};
-std::atomic<long> g_dbg_hit{0}, g_dbg_miss{0}, g_dbg_released{0}, g_dbg_fresh{0};
+std::atomic<long> g_dbg_hit{0}, g_dbg_miss{0}, g_dbg_released{0};
 std::atomic<int> g_envs{0};
 void mark_exiting_atexit() { g_exiting.store(true); }
 
@@ -165,14 +185,22 @@ struct ResultMem {
   uint8_t* p = nullptr;
   size_t cap = 0;
 };
+// only what the pool holds (fresh = false: what may be asked from inside one of the library's calls), or nothing
+ResultMem pooled(size_t n, bool note_miss = true) {
+  ResultMem m;
+  if (n >= BIG_MIN) m.p = g_big.take(n, &m.cap, false, note_miss);
+  if (!m.p) m.cap = 0;
+  return m;
+}
+ResultMem result_malloc(size_t n) {
+  ResultMem m;
+  m.p = static_cast<uint8_t*>(malloc(n ? n : 1));
+  return m;
+}
 ResultMem result_alloc(size_t n, bool fresh = true) {
   ResultMem m;
   if (n >= BIG_MIN) m.p = g_big.take(n, &m.cap, fresh);
-  if (!m.p) {
-    m.cap = 0;
-    m.p = static_cast<uint8_t*>(malloc(n ? n : 1));
-  }
-  return m;
+  return m.p ? m : result_malloc(n);
 }
 void result_free(ResultMem m) {
   if (!m.p) return;
@@ -181,6 +209,33 @@ void result_free(ResultMem m) {
   else
     free(m.p);
 }
+
+// A synchronous deflate() that finds no pooled block (a tight loop: Node runs no finalizer inside it) would hand the
+// library ~64 MiB of untouched malloc'd memory to download into piece by piece — every page faulted under the copy
+// engine's hands, ~40 ms.  Instead the library writes into ONE page-locked scratch block the addon keeps for this purpose,
+// and the exact-length result is copied out of it by a few threads (the faults of the fresh result spread over them).
+// One block per environment (EnvState): a synchronous call owns it from get() until the copy out of it is done, and
+// two environments' JS threads run such calls side by side.
+struct SyncScratch {
+  uint8_t* p = nullptr;
+  size_t cap = 0;
+  uint8_t* get(size_t n) {
+    if (n <= cap) return p;
+    clear();
+    void* q = nullptr;
+    const size_t want = (n + (4u << 20) - 1) & ~(size_t)((4u << 20) - 1);
+    if (zes_host_alloc(want, &q) != 0 || !q) return nullptr;
+    p = static_cast<uint8_t*>(q);
+    cap = want;
+    return p;
+  }
+  void clear() {
+    if (p) zes_host_free(p);
+    p = nullptr;
+    cap = 0;
+  }
+};
+
 // ---- whose memory is still in use: no finalizers ----
 // The memory behind an array handed to JS (a result, an allocPinned() array) is an external ArrayBuffer WITHOUT a finalizer;
 // the addon keeps a weak reference to it and looks, at the start of every call, which of them the collector has cleared:
@@ -197,16 +252,19 @@ struct Track {
   int64_t told;   // bytes reported with napi_adjust_external_memory
   bool pinned;    // allocPinned(): goes back with zes_host_free
 };
-struct EnvTracks {
+// what one environment owns: the arrays it handed to JS and what its synchronous calls keep between them
+struct EnvState {
   napi_env env;
   std::vector<Track> v;
   size_t cursor = 0;
+  SyncScratch scratch;
+  size_t last_inflate_out = 0;  // what the last synchronous inflate produced (Inflate sizes the scratch block by it)
 };
 std::mutex g_tracks_mu;
-std::vector<EnvTracks*> g_tracks;  // one per environment (a Worker has its own); an entry is used by its environment's thread only
-EnvTracks* tracks_of(napi_env env) {
+std::vector<EnvState*> g_tracks;  // one per environment (a Worker has its own); an entry is used by its environment's thread only
+EnvState* tracks_of(napi_env env) {
   std::lock_guard<std::mutex> lk(g_tracks_mu);
-  for (EnvTracks* t : g_tracks)
+  for (EnvState* t : g_tracks)
     if (t->env == env) return t;
   return nullptr;
 }
@@ -222,7 +280,7 @@ void release_memory(const Track& t) {
 }
 constexpr size_t SWEEP_MAX = 4096;  // references looked at per call (a host that keeps more arrays alive is swept in turns)
 void sweep(napi_env env) {
-  EnvTracks* et = tracks_of(env);
+  EnvState* et = tracks_of(env);
   if (!et || et->v.empty()) return;
   size_t todo = et->v.size() < SWEEP_MAX ? et->v.size() : SWEEP_MAX;
   size_t i = et->cursor < et->v.size() ? et->cursor : 0;
@@ -247,10 +305,11 @@ void sweep(napi_env env) {
   }
   et->cursor = i;
 }
-// the environment goes down: its arrays with it (no N-API call from here; pooled blocks stay pooled for other environments)
+// the environment goes down: its arrays and its scratch block with it (no N-API call from here; pooled blocks stay pooled
+// for other environments)
 void env_cleanup(void* arg) {
   napi_env env = static_cast<napi_env>(arg);
-  EnvTracks* mine = nullptr;
+  EnvState* mine = nullptr;
   {
     std::lock_guard<std::mutex> lk(g_tracks_mu);
     for (size_t i = 0; i < g_tracks.size(); i++)
@@ -266,8 +325,10 @@ void env_cleanup(void* arg) {
   const bool last = g_envs.fetch_sub(1) == 1;
   if (last) g_exiting.store(true);
   if (mine) {
-    if (!last)
+    if (!last) {
       for (const Track& t : mine->v) release_memory(t);
+      mine->scratch.clear();
+    }
     delete mine;
   }
 }
@@ -279,7 +340,7 @@ napi_value adopt(napi_env env, uint8_t* p, size_t n, size_t cap, bool pinned) {
   t.cap = cap;
   t.told = (int64_t)(cap ? cap : n);
   t.pinned = pinned;
-  EnvTracks* et = tracks_of(env);
+  EnvState* et = tracks_of(env);
   napi_value ab, ta;
   if (!et || napi_create_external_arraybuffer(env, p, n, nullptr, nullptr, &ab) != napi_ok) {
     release_memory(t);
@@ -307,32 +368,89 @@ napi_value take_u8(napi_env env, ResultMem m, size_t n) {
   return adopt(env, m.p, n, m.cap, false);
 }
 
-// A synchronous deflate() that finds no pooled block (a tight loop: Node runs no finalizer inside it) would hand the
-// library ~64 MiB of untouched malloc'd memory to download into piece by piece — every page faulted under the copy
-// engine's hands, ~40 ms.  Instead the library writes into ONE page-locked scratch block the addon keeps for this purpose,
-// and the exact-length result is copied out of it by a few threads (the faults of the fresh result spread over them).
-struct SyncScratch {
-  uint8_t* p = nullptr;
-  size_t cap = 0;
-  uint8_t* get(size_t n) {
-    if (n <= cap) return p;
-    if (p) zes_host_free(p);
-    p = nullptr;
-    cap = 0;
-    void* q = nullptr;
-    const size_t want = (n + (4u << 20) - 1) & ~(size_t)((4u << 20) - 1);
-    if (zes_host_alloc(want, &q) != 0 || !q) return nullptr;
-    p = static_cast<uint8_t*>(q);
-    cap = want;
-    return p;
-  }
-  void clear() {
-    if (p) zes_host_free(p);
-    p = nullptr;
-    cap = 0;
-  }
+// ---- arguments ----
+struct Args {
+  size_t argc = 4;  // (in: the length of argv, the longest signature's; out: how many the caller passed)
+  napi_value argv[4];  // (the ones not passed are undefined)
 };
-SyncScratch g_sync_scratch;  // (JS thread only)
+Args get_args(napi_env env, napi_callback_info info) {
+  Args a;
+  napi_get_cb_info(env, info, &a.argc, a.argv, nullptr, nullptr);
+  return a;
+}
+
+// argument i as bytes, or (ok = false) the TypeError "<sig>: <name> must be a Uint8Array" is thrown
+struct Bytes {
+  const uint8_t* p = nullptr;
+  size_t n = 0;
+  bool ok = false;
+};
+Bytes need_bytes(napi_env env, const Args& a, size_t i, const char* sig, const char* name) {
+  Bytes b;
+  b.ok = i < a.argc && get_bytes(env, a.argv[i], &b.p, &b.n);
+  if (!b.ok) throw_type(env, std::string(sig) + ": " + name + " must be a Uint8Array");
+  return b;
+}
+
+// a non-negative safe integer given as a number — nothing else: null, a string, a bigint are not numbers
+bool get_safe_uint(napi_env env, napi_value v, uint64_t* out) {
+  double d = 0;
+  if (napi_get_value_double(env, v, &d) != napi_ok || !(d >= 0) || d > 9007199254740991.0 || d != (double)(uint64_t)d) return false;
+  *out = (uint64_t)d;
+  return true;
+}
+// a position or length: that, or a bigint below 2^64
+bool get_offset(napi_env env, napi_value v, uint64_t* out) {
+  napi_valuetype vt;
+  if (napi_typeof(env, v, &vt) != napi_ok) return false;
+  if (vt != napi_bigint) return get_safe_uint(env, v, out);
+  bool lossless = false;
+  return napi_get_value_bigint_uint64(env, v, out, &lossless) == napi_ok && lossless;
+}
+int32_t int32_or_0(napi_env env, napi_value v) {
+  int32_t x = 0;
+  napi_get_value_int32(env, v, &x);  // (not a number: x stays 0)
+  return x;
+}
+
+// the optional `options` argument of the inflate forms, { verify?: boolean }: ZES_F_CHECK_ADLER when verify is true, else
+// nothing (no second argument, undefined, null, an object without the property: the call is the one-argument call)
+uint32_t verify_flag(napi_env env, const Args& a, size_t at) {
+  if (a.argc <= at) return 0;
+  napi_valuetype t = napi_undefined;
+  if (napi_typeof(env, a.argv[at], &t) != napi_ok || t != napi_object) return 0;
+  napi_value v;
+  bool on = false;
+  if (napi_get_named_property(env, a.argv[at], "verify", &v) != napi_ok || napi_typeof(env, v, &t) != napi_ok || t != napi_boolean) return 0;
+  return napi_get_value_bool(env, v, &on) == napi_ok && on ? ZES_F_CHECK_ADLER : 0;
+}
+
+// ---- the bounded result ----
+// A call that writes at most a known number of bytes into memory it is given: fill() makes the call and gives the memory
+// back when it answers a status (no N-API call: the worker thread of deflateAsync fills too); as_u8() turns what fill()
+// left into the exact-length Uint8Array or the thrown Error; bounded() is both, the whole of most synchronous entry points.
+struct Filled {
+  ResultMem m;
+  uint64_t len = 0;
+  int rc = 0;
+};
+template <class Call>  // int call(uint8_t* out, uint64_t* out_len)
+Filled fill(ResultMem m, Call call) {
+  Filled f;
+  f.m = m;
+  f.rc = m.p ? call(m.p, &f.len) : ZES_E_ARG;
+  if (f.rc) {
+    result_free(f.m);
+    f.m = ResultMem();
+  }
+  return f;
+}
+napi_value as_u8(napi_env env, const Filled& f) { return f.rc ? throw_status(env, f.rc) : take_u8(env, f.m, (size_t)f.len); }
+template <class Call>
+napi_value bounded(napi_env env, ResultMem m, Call call) {
+  return as_u8(env, fill(m, call));
+}
+
 void copy_parallel(uint8_t* dst, const uint8_t* src, size_t n) {
   const unsigned hw = std::thread::hardware_concurrency();
   const unsigned nt = n < (8u << 20) ? 1u : (hw >= 8 ? 4u : 2u);
@@ -349,255 +467,165 @@ void copy_parallel(uint8_t* dst, const uint8_t* src, size_t n) {
   memcpy(dst, src, part < n ? part : n);
   for (auto& t : th) t.join();
 }
+// the result a call left at the head of the scratch block, copied out into m
+napi_value out_of_scratch(napi_env env, const uint8_t* scratch, ResultMem m, uint64_t len) {
+  if (!m.p) return throw_status(env, ZES_E_ARG);
+  copy_parallel(m.p, scratch, (size_t)len);
+  return take_u8(env, m, (size_t)len);
+}
 
-// zes_alloc_fn of the synchronous inflate: runs on the JS thread, inside zes_inflate_alloc
-struct SyncAlloc {
+// ---- zes_alloc_fn: the library asks for the result's memory from inside its call ----
+// The exact-size leg of every such callback: the block handed out before goes back (ZES_F_ALLOC_BOUND: a second call when
+// the first one's estimate fell short, or the call started over), then a pooled block or malloc — never zes_host_alloc,
+// which takes the lock the library is holding.
+struct ExactMem {
   ResultMem m;
-  bool failed;
+  bool failed = false;
+  void drop() {
+    result_free(m);
+    m = ResultMem();
+  }
+  uint8_t* renew(size_t n) {
+    drop();
+    m = result_alloc(n, false);
+    if (!m.p) failed = true;
+    return m.p;
+  }
+};
+uint8_t* exact_alloc(void* user, uint32_t, uint64_t n) { return static_cast<ExactMem*>(user)->renew((size_t)n); }  // gunzip: no early request
+
+// the synchronous inflate's: runs on the JS thread, inside zes_inflate_alloc
+struct SyncAlloc : ExactMem {
+  const SyncScratch* scratch = nullptr;  // its environment's
   bool in_scratch = false;  // the early estimate was served from the scratch block: the result is copied out of it afterwards
 };
-// an early request (ZES_F_ALLOC_BOUND: an upper estimate, the bytes then come down beside the decode) is only worth
-// taking with a pooled block: downloads piece by piece into fresh malloc'd memory pay its page faults the slow way
-ResultMem early_alloc(size_t n) {
-  ResultMem m;
-  if (n >= BIG_MIN) m.p = g_big.take(n, &m.cap, false);
-  if (!m.p) m.cap = 0;
-  return m;
-}
 uint8_t* sync_alloc(void* user, uint32_t index, uint64_t n) {
   SyncAlloc* a = static_cast<SyncAlloc*>(user);
-  result_free(a->m);  // (ZES_F_ALLOC_BOUND: a second call when the first one's estimate fell short, or the call started over)
-  a->m = ResultMem();
   a->in_scratch = false;
-  if (index & ZES_ALLOC_EARLY) {
-    // a pooled block if the pool holds one; else the scratch block when it is long enough (grown outside the library's call,
-    // from what the calls before needed): the bytes come down beside the decode into page-locked memory, and the exact-length
-    // result is copied out by a few threads afterwards — a tight loop's results are fresh memory either way, but this way
-    // its page faults are spread over the copy's threads instead of being taken under the copy engine, and no block is
-    // page-locked for the next call (a loop over 64 MiB results alternated between 2.5 ms and 25 ms a call)
-    if (n >= BIG_MIN) a->m.p = g_big.take((size_t)n, &a->m.cap, false, false);
-    if (a->m.p) return a->m.p;
-    a->m.cap = 0;
-    if (g_sync_scratch.p && n <= g_sync_scratch.cap) {
-      a->in_scratch = true;
-      return g_sync_scratch.p;
-    }
-    if (n >= BIG_MIN) g_big.take((size_t)n, &a->m.cap, false, true);  // (notes the miss: the pool is topped up after the call)
-    a->m = ResultMem();
-    return nullptr;  // ("not now" — the exact size is asked for once, later)
+  if (!(index & ZES_ALLOC_EARLY)) return a->renew((size_t)n);
+  // an early request (ZES_F_ALLOC_BOUND: an upper estimate, the bytes then come down beside the decode) is only worth
+  // taking with page-locked memory: downloads piece by piece into fresh malloc'd memory pay its page faults the slow way.
+  // A pooled block if the pool holds one; else the scratch block when it is long enough (grown outside the library's call,
+  // from what the calls before needed): the exact-length result is copied out by a few threads afterwards — a tight
+  // loop's results are fresh memory either way, but this way its page faults are spread over the copy's threads instead
+  // of being taken under the copy engine, and no block is page-locked for the next call (a loop over 64 MiB results
+  // alternated between 2.5 ms and 25 ms a call)
+  a->drop();
+  a->m = pooled((size_t)n, false);
+  if (a->m.p) return a->m.p;
+  if (a->scratch && a->scratch->p && n <= a->scratch->cap) {
+    a->in_scratch = true;
+    return a->scratch->p;
   }
-  a->m = result_alloc((size_t)n, false);  // (inside the library's call)
-  if (!a->m.p) a->failed = true;
-  return a->m.p;
+  a->m = pooled((size_t)n);  // (notes the miss: the pool is topped up after the call)
+  return a->m.p;             // (nullptr unless a block came back meanwhile: "not now" — the exact size is asked for once, later)
 }
 
 napi_value Deflate(napi_env env, napi_callback_info info) {
-  size_t argc = 1;
-  napi_value argv[1];
-  napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr);
-  const uint8_t* in = nullptr;
-  size_t n = 0;
-  if (argc < 1 || !get_bytes(env, argv[0], &in, &n)) {
-    napi_throw_type_error(env, nullptr, "deflate(input): input must be a Uint8Array");
-    return nullptr;
-  }
-  uint64_t cap = 0, out_len = 0;
-  zes_deflate_bound(n, &cap);
-  ResultMem tmp;
-  if (cap >= BIG_MIN) tmp.p = g_big.take(cap, &tmp.cap, false);  // a block the pool holds, if any
-  if (!tmp.p && cap >= (4u << 20)) {  // none (a tight synchronous loop): through the scratch block, see above
-    tmp.cap = 0;
-    uint8_t* sc = g_sync_scratch.get(cap);
+  const Args a = get_args(env, info);
+  const Bytes in = need_bytes(env, a, 0, "deflate(input)", "input");
+  if (!in.ok) return nullptr;
+  uint64_t cap = 0;
+  zes_deflate_bound(in.n, &cap);
+  ResultMem tmp = pooled(cap);  // a block the pool holds, if any
+  if (!tmp.p && cap >= (4u << 20)) {  // none (a tight synchronous loop): through this environment's scratch block, see SyncScratch
+    EnvState* es = tracks_of(env);
+    uint8_t* sc = es ? es->scratch.get(cap) : nullptr;
     if (sc) {
-      const int rc = zes_deflate(in, n, sc, cap, &out_len);
-      if (rc) return throw_status(env, rc);
-      ResultMem m;
-      m.p = static_cast<uint8_t*>(malloc(out_len ? out_len : 1));
-      if (!m.p) return throw_status(env, ZES_E_ARG);
-      copy_parallel(m.p, sc, (size_t)out_len);
-      return take_u8(env, m, out_len);
+      uint64_t out_len = 0;
+      const int rc = zes_deflate(in.p, in.n, sc, cap, &out_len);
+      return rc ? throw_status(env, rc) : out_of_scratch(env, sc, result_malloc(out_len), out_len);
     }
   }
-  if (!tmp.p) tmp = result_alloc(cap, false);
-  if (!tmp.p) return throw_status(env, ZES_E_ARG);
-  const int rc = zes_deflate(in, n, tmp.p, cap, &out_len);
-  if (rc) {
-    result_free(tmp);
-    return throw_status(env, rc);
-  }
-  return take_u8(env, tmp, out_len);
-}
-
-// the optional `options` argument of the inflate forms, { verify?: boolean }: ZES_F_CHECK_ADLER when verify is true, else
-// nothing (no second argument, undefined, null, an object without the property: the call is the one-argument call)
-uint32_t verify_flag(napi_env env, size_t argc, const napi_value* argv, size_t at) {
-  if (argc <= at) return 0;
-  napi_valuetype t = napi_undefined;
-  if (napi_typeof(env, argv[at], &t) != napi_ok || t != napi_object) return 0;
-  napi_value v;
-  bool on = false;
-  if (napi_get_named_property(env, argv[at], "verify", &v) != napi_ok || napi_typeof(env, v, &t) != napi_ok || t != napi_boolean) return 0;
-  return napi_get_value_bool(env, v, &on) == napi_ok && on ? ZES_F_CHECK_ADLER : 0;
+  return bounded(env, tmp.p ? tmp : result_alloc(cap, false), [&](uint8_t* out, uint64_t* len) { return zes_deflate(in.p, in.n, out, cap, len); });
 }
 
 napi_value Inflate(napi_env env, napi_callback_info info) {
-  size_t argc = 2;
-  napi_value argv[2];
-  napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr);
-  const uint8_t* in = nullptr;
-  size_t c = 0;
-  if (argc < 1 || !get_bytes(env, argv[0], &in, &c)) {
-    napi_throw_type_error(env, nullptr, "inflate(input): input must be a Uint8Array");
-    return nullptr;
-  }
+  const Args a = get_args(env, info);
+  const Bytes in = need_bytes(env, a, 0, "inflate(input)", "input");
+  if (!in.ok) return nullptr;
   // one call, one lock: the library decodes, then asks for the exact ArrayBuffer (the reference grows a
   // Uint8WriteStream instead, src/inflate.ts:17) and copies straight into it — nothing is kept between calls,
   // so an inflateAsync() in flight on a worker thread cannot get in between
   SyncAlloc sa;
-  sa.failed = false;
   uint64_t out_len = 0;
-  // the scratch block, long enough for what the last synchronous inflate produced (a loop decodes like after like) and
-  // never shorter than the stream: grown here, outside the library's call
-  static size_t s_last_out = 0;
-  {
-    const size_t want = s_last_out > c ? s_last_out + s_last_out / 16 + (1u << 20) : 0;
-    if (want >= (4u << 20) && want <= (1024u << 20)) (void)g_sync_scratch.get(want);
+  // the scratch block, long enough for what this environment's last synchronous inflate produced (a loop decodes like
+  // after like) and never shorter than the stream: grown here, outside the library's call
+  EnvState* es = tracks_of(env);
+  if (es) {
+    const size_t last = es->last_inflate_out;
+    const size_t want = last > in.n ? last + last / 16 + (1u << 20) : 0;
+    if (want >= (4u << 20) && want <= (1024u << 20)) (void)es->scratch.get(want);
+    sa.scratch = &es->scratch;
   }
   // (the pooled block is longer than the ArrayBuffer shows of it anyway: the library may ask early for an upper estimate and
   // send the bytes down while it is still decoding)
   // (with ZES_F_CHECK_ADLER the library takes its one-pass path, where ZES_F_ALLOC_BOUND asks for nothing early)
-  const int rc = zes_inflate_alloc(in, c, sync_alloc, &sa, &out_len, ZES_F_ALLOC_BOUND | verify_flag(env, argc, argv, 1));
+  const int rc = zes_inflate_alloc(in.p, in.n, sync_alloc, &sa, &out_len, ZES_F_ALLOC_BOUND | verify_flag(env, a, 1));
   if (!sa.in_scratch) g_big.top_up();
   if (rc) {
-    if (!sa.in_scratch) result_free(sa.m);
+    sa.drop();
     return throw_status(env, sa.failed ? ZES_E_ARG : rc);
   }
-  s_last_out = (size_t)out_len;
-  if (sa.in_scratch) {  // (the estimate held: the result is the scratch block's head)
-    ResultMem m;
-    if (out_len >= BIG_MIN) m.p = g_big.take((size_t)out_len, &m.cap, false, false);
-    if (!m.p) {
-      m.cap = 0;
-      m.p = static_cast<uint8_t*>(malloc(out_len ? (size_t)out_len : 1));
-    }
-    if (!m.p) return throw_status(env, ZES_E_ARG);
-    copy_parallel(m.p, g_sync_scratch.p, (size_t)out_len);
-    return take_u8(env, m, out_len);
-  }
-  return take_u8(env, sa.m, out_len);
+  if (es) es->last_inflate_out = (size_t)out_len;
+  if (!sa.in_scratch) return take_u8(env, sa.m, (size_t)out_len);
+  // (the estimate held: the result is the scratch block's head)
+  const ResultMem m = pooled((size_t)out_len, false);
+  return out_of_scratch(env, sa.scratch->p, m.p ? m : result_malloc((size_t)out_len), out_len);
 }
 
 // deflateRaw(input): the raw stream of the reference's src/deflate.ts:14 (no zlib wrapper)
 napi_value DeflateRaw(napi_env env, napi_callback_info info) {
-  size_t argc = 1;
-  napi_value argv[1];
-  napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr);
-  const uint8_t* in = nullptr;
-  size_t n = 0;
-  if (argc < 1 || !get_bytes(env, argv[0], &in, &n)) {
-    napi_throw_type_error(env, nullptr, "deflateRaw(input): input must be a Uint8Array");
-    return nullptr;
-  }
-  uint64_t cap = 0, out_len = 0;
-  zes_deflate_bound(n, &cap);
-  ResultMem tmp = result_alloc(cap);
-  if (!tmp.p) return throw_status(env, ZES_E_ARG);
-  const int rc = zes_deflate_raw(in, n, tmp.p, cap, &out_len);
-  if (rc) {
-    result_free(tmp);
-    return throw_status(env, rc);
-  }
-  return take_u8(env, tmp, out_len);
+  const Args a = get_args(env, info);
+  const Bytes in = need_bytes(env, a, 0, "deflateRaw(input)", "input");
+  if (!in.ok) return nullptr;
+  uint64_t cap = 0;
+  zes_deflate_bound(in.n, &cap);
+  return bounded(env, result_alloc(cap), [&](uint8_t* out, uint64_t* len) { return zes_deflate_raw(in.p, in.n, out, cap, len); });
 }
 
 // inflateRaw(input, offset = 0): the reference's src/inflate.ts:16 (what src/zlib.ts:21 calls with offset 2)
 napi_value InflateRaw(napi_env env, napi_callback_info info) {
-  size_t argc = 2;
-  napi_value argv[2];
-  napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr);
-  const uint8_t* in = nullptr;
-  size_t c = 0;
-  if (argc < 1 || !get_bytes(env, argv[0], &in, &c)) {
-    napi_throw_type_error(env, nullptr, "inflateRaw(input, offset): input must be a Uint8Array");
-    return nullptr;
-  }
+  static const char SIG[] = "inflateRaw(input, offset)";
+  const Args a = get_args(env, info);
+  const Bytes in = need_bytes(env, a, 0, SIG, "input");
+  if (!in.ok) return nullptr;
   uint64_t offset = 0;
-  if (argc >= 2) {
-    napi_valuetype vt;
-    double d = 0;
-    if (napi_typeof(env, argv[1], &vt) != napi_ok || (vt != napi_number && vt != napi_undefined) ||
-        (vt == napi_number && (napi_get_value_double(env, argv[1], &d) != napi_ok || !(d >= 0) || d > 9007199254740991.0 || d != (double)(uint64_t)d))) {
-      napi_throw_type_error(env, nullptr, "inflateRaw(input, offset): offset must be a non-negative safe integer");
-      return nullptr;
-    }
-    offset = (uint64_t)d;
-  }
+  napi_valuetype vt = napi_undefined;
+  if (napi_typeof(env, a.argv[1], &vt) != napi_ok || (vt != napi_undefined && !get_safe_uint(env, a.argv[1], &offset)))
+    return throw_type(env, std::string(SIG) + ": offset must be a non-negative safe integer");
   // grow-and-retry like the reference's Uint8WriteStream (src/utils/Uint8WriteStream.ts:13-21)
-  uint64_t cap = c * 4 + 65536, out_len = 0;
+  uint64_t cap = in.n * 4 + 65536;
   for (int attempt = 0; attempt < 8; attempt++) {
-    ResultMem tmp = result_alloc(cap);
-    if (!tmp.p) return throw_status(env, ZES_E_ARG);
-    const int rc = zes_inflate_raw(in, c, offset, tmp.p, cap, &out_len, ZES_F_DEFAULT);
-    if (rc == ZES_E_NOSPACE && out_len > cap) {
-      result_free(tmp);
-      cap = out_len;
-      continue;
-    }
-    if (rc) {
-      result_free(tmp);
-      return throw_status(env, rc);
-    }
-    return take_u8(env, tmp, out_len);
+    const Filled f = fill(result_alloc(cap), [&](uint8_t* out, uint64_t* len) { return zes_inflate_raw(in.p, in.n, offset, out, cap, len, ZES_F_DEFAULT); });
+    if (f.rc != ZES_E_NOSPACE || f.len <= cap) return as_u8(env, f);
+    cap = f.len;
   }
   return throw_status(env, ZES_E_DEVICE);
 }
 
 // gzip(input): one gzip member (RFC 1952) whose body is the reference's raw stream (include/zes.h: zes_gzip)
 napi_value Gzip(napi_env env, napi_callback_info info) {
-  size_t argc = 1;
-  napi_value argv[1];
-  napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr);
-  const uint8_t* in = nullptr;
-  size_t n = 0;
-  if (argc < 1 || !get_bytes(env, argv[0], &in, &n)) {
-    napi_throw_type_error(env, nullptr, "gzip(input): input must be a Uint8Array");
-    return nullptr;
-  }
-  uint64_t cap = 0, out_len = 0;
-  zes_gzip_bound(n, &cap);
-  ResultMem tmp = result_alloc(cap);
-  if (!tmp.p) return throw_status(env, ZES_E_ARG);
-  const int rc = zes_gzip(in, n, tmp.p, cap, &out_len);
-  if (rc) {
-    result_free(tmp);
-    return throw_status(env, rc);
-  }
-  return take_u8(env, tmp, out_len);
+  const Args a = get_args(env, info);
+  const Bytes in = need_bytes(env, a, 0, "gzip(input)", "input");
+  if (!in.ok) return nullptr;
+  uint64_t cap = 0;
+  zes_gzip_bound(in.n, &cap);
+  return bounded(env, result_alloc(cap), [&](uint8_t* out, uint64_t* len) { return zes_gzip(in.p, in.n, out, cap, len); });
 }
 
 // bgzip(input) / bgzipIndex(input): a BGZF file, a gzip member per 65280-byte chunk and the end-of-file marker
 // (include/zes.h: zes_bgzip); with_index: { data, offsets } with the position of every member, the marker's last
 napi_value bgzip_common(napi_env env, napi_callback_info info, bool with_index) {
-  size_t argc = 1;
-  napi_value argv[1];
-  napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr);
-  const uint8_t* in = nullptr;
-  size_t n = 0;
-  if (argc < 1 || !get_bytes(env, argv[0], &in, &n)) {
-    napi_throw_type_error(env, nullptr, with_index ? "bgzipIndex(input): input must be a Uint8Array" : "bgzip(input): input must be a Uint8Array");
-    return nullptr;
-  }
-  uint64_t cap = 0, out_len = 0, members = 0;
-  if (zes_bgzip_bound(n, &cap) || zes_bgzip_members(n, &members)) return throw_status(env, ZES_E_ARG);
+  const Args a = get_args(env, info);
+  const Bytes in = need_bytes(env, a, 0, with_index ? "bgzipIndex(input)" : "bgzip(input)", "input");
+  if (!in.ok) return nullptr;
+  uint64_t cap = 0, members = 0;
+  if (zes_bgzip_bound(in.n, &cap) || zes_bgzip_members(in.n, &members)) return throw_status(env, ZES_E_ARG);
   std::vector<uint64_t> off(with_index ? (size_t)members : 0);
-  ResultMem tmp = result_alloc(cap);
-  if (!tmp.p) return throw_status(env, ZES_E_ARG);
-  const int rc = zes_bgzip(in, n, tmp.p, cap, &out_len, with_index ? off.data() : nullptr, ZES_F_DEFAULT);
-  if (rc) {
-    result_free(tmp);
-    return throw_status(env, rc);
-  }
-  napi_value data = take_u8(env, tmp, out_len);
+  napi_value data = bounded(env, result_alloc(cap), [&](uint8_t* out, uint64_t* len) {
+    return zes_bgzip(in.p, in.n, out, cap, len, with_index ? off.data() : nullptr, ZES_F_DEFAULT);
+  });
   if (!with_index || !data) return data;
   napi_value res, arr;
   if (napi_create_object(env, &res) != napi_ok || napi_create_array_with_length(env, off.size(), &arr) != napi_ok) return nullptr;
@@ -616,17 +644,11 @@ napi_value BgzipIndex(napi_env env, napi_callback_info info) { return bgzip_comm
 // bgzfIndex(file): the member index of a BGZF file, { compressed, uncompressed }: two BigUint64Arrays of members + 1 entries
 // (include/zes.h: zes_bgzf_index, the host form: no device is touched)
 napi_value BgzfIndex(napi_env env, napi_callback_info info) {
-  size_t argc = 1;
-  napi_value argv[1];
-  napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr);
-  const uint8_t* in = nullptr;
-  size_t c = 0;
-  if (argc < 1 || !get_bytes(env, argv[0], &in, &c)) {
-    napi_throw_type_error(env, nullptr, "bgzfIndex(file): file must be a Uint8Array");
-    return nullptr;
-  }
+  const Args a = get_args(env, info);
+  const Bytes in = need_bytes(env, a, 0, "bgzfIndex(file)", "file");
+  if (!in.ok) return nullptr;
   uint64_t members = 0;
-  int rc = zes_bgzf_index(in, c, nullptr, nullptr, 0, &members, ZES_F_DEFAULT);  // (the count: ZES_E_NOSPACE on a valid file)
+  int rc = zes_bgzf_index(in.p, in.n, nullptr, nullptr, 0, &members, ZES_F_DEFAULT);  // (the count: ZES_E_NOSPACE on a valid file)
   if (rc != ZES_E_NOSPACE) return throw_status(env, rc ? rc : ZES_E_ARG);
   napi_value res, ab[2], ta[2];
   void* mem[2] = {nullptr, nullptr};
@@ -634,26 +656,12 @@ napi_value BgzfIndex(napi_env env, napi_callback_info info) {
   for (int k = 0; k < 2; k++)
     if (napi_create_arraybuffer(env, entries * 8, &mem[k], &ab[k]) != napi_ok || napi_create_typedarray(env, napi_biguint64_array, entries, ab[k], 0, &ta[k]) != napi_ok)
       return nullptr;
-  rc = zes_bgzf_index(in, c, static_cast<uint64_t*>(mem[0]), static_cast<uint64_t*>(mem[1]), entries, &members, ZES_F_DEFAULT);
+  rc = zes_bgzf_index(in.p, in.n, static_cast<uint64_t*>(mem[0]), static_cast<uint64_t*>(mem[1]), entries, &members, ZES_F_DEFAULT);
   if (rc) return throw_status(env, rc);
   if (napi_create_object(env, &res) != napi_ok) return nullptr;
   napi_set_named_property(env, res, "compressed", ta[0]);
   napi_set_named_property(env, res, "uncompressed", ta[1]);
   return res;
-}
-
-// a position or length: a non-negative safe integer as a number, or a bigint below 2^64
-bool get_offset(napi_env env, napi_value v, uint64_t* out) {
-  napi_valuetype vt;
-  if (napi_typeof(env, v, &vt) != napi_ok) return false;
-  if (vt == napi_bigint) {
-    bool lossless = false;
-    return napi_get_value_bigint_uint64(env, v, out, &lossless) == napi_ok && lossless;
-  }
-  double d = 0;
-  if (vt != napi_number || napi_get_value_double(env, v, &d) != napi_ok || !(d >= 0) || d > 9007199254740991.0 || d != (double)(uint64_t)d) return false;
-  *out = (uint64_t)d;
-  return true;
 }
 
 bool get_u64_array(napi_env env, napi_value v, const uint64_t** data, size_t* len) {
@@ -671,114 +679,59 @@ bool get_u64_array(napi_env env, napi_value v, const uint64_t** data, size_t* le
 // bgzfRead(file, index, pos, len): bytes [pos, pos + len) of the uncompressed data, clipped at its end, through the index
 // bgzfIndex(file) returned; only the members that hold the range are uploaded and decoded (include/zes.h: zes_bgzf_read)
 napi_value BgzfRead(napi_env env, napi_callback_info info) {
-  size_t argc = 4;
-  napi_value argv[4];
-  napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr);
-  const uint8_t* in = nullptr;
-  size_t c = 0;
-  if (argc < 4 || !get_bytes(env, argv[0], &in, &c)) {
-    napi_throw_type_error(env, nullptr, "bgzfRead(file, index, pos, len): file must be a Uint8Array");
-    return nullptr;
-  }
+  static const char SIG[] = "bgzfRead(file, index, pos, len)";
+  const Args a = get_args(env, info);
+  const Bytes in = need_bytes(env, a, 0, SIG, "file");
+  if (!in.ok) return nullptr;
   const uint64_t *coff = nullptr, *uoff = nullptr;
   size_t nc = 0, nu = 0;
   napi_value vc, vu;
-  if (napi_get_named_property(env, argv[1], "compressed", &vc) != napi_ok || napi_get_named_property(env, argv[1], "uncompressed", &vu) != napi_ok ||
-      !get_u64_array(env, vc, &coff, &nc) || !get_u64_array(env, vu, &uoff, &nu) || nc != nu || nc < 2) {
-    napi_throw_type_error(env, nullptr, "bgzfRead(file, index, pos, len): index must be what bgzfIndex(file) returned");
-    return nullptr;
-  }
+  if (napi_get_named_property(env, a.argv[1], "compressed", &vc) != napi_ok || napi_get_named_property(env, a.argv[1], "uncompressed", &vu) != napi_ok ||
+      !get_u64_array(env, vc, &coff, &nc) || !get_u64_array(env, vu, &uoff, &nu) || nc != nu || nc < 2)
+    return throw_type(env, std::string(SIG) + ": index must be what bgzfIndex(file) returned");
   uint64_t pos = 0, len = 0;
-  if (!get_offset(env, argv[2], &pos) || !get_offset(env, argv[3], &len)) {
-    napi_throw_type_error(env, nullptr, "bgzfRead(file, index, pos, len): pos and len must be non-negative safe integers or bigints");
-    return nullptr;
-  }
+  if (!get_offset(env, a.argv[2], &pos) || !get_offset(env, a.argv[3], &len))
+    return throw_type(env, std::string(SIG) + ": pos and len must be non-negative safe integers or bigints");
   const uint64_t total = uoff[nu - 1];
   const uint64_t cap = pos <= total ? std::min<uint64_t>(len, total - pos) : 0;  // (pos > total: the library answers ZES_E_ARG)
-  ResultMem tmp = result_alloc((size_t)cap);
-  if (!tmp.p) return throw_status(env, ZES_E_ARG);
-  uint64_t out_len = 0;
-  const int rc = zes_bgzf_read(in, c, coff, uoff, nu - 1, pos, len, tmp.p, cap, &out_len, ZES_F_DEFAULT);
-  if (rc) {
-    result_free(tmp);
-    return throw_status(env, rc);
-  }
-  return take_u8(env, tmp, out_len);
+  return bounded(env, result_alloc((size_t)cap), [&](uint8_t* out, uint64_t* out_len) {
+    return zes_bgzf_read(in.p, in.n, coff, uoff, nu - 1, pos, len, out, cap, out_len, ZES_F_DEFAULT);
+  });
 }
 
 // gunzip(input): every member of a gzip file, their outputs concatenated; one decode, then the exact-size result
-struct GunzipAlloc {
-  ResultMem m;
-  bool failed = false;
-};
-uint8_t* gunzip_alloc(void* user, uint32_t, uint64_t n) {
-  GunzipAlloc* a = static_cast<GunzipAlloc*>(user);
-  result_free(a->m);
-  a->m = result_alloc((size_t)n, false);  // (inside the library's call: a pooled block or malloc, never zes_host_alloc)
-  if (!a->m.p) a->failed = true;
-  return a->m.p;
-}
-
 napi_value Gunzip(napi_env env, napi_callback_info info) {
-  size_t argc = 1;
-  napi_value argv[1];
-  napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr);
-  const uint8_t* in = nullptr;
-  size_t c = 0;
-  if (argc < 1 || !get_bytes(env, argv[0], &in, &c)) {
-    napi_throw_type_error(env, nullptr, "gunzip(input): input must be a Uint8Array");
-    return nullptr;
-  }
-  GunzipAlloc ga;
+  const Args a = get_args(env, info);
+  const Bytes in = need_bytes(env, a, 0, "gunzip(input)", "input");
+  if (!in.ok) return nullptr;
+  ExactMem ga;
   uint64_t out_len = 0;
-  const int rc = zes_gunzip_alloc(in, c, gunzip_alloc, &ga, &out_len, ZES_F_DEFAULT);
+  const int rc = zes_gunzip_alloc(in.p, in.n, exact_alloc, &ga, &out_len, ZES_F_DEFAULT);
   if (rc) {
-    result_free(ga.m);
+    ga.drop();
     return throw_status(env, ga.failed ? ZES_E_ARG : rc);
   }
-  return take_u8(env, ga.m, out_len);
+  return take_u8(env, ga.m, (size_t)out_len);
 }
 
 napi_value Adler32(napi_env env, napi_callback_info info) {
-  size_t argc = 1;
-  napi_value argv[1];
-  napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr);
-  const uint8_t* in = nullptr;
-  size_t n = 0;
-  if (argc < 1 || !get_bytes(env, argv[0], &in, &n)) {
-    napi_throw_type_error(env, nullptr, "adler32(input): input must be a Uint8Array");
-    return nullptr;
-  }
-  uint32_t a = 0;
-  const int rc = zes_adler32(in, n, &a);
+  const Args a = get_args(env, info);
+  const Bytes in = need_bytes(env, a, 0, "adler32(input)", "input");
+  if (!in.ok) return nullptr;
+  uint32_t sum = 0;
+  const int rc = zes_adler32(in.p, in.n, &sum);
   if (rc) return throw_status(env, rc);
   napi_value v;
-  napi_create_uint32(env, a, &v);
+  napi_create_uint32(env, sum, &v);
   return v;
 }
 
-napi_value Init(napi_env env, napi_callback_info info) {
-  size_t argc = 1;
-  napi_value argv[1];
-  napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr);
-  int32_t dev = 0;
-  if (argc >= 1) napi_get_value_int32(env, argv[0], &dev);
-  const int rc = zes_init(dev);
-  if (rc) return throw_status(env, rc);
-  napi_value v;
-  napi_get_undefined(env, &v);
-  return v;
-}
+napi_value Init(napi_env env, napi_callback_info info) { return undefined_unless(env, zes_init(int32_or_0(env, get_args(env, info).argv[0]))); }
 
 // initDevices(n): one process, n GPUs (n omitted or <= 0: every visible one) — the batch calls then partition their
 // buffers over all of them, single calls take them in turn (zes_init_devices).  Returns the number of devices in use.
 napi_value InitDevices(napi_env env, napi_callback_info info) {
-  size_t argc = 1;
-  napi_value argv[1];
-  napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr);
-  int32_t n = 0;
-  if (argc >= 1) napi_get_value_int32(env, argv[0], &n);
-  const int rc = zes_init_devices(n);
+  const int rc = zes_init_devices(int32_or_0(env, get_args(env, info).argv[0]));
   if (rc) return throw_status(env, rc);
   napi_value v;
   napi_create_int32(env, zes_device_count(), &v);
@@ -792,188 +745,167 @@ napi_value LastGunzipMembers(napi_env env, napi_callback_info) {
   return v;
 }
 
-// trim(): the library's pooled device scratch goes back to the driver (zes_trim); the next call allocates again
+// trim(): the addon's pooled blocks, the calling environment's scratch block and the library's pooled device scratch go
+// back to the driver (zes_trim); the next call allocates again
 napi_value Trim(napi_env env, napi_callback_info) {
   g_big.clear();
-  g_sync_scratch.clear();
-  const int rc = zes_trim();
-  if (rc) return throw_status(env, rc);
-  napi_value v;
-  napi_get_undefined(env, &v);
-  return v;
+  if (EnvState* es = tracks_of(env)) es->scratch.clear();
+  return undefined_unless(env, zes_trim());
 }
 
 // ---- Promise-returning forms: the blocking C-ABI call runs on a libuv worker thread ----
-struct AsyncJob {
+struct Job {
   napi_async_work work = nullptr;
   napi_deferred deferred = nullptr;
-  napi_ref input_ref = nullptr;  // keeps the caller's array alive (and its memory in place) while the worker reads it
-  const uint8_t* in = nullptr;
-  size_t n = 0;
-  bool inflate = false;
-  uint32_t flags = 0;  // inflate: ZES_F_CHECK_ADLER when the caller asked for { verify: true }
-  ResultMem out;
-  uint64_t out_len = 0;
-  int rc = 0;
+  napi_ref input_ref = nullptr;  // keeps the caller's value alive (and its memory in place) while the worker reads it
 };
-
-uint8_t* async_alloc(void* user, uint32_t index, uint64_t n) {  // zes_alloc_fn on the worker thread: pool or malloc, no N-API calls
-  AsyncJob* j = static_cast<AsyncJob*>(user);
-  result_free(j->out);  // (ZES_F_ALLOC_BOUND: see sync_alloc)
-  if (index & ZES_ALLOC_EARLY) {
-    j->out = early_alloc((size_t)n);
-    return j->out.p;
-  }
-  j->out = result_alloc((size_t)n, false);  // (inside the library's call)
-  return j->out.p;
-}
-
-void async_execute(napi_env, void* data) {  // worker thread: no N-API calls here
-  AsyncJob* j = static_cast<AsyncJob*>(data);
-  if (!j->inflate) {
-    uint64_t cap = 0;
-    zes_deflate_bound(j->n, &cap);
-    j->out = result_alloc(cap ? cap : 1);
-    j->rc = j->out.p ? zes_deflate(j->in, j->n, j->out.p, cap, &j->out_len) : ZES_E_ARG;
-    return;
-  }
-  // one call: the library decodes, then asks for memory of the exact size (no state is kept in the library between calls)
-  j->rc = zes_inflate_alloc(j->in, j->n, async_alloc, j, &j->out_len, ZES_F_ALLOC_BOUND | j->flags);
-  g_big.top_up();
-}
-
-
-void async_complete(napi_env env, napi_status, void* data) {  // JS thread again
-  AsyncJob* j = static_cast<AsyncJob*>(data);
-  napi_value result = nullptr;
-  bool ok = j->rc == 0;
-  if (ok) {
-    // the worker's memory becomes the result's ArrayBuffer (exact length, no copy on the JS thread)
-    result = take_u8(env, j->out, (size_t)j->out_len);
-    j->out = ResultMem();  // owned by the ArrayBuffer now (or given back by take_u8)
-    if (!result) {
-      ok = false;
-      j->rc = ZES_E_ARG;
-    }
-  }
-  if (ok) {
-    napi_resolve_deferred(env, j->deferred, result);
-  } else {
-    napi_value msg, err;
-    napi_create_string_utf8(env, zes_strerror(j->rc), NAPI_AUTO_LENGTH, &msg);
-    napi_create_error(env, nullptr, msg, &err);  // plain Error with the reference's message, as a rejection
-    napi_reject_deferred(env, j->deferred, err);
-  }
-  result_free(j->out);
-  napi_delete_reference(env, j->input_ref);
-  napi_delete_async_work(env, j->work);
-  delete j;
-}
-
-napi_value start_async(napi_env env, napi_callback_info info, bool inflate) {
-  size_t argc = 2;
-  napi_value argv[2];
-  napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr);
-  const uint8_t* in = nullptr;
-  size_t n = 0;
-  if (argc < 1 || !get_bytes(env, argv[0], &in, &n)) {
-    napi_throw_type_error(env, nullptr, inflate ? "inflateAsync(input): input must be a Uint8Array" : "deflateAsync(input): input must be a Uint8Array");
-    return nullptr;
-  }
-  AsyncJob* j = new AsyncJob();
-  j->in = in;
-  j->n = n;
-  j->inflate = inflate;
-  if (inflate) j->flags = verify_flag(env, argc, argv, 1);
+// The promise of a job, and the job on its way to a worker thread; takes the job over.  The reference on `keep` keeps the
+// input (and its memory) alive while the worker reads it.  The caller must not transfer or detach its ArrayBuffer
+// before the promise settles (documented in zlib.ts): N-API v3 has no way to pin a backing store against a transfer.
+template <class J>
+napi_value start_job(napi_env env, J* j, napi_value keep, const char* work_name, napi_async_execute_callback execute, napi_async_complete_callback complete) {
   napi_value promise, name;
   if (napi_create_promise(env, &j->deferred, &promise) != napi_ok) {
     delete j;
     napi_throw_error(env, nullptr, "zes: could not create a promise");
     return nullptr;
   }
-  // The reference on the array keeps it (and its memory) alive while the worker reads it.  The caller must not
-  // transfer or detach its ArrayBuffer before the promise settles (documented in zlib.ts): N-API v3 has no way to
-  // pin a backing store against a transfer.
-  bool ok = napi_create_reference(env, argv[0], 1, &j->input_ref) == napi_ok &&
-            napi_create_string_utf8(env, inflate ? "zes_inflate" : "zes_deflate", NAPI_AUTO_LENGTH, &name) == napi_ok &&
-            napi_create_async_work(env, nullptr, name, async_execute, async_complete, j, &j->work) == napi_ok;
+  bool ok = napi_create_reference(env, keep, 1, &j->input_ref) == napi_ok && napi_create_string_utf8(env, work_name, NAPI_AUTO_LENGTH, &name) == napi_ok &&
+            napi_create_async_work(env, nullptr, name, execute, complete, j, &j->work) == napi_ok;
   if (ok && napi_queue_async_work(env, j->work) != napi_ok) {
     napi_delete_async_work(env, j->work);
     ok = false;
   }
   if (!ok) {  // nothing was queued: settle the promise here, free the job
-    napi_value msg, err;
-    napi_create_string_utf8(env, "zes: could not queue the work", NAPI_AUTO_LENGTH, &msg);
-    napi_create_error(env, nullptr, msg, &err);
-    napi_reject_deferred(env, j->deferred, err);
+    napi_reject_deferred(env, j->deferred, make_error(env, "zes: could not queue the work"));
     if (j->input_ref) napi_delete_reference(env, j->input_ref);
     delete j;
   }
   return promise;
+}
+// the end of a completion, on the JS thread again: the promise settles (no result: a plain Error with the status's
+// message, as a rejection), the input is let go, the job ends
+template <class J>
+void finish_job(napi_env env, J* j, napi_value result, int rc) {
+  if (result)
+    napi_resolve_deferred(env, j->deferred, result);
+  else
+    napi_reject_deferred(env, j->deferred, make_error(env, zes_strerror(rc ? rc : ZES_E_ARG)));
+  napi_delete_reference(env, j->input_ref);
+  napi_delete_async_work(env, j->work);
+  delete j;
+}
+
+struct AsyncJob : Job {
+  Bytes in;
+  bool inflate = false;
+  uint32_t flags = 0;  // inflate: ZES_F_CHECK_ADLER when the caller asked for { verify: true }
+  ExactMem out;
+  uint64_t out_len = 0;
+  int rc = 0;
+  ~AsyncJob() { out.drop(); }  // (what no ArrayBuffer took over)
+};
+
+uint8_t* async_alloc(void* user, uint32_t index, uint64_t n) {  // zes_alloc_fn on the worker thread: pool or malloc, no N-API calls
+  ExactMem& out = static_cast<AsyncJob*>(user)->out;
+  if (!(index & ZES_ALLOC_EARLY)) return out.renew((size_t)n);
+  out.drop();
+  out.m = pooled((size_t)n);  // (an early request is only worth taking with a pooled block: see sync_alloc)
+  return out.m.p;
+}
+
+void async_execute(napi_env, void* data) {  // worker thread: no N-API calls here
+  AsyncJob* j = static_cast<AsyncJob*>(data);
+  if (!j->inflate) {
+    uint64_t cap = 0;
+    zes_deflate_bound(j->in.n, &cap);
+    const Filled f = fill(result_alloc(cap), [&](uint8_t* out, uint64_t* len) { return zes_deflate(j->in.p, j->in.n, out, cap, len); });
+    j->out.m = f.m;
+    j->out_len = f.len;
+    j->rc = f.rc;
+    return;
+  }
+  // one call: the library decodes, then asks for memory of the exact size (no state is kept in the library between calls)
+  j->rc = zes_inflate_alloc(j->in.p, j->in.n, async_alloc, j, &j->out_len, ZES_F_ALLOC_BOUND | j->flags);
+  g_big.top_up();
+}
+
+void async_complete(napi_env env, napi_status, void* data) {  // JS thread again
+  AsyncJob* j = static_cast<AsyncJob*>(data);
+  napi_value result = nullptr;
+  if (j->rc == 0) {
+    // the worker's memory becomes the result's ArrayBuffer (exact length, no copy on the JS thread)
+    result = take_u8(env, j->out.m, (size_t)j->out_len);
+    j->out.m = ResultMem();  // owned by the ArrayBuffer now (or given back by take_u8)
+  }
+  finish_job(env, j, result, j->rc);
+}
+
+napi_value start_async(napi_env env, napi_callback_info info, bool inflate) {
+  const Args a = get_args(env, info);
+  const Bytes in = need_bytes(env, a, 0, inflate ? "inflateAsync(input)" : "deflateAsync(input)", "input");
+  if (!in.ok) return nullptr;
+  AsyncJob* j = new AsyncJob();
+  j->in = in;
+  j->inflate = inflate;
+  if (inflate) j->flags = verify_flag(env, a, 1);
+  return start_job(env, j, a.argv[0], inflate ? "zes_inflate" : "zes_deflate", async_execute, async_complete);
 }
 napi_value DeflateAsync(napi_env env, napi_callback_info info) { return start_async(env, info, false); }
 napi_value InflateAsync(napi_env env, napi_callback_info info) { return start_async(env, info, true); }
 
 // ---- batch forms (deflateBatch / inflateBatch): an array of independent buffers in one call, so that
 // small buffers share the launches and fill the chip together (zes_deflate_batch / zes_inflate_batch_alloc) ----
-struct BatchJob {
-  napi_async_work work = nullptr;
-  napi_deferred deferred = nullptr;  // null: synchronous call
-  napi_ref input_ref = nullptr;
+struct BatchJob : Job {  // (deferred null: a synchronous call)
   bool inflate = false;
   uint32_t flags = 0;  // inflate: ZES_F_CHECK_ADLER when the caller asked for { verify: true }
-  uint32_t count = 0;
-  const uint8_t** in = nullptr;
-  uint64_t* in_len = nullptr;
-  uint8_t** out = nullptr;
-  size_t* out_pool = nullptr;  // capacity of the pooled block behind out[i], or 0: malloc'd
-  uint64_t* out_cap = nullptr;
-  uint64_t* out_len = nullptr;
-  int32_t* status = nullptr;
+  uint32_t count;
+  // one element more than count: an empty batch still hands the library pointers (zes_deflate_batch answers ZES_E_ARG to
+  // a null one) and returns []
+  std::vector<const uint8_t*> in;
+  std::vector<uint64_t> in_len;
+  std::vector<uint8_t*> out;
+  std::vector<size_t> out_pool;  // capacity of the pooled block behind out[i], or 0: malloc'd
+  std::vector<uint64_t> out_cap, out_len;
+  std::vector<int32_t> status;
   int rc = 0;
-  ~BatchJob() {
-    if (out)
-      for (uint32_t i = 0; i < count; i++) {
-        ResultMem m;
-        m.p = out[i];
-        m.cap = out_pool ? out_pool[i] : 0;
-        result_free(m);
-      }
-    delete[] out_pool;
-    delete[] in;
-    delete[] in_len;
-    delete[] out;
-    delete[] out_cap;
-    delete[] out_len;
-    delete[] status;
+  explicit BatchJob(uint32_t n)
+      : count(n), in((size_t)n + 1), in_len((size_t)n + 1), out((size_t)n + 1), out_pool((size_t)n + 1), out_cap((size_t)n + 1), out_len((size_t)n + 1), status((size_t)n + 1) {}
+  uint8_t* put(uint32_t i, ResultMem m) {
+    out[i] = m.p;
+    out_pool[i] = m.cap;
+    return m.p;
+  }
+  ResultMem claim(uint32_t i) {  // out[i] is the caller's from here on
+    ResultMem m;
+    m.p = out[i];
+    m.cap = out_pool[i];
+    put(i, ResultMem());
+    return m;
+  }
+  ~BatchJob() {  // (the blocks no ArrayBuffer took over)
+    for (uint32_t i = 0; i < count; i++) result_free(claim(i));
   }
 };
 
-uint8_t* batch_alloc(void* user, uint32_t i, uint64_t n) {  // any thread: plain malloc, wrapped into an ArrayBuffer later
-  BatchJob* j = static_cast<BatchJob*>(user);
-  const ResultMem m = result_alloc((size_t)n, false);  // (inside the library's call, possibly on one of its threads)
-  j->out[i] = m.p;
-  j->out_pool[i] = m.cap;
-  return j->out[i];
+uint8_t* batch_alloc(void* user, uint32_t i, uint64_t n) {  // any thread: pool or malloc, wrapped into an ArrayBuffer later
+  return static_cast<BatchJob*>(user)->put(i, result_alloc((size_t)n, false));  // (inside the library's call, possibly on one of its threads)
 }
 
 void batch_execute(napi_env, void* data) {
   BatchJob* j = static_cast<BatchJob*>(data);
   if (j->inflate) {
-    j->rc = zes_inflate_batch_alloc(j->in, j->in_len, batch_alloc, j, j->out_len, j->status, j->count, ZES_F_DEFAULT | j->flags);
+    j->rc = zes_inflate_batch_alloc(j->in.data(), j->in_len.data(), batch_alloc, j, j->out_len.data(), j->status.data(), j->count, ZES_F_DEFAULT | j->flags);
     return;
   }
   for (uint32_t i = 0; i < j->count; i++) {
     zes_deflate_bound(j->in_len[i], &j->out_cap[i]);
-    const ResultMem m = result_alloc((size_t)j->out_cap[i]);
-    j->out[i] = m.p;
-    j->out_pool[i] = m.cap;
-    if (!j->out[i]) {
+    if (!j->put(i, result_alloc((size_t)j->out_cap[i]))) {
       j->rc = ZES_E_ARG;
       return;
     }
   }
-  j->rc = zes_deflate_batch(j->in, j->in_len, j->out, j->out_cap, j->out_len, j->status, j->count);
+  j->rc = zes_deflate_batch(j->in.data(), j->in_len.data(), j->out.data(), j->out_cap.data(), j->out_len.data(), j->status.data(), j->count);
 }
 
 // results: an array with, per buffer, a fresh Uint8Array or an Error carrying the reference's message
@@ -982,20 +914,8 @@ napi_value batch_results(napi_env env, BatchJob* j) {
   napi_value arr;
   if (napi_create_array_with_length(env, j->count, &arr) != napi_ok) return nullptr;
   for (uint32_t i = 0; i < j->count; i++) {
-    napi_value v = nullptr;
-    if (j->status[i] == 0) {
-      ResultMem m;
-      m.p = j->out[i];
-      m.cap = j->out_pool[i];
-      j->out[i] = nullptr;  // owned by the ArrayBuffer from here on (or given back by take_u8)
-      j->out_pool[i] = 0;
-      v = take_u8(env, m, (size_t)j->out_len[i]);
-      if (!v) return nullptr;
-    } else {
-      napi_value msg;
-      napi_create_string_utf8(env, zes_strerror(j->status[i]), NAPI_AUTO_LENGTH, &msg);
-      napi_create_error(env, nullptr, msg, &v);
-    }
+    napi_value v = j->status[i] == 0 ? take_u8(env, j->claim(i), (size_t)j->out_len[i]) : make_error(env, zes_strerror(j->status[i]));
+    if (!v) return nullptr;
     napi_set_element(env, arr, i, v);
   }
   return arr;
@@ -1003,79 +923,29 @@ napi_value batch_results(napi_env env, BatchJob* j) {
 
 void batch_complete(napi_env env, napi_status, void* data) {
   BatchJob* j = static_cast<BatchJob*>(data);
-  napi_value res = j->rc == 0 ? batch_results(env, j) : nullptr;
-  if (res) {
-    napi_resolve_deferred(env, j->deferred, res);
-  } else {
-    napi_value msg, err;
-    napi_create_string_utf8(env, zes_strerror(j->rc ? j->rc : ZES_E_ARG), NAPI_AUTO_LENGTH, &msg);
-    napi_create_error(env, nullptr, msg, &err);
-    napi_reject_deferred(env, j->deferred, err);
-  }
-  napi_delete_reference(env, j->input_ref);
-  napi_delete_async_work(env, j->work);
-  delete j;
+  finish_job(env, j, j->rc == 0 ? batch_results(env, j) : nullptr, j->rc);
 }
 
 napi_value start_batch(napi_env env, napi_callback_info info, bool inflate, bool async) {
-  size_t argc = 2;
-  napi_value argv[2];
-  napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr);
+  const Args a = get_args(env, info);
   bool is_arr = false;
   uint32_t count = 0;
-  if (argc < 1 || napi_is_array(env, argv[0], &is_arr) != napi_ok || !is_arr || napi_get_array_length(env, argv[0], &count) != napi_ok) {
-    napi_throw_type_error(env, nullptr, "batch(inputs): inputs must be an array of Uint8Array");
-    return nullptr;
-  }
-  BatchJob* j = new BatchJob();
+  if (a.argc < 1 || napi_is_array(env, a.argv[0], &is_arr) != napi_ok || !is_arr || napi_get_array_length(env, a.argv[0], &count) != napi_ok)
+    return throw_type(env, "batch(inputs): inputs must be an array of Uint8Array");
+  std::unique_ptr<BatchJob> j(new BatchJob(count));
   j->inflate = inflate;
-  if (inflate) j->flags = verify_flag(env, argc, argv, 1);
-  j->count = count;
-  j->in = new const uint8_t*[count + 1]();
-  j->in_len = new uint64_t[count + 1]();
-  j->out = new uint8_t*[count + 1]();
-  j->out_pool = new size_t[count + 1]();
-  j->out_cap = new uint64_t[count + 1]();
-  j->out_len = new uint64_t[count + 1]();
-  j->status = new int32_t[count + 1]();
+  if (inflate) j->flags = verify_flag(env, a, 1);
   for (uint32_t i = 0; i < count; i++) {
     napi_value e;
     size_t n = 0;
-    if (napi_get_element(env, argv[0], i, &e) != napi_ok || !get_bytes(env, e, &j->in[i], &n)) {
-      delete j;
-      napi_throw_type_error(env, nullptr, "batch(inputs): every element must be a Uint8Array");
-      return nullptr;
-    }
+    if (napi_get_element(env, a.argv[0], i, &e) != napi_ok || !get_bytes(env, e, &j->in[i], &n))
+      return throw_type(env, "batch(inputs): every element must be a Uint8Array");
     j->in_len[i] = n;
   }
-  if (!async) {
-    batch_execute(env, j);
-    napi_value res = j->rc == 0 ? batch_results(env, j) : throw_status(env, j->rc);
-    delete j;
-    return res;
-  }
-  napi_value promise, name;
-  if (napi_create_promise(env, &j->deferred, &promise) != napi_ok) {
-    delete j;
-    napi_throw_error(env, nullptr, "zes: could not create a promise");
-    return nullptr;
-  }
-  bool ok = napi_create_reference(env, argv[0], 1, &j->input_ref) == napi_ok &&  // the outer array keeps every element alive
-            napi_create_string_utf8(env, inflate ? "zes_inflate_batch" : "zes_deflate_batch", NAPI_AUTO_LENGTH, &name) == napi_ok &&
-            napi_create_async_work(env, nullptr, name, batch_execute, batch_complete, j, &j->work) == napi_ok;
-  if (ok && napi_queue_async_work(env, j->work) != napi_ok) {
-    napi_delete_async_work(env, j->work);
-    ok = false;
-  }
-  if (!ok) {
-    napi_value msg, err;
-    napi_create_string_utf8(env, "zes: could not queue the work", NAPI_AUTO_LENGTH, &msg);
-    napi_create_error(env, nullptr, msg, &err);
-    napi_reject_deferred(env, j->deferred, err);
-    if (j->input_ref) napi_delete_reference(env, j->input_ref);
-    delete j;
-  }
-  return promise;
+  if (async)  // (the outer array keeps every element alive)
+    return start_job(env, j.release(), a.argv[0], inflate ? "zes_inflate_batch" : "zes_deflate_batch", batch_execute, batch_complete);
+  batch_execute(env, j.get());
+  return j->rc == 0 ? batch_results(env, j.get()) : throw_status(env, j->rc);
 }
 napi_value DeflateBatch(napi_env env, napi_callback_info info) { return start_batch(env, info, false, false); }
 napi_value InflateBatch(napi_env env, napi_callback_info info) { return start_batch(env, info, true, false); }
@@ -1083,22 +953,16 @@ napi_value DeflateBatchAsync(napi_env env, napi_callback_info info) { return sta
 napi_value InflateBatchAsync(napi_env env, napi_callback_info info) { return start_batch(env, info, true, true); }
 
 // allocPinned(n): a Uint8Array in page-locked memory (zes_host_alloc) — buffers from here cross PCIe without the
-// library's staging copy; released when the array is collected.  The finalizer runs on the JS thread and takes
+// library's staging copy; released when the array is collected.  The release runs on the JS thread and takes
 // the library's lock for a moment (no stream is waited for: hipHostFree itself waits for work that uses the block), so
 // it can stall behind a call that is holding the lock; zes_host_free also works after zes_shutdown.
 napi_value AllocPinned(napi_env env, napi_callback_info info) {
-  size_t argc = 1;
-  napi_value argv[1];
-  napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr);
-  double d = -1;
-  if (argc < 1 || napi_get_value_double(env, argv[0], &d) != napi_ok || !(d >= 0) || d > 1e12 || d != (double)(uint64_t)d) {
-    napi_throw_type_error(env, nullptr, "allocPinned(n): n must be a non-negative integer");
-    return nullptr;
-  }
+  uint64_t n = 0;
+  if (!get_safe_uint(env, get_args(env, info).argv[0], &n) || n > 1000000000000ull) return throw_type(env, "allocPinned(n): n must be a non-negative integer");
   void* p = nullptr;
-  const int rc = zes_host_alloc((uint64_t)d, &p);
+  const int rc = zes_host_alloc(n, &p);
   if (rc) return throw_status(env, rc);
-  return adopt(env, static_cast<uint8_t*>(p), (size_t)d, 0, true);  // (released by a later call's sweep once the array is collected)
+  return adopt(env, static_cast<uint8_t*>(p), (size_t)n, 0, true);  // (released by a later call's sweep once the array is collected)
 }
 
 // every entry point first looks which arrays the collector has taken since the last call
@@ -1109,31 +973,36 @@ napi_value swept(napi_env env, napi_callback_info info) {
 }
 
 napi_value ModuleInit(napi_env env, napi_value exports) {
-  napi_property_descriptor props[] = {
-      {"deflate", nullptr, swept<Deflate>, nullptr, nullptr, nullptr, napi_default, nullptr},
-      {"inflate", nullptr, swept<Inflate>, nullptr, nullptr, nullptr, napi_default, nullptr},
-      {"deflateRaw", nullptr, swept<DeflateRaw>, nullptr, nullptr, nullptr, napi_default, nullptr},
-      {"inflateRaw", nullptr, swept<InflateRaw>, nullptr, nullptr, nullptr, napi_default, nullptr},
-      {"deflateAsync", nullptr, swept<DeflateAsync>, nullptr, nullptr, nullptr, napi_default, nullptr},
-      {"inflateAsync", nullptr, swept<InflateAsync>, nullptr, nullptr, nullptr, napi_default, nullptr},
-      {"deflateBatch", nullptr, swept<DeflateBatch>, nullptr, nullptr, nullptr, napi_default, nullptr},
-      {"inflateBatch", nullptr, swept<InflateBatch>, nullptr, nullptr, nullptr, napi_default, nullptr},
-      {"deflateBatchAsync", nullptr, swept<DeflateBatchAsync>, nullptr, nullptr, nullptr, napi_default, nullptr},
-      {"inflateBatchAsync", nullptr, swept<InflateBatchAsync>, nullptr, nullptr, nullptr, napi_default, nullptr},
-      {"allocPinned", nullptr, swept<AllocPinned>, nullptr, nullptr, nullptr, napi_default, nullptr},
-      {"adler32", nullptr, swept<Adler32>, nullptr, nullptr, nullptr, napi_default, nullptr},
-      {"gzip", nullptr, swept<Gzip>, nullptr, nullptr, nullptr, napi_default, nullptr},
-      {"gunzip", nullptr, swept<Gunzip>, nullptr, nullptr, nullptr, napi_default, nullptr},
-      {"bgzip", nullptr, swept<Bgzip>, nullptr, nullptr, nullptr, napi_default, nullptr},
-      {"bgzipIndex", nullptr, swept<BgzipIndex>, nullptr, nullptr, nullptr, napi_default, nullptr},
-      {"bgzfIndex", nullptr, swept<BgzfIndex>, nullptr, nullptr, nullptr, napi_default, nullptr},
-      {"bgzfRead", nullptr, swept<BgzfRead>, nullptr, nullptr, nullptr, napi_default, nullptr},
-      {"lastGunzipMembers", nullptr, swept<LastGunzipMembers>, nullptr, nullptr, nullptr, napi_default, nullptr},
-      {"init", nullptr, swept<Init>, nullptr, nullptr, nullptr, napi_default, nullptr},
-      {"initDevices", nullptr, swept<InitDevices>, nullptr, nullptr, nullptr, napi_default, nullptr},
-      {"trim", nullptr, swept<Trim>, nullptr, nullptr, nullptr, napi_default, nullptr},
+  const struct {
+    const char* name;
+    napi_callback fn;
+  } entries[] = {
+      {"deflate", swept<Deflate>},
+      {"inflate", swept<Inflate>},
+      {"deflateRaw", swept<DeflateRaw>},
+      {"inflateRaw", swept<InflateRaw>},
+      {"deflateAsync", swept<DeflateAsync>},
+      {"inflateAsync", swept<InflateAsync>},
+      {"deflateBatch", swept<DeflateBatch>},
+      {"inflateBatch", swept<InflateBatch>},
+      {"deflateBatchAsync", swept<DeflateBatchAsync>},
+      {"inflateBatchAsync", swept<InflateBatchAsync>},
+      {"allocPinned", swept<AllocPinned>},
+      {"adler32", swept<Adler32>},
+      {"gzip", swept<Gzip>},
+      {"gunzip", swept<Gunzip>},
+      {"bgzip", swept<Bgzip>},
+      {"bgzipIndex", swept<BgzipIndex>},
+      {"bgzfIndex", swept<BgzfIndex>},
+      {"bgzfRead", swept<BgzfRead>},
+      {"lastGunzipMembers", swept<LastGunzipMembers>},
+      {"init", swept<Init>},
+      {"initDevices", swept<InitDevices>},
+      {"trim", swept<Trim>},
   };
-  napi_define_properties(env, exports, sizeof(props) / sizeof(props[0]), props);
+  std::vector<napi_property_descriptor> props;
+  for (const auto& e : entries) props.push_back({e.name, nullptr, e.fn, nullptr, nullptr, nullptr, napi_default, nullptr});
+  napi_define_properties(env, exports, props.size(), props.data());
   if (getenv("ZES_NAPI_SEGV_TRACE")) {  // development: where a SIGSEGV comes from
     signal(SIGSEGV, [](int) {
       void* bt[64];
@@ -1145,10 +1014,10 @@ napi_value ModuleInit(napi_env env, napi_value exports) {
   g_envs.fetch_add(1);
   g_exiting.store(false);
   {
-    EnvTracks* et = new EnvTracks;
-    et->env = env;
+    EnvState* es = new EnvState;
+    es->env = env;
     std::lock_guard<std::mutex> lk(g_tracks_mu);
-    g_tracks.push_back(et);
+    g_tracks.push_back(es);
   }
   napi_add_env_cleanup_hook(env, env_cleanup, env);
   static bool once = false;

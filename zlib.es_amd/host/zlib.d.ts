@@ -1,4 +1,5 @@
 /** Same declarations as the reference's dist/tsc/zlib.d.ts:4-5, plus the raw, Promise and batch forms and the extras. */
+/** No returned Uint8Array (allocPinned()'s included) may be transferred or detached: its memory is reused once the original ArrayBuffer object is collected. */
 /** `verify: true`: the stream's Adler-32 trailer must be there and match the result, else the Error "zes: checksum mismatch". */
 export declare type InflateOptions = { verify?: boolean };
 export declare function inflate(input: Uint8Array, options?: InflateOptions): Uint8Array;

@@ -10,6 +10,10 @@
  *
  * zlib.js next to this file is generated from it by strip_types.py (this image has no tsc);
  * keep to erasable syntax: annotations on parameters / return types only.
+ *
+ * Every Uint8Array a function here returns, allocPinned()'s included, must not be transferred or detached (postMessage
+ * with a transfer list): its memory goes back to the addon's pool once the original ArrayBuffer object is collected, and
+ * a transfer leaves that object without it while the receiver still uses the bytes.  Pass a copy instead.
  */
 const addon = require('./build/zes_napi.node');
 
