@@ -129,7 +129,7 @@ int zes_deflate_bound(uint64_t n, uint64_t* cap);
  * Device forms (here and below): d_out, and in the batch forms every out_off, must be 16-byte aligned — results are
  * written as whole 16-byte groups — else ZES_E_ARG; the inflate device forms ask the same of d_in / in_off.  The
  * deflate device forms read an input at any alignment (the kernels fall back to narrower loads for an unaligned
- * block).  The host forms take any alignment. */
+ * block); zes_deflate_range_dev alone asks for an aligned d_in, see there.  The host forms take any alignment. */
 int zes_deflate(const uint8_t* in, uint64_t n, uint8_t* out, uint64_t cap, uint64_t* out_len);
 int zes_deflate_dev(const uint8_t* d_in, uint64_t n, uint8_t* d_out, uint64_t cap, uint64_t* out_len);
 
@@ -351,6 +351,8 @@ int zes_inflate_batch_alloc(const uint8_t* const* in, const uint64_t* in_len, ze
  *   (src/lz77.ts:78-85), so a range that is not the last needs that much of the next one behind it.  final_range != 0
  *   sets BFINAL on the range's last block (src/deflate.ts:21-27).  d_out receives the raw bit stream from bit 0
  *   ((*out_bits + 7) / 8 bytes, zero padded; cap >= zes_deflate_bound(n)); *adler = Adler-32 of the range's bytes.
+ *   Unlike the other deflate device forms it asks for a 16-byte aligned d_in as well as d_out, else ZES_E_ARG (decided
+ *   before any launch): a range starts on a block boundary of the caller's buffer, so it is aligned whenever that is.
  * zes_deflate_join_dev: 78 9C | the pieces, bit-concatenated | zero pad | Adler-32 of the whole (combined from the
  *   pieces' values and lengths: src/adler32.ts:1-10 is associative in that sense), into d_out.  The pieces are device
  *   pointers on this GPU (4-byte aligned), in order; they are read, and d_out is written, in whole dwords: piece i

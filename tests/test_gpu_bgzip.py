@@ -130,6 +130,19 @@ def test_every_source_alignment_of_stored_bodies(z, gpu, oracle):
         assert rc == 0 and got == want, at
 
 
+@pytest.mark.parametrize("kind", ("itext", "lowent4k"))
+def test_every_source_alignment_of_stream_bodies(z, gpu, oracle, kind):
+    """(A stream body is encoded from the caller's input where it lies: the deflate kernels' unaligned loads, on data with
+    matches — text for k_lz_sort's own sort, the 4 KiB pattern for k_lz_index.)"""
+    x, want = data_of(z, kind, 65280 + 100)
+    assert not E.plan(x)[2][0]  # the full chunk goes as a stream (the pattern's 100-byte tail goes stored)
+    rc, host, pos = host_form(z, x)
+    assert rc == 0 and host == want
+    for at in range(16):
+        rc, m, got, off = dev_form(z, gpu, x, in_at=at, out_at=(5 * at + 1) % 16)
+        assert rc == 0 and m == len(host) and got == host and off == pos, at
+
+
 # 4 ------------------------------------------------------------------------------------------------
 def test_group_seams(z, gpu, oracle):
     x, want = mixed(z, ["itext", "xorshift", "lowent4k", "xorshift", "itext", "lowent4k", "xorshift", "itext"], 2)

@@ -505,16 +505,17 @@ def adler32(data):
 
 # ---- HBM-resident API (torch uint8 CUDA tensors; torch is plumbing for device memory) --------
 def _aligned(t):
-    """The device forms need 16-byte aligned pointers (include/zes.h); a sliced view such as t[3:] is copied once."""
+    """The inflate and range device forms need a 16-byte aligned input (include/zes.h); a sliced view such as t[3:] is
+    copied once."""
     return t if t.data_ptr() % 16 == 0 else t.clone()
 
 
 def deflate_tensor(t, out=None):
-    """Compress a 1-D uint8 CUDA tensor; returns a view of ``out`` (allocated if None)."""
+    """Compress a 1-D uint8 CUDA tensor, which may start at any byte (zes_deflate_dev reads an input at any alignment);
+    returns a view of ``out`` (allocated if None)."""
     import torch
 
     assert t.is_cuda and t.dtype == torch.uint8 and t.is_contiguous()
-    t = _aligned(t)
     cap = deflate_bound(t.numel())
     if out is None:
         out = torch.empty(cap, dtype=torch.uint8, device=t.device)
@@ -684,7 +685,8 @@ def _batch_call(fn, d_in, in_off, in_len, d_out, out_off, out_cap, *extra):
 
 
 def deflate_batch_tensor(d_in, in_off, in_len, d_out, out_off, out_cap):
-    """Independent buffers inside one arena (offsets 16-byte aligned); returns (out_len[], status[])."""
+    """Independent buffers inside one arena: every in_off may be any byte, every out_off (and d_out) 16-byte aligned;
+    returns (out_len[], status[])."""
     return _batch_call(lib().zes_deflate_batch_dev, d_in, in_off, in_len, d_out, out_off, out_cap)
 
 
