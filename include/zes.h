@@ -40,7 +40,12 @@ typedef enum zes_status {
   ZES_E_ARG = -18,          /* bad argument (null pointer, size overflow) */
   ZES_E_NOTRANGE = -19,     /* zes_inflate_range_dev: the range does not hold a clean chain of reference-made blocks */
   ZES_E_GZIP = -20,         /* zes_gunzip*: not a gzip member (magic, CM, reserved flags, a header cut short), c == 0, or a trailer cut short */
-  ZES_E_CHECKSUM = -21      /* a trailer does not match the data: gzip CRC-32 / ISIZE / FHCRC, or zlib Adler-32 with ZES_F_CHECK_ADLER */
+  ZES_E_CHECKSUM = -21,     /* a trailer does not match the data: gzip CRC-32 / ISIZE / FHCRC, or zlib Adler-32 with ZES_F_CHECK_ADLER;
+                               zes_zip_read*: an entry's size, stream end or CRC-32 is not what its directory record says */
+  ZES_E_ZIP = -22,          /* zes_zip_*: not a ZIP archive this reader accepts, or an entry whose local header or sizes do not fit its
+                               directory record */
+  ZES_E_UNSUPPORTED = -23   /* zes_zip_*: a valid archive or entry that uses something this reader does not implement: ZIP64, several
+                               disks, encryption, a method other than 0 (stored) or 8 (DEFLATE) */
 } zes_status;
 
 /* Geometry of the reference format (src/const.ts:7). */
@@ -308,6 +313,78 @@ int zes_bgzf_read(const uint8_t* in, uint64_t c, const uint64_t* coff, const uin
                   uint8_t* out, uint64_t cap, uint64_t* out_len, uint32_t flags);
 int zes_bgzf_read_dev(const uint8_t* d_in, uint64_t c, const uint64_t* coff, const uint64_t* uoff, uint64_t members, uint64_t pos, uint64_t len,
                       uint8_t* d_out, uint64_t cap, uint64_t* out_len, uint32_t flags);
+
+/* ZIP archives (PKWARE APPNOTE 6.3): the entry index out of the central directory, and batch extraction through it.
+ * A reader only: ZIP64, archives over several disks, encryption and methods other than 0 and 8 are ZES_E_UNSUPPORTED.
+ *
+ * zes_zip_index*: the archive's entries in directory order, from the end record and the central directory alone; local
+ * headers are not looked at and nothing is decoded (as CPython's zipfile, the reader meets them when an entry is opened).
+ * Method and flags are copied as they are, so an archive with a bzip2 or an encrypted entry still lists.  The rule:
+ *   end record   scanning backwards from c - 22 over at most 65535 further positions, the first position p whose four bytes
+ *                are 50 4b 05 06 and for which p + 22 + comment length == c.  None, or c < 22: ZES_E_ZIP.  Stricter than
+ *                CPython 3.10 in one place (CPython accepts bytes behind the comment) and more lenient in another (CPython
+ *                takes the last signature even when it lies inside the comment, and then fails or lists nothing)
+ *   unsupported  either disk number non-zero, the two entry counts different, a count of 0xFFFF, a directory size or
+ *                offset of 0xFFFFFFFF, a ZIP64 locator 50 4b 06 07 at p - 20: ZES_E_UNSUPPORTED
+ *   directory    cd_size + cd_off > p: ZES_E_ZIP.  Else base = p - cd_size - cd_off is the length of whatever stands in
+ *                front of the archive (a self-extractor's stub), and the directory is [base + cd_off, p)
+ *   records      walked from the directory's first byte to exactly p: each starts with 50 4b 01 02, its 46 bytes plus name,
+ *                extra field and comment lie inside the directory, and there are as many as the end record says; else
+ *                ZES_E_ZIP.  A record's csize, usize or offset of 0xFFFFFFFF or a non-zero disk number: ZES_E_UNSUPPORTED.
+ *                hdr_off = base + offset must leave room for a local header in front of the directory,
+ *                hdr_off + 30 <= base + cd_off, else ZES_E_ZIP.  The first record in directory order that fails decides
+ * On ZES_OK `*entries` records are written to ent and the names, back to back, to names (`*names_len` bytes in all).
+ *   ZES_E_NOSPACE  cap < *entries or names_cap < *names_len: both counts are set, nothing is written.  ent == names == NULL
+ *                  with both capacities 0 asks for the counts: ZES_E_NOSPACE on every valid archive
+ *   ZES_E_ARG      a null entries or names_len, a null in with c != 0, any flag bit, ent or names null while its capacity
+ *                  is not 0
+ * The host form touches no device and works without one.  The device form takes d_in at any alignment, makes two
+ * device-to-host copies — the last min(c, 65557) bytes, then the directory — and runs the same host function on them; it
+ * launches no kernel.
+ * replaces: nothing (the reference has no ZIP container) */
+typedef struct zes_zip_entry {   /* 40 bytes, all little-endian host values */
+  uint64_t hdr_off;    /* the local header's position in the file (any prefix in front of the archive already added) */
+  uint64_t name_pos;   /* where the central directory's copy of the name lies in the file */
+  uint32_t csize, usize, crc;
+  uint32_t name_off;   /* the name inside the names blob the index call fills */
+  uint16_t name_len, method, flags, pad;   /* pad 0 */
+} zes_zip_entry;
+int zes_zip_index(const uint8_t* in, uint64_t c, zes_zip_entry* ent, uint64_t cap, uint64_t* entries, uint8_t* names, uint64_t names_cap,
+                  uint64_t* names_len, uint32_t flags);
+int zes_zip_index_dev(const uint8_t* d_in, uint64_t c, zes_zip_entry* ent, uint64_t cap, uint64_t* entries, uint8_t* names, uint64_t names_cap,
+                      uint64_t* names_len, uint32_t flags);
+
+/* zes_zip_read*: `count` entries of the index `ent[0, nent)` extracted as one batch: entry sel[i], or entry i when sel is NULL
+ * (then count <= nent).  Any order, duplicates included.  status[i] and out_len[i] are filled per entry (out_len[i] = usize on
+ * ZES_OK, else 0); the return value is non-zero only when the call as a whole could not run.
+ *   ZES_E_ARG   a null array with count != 0, a null file with c != 0, sel[i] >= nent, count > nent without sel, flag bits other
+ *               than ZES_F_PIECES (passed on to the inflate tiers)
+ *   count == 0  ZES_OK, no device work; zes_last_kernel_times then reports no launch and zes_last_inflate_tier 0, as after a
+ *               call that decoded nothing
+ * An entry's status, decided in this order:
+ *   1. from the entry alone, without a launch for it: flags & 0x61 (encrypted, patched data, strong encryption) or a method
+ *      other than 0 or 8: ZES_E_UNSUPPORTED; method 0 with csize != usize: ZES_E_ZIP; hdr_off + 30 > c or
+ *      name_pos + name_len > c (a stale or foreign index): ZES_E_ZIP; so is an entry whose name and csize bytes cannot lie
+ *      between hdr_off + 30 and c (step 2's last test, with an extra field of no bytes)
+ *   2. the local header, read from the file by k_zip_stage: ZES_E_ZIP unless its signature is 50 4b 03 04, its method is the
+ *      entry's, its flag bit 0 the entry's, its name length name_len, its name the name_len bytes at name_pos, and
+ *      hdr_off + 30 + name_len + extra length + csize <= c.  Its own CRC and size fields are not compared (with a data
+ *      descriptor, flag bit 3, they are zero)
+ *   3. method 8: the body decoded as by zes_inflate_raw_used, all bodies of the call in one pass through the inflate tiers; a
+ *      body that fails keeps its inflate status; ZES_E_CHECKSUM when the result is not usize bytes long, the stream does not
+ *      end in the body's last byte, or the CRC-32 differs
+ *   4. method 0: a copy, then the same CRC-32 check.  One segmented CRC-32 launch checks all results of both methods.
+ * The device form writes entry i to d_out + out_off[i] at any alignment: exactly usize bytes for an entry that checks out, and
+ * no byte outside the selected entries' ranges [out_off[i], out_off[i] + usize), which must not overlap; a failed entry's range
+ * is unspecified.  d_in at any alignment; it is read only inside the aligned 16-byte groups that hold bytes of [0, c).
+ * The alloc form calls alloc(user, i, usize) once per entry with ZES_OK, after it is checked (usize may be 0), never for a
+ * failed one (NULL from alloc: that entry is ZES_E_ARG); it uploads only the selected entries' header, name and data bytes, not
+ * the file, and runs on one context as the other single host calls do.
+ * replaces: nothing (the reference has no ZIP container) */
+int zes_zip_read_dev(const uint8_t* d_in, uint64_t c, const zes_zip_entry* ent, uint64_t nent, const uint32_t* sel, uint32_t count,
+                     uint8_t* d_out, const uint64_t* out_off, uint64_t* out_len, int32_t* status, uint32_t flags);
+int zes_zip_read_alloc(const uint8_t* in, uint64_t c, const zes_zip_entry* ent, uint64_t nent, const uint32_t* sel, uint32_t count,
+                       zes_alloc_fn alloc, void* user, uint64_t* out_len, int32_t* status, uint32_t flags);
 
 /* Adler-32 of a buffer (standard value as an unsigned 32-bit).
  * replaces: `calcAdler32` src/adler32.ts:1-10 (byte extraction at src/zlib.ts:37-40). */

@@ -43,6 +43,8 @@ ZES_ALLOC_EARLY = 0x80000000  # in the allocator's index argument: an early requ
 ZES_E_NOTRANGE = -19
 ZES_E_GZIP = -20  # zes_gunzip*: not a valid gzip member (header, or a trailer cut short), or no input at all
 ZES_E_CHECKSUM = -21  # a trailer does not match: gzip CRC-32 / ISIZE / FHCRC, zlib Adler-32 under ZES_F_CHECK_ADLER
+ZES_E_ZIP = -22  # zes_zip_*: not a ZIP archive this reader accepts, or an entry whose local header or sizes do not fit its directory record
+ZES_E_UNSUPPORTED = -23  # zes_zip_*: ZIP64, several disks, encryption, a method other than 0 or 8
 ZES_F_GZIP_SERIAL = 32  # zes_gunzip*: the members one after the other even where they could go as one batch (testing aid)
 ZES_F_INDEX_WALK = 64  # zes_bgzf_index_dev: the members by k_gz_walk's serial chain instead of the parallel finder (testing aid, baseline)
 ZES_F_CHECK_ADLER = 16  # zes_inflate*, the batch forms included: the Adler-32 trailer behind the stream must be there and match
@@ -61,6 +63,11 @@ class ZlibEsError(Exception):
 class ZesKTime(C.Structure):
     _fields_ = [("name", C.c_char_p), ("ms", C.c_float), ("launches", C.c_uint32)]
 
+
+# zes_zip_entry of include/zes.h: one record of a ZIP archive's index
+ZIP_ENTRY = np.dtype([("hdr_off", "<u8"), ("name_pos", "<u8"), ("csize", "<u4"), ("usize", "<u4"), ("crc", "<u4"), ("name_off", "<u4"),
+                      ("name_len", "<u2"), ("method", "<u2"), ("flags", "<u2"), ("pad", "<u2")])
+assert ZIP_ENTRY.itemsize == 40
 
 ALLOC_FN = C.CFUNCTYPE(C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint64)  # zes_alloc_fn of include/zes.h
 
@@ -124,6 +131,12 @@ def lib():
         for name in ("zes_bgzf_read", "zes_bgzf_read_dev"):
             getattr(L, name).argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_void_p, C.c_uint64,
                                          u64p, C.c_uint32]
+        for name in ("zes_zip_index", "zes_zip_index_dev"):
+            getattr(L, name).argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, u64p, C.c_void_p, C.c_uint64, u64p, C.c_uint32]
+        L.zes_zip_read_dev.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                       C.c_void_p, C.c_uint32]
+        L.zes_zip_read_alloc.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, ALLOC_FN, C.c_void_p, C.c_void_p,
+                                         C.c_void_p, C.c_uint32]
         L.zes_gunzip_alloc.argtypes = [C.c_void_p, C.c_uint64, ALLOC_FN, C.c_void_p, u64p, C.c_uint32]
         L.zes_adler32.argtypes = [C.c_void_p, C.c_uint64, u32p]
         L.zes_adler32_dev.argtypes = [C.c_void_p, C.c_uint64, u32p]
@@ -478,6 +491,67 @@ def bgzf_read(data, index, pos, length):
     return out[: n.value]
 
 
+def _zip_index_call(fn, ptr, c):
+    """(entries, names) of a ZIP archive through zes_zip_index / zes_zip_index_dev: the counts first, then the arrays."""
+    n, nl = C.c_uint64(), C.c_uint64()
+    rc = fn(ptr, c, None, 0, C.byref(n), None, 0, C.byref(nl), 0)
+    if rc != ZES_E_NOSPACE:
+        _raise(rc if rc else ZES_E_ARG)
+    ent = np.zeros(n.value, dtype=ZIP_ENTRY)
+    blob = np.zeros(max(nl.value, 1), dtype=np.uint8)
+    if n.value:
+        rc = fn(ptr, c, ent.ctypes.data, ent.size, C.byref(n), blob.ctypes.data, nl.value, C.byref(nl), 0)
+        if rc:
+            _raise(rc)
+    raw = blob.tobytes()
+    return ent, [raw[int(e["name_off"]) : int(e["name_off"]) + int(e["name_len"])] for e in ent]
+
+
+def _zip_entries(index):
+    ent = index[0] if isinstance(index, tuple) else index
+    ent = np.ascontiguousarray(ent, dtype=ZIP_ENTRY)
+    assert ent.ndim == 1, "a ZIP index is the structured array zip_index() returns (or its (entries, names) pair)"
+    return ent
+
+
+def _zip_sel(ent, sel):
+    if sel is None:
+        return None, ent.size
+    s = np.ascontiguousarray(sel, dtype=np.uint32)
+    assert s.ndim == 1
+    return s, s.size
+
+
+def zip_index(data):
+    """The entries of a ZIP archive in directory order (zes_zip_index; no GPU needed): ``(entries, names)``, a numpy
+    structured array with zes_zip_entry's layout (ZIP_ENTRY) and the names as a list of ``bytes``.  Nothing is decoded and
+    no local header is looked at; ZlibEsError(ZES_E_ZIP / ZES_E_UNSUPPORTED) for what the reader does not accept."""
+    a = _as_u8(data)
+    return _zip_index_call(lib().zes_zip_index, a.ctypes.data if a.size else None, a.size)
+
+
+def zip_read(data, index, sel=None):
+    """Entries ``sel`` (all when None; any order, duplicates fine) of a ZIP archive extracted as one batch through
+    ``index`` = ``zip_index(data)`` (zes_zip_read_alloc): a list with one uint8 array or one ZlibEsError per entry (not
+    raised, as with inflate_batch).  Only the selected entries' bytes are uploaded."""
+    a = _as_u8(data)
+    ent = _zip_entries(index)
+    s, cnt = _zip_sel(ent, sel)
+    got = {}
+
+    def alloc(_user, i, n):
+        got[i] = np.empty(max(int(n), 1), dtype=np.uint8)
+        return got[i].ctypes.data
+
+    out_len = (C.c_uint64 * max(cnt, 1))()
+    status = (C.c_int32 * max(cnt, 1))()
+    rc = lib().zes_zip_read_alloc(a.ctypes.data if a.size else None, a.size, ent.ctypes.data if ent.size else None, ent.size,
+                                  s.ctypes.data if s is not None and cnt else None, cnt, ALLOC_FN(alloc), None, out_len, status, 0)
+    if rc:
+        _raise(rc)
+    return [got[i][: out_len[i]] if status[i] == 0 else ZlibEsError(status[i], strerror(status[i])) for i in range(cnt)]
+
+
 def gunzip(data, flags=0):
     """gzip.decompress: every member, their outputs concatenated (zes_gunzip_alloc: one decode, an exact-size result)."""
     a = _as_u8(data)
@@ -668,6 +742,48 @@ def bgzf_read_tensor(t, index, pos, length, out, flags=0):
                                  C.byref(n), flags)
     _raise_need(rc, n)
     return out[: n.value]
+
+
+def zip_index_tensor(t):
+    """zip_index of a 1-D uint8 CUDA tensor (any alignment; zes_zip_index_dev): two copies to the host — the file's last
+    65557 bytes, then the directory — and no launch."""
+    import torch
+
+    assert t.is_cuda and t.dtype == torch.uint8 and t.is_contiguous()
+    torch.cuda.current_stream(t.device).synchronize()
+    return _zip_index_call(lib().zes_zip_index_dev, t.data_ptr() if t.numel() else None, t.numel())
+
+
+def zip_read_tensor(t, index, sel=None, out=None, off=None, flags=0):
+    """zip_read of a 1-D uint8 CUDA tensor (zes_zip_read_dev): ``(out, off, out_len, status)``.  Entry i of the selection is
+    written to ``out[off[i] : off[i] + usize]`` and nothing else is; ``t``, ``out`` and every offset may be any byte.  Without
+    ``off`` the entries are packed at 16-byte boundaries from the start of ``out``, which is allocated when it is None."""
+    import torch
+
+    assert t.is_cuda and t.dtype == torch.uint8 and t.is_contiguous()
+    ent = _zip_entries(index)
+    s, cnt = _zip_sel(ent, sel)
+    if s is not None and cnt and int(s.max()) >= ent.size:
+        _raise(ZES_E_ARG)
+    picked = ent if s is None else ent[s]
+    if off is None:  # packed at 16-byte boundaries
+        sizes = (picked["usize"].astype(np.uint64) + np.uint64(15)) & ~np.uint64(15)
+        off = np.concatenate([np.zeros(1, dtype=np.uint64), np.cumsum(sizes, dtype=np.uint64)])[: picked.size]
+        if out is None:
+            out = torch.empty(int(sizes.sum()) if picked.size else 0, dtype=torch.uint8, device=t.device)
+    assert out is not None and out.is_cuda and out.dtype == torch.uint8 and out.is_contiguous()
+    off = np.ascontiguousarray(off, dtype=np.uint64)
+    assert off.size == cnt, "zip_read_tensor: one offset per selected entry"
+    assert all(int(o) + int(e["usize"]) <= out.numel() for o, e in zip(off, picked)), "zip_read_tensor: an entry reaches beyond `out`"
+    torch.cuda.current_stream(t.device).synchronize()
+    out_len = np.zeros(max(cnt, 1), dtype=np.uint64)
+    status = np.zeros(max(cnt, 1), dtype=np.int32)
+    rc = lib().zes_zip_read_dev(t.data_ptr() if t.numel() else None, t.numel(), ent.ctypes.data if ent.size else None, ent.size,
+                                s.ctypes.data if s is not None and cnt else None, cnt, out.data_ptr() if out.numel() else None,
+                                off.ctypes.data if cnt else None, out_len.ctypes.data, status.ctypes.data, flags)
+    if rc:
+        _raise(rc)
+    return out, off, [int(x) for x in out_len[:cnt]], [int(x) for x in status[:cnt]]
 
 
 def _batch_call(fn, d_in, in_off, in_len, d_out, out_off, out_cap, *extra):

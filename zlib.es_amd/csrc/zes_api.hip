@@ -2859,6 +2859,8 @@ const char* zes_strerror(int status) {
     case ZES_E_NOTRANGE: return "zes: not a clean chain of reference-made blocks in this range";
     case ZES_E_GZIP: return "zes: not a valid gzip member (header or trailer)";
     case ZES_E_CHECKSUM: return "zes: checksum mismatch";
+    case ZES_E_ZIP: return "zes: not a valid ZIP archive or entry (end record, directory or local header)";
+    case ZES_E_UNSUPPORTED: return "zes: unsupported ZIP feature (ZIP64, several disks, encryption, a method other than 0 or 8)";
     default: return "zes: unknown status";
   }
 }
@@ -4400,6 +4402,22 @@ struct GzPart {
   uint32_t skip, take;
 };
 
+// What gz_decode_batch and zip_read_core share, stated once.  A body of `len` bytes stands in gz_bodies behind a 78 9C, in a slot
+// of gz_slot_in(len) bytes (the decoders read whole 16-byte groups, and some way past a stream's end); an output of m bytes
+// that cannot be decoded in place gets gz_slot_out(m) bytes of gz_outs, of which the job may write gz_slot_cap(m).
+static uint64_t gz_up16(uint64_t v) { return (v + 15) & ~15ull; }
+static uint64_t gz_slot_in(uint64_t len) { return gz_up16(2 + len) + 64; }
+static uint64_t gz_slot_cap(uint64_t m) { return std::max<uint64_t>(gz_up16(m), 16); }
+static uint64_t gz_slot_out(uint64_t m) { return gz_slot_cap(m) + 16; }
+// A body's job behind inflate_jobs (want_end set) against what its container says: the body's inflate status when it does not
+// decode; ZES_E_CHECKSUM when the output is not `want` bytes long (one that outgrew its capacity included) or the stream does
+// not end in the last of the body's `len` bytes; else ZES_OK (the CRC-32 is the caller's next step).
+static int gz_job_verdict(const InfJob& j, uint64_t want, uint64_t len) {
+  if (j.status != ZES_OK && j.status != ZES_E_NOSPACE) return j.status;
+  if (j.status != ZES_OK || j.out_len != want || j.end_bit < 16 || (j.end_bit - 16 + 7) / 8 != len) return ZES_E_CHECKSUM;
+  return ZES_OK;
+}
+
 // Members as one batch (gunzip_parallel: a whole file; bgzf_read_core: the members a range touches): one gather of the
 // bodies behind a 78 9C each, one inflate_jobs call, one gather of the outputs that could not be decoded in place, one
 // segmented CRC-32 launch.  Every member is decoded whole and must check out: *verdict is ZES_OK when all do, else what
@@ -4420,7 +4438,7 @@ static int gz_decode_batch(const uint8_t* d_src, const std::vector<GzPart>& ps, 
   if (!exact)
     for (uint32_t k = 0; k < n; k++)
       if (ps[k].m.isize) last_out = k;
-  auto up16 = [](uint64_t v) { return (v + 15) & ~15ull; };
+  auto up16 = gz_up16;
   auto whole = [&](uint32_t k) { return ps[k].skip == 0 && ps[k].take == ps[k].m.isize; };
   std::vector<char> direct(n);
   std::vector<uint64_t> islot(n), oslot(n);
@@ -4429,13 +4447,13 @@ static int gz_decode_batch(const uint8_t* d_src, const std::vector<GzPart>& ps, 
   for (uint32_t k = 0; k < n; k++) {
     const uint64_t dlen = ps[k].m.size - ps[k].m.hlen - 8, m = ps[k].m.isize;
     islot[k] = ipos;
-    ipos += up16(2 + dlen) + 64;
+    ipos += gz_slot_in(dlen);
     segs[k] = ZesGzSeg{ps[k].pos + ps[k].m.hlen, islot[k] + 2, dlen, 1u, 0u};
     direct[k] = dst && m && whole(k) && ((uintptr_t)(dst + ps[k].dst_off) & 15u) == 0 &&
                 ((m & 15u) == 0 || ((int64_t)k == last_out && up16(ps[k].dst_off + m) <= dst_cap));
     if (!direct[k]) {
       oslot[k] = opos;
-      opos += std::max<uint64_t>(up16(m), 16) + 16;
+      opos += gz_slot_out(m);
     }
   }
   if ((rc = ensure(g.gz_bodies, ipos + 64)) || (rc = ensure(g.gz_outs, opos + 64))) {
@@ -4450,7 +4468,7 @@ static int gz_decode_batch(const uint8_t* d_src, const std::vector<GzPart>& ps, 
   for (uint32_t k = 0; k < n; k++) {
     const uint64_t dlen = ps[k].m.size - ps[k].m.hlen - 8, m = ps[k].m.isize;
     uint8_t* to = direct[k] ? dst + ps[k].dst_off : outs + oslot[k];
-    jobs[k] = InfJob{islot[k], 2 + dlen, (uint64_t)(to - base), direct[k] ? m : std::max<uint64_t>(up16(m), 16), 0, ZES_OK, 0};
+    jobs[k] = InfJob{islot[k], 2 + dlen, (uint64_t)(to - base), direct[k] ? m : gz_slot_cap(m), 0, ZES_OK, 0};
     jobs[k].want_end = true;
   }
   const std::vector<uint8_t> firsts(n, 0x78);
@@ -4460,11 +4478,7 @@ static int gz_decode_batch(const uint8_t* d_src, const std::vector<GzPart>& ps, 
   if (stamps) stamps[1] = std::chrono::steady_clock::now();
   for (uint32_t k = 0; k < n; k++) {
     const uint64_t dlen = ps[k].m.size - ps[k].m.hlen - 8;
-    if (jobs[k].status != ZES_OK && jobs[k].status != ZES_E_NOSPACE)
-      *verdict = jobs[k].status;
-    else if (jobs[k].status != ZES_OK || jobs[k].out_len != ps[k].m.isize || jobs[k].end_bit < 16 || (jobs[k].end_bit - 16 + 7) / 8 != dlen)
-      *verdict = ZES_E_CHECKSUM;
-    if (*verdict) return ZES_OK;
+    if ((*verdict = gz_job_verdict(jobs[k], ps[k].m.isize, dlen))) return ZES_OK;
   }
   // a whole member's output is checked where it ends up, a trimmed one's in its slot
   segs.clear();
@@ -4824,6 +4838,348 @@ int zes_bgzf_read(const uint8_t* in, uint64_t c, const uint64_t* coff, const uin
   collect_times();
   if (rc) return rc;
   return download(out, (const uint8_t*)g.gz_acc.p, n);
+}
+
+// ---- ZIP archives (include/zes.h: "ZIP archives"): the entry index and batch extraction through it ----
+static uint32_t get_le16(const uint8_t* p) { return (uint32_t)p[0] | (uint32_t)p[1] << 8; }
+
+constexpr uint64_t ZIP_END = 22, ZIP_TAIL = ZIP_END + 65535;  // the end record without its comment; with the longest one
+
+// The index rule, once, for both forms: fetch(pos, len) answers with the file's bytes [pos, pos + len) (null: they could not
+// be had, *frc says why), and is called twice at most — for the last min(c, ZIP_TAIL) bytes, then for the directory (from 20
+// bytes in front of the end record on, when a comment of more than 65515 bytes has pushed those out of the first piece).
+static int zip_index_core(uint64_t c, const std::function<const uint8_t*(uint64_t, uint64_t)>& fetch, int* frc, std::vector<zes_zip_entry>& ent,
+                          std::vector<uint8_t>& names) {
+  ent.clear();
+  names.clear();
+  if (c < ZIP_END) return ZES_E_ZIP;
+  const uint64_t tail_at = c - std::min(c, ZIP_TAIL);
+  const uint8_t* tail = fetch(tail_at, c - tail_at);
+  if (!tail) return *frc;
+  uint64_t p = c - ZIP_END;
+  for (;; p--) {
+    const uint8_t* e = tail + (p - tail_at);
+    if (e[0] == 0x50 && e[1] == 0x4b && e[2] == 5 && e[3] == 6 && p + ZIP_END + get_le16(e + 20) == c) break;
+    if (p == tail_at) return ZES_E_ZIP;
+  }
+  const uint8_t* e = tail + (p - tail_at);
+  const uint32_t count = get_le16(e + 10);
+  const uint64_t cd_size = get_le32(e + 12), cd_off = get_le32(e + 16);
+  if (get_le16(e + 4) || get_le16(e + 6) || get_le16(e + 8) != count || count == 0xFFFF || cd_size == 0xFFFFFFFFull || cd_off == 0xFFFFFFFFull)
+    return ZES_E_UNSUPPORTED;
+  const bool bounds = cd_size + cd_off <= p;
+  const bool loc_in_tail = p < 20 || p - 20 >= tail_at;
+  auto locator = [](const uint8_t* q) { return q[0] == 0x50 && q[1] == 0x4b && q[2] == 6 && q[3] == 7; };
+  if (loc_in_tail) {
+    if (p >= 20 && locator(e - 20)) return ZES_E_UNSUPPORTED;
+    if (!bounds) return ZES_E_ZIP;
+  }
+  const uint64_t dir_at = bounds ? p - cd_size : p, got_at = loc_in_tail ? dir_at : std::min(dir_at, p - 20);
+  const uint8_t* got = fetch(got_at, p - got_at);
+  if (!got && p != got_at) return *frc;
+  if (!loc_in_tail) {
+    if (locator(got + (p - 20 - got_at))) return ZES_E_UNSUPPORTED;
+    if (!bounds) return ZES_E_ZIP;
+  }
+  const uint8_t* dir = got + (dir_at - got_at);
+  const uint64_t base = p - cd_size - cd_off;
+  uint64_t at = 0;
+  while (at < cd_size) {
+    const uint8_t* r = dir + at;
+    if (cd_size - at < 46 || r[0] != 0x50 || r[1] != 0x4b || r[2] != 1 || r[3] != 2) return ZES_E_ZIP;
+    const uint64_t nlen = get_le16(r + 28), len = 46 + nlen + get_le16(r + 30) + get_le16(r + 32);
+    if (len > cd_size - at) return ZES_E_ZIP;
+    const uint64_t csize = get_le32(r + 20), usize = get_le32(r + 24), off = get_le32(r + 42);
+    if (csize == 0xFFFFFFFFull || usize == 0xFFFFFFFFull || off == 0xFFFFFFFFull || get_le16(r + 34)) return ZES_E_UNSUPPORTED;
+    if (off + 30 > cd_off) return ZES_E_ZIP;
+    zes_zip_entry z;
+    z.hdr_off = base + off;
+    z.name_pos = dir_at + at + 46;
+    z.csize = (uint32_t)csize;
+    z.usize = (uint32_t)usize;
+    z.crc = get_le32(r + 16);
+    z.name_off = (uint32_t)names.size();
+    z.name_len = (uint16_t)nlen;
+    z.method = (uint16_t)get_le16(r + 10);
+    z.flags = (uint16_t)get_le16(r + 8);
+    z.pad = 0;
+    ent.push_back(z);
+    names.insert(names.end(), r + 46, r + 46 + nlen);
+    at += len;
+  }
+  return ent.size() == count ? ZES_OK : ZES_E_ZIP;
+}
+
+static int zip_index_args(const uint8_t* in, uint64_t c, const zes_zip_entry* ent, uint64_t cap, uint64_t* entries, const uint8_t* names,
+                          uint64_t names_cap, uint64_t* names_len, uint32_t flags) {
+  if (!entries || !names_len || (!in && c) || flags || (!ent && cap) || (!names && names_cap)) return ZES_E_ARG;
+  *entries = 0;
+  *names_len = 0;
+  return ZES_OK;
+}
+
+static int zip_index_out(const std::vector<zes_zip_entry>& e, const std::vector<uint8_t>& nm, zes_zip_entry* ent, uint64_t cap, uint64_t* entries,
+                         uint8_t* names, uint64_t names_cap, uint64_t* names_len) {
+  *entries = e.size();
+  *names_len = nm.size();
+  if (cap < e.size() || names_cap < nm.size() || (!ent && !names)) return ZES_E_NOSPACE;
+  if (!e.empty()) memcpy(ent, e.data(), sizeof(zes_zip_entry) * e.size());
+  if (!nm.empty()) memcpy(names, nm.data(), nm.size());
+  return ZES_OK;
+}
+
+int zes_zip_index(const uint8_t* in, uint64_t c, zes_zip_entry* ent, uint64_t cap, uint64_t* entries, uint8_t* names, uint64_t names_cap,
+                  uint64_t* names_len, uint32_t flags) {
+  if (const int arc = zip_index_args(in, c, ent, cap, entries, names, names_cap, names_len, flags)) return arc;
+  std::vector<zes_zip_entry> e;
+  std::vector<uint8_t> nm;
+  int frc = ZES_OK;
+  if (const int irc = zip_index_core(c, [&](uint64_t pos, uint64_t) { return in + pos; }, &frc, e, nm)) return irc;
+  return zip_index_out(e, nm, ent, cap, entries, names, names_cap, names_len);
+}
+
+int zes_zip_index_dev(const uint8_t* d_in, uint64_t c, zes_zip_entry* ent, uint64_t cap, uint64_t* entries, uint8_t* names, uint64_t names_cap,
+                      uint64_t* names_len, uint32_t flags) {
+  ROUTE_DEV(d_in);
+  if (const int arc = zip_index_args(d_in, c, ent, cap, entries, names, names_cap, names_len, flags)) return arc;
+  if (c < ZIP_END) return ZES_E_ZIP;
+  LOCK_READY();
+  std::vector<zes_zip_entry> e;
+  std::vector<uint8_t> nm;
+  std::vector<uint8_t> piece[2];
+  int k = 0, frc = ZES_OK;
+  auto fetch = [&](uint64_t pos, uint64_t len) -> const uint8_t* {
+    std::vector<uint8_t>& b = piece[k++ & 1];
+    b.resize(len + 1);
+    if (len && (hipMemcpyAsync(b.data(), d_in + pos, len, hipMemcpyDeviceToHost, g.stream) != hipSuccess || hipStreamSynchronize(g.stream) != hipSuccess)) {
+      (void)hipGetLastError();
+      frc = ZES_E_DEVICE;
+      return nullptr;
+    }
+    return b.data();
+  };
+  if (const int irc = zip_index_core(c, fetch, &frc, e, nm)) return irc;
+  return zip_index_out(e, nm, ent, cap, entries, names, names_cap, names_len);
+}
+
+// An entry's status as far as its index record alone decides it (include/zes.h, zes_zip_read*: step 1)
+static int zip_entry_alone(const zes_zip_entry& z, uint64_t c) {
+  if ((z.flags & 0x61u) || (z.method != 0 && z.method != 8)) return ZES_E_UNSUPPORTED;
+  if (z.method == 0 && z.csize != z.usize) return ZES_E_ZIP;
+  if (z.hdr_off > c || c - z.hdr_off < 30 || z.name_pos > c || c - z.name_pos < z.name_len) return ZES_E_ZIP;
+  // (step 2's last test with an extra field of no bytes: a csize no file has gets its status here, not a scratch slot first)
+  if (30ull + z.name_len + z.csize > c - z.hdr_off) return ZES_E_ZIP;
+  return ZES_OK;
+}
+
+static int zip_read_args(const uint8_t* in, uint64_t c, const zes_zip_entry* ent, uint64_t nent, const uint32_t* sel, uint32_t count,
+                         const uint64_t* out_len, const int32_t* status, uint32_t flags) {
+  if ((flags & ~ZES_F_PIECES) || (!in && c)) return ZES_E_ARG;
+  if (count && (!ent || !out_len || !status)) return ZES_E_ARG;
+  if (!sel && count > nent) return ZES_E_ARG;
+  for (uint32_t i = 0; sel && i < count; i++)
+    if (sel[i] >= nent) return ZES_E_ARG;
+  return ZES_OK;
+}
+
+// a call with nothing to extract: no device work; the times and the tier of the call before do not stay
+static void zip_read_none() {
+  std::lock_guard<std::mutex> lk(g_mu);
+  g.last_tier = 0;
+  collect_times();
+}
+
+// One entry of a zip_read_core batch: its index record, where its header and the directory's name lie in d_src and how many
+// bytes of the file follow the header's first byte, and where its usize bytes go in dst
+struct ZipPart {
+  zes_zip_entry z;
+  uint64_t hdr_at, name_at, limit, dst_off;
+};
+
+// The entries of ps whose status[k] is ZES_OK on entry (zip_entry_alone has passed them), as one batch: k_zip_stage judges the
+// local headers and puts the bodies in place, one read-back brings the verdicts down, the DEFLATE bodies go through one
+// inflate_jobs call, one gather moves the outputs that could not be decoded in place, one segmented CRC-32 launch checks all
+// results (gz_decode_batch's plan, with a verdict per entry instead of one for the batch, and its `exact` mode: no byte of dst
+// outside the parts is written).  status[k] becomes the entry's status (include/zes.h, steps 2 to 4).
+static int zip_read_core(const uint8_t* d_src, const std::vector<ZipPart>& ps, uint8_t* dst, int32_t* status, uint32_t flags) {
+  int rc;
+  g.last_tier = 0;
+  std::vector<uint32_t> st;  // the staged entries
+  for (uint32_t k = 0; k < ps.size(); k++)
+    if (status[k] == ZES_OK) st.push_back(k);
+  const uint32_t n = (uint32_t)st.size();
+  if (!n) return ZES_OK;
+  std::vector<char> direct(n, 0);
+  std::vector<uint64_t> islot(n, 0), oslot(n, 0);
+  std::vector<ZesZipRec> recs(n);
+  uint64_t ipos = 0, opos = 0, longest = 0;
+  for (uint32_t q = 0; q < n; q++) {
+    const ZipPart& p = ps[st[q]];
+    const uint64_t m = p.z.usize;
+    ZesZipRec r;
+    memset(&r, 0, sizeof r);
+    r.hdr_at = p.hdr_at;
+    r.name_at = p.name_at;
+    r.limit = p.limit;
+    r.csize = p.z.csize;
+    r.name_len = p.z.name_len;
+    r.method = p.z.method;
+    r.flag0 = p.z.flags & 1u;
+    longest = std::max<uint64_t>(longest, p.z.csize);
+    if (p.z.method == 8) {
+      islot[q] = ipos;
+      ipos += gz_slot_in(p.z.csize);
+      r.dst_off = islot[q] + 2;
+      direct[q] = dst && m && ((uintptr_t)(dst + p.dst_off) & 15u) == 0 && (m & 15u) == 0;
+      if (!direct[q]) {
+        oslot[q] = opos;
+        opos += gz_slot_out(m);
+      }
+    } else {
+      r.dst_off = p.dst_off;
+    }
+    recs[q] = r;
+  }
+  const size_t o_verd = sizeof(ZesZipRec) * (size_t)n;
+  if ((rc = ensure(g.gz_bodies, ipos + 64)) || (rc = ensure(g.gz_outs, opos + 64)) || (rc = ensure(g.gz_tab, o_verd + sizeof(ZesZipVerdict) * (size_t)n)))
+    return rc;
+  ZesZipVerdict* d_verd = (ZesZipVerdict*)((uint8_t*)g.gz_tab.p + o_verd);
+  HIPCHK(hipMemcpyAsync(g.gz_tab.p, recs.data(), o_verd, hipMemcpyHostToDevice, g.stream));
+  {
+    const uint32_t ny = (uint32_t)std::min<uint64_t>(std::max<uint64_t>((longest + GZ_GATHER_PIECE - 1) / GZ_GATHER_PIECE, 1), 256);
+    Timed t("k_zip_stage");
+    hipLaunchKernelGGL(k_zip_stage, dim3(n, ny), dim3(GZ_GATHER_THREADS), 0, g.stream, d_src, (uint8_t*)g.gz_bodies.p, dst, (const ZesZipRec*)g.gz_tab.p,
+                       d_verd);
+  }
+  HIPCHK(hipGetLastError());
+  std::vector<ZesZipVerdict> verd(n);
+  HIPCHK(hipMemcpyAsync(verd.data(), d_verd, sizeof(ZesZipVerdict) * (size_t)n, hipMemcpyDeviceToHost, g.stream));
+  HIPCHK(hipStreamSynchronize(g.stream));
+  // one base for both kinds of destination (inflate_jobs takes one pointer and an offset per job): the lower of the two
+  uint8_t* outs = (uint8_t*)g.gz_outs.p;
+  uint8_t* base = dst && dst < outs ? dst : outs;
+  std::vector<InfJob> jobs;
+  std::vector<uint32_t> jq;  // job -> staged entry
+  for (uint32_t q = 0; q < n; q++) {
+    const ZipPart& p = ps[st[q]];
+    status[st[q]] = verd[q].status;
+    if (p.z.method != 8) continue;
+    const uint64_t m = p.z.usize;
+    uint8_t* to = direct[q] ? dst + p.dst_off : outs + oslot[q];
+    InfJob j{islot[q], 2 + (uint64_t)p.z.csize, (uint64_t)(to - base), direct[q] ? m : gz_slot_cap(m), 0, verd[q].status, 0};
+    j.want_end = true;
+    jobs.push_back(j);
+    jq.push_back(q);
+  }
+  bool any = false;
+  for (const InfJob& j : jobs) any = any || j.status == ZES_OK;
+  if (any) {
+    const std::vector<uint8_t> firsts(jobs.size(), 0x78);
+    if ((rc = inflate_jobs((const uint8_t*)g.gz_bodies.p, base, jobs, firsts.data(), flags & ZES_F_PIECES))) return rc;
+    keep_times();
+  }
+  std::vector<ZesGzSeg> segs;
+  for (size_t i = 0; i < jobs.size(); i++) {
+    const uint32_t q = jq[i];
+    const ZipPart& p = ps[st[q]];
+    const InfJob& j = jobs[i];
+    if (verd[q].status) continue;
+    if ((status[st[q]] = gz_job_verdict(j, p.z.usize, p.z.csize))) continue;
+    if (!direct[q] && p.z.usize)
+      segs.push_back(ZesGzSeg{oslot[q], p.dst_off, p.z.usize, 0u, 0u});
+  }
+  if ((rc = gz_gather(outs, dst, segs))) return rc;
+  std::vector<ZesCrcSeg> csegs(n);
+  for (uint32_t q = 0; q < n; q++) {
+    const bool ok = status[st[q]] == ZES_OK && ps[st[q]].z.usize;
+    csegs[q] = ZesCrcSeg{ok ? ps[st[q]].dst_off : 0, ok ? ps[st[q]].z.usize : 0};
+  }
+  std::vector<uint32_t> crc(n);
+  if ((rc = crc32_batch_locked(dst, csegs.data(), n, crc.data()))) return rc;
+  for (uint32_t q = 0; q < n; q++)
+    if (status[st[q]] == ZES_OK && crc[q] != ps[st[q]].z.crc) status[st[q]] = ZES_E_CHECKSUM;
+  return ZES_OK;
+}
+
+int zes_zip_read_dev(const uint8_t* d_in, uint64_t c, const zes_zip_entry* ent, uint64_t nent, const uint32_t* sel, uint32_t count, uint8_t* d_out,
+                     const uint64_t* out_off, uint64_t* out_len, int32_t* status, uint32_t flags) {
+  ROUTE_DEV(d_in, d_out);
+  if (const int arc = zip_read_args(d_in, c, ent, nent, sel, count, out_len, status, flags)) return arc;
+  if (count && !out_off) return ZES_E_ARG;
+  if (!count) {
+    zip_read_none();
+    return ZES_OK;
+  }
+  std::vector<ZipPart> ps(count);
+  for (uint32_t i = 0; i < count; i++) {
+    const zes_zip_entry& z = ent[sel ? sel[i] : i];
+    out_len[i] = 0;
+    status[i] = zip_entry_alone(z, c);
+    ps[i] = ZipPart{z, z.hdr_off, z.name_pos, c - std::min(c, z.hdr_off), out_off[i]};
+    if (status[i] == ZES_OK && z.usize && !d_out) return ZES_E_ARG;
+  }
+  LOCK_READY();
+  rc = zip_read_core(d_in, ps, d_out, status, flags);
+  if (rc) (void)hipGetLastError();
+  collect_times();
+  if (rc) return rc;
+  for (uint32_t i = 0; i < count; i++)
+    if (status[i] == ZES_OK) out_len[i] = ps[i].z.usize;
+  return ZES_OK;
+}
+
+int zes_zip_read_alloc(const uint8_t* in, uint64_t c, const zes_zip_entry* ent, uint64_t nent, const uint32_t* sel, uint32_t count, zes_alloc_fn alloc,
+                       void* user, uint64_t* out_len, int32_t* status, uint32_t flags) {
+  UseDev ud(route_host());
+  if (const int arc = zip_read_args(in, c, ent, nent, sel, count, out_len, status, flags)) return arc;
+  if (!alloc) return ZES_E_ARG;
+  if (!count) {
+    zip_read_none();
+    return ZES_OK;
+  }
+  LOCK_READY();
+  // only the selected entries' bytes cross to the device: header, name, extra field and body in one piece, the directory's
+  // copy of the name in another, each at a 16-byte boundary of g.gz_in
+  std::vector<ZipPart> ps(count);
+  std::vector<uint64_t> take(count, 0);
+  uint64_t tin = 0, tout = 0;
+  for (uint32_t i = 0; i < count; i++) {
+    const zes_zip_entry& z = ent[sel ? sel[i] : i];
+    out_len[i] = 0;
+    status[i] = zip_entry_alone(z, c);
+    ps[i] = ZipPart{z, 0, 0, 0, tout};
+    if (status[i]) continue;
+    ps[i].limit = c - z.hdr_off;
+    take[i] = std::min<uint64_t>(ps[i].limit, 30ull + z.name_len + get_le16(in + z.hdr_off + 28) + z.csize);
+    ps[i].hdr_at = tin;
+    tin += ((take[i] + 15) & ~15ull) + 16;
+    ps[i].name_at = tin;
+    tin += (((uint64_t)z.name_len + 15) & ~15ull) + 16;
+    tout += (((uint64_t)z.usize + 15) & ~15ull) + 16;
+  }
+  if ((rc = ensure(g.gz_in, tin + 64)) || (rc = ensure(g.gz_acc, tout + 64))) return rc;
+  for (uint32_t i = 0; i < count; i++) {
+    if (status[i]) continue;
+    if ((rc = upload((uint8_t*)g.gz_in.p + ps[i].hdr_at, in + ps[i].z.hdr_off, take[i]))) return rc;
+    if ((rc = upload((uint8_t*)g.gz_in.p + ps[i].name_at, in + ps[i].z.name_pos, ps[i].z.name_len))) return rc;
+  }
+  rc = zip_read_core((const uint8_t*)g.gz_in.p, ps, (uint8_t*)g.gz_acc.p, status, flags);
+  if (rc) (void)hipGetLastError();
+  collect_times();
+  if (rc) return rc;
+  for (uint32_t i = 0; i < count; i++) {
+    if (status[i]) continue;
+    uint8_t* to = alloc(user, i, ps[i].z.usize);
+    if (!to) {
+      status[i] = ZES_E_ARG;
+      continue;
+    }
+    // (a short result is only enqueued: one synchronisation behind the loop serves them all)
+    if ((rc = download(to, (const uint8_t*)g.gz_acc.p + ps[i].dst_off, ps[i].z.usize, nullptr, false))) return rc;
+    out_len[i] = ps[i].z.usize;
+  }
+  HIPCHK(hipStreamSynchronize(g.stream));
+  return ZES_OK;
 }
 
 int zes_stage_lz77_dev(const uint8_t* d_in, uint64_t n, uint64_t start, uint32_t len, uint32_t* h_tokens, uint32_t* ntokens) {

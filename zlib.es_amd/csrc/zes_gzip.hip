@@ -1,5 +1,5 @@
 // zes_gzip.hip — device pieces of the member-parallel gzip reader (zes_api.hip: gunzip_parallel) and of the BGZF writer
-// (zes_api.hip: bgzip_core).
+// (zes_api.hip: bgzip_core), and of the ZIP reader (zes_api.hip: zip_read_core).
 //
 // A file whose members all state their own size — BGZF, the format of bgzip / htslib: every member's extra field holds a
 // subfield 'B','C' with BSIZE = member size - 1 — can be cut into its members without decoding anything.
@@ -22,6 +22,14 @@
 //                body at whatever alignment its place has — the encoder's stream out of its scratch slot, or a stored block:
 //                five bytes and the chunk out of the caller's input — and the 8 trailer bytes.  Only the member's own bytes
 //                are written, and the input is read only inside the aligned 16-byte groups that hold the chunk's bytes.
+//   k_zip_stage  workgroups (e, y) for entry e of a ZIP batch: each judges the entry's local header against its directory
+//                record (include/zes.h, zes_zip_read*: step 2) — the 30 header bytes at any alignment, the name against the
+//                directory's copy strided over the workgroup and joined by a block-wide OR — and workgroup (e, 0) writes
+//                the verdict {status, data_off}, whatever the outcome.  When the entry checks out, the workgroups copy its
+//                csize body bytes as shares y of gz_copy: a DEFLATE body into its scratch slot behind a 78 9C (k_gz_gather's
+//                zhdr layout), a stored one straight to its place in the output.  Only the entry's own bytes are written, and
+//                the file is read only inside the aligned 16-byte groups that hold bytes of it.
+#include "../../include/zes.h"
 #include "zes_common.h"
 #include "zes_kernels.h"
 
@@ -214,5 +222,40 @@ __global__ __launch_bounds__(GZ_GATHER_THREADS) void k_bgzf_pack(const uint8_t* 
     gz_copy(in + r.src_off, body + 5, r.len, tid, 0, 1);
   } else if (tid < 2) {  // the end-of-file marker's body: an empty fixed-Huffman block
     body[tid] = tid ? 0 : 3;
+  }
+}
+
+__global__ __launch_bounds__(GZ_GATHER_THREADS) void k_zip_stage(const uint8_t* __restrict__ src, uint8_t* __restrict__ slots, uint8_t* __restrict__ out,
+                                                                const ZesZipRec* __restrict__ recs, ZesZipVerdict* __restrict__ verdicts) {
+  const ZesZipRec r = recs[blockIdx.x];
+  const uint32_t tid = threadIdx.x;
+  const uint8_t* h = src + r.hdr_at;  // (the host has seen to it that the header's 30 bytes and the directory's name lie inside the file)
+  auto le16 = [&](uint32_t i) -> uint32_t { return (uint32_t)h[i] | (uint32_t)h[i + 1] << 8; };
+  const uint32_t nlen = le16(26);
+  const uint64_t data = 30ull + nlen + le16(28);  // the body's distance from the header
+  const bool fits = h[0] == 0x50 && h[1] == 0x4b && h[2] == 3 && h[3] == 4 && le16(8) == r.method && (h[6] & 1u) == r.flag0 && nlen == r.name_len &&
+                    data + r.csize <= r.limit;
+  uint32_t diff = fits ? 0u : 1u;
+  if (fits) {
+    const uint8_t* a = h + 30;
+    const uint8_t* b = src + r.name_at;
+    for (uint32_t i = tid; i < nlen; i += GZ_GATHER_THREADS) diff |= (uint32_t)(a[i] ^ b[i]);
+  }
+  const bool ok = __syncthreads_or((int)diff) == 0;
+  if (blockIdx.y == 0 && tid == 0) {
+    ZesZipVerdict v;
+    v.status = ok ? ZES_OK : ZES_E_ZIP;
+    v.pad = 0;
+    v.data_off = r.hdr_at + data;
+    verdicts[blockIdx.x] = v;
+  }
+  if (!ok) return;
+  const uint8_t* body = h + data;
+  if (r.method == 8) {
+    uint8_t* d = slots + r.dst_off;
+    if (blockIdx.y == 0 && tid < 2) d[(int)tid - 2] = tid ? 0x9C : 0x78;
+    gz_copy(body, d, r.csize, tid, blockIdx.y, gridDim.y);
+  } else {
+    gz_copy(body, out + r.dst_off, r.csize, tid, blockIdx.y, gridDim.y);
   }
 }

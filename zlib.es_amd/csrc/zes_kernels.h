@@ -187,6 +187,23 @@ struct ZesBgzfRec {
 #define ZES_BGZF_STORED 1u  // the body is one stored block: 01 | LEN | NLEN | the chunk
 #define ZES_BGZF_EOF 2u     // the end-of-file marker: no chunk, the body is 03 00
 #define ZES_BGZF_HLEN 18u   // a member's header
+// k_zip_stage (zes_gzip.hip): one entry of a ZIP archive on its way to the decoders.  Positions are relative to the kernel's
+// source pointer: the file itself (device form), or the staged copies of the entry's bytes (host form)
+struct ZesZipRec {
+  uint64_t hdr_at;    // the local header
+  uint64_t name_at;   // the central directory's copy of the name
+  uint64_t limit;     // bytes of the file from the local header's first byte to the file's end
+  uint64_t dst_off;   // where the body goes: method 8 its scratch slot's byte 2 (behind 78 9C), method 0 its place in the output
+  uint32_t csize;     // the body's bytes
+  uint16_t name_len, method;
+  uint32_t flag0;     // bit 0 of the entry's flags
+  uint32_t pad;
+};
+struct ZesZipVerdict {
+  int32_t status;     // ZES_OK, or ZES_E_ZIP: the local header is not what the entry says
+  uint32_t pad;
+  uint64_t data_off;  // the body's first byte (as hdr_at)
+};
 
 // CRC-32 host arithmetic (zes_crc.hip): shift(s, k) = s * x^(8k) mod P; the kernel's table with npow powers
 uint32_t zes_crc_shift(uint32_t s, uint64_t k);
@@ -266,6 +283,7 @@ __global__ void k_gz_walk(const uint8_t*, uint64_t, ZesGzWalk*, ZesGzMember*, ui
 __global__ void k_bgzf_mark(const uint8_t*, uint64_t, ZesBgzfMark*, ZesBgzfCand*, uint32_t);
 __global__ void k_gz_gather(const uint8_t*, uint8_t*, const ZesGzSeg*);
 __global__ void k_bgzf_pack(const uint8_t*, const uint8_t*, uint8_t*, const ZesBgzfRec*);
+__global__ void k_zip_stage(const uint8_t*, uint8_t*, uint8_t*, const ZesZipRec*, ZesZipVerdict*);
 __global__ void k_adler_blocks(const uint8_t*, const ZesBuf*, const ZesBlk*, unsigned long long*);
 __global__ void k_adler_seg(const uint8_t*, const ZesCrcSeg*, const uint2*, unsigned long long*);
 __global__ void k_layout(uint8_t*, const ZesBuf*, ZesBlk*, const unsigned long long*, ZesRes*);

@@ -952,6 +952,86 @@ napi_value InflateBatch(napi_env env, napi_callback_info info) { return start_ba
 napi_value DeflateBatchAsync(napi_env env, napi_callback_info info) { return start_batch(env, info, false, true); }
 napi_value InflateBatchAsync(napi_env env, napi_callback_info info) { return start_batch(env, info, true, true); }
 
+// ---- ZIP archives (include/zes.h: zes_zip_index, zes_zip_read_alloc) ----
+// a fresh Uint8Array of n bytes in memory of the engine's own (*mem: where to fill it)
+napi_value new_u8(napi_env env, size_t n, void** mem) {
+  napi_value ab, ta;
+  if (napi_create_arraybuffer(env, n, mem, &ab) != napi_ok || napi_create_typedarray(env, napi_uint8_array, n, ab, 0, &ta) != napi_ok) return nullptr;
+  return ta;
+}
+
+// zipIndex(file): { raw, names } — the entries as zes_zip_entry records (what zipRead hands back to the library) and the
+// names back to back; the façade makes the entry objects out of the two.  The host form: no device is touched.
+napi_value ZipIndex(napi_env env, napi_callback_info info) {
+  const Args a = get_args(env, info);
+  const Bytes in = need_bytes(env, a, 0, "zipIndex(file)", "file");
+  if (!in.ok) return nullptr;
+  uint64_t entries = 0, names_len = 0;
+  int rc = zes_zip_index(in.p, in.n, nullptr, 0, &entries, nullptr, 0, &names_len, ZES_F_DEFAULT);  // (the counts: ZES_E_NOSPACE on a valid archive)
+  if (rc != ZES_E_NOSPACE) return throw_status(env, rc ? rc : ZES_E_ARG);
+  void *raw = nullptr, *names = nullptr;
+  napi_value res, vraw = new_u8(env, (size_t)entries * sizeof(zes_zip_entry), &raw), vnames = new_u8(env, (size_t)names_len, &names);
+  if (!vraw || !vnames) return nullptr;
+  std::vector<zes_zip_entry> ent((size_t)entries + 1);  // (an ArrayBuffer's memory need not be aligned for the records)
+  uint8_t none = 0;
+  rc = zes_zip_index(in.p, in.n, ent.data(), entries, &entries, names ? static_cast<uint8_t*>(names) : &none, names_len, &names_len, ZES_F_DEFAULT);
+  if (rc) return throw_status(env, rc);
+  if (entries) memcpy(raw, ent.data(), (size_t)entries * sizeof(zes_zip_entry));
+  if (napi_create_object(env, &res) != napi_ok) return nullptr;
+  napi_set_named_property(env, res, "raw", vraw);
+  napi_set_named_property(env, res, "names", vnames);
+  return res;
+}
+
+// zipRead(file, index, sel): the selected entries (all without sel) as one batch: per entry a fresh Uint8Array or the Error
+// that says why not, as the batch forms answer
+napi_value ZipRead(napi_env env, napi_callback_info info) {
+  static const char SIG[] = "zipRead(file, index, sel)";
+  const Args a = get_args(env, info);
+  const Bytes in = need_bytes(env, a, 0, SIG, "file");
+  if (!in.ok) return nullptr;
+  napi_value vraw;
+  napi_valuetype vt = napi_undefined;
+  const uint8_t* raw = nullptr;
+  size_t raw_n = 0;
+  if (a.argc < 2 || napi_typeof(env, a.argv[1], &vt) != napi_ok || vt != napi_object || napi_get_named_property(env, a.argv[1], "raw", &vraw) != napi_ok ||
+      !get_bytes(env, vraw, &raw, &raw_n) || raw_n % sizeof(zes_zip_entry))
+    return throw_type(env, std::string(SIG) + ": index must be what zipIndex(file) returned");
+  std::vector<zes_zip_entry> ent(raw_n / sizeof(zes_zip_entry) + 1);
+  if (raw_n) memcpy(ent.data(), raw, raw_n);
+  const uint64_t nent = raw_n / sizeof(zes_zip_entry);
+  std::vector<uint32_t> sel;
+  bool all = a.argc < 3 || napi_typeof(env, a.argv[2], &vt) != napi_ok || vt == napi_undefined || vt == napi_null;
+  if (!all) {
+    bool is_arr = false, is_ta = false;
+    uint32_t n = 0;
+    if (napi_is_array(env, a.argv[2], &is_arr) == napi_ok && is_arr && napi_get_array_length(env, a.argv[2], &n) == napi_ok) {
+      sel.resize(n);
+      for (uint32_t i = 0; i < n; i++) {
+        napi_value e;
+        uint64_t v = 0;
+        if (napi_get_element(env, a.argv[2], i, &e) != napi_ok || !get_safe_uint(env, e, &v) || v > 0xFFFFFFFFull)
+          return throw_type(env, std::string(SIG) + ": sel must be an array of entry numbers or a Uint32Array");
+        sel[i] = (uint32_t)v;
+      }
+    } else if (napi_is_typedarray(env, a.argv[2], &is_ta) == napi_ok && is_ta) {
+      napi_typedarray_type type;
+      void* p = nullptr;
+      size_t len = 0, off = 0;
+      napi_value ab;
+      if (napi_get_typedarray_info(env, a.argv[2], &type, &len, &p, &ab, &off) != napi_ok || type != napi_uint32_array || len > 0xFFFFFFFFull)
+        return throw_type(env, std::string(SIG) + ": sel must be an array of entry numbers or a Uint32Array");
+      sel.assign(static_cast<const uint32_t*>(p), static_cast<const uint32_t*>(p) + len);
+    } else {
+      return throw_type(env, std::string(SIG) + ": sel must be an array of entry numbers or a Uint32Array");
+    }
+  }
+  if (all && nent > 0xFFFFFFFFull) return throw_status(env, ZES_E_ARG);
+  BatchJob j(all ? (uint32_t)nent : (uint32_t)sel.size());
+  j.rc = zes_zip_read_alloc(in.p, in.n, ent.data(), nent, all ? nullptr : sel.data(), j.count, batch_alloc, &j, j.out_len.data(), j.status.data(), ZES_F_DEFAULT);
+  return j.rc == 0 ? batch_results(env, &j) : throw_status(env, j.rc);
+}
+
 // allocPinned(n): a Uint8Array in page-locked memory (zes_host_alloc) — buffers from here cross PCIe without the
 // library's staging copy; released when the array is collected.  The release runs on the JS thread and takes
 // the library's lock for a moment (no stream is waited for: hipHostFree itself waits for work that uses the block), so
@@ -995,6 +1075,8 @@ napi_value ModuleInit(napi_env env, napi_value exports) {
       {"bgzipIndex", swept<BgzipIndex>},
       {"bgzfIndex", swept<BgzfIndex>},
       {"bgzfRead", swept<BgzfRead>},
+      {"zipIndex", swept<ZipIndex>},
+      {"zipRead", swept<ZipRead>},
       {"lastGunzipMembers", swept<LastGunzipMembers>},
       {"init", swept<Init>},
       {"initDevices", swept<InitDevices>},

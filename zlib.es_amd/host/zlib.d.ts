@@ -22,6 +22,11 @@ export declare function bgzip(input: Uint8Array): Uint8Array;
 export declare function bgzipIndex(input: Uint8Array): { data: Uint8Array, offsets: number[] };
 export declare function bgzfIndex(file: Uint8Array): { compressed: BigUint64Array, uncompressed: BigUint64Array };
 export declare function bgzfRead(file: Uint8Array, index: { compressed: BigUint64Array, uncompressed: BigUint64Array }, pos: number | bigint, len: number | bigint): Uint8Array;
+/** ZIP archives, read only: the entries out of the central directory (no device is touched), and batch extraction through that index. */
+export declare type ZipEntry = { nameBytes: Uint8Array, name: string, method: number, flags: number, compressedSize: number, size: number, crc32: number };
+export declare type ZipIndex = { entries: ZipEntry[], raw: Uint8Array };
+export declare function zipIndex(file: Uint8Array): ZipIndex;
+export declare function zipRead(file: Uint8Array, index: ZipIndex, sel?: number[] | Uint32Array): BatchResult[];
 export declare function init(device: number): void;
 export declare function initDevices(n?: number): number;
 export declare function trim(): void;

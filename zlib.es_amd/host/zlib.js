@@ -133,6 +133,38 @@ function bgzfRead(file, index, pos, len) {
 }
 
 /**
+ * Extra (not in the reference API): ZIP archives, read only.  `zipIndex` lists the archive's entries from its central
+ * directory on the host (no device is touched, nothing is decoded): per entry the name as the archive holds it (`nameBytes`)
+ * and as a string (`name`: UTF-8 when flag bit 11 says so, else byte for byte as code points — CP437 is not decoded), the
+ * method, the flags, both sizes and the CRC-32; `raw` is the same list as the records the library reads (40 bytes an entry)
+ * and is all that `zipRead` looks at.  `zipRead` extracts the entries `sel` names by number (all of them without it; any
+ * order, duplicates fine) as one batch: only their bytes are uploaded, every DEFLATE body goes through the inflate tiers in
+ * one call, and one launch checks every CRC-32.  Element i of the result is the entry's bytes or — instead of a throw — the
+ * `Error` that says why not (a checksum mismatch, a local header that does not fit the directory, encryption, a method other
+ * than stored and DEFLATE).  ZIP64 archives and archives over several disks are refused by `zipIndex`.  (A rest parameter,
+ * not `sel?`: zlib.d.ts declares one optional argument.)
+ */
+function zipIndex(file) {
+  const got = addon.zipIndex(file);
+  const view = new DataView(got.raw.buffer, got.raw.byteOffset, got.raw.byteLength);
+  const entries = [];
+  for (let at = 0; at < got.raw.length; at += 40) {
+    const nameOff = view.getUint32(at + 28, true), flags = view.getUint16(at + 36, true);
+    const nameBytes = got.names.slice(nameOff, nameOff + view.getUint16(at + 32, true));
+    entries.push({
+      nameBytes, name: Buffer.from(nameBytes.buffer, nameBytes.byteOffset, nameBytes.length).toString(flags & 0x800 ? 'utf8' : 'latin1'),
+      method: view.getUint16(at + 34, true), flags, compressedSize: view.getUint32(at + 16, true), size: view.getUint32(at + 20, true),
+      crc32: view.getUint32(at + 24, true),
+    });
+  }
+  return { entries, raw: got.raw };
+}
+
+function zipRead(file, index, ...sel) {
+  return addon.zipRead(file, index, sel[0]);
+}
+
+/**
  * Extra: how many members the last gunzip() of this thread decoded as one batch (a BGZF file: all of them, the
  * end-of-file marker included); 0 when the members went one after the other.
  */
@@ -182,6 +214,8 @@ exports.bgzip = bgzip;
 exports.bgzipIndex = bgzipIndex;
 exports.bgzfIndex = bgzfIndex;
 exports.bgzfRead = bgzfRead;
+exports.zipIndex = zipIndex;
+exports.zipRead = zipRead;
 exports.lastGunzipMembers = lastGunzipMembers;
 exports.adler32 = adler32;
 exports.init = init;

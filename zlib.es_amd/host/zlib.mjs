@@ -21,6 +21,8 @@ export const bgzip = z.bgzip;
 export const bgzipIndex = z.bgzipIndex;
 export const bgzfIndex = z.bgzfIndex;
 export const bgzfRead = z.bgzfRead;
+export const zipIndex = z.zipIndex;
+export const zipRead = z.zipRead;
 export const init = z.init;
 export const initDevices = z.initDevices;
 export const trim = z.trim;
