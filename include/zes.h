@@ -315,7 +315,8 @@ int zes_bgzf_read_dev(const uint8_t* d_in, uint64_t c, const uint64_t* coff, con
                       uint8_t* d_out, uint64_t cap, uint64_t* out_len, uint32_t flags);
 
 /* ZIP archives (PKWARE APPNOTE 6.3): the entry index out of the central directory, and batch extraction through it.
- * A reader only: ZIP64, archives over several disks, encryption and methods other than 0 and 8 are ZES_E_UNSUPPORTED.
+ * The reader takes no ZIP64, no archive over several disks, no encryption and no method other than 0 and 8
+ * (ZES_E_UNSUPPORTED); the writer (zes_zipwrite*, below) makes none of them.
  *
  * zes_zip_index*: the archive's entries in directory order, from the end record and the central directory alone; local
  * headers are not looked at and nothing is decoded (as CPython's zipfile, the reader meets them when an entry is opened).
@@ -385,6 +386,52 @@ int zes_zip_read_dev(const uint8_t* d_in, uint64_t c, const zes_zip_entry* ent, 
                      uint8_t* d_out, const uint64_t* out_off, uint64_t* out_len, int32_t* status, uint32_t flags);
 int zes_zip_read_alloc(const uint8_t* in, uint64_t c, const zes_zip_entry* ent, uint64_t nent, const uint32_t* sel, uint32_t count,
                        zes_alloc_fn alloc, void* user, uint64_t* out_len, int32_t* status, uint32_t flags);
+
+/* zes_zipwrite*: a ZIP archive of `count` entries, entry i the in_len[i] bytes at d_in + in_off[i] (in[i], host form) under the
+ * name of name_len[i] bytes that stands in `names` behind the names before it.  in_off, in_len, name_len and names are host
+ * memory; the entries' bytes may overlap and repeat; duplicate and empty names are the caller's business.  The result is
+ * deterministic, the same inputs give the same bytes:
+ *   local header  50 4b 03 04, version needed 20, flags 0x0800 when the name holds a byte >= 0x80 (names are taken as UTF-8,
+ *                 CPython's rule) else 0, method, time 0, date 33 (1980-01-01), CRC-32, csize, usize, name length, extra
+ *                 length 0; then the name, then the body.  No data descriptor, no extra field, no bytes between entries
+ *   method        let s be zes_deflate_raw of the entry's bytes alone.  Method 8 with body s when the encoder accepts the
+ *                 length (not 0, not 1, not = 1 mod 131072) and s is shorter than the entry; otherwise method 0 with the
+ *                 bytes themselves as the body (a stream of exactly in_len[i] bytes is not kept)
+ *   directory     in entry order, 46 bytes and the name each: 50 4b 01 02, made-by 20, needed 20, the local header's flags,
+ *                 method, time, date, CRC and sizes, name length, extra, comment, disk and both attribute fields 0, the
+ *                 local header's offset
+ *   end record    50 4b 05 06, disks 0, both counts, the directory's size and offset, comment length 0.  count == 0 gives
+ *                 the end record alone: 22 bytes
+ * zes_zipwrite_bound: sum(30 + name + len) + sum(46 + name) + 22 — exact when every entry is stored, and always enough, as
+ * method 8 is chosen only when it is shorter.  It touches no device.
+ * ent: NULL, or room for `count` records, which on ZES_OK are what zes_zip_index lists for the result (name_off: the running
+ * sum of name_len).  Statuses, for the whole call:
+ *   ZES_E_ARG          a null array with count != 0, a null out_len, a null d_out / out with cap != 0, a null d_in / in[i]
+ *                      with a non-zero length, flag bits other than ZES_F_PIECES
+ *   ZES_E_UNSUPPORTED  from the arguments alone, before any device work and before a byte of the data is read: count > 65534,
+ *                      an in_len[i] > 0xFFFFFFFE; once known: a local header's offset, the directory's offset or its size
+ *                      reaches 0xFFFFFFFF (no ZIP64 is written)
+ *   ZES_E_NOSPACE      the result does not fit cap (or d_out is NULL with cap 0: a size query): *out_len = the size needed;
+ *                      every entry is still encoded, as for zes_bgzip*, and nothing at or behind cap is touched
+ * The entries go in groups, in order: up to 1024 of them whose encoder slots take up to 256 MiB (4 of them and 1 MiB under
+ * ZES_F_PIECES, a testing aid for both seams: same bytes), and one entry at least.  An entry's slot is zes_deflate_bound of its
+ * length, about twice the length, so the scratch is bounded by the larger of 256 MiB of slots and the longest entry's slot
+ * (about 8 GiB for an entry of 4 GiB), with the encoder's per-block tables for as many blocks, however many entries the
+ * archive holds.  Per group one
+ * segmented CRC-32 launch, one batch encode, one read-back of the sizes and one k_zip_pack launch that writes headers, names
+ * and bodies; the directory and the end record are made on the host and go up in one copy.  No launch, copy or
+ * synchronisation per entry.
+ * The device form takes d_in, every in_off and d_out at any alignment, writes exactly *out_len bytes and no byte in front of or
+ * behind them, and reads the input only inside the aligned 16-byte groups that hold its bytes (zes_bgzip_dev's contract).
+ * The host form stages the entries (one upload per entry: "nothing per entry" is the device form's), downloads the result
+ * once and runs on one context as the other single host calls do;
+ * count == 0 is answered without a device.
+ * replaces: nothing (the reference has no ZIP container) */
+int zes_zipwrite_bound(const uint64_t* in_len, const uint16_t* name_len, uint32_t count, uint64_t* cap);
+int zes_zipwrite_dev(const uint8_t* d_in, const uint64_t* in_off, const uint64_t* in_len, const uint8_t* names, const uint16_t* name_len,
+                     uint32_t count, uint8_t* d_out, uint64_t cap, uint64_t* out_len, zes_zip_entry* ent, uint32_t flags);
+int zes_zipwrite(const uint8_t* const* in, const uint64_t* in_len, const uint8_t* names, const uint16_t* name_len, uint32_t count,
+                 uint8_t* out, uint64_t cap, uint64_t* out_len, zes_zip_entry* ent, uint32_t flags);
 
 /* Adler-32 of a buffer (standard value as an unsigned 32-bit).
  * replaces: `calcAdler32` src/adler32.ts:1-10 (byte extraction at src/zlib.ts:37-40). */

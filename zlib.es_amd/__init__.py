@@ -137,6 +137,10 @@ def lib():
                                        C.c_void_p, C.c_uint32]
         L.zes_zip_read_alloc.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, ALLOC_FN, C.c_void_p, C.c_void_p,
                                          C.c_void_p, C.c_uint32]
+        L.zes_zipwrite_bound.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, u64p]
+        L.zes_zipwrite_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64, u64p, C.c_void_p,
+                                       C.c_uint32]
+        L.zes_zipwrite.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64, u64p, C.c_void_p, C.c_uint32]
         L.zes_gunzip_alloc.argtypes = [C.c_void_p, C.c_uint64, ALLOC_FN, C.c_void_p, u64p, C.c_uint32]
         L.zes_adler32.argtypes = [C.c_void_p, C.c_uint64, u32p]
         L.zes_adler32_dev.argtypes = [C.c_void_p, C.c_uint64, u32p]
@@ -552,6 +556,50 @@ def zip_read(data, index, sel=None):
     return [got[i][: out_len[i]] if status[i] == 0 else ZlibEsError(status[i], strerror(status[i])) for i in range(cnt)]
 
 
+def _ptr(a):
+    return a.ctypes.data if a.size else None
+
+
+def _zip_names(names):
+    """(blob, name_len) of a list of ``bytes``: the names back to back and their lengths."""
+    names = [bytes(n) for n in names]
+    assert all(len(n) <= 65535 for n in names), "a ZIP entry's name has at most 65535 bytes"
+    return np.frombuffer(b"".join(names), dtype=np.uint8), np.array([len(n) for n in names], dtype=np.uint16)
+
+
+def zip_bound(lens, name_lens):
+    """A capacity that always suffices for the archive of entries of ``lens`` bytes under names of ``name_lens`` bytes, exact
+    when every entry is stored (zes_zipwrite_bound; no GPU needed)."""
+    ln = np.ascontiguousarray(lens, dtype=np.uint64)
+    nl = np.ascontiguousarray(name_lens, dtype=np.uint16)
+    assert ln.ndim == 1 and ln.shape == nl.shape
+    cap = C.c_uint64()
+    rc = lib().zes_zipwrite_bound(_ptr(ln), _ptr(nl), ln.size, C.byref(cap))
+    if rc:
+        _raise(rc)
+    return cap.value
+
+
+def zip_write(entries, flags=0):
+    """A ZIP archive of ``entries``, a list of ``(name: bytes, data)``: ``(archive, index)``, the archive as a uint8 array and
+    ``index`` as zip_index() returns it (zes_zipwrite).  An entry is deflated when that is shorter, else stored; the same
+    entries give the same bytes (date 1980-01-01)."""
+    datas = [_as_u8(d) for _, d in entries]
+    blob, nl = _zip_names([n for n, _ in entries])
+    cnt = len(datas)
+    ln = np.array([d.size for d in datas], dtype=np.uint64)
+    cap = zip_bound(ln, nl)
+    out = np.empty(cap, dtype=np.uint8)
+    ent = np.zeros(cnt, dtype=ZIP_ENTRY)
+    ptrs = (C.c_void_p * max(cnt, 1))(*[d.ctypes.data if d.size else None for d in datas])
+    n = C.c_uint64()
+    rc = lib().zes_zipwrite(ptrs, _ptr(ln), _ptr(blob), _ptr(nl), cnt, out.ctypes.data, cap, C.byref(n), _ptr(ent), flags)
+    if rc:
+        _raise(rc)
+    raw = blob.tobytes()
+    return out[: n.value].copy(), (ent, [raw[int(e["name_off"]) : int(e["name_off"]) + int(e["name_len"])] for e in ent])
+
+
 def gunzip(data, flags=0):
     """gzip.decompress: every member, their outputs concatenated (zes_gunzip_alloc: one decode, an exact-size result)."""
     a = _as_u8(data)
@@ -784,6 +832,32 @@ def zip_read_tensor(t, index, sel=None, out=None, off=None, flags=0):
     if rc:
         _raise(rc)
     return out, off, [int(x) for x in out_len[:cnt]], [int(x) for x in status[:cnt]]
+
+
+def zip_write_tensor(d_in, in_off, in_len, names, out=None, flags=0):
+    """zip_write of entries in a 1-D uint8 CUDA tensor (zes_zipwrite_dev): entry i is ``d_in[in_off[i] : in_off[i] + in_len[i]]``
+    under ``names[i]``.  Returns ``(view, index)``: the filled view of ``out`` (allocated to zip_bound() if None) and the index
+    as zip_index() returns it.  ``d_in``, ``out`` and every offset may be any byte; only the result's bytes are written."""
+    import torch
+
+    assert d_in.is_cuda and d_in.dtype == torch.uint8 and d_in.is_contiguous()
+    off = np.ascontiguousarray(in_off, dtype=np.uint64)
+    ln = np.ascontiguousarray(in_len, dtype=np.uint64)
+    blob, nl = _zip_names(names)
+    cnt = ln.size
+    assert off.ndim == 1 and off.shape == ln.shape and nl.size == cnt, "zip_write_tensor: one offset, one length and one name per entry"
+    assert all(int(o) + int(n) <= d_in.numel() for o, n in zip(off, ln)), "zip_write_tensor: an entry reaches beyond `d_in`"
+    if out is None:
+        out = torch.empty(zip_bound(ln, nl), dtype=torch.uint8, device=d_in.device)
+    assert out.is_cuda and out.dtype == torch.uint8 and out.is_contiguous()
+    torch.cuda.current_stream(d_in.device).synchronize()
+    ent = np.zeros(cnt, dtype=ZIP_ENTRY)
+    n = C.c_uint64()
+    rc = lib().zes_zipwrite_dev(d_in.data_ptr() if d_in.numel() else None, _ptr(off), _ptr(ln), _ptr(blob), _ptr(nl), cnt,
+                                out.data_ptr() if out.numel() else None, out.numel(), C.byref(n), _ptr(ent), flags)
+    _raise_need(rc, n)
+    raw = blob.tobytes()
+    return out[: n.value], (ent, [raw[int(e["name_off"]) : int(e["name_off"]) + int(e["name_len"])] for e in ent])
 
 
 def _batch_call(fn, d_in, in_off, in_len, d_out, out_off, out_cap, *extra):

@@ -5182,6 +5182,267 @@ int zes_zip_read_alloc(const uint8_t* in, uint64_t c, const zes_zip_entry* ent, 
   return ZES_OK;
 }
 
+// ---- ZIP writer (include/zes.h: "zes_zipwrite*"): local headers, names and bodies by k_zip_pack, the directory by the host ----
+constexpr uint32_t ZIPW_GROUP = 1024;             // entries encoded at once ...
+constexpr uint32_t ZIPW_GROUP_PIECES = 4;         // ... under ZES_F_PIECES
+constexpr uint64_t ZIPW_GROUP_SLOTS = 256ull << 20;  // ... and the bytes of their encoder slots (1024 entries of up to 64 KiB take half of it)
+constexpr uint64_t ZIPW_GROUP_SLOTS_PIECES = 1ull << 20;  // ... under ZES_F_PIECES: two entries of 300000 bytes do not share a group
+constexpr uint32_t ZIPW_COUNT_MAX = 65534;        // (65535 is ZIP64's mark)
+constexpr uint64_t ZIPW_LEN_MAX = 0xFFFFFFFEull;  // (as is 0xFFFFFFFF in a size or an offset)
+static_assert(ZIPW_GROUP <= DEFLATE_TABLE_BUFS && ZIPW_GROUP <= DEFLATE_DIRECT_BUFS, "a group's buffer table and results go through the page-locked area");
+
+static void put_le16(uint8_t* p, uint32_t v) {
+  p[0] = (uint8_t)v;
+  p[1] = (uint8_t)(v >> 8);
+}
+
+static uint64_t zipwrite_bound(const uint64_t* in_len, const uint16_t* name_len, uint32_t count) {
+  uint64_t b = ZIP_END;
+  for (uint32_t i = 0; i < count; i++) b += 30 + 46 + 2 * (uint64_t)name_len[i] + in_len[i];
+  return b;
+}
+
+// the end record of an archive of `count` entries whose directory is [cd_off, cd_off + cd_size)
+static void zip_end_record(uint8_t* e, uint32_t count, uint64_t cd_size, uint64_t cd_off) {
+  memset(e, 0, ZIP_END);
+  put_le32(e, 0x06054b50u);
+  put_le16(e + 8, count);
+  put_le16(e + 10, count);
+  put_le32(e + 12, (uint32_t)cd_size);
+  put_le32(e + 16, (uint32_t)cd_off);
+}
+
+// What both forms decide from the arguments alone (`data(i)`: entry i's bytes are there): ZES_E_ARG, then ZES_E_UNSUPPORTED
+static int zipwrite_args(const std::function<bool(uint32_t)>& data, const uint64_t* in_len, const uint8_t* names, const uint16_t* name_len, uint32_t count, const uint8_t* out, uint64_t cap,
+                         uint64_t* out_len, uint32_t flags) {
+  if (!out_len || (flags & ~ZES_F_PIECES) || (!out && cap)) return ZES_E_ARG;
+  *out_len = 0;
+  if (count && (!in_len || !name_len)) return ZES_E_ARG;
+  uint64_t nbytes = 0;
+  for (uint32_t i = 0; i < count; i++) {
+    if (in_len[i] && !data(i)) return ZES_E_ARG;
+    nbytes += name_len[i];
+  }
+  if (nbytes && !names) return ZES_E_ARG;
+  if (count > ZIPW_COUNT_MAX) return ZES_E_UNSUPPORTED;
+  for (uint32_t i = 0; i < count; i++)
+    if (in_len[i] > ZIPW_LEN_MAX) return ZES_E_UNSUPPORTED;
+  return ZES_OK;
+}
+
+// The archive of the entries d_in[in_off[i], + in_len[i]) into d_out[0, cap), group by group as bgzip_core goes: a group is
+// up to ZIPW_GROUP entries (ZIPW_GROUP_PIECES under ZES_F_PIECES) whose encoder slots take up to ZIPW_GROUP_SLOTS bytes (ZIPW_GROUP_SLOTS_PIECES),
+// and one entry at least.  The group's entries are checksummed by one segmented CRC-32 launch and those the encoder accepts
+// are encoded as independent buffers into 16-byte aligned slots of g.gz_bodies; the sizes come back, the host chooses the
+// method (8 when the raw stream is shorter than the entry, else 0) and the places, and one k_zip_pack launch writes the
+// group's headers, names and bodies.  The directory and the end record are made here and go up in one copy behind the last
+// group.  g.gz_tab holds the names (uploaded once, padded to whole 16-byte groups) and behind them the group's records.  A
+// result beyond cap: every group is still encoded (the size needed is the answer), and from the first group that does not
+// fit whole nothing more is written.  ent: null, or the records zes_zip_index lists for the result.
+// The host memory that the call's asynchronous uploads read (the padded names, every group's records, the directory) is the
+// caller's, zipwrite_core's, which lets the stream finish before it gives it up on any way out.
+struct ZipwHost {
+  std::vector<uint8_t> names, cd;
+  std::vector<ZesZipPackRec> recs;
+};
+static int zipwrite_groups(ZipwHost& hm, const uint8_t* d_in, const uint64_t* in_off, const uint64_t* in_len, const uint8_t* names, const uint16_t* name_len, uint32_t count,
+                         uint8_t* d_out, uint64_t cap, uint64_t* out_len, zes_zip_entry* ent, uint32_t flags) {
+  int rc;
+  g.carry.clear();
+  const uint32_t group = (flags & ZES_F_PIECES) ? ZIPW_GROUP_PIECES : ZIPW_GROUP;
+  const uint64_t group_slots = (flags & ZES_F_PIECES) ? ZIPW_GROUP_SLOTS_PIECES : ZIPW_GROUP_SLOTS;
+  std::vector<uint32_t> name_off((size_t)count + 1, 0);
+  for (uint32_t i = 0; i < count; i++) name_off[i + 1] = name_off[i] + name_len[i];  // (65534 names of 65535 bytes fit 32 bits)
+  const size_t names_pad = ((size_t)name_off[count] + 15) & ~(size_t)15;
+  std::vector<uint8_t>& hnames = hm.names;
+  hnames.assign(names_pad, 0);
+  if (name_off[count]) memcpy(hnames.data(), names, name_off[count]);
+  if ((rc = ensure(g.gz_tab, names_pad + sizeof(ZesZipPackRec) * ((size_t)std::min(group, count) + 1)))) return rc;
+  if (names_pad) HIPCHK(hipMemcpyAsync(g.gz_tab.p, hnames.data(), names_pad, hipMemcpyHostToDevice, g.stream));
+  ZesZipPackRec* d_recs = (ZesZipPackRec*)((uint8_t*)g.gz_tab.p + names_pad);
+  std::vector<zes_zip_entry> z(count);
+  // (of the whole call: uploads read it until the last synchronisation.  A group has one entry at least and a closing record:
+  // at most `count` groups, whichever bound ends them)
+  std::vector<ZesZipPackRec>& recs = hm.recs;
+  recs.resize(2 * (size_t)count + 1);
+  size_t rpos = 0;
+  const size_t gmax = std::min(group, count);
+  std::vector<uint64_t> o_off(gmax), o_cap(gmax), o_len(gmax);
+  std::vector<int32_t> status(gmax);
+  std::vector<ZesCrcSeg> csegs(gmax);
+  std::vector<uint32_t> crc(gmax);
+  auto slot_of = [](uint64_t len) { return deflate_throws(len) ? 0ull : gz_up16(deflate_bound(len)); };
+  uint64_t total = 0;
+  bool fits = true;
+  for (uint32_t e0 = 0; e0 < count;) {
+    uint32_t cnt = 0;
+    uint64_t slots = 0;
+    while (e0 + cnt < count && cnt < group && (cnt == 0 || slots + slot_of(in_len[e0 + cnt]) <= group_slots)) {
+      o_off[cnt] = slots;
+      o_cap[cnt] = slot_of(in_len[e0 + cnt]);
+      slots += o_cap[cnt];
+      csegs[cnt] = ZesCrcSeg{in_off[e0 + cnt], in_len[e0 + cnt]};
+      cnt++;
+    }
+    if ((rc = ensure(g.gz_bodies, slots + 64))) return rc;
+    if ((rc = crc32_batch_locked(d_in, csegs.data(), cnt, crc.data()))) return rc;
+    if (slots) {  // (a group of entries the encoder refuses makes no call: no times of its own to keep)
+      if ((rc = deflate_batch_core(d_in, in_off + e0, in_len + e0, (uint8_t*)g.gz_bodies.p, o_off.data(), o_cap.data(), o_len.data(), status.data(), cnt)))
+        return rc;
+      keep_times();
+    }
+    ZesZipPackRec* gr = &recs[rpos];
+    uint32_t wgs = 0;
+    for (uint32_t k = 0; k < cnt; k++) {
+      const uint32_t i = e0 + k;
+      const uint64_t len = in_len[i];
+      const bool enc = !deflate_throws(len);
+      if (enc && (status[k] != ZES_OK || o_len[k] < 6)) return status[k] ? status[k] : ZES_E_DEVICE;
+      const uint64_t raw = enc ? o_len[k] - 6 : 0;  // without 78 9C and the Adler-32
+      const bool deflated = enc && raw < len;
+      if (total >= 0xFFFFFFFFull) return ZES_E_UNSUPPORTED;
+      bool utf8 = false;
+      for (uint32_t b = 0; b < name_len[i]; b++) utf8 = utf8 || names[name_off[i] + b] >= 0x80;
+      zes_zip_entry& t = z[i];
+      t.hdr_off = total;
+      t.name_pos = 0;  // (known with the directory's place)
+      t.csize = (uint32_t)(deflated ? raw : len);
+      t.usize = (uint32_t)len;
+      t.crc = crc[k];
+      t.name_off = name_off[i];
+      t.name_len = name_len[i];
+      t.method = deflated ? 8 : 0;
+      t.flags = utf8 ? 0x0800 : 0;
+      t.pad = 0;
+      ZesZipPackRec& r = gr[k];
+      memset(&r, 0, sizeof r);
+      r.src_off = deflated ? o_off[k] + 2 : in_off[i];
+      r.dst_off = total;
+      r.csize = t.csize;
+      r.usize = t.usize;
+      r.crc = t.crc;
+      r.name_off = t.name_off;
+      r.first_wg = wgs;
+      r.name_len = t.name_len;
+      r.method = t.method;
+      r.flags = t.flags;
+      wgs += (uint32_t)std::min<uint64_t>(std::max<uint64_t>(((uint64_t)t.csize + GZ_GATHER_PIECE - 1) / GZ_GATHER_PIECE, 1), ZES_ZIP_PACK_SHARES);
+      total += 30ull + t.name_len + t.csize;
+    }
+    memset(&gr[cnt], 0, sizeof(ZesZipPackRec));
+    gr[cnt].first_wg = wgs;
+    fits = fits && total <= cap && d_out != nullptr;
+    if (fits) {
+      HIPCHK(hipMemcpyAsync(d_recs, gr, sizeof(ZesZipPackRec) * ((size_t)cnt + 1), hipMemcpyHostToDevice, g.stream));
+      Timed t("k_zip_pack");
+      hipLaunchKernelGGL(k_zip_pack, dim3(wgs), dim3(GZ_GATHER_THREADS), 0, g.stream, d_in, (const uint8_t*)g.gz_bodies.p, (const uint8_t*)g.gz_tab.p, d_out,
+                         (const ZesZipPackRec*)d_recs, cnt);
+    }
+    HIPCHK(hipGetLastError());
+    rpos += (size_t)cnt + 1;
+    e0 += cnt;
+  }
+  // the directory and the end record
+  const uint64_t cd_off = total;
+  std::vector<uint8_t>& cd = hm.cd;
+  cd.clear();
+  cd.reserve((size_t)count * 46 + name_off[count] + ZIP_END);
+  for (uint32_t i = 0; i < count; i++) {
+    zes_zip_entry& t = z[i];
+    const size_t at = cd.size();
+    cd.resize(at + 46 + t.name_len, 0);
+    uint8_t* r = &cd[at];
+    put_le32(r, 0x02014b50u);
+    put_le16(r + 4, 20);
+    put_le16(r + 6, 20);
+    put_le16(r + 8, t.flags);
+    put_le16(r + 10, t.method);
+    put_le16(r + 14, 33);  // 1980-01-01, time 0
+    put_le32(r + 16, t.crc);
+    put_le32(r + 20, t.csize);
+    put_le32(r + 24, t.usize);
+    put_le16(r + 28, t.name_len);
+    put_le32(r + 42, (uint32_t)t.hdr_off);
+    if (t.name_len) memcpy(r + 46, names + t.name_off, t.name_len);
+    t.name_pos = cd_off + at + 46;
+  }
+  const uint64_t cd_size = cd.size();
+  if (cd_off >= 0xFFFFFFFFull || cd_size >= 0xFFFFFFFFull) return ZES_E_UNSUPPORTED;
+  cd.resize((size_t)cd_size + ZIP_END);
+  zip_end_record(&cd[(size_t)cd_size], count, cd_size, cd_off);
+  total += cd.size();
+  fits = fits && total <= cap && d_out != nullptr;
+  if (fits) HIPCHK(hipMemcpyAsync(d_out + cd_off, cd.data(), cd.size(), hipMemcpyHostToDevice, g.stream));
+  HIPCHK(hipStreamSynchronize(g.stream));
+  *out_len = total;
+  if (!fits) return ZES_E_NOSPACE;
+  if (ent && count) memcpy(ent, z.data(), sizeof(zes_zip_entry) * (size_t)count);
+  return ZES_OK;
+}
+
+static int zipwrite_core(const uint8_t* d_in, const uint64_t* in_off, const uint64_t* in_len, const uint8_t* names, const uint16_t* name_len, uint32_t count,
+                         uint8_t* d_out, uint64_t cap, uint64_t* out_len, zes_zip_entry* ent, uint32_t flags) {
+  ZipwHost hm;
+  const int rc = zipwrite_groups(hm, d_in, in_off, in_len, names, name_len, count, d_out, cap, out_len, ent, flags);
+  // (a way out in the middle: what is under way may still read hm.  ZES_OK and ZES_E_NOSPACE come from behind the last synchronisation)
+  if (rc && rc != ZES_E_NOSPACE && hipStreamSynchronize(g.stream) != hipSuccess) (void)hipGetLastError();
+  return rc;
+}
+
+int zes_zipwrite_bound(const uint64_t* in_len, const uint16_t* name_len, uint32_t count, uint64_t* cap) {
+  if (!cap || (count && (!in_len || !name_len))) return ZES_E_ARG;
+  *cap = zipwrite_bound(in_len, name_len, count);
+  return ZES_OK;
+}
+
+int zes_zipwrite_dev(const uint8_t* d_in, const uint64_t* in_off, const uint64_t* in_len, const uint8_t* names, const uint16_t* name_len, uint32_t count,
+                     uint8_t* d_out, uint64_t cap, uint64_t* out_len, zes_zip_entry* ent, uint32_t flags) {
+  ROUTE_DEV(d_out, d_in);
+  if (count && !in_off) return ZES_E_ARG;
+  if (const int arc = zipwrite_args([&](uint32_t) { return d_in != nullptr; }, in_len, names, name_len, count, d_out, cap, out_len, flags)) return arc;
+  LOCK_READY();
+  rc = zipwrite_core(d_in, in_off, in_len, names, name_len, count, d_out, cap, out_len, ent, flags);
+  if (rc && rc != ZES_E_NOSPACE) (void)hipGetLastError();
+  collect_times();
+  return rc;
+}
+
+int zes_zipwrite(const uint8_t* const* in, const uint64_t* in_len, const uint8_t* names, const uint16_t* name_len, uint32_t count, uint8_t* out, uint64_t cap,
+                 uint64_t* out_len, zes_zip_entry* ent, uint32_t flags) {
+  UseDev ud(route_host());
+  if (count && !in) return ZES_E_ARG;
+  if (const int arc = zipwrite_args([&](uint32_t i) { return in[i] != nullptr; }, in_len, names, name_len, count, out, cap, out_len, flags)) return arc;
+  if (count == 0) {  // the end record alone: nothing to compute
+    *out_len = ZIP_END;
+    if (cap < ZIP_END) return ZES_E_NOSPACE;
+    zip_end_record(out, 0, 0, 0);
+    return ZES_OK;
+  }
+  LOCK_READY();
+  // every entry at a 16-byte boundary of g.gz_in
+  std::vector<uint64_t> in_off(count);
+  uint64_t tin = 0;
+  for (uint32_t i = 0; i < count; i++) {
+    in_off[i] = tin;
+    tin += gz_up16(in_len[i]);
+  }
+  const uint64_t bound = zipwrite_bound(in_len, name_len, count);
+  if ((rc = ensure(g.gz_in, tin + 64)) || (rc = ensure(g.gz_acc, bound + 64))) return rc;
+  for (uint32_t i = 0; i < count; i++)
+    if ((rc = upload((uint8_t*)g.gz_in.p + in_off[i], in[i], in_len[i]))) return rc;
+  uint64_t total = 0;
+  std::vector<zes_zip_entry> z(ent ? count : 0);
+  rc = zipwrite_core((const uint8_t*)g.gz_in.p, in_off.data(), in_len, names, name_len, count, (uint8_t*)g.gz_acc.p, bound, &total, ent ? z.data() : nullptr, flags);
+  if (rc) (void)hipGetLastError();
+  collect_times();
+  if (rc) return rc;
+  *out_len = total;
+  if (total > cap) return ZES_E_NOSPACE;
+  if ((rc = download(out, (const uint8_t*)g.gz_acc.p, total))) return rc;
+  if (ent) memcpy(ent, z.data(), sizeof(zes_zip_entry) * (size_t)count);
+  return ZES_OK;
+}
+
 int zes_stage_lz77_dev(const uint8_t* d_in, uint64_t n, uint64_t start, uint32_t len, uint32_t* h_tokens, uint32_t* ntokens) {
   ROUTE_DEV(d_in);
   if (!h_tokens || !ntokens || len < 2 || len > ZES_BLK || start + len > n || (start % ZES_BLK)) return ZES_E_ARG;

@@ -1,5 +1,5 @@
 // zes_gzip.hip — device pieces of the member-parallel gzip reader (zes_api.hip: gunzip_parallel) and of the BGZF writer
-// (zes_api.hip: bgzip_core), and of the ZIP reader (zes_api.hip: zip_read_core).
+// (zes_api.hip: bgzip_core), and of the ZIP reader and writer (zes_api.hip: zip_read_core, zipwrite_core).
 //
 // A file whose members all state their own size — BGZF, the format of bgzip / htslib: every member's extra field holds a
 // subfield 'B','C' with BSIZE = member size - 1 — can be cut into its members without decoding anything.
@@ -29,6 +29,13 @@
 //                csize body bytes as shares y of gz_copy: a DEFLATE body into its scratch slot behind a 78 9C (k_gz_gather's
 //                zhdr layout), a stored one straight to its place in the output.  Only the entry's own bytes are written, and
 //                the file is read only inside the aligned 16-byte groups that hold bytes of it.
+//   k_zip_pack   the local part of a ZIP archive being written, over a flat list of workgroups: an entry has as many as its
+//                body has 64 KiB pieces (one at least, ZES_ZIP_PACK_SHARES at most), so a body of gigabytes is shared and a
+//                thousand tiny entries launch a thousand workgroups.  A workgroup finds its entry by bisection over the
+//                records' first workgroups.  The entry's first one writes the 30 header bytes and the name (out of the device
+//                copy of the names); all of them copy the body as shares of gz_copy — the encoder's stream out of its scratch
+//                slot, or the caller's bytes.  Entries meet at any byte: only the entry's own bytes are written, each by one
+//                workgroup, and the input is read only inside the aligned 16-byte groups that hold the entry's bytes.
 #include "../../include/zes.h"
 #include "zes_common.h"
 #include "zes_kernels.h"
@@ -258,4 +265,35 @@ __global__ __launch_bounds__(GZ_GATHER_THREADS) void k_zip_stage(const uint8_t* 
   } else {
     gz_copy(body, out + r.dst_off, r.csize, tid, blockIdx.y, gridDim.y);
   }
+}
+
+__global__ __launch_bounds__(GZ_GATHER_THREADS) void k_zip_pack(const uint8_t* __restrict__ in, const uint8_t* __restrict__ slots,
+                                                               const uint8_t* __restrict__ names, uint8_t* __restrict__ out,
+                                                               const ZesZipPackRec* __restrict__ recs, uint32_t count) {
+  // the last record whose first workgroup is not behind this one (recs[count] closes the table: no workgroup is its own)
+  uint32_t lo = 0, hi = count;
+  while (hi - lo > 1) {
+    const uint32_t mid = (lo + hi) / 2;
+    if (recs[mid].first_wg <= blockIdx.x) lo = mid; else hi = mid;
+  }
+  const ZesZipPackRec r = recs[lo];
+  const uint32_t y = blockIdx.x - r.first_wg, ny = recs[lo + 1].first_wg - r.first_wg;
+  const uint32_t tid = threadIdx.x;
+  uint8_t* h = out + r.dst_off;
+  if (y == 0) {
+    if (tid < 30) {  // the local header, as eight little-endian words (the last one's upper half is not part of it)
+      const uint32_t k = tid >> 2;
+      const uint32_t w = k == 0 ? 0x04034b50u
+                       : k == 1 ? 20u | (uint32_t)r.flags << 16
+                       : k == 2 ? (uint32_t)r.method  // time 0
+                       : k == 3 ? 33u | r.crc << 16   // date 1980-01-01
+                       : k == 4 ? r.crc >> 16 | r.csize << 16
+                       : k == 5 ? r.csize >> 16 | r.usize << 16
+                       : k == 6 ? r.usize >> 16 | (uint32_t)r.name_len << 16
+                                : 0u;                 // no extra field
+      h[tid] = (uint8_t)(w >> (8 * (tid & 3u)));
+    }
+    gz_copy(names + r.name_off, h + 30, r.name_len, tid, 0, 1);
+  }
+  gz_copy((r.method == 8 ? slots : in) + r.src_off, h + 30 + r.name_len, r.csize, tid, y, ny);
 }

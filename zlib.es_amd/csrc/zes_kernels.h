@@ -204,6 +204,20 @@ struct ZesZipVerdict {
   uint32_t pad;
   uint64_t data_off;  // the body's first byte (as hdr_at)
 };
+// k_zip_pack (zes_gzip.hip): one entry of a ZIP archive being written.  The table has a closing record behind the last
+// entry: only its first_wg counts, the launch's workgroups
+struct ZesZipPackRec {
+  uint64_t src_off;   // the body's source: method 8 the raw stream's first byte in the slots, method 0 the entry's bytes in the input
+  uint64_t dst_off;   // the local header's first byte in the output
+  uint32_t csize;     // the body's bytes
+  uint32_t usize;     // the entry's bytes
+  uint32_t crc;       // their CRC-32
+  uint32_t name_off;  // the name in the device copy of the names
+  uint32_t first_wg;  // the entry's first workgroup: it has the workgroups up to the next record's first one
+  uint16_t name_len, method, flags, pad;
+  uint32_t pad2;
+};
+#define ZES_ZIP_PACK_SHARES 1024u  // workgroups that share one entry's body, at most (a share is whole 64 KiB pieces)
 
 // CRC-32 host arithmetic (zes_crc.hip): shift(s, k) = s * x^(8k) mod P; the kernel's table with npow powers
 uint32_t zes_crc_shift(uint32_t s, uint64_t k);
@@ -284,6 +298,7 @@ __global__ void k_bgzf_mark(const uint8_t*, uint64_t, ZesBgzfMark*, ZesBgzfCand*
 __global__ void k_gz_gather(const uint8_t*, uint8_t*, const ZesGzSeg*);
 __global__ void k_bgzf_pack(const uint8_t*, const uint8_t*, uint8_t*, const ZesBgzfRec*);
 __global__ void k_zip_stage(const uint8_t*, uint8_t*, uint8_t*, const ZesZipRec*, ZesZipVerdict*);
+__global__ void k_zip_pack(const uint8_t*, const uint8_t*, const uint8_t*, uint8_t*, const ZesZipPackRec*, uint32_t);
 __global__ void k_adler_blocks(const uint8_t*, const ZesBuf*, const ZesBlk*, unsigned long long*);
 __global__ void k_adler_seg(const uint8_t*, const ZesCrcSeg*, const uint2*, unsigned long long*);
 __global__ void k_layout(uint8_t*, const ZesBuf*, ZesBlk*, const unsigned long long*, ZesRes*);

@@ -1032,6 +1032,39 @@ napi_value ZipRead(napi_env env, napi_callback_info info) {
   return j.rc == 0 ? batch_results(env, &j) : throw_status(env, j.rc);
 }
 
+// zip(names, datas): a ZIP archive of datas[i] under names[i], two arrays of Uint8Array of one length (the façade takes the
+// file objects apart and encodes string names): one call, the bounded result (include/zes.h: zes_zipwrite)
+napi_value Zip(napi_env env, napi_callback_info info) {
+  static const char SIG[] = "zip(files)";
+  const Args a = get_args(env, info);
+  bool arr_n = false, arr_d = false;
+  uint32_t count = 0, count_d = 0;
+  if (a.argc < 2 || napi_is_array(env, a.argv[0], &arr_n) != napi_ok || !arr_n || napi_is_array(env, a.argv[1], &arr_d) != napi_ok || !arr_d ||
+      napi_get_array_length(env, a.argv[0], &count) != napi_ok || napi_get_array_length(env, a.argv[1], &count_d) != napi_ok || count != count_d)
+    return throw_type(env, std::string(SIG) + ": files must be an array of { name, data }");
+  std::vector<const uint8_t*> in((size_t)count + 1);
+  std::vector<uint64_t> in_len((size_t)count + 1);
+  std::vector<uint16_t> name_len((size_t)count + 1);
+  std::vector<uint8_t> names(1);
+  for (uint32_t i = 0; i < count; i++) {
+    napi_value vn, vd;
+    const uint8_t* np = nullptr;
+    size_t nn = 0, dn = 0;
+    if (napi_get_element(env, a.argv[0], i, &vn) != napi_ok || !get_bytes(env, vn, &np, &nn) || nn > 65535)
+      return throw_type(env, std::string(SIG) + ": every name must be a string or a Uint8Array of at most 65535 bytes");
+    if (napi_get_element(env, a.argv[1], i, &vd) != napi_ok || !get_bytes(env, vd, &in[i], &dn))
+      return throw_type(env, std::string(SIG) + ": every data must be a Uint8Array");
+    in_len[i] = dn;
+    name_len[i] = (uint16_t)nn;
+    names.insert(names.end(), np, np + nn);
+  }
+  uint64_t cap = 0;
+  if (zes_zipwrite_bound(in_len.data(), name_len.data(), count, &cap)) return throw_status(env, ZES_E_ARG);
+  return bounded(env, result_alloc(cap), [&](uint8_t* out, uint64_t* len) {
+    return zes_zipwrite(in.data(), in_len.data(), names.data() + 1, name_len.data(), count, out, cap, len, nullptr, ZES_F_DEFAULT);
+  });
+}
+
 // allocPinned(n): a Uint8Array in page-locked memory (zes_host_alloc) — buffers from here cross PCIe without the
 // library's staging copy; released when the array is collected.  The release runs on the JS thread and takes
 // the library's lock for a moment (no stream is waited for: hipHostFree itself waits for work that uses the block), so
@@ -1077,6 +1110,7 @@ napi_value ModuleInit(napi_env env, napi_value exports) {
       {"bgzfRead", swept<BgzfRead>},
       {"zipIndex", swept<ZipIndex>},
       {"zipRead", swept<ZipRead>},
+      {"zip", swept<Zip>},
       {"lastGunzipMembers", swept<LastGunzipMembers>},
       {"init", swept<Init>},
       {"initDevices", swept<InitDevices>},

@@ -27,6 +27,7 @@ export declare type ZipEntry = { nameBytes: Uint8Array, name: string, method: nu
 export declare type ZipIndex = { entries: ZipEntry[], raw: Uint8Array };
 export declare function zipIndex(file: Uint8Array): ZipIndex;
 export declare function zipRead(file: Uint8Array, index: ZipIndex, sel?: number[] | Uint32Array): BatchResult[];
+export declare function zip(files: { name: string | Uint8Array, data: Uint8Array }[]): Uint8Array;
 export declare function init(device: number): void;
 export declare function initDevices(n?: number): number;
 export declare function trim(): void;

@@ -133,7 +133,7 @@ function bgzfRead(file, index, pos, len) {
 }
 
 /**
- * Extra (not in the reference API): ZIP archives, read only.  `zipIndex` lists the archive's entries from its central
+ * Extra (not in the reference API): ZIP archives, reading.  `zipIndex` lists the archive's entries from its central
  * directory on the host (no device is touched, nothing is decoded): per entry the name as the archive holds it (`nameBytes`)
  * and as a string (`name`: UTF-8 when flag bit 11 says so, else byte for byte as code points — CP437 is not decoded), the
  * method, the flags, both sizes and the CRC-32; `raw` is the same list as the records the library reads (40 bytes an entry)
@@ -162,6 +162,19 @@ function zipIndex(file) {
 
 function zipRead(file, index, ...sel) {
   return addon.zipRead(file, index, sel[0]);
+}
+
+/**
+ * Extra (not in the reference API): `zip` writes a ZIP archive of `files` in one call: every entry is checksummed and encoded
+ * on the device as one batch, deflated where that is shorter than the data and stored otherwise.  A `name` given as a string is
+ * encoded as UTF-8 (a name with a byte >= 0x80 sets flag bit 11); a Uint8Array is taken as it is.  The same files give the
+ * same bytes (date 1980-01-01); zipIndex() / zipRead() and any unzip read the result.  No ZIP64: at most 65534 entries, and
+ * sizes and offsets below 4 GiB, else the library's "unsupported ZIP feature" Error.
+ */
+function zip(files) {
+  if (!Array.isArray(files)) throw new TypeError('zip(files): files must be an array of { name, data }');
+  const names = files.map((f) => (f && typeof f.name === 'string' ? new TextEncoder().encode(f.name) : f && f.name));
+  return addon.zip(names, files.map((f) => f && f.data));
 }
 
 /**
@@ -216,6 +229,7 @@ exports.bgzfIndex = bgzfIndex;
 exports.bgzfRead = bgzfRead;
 exports.zipIndex = zipIndex;
 exports.zipRead = zipRead;
+exports.zip = zip;
 exports.lastGunzipMembers = lastGunzipMembers;
 exports.adler32 = adler32;
 exports.init = init;

@@ -23,6 +23,7 @@ export const bgzfIndex = z.bgzfIndex;
 export const bgzfRead = z.bgzfRead;
 export const zipIndex = z.zipIndex;
 export const zipRead = z.zipRead;
+export const zip = z.zip;
 export const init = z.init;
 export const initDevices = z.initDevices;
 export const trim = z.trim;

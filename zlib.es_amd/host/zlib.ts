@@ -22,6 +22,7 @@ type Offset = number | bigint;
 type ZipEntry = { nameBytes: Uint8Array, name: string, method: number, flags: number, compressedSize: number, size: number, crc32: number };
 type ZipIndex = { entries: ZipEntry[], raw: Uint8Array };
 type ZipSelection = number[] | Uint32Array;
+type ZipFile = { name: string | Uint8Array, data: Uint8Array };
 /**
  * Extra (not in the reference API): `verify: true` makes an inflate form check the stream's Adler-32 trailer against its
  * result; a trailer that is missing or does not match is the Error "zes: checksum mismatch".  The reference ignores the
@@ -139,7 +140,7 @@ export function bgzfRead(file: Uint8Array, index: BgzfIndex, pos: Offset, len: O
 }
 
 /**
- * Extra (not in the reference API): ZIP archives, read only.  `zipIndex` lists the archive's entries from its central
+ * Extra (not in the reference API): ZIP archives, reading.  `zipIndex` lists the archive's entries from its central
  * directory on the host (no device is touched, nothing is decoded): per entry the name as the archive holds it (`nameBytes`)
  * and as a string (`name`: UTF-8 when flag bit 11 says so, else byte for byte as code points — CP437 is not decoded), the
  * method, the flags, both sizes and the CRC-32; `raw` is the same list as the records the library reads (40 bytes an entry)
@@ -168,6 +169,19 @@ export function zipIndex(file: Uint8Array): ZipIndex {
 
 export function zipRead(file: Uint8Array, index: ZipIndex, ...sel: ZipSelection[]): BatchResult[] {
   return addon.zipRead(file, index, sel[0]);
+}
+
+/**
+ * Extra (not in the reference API): `zip` writes a ZIP archive of `files` in one call: every entry is checksummed and encoded
+ * on the device as one batch, deflated where that is shorter than the data and stored otherwise.  A `name` given as a string is
+ * encoded as UTF-8 (a name with a byte >= 0x80 sets flag bit 11); a Uint8Array is taken as it is.  The same files give the
+ * same bytes (date 1980-01-01); zipIndex() / zipRead() and any unzip read the result.  No ZIP64: at most 65534 entries, and
+ * sizes and offsets below 4 GiB, else the library's "unsupported ZIP feature" Error.
+ */
+export function zip(files: ZipFile[]): Uint8Array {
+  if (!Array.isArray(files)) throw new TypeError('zip(files): files must be an array of { name, data }');
+  const names = files.map((f) => (f && typeof f.name === 'string' ? new TextEncoder().encode(f.name) : f && f.name));
+  return addon.zip(names, files.map((f) => f && f.data));
 }
 
 /**
