@@ -1,11 +1,12 @@
-"""The checksum / gzip / BGZF layer's launches: a case per seam of the layer, each at the smallest shape that reaches it, and
+"""The checksum / gzip / BGZF / ZIP layer's launches: a case per seam of the layer, each at the smallest shape that reaches it, and
 a runner that records what a call came to — status, result, and the launches per profiled name (zes_last_kernel_times).
 tests/test_gpu_container_launches.py compares the records with tests/golden/container_launches.json.
 
     python -m tests._container_cases      writes tests/golden/container_launches.json (ZES_LIB selects the library)
 
 The launch counts are kept for this layer's kernels (LAYER); of a call's inflate and deflate kernels only the set of names.
-Every input is the library's own (its generators, its encoders): nothing depends on the zlib build beside it.
+Every input of the checksum, gzip and BGZF cases is the library's own (its generators, its encoders); the ZIP archives are
+those of tests/_zip.py and tests/_zipwrite.py (CPython's bodies, the oracle's expected archive), built on the host.
 """
 import functools
 import gzip as pygzip
@@ -19,7 +20,12 @@ import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLDEN = os.path.join(ROOT, "tests", "golden", "container_launches.json")
-LAYER = ("k_crc32", "k_crc32_seg", "k_adler", "k_adler_seg", "k_gz_walk", "k_gz_gather", "k_bgzf_mark", "k_bgzf_pack")
+if os.path.join(ROOT, "tests") not in sys.path:  # (python -m tests._container_cases)
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+import _zip  # noqa: E402
+import _zipwrite  # noqa: E402
+
+LAYER = ("k_crc32", "k_crc32_seg", "k_adler", "k_adler_seg", "k_gz_walk", "k_gz_gather", "k_bgzf_mark", "k_bgzf_pack", "k_zip_stage", "k_zip_pack")
 CHUNK = 65280  # ZES_BGZF_CHUNK
 
 # (alignment, length) of the checksum cases' buffers: a start inside a 16-byte piece, a tail behind the last 16-byte boundary,
@@ -29,7 +35,10 @@ SEGMENTS = [(15, 0), (15, 1), (0, 0), (15, 17), (0, 65536), (1, 65537), (7, 1310
 CASES = ["crc32 batch", "adler32 batch", "crc32 batch, every length 0", "adler32 batch, every length 0", "crc32 batch, count 0",
          "adler32 batch, count 0", "gunzip_tensor bgzf", "gunzip bgzf", "gunzip two members", "bgzip_tensor", "bgzip_tensor pieces",
          "bgzf_index_tensor", "bgzf_index_tensor walk", "bgzf_read_tensor", "bgzf_read", "inflate_batch_tensor checked",
-         "inflate_batch checked"]
+         "inflate_batch checked",
+         "zip_read_tensor standard", "zip_read standard", "zip_read_tensor failures", "zip_read failures", "zip_read_tensor stored only",
+         "zip_read_tensor one rejected", "zip_read_tensor count 0", "zipwrite_tensor nine pieces", "zipwrite_tensor refused only", "zipwrite nine",
+         "bgzip_tensor 1 byte", "bgzf_read_tensor body damaged", "bgzf_read_tensor crc damaged", "gunzip_tensor bgzf crc damaged"]
 
 
 def _pkg():
@@ -64,6 +73,34 @@ def bgzf_file(n):
     blob = _pkg().bgzip(plain)
     assert pygzip.decompress(blob.tobytes()) == plain.tobytes()
     return blob, plain.tobytes()
+
+
+@functools.lru_cache(maxsize=None)
+def bgzf_damaged(what):
+    """The 70000-byte file with one bit flipped: the first of member 0's body, its first block's BFINAL ("body": the stream no
+    longer ends where the member says), or one of member 1's CRC-32 ("crc")."""
+    blob, plain = bgzf_file(70000)
+    coff = _pkg().bgzf_index(blob)[0].tolist()
+    bad = blob.copy()
+    bad[coff[0] + 18 if what == "body" else coff[2] - 8] ^= 1
+    return bad, plain
+
+
+@functools.lru_cache(maxsize=None)
+def zip_archive(which):
+    """(the standard or the failure archive of tests/_zip.py, per entry (the expected status or statuses, the plain bytes))."""
+    if which == "standard":
+        blob, plain, _ = _zip.standard()
+        return np.frombuffer(blob, dtype=np.uint8).copy(), [(0, p) for p in plain]
+    blob, plan = _zip.failures()
+    return np.frombuffer(blob, dtype=np.uint8).copy(), [(want, data) for _, want, data in plan]
+
+
+def zipwrite_entries(z, which):
+    if which == "nine":
+        return _zipwrite.nine(z)
+    c = dict(_zipwrite.cases(z))
+    return [(n, c[n]) for n in (b"refused/%d" % n for n in _zipwrite.THROW_LENGTHS)]
 
 
 @functools.lru_cache(maxsize=None)
@@ -125,6 +162,40 @@ def _gunzip(z, gpu, blob, plain, on_device):
                    members=z.last_gunzip_members())
 
 
+def _zip_read(z, gpu, which, on_device, sel=None):
+    """`expected`: every entry's status is one that tests/_zip.py expects of it; `bytes_equal`: None for an entry with a status."""
+    blob, rows = zip_archive(which)
+    index = z.zip_index(blob)
+    rows = rows if sel is None else [rows[k] for k in sel]
+    if on_device:
+        status, got, _ = _call(z, lambda: z.zip_read_tensor(_dev(blob, gpu, lead=1), index, sel=sel))
+        out, off, out_len, st = got
+        host = out.cpu().numpy()
+        datas = [host[int(o):int(o) + n].tobytes() for o, n in zip(off, out_len)]
+    else:
+        status, res, _ = _call(z, lambda: z.zip_read(blob, index, sel=sel))
+        st = [r.code if isinstance(r, z.ZlibEsError) else 0 for r in res]
+        datas = [b"" if s else r.tobytes() for r, s in zip(res, st)]
+    expected = [s == w or (isinstance(w, tuple) and s in w) for s, (w, _) in zip(st, rows)]
+    return _record(z, status, statuses=st, expected=expected, bytes_equal=[d == p if s == 0 else None for d, s, (_, p) in zip(datas, st, rows)])
+
+
+def _zip_write(z, gpu, which, on_device, flags=0):
+    entries = zipwrite_entries(z, which)
+    if on_device:
+        lens = [len(d) for _, d in entries]
+        arena_ = np.frombuffer(b"".join(d for _, d in entries), dtype=np.uint8).copy()
+        status, got, _ = _call(z, lambda: z.zip_write_tensor(_dev(arena_, gpu, lead=3), np.cumsum([0] + lens)[:-1], lens, [n for n, _ in entries],
+                                                             flags=flags))
+        blob = got[0].cpu().numpy().tobytes()
+    else:
+        status, got, _ = _call(z, lambda: z.zip_write(entries, flags))
+        blob = got[0].tobytes()
+    sha = hashlib.sha256(blob).hexdigest()
+    return _record(z, status, out_len=len(blob), sha256=sha, sha256_expected=sha == hashlib.sha256(_zipwrite.expect(entries)).hexdigest(),
+                   methods=[int(e["method"]) for e in got[1][0]])
+
+
 def _bgzip(z, gpu, n, flags):
     plain = _itext(n, 11)
     status, got, _ = _call(z, lambda: z.bgzip_tensor(_dev(plain, gpu), flags=flags, index=True))
@@ -140,11 +211,13 @@ def _index(z, gpu, flags):
     return _record(z, status, coff=got[0].tolist(), uoff=got[1].tolist(), same_as_host_index=same)
 
 
-def _read(z, gpu, on_device):
+def _read(z, gpu, on_device, damage=None):
     import torch
 
     blob, plain = bgzf_file(70000)
     index = z.bgzf_index(blob)
+    if damage:
+        blob, _ = bgzf_damaged(damage)
     pos, length = 30000, CHUNK + 2000 - 30000  # the middle of member 0 to the middle of member 1
     if on_device:
         out = torch.zeros(3 + length, dtype=torch.uint8, device=gpu)[3:]
@@ -152,6 +225,8 @@ def _read(z, gpu, on_device):
         status, got, _ = _call(z, lambda: z.bgzf_read_tensor(_dev(blob, gpu), index, pos, length, out).cpu().numpy())
     else:
         status, got, _ = _call(z, lambda: z.bgzf_read(blob, index, pos, length))
+    if got is None:
+        return _record(z, status, out_len=None, bytes_equal=None, members=z.last_gunzip_members())
     return _record(z, status, out_len=int(got.size), bytes_equal=got.tobytes() == plain[pos:pos + length], members=z.last_gunzip_members())
 
 
@@ -181,6 +256,15 @@ def run_case(z, gpu, name):
     """A case's record; profiling is on for the call and off again behind it."""
     z.set_profiling(True)
     try:
+        if name.split()[0] in ("zip_read_tensor", "zip_read"):
+            on_device = name.startswith("zip_read_tensor")
+            if name.endswith("stored only"):
+                return _zip_read(z, gpu, "standard", on_device, sel=[k for k, e in enumerate(z.zip_index(zip_archive("standard")[0])[0]) if e["method"] == 0])
+            if name.endswith("one rejected"):
+                return _zip_read(z, gpu, "failures", on_device, sel=[[what for what, _, _ in _zip.failures()[1]].index("local signature damaged")])
+            if name.endswith("count 0"):
+                return _zip_read(z, gpu, "standard", on_device, sel=[])
+            return _zip_read(z, gpu, name.split()[1], on_device)
         if name.endswith("batch"):
             return _checksums(z, gpu, name.split()[0])
         if name.endswith("every length 0"):
@@ -202,6 +286,21 @@ def run_case(z, gpu, name):
             return _read(z, gpu, name == "bgzf_read_tensor")
         if name in ("inflate_batch_tensor checked", "inflate_batch checked"):
             return _checked(z, gpu, name.startswith("inflate_batch_tensor"))
+        if name == "zipwrite_tensor nine pieces":
+            return _zip_write(z, gpu, "nine", True, z.ZES_F_PIECES)
+        if name == "zipwrite_tensor refused only":
+            return _zip_write(z, gpu, "refused", True)
+        if name == "zipwrite nine":
+            return _zip_write(z, gpu, "nine", False)
+        if name == "bgzip_tensor 1 byte":
+            # behind a call whose report is empty: where the encoder refuses a whole group, the report of the call in front
+            # is kept as this call's own (NOTES.md), and the record would depend on what ran before
+            z.crc32_batch_tensor(_dev(_itext(16), gpu), [], [])
+            return _bgzip(z, gpu, 1, 0)
+        if name.startswith("bgzf_read_tensor") and name.endswith("damaged"):
+            return _read(z, gpu, True, damage=name.split()[1])
+        if name == "gunzip_tensor bgzf crc damaged":
+            return _gunzip(z, gpu, *bgzf_damaged("crc"), on_device=True)
         raise KeyError(name)
     finally:
         z.set_profiling(False)

@@ -527,7 +527,9 @@ CHECKSUM_LENGTHS = (1, 65537, 131075)
 def _container_entries(z, oracle):
     out = []
     for name in K.CASES:
-        calls = CONTAINER_CALLS.get(name) or CONTAINER_CALLS[name.split(",")[0]]
+        calls = CONTAINER_CALLS.get(name) or CONTAINER_CALLS.get(name.split(",")[0])
+        if calls is None:  # the ZIP cases (tests/_zip_poison.py, tests/_zipwrite_poison.py hold the ZIP calls' entries) and the damaged files
+            continue
         out.append(Entry("container: " + name, calls + ["zes_last_kernel_times", "zes_set_profiling"], lambda z, gpu, oracle, name=name: K.run_case(z, gpu, name),
                          lambda name=name: golden("container_launches.json")[name], "golden"))
     for n in CHECKSUM_LENGTHS:

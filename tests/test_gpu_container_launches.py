@@ -1,7 +1,7 @@
-"""Which launches the checksum / gzip / BGZF layer makes, pinned: every case of tests/_container_cases.py — status, result,
+"""Which launches the checksum / gzip / BGZF / ZIP layer makes, pinned: every case of tests/_container_cases.py — status, result,
 the launch count of each of the layer's kernels and the names of the inflate and deflate kernels beside them — against
-tests/golden/container_launches.json, which was recorded from the commit in front of the layer's refactor (NOTES.md says
-which).  A driver that launched a gather twice, walked a file on the device that the host had walked already, or ran a
+tests/golden/container_launches.json, which was recorded from the commits in front of the layer's two refactors (NOTES.md
+says which).  A driver that launched a gather twice, walked a file on the device that the host had walked already, or ran a
 checksum kernel over buffers of no bytes computes the same values; here it shows as a count.
 
 Every case runs twice in a row on the same context and the second record must equal the first: the pools a call has grown
@@ -30,7 +30,42 @@ def facts(name, rec):
     """What a case's record must say whatever was recorded: the values (CPython's zlib, the inputs' own bytes), the statuses
     the streams were built for, and the launches the entry points' descriptions state."""
     n = rec["launches"]
+    if name.endswith("damaged"):  # one bit of the 70000-byte BGZF file flipped: the call fails
+        assert rec["status"] != 0 and rec["members"] == 0 and rec["out_len"] is None, rec
+        if name.startswith("gunzip_tensor"):  # the batch gives up, the serial path answers
+            assert rec["status"] == -21 and n.get("k_crc32", 0) >= 1 and "k_crc32_seg" not in n, rec
+        elif name.endswith("body damaged"):  # the job's verdict comes before the output gather and the CRC launch
+            assert "k_crc32_seg" not in n and "k_crc32" not in n, rec
+        else:  # ZES_E_CHECKSUM behind the CRC launch
+            assert rec["status"] == -21 and n.get("k_crc32_seg") == 1, rec
+        return
     assert rec["status"] == 0, rec
+    if name.split()[0] in ("zip_read_tensor", "zip_read"):
+        # every status is the one tests/_zip.py expects of the entry (entry_rule), the bytes are the entries' own
+        assert all(rec["expected"]) and all(b for b, s in zip(rec["bytes_equal"], rec["statuses"]) if s == 0), rec
+        assert all((b is None) == (s != 0) for b, s in zip(rec["bytes_equal"], rec["statuses"])), rec
+        if name.endswith("count 0"):
+            assert n == {} and not rec["others"] and rec["statuses"] == [], rec  # no launch at all
+        elif name.endswith("one rejected"):  # no job at ZES_OK: no decoder, and nothing to gather or to check
+            assert rec["statuses"] == [-22] and n == {"k_zip_stage": 1} and not rec["others"], rec
+        elif name.endswith("stored only"):  # no job: the copy is the stage kernel's
+            assert set(rec["statuses"]) == {0} and n == {"k_zip_stage": 1, "k_crc32_seg": 1} and not rec["others"], rec
+        else:  # one stage launch, one CRC launch that covers the good entries beside the damaged ones
+            assert n.get("k_zip_stage") == 1 and n.get("k_crc32_seg") == 1 and n.get("k_gz_gather", 0) >= 1 and rec["others"], rec
+            good = rec["statuses"].count(0)
+            assert good == 18 == len(rec["statuses"]) if name.endswith("standard") else 6 <= good < len(rec["statuses"]), rec
+        return
+    if name.startswith("zipwrite"):
+        groups = 3 if name.endswith("pieces") else 1
+        assert rec["sha256_expected"] and n.get("k_crc32_seg") == groups and n.get("k_zip_pack") == groups, rec
+        if name.endswith("refused only"):  # no encoder slot: no deflate kernel
+            assert set(n) == {"k_crc32_seg", "k_zip_pack"} and not rec["others"] and set(rec["methods"]) == {0}, rec
+        else:
+            assert rec["others"] and 8 in rec["methods"], rec
+        return
+    if name == "bgzip_tensor 1 byte":  # the only chunk is one the encoder refuses: a stored member and the marker
+        assert rec["bytes_equal"] and rec["out_len"] == 32 + 28 and n == {"k_crc32_seg": 1, "k_bgzf_pack": 1} and not rec["others"], rec
+        return
     if "values_equal" in rec:
         assert rec["values_equal"], rec
     if "bytes_equal" in rec and not isinstance(rec["bytes_equal"], list):

@@ -2693,7 +2693,16 @@ int inflate_one(const uint8_t* d_in, uint64_t in_off, uint64_t c, uint8_t* d_out
 int adler32_locked(const uint8_t* d_in, uint64_t n, uint32_t* adler_out);
 int adler32_batch_locked(const uint8_t* d, const ZesCrcSeg* segs, uint32_t count, uint32_t* adler);
 
-uint32_t get_le32(const uint8_t* p) { return (uint32_t)p[0] | (uint32_t)p[1] << 8 | (uint32_t)p[2] << 16 | (uint32_t)p[3] << 24; }
+uint32_t get_le16(const uint8_t* p) { return (uint32_t)p[0] | (uint32_t)p[1] << 8; }
+uint32_t get_le32(const uint8_t* p) { return get_le16(p) | get_le16(p + 2) << 16; }
+void put_le16(uint8_t* p, uint32_t v) {
+  p[0] = (uint8_t)v;
+  p[1] = (uint8_t)(v >> 8);
+}
+void put_le32(uint8_t* p, uint32_t v) {
+  put_le16(p, v);
+  put_le16(p + 2, v >> 16);
+}
 uint32_t get_be32(const uint8_t* p) { return (uint32_t)p[0] << 24 | (uint32_t)p[1] << 16 | (uint32_t)p[2] << 8 | p[3]; }
 
 // segs[i].len bytes from src + src_off to dst + dst_off for every i, in one launch (k_gz_gather); the table goes through g.gz_tab
@@ -4029,9 +4038,6 @@ int zes_adler32_batch_dev(const uint8_t* d_in, const uint64_t* off, const uint64
 // ---- gzip writer (RFC 1952): fixed header | zes_deflate_raw's bytes | CRC-32, ISIZE ----
 static const uint8_t kGzHeader[10] = {0x1f, 0x8b, 8, 0, 0, 0, 0, 0, 0, 0xff};  // FLG 0, MTIME 0, XFL 0, OS 255
 static uint64_t gzip_bound(uint64_t n) { return deflate_bound(n) - 6 + 18; }
-static void put_le32(uint8_t* p, uint32_t v) {
-  for (int k = 0; k < 4; k++) p[k] = (uint8_t)(v >> (8 * k));
-}
 
 // the body into g.st_out + 2 (as zes_deflate_raw does); the input's CRC-32 runs on the second stream beside the deflate
 // kernels, as the Adler-32 pass does
@@ -4094,6 +4100,47 @@ int zes_gzip(const uint8_t* in, uint64_t n, uint8_t* out, uint64_t cap, uint64_t
   return ZES_OK;
 }
 
+// The end of a container call's device work (zes_bgzip*, zes_bgzf_read*, zes_zip_read*, zes_zipwrite*): with `clear`, a call
+// that failed leaves no HIP error behind for the next one; the call's times are collected either way.
+static int call_done(int rc, bool clear) {
+  if (rc && clear) (void)hipGetLastError();
+  collect_times();
+  return rc;
+}
+
+// ---- A group of buffers encoded for a container: the step that bgzip_core (members) and zipwrite_groups (entries) share ----
+// The caller lays the group out: buffer k is d_in[in_off[k], + in_len[k]) and has the 16-byte aligned slot [o_off[k], + o_cap[k])
+// of g.gz_bodies, o_cap[k] == 0 for a buffer that the encoder is spared (the caller's rule).  encode() gives every buffer its
+// CRC-32 by one segmented launch and encodes the group by one deflate_batch_core call (none when the slots take no bytes: no
+// times of its own to keep); raw[k] is then the length of buffer k's raw stream, which starts at o_off[k] + 2 (78 9C in
+// front, the Adler-32 behind), and 0 for a spared buffer.
+// A result beyond the caller's capacity, by room(): every group is still encoded (the size needed is the answer), and from
+// the first group that does not fit whole nothing more is written.
+struct EncGroup {
+  std::vector<uint64_t> o_off, o_cap, o_len, raw;
+  std::vector<int32_t> status;
+  std::vector<ZesCrcSeg> csegs;
+  std::vector<uint32_t> crc;
+  bool fits = true;
+  explicit EncGroup(size_t most) : o_off(most), o_cap(most), o_len(most), raw(most), status(most), csegs(most), crc(most) {}
+  int encode(const uint8_t* d_in, const uint64_t* in_off, const uint64_t* in_len, uint32_t cnt, uint64_t slots) {
+    int rc;
+    for (uint32_t k = 0; k < cnt; k++) csegs[k] = ZesCrcSeg{in_off[k], in_len[k]};
+    if ((rc = ensure(g.gz_bodies, slots + 64))) return rc;
+    if ((rc = crc32_batch_locked(d_in, csegs.data(), cnt, crc.data()))) return rc;
+    if (slots) {
+      if ((rc = deflate_batch_core(d_in, in_off, in_len, (uint8_t*)g.gz_bodies.p, o_off.data(), o_cap.data(), o_len.data(), status.data(), cnt))) return rc;
+      keep_times();
+    }
+    for (uint32_t k = 0; k < cnt; k++) {
+      if (o_cap[k] && (status[k] != ZES_OK || o_len[k] < 6)) return status[k] ? status[k] : ZES_E_DEVICE;
+      raw[k] = o_cap[k] ? o_len[k] - 6 : 0;  // without 78 9C and the Adler-32
+    }
+    return ZES_OK;
+  }
+  bool room(uint64_t total, uint64_t cap, const uint8_t* d_out) { return fits = fits && total <= cap && d_out != nullptr; }
+};
+
 // ---- BGZF writer: the input in chunks of ZES_BGZF_CHUNK bytes, a gzip member each, and the end-of-file marker ----
 static const uint8_t kBgzfEof[28] = {0x1f, 0x8b, 8, 4, 0, 0, 0, 0, 0, 0xff, 6, 0, 'B', 'C', 2, 0, 0x1b, 0, 3, 0, 0, 0, 0, 0, 0, 0, 0, 0};
 constexpr uint32_t BGZF_GROUP = 1024;       // members encoded at once: a block's scratch each, what zes_deflate_dev pools for 128 MiB
@@ -4108,12 +4155,11 @@ static uint64_t bgzip_bound(uint64_t n) {
   return n / ZES_BGZF_CHUNK * BGZF_MEMBER_MAX + (tail ? tail + ZES_BGZF_HLEN + 5 + 8 : 0) + sizeof kBgzfEof;
 }
 
-// The members of d_in[0, n) and the marker into d_out[0, cap), group by group: the group's chunks are checksummed by one
-// segmented CRC-32 launch and encoded as independent buffers into 16-byte aligned slots of g.gz_bodies (a chunk of one byte,
-// which the encoder refuses, is left out), their sizes come back, the host chooses stream or stored block per member and
-// k_bgzf_pack puts the members in their places.  The marker is the last launch's last record.  A result beyond cap:
-// every group is still encoded (the size needed is the answer), and from the first group that does not fit whole no
-// member is written.  member_off: null, or where every member starts, the marker's last.
+// The members of d_in[0, n) and the marker into d_out[0, cap), group by group (EncGroup): every chunk has a slot of its own
+// size class, a chunk of one byte, which the encoder refuses, is spared, and the call is made whenever the group has members.
+// The sizes come back, the host chooses stream or stored block per member and k_bgzf_pack puts the members in their places.
+// The marker is the last launch's last record.  A result beyond cap: EncGroup's rule.  member_off: null, or where every
+// member starts, the marker's last.
 static int bgzip_core(const uint8_t* d_in, uint64_t n, uint8_t* d_out, uint64_t cap, uint64_t* out_len, uint64_t* member_off, uint32_t flags) {
   int rc;
   g.carry.clear();
@@ -4122,40 +4168,28 @@ static int bgzip_core(const uint8_t* d_in, uint64_t n, uint8_t* d_out, uint64_t 
   const uint64_t slot = (deflate_bound(ZES_BGZF_CHUNK) + 15) & ~(uint64_t)15;
   std::vector<ZesBgzfRec> recs((size_t)nm + 1);  // (of the whole call: uploads read it until the last synchronisation)
   const size_t gmax = (size_t)std::min(group, nm);
-  std::vector<uint64_t> in_off(gmax), in_len(gmax), o_off(gmax), o_cap(gmax), o_len(gmax);
-  std::vector<int32_t> status(gmax);
-  std::vector<ZesCrcSeg> csegs(gmax);
-  std::vector<uint32_t> crc(gmax);
+  std::vector<uint64_t> in_off(gmax), in_len(gmax);
+  EncGroup eg(gmax);
   uint64_t total = 0;
-  bool fits = true;
   for (uint64_t m0 = 0;; m0 += group) {
     const uint32_t cnt = (uint32_t)std::min(group, nm - m0);
     const bool last = m0 + cnt == nm;
-    if (cnt) {
-      for (uint32_t k = 0; k < cnt; k++) {
-        in_off[k] = (m0 + k) * ZES_BGZF_CHUNK;
-        in_len[k] = std::min<uint64_t>(ZES_BGZF_CHUNK, n - in_off[k]);
-        o_off[k] = k * slot;
-        o_cap[k] = slot;
-        csegs[k] = ZesCrcSeg{in_off[k], in_len[k]};
-      }
-      if ((rc = ensure(g.gz_bodies, (size_t)cnt * slot))) return rc;
-      if ((rc = crc32_batch_locked(d_in, csegs.data(), cnt, crc.data()))) return rc;
-      if ((rc = deflate_batch_core(d_in, in_off.data(), in_len.data(), (uint8_t*)g.gz_bodies.p, o_off.data(), o_cap.data(), o_len.data(), status.data(), cnt)))
-        return rc;
-      keep_times();
+    for (uint32_t k = 0; k < cnt; k++) {
+      in_off[k] = (m0 + k) * ZES_BGZF_CHUNK;
+      in_len[k] = std::min<uint64_t>(ZES_BGZF_CHUNK, n - in_off[k]);
+      eg.o_off[k] = k * slot;
+      eg.o_cap[k] = in_len[k] == 1 ? 0 : slot;
     }
+    if (cnt && (rc = eg.encode(d_in, in_off.data(), in_len.data(), cnt, cnt * slot))) return rc;
     for (uint32_t k = 0; k < cnt; k++) {
       const uint32_t len = (uint32_t)in_len[k];
-      if (len > 1 && (status[k] != ZES_OK || o_len[k] < 6)) return status[k] ? status[k] : ZES_E_DEVICE;
-      const uint64_t raw = len > 1 ? o_len[k] - 6 : 0;  // without 78 9C and the Adler-32
-      const bool stored = len == 1 || raw > (uint64_t)len + 5;
+      const bool stored = len == 1 || eg.raw[k] > (uint64_t)len + 5;
       ZesBgzfRec& r = recs[(size_t)(m0 + k)];
-      r.src_off = stored ? in_off[k] : o_off[k] + 2;
+      r.src_off = stored ? in_off[k] : eg.o_off[k] + 2;
       r.dst_off = total;
-      r.body_len = stored ? len + 5 : (uint32_t)raw;
+      r.body_len = stored ? len + 5 : (uint32_t)eg.raw[k];
       r.len = len;
-      r.crc = crc[k];
+      r.crc = eg.crc[k];
       r.kind = stored ? ZES_BGZF_STORED : ZES_BGZF_STREAM;
       total += ZES_BGZF_HLEN + r.body_len + 8;
     }
@@ -4164,8 +4198,7 @@ static int bgzip_core(const uint8_t* d_in, uint64_t n, uint8_t* d_out, uint64_t 
       total += sizeof kBgzfEof;
     }
     const uint32_t nrec = cnt + (last ? 1u : 0u);
-    fits = fits && total <= cap && d_out != nullptr;
-    if (fits) {
+    if (eg.room(total, cap, d_out)) {
       if ((rc = ensure(g.gz_tab, sizeof(ZesBgzfRec) * (size_t)nrec))) return rc;
       HIPCHK(hipMemcpyAsync(g.gz_tab.p, &recs[(size_t)m0], sizeof(ZesBgzfRec) * (size_t)nrec, hipMemcpyHostToDevice, g.stream));
       Timed t("k_bgzf_pack");
@@ -4179,7 +4212,7 @@ static int bgzip_core(const uint8_t* d_in, uint64_t n, uint8_t* d_out, uint64_t 
   if (member_off)
     for (uint64_t k = 0; k <= nm; k++) member_off[k] = recs[(size_t)k].dst_off;
   *out_len = total;
-  return fits ? ZES_OK : ZES_E_NOSPACE;
+  return eg.fits ? ZES_OK : ZES_E_NOSPACE;
 }
 
 int zes_bgzip_members(uint64_t n, uint64_t* members) {
@@ -4199,9 +4232,7 @@ int zes_bgzip_dev(const uint8_t* d_in, uint64_t n, uint8_t* d_out, uint64_t cap,
   if (!out_len || (n && (!d_in || !d_out)) || (!d_out && cap) || (flags & ~ZES_F_PIECES) || n > BGZF_N_MAX) return ZES_E_ARG;
   *out_len = 0;
   LOCK_READY();
-  rc = bgzip_core(d_in, n, d_out, cap, out_len, member_off, flags);
-  collect_times();
-  return rc;
+  return call_done(bgzip_core(d_in, n, d_out, cap, out_len, member_off, flags), false);
 }
 
 int zes_bgzip(const uint8_t* in, uint64_t n, uint8_t* out, uint64_t cap, uint64_t* out_len, uint64_t* member_off, uint32_t flags) {
@@ -4220,9 +4251,7 @@ int zes_bgzip(const uint8_t* in, uint64_t n, uint8_t* out, uint64_t cap, uint64_
   const uint64_t bound = bgzip_bound(n);
   if ((rc = ensure(g.gz_acc, bound + 64))) return rc;
   uint64_t total = 0;
-  rc = bgzip_core((const uint8_t*)g.gz_in.p, n, (uint8_t*)g.gz_acc.p, bound, &total, member_off, flags);
-  collect_times();
-  if (rc) return rc;
+  if ((rc = call_done(bgzip_core((const uint8_t*)g.gz_in.p, n, (uint8_t*)g.gz_acc.p, bound, &total, member_off, flags), false))) return rc;
   *out_len = total;
   if (total > cap) return ZES_E_NOSPACE;
   return download(out, (const uint8_t*)g.gz_acc.p, total);
@@ -4402,13 +4431,58 @@ struct GzPart {
   uint32_t skip, take;
 };
 
-// What gz_decode_batch and zip_read_core share, stated once.  A body of `len` bytes stands in gz_bodies behind a 78 9C, in a slot
-// of gz_slot_in(len) bytes (the decoders read whole 16-byte groups, and some way past a stream's end); an output of m bytes
-// that cannot be decoded in place gets gz_slot_out(m) bytes of gz_outs, of which the job may write gz_slot_cap(m).
+// ---- DEFLATE bodies as one batch: the plan of gz_decode_batch (gzip members) and zip_read_core (ZIP entries), stated once ----
+// body_plan gives every part its places, the caller puts the bodies there (the staging is what differs: k_gz_gather for
+// members, k_zip_stage for entries, which also judges the local headers), body_run decodes and checks them.
+// A body of `len` bytes stands in gz_bodies behind a 78 9C, in a slot of gz_slot_in(len) bytes (the decoders read whole 16-byte
+// groups, and some way past a stream's end); an output of m bytes that cannot be decoded in place gets gz_slot_out(m) bytes of
+// gz_outs, of which the job may write gz_slot_cap(m).
 static uint64_t gz_up16(uint64_t v) { return (v + 15) & ~15ull; }
 static uint64_t gz_slot_in(uint64_t len) { return gz_up16(2 + len) + 64; }
 static uint64_t gz_slot_cap(uint64_t m) { return std::max<uint64_t>(gz_up16(m), 16); }
 static uint64_t gz_slot_out(uint64_t m) { return gz_slot_cap(m) + 16; }
+
+// One part of a batch: what its container says, and the part of its output that is wanted: bytes [skip, skip + take) of it go
+// to dst + dst_off (a whole part: skip 0, take = isize)
+struct BodyPart {
+  uint64_t len;         // the body's bytes
+  uint32_t isize, crc;  // the output's length and CRC-32
+  uint64_t dst_off;
+  uint32_t skip, take;
+  bool deflate;         // a DEFLATE body; else the staging puts the bytes in place itself (a stored entry)
+  int status;           // so far: a part that is not at ZES_OK is neither decoded nor checked
+  // body_plan's: the slot in gz_bodies, and either decoded in place (direct) or into a slot of gz_outs
+  uint64_t islot = 0, oslot = 0;
+  bool direct = false;
+  bool whole() const { return skip == 0 && take == isize; }
+};
+
+// A part is decoded in place when the 16-byte groups the decoders write stay inside its own part of dst: whole, at a 16-byte
+// boundary, a multiple of 16 long.  The others get a slot of their own (the parts run side by side: a group that reaches into
+// a neighbour's range would race with it).  exact: no byte of dst outside the parts is written; else the last part with
+// output may also be decoded in place up to the next 16-byte boundary below dst_cap.
+static int body_plan(std::vector<BodyPart>& ps, uint8_t* dst, uint64_t dst_cap, bool exact) {
+  int rc;
+  const BodyPart* last_out = nullptr;
+  for (const BodyPart& p : ps)
+    if (!exact && p.isize) last_out = &p;
+  uint64_t ipos = 0, opos = 0;
+  for (BodyPart& p : ps) {
+    if (!p.deflate) continue;
+    const uint64_t m = p.isize;
+    p.islot = ipos;
+    ipos += gz_slot_in(p.len);
+    p.direct = dst && m && p.whole() && ((uintptr_t)(dst + p.dst_off) & 15u) == 0 &&
+               ((m & 15u) == 0 || (&p == last_out && gz_up16(p.dst_off + m) <= dst_cap));
+    if (!p.direct) {
+      p.oslot = opos;
+      opos += gz_slot_out(m);
+    }
+  }
+  if ((rc = ensure(g.gz_bodies, ipos + 64)) || (rc = ensure(g.gz_outs, opos + 64))) return rc;
+  return ZES_OK;
+}
+
 // A body's job behind inflate_jobs (want_end set) against what its container says: the body's inflate status when it does not
 // decode; ZES_E_CHECKSUM when the output is not `want` bytes long (one that outgrew its capacity included) or the stream does
 // not end in the last of the body's `len` bytes; else ZES_OK (the CRC-32 is the caller's next step).
@@ -4418,86 +4492,78 @@ static int gz_job_verdict(const InfJob& j, uint64_t want, uint64_t len) {
   return ZES_OK;
 }
 
-// Members as one batch (gunzip_parallel: a whole file; bgzf_read_core: the members a range touches): one gather of the
-// bodies behind a 78 9C each, one inflate_jobs call, one gather of the outputs that could not be decoded in place, one
-// segmented CRC-32 launch.  Every member is decoded whole and must check out: *verdict is ZES_OK when all do, else what
-// the first member in file order that does not is guilty of — its body's inflate status, or ZES_E_CHECKSUM: an output
-// that is not ISIZE bytes long (one that would outgrow its slot included), a stream that does not end in the last byte in
-// front of the trailer, a CRC-32 mismatch — or the status of a scratch buffer that could not grow.  With a verdict the
-// result's memory may have been written to.
-// A member is decoded in place when the 16-byte groups the decoders write stay inside its own part of dst; the others get a
-// slot of their own (the members run side by side: a group that reaches into a neighbour's range would race with it).
-// exact: no byte of dst outside the parts is written; else the last member with output may be decoded in place up to the
-// next 16-byte boundary below dst_cap.  stamps: the time in front of and behind inflate_jobs.
-static int gz_decode_batch(const uint8_t* d_src, const std::vector<GzPart>& ps, uint8_t* dst, uint64_t dst_cap, bool exact, uint32_t flags, int* verdict,
-                           std::chrono::steady_clock::time_point* stamps) {
-  *verdict = ZES_OK;
+// The staged parts decoded and checked: one inflate_jobs call for the DEFLATE bodies at ZES_OK (none when there is no such
+// body), one gather of the outputs that were not decoded in place, one segmented CRC-32 launch with a segment per part (of
+// no bytes for a part with a status).  A part's status becomes what it is guilty of: its body's inflate status, or
+// ZES_E_CHECKSUM — an output that is not isize bytes long (one that would outgrow its slot included), a stream that does not
+// end in the body's last byte, a CRC-32 mismatch.  stop: the first part in order with a status ends the call, and that status
+// is returned (a job's verdict comes before the gather and the CRC launch); else every part gets its own and the call goes
+// on.  With a status a part's memory may have been written to.  stamps: null, or the time in front of and behind inflate_jobs.
+static int body_run(std::vector<BodyPart>& ps, uint8_t* dst, uint32_t flags, bool stop, std::chrono::steady_clock::time_point* stamps) {
   int rc;
   const uint32_t n = (uint32_t)ps.size();
-  int64_t last_out = -1;  // the last member with output
-  if (!exact)
-    for (uint32_t k = 0; k < n; k++)
-      if (ps[k].m.isize) last_out = k;
-  auto up16 = gz_up16;
-  auto whole = [&](uint32_t k) { return ps[k].skip == 0 && ps[k].take == ps[k].m.isize; };
-  std::vector<char> direct(n);
-  std::vector<uint64_t> islot(n), oslot(n);
-  std::vector<ZesGzSeg> segs(n);
-  uint64_t ipos = 0, opos = 0;
-  for (uint32_t k = 0; k < n; k++) {
-    const uint64_t dlen = ps[k].m.size - ps[k].m.hlen - 8, m = ps[k].m.isize;
-    islot[k] = ipos;
-    ipos += gz_slot_in(dlen);
-    segs[k] = ZesGzSeg{ps[k].pos + ps[k].m.hlen, islot[k] + 2, dlen, 1u, 0u};
-    direct[k] = dst && m && whole(k) && ((uintptr_t)(dst + ps[k].dst_off) & 15u) == 0 &&
-                ((m & 15u) == 0 || ((int64_t)k == last_out && up16(ps[k].dst_off + m) <= dst_cap));
-    if (!direct[k]) {
-      oslot[k] = opos;
-      opos += gz_slot_out(m);
-    }
-  }
-  if ((rc = ensure(g.gz_bodies, ipos + 64)) || (rc = ensure(g.gz_outs, opos + 64))) {
-    *verdict = rc;
-    return ZES_OK;
-  }
-  if ((rc = gz_gather(d_src, (uint8_t*)g.gz_bodies.p, segs))) return rc;
   // one base for both kinds of destination (inflate_jobs takes one pointer and an offset per job): the lower of the two
   uint8_t* outs = (uint8_t*)g.gz_outs.p;
   uint8_t* base = dst && dst < outs ? dst : outs;
-  std::vector<InfJob> jobs(n);
+  std::vector<InfJob> jobs;
+  std::vector<uint32_t> jp;  // job -> part
+  bool any = false;
   for (uint32_t k = 0; k < n; k++) {
-    const uint64_t dlen = ps[k].m.size - ps[k].m.hlen - 8, m = ps[k].m.isize;
-    uint8_t* to = direct[k] ? dst + ps[k].dst_off : outs + oslot[k];
-    jobs[k] = InfJob{islot[k], 2 + dlen, (uint64_t)(to - base), direct[k] ? m : gz_slot_cap(m), 0, ZES_OK, 0};
-    jobs[k].want_end = true;
+    const BodyPart& p = ps[k];
+    if (!p.deflate) continue;
+    uint8_t* to = p.direct ? dst + p.dst_off : outs + p.oslot;
+    InfJob j{p.islot, 2 + p.len, (uint64_t)(to - base), p.direct ? p.isize : gz_slot_cap(p.isize), 0, p.status, 0};
+    j.want_end = true;
+    jobs.push_back(j);
+    jp.push_back(k);
+    any = any || p.status == ZES_OK;
   }
-  const std::vector<uint8_t> firsts(n, 0x78);
-  if (stamps) stamps[0] = std::chrono::steady_clock::now();
-  if ((rc = inflate_jobs((const uint8_t*)g.gz_bodies.p, base, jobs, firsts.data(), flags & ~(ZES_F_CHECK_ADLER | ZES_F_GZIP_SERIAL)))) return rc;
-  keep_times();
-  if (stamps) stamps[1] = std::chrono::steady_clock::now();
-  for (uint32_t k = 0; k < n; k++) {
-    const uint64_t dlen = ps[k].m.size - ps[k].m.hlen - 8;
-    if ((*verdict = gz_job_verdict(jobs[k], ps[k].m.isize, dlen))) return ZES_OK;
+  if (any) {  // (inflate_jobs leaves a job with a status alone)
+    const std::vector<uint8_t> firsts(jobs.size(), 0x78);
+    if (stamps) stamps[0] = std::chrono::steady_clock::now();
+    if ((rc = inflate_jobs((const uint8_t*)g.gz_bodies.p, base, jobs, firsts.data(), flags))) return rc;
+    keep_times();
+    if (stamps) stamps[1] = std::chrono::steady_clock::now();
   }
-  // a whole member's output is checked where it ends up, a trimmed one's in its slot
-  segs.clear();
+  for (size_t i = 0; i < jobs.size(); i++) {
+    BodyPart& p = ps[jp[i]];
+    if (p.status == ZES_OK) p.status = gz_job_verdict(jobs[i], p.isize, p.len);
+    if (p.status && stop) return p.status;
+  }
+  // a whole part's output is checked where it ends up, a trimmed one's in its slot, over all its bytes
+  std::vector<ZesGzSeg> segs;
   std::vector<ZesCrcSeg> csegs(n);
-  const uint8_t* cbase = base;
   for (uint32_t k = 0; k < n; k++) {
-    if (!direct[k] && ps[k].take) segs.push_back(ZesGzSeg{oslot[k] + ps[k].skip, ps[k].dst_off, ps[k].take, 0u, 0u});
-    const uint8_t* at = whole(k) ? dst + ps[k].dst_off : outs + oslot[k];
-    csegs[k] = ZesCrcSeg{ps[k].m.isize ? (uint64_t)(at - cbase) : 0, ps[k].m.isize};
+    const BodyPart& p = ps[k];
+    const bool ok = p.status == ZES_OK && p.isize;
+    if (ok && p.deflate && !p.direct && p.take) segs.push_back(ZesGzSeg{p.oslot + p.skip, p.dst_off, p.take, 0u, 0u});
+    csegs[k] = ok ? ZesCrcSeg{(uint64_t)((p.whole() ? dst + p.dst_off : outs + p.oslot) - base), p.isize} : ZesCrcSeg{0, 0};
   }
   if ((rc = gz_gather(outs, dst, segs))) return rc;
   std::vector<uint32_t> crc(n);
-  if ((rc = crc32_batch_locked(cbase, csegs.data(), n, crc.data()))) return rc;
+  if ((rc = crc32_batch_locked(base, csegs.data(), n, crc.data()))) return rc;
   for (uint32_t k = 0; k < n; k++)
-    if (crc[k] != ps[k].m.crc) {
-      *verdict = ZES_E_CHECKSUM;
-      return ZES_OK;
+    if (ps[k].status == ZES_OK && crc[k] != ps[k].crc) {
+      ps[k].status = ZES_E_CHECKSUM;
+      if (stop) return ZES_E_CHECKSUM;
     }
   return ZES_OK;
+}
+
+// Members as one batch (gunzip_parallel: a whole file; bgzf_read_core: the members a range touches): one gather of the
+// bodies into body_plan's slots, then body_run.  Every member is decoded whole and must check out: ZES_OK when all do, else
+// what the first member in file order that does not is guilty of (body_run, stop), or the status of a scratch buffer that
+// could not grow.  exact, stamps: body_plan's and body_run's.
+static int gz_decode_batch(const uint8_t* d_src, const std::vector<GzPart>& ps, uint8_t* dst, uint64_t dst_cap, bool exact, uint32_t flags,
+                           std::chrono::steady_clock::time_point* stamps) {
+  int rc;
+  std::vector<BodyPart> bs;
+  for (const GzPart& p : ps) bs.push_back(BodyPart{p.m.size - p.m.hlen - 8, p.m.isize, p.m.crc, p.dst_off, p.skip, p.take, true, ZES_OK});
+  if ((rc = body_plan(bs, dst, dst_cap, exact))) return rc;
+  std::vector<ZesGzSeg> segs;
+  for (size_t k = 0; k < ps.size(); k++) segs.push_back(ZesGzSeg{ps[k].pos + ps[k].m.hlen, bs[k].islot + 2, bs[k].len, 1u, 0u});
+  if ((rc = gz_gather(d_src, (uint8_t*)g.gz_bodies.p, segs))) return rc;
+  return body_run(bs, dst, flags & ~(ZES_F_CHECK_ADLER | ZES_F_GZIP_SERIAL), true, stamps);
 }
 
 // All members of a file as one batch (gz_decode_batch).  *done only when every member checks out; in every other case
@@ -4526,10 +4592,8 @@ static int gunzip_parallel(GzSrc& S, bool dev, uint8_t* d_dst, uint64_t cap, uin
   }
   if (dev && total > cap) return ZES_OK;
   if (!dev && ensure(g.gz_acc, total + 64)) return ZES_OK;
-  int verdict = ZES_OK;
   std::chrono::steady_clock::time_point st[2];
-  if ((rc = gz_decode_batch(S.d, ps, dev ? d_dst : (uint8_t*)g.gz_acc.p, dev ? cap : g.gz_acc.cap, false, flags, &verdict, st))) return rc;
-  if (verdict) return ZES_OK;
+  if ((rc = gz_decode_batch(S.d, ps, dev ? d_dst : (uint8_t*)g.gz_acc.p, dev ? cap : g.gz_acc.cap, false, flags, st))) return rc;
   if (dbg)
     fprintf(stderr, "zes gunzip, %u members as one batch: walk %.3f ms, plan + gather %.3f, inflate_jobs %.3f, gather + CRC-32 %.3f\n", n, ms(t0, t1),
             ms(t1, st[0]), ms(st[0], st[1]), ms(st[1], now()));
@@ -4781,9 +4845,7 @@ static int bgzf_read_core(const uint8_t* h, const uint8_t* d_src, uint64_t src_a
     const uint64_t lo = std::max(pos, u0), hi = std::min(pos + n, u1);
     ps[i] = GzPart{at - src_at, m, lo - pos, (uint32_t)(lo - u0), (uint32_t)(hi - lo)};
   }
-  int verdict = ZES_OK;
-  if ((rc = gz_decode_batch(d_src, ps, dst, n, true, flags, &verdict, nullptr))) return rc;
-  if (verdict) return verdict;
+  if ((rc = gz_decode_batch(d_src, ps, dst, n, true, flags, nullptr))) return rc;
   g.last_members = (int)nt;
   return ZES_OK;
 }
@@ -4795,7 +4857,8 @@ static int bgzf_read_args(const uint8_t* in, const uint64_t* coff, const uint64_
   return ZES_OK;
 }
 
-// a call that decodes nothing: zes_last_gunzip_members reports 0 after it
+// a call that decodes nothing: zes_last_gunzip_members reports 0 after it.  (Not one helper with zip_read_none: this one is
+// also the way out of a call whose plan failed, and leaves the times alone as every call does that ends in its checks.)
 static void bgzf_read_none() {
   std::lock_guard<std::mutex> lk(g_mu);
   g.last_members = 0;
@@ -4812,10 +4875,7 @@ int zes_bgzf_read_dev(const uint8_t* d_in, uint64_t c, const uint64_t* coff, con
   }
   LOCK_READY();
   g.last_members = 0;
-  rc = bgzf_read_core(nullptr, d_in, 0, c, coff, uoff, pos, *out_len, touched, d_out, flags);
-  if (rc) (void)hipGetLastError();
-  collect_times();
-  return rc;
+  return call_done(bgzf_read_core(nullptr, d_in, 0, c, coff, uoff, pos, *out_len, touched, d_out, flags), true);
 }
 
 int zes_bgzf_read(const uint8_t* in, uint64_t c, const uint64_t* coff, const uint64_t* uoff, uint64_t members, uint64_t pos, uint64_t len, uint8_t* out,
@@ -4833,16 +4893,11 @@ int zes_bgzf_read(const uint8_t* in, uint64_t c, const uint64_t* coff, const uin
   const uint64_t lo = coff[touched.front()], hi = coff[touched.back() + 1], n = *out_len;
   if ((rc = stage_in(g.gz_in, in + lo, hi - lo))) return rc;
   if ((rc = ensure(g.gz_acc, n + 64))) return rc;
-  rc = bgzf_read_core(in, (const uint8_t*)g.gz_in.p, lo, c, coff, uoff, pos, n, touched, (uint8_t*)g.gz_acc.p, flags);
-  if (rc) (void)hipGetLastError();
-  collect_times();
-  if (rc) return rc;
+  if ((rc = call_done(bgzf_read_core(in, (const uint8_t*)g.gz_in.p, lo, c, coff, uoff, pos, n, touched, (uint8_t*)g.gz_acc.p, flags), true))) return rc;
   return download(out, (const uint8_t*)g.gz_acc.p, n);
 }
 
 // ---- ZIP archives (include/zes.h: "ZIP archives"): the entry index and batch extraction through it ----
-static uint32_t get_le16(const uint8_t* p) { return (uint32_t)p[0] | (uint32_t)p[1] << 8; }
-
 constexpr uint64_t ZIP_END = 22, ZIP_TAIL = ZIP_END + 65535;  // the end record without its comment; with the longest one
 
 // The index rule, once, for both forms: fetch(pos, len) answers with the file's bytes [pos, pos + len) (null: they could not
@@ -4982,7 +5037,8 @@ static int zip_read_args(const uint8_t* in, uint64_t c, const zes_zip_entry* ent
   return ZES_OK;
 }
 
-// a call with nothing to extract: no device work; the times and the tier of the call before do not stay
+// a call with nothing to extract: no device work; the times and the tier of the call before do not stay (a successful call
+// that launches nothing reports no launch; bgzf_read_none says why the two differ)
 static void zip_read_none() {
   std::lock_guard<std::mutex> lk(g_mu);
   g.last_tier = 0;
@@ -4996,27 +5052,29 @@ struct ZipPart {
   uint64_t hdr_at, name_at, limit, dst_off;
 };
 
-// The entries of ps whose status[k] is ZES_OK on entry (zip_entry_alone has passed them), as one batch: k_zip_stage judges the
-// local headers and puts the bodies in place, one read-back brings the verdicts down, the DEFLATE bodies go through one
-// inflate_jobs call, one gather moves the outputs that could not be decoded in place, one segmented CRC-32 launch checks all
-// results (gz_decode_batch's plan, with a verdict per entry instead of one for the batch, and its `exact` mode: no byte of dst
-// outside the parts is written).  status[k] becomes the entry's status (include/zes.h, steps 2 to 4).
+// The entries of ps whose status[k] is ZES_OK on entry (zip_entry_alone has passed them), as one batch on the plan of the gzip
+// members (body_plan, body_run): every entry is whole and the mode is `exact`, no byte of dst outside the parts is written.
+// The staging is k_zip_stage, which judges the local headers and puts the DEFLATE bodies into their slots and the stored
+// entries in place; one read-back brings its verdicts down and they become the parts' statuses.  body_run goes on per
+// entry: status[k] becomes the entry's status (include/zes.h, steps 2 to 4).
 static int zip_read_core(const uint8_t* d_src, const std::vector<ZipPart>& ps, uint8_t* dst, int32_t* status, uint32_t flags) {
   int rc;
   g.last_tier = 0;
   std::vector<uint32_t> st;  // the staged entries
+  std::vector<BodyPart> bs;
   for (uint32_t k = 0; k < ps.size(); k++)
-    if (status[k] == ZES_OK) st.push_back(k);
+    if (status[k] == ZES_OK) {
+      st.push_back(k);
+      bs.push_back(BodyPart{ps[k].z.csize, ps[k].z.usize, ps[k].z.crc, ps[k].dst_off, 0u, ps[k].z.usize, ps[k].z.method == 8, ZES_OK});
+    }
   const uint32_t n = (uint32_t)st.size();
   if (!n) return ZES_OK;
-  std::vector<char> direct(n, 0);
-  std::vector<uint64_t> islot(n, 0), oslot(n, 0);
+  if ((rc = body_plan(bs, dst, 0, true))) return rc;
   std::vector<ZesZipRec> recs(n);
-  uint64_t ipos = 0, opos = 0, longest = 0;
+  uint64_t longest = 0;
   for (uint32_t q = 0; q < n; q++) {
     const ZipPart& p = ps[st[q]];
-    const uint64_t m = p.z.usize;
-    ZesZipRec r;
+    ZesZipRec& r = recs[q];
     memset(&r, 0, sizeof r);
     r.hdr_at = p.hdr_at;
     r.name_at = p.name_at;
@@ -5025,24 +5083,11 @@ static int zip_read_core(const uint8_t* d_src, const std::vector<ZipPart>& ps, u
     r.name_len = p.z.name_len;
     r.method = p.z.method;
     r.flag0 = p.z.flags & 1u;
+    r.dst_off = bs[q].deflate ? bs[q].islot + 2 : p.dst_off;
     longest = std::max<uint64_t>(longest, p.z.csize);
-    if (p.z.method == 8) {
-      islot[q] = ipos;
-      ipos += gz_slot_in(p.z.csize);
-      r.dst_off = islot[q] + 2;
-      direct[q] = dst && m && ((uintptr_t)(dst + p.dst_off) & 15u) == 0 && (m & 15u) == 0;
-      if (!direct[q]) {
-        oslot[q] = opos;
-        opos += gz_slot_out(m);
-      }
-    } else {
-      r.dst_off = p.dst_off;
-    }
-    recs[q] = r;
   }
   const size_t o_verd = sizeof(ZesZipRec) * (size_t)n;
-  if ((rc = ensure(g.gz_bodies, ipos + 64)) || (rc = ensure(g.gz_outs, opos + 64)) || (rc = ensure(g.gz_tab, o_verd + sizeof(ZesZipVerdict) * (size_t)n)))
-    return rc;
+  if ((rc = ensure(g.gz_tab, o_verd + sizeof(ZesZipVerdict) * (size_t)n))) return rc;
   ZesZipVerdict* d_verd = (ZesZipVerdict*)((uint8_t*)g.gz_tab.p + o_verd);
   HIPCHK(hipMemcpyAsync(g.gz_tab.p, recs.data(), o_verd, hipMemcpyHostToDevice, g.stream));
   {
@@ -5055,50 +5100,10 @@ static int zip_read_core(const uint8_t* d_src, const std::vector<ZipPart>& ps, u
   std::vector<ZesZipVerdict> verd(n);
   HIPCHK(hipMemcpyAsync(verd.data(), d_verd, sizeof(ZesZipVerdict) * (size_t)n, hipMemcpyDeviceToHost, g.stream));
   HIPCHK(hipStreamSynchronize(g.stream));
-  // one base for both kinds of destination (inflate_jobs takes one pointer and an offset per job): the lower of the two
-  uint8_t* outs = (uint8_t*)g.gz_outs.p;
-  uint8_t* base = dst && dst < outs ? dst : outs;
-  std::vector<InfJob> jobs;
-  std::vector<uint32_t> jq;  // job -> staged entry
-  for (uint32_t q = 0; q < n; q++) {
-    const ZipPart& p = ps[st[q]];
-    status[st[q]] = verd[q].status;
-    if (p.z.method != 8) continue;
-    const uint64_t m = p.z.usize;
-    uint8_t* to = direct[q] ? dst + p.dst_off : outs + oslot[q];
-    InfJob j{islot[q], 2 + (uint64_t)p.z.csize, (uint64_t)(to - base), direct[q] ? m : gz_slot_cap(m), 0, verd[q].status, 0};
-    j.want_end = true;
-    jobs.push_back(j);
-    jq.push_back(q);
-  }
-  bool any = false;
-  for (const InfJob& j : jobs) any = any || j.status == ZES_OK;
-  if (any) {
-    const std::vector<uint8_t> firsts(jobs.size(), 0x78);
-    if ((rc = inflate_jobs((const uint8_t*)g.gz_bodies.p, base, jobs, firsts.data(), flags & ZES_F_PIECES))) return rc;
-    keep_times();
-  }
-  std::vector<ZesGzSeg> segs;
-  for (size_t i = 0; i < jobs.size(); i++) {
-    const uint32_t q = jq[i];
-    const ZipPart& p = ps[st[q]];
-    const InfJob& j = jobs[i];
-    if (verd[q].status) continue;
-    if ((status[st[q]] = gz_job_verdict(j, p.z.usize, p.z.csize))) continue;
-    if (!direct[q] && p.z.usize)
-      segs.push_back(ZesGzSeg{oslot[q], p.dst_off, p.z.usize, 0u, 0u});
-  }
-  if ((rc = gz_gather(outs, dst, segs))) return rc;
-  std::vector<ZesCrcSeg> csegs(n);
-  for (uint32_t q = 0; q < n; q++) {
-    const bool ok = status[st[q]] == ZES_OK && ps[st[q]].z.usize;
-    csegs[q] = ZesCrcSeg{ok ? ps[st[q]].dst_off : 0, ok ? ps[st[q]].z.usize : 0};
-  }
-  std::vector<uint32_t> crc(n);
-  if ((rc = crc32_batch_locked(dst, csegs.data(), n, crc.data()))) return rc;
-  for (uint32_t q = 0; q < n; q++)
-    if (status[st[q]] == ZES_OK && crc[q] != ps[st[q]].z.crc) status[st[q]] = ZES_E_CHECKSUM;
-  return ZES_OK;
+  for (uint32_t q = 0; q < n; q++) bs[q].status = verd[q].status;
+  rc = body_run(bs, dst, flags & ZES_F_PIECES, false, nullptr);
+  for (uint32_t q = 0; q < n; q++) status[st[q]] = bs[q].status;
+  return rc;
 }
 
 int zes_zip_read_dev(const uint8_t* d_in, uint64_t c, const zes_zip_entry* ent, uint64_t nent, const uint32_t* sel, uint32_t count, uint8_t* d_out,
@@ -5119,10 +5124,7 @@ int zes_zip_read_dev(const uint8_t* d_in, uint64_t c, const zes_zip_entry* ent, 
     if (status[i] == ZES_OK && z.usize && !d_out) return ZES_E_ARG;
   }
   LOCK_READY();
-  rc = zip_read_core(d_in, ps, d_out, status, flags);
-  if (rc) (void)hipGetLastError();
-  collect_times();
-  if (rc) return rc;
+  if ((rc = call_done(zip_read_core(d_in, ps, d_out, status, flags), true))) return rc;
   for (uint32_t i = 0; i < count; i++)
     if (status[i] == ZES_OK) out_len[i] = ps[i].z.usize;
   return ZES_OK;
@@ -5163,10 +5165,7 @@ int zes_zip_read_alloc(const uint8_t* in, uint64_t c, const zes_zip_entry* ent, 
     if ((rc = upload((uint8_t*)g.gz_in.p + ps[i].hdr_at, in + ps[i].z.hdr_off, take[i]))) return rc;
     if ((rc = upload((uint8_t*)g.gz_in.p + ps[i].name_at, in + ps[i].z.name_pos, ps[i].z.name_len))) return rc;
   }
-  rc = zip_read_core((const uint8_t*)g.gz_in.p, ps, (uint8_t*)g.gz_acc.p, status, flags);
-  if (rc) (void)hipGetLastError();
-  collect_times();
-  if (rc) return rc;
+  if ((rc = call_done(zip_read_core((const uint8_t*)g.gz_in.p, ps, (uint8_t*)g.gz_acc.p, status, flags), true))) return rc;
   for (uint32_t i = 0; i < count; i++) {
     if (status[i]) continue;
     uint8_t* to = alloc(user, i, ps[i].z.usize);
@@ -5190,11 +5189,6 @@ constexpr uint64_t ZIPW_GROUP_SLOTS_PIECES = 1ull << 20;  // ... under ZES_F_PIE
 constexpr uint32_t ZIPW_COUNT_MAX = 65534;        // (65535 is ZIP64's mark)
 constexpr uint64_t ZIPW_LEN_MAX = 0xFFFFFFFEull;  // (as is 0xFFFFFFFF in a size or an offset)
 static_assert(ZIPW_GROUP <= DEFLATE_TABLE_BUFS && ZIPW_GROUP <= DEFLATE_DIRECT_BUFS, "a group's buffer table and results go through the page-locked area");
-
-static void put_le16(uint8_t* p, uint32_t v) {
-  p[0] = (uint8_t)v;
-  p[1] = (uint8_t)(v >> 8);
-}
 
 static uint64_t zipwrite_bound(const uint64_t* in_len, const uint16_t* name_len, uint32_t count) {
   uint64_t b = ZIP_END;
@@ -5232,13 +5226,12 @@ static int zipwrite_args(const std::function<bool(uint32_t)>& data, const uint64
 
 // The archive of the entries d_in[in_off[i], + in_len[i]) into d_out[0, cap), group by group as bgzip_core goes: a group is
 // up to ZIPW_GROUP entries (ZIPW_GROUP_PIECES under ZES_F_PIECES) whose encoder slots take up to ZIPW_GROUP_SLOTS bytes (ZIPW_GROUP_SLOTS_PIECES),
-// and one entry at least.  The group's entries are checksummed by one segmented CRC-32 launch and those the encoder accepts
-// are encoded as independent buffers into 16-byte aligned slots of g.gz_bodies; the sizes come back, the host chooses the
-// method (8 when the raw stream is shorter than the entry, else 0) and the places, and one k_zip_pack launch writes the
-// group's headers, names and bodies.  The directory and the end record are made here and go up in one copy behind the last
-// group.  g.gz_tab holds the names (uploaded once, padded to whole 16-byte groups) and behind them the group's records.  A
-// result beyond cap: every group is still encoded (the size needed is the answer), and from the first group that does not
-// fit whole nothing more is written.  ent: null, or the records zes_zip_index lists for the result.
+// and one entry at least.  The group goes through EncGroup (an entry that the encoder refuses is spared and has no slot, so
+// a group of such entries makes no encoder call); the sizes come back, the host chooses the method (8 when the raw stream
+// is shorter than the entry, else 0) and the places, and one k_zip_pack launch writes the group's headers, names and bodies.
+// The directory and the end record are made here and go up in one copy behind the last group.  g.gz_tab holds the names
+// (uploaded once, padded to whole 16-byte groups) and behind them the group's records.  A result beyond cap: EncGroup's
+// rule, with the directory as one more group.  ent: null, or the records zes_zip_index lists for the result.
 // The host memory that the call's asynchronous uploads read (the padded names, every group's records, the directory) is the
 // caller's, zipwrite_core's, which lets the stream finish before it gives it up on any way out.
 struct ZipwHost {
@@ -5266,40 +5259,25 @@ static int zipwrite_groups(ZipwHost& hm, const uint8_t* d_in, const uint64_t* in
   std::vector<ZesZipPackRec>& recs = hm.recs;
   recs.resize(2 * (size_t)count + 1);
   size_t rpos = 0;
-  const size_t gmax = std::min(group, count);
-  std::vector<uint64_t> o_off(gmax), o_cap(gmax), o_len(gmax);
-  std::vector<int32_t> status(gmax);
-  std::vector<ZesCrcSeg> csegs(gmax);
-  std::vector<uint32_t> crc(gmax);
+  EncGroup eg(std::min(group, count));
   auto slot_of = [](uint64_t len) { return deflate_throws(len) ? 0ull : gz_up16(deflate_bound(len)); };
   uint64_t total = 0;
-  bool fits = true;
   for (uint32_t e0 = 0; e0 < count;) {
     uint32_t cnt = 0;
     uint64_t slots = 0;
     while (e0 + cnt < count && cnt < group && (cnt == 0 || slots + slot_of(in_len[e0 + cnt]) <= group_slots)) {
-      o_off[cnt] = slots;
-      o_cap[cnt] = slot_of(in_len[e0 + cnt]);
-      slots += o_cap[cnt];
-      csegs[cnt] = ZesCrcSeg{in_off[e0 + cnt], in_len[e0 + cnt]};
+      eg.o_off[cnt] = slots;
+      eg.o_cap[cnt] = slot_of(in_len[e0 + cnt]);
+      slots += eg.o_cap[cnt];
       cnt++;
     }
-    if ((rc = ensure(g.gz_bodies, slots + 64))) return rc;
-    if ((rc = crc32_batch_locked(d_in, csegs.data(), cnt, crc.data()))) return rc;
-    if (slots) {  // (a group of entries the encoder refuses makes no call: no times of its own to keep)
-      if ((rc = deflate_batch_core(d_in, in_off + e0, in_len + e0, (uint8_t*)g.gz_bodies.p, o_off.data(), o_cap.data(), o_len.data(), status.data(), cnt)))
-        return rc;
-      keep_times();
-    }
+    if ((rc = eg.encode(d_in, in_off + e0, in_len + e0, cnt, slots))) return rc;
     ZesZipPackRec* gr = &recs[rpos];
     uint32_t wgs = 0;
     for (uint32_t k = 0; k < cnt; k++) {
       const uint32_t i = e0 + k;
-      const uint64_t len = in_len[i];
-      const bool enc = !deflate_throws(len);
-      if (enc && (status[k] != ZES_OK || o_len[k] < 6)) return status[k] ? status[k] : ZES_E_DEVICE;
-      const uint64_t raw = enc ? o_len[k] - 6 : 0;  // without 78 9C and the Adler-32
-      const bool deflated = enc && raw < len;
+      const uint64_t len = in_len[i], raw = eg.raw[k];
+      const bool deflated = eg.o_cap[k] && raw < len;
       if (total >= 0xFFFFFFFFull) return ZES_E_UNSUPPORTED;
       bool utf8 = false;
       for (uint32_t b = 0; b < name_len[i]; b++) utf8 = utf8 || names[name_off[i] + b] >= 0x80;
@@ -5308,7 +5286,7 @@ static int zipwrite_groups(ZipwHost& hm, const uint8_t* d_in, const uint64_t* in
       t.name_pos = 0;  // (known with the directory's place)
       t.csize = (uint32_t)(deflated ? raw : len);
       t.usize = (uint32_t)len;
-      t.crc = crc[k];
+      t.crc = eg.crc[k];
       t.name_off = name_off[i];
       t.name_len = name_len[i];
       t.method = deflated ? 8 : 0;
@@ -5316,7 +5294,7 @@ static int zipwrite_groups(ZipwHost& hm, const uint8_t* d_in, const uint64_t* in
       t.pad = 0;
       ZesZipPackRec& r = gr[k];
       memset(&r, 0, sizeof r);
-      r.src_off = deflated ? o_off[k] + 2 : in_off[i];
+      r.src_off = deflated ? eg.o_off[k] + 2 : in_off[i];
       r.dst_off = total;
       r.csize = t.csize;
       r.usize = t.usize;
@@ -5331,8 +5309,7 @@ static int zipwrite_groups(ZipwHost& hm, const uint8_t* d_in, const uint64_t* in
     }
     memset(&gr[cnt], 0, sizeof(ZesZipPackRec));
     gr[cnt].first_wg = wgs;
-    fits = fits && total <= cap && d_out != nullptr;
-    if (fits) {
+    if (eg.room(total, cap, d_out)) {
       HIPCHK(hipMemcpyAsync(d_recs, gr, sizeof(ZesZipPackRec) * ((size_t)cnt + 1), hipMemcpyHostToDevice, g.stream));
       Timed t("k_zip_pack");
       hipLaunchKernelGGL(k_zip_pack, dim3(wgs), dim3(GZ_GATHER_THREADS), 0, g.stream, d_in, (const uint8_t*)g.gz_bodies.p, (const uint8_t*)g.gz_tab.p, d_out,
@@ -5371,11 +5348,10 @@ static int zipwrite_groups(ZipwHost& hm, const uint8_t* d_in, const uint64_t* in
   cd.resize((size_t)cd_size + ZIP_END);
   zip_end_record(&cd[(size_t)cd_size], count, cd_size, cd_off);
   total += cd.size();
-  fits = fits && total <= cap && d_out != nullptr;
-  if (fits) HIPCHK(hipMemcpyAsync(d_out + cd_off, cd.data(), cd.size(), hipMemcpyHostToDevice, g.stream));
+  if (eg.room(total, cap, d_out)) HIPCHK(hipMemcpyAsync(d_out + cd_off, cd.data(), cd.size(), hipMemcpyHostToDevice, g.stream));
   HIPCHK(hipStreamSynchronize(g.stream));
   *out_len = total;
-  if (!fits) return ZES_E_NOSPACE;
+  if (!eg.fits) return ZES_E_NOSPACE;
   if (ent && count) memcpy(ent, z.data(), sizeof(zes_zip_entry) * (size_t)count);
   return ZES_OK;
 }
@@ -5402,9 +5378,7 @@ int zes_zipwrite_dev(const uint8_t* d_in, const uint64_t* in_off, const uint64_t
   if (const int arc = zipwrite_args([&](uint32_t) { return d_in != nullptr; }, in_len, names, name_len, count, d_out, cap, out_len, flags)) return arc;
   LOCK_READY();
   rc = zipwrite_core(d_in, in_off, in_len, names, name_len, count, d_out, cap, out_len, ent, flags);
-  if (rc && rc != ZES_E_NOSPACE) (void)hipGetLastError();
-  collect_times();
-  return rc;
+  return call_done(rc, rc != ZES_E_NOSPACE);  // (ZES_E_NOSPACE is an answer, not a failure)
 }
 
 int zes_zipwrite(const uint8_t* const* in, const uint64_t* in_len, const uint8_t* names, const uint16_t* name_len, uint32_t count, uint8_t* out, uint64_t cap,
@@ -5433,9 +5407,7 @@ int zes_zipwrite(const uint8_t* const* in, const uint64_t* in_len, const uint8_t
   uint64_t total = 0;
   std::vector<zes_zip_entry> z(ent ? count : 0);
   rc = zipwrite_core((const uint8_t*)g.gz_in.p, in_off.data(), in_len, names, name_len, count, (uint8_t*)g.gz_acc.p, bound, &total, ent ? z.data() : nullptr, flags);
-  if (rc) (void)hipGetLastError();
-  collect_times();
-  if (rc) return rc;
+  if ((rc = call_done(rc, true))) return rc;
   *out_len = total;
   if (total > cap) return ZES_E_NOSPACE;
   if ((rc = download(out, (const uint8_t*)g.gz_acc.p, total))) return rc;

@@ -1,5 +1,7 @@
 // zes_gzip.hip — device pieces of the member-parallel gzip reader (zes_api.hip: gunzip_parallel) and of the BGZF writer
-// (zes_api.hip: bgzip_core), and of the ZIP reader and writer (zes_api.hip: zip_read_core, zipwrite_core).
+// (zes_api.hip: bgzip_core), and of the ZIP reader and writer (zes_api.hip: zip_read_core, zipwrite_core).  The two readers
+// share their plan (body_plan, body_run) and differ in the staging kernel, the two writers share the group step (EncGroup)
+// and differ in the pack kernel.
 //
 // A file whose members all state their own size — BGZF, the format of bgzip / htslib: every member's extra field holds a
 // subfield 'B','C' with BSIZE = member size - 1 — can be cut into its members without decoding anything.
