@@ -933,7 +933,7 @@ def inflate_range_tensor(t, lo_bit, own_bit, exact, out):
 
     assert t.is_cuda and t.dtype == torch.uint8 and t.is_contiguous() and out.is_cuda
     lo_bit = max(16, int(lo_bit))
-    byte0 = (lo_bit >> 3) & ~15
+    byte0 = (lo_bit >> 3) & ~15  # (t1_piece_origin of csrc/zes_api.hip, restated: the C ABI takes the piece, not the stream)
     if byte0 >= 16:
         byte0 -= 16  # (the search starts 16 bits into what it is given)
     end = min(t.numel(), (int(own_bit) + 7) // 8 + (1 << 20))  # the last block's bytes and the header behind it

@@ -861,12 +861,20 @@ int launch_lz77(const uint8_t* d_in, uint32_t grid, bool use_index, bool heavies
   return ZES_OK;
 }
 
+// What only a one-buffer call has to say (deflate_one): the range form of the buffer, and its Adler-32 on the way back
+struct DeflateRange {
+  uint64_t n_read = 0;     // bytes readable from the buffer's start on (the match finder's halo behind it); less than its length: its length
+  uint32_t flags = 0;      // ZES_BUF_*
+  uint32_t start_bit = 0;  // the first bit of the result lies this far into d_out + out_off
+  bool defer = false;      // return behind the launches: the caller synchronises g.stream itself and reads g.pinned->def.res[0]
+  uint32_t adler = 1;      // out (not when deferred): Adler-32 of the buffer
+};
+
 // Core: count buffers inside d_in / d_out.  Buffers whose status[] comes back non-zero were
-// rejected on the host (throw cases, capacity) and are skipped by the device pass.
+// rejected on the host (throw cases, capacity) and are skipped by the device pass.  `one`: with count == 1 only.
 int deflate_batch_core(const uint8_t* d_in, const uint64_t* in_off, const uint64_t* in_len, uint8_t* d_out,
                        const uint64_t* out_off, const uint64_t* out_cap, uint64_t* out_len, int32_t* status,
-                       uint32_t count, const uint64_t* in_read = nullptr, const uint32_t* bflags = nullptr, uint32_t* adler_out = nullptr,
-                       const uint32_t* start_bits = nullptr, bool defer = false) {
+                       uint32_t count, DeflateRange* one = nullptr) {
   std::vector<ZesBuf> hb;
   uint64_t nblk_total = 0;
   std::vector<uint32_t> live;
@@ -894,9 +902,9 @@ int deflate_batch_core(const uint8_t* d_in, const uint64_t* in_off, const uint64
     b.cap = out_cap[i];
     b.first_blk = (uint32_t)nblk_total;
     b.nblk = (uint32_t)((in_len[i] + ZES_BLK - 1) / ZES_BLK);
-    b.n_read = in_read ? std::max(in_read[i], in_len[i]) : in_len[i];
-    b.flags = bflags ? bflags[i] : 0u;
-    b.start_bit = start_bits ? start_bits[i] : 0u;
+    b.n_read = one ? std::max(one->n_read, in_len[i]) : in_len[i];
+    b.flags = one ? one->flags : 0u;
+    b.start_bit = one ? one->start_bit : 0u;
     nblk_total += b.nblk;
     hb.push_back(b);
     live.push_back(i);
@@ -996,15 +1004,24 @@ int deflate_batch_core(const uint8_t* d_in, const uint64_t* in_off, const uint64
     r = g.res_more;
   }
   if (!res_direct) HIPCHK(hipMemcpyAsync(r, g.res.p, sizeof(ZesRes) * nbuf, hipMemcpyDeviceToHost, g.stream));
-  if (defer) return ZES_OK;  // (one buffer: the caller reads def.res after its own synchronisation, deflate_host_pipelined)
+  if (one && one->defer) return ZES_OK;  // (the caller reads def.res after its own synchronisation, deflate_host_pipelined)
   HIPCHK(hipStreamSynchronize(g.stream));
   collect_times();
   for (uint32_t k = 0; k < nbuf; k++) {
     out_len[live[k]] = r[k].out_len;
     status[live[k]] = r[k].status;
-    if (adler_out) adler_out[live[k]] = r[k].aux;
   }
+  if (one) one->adler = r[0].aux;
   return ZES_OK;
+}
+
+// One buffer at d_in+in_off, its result at d_out+out_off (16-byte aligned) with room for cap bytes: inflate_one's mirror.
+// Returns the reference-equivalent status; *out_len = bytes produced (a range: bits), or the capacity needed on NOSPACE.
+int deflate_one(const uint8_t* d_in, uint64_t in_off, uint64_t n, uint8_t* d_out, uint64_t out_off, uint64_t cap, uint64_t* out_len,
+                DeflateRange* range = nullptr) {
+  int32_t st = 0;
+  const int rc = deflate_batch_core(d_in, &in_off, &n, d_out, &out_off, &cap, out_len, &st, 1, range);
+  return rc ? rc : st;
 }
 
 // ---- inflate ----
@@ -2340,7 +2357,10 @@ int inflate_segments_pieces(const uint8_t* d_in, uint8_t* d_out, InfJob& j) {
   uint64_t piece_now = piece;  // (grows when a piece does not hold its first block whole: an encoder with very long blocks)
   bool nospace = false;  // the caller's room ran out: the pieces behind are only measured (the chain's lengths need no output)
   for (int guard = 0; guard < (1 << 20); guard++) {
-    // the piece: from a 16-byte boundary at least two bytes in front of the block (work item 0 starts at bit >= 16 of it)
+    // the piece: from a 16-byte boundary at least two bytes in front of the block (work item 0 starts at bit >= 16 of it).
+    // Not t1_piece_origin's rule, which always steps one boundary back: here it is the nearest boundary that leaves the
+    // two bytes.  Both keep the block at bit >= 16; they give different bit positions inside the piece (start0 here, the
+    // range's lo_bit there), which the kernels see, so each tier keeps its own.
     const uint64_t pb = pos_bit >> 3;
     const uint64_t byte0 = pb >= 2 ? ((pb - 2) & ~15ull) : 0;
     std::vector<InfJob> sub(1);
@@ -2489,13 +2509,19 @@ int inflate_slow(const uint8_t* d_in, uint8_t* d_out, InfJob& j) {
 // the piece before; it is handed over with enough bytes behind it for its last block and the header behind that.
 constexpr uint64_t T1_PIECE = 256ull << 20;
 constexpr uint64_t T1_PIECE_SLACK = 1ull << 20;
+// Where the buffer of a piece that starts at stream bit `bit` begins: a 16-byte boundary, one in front of the bit's own
+// (the block search starts 16 bits into a buffer: keep the piece's first block behind that)
+uint64_t t1_piece_origin(uint64_t bit) {
+  uint64_t byte0 = (bit >> 3) & ~15ull;
+  if (byte0 >= 16) byte0 -= 16;
+  return byte0;
+}
 int inflate_pieces(const uint8_t* d_in, uint8_t* d_out, InfJob& j, uint32_t flags) {
   uint64_t piece = T1_PIECE;
   if (flags & ZES_F_PIECES) piece = 1ull << 20;  // testing aid: 1 MiB pieces
   uint64_t pos_bit = 16, total = 0, blocks = 0;
   for (uint32_t round = 0; round < (1u << 20); round++) {
-    uint64_t byte0 = (pos_bit >> 3) & ~15ull;
-    if (byte0 >= 16) byte0 -= 16;  // (the block search starts 16 bits into a buffer: keep the piece's first block behind that)
+    const uint64_t byte0 = t1_piece_origin(pos_bit);
     const uint64_t rel = pos_bit - 8 * byte0;
     const uint64_t pc = std::min<uint64_t>(j.c - byte0, piece + T1_PIECE_SLACK);
     const uint64_t done_bytes = blocks * ZES_BLK;
@@ -2704,6 +2730,19 @@ void put_le32(uint8_t* p, uint32_t v) {
   put_le16(p + 2, v >> 16);
 }
 uint32_t get_be32(const uint8_t* p) { return (uint32_t)p[0] << 24 | (uint32_t)p[1] << 16 | (uint32_t)p[2] << 8 | p[3]; }
+void put_be32(uint8_t* p, uint32_t v) {  // (the zlib trailer, src/zlib.ts:37-40)
+  for (int k = 0; k < 4; k++) p[k] = (uint8_t)(v >> (24 - 8 * k));
+}
+
+// Adler-32 of a concatenation from its pieces' (src/adler32.ts:1-10): s1 adds up; a piece's s2 also sees len * (s1 so far - 1)
+struct AdlerJoin {
+  uint64_t s1 = 1, s2 = 0;
+  void add(uint32_t adler, uint64_t len) {
+    s2 = (s2 + (adler >> 16) + (len % 65521u) * ((s1 + 65520u) % 65521u)) % 65521u;
+    s1 = (s1 + (adler & 0xFFFFu) + 65520u) % 65521u;
+  }
+  uint32_t value() const { return (uint32_t)((s2 << 16) | s1); }
+};
 
 // segs[i].len bytes from src + src_off to dst + dst_off for every i, in one launch (k_gz_gather); the table goes through g.gz_tab
 int gz_gather(const uint8_t* src, uint8_t* dst, const std::vector<ZesGzSeg>& segs) {
@@ -3016,11 +3055,74 @@ int zes_deflate_batch_dev(const uint8_t* d_in, const uint64_t* in_off, const uin
 int zes_deflate_dev(const uint8_t* d_in, uint64_t n, uint8_t* d_out, uint64_t cap, uint64_t* out_len) {
   ROUTE_DEV(d_in, d_out);
   if (!out_len) return ZES_E_ARG;
-  uint64_t zero = 0;
-  int32_t st = 0;
-  int rc = zes_deflate_batch_dev(d_in, &zero, &n, d_out, &zero, &cap, out_len, &st, 1);
-  return rc ? rc : st;
+  LOCK_READY();
+  return deflate_one(d_in, 0, n, d_out, 0, cap, out_len);
 }
+
+// The conveyor of the two pipelined host calls below: the caller's buffer goes up piece by piece on g.cs_in (one side
+// thread), finished windows of the result go down on g.cs_out (another), and g.stream waits for a piece's upload by its
+// event, ev_up[k & 1].  What a piece is, when the next one is sent up and when a window goes down is the caller's.
+// The side tasks use this object and, through `rule` and `stamp`, the caller's frame: declare it behind everything they
+// touch, so that it is destroyed first — its destructor waits for both tasks on every way out of the caller.
+// A download into pinned memory is only enqueued (download(..., wait = false)): a caller that has sent anything leaves
+// through drain(), which synchronises g.cs_out.
+struct HostPipe {
+  const uint8_t* src;  // the caller's buffer, n bytes
+  uint8_t* d_src;      // its place on the device
+  uint64_t n;
+  uint32_t np;                                       // pieces
+  std::function<uint64_t(uint32_t)> rule;            // upload k carries [cut(k), cut(k + 1)): cut(k) = min(n, rule(k)) for 0 < k < np
+  std::function<void(const char*, uint32_t)> stamp;  // ZES_PIPE_DBG's timeline ("up done", "down issued"): may be empty
+  std::future<int> f_up, f_down;
+  bool in_flight = false;  // a window may still be on its way into the caller's memory
+  ~HostPipe() {  // no side task may outlive the frame whose variables it uses, no copy the call
+    (void)settle();
+    if (in_flight) (void)hipStreamSynchronize(g.cs_out);  // (an error's way out: drain() was not reached)
+  }
+  static int settle(std::future<int>& f) { return f.valid() ? f.get() : (int)ZES_OK; }
+  int settle() {  // both side tasks done: the first one's error, else the second's
+    const int ru = settle(f_up), rd = settle(f_down);
+    return ru ? ru : rd;
+  }
+  uint64_t cut(uint32_t k) const { return k == 0 ? 0ull : k >= np ? n : std::min<uint64_t>(n, rule(k)); }
+  int up(uint32_t k) {  // (an upload of no bytes still records its event)
+    const uint64_t a = cut(k), b = cut(k + 1);
+    const int r = upload(d_src + a, src + a, b - a, g.cs_in);
+    if (r == ZES_OK) HIPCHK(hipEventRecord(g.ev_up[k & 1], g.cs_in));
+    if (stamp) stamp("up done", k);
+    return r;
+  }
+  void submit_up(uint32_t k) { f_up = g_side_up.submit([this, k] { return up(k); }); }
+  // piece k is up, or on its way with its event recorded: g.stream waits for it (`next`: a piece to send up first, so
+  // that its upload starts in front of the wait's enqueue: the pipelined inflate, whose uploads lead by two)
+  int ready(uint32_t k, uint32_t next = UINT32_MAX) {
+    if (const int rc = settle(f_up)) return rc;
+    if (next < np) submit_up(next);
+    HIPCHK(hipStreamWaitEvent(g.stream, g.ev_up[k & 1], 0));
+    return ZES_OK;
+  }
+  // bytes [a, b) of the result on their way to the caller, behind the window sent before (`k`: for the timeline)
+  int send(uint8_t* out, const uint8_t* d_out, uint64_t a, uint64_t b, uint32_t k) {
+    if (const int rc = settle(f_down)) return rc;
+    in_flight = true;
+    f_down = g_side_down.submit([this, out, d_out, a, b, k] {
+      const int r = download(out + a, d_out + a, b - a, g.cs_out, false);
+      if (stamp) stamp("down issued", k);
+      return r;
+    });
+    return ZES_OK;
+  }
+  // the one tail: both side tasks done, a last window [a, b) if there is one, and every byte sent has arrived
+  int drain(uint8_t* out = nullptr, const uint8_t* d_out = nullptr, uint64_t a = 0, uint64_t b = 0) {
+    int rc = settle();
+    if (rc) return rc;
+    in_flight = in_flight || b > a;
+    if (b > a && (rc = download(out + a, d_out + a, b - a, g.cs_out, false))) return rc;
+    HIPCHK(hipStreamSynchronize(g.cs_out));
+    in_flight = false;
+    return ZES_OK;
+  }
+};
 
 // Host deflate of a large buffer in pieces of 256 blocks (one workgroup per CU), so that the three legs overlap: while
 // the kernels work on piece k, piece k+1 crosses PCIe on one copy stream and the finished bytes of piece k-1 go back
@@ -3029,13 +3131,6 @@ int zes_deflate_dev(const uint8_t* d_in, uint64_t n, uint8_t* d_out, uint64_t ca
 // the last dword of the piece before (ZES_BUF_CONT).  78 9C and the Adler-32 of the whole input (combined from the
 // pieces': src/adler32.ts:1-10 is associative) are put into the caller's buffer by the host.  Same bytes as the
 // one-pass path (tests/test_gpu_configs.py::test_pipelined_host_calls).
-struct SettleGuard {  // no side task may outlive the frame whose variables it uses
-  std::future<int>&a, &b;
-  ~SettleGuard() {
-    if (a.valid()) a.wait();
-    if (b.valid()) b.wait();
-  }
-};
 constexpr uint64_t PIPE_PIECE = 256ull * ZES_BLK;  // 32 MiB
 constexpr uint64_t PIPE_MIN = PIPE_PIECE + PIPE_PIECE / 2;
 constexpr uint64_t PIPE_HALO = 4096;  // a piece's match finder reads up to 258 bytes behind it: uploads are cut this far behind the piece ends
@@ -3047,94 +3142,53 @@ static int deflate_host_pipelined(const uint8_t* in, uint64_t n, uint8_t* out, u
   const uint8_t* d_in = (const uint8_t*)g.st_in.p;
   uint8_t* d_out = (uint8_t*)g.st_out.p;
   const uint32_t np = (uint32_t)((n + PIPE_PIECE - 1) / PIPE_PIECE);
-  auto cut = [&](uint32_t k) { return k == 0 ? 0ull : k >= np ? n : std::min<uint64_t>(n, (uint64_t)k * PIPE_PIECE + PIPE_HALO); };
-  auto up = [&](uint32_t k) -> int {  // upload k: bytes [cut(k), cut(k+1))
-    int r = upload((uint8_t*)g.st_in.p + cut(k), in + cut(k), cut(k + 1) - cut(k), g.cs_in);
-    if (r) return r;
-    HIPCHK(hipEventRecord(g.ev_up[k & 1], g.cs_in));
-    return ZES_OK;
-  };
   const bool pdbg = getenv("ZES_PIPE_DBG") != nullptr;
   const auto t00 = std::chrono::steady_clock::now();
   auto stamp = [&](const char* what, uint32_t k) {
     if (pdbg) fprintf(stderr, "  pipe %-14s %u  %.3f ms\n", what, k, std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t00).count());
   };
-  if ((rc = up(0))) return rc;
-  stamp("up done", 0);
-  uint64_t pos = 16;       // bit position of the next piece in the output stream (behind 78 9C)
-  uint64_t sent = 0;       // bytes of the output already on their way to the caller
-  uint64_t s1 = 1, s2 = 0;  // Adler-32 of the pieces so far
+  uint64_t pos = 16;  // bit position of the next piece in the output stream (behind 78 9C)
+  uint64_t sent = 0;  // bytes of the output already on their way to the caller
+  AdlerJoin adler;    // of the pieces so far
   const bool out_fits = cap >= bound;  // (else: count first, the caller gets the size needed)
   uint64_t pend_lo = 0, pend_hi = 0;   // bytes of the output finished by the piece before, not yet sent
-  std::future<int> f_up, f_down;
-  SettleGuard guard{f_up, f_down};
-  auto settle = [&](std::future<int>& f) { return f.valid() ? f.get() : (int)ZES_OK; };
+  HostPipe pipe{in, (uint8_t*)g.st_in.p, n, np, [](uint32_t k) { return (uint64_t)k * PIPE_PIECE + PIPE_HALO; }, stamp};
+  if ((rc = pipe.up(0))) return rc;
   for (uint32_t k = 0; k < np; k++) {
     const uint64_t lo = (uint64_t)k * PIPE_PIECE, len = std::min<uint64_t>(PIPE_PIECE, n - lo);
-    const uint64_t readable = std::min<uint64_t>(n - lo, len + 258);
     const uint64_t o_off = (pos >> 7) << 4;  // 16-byte aligned byte offset; the piece starts start_bit bits into it
-    const uint32_t sbit = (uint32_t)(pos - o_off * 8);
-    const uint64_t o_cap = bound + 64 - o_off;
-    const uint32_t fl = ZES_BUF_RANGE | (k + 1 < np ? ZES_BUF_NOTFINAL : 0u) | (k ? ZES_BUF_CONT : 0u);
-    uint64_t bits = 0, in_off = lo;
-    int32_t st = 0;
-    uint32_t ad = 1;
-    if ((rc = settle(f_up))) {  // (piece k is up, or on its way with its event recorded)
-      (void)settle(f_down);
-      return rc;
-    }
-    HIPCHK(hipStreamWaitEvent(g.stream, g.ev_up[k & 1], 0));
-    rc = deflate_batch_core(d_in, &in_off, &len, d_out, &o_off, &o_cap, &bits, &st, 1, &readable, &fl, &ad, &sbit, true);
-    if (rc || st) {
-      (void)settle(f_down);
-      return rc ? rc : st;
-    }
+    DeflateRange piece{std::min<uint64_t>(n - lo, len + 258), ZES_BUF_RANGE | (k + 1 < np ? ZES_BUF_NOTFINAL : 0u) | (k ? ZES_BUF_CONT : 0u),
+                       (uint32_t)(pos - o_off * 8), true};  // readable, flags, start bit, deferred
+    uint64_t bits = 0;
+    if ((rc = pipe.ready(k))) return rc;
+    if ((rc = deflate_one(d_in, lo, len, d_out, o_off, bound + 64 - o_off, &bits, &piece))) return rc;
     // beside the kernels: the next piece up, the bytes the piece before finished down
     stamp("launched", k);
-    if (k + 1 < np) f_up = g_side_up.submit([&up, &stamp, k] { int r = up(k + 1); stamp("up done", k + 1); return r; });
+    if (k + 1 < np) pipe.submit_up(k + 1);
     if (out_fits && pend_hi > pend_lo) {
-      if ((rc = settle(f_down))) return rc;
-      const uint64_t a = pend_lo, b = pend_hi;
-      f_down = g_side_down.submit([=, &stamp] { int r = download(out + a, d_out + a, b - a, g.cs_out, false); stamp("down issued", k); return r; });
+      if ((rc = pipe.send(out, d_out, pend_lo, pend_hi, k))) return rc;
       sent = pend_hi;
     }
-    if (hipStreamSynchronize(g.stream) != hipSuccess) {
-      (void)settle(f_up);
-      (void)settle(f_down);
-      return ZES_E_DEVICE;
-    }
+    HIPCHK(hipStreamSynchronize(g.stream));
     collect_times();
     stamp("kernels done", k);
     const ZesRes* r = g.pinned->def.res;
-    if (r[0].status) {
-      (void)settle(f_up);
-      (void)settle(f_down);
-      return r[0].status;
-    }
-    bits = r[0].out_len;
-    ad = r[0].aux;
-    pos += bits;
-    const uint64_t a1 = ad & 0xFFFFu, a2 = ad >> 16;
-    s2 = (s2 + a2 + (len % 65521u) * ((s1 + 65520u) % 65521u)) % 65521u;
-    s1 = (s1 + a1 + 65520u) % 65521u;
+    if (r[0].status) return r[0].status;
+    pos += r[0].out_len;
+    adler.add(r[0].aux, len);
     pend_lo = sent;
     pend_hi = (k + 1 < np) ? (pos >> 3) : ((pos + 7) >> 3);  // whole bytes; the last piece's padded end
   }
-  if ((rc = settle(f_down))) return rc;
   const uint64_t raw_end = (pos + 7) >> 3, total = raw_end + 4;
+  if (out_fits && (rc = pipe.drain(out, d_out, pend_lo, pend_hi))) return rc;  // (total <= bound <= cap)
   *out_len = total;
   if (total > cap) return ZES_E_NOSPACE;
-  if (!out_fits) {  // a capacity below the bound that still holds the result: one copy now
-    if ((rc = download(out, d_out, raw_end, g.cs_out, true))) return rc;
-  } else {
-    if (pend_hi > pend_lo && (rc = download(out + pend_lo, d_out + pend_lo, pend_hi - pend_lo, g.cs_out, false))) return rc;
-    HIPCHK(hipStreamSynchronize(g.cs_out));
-  }
+  // a capacity below the bound that still holds the result: nothing has gone down so far, one copy now
+  if (!out_fits && (rc = download(out, d_out, raw_end, g.cs_out, true))) return rc;
   stamp("all down", np);
   out[0] = 0x78;  // src/zlib.ts:29-34
   out[1] = 0x9C;
-  const uint32_t adl = (uint32_t)((s2 << 16) | s1);
-  for (int k = 0; k < 4; k++) out[raw_end + k] = (uint8_t)(adl >> (24 - 8 * k));  // big-endian trailer (src/zlib.ts:37-40)
+  put_be32(out + raw_end, adler.value());
   return ZES_OK;
 }
 
@@ -3149,11 +3203,8 @@ int zes_deflate(const uint8_t* in, uint64_t n, uint8_t* out, uint64_t cap, uint6
     if (n >= PIPE_MIN && !getenv("ZES_NO_PIPELINE")) return deflate_host_pipelined(in, n, out, cap, out_len);
     if ((rc = ensure(g.st_out, bound + 64))) return rc;
     if ((rc = stage_in(g.st_in, in, n))) return rc;
-    uint64_t zero = 0, dl = 0;
-    int32_t st = 0;
-    rc = deflate_batch_core((const uint8_t*)g.st_in.p, &zero, &n, (uint8_t*)g.st_out.p, &zero, &bound, &dl, &st, 1);
-    if (rc) return rc;
-    if (st) return st;
+    uint64_t dl = 0;
+    if ((rc = deflate_one((const uint8_t*)g.st_in.p, 0, n, (uint8_t*)g.st_out.p, 0, bound, &dl))) return rc;
     *out_len = dl;
     if (dl > cap) return ZES_E_NOSPACE;
     return download(out, (const uint8_t*)g.st_out.p, dl);
@@ -3242,45 +3293,29 @@ static int inflate_host_pipelined(const uint8_t* in, uint64_t c, uint8_t* out, u
   if ((rc = ensure(g.st_out, dcap + 64))) return rc;
   const uint8_t* d_in = (const uint8_t*)g.st_in.p;
   uint8_t* d_out = (uint8_t*)g.st_out.p;
-  auto cut = [&](uint32_t k) { return k == 0 ? 0ull : k >= np ? c : std::min<uint64_t>(c, B[k] + T1_PIECE_SLACK); };
-  auto up = [&](uint32_t k) -> int {
-    int r = upload((uint8_t*)g.st_in.p + cut(k), in + cut(k), cut(k + 1) - cut(k), g.cs_in);
-    if (r) return r;
-    HIPCHK(hipEventRecord(g.ev_up[k & 1], g.cs_in));
-    return ZES_OK;
-  };
   {
     uint64_t cmax = 0;
     for (uint32_t k = 0; k < np; k++) cmax = std::max<uint64_t>(cmax, B[k + 1] - B[k] + T1_PIECE_SLACK + 64);
     if ((rc = range_reserve(cmax))) return rc;
   }
-  if ((rc = up(0))) return rc;
   uint64_t blocks = 0, total = 0, prev_end = 16, pend_lo = 0, pend_hi = 0;
   bool final_seen = false, chain = true;
-  std::future<int> f_up, f_down;
-  SettleGuard guard{f_up, f_down};
-  auto settle = [&](std::future<int>& f) { return f.valid() ? f.get() : (int)ZES_OK; };
   // compressible data or not (which form of the block decoder): by the whole call, not by a piece
   const bool two = c * 10 < std::min<uint64_t>(dcap, cap ? cap : dcap) * 7;
   bool early = alloc && (flags & ZES_F_ALLOC_BOUND);  // the allocator takes an upper estimate (include/zes.h)
   RangePiece pend[2];
   uint64_t byte0s[2] = {0, 0};
-  auto begin = [&](uint32_t k) -> int {  // (range k is up, or on its way with its event recorded)
-    HIPCHK(hipStreamWaitEvent(g.stream, g.ev_up[k & 1], 0));
+  auto begin = [&](uint32_t k) -> int {  // (behind pipe.ready(k): g.stream waits for range k's upload)
     const uint64_t lo_bit = k == 0 ? 16 : B[k] * 8, own_bit = B[k + 1] * 8;
-    uint64_t byte0 = (lo_bit >> 3) & ~15ull;
-    if (byte0 >= 16) byte0 -= 16;
-    byte0s[k & 1] = byte0;
+    const uint64_t byte0 = byte0s[k & 1] = t1_piece_origin(lo_bit);
     const uint64_t pc = std::min<uint64_t>(c - byte0, (own_bit >> 3) - byte0 + T1_PIECE_SLACK);
     return range_begin((int)(k & 1), pend[k & 1], d_in, byte0, pc, lo_bit - 8 * byte0, own_bit - 8 * byte0, k == 0, d_out, dcap, two, flags);
   };
-  if (np > 1) f_up = g_side_up.submit([&up] { return up(1); });
-  if ((rc = begin(0))) return rc;
+  HostPipe pipe{in, (uint8_t*)g.st_in.p, c, np, [&B](uint32_t k) { return B[k] + T1_PIECE_SLACK; }, nullptr};
+  if ((rc = pipe.up(0)) || (rc = pipe.ready(0, 1)) || (rc = begin(0))) return rc;
   for (uint32_t k = 0; k < np && chain && !final_seen; k++) {
     if (k + 1 < np) {  // the next piece is enqueued before this one's results are waited for
-      if ((rc = settle(f_up))) return rc;
-      if (k + 2 < np) f_up = g_side_up.submit([&up, k] { return up(k + 2); });
-      if ((rc = begin(k + 1))) return rc;
+      if ((rc = pipe.ready(k + 1, k + 2)) || (rc = begin(k + 1))) return rc;  // (upload k + 2 starts, then the wait for k + 1)
     }
     RangeRes rr;
     if ((rc = range_finish((int)(k & 1), pend[k & 1], &rr))) return rc;
@@ -3313,9 +3348,7 @@ static int inflate_host_pipelined(const uint8_t* in, uint64_t c, uint8_t* out, u
           }
         }
         if (out && (!alloc || early) && pend_hi > pend_lo && !(final_seen || k + 1 == np)) {  // (the last piece's bytes go down below)
-          if ((rc = settle(f_down))) return rc;
-          const uint64_t a = pend_lo, b = pend_hi;
-          f_down = g_side_down.submit([=] { return download(out + a, d_out + a, b - a, g.cs_out, false); });
+          if ((rc = pipe.send(out, d_out, pend_lo, pend_hi, k))) return rc;
           pend_lo = pend_hi = 0;
         }
       }
@@ -3324,25 +3357,17 @@ static int inflate_host_pipelined(const uint8_t* in, uint64_t c, uint8_t* out, u
   const bool dbgp = getenv("ZES_DEBUG_PIPE") != nullptr;
   auto tnow = [] { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
   const double tp0 = dbgp ? tnow() : 0;
-  if ((rc = settle(f_up))) return rc;
-  if ((rc = settle(f_down))) return rc;
+  if ((rc = pipe.settle())) return rc;
   HIPCHK(hipStreamSynchronize(g.cs_in));
   HIPCHK(hipStreamSynchronize(g.stream));  // (a piece enqueued ahead of a result that ended the loop)
   if (dbgp) fprintf(stderr, "zes pipe: loop done, settle+sync %.3f ms, np %u total %llu\n", tnow() - tp0, np, (unsigned long long)total);
-  if (!chain || !final_seen || total > dcap) {
-    HIPCHK(hipStreamSynchronize(g.cs_out));
-    return ZES_OK;  // not this way: the one-pass path decides
-  }
+  // every way out from here on is pipe.drain(): what has been sent has arrived when the caller has its answer
+  if (!chain || !final_seen || total > dcap) return pipe.drain();  // not this way: the one-pass path decides
   *done = true;
   g.last_tier = 1;
   *out_len = total;
-  if (alloc && early && out && total <= cap) {  // the estimate held: what is left to go down is the last piece
-    if (pend_hi > pend_lo && (rc = download(out + pend_lo, d_out + pend_lo, pend_hi - pend_lo, g.cs_out, false))) return rc;
-    HIPCHK(hipStreamSynchronize(g.cs_out));
-    return ZES_OK;
-  }
-  if (alloc) {  // the caller allocates the exact result now that its size is known (or: the early estimate fell short)
-    HIPCHK(hipStreamSynchronize(g.cs_out));
+  if (alloc && !(early && out && total <= cap)) {  // the caller allocates the exact result now that its size is known (or: the early estimate fell short)
+    if ((rc = pipe.drain())) return rc;
     const double ta = dbgp ? tnow() : 0;
     out = alloc(user, 0, total);
     if (!out) return ZES_E_ARG;
@@ -3351,13 +3376,8 @@ static int inflate_host_pipelined(const uint8_t* in, uint64_t c, uint8_t* out, u
     if (dbgp) fprintf(stderr, "zes pipe: alloc %.3f ms, download %.3f ms\n", tb - ta, tnow() - tb);
     return rc;
   }
-  if (total > cap) {
-    HIPCHK(hipStreamSynchronize(g.cs_out));
-    return ZES_E_NOSPACE;
-  }
-  if (pend_hi > pend_lo && (rc = download(out + pend_lo, d_out + pend_lo, pend_hi - pend_lo, g.cs_out, false))) return rc;
-  HIPCHK(hipStreamSynchronize(g.cs_out));
-  return ZES_OK;
+  if (total > cap) return (rc = pipe.drain()) ? rc : ZES_E_NOSPACE;
+  return pipe.drain(out, d_out, pend_lo, pend_hi);  // what is left to go down is the last piece (with an early estimate: it held)
 }
 
 static int inflate_host(const uint8_t* in, uint64_t c, uint8_t* out, uint64_t cap, uint64_t* out_len, uint32_t flags,
@@ -3406,6 +3426,8 @@ int zes_inflate_alloc(const uint8_t* in, uint64_t c, zes_alloc_fn alloc, void* u
 }
 
 // ---- batch over host pointers: one arena up, the device batch, results down ----
+// a buffer's slot in the arena that goes up: its bytes and 64 of slack behind them (as stage_in leaves), to a 16-byte boundary
+static uint64_t arena_slot(uint64_t len) { return (len + 64 + 15) & ~15ull; }
 static int deflate_batch_one(const uint8_t* const* in, const uint64_t* in_len, uint8_t* const* out, const uint64_t* out_cap,
                              uint64_t* out_len, int32_t* status, uint32_t count) {
   LOCK_READY();
@@ -3414,7 +3436,7 @@ static int deflate_batch_one(const uint8_t* const* in, const uint64_t* in_len, u
   for (uint32_t i = 0; i < count; i++) {
     if (!in[i] && in_len[i]) return ZES_E_ARG;
     in_off[i] = tin;
-    tin += (in_len[i] + 64 + 15) & ~15ull;
+    tin += arena_slot(in_len[i]);
     o_off[i] = tout;
     o_cap[i] = deflate_bound(in_len[i]);
     tout += (o_cap[i] + 15) & ~15ull;
@@ -3447,7 +3469,7 @@ static int inflate_batch_alloc_one(const uint8_t* const* in, const uint64_t* in_
   for (uint32_t i = 0; i < count; i++) {
     if (!in[i] && in_len[i]) return ZES_E_ARG;
     in_off[i] = tin;
-    tin += (in_len[i] + 64 + 15) & ~15ull;
+    tin += arena_slot(in_len[i]);
     firsts[i] = in_len[i] ? in[i][0] : 0;
     // first guess at the result size: a reference-made stream of c bytes rarely inflates beyond 4c; the retry below has exact sizes
     o_cap[i] = std::max<uint64_t>(in_len[i] * 4, 1 << 16);
@@ -3641,17 +3663,12 @@ int zes_deflate_range_dev(const uint8_t* d_in, uint64_t n, uint64_t n_readable, 
   if ((n % ZES_BLK) == 1) return ZES_E_CORRUPT;         // the reference throws on a 1-byte last block
   if ((((uintptr_t)d_in) & 15u) || (((uintptr_t)d_out) & 15u)) return ZES_E_ARG;
   LOCK_READY();
-  uint64_t zero = 0, bits = 0;
-  int32_t st = 0;
-  uint32_t fl = ZES_BUF_RANGE | (final_range ? 0u : ZES_BUF_NOTFINAL), ad = 1;
-  rc = deflate_batch_core(d_in, &zero, &n, d_out, &zero, &cap, &bits, &st, 1, &n_readable, &fl, &ad);
+  uint64_t bits = 0;
+  DeflateRange range{n_readable, ZES_BUF_RANGE | (final_range ? 0u : ZES_BUF_NOTFINAL)};
+  rc = deflate_one(d_in, 0, n, d_out, 0, cap, &bits, &range);
+  if (rc == ZES_OK || rc == ZES_E_NOSPACE) *out_bits = bits;  // (NOSPACE: the capacity needed, in bytes)
   if (rc) return rc;
-  if (st) {
-    if (st == ZES_E_NOSPACE) *out_bits = bits;  // (the capacity needed, in bytes)
-    return st;
-  }
-  *out_bits = bits;
-  if (adler) *adler = ad;
+  if (adler) *adler = range.adler;
   return ZES_OK;
 }
 
@@ -3661,14 +3678,11 @@ int zes_deflate_join_dev(const uint8_t* const* d_piece, const uint64_t* piece_bi
   if (!d_piece || !piece_bits || !piece_adler || !piece_len || !d_out || !out_len || count == 0) return ZES_E_ARG;
   if (((uintptr_t)d_out) & 15u) return ZES_E_ARG;
   uint64_t bits = 0;
-  // Adler-32 of the concatenation (src/adler32.ts:1-10): s1 adds up; a piece's s2 also sees len * (s1 so far - 1)
-  uint64_t s1 = 1, s2 = 0;
+  AdlerJoin adler;
   for (uint32_t i = 0; i < count; i++) {
     if (piece_bits[i] && (!d_piece[i] || (((uintptr_t)d_piece[i]) & 3u))) return ZES_E_ARG;
     bits += piece_bits[i];
-    const uint64_t a1 = piece_adler[i] & 0xFFFFu, a2 = piece_adler[i] >> 16;
-    s2 = (s2 + a2 + (piece_len[i] % 65521u) * ((s1 + 65520u) % 65521u)) % 65521u;
-    s1 = (s1 + a1 + 65520u) % 65521u;
+    adler.add(piece_adler[i], piece_len[i]);
   }
   const uint64_t raw_end = 2 + (bits + 7) / 8, total = raw_end + 4;
   *out_len = total;
@@ -3690,8 +3704,7 @@ int zes_deflate_join_dev(const uint8_t* const* d_piece, const uint64_t* piece_bi
   uint8_t *head = g.pinned->head, *tail = g.pinned->tail;
   head[0] = 0x78;  // src/zlib.ts:29-34
   head[1] = 0x9C;
-  const uint32_t ad = (uint32_t)((s2 << 16) | s1);
-  for (int k = 0; k < 4; k++) tail[k] = (uint8_t)(ad >> (24 - 8 * k));  // big-endian trailer (src/zlib.ts:37-40)
+  put_be32(tail, adler.value());
   HIPCHK(hipMemcpyAsync(d_out, head, 2, hipMemcpyHostToDevice, g.stream));
   HIPCHK(hipMemcpyAsync(d_out + raw_end, tail, 4, hipMemcpyHostToDevice, g.stream));
   HIPCHK(hipStreamSynchronize(g.stream));
@@ -3786,11 +3799,8 @@ static int deflate_raw_common(const uint8_t* d_in, uint64_t n, uint64_t* raw_len
   const uint64_t bound = deflate_bound(n);
   int rc;
   if ((rc = ensure(g.st_out, bound + 64))) return rc;
-  uint64_t zero = 0, dl = 0;
-  int32_t st = 0;
-  rc = deflate_batch_core(d_in, &zero, &n, (uint8_t*)g.st_out.p, &zero, &bound, &dl, &st, 1);
-  if (rc) return rc;
-  if (st) return st;
+  uint64_t dl = 0;
+  if ((rc = deflate_one(d_in, 0, n, (uint8_t*)g.st_out.p, 0, bound, &dl))) return rc;
   *raw_len = dl - 6;  // without 78 9C and the Adler-32 trailer (src/zlib.ts:28-46)
   return ZES_OK;
 }
