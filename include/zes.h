@@ -44,8 +44,11 @@ typedef enum zes_status {
                                zes_zip_read*: an entry's size, stream end or CRC-32 is not what its directory record says */
   ZES_E_ZIP = -22,          /* zes_zip_*: not a ZIP archive this reader accepts, or an entry whose local header or sizes do not fit its
                                directory record */
-  ZES_E_UNSUPPORTED = -23   /* zes_zip_*: a valid archive or entry that uses something this reader does not implement: ZIP64, several
-                               disks, encryption, a method other than 0 (stored) or 8 (DEFLATE) */
+  ZES_E_UNSUPPORTED = -23,  /* zes_zip_*: a valid archive or entry that uses something this reader does not implement: ZIP64, several
+                               disks, encryption, a method other than 0 (stored) or 8 (DEFLATE); zes_png_*: a valid file with a
+                               critical chunk this reader does not know, filtered data of more than 0xFFFFFFFF bytes, or (the
+                               decode calls) Adam7 interlace */
+  ZES_E_PNG = -24           /* zes_png_*: not a PNG file this reader accepts, or image data that does not fit its header */
 } zes_status;
 
 /* Geometry of the reference format (src/const.ts:7). */
@@ -432,6 +435,85 @@ int zes_zipwrite_dev(const uint8_t* d_in, const uint64_t* in_off, const uint64_t
                      uint32_t count, uint8_t* d_out, uint64_t cap, uint64_t* out_len, zes_zip_entry* ent, uint32_t flags);
 int zes_zipwrite(const uint8_t* const* in, const uint64_t* in_len, const uint8_t* names, const uint16_t* name_len, uint32_t count,
                  uint8_t* out, uint64_t cap, uint64_t* out_len, zes_zip_entry* ent, uint32_t flags);
+
+/* PNG images (PNG specification, second edition): the header of a file, and batch decoding of files to their scanlines.
+ * The reader undoes the container, the zlib stream and the scanline filters and nothing else: samples stay as stored (16-bit
+ * big-endian, sub-byte samples packed, palette indices as indices).  No Adam7 interlace, no APNG, no writer.
+ *
+ * zes_png_info: what a decode call works from.  All values are little-endian host values; pad fields are 0.
+ * The file rule.  A file in[0, c) is judged chunk by chunk from byte 8; the first failure in file order decides:
+ *   signature   c >= 8 and the bytes are 89 50 4e 47 0d 0a 1a 0a, else ZES_E_PNG
+ *   chunk chain chunks start at byte 8: a big-endian length L <= 0x7fffffff, four type bytes that are all ASCII letters, L data
+ *               bytes and 4 CRC bytes, all inside [0, c); the chain must reach an IEND; else ZES_E_PNG
+ *   IHDR        the first chunk, L == 13; width and height in 1 .. 2^31 - 1; (colour, depth) one of 0:{1,2,4,8,16}, 2:{8,16},
+ *               3:{1,2,4,8}, 4:{8,16}, 6:{8,16}; compression 0, filter 0, interlace 0 or 1; a second IHDR; else ZES_E_PNG
+ *   IDAT        at least one (decided at IEND), all of them consecutive; colour type 3 needs a PLTE in front of the first
+ *               one (decided there); else ZES_E_PNG
+ *   PLTE        at most once, in front of the IDATs, L % 3 == 0 and 3 <= L <= 768, else ZES_E_PNG
+ *   IEND        L == 0 and its CRC field ends exactly at byte c, else ZES_E_PNG; the walk ends here
+ *   others      any other chunk whose type starts with an upper-case letter (a critical chunk): ZES_E_UNSUPPORTED; ancillary
+ *               chunks are passed over (tRNS is noted when it stands in front of the first IDAT: the first such one)
+ *   size        behind a sound chain: the filtered size F = height * (1 + rowbytes) > 0xFFFFFFFF is ZES_E_UNSUPPORTED
+ * zes_png_info_get applies the rule to the caller's memory on the host and touches no device, so it checks no CRC.  It
+ * answers ZES_OK for an interlaced file and reports the method (as zes_zip_index lists entries it cannot extract); the
+ * decode calls answer ZES_E_UNSUPPORTED for one.  With a status the record is all zeros.  ZES_E_ARG: a null info, a null in
+ * with c != 0, any flag bit.
+ * replaces: nothing (the reference has no PNG container) */
+typedef struct zes_png_info {   /* 72 bytes */
+  uint32_t width, height;
+  uint8_t depth, colour, interlace, channels;   /* channels: 1, 2, 3 or 4 samples a pixel (a palette index is one) */
+  uint8_t bpp;          /* the filter unit: max(1, channels * depth / 8) */
+  uint8_t pad[3];
+  uint64_t rowbytes;    /* ceil(width * channels * depth / 8) */
+  uint64_t out_size;    /* height * rowbytes */
+  uint32_t idat_count;  /* IDAT chunks ... */
+  uint32_t plte_len;    /* PLTE's data bytes (0: none) */
+  uint64_t idat_bytes;  /* ... and their data bytes in all: the zlib stream */
+  uint64_t plte_pos;    /* PLTE's data in the file (0: none) */
+  uint64_t trns_pos;    /* the data of a tRNS in front of the first IDAT (0: none) ... */
+  uint32_t trns_len;    /* ... and its length */
+  uint32_t pad2;
+} zes_png_info;
+int zes_png_info_get(const uint8_t* in, uint64_t c, zes_png_info* info, uint32_t flags);
+
+/* zes_png_decode*: `count` files decoded as one batch, file i the in_len[i] bytes at d_in + in_off[i] (in[i], alloc form).
+ * status[i] and out_len[i] are filled per image (out_len[i] = out_size on ZES_OK and on ZES_E_NOSPACE, else 0), and info[i]
+ * when info is not NULL (zeros for a file the rule rejects); the return value is non-zero only when the call as a whole could
+ * not run.  in_off, in_len, out_off, out_cap, out_len, status and info are host arrays.
+ *   ZES_E_ARG   a null array with count != 0, a null d_in / in[i] with a non-zero length, a null d_out while an image has
+ *               bytes to write, flag bits other than ZES_F_PIECES (passed on to the inflate tiers)
+ *   count == 0  ZES_OK, no device work; zes_last_kernel_times then reports no launch and zes_last_inflate_tier 0
+ * An image's status, decided in this order; an image with a status costs no later launch for itself:
+ *   1. the file rule above (device form: k_png_walk, one lane a file, which also lists every chunk; alloc form: the host's
+ *      function), then interlace 1: ZES_E_UNSUPPORTED, then (device form) out_cap[i] < out_size: ZES_E_NOSPACE.  A call whose
+ *      capacities are all 0 is the sizing pass and costs the walk alone.
+ *   2. chunk CRCs: one segmented CRC-32 launch over type and data of every chunk of every image still at ZES_OK; any
+ *      mismatch, ancillary chunks included, is ZES_E_CHECKSUM
+ *   3. the IDAT payloads gathered into one zlib stream an image (one segmented copy for the batch), all streams decoded in one
+ *      pass through the inflate tiers into scratch slots of F bytes, their Adler-32 trailers checked by one segmented
+ *      launch.  A stream that fails keeps its inflate status; a result that is not exactly F bytes, one that would outgrow
+ *      its slot included, is ZES_E_PNG; a wrong or missing Adler-32 is ZES_E_CHECKSUM; bytes behind the trailer inside the
+ *      IDATs are ignored
+ *   4. one k_png_unfilter launch for the batch writes the scanlines without their filter bytes.  A filter byte above 4 makes
+ *      the image ZES_E_PNG
+ * The device form writes image i to d_out + out_off[i] at any alignment: exactly out_size bytes for an image that checks out,
+ * and no byte outside the ranges [out_off[i], out_off[i] + out_size) of the images that reach step 4, which must not overlap;
+ * a failed image's range is unspecified (zes_zip_read_dev's contract).  d_in and every in_off may have any alignment.  The
+ * walk is launched at most twice (a file with more chunks than its share of the chunk table, 16 + in_len / 4096, makes it run
+ * once more with the exact sizes); there is no launch, copy or synchronisation per image.
+ * The alloc form walks the caller's memory with the host function, uploads the files that pass, runs the same steps on one
+ * context and calls alloc(user, i, out_size) once per image that checks out, never for one that fails (NULL from alloc: that
+ * image is ZES_E_ARG).
+ * Scratch grows with the batch, as it does for zes_zip_read_dev: the gathered streams, a slot of F bytes an image, the chunk
+ * table; the alloc form also holds the files and the results.
+ * Known limit: the filters of Up, Average and Paeth rows depend on the row above, so an image is unfiltered by one wave from
+ * each row of filter None or Sub that starts a band of 64 rows (and from row 0) to the next such row.  An image without such
+ * rows is unfiltered by a single wave: the design point is a batch of images, not one large image.
+ * replaces: nothing (the reference has no PNG container) */
+int zes_png_decode_dev(const uint8_t* d_in, const uint64_t* in_off, const uint64_t* in_len, uint32_t count, uint8_t* d_out,
+                       const uint64_t* out_off, const uint64_t* out_cap, uint64_t* out_len, int32_t* status, zes_png_info* info, uint32_t flags);
+int zes_png_decode_alloc(const uint8_t* const* in, const uint64_t* in_len, uint32_t count, zes_alloc_fn alloc, void* user, uint64_t* out_len,
+                         int32_t* status, zes_png_info* info, uint32_t flags);
 
 /* Adler-32 of a buffer (standard value as an unsigned 32-bit).
  * replaces: `calcAdler32` src/adler32.ts:1-10 (byte extraction at src/zlib.ts:37-40). */

@@ -45,6 +45,7 @@ ZES_E_GZIP = -20  # zes_gunzip*: not a valid gzip member (header, or a trailer c
 ZES_E_CHECKSUM = -21  # a trailer does not match: gzip CRC-32 / ISIZE / FHCRC, zlib Adler-32 under ZES_F_CHECK_ADLER
 ZES_E_ZIP = -22  # zes_zip_*: not a ZIP archive this reader accepts, or an entry whose local header or sizes do not fit its directory record
 ZES_E_UNSUPPORTED = -23  # zes_zip_*: ZIP64, several disks, encryption, a method other than 0 or 8
+ZES_E_PNG = -24  # zes_png_*: not a PNG file this reader accepts, or image data that does not fit its header
 ZES_F_GZIP_SERIAL = 32  # zes_gunzip*: the members one after the other even where they could go as one batch (testing aid)
 ZES_F_INDEX_WALK = 64  # zes_bgzf_index_dev: the members by k_gz_walk's serial chain instead of the parallel finder (testing aid, baseline)
 ZES_F_CHECK_ADLER = 16  # zes_inflate*, the batch forms included: the Adler-32 trailer behind the stream must be there and match
@@ -68,6 +69,12 @@ class ZesKTime(C.Structure):
 ZIP_ENTRY = np.dtype([("hdr_off", "<u8"), ("name_pos", "<u8"), ("csize", "<u4"), ("usize", "<u4"), ("crc", "<u4"), ("name_off", "<u4"),
                       ("name_len", "<u2"), ("method", "<u2"), ("flags", "<u2"), ("pad", "<u2")])
 assert ZIP_ENTRY.itemsize == 40
+
+# zes_png_info of include/zes.h: what the PNG reader says about one file
+PNG_INFO = np.dtype([("width", "<u4"), ("height", "<u4"), ("depth", "u1"), ("colour", "u1"), ("interlace", "u1"), ("channels", "u1"), ("bpp", "u1"),
+                     ("pad", "u1", (3,)), ("rowbytes", "<u8"), ("out_size", "<u8"), ("idat_count", "<u4"), ("plte_len", "<u4"), ("idat_bytes", "<u8"),
+                     ("plte_pos", "<u8"), ("trns_pos", "<u8"), ("trns_len", "<u4"), ("pad2", "<u4")])
+assert PNG_INFO.itemsize == 72
 
 ALLOC_FN = C.CFUNCTYPE(C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint64)  # zes_alloc_fn of include/zes.h
 
@@ -141,6 +148,10 @@ def lib():
         L.zes_zipwrite_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64, u64p, C.c_void_p,
                                        C.c_uint32]
         L.zes_zipwrite.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64, u64p, C.c_void_p, C.c_uint32]
+        L.zes_png_info_get.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32]
+        L.zes_png_decode_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                         C.c_void_p, C.c_uint32]
+        L.zes_png_decode_alloc.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, ALLOC_FN, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32]
         L.zes_gunzip_alloc.argtypes = [C.c_void_p, C.c_uint64, ALLOC_FN, C.c_void_p, u64p, C.c_uint32]
         L.zes_adler32.argtypes = [C.c_void_p, C.c_uint64, u32p]
         L.zes_adler32_dev.argtypes = [C.c_void_p, C.c_uint64, u32p]
@@ -600,6 +611,50 @@ def zip_write(entries, flags=0):
     return out[: n.value].copy(), (ent, [raw[int(e["name_off"]) : int(e["name_off"]) + int(e["name_len"])] for e in ent])
 
 
+def png_info(data):
+    """What the PNG reader says about a file (zes_png_info_get; no GPU needed): one PNG_INFO record — size, bit depth, colour
+    type, interlace method, the filter unit ``bpp``, ``rowbytes``, ``out_size`` and where the IDAT, PLTE and tRNS data lie.
+    ZlibEsError(ZES_E_PNG / ZES_E_UNSUPPORTED) for a file the reader does not accept; no CRC is checked here."""
+    a = _as_u8(data)
+    info = np.zeros(1, dtype=PNG_INFO)
+    rc = lib().zes_png_info_get(a.ctypes.data if a.size else None, a.size, info.ctypes.data, 0)
+    if rc:
+        _raise(rc)
+    return info[0]
+
+
+def png_decode_batch(buffers, flags=0):
+    """PNG files decoded as one batch (zes_png_decode_alloc): a list with one ``(info, scanlines)`` pair or one ZlibEsError
+    per file (not raised, as with zip_read).  ``scanlines`` is a uint8 array of ``height`` x ``rowbytes``: the samples as the
+    file stores them (16-bit big-endian, sub-byte samples packed, palette indices), the filters undone."""
+    arrs = [_as_u8(b) for b in buffers]
+    cnt = len(arrs)
+    got = {}
+
+    def alloc(_user, i, n):
+        got[i] = np.empty(max(int(n), 1), dtype=np.uint8)
+        return got[i].ctypes.data
+
+    ptrs = (C.c_void_p * max(cnt, 1))(*[a.ctypes.data if a.size else None for a in arrs])
+    ln = np.array([a.size for a in arrs], dtype=np.uint64)
+    out_len = np.zeros(max(cnt, 1), dtype=np.uint64)
+    status = np.zeros(max(cnt, 1), dtype=np.int32)
+    info = np.zeros(max(cnt, 1), dtype=PNG_INFO)
+    rc = lib().zes_png_decode_alloc(ptrs, _ptr(ln), cnt, ALLOC_FN(alloc), None, out_len.ctypes.data, status.ctypes.data, info.ctypes.data, flags)
+    if rc:
+        _raise(rc)
+    return [(info[i], got[i][: int(out_len[i])].reshape(int(info[i]["height"]), int(info[i]["rowbytes"]))) if status[i] == 0
+            else ZlibEsError(int(status[i]), strerror(int(status[i]))) for i in range(cnt)]
+
+
+def png_decode(data, flags=0):
+    """One PNG file decoded: ``(info, scanlines)`` as png_decode_batch gives them; a file that fails raises."""
+    got = png_decode_batch([data], flags)[0]
+    if isinstance(got, Exception):
+        raise got
+    return got
+
+
 def gunzip(data, flags=0):
     """gzip.decompress: every member, their outputs concatenated (zes_gunzip_alloc: one decode, an exact-size result)."""
     a = _as_u8(data)
@@ -858,6 +913,54 @@ def zip_write_tensor(d_in, in_off, in_len, names, out=None, flags=0):
     _raise_need(rc, n)
     raw = blob.tobytes()
     return out[: n.value], (ent, [raw[int(e["name_off"]) : int(e["name_off"]) + int(e["name_len"])] for e in ent])
+
+
+def png_decode_tensor(d_in, in_off, in_len, out=None, off=None, flags=0, cap=None):
+    """PNG files in a 1-D uint8 CUDA tensor decoded as one batch (zes_png_decode_dev): file i is
+    ``d_in[in_off[i] : in_off[i] + in_len[i]]``.  Returns ``(out, off, out_len, status, info)``: image i's scanlines are
+    ``out[off[i] : off[i] + out_len[i]]`` when ``status[i]`` is 0, and nothing else of ``out`` is written; ``info`` is a PNG_INFO
+    array.  ``d_in``, ``out`` and every offset may be any byte.  Without ``off`` a sizing pass (the chunk walk alone) comes
+    first and the images are packed at 16-byte boundaries from the start of ``out``, which is allocated when it is None.
+    ``cap``: the capacity of every image's place (default: up to the end of ``out``); an image that needs more is
+    ZES_E_NOSPACE with its ``out_len`` the size needed."""
+    import torch
+
+    assert d_in.is_cuda and d_in.dtype == torch.uint8 and d_in.is_contiguous()
+    ioff = np.ascontiguousarray(in_off, dtype=np.uint64)
+    ilen = np.ascontiguousarray(in_len, dtype=np.uint64)
+    cnt = ilen.size
+    assert ioff.ndim == 1 and ioff.shape == ilen.shape, "png_decode_tensor: one offset and one length per file"
+    assert all(int(o) + int(n) <= d_in.numel() for o, n in zip(ioff, ilen)), "png_decode_tensor: a file reaches beyond `d_in`"
+    torch.cuda.current_stream(d_in.device).synchronize()
+    out_len = np.zeros(max(cnt, 1), dtype=np.uint64)
+    status = np.zeros(max(cnt, 1), dtype=np.int32)
+    info = np.zeros(max(cnt, 1), dtype=PNG_INFO)
+    src = d_in.data_ptr() if d_in.numel() else None
+
+    def call(dst, o, c):
+        rc = lib().zes_png_decode_dev(src, _ptr(ioff), _ptr(ilen), cnt, dst, _ptr(o), _ptr(c), out_len.ctypes.data, status.ctypes.data,
+                                      info.ctypes.data, flags)
+        if rc:
+            _raise(rc)
+
+    if off is None:  # the sizes first, then packed at 16-byte boundaries
+        zeros = np.zeros(max(cnt, 1), dtype=np.uint64)
+        call(None, zeros, zeros)
+        sizes = (np.where(status[:cnt] == ZES_E_NOSPACE, out_len[:cnt], 0).astype(np.uint64) + np.uint64(15)) & ~np.uint64(15)
+        off = np.concatenate([np.zeros(1, dtype=np.uint64), np.cumsum(sizes, dtype=np.uint64)])[:cnt]
+        if out is None:
+            out = torch.empty(int(sizes.sum()), dtype=torch.uint8, device=d_in.device)
+        if cap is None:
+            cap = sizes
+    assert out is not None and out.is_cuda and out.dtype == torch.uint8 and out.is_contiguous()
+    off = np.ascontiguousarray(off, dtype=np.uint64)
+    assert off.size == cnt, "png_decode_tensor: one offset per file"
+    if cap is None:
+        cap = np.array([max(out.numel() - int(o), 0) for o in off], dtype=np.uint64)
+    cap = np.ascontiguousarray(cap, dtype=np.uint64)
+    assert cap.size == cnt and all(int(o) + int(c) <= out.numel() for o, c in zip(off, cap)), "png_decode_tensor: a place reaches beyond `out`"
+    call(out.data_ptr() if out.numel() else None, off, cap)
+    return out, off, [int(x) for x in out_len[:cnt]], [int(x) for x in status[:cnt]], info[:cnt]
 
 
 def _batch_call(fn, d_in, in_off, in_len, d_out, out_off, out_cap, *extra):

@@ -2909,6 +2909,7 @@ const char* zes_strerror(int status) {
     case ZES_E_CHECKSUM: return "zes: checksum mismatch";
     case ZES_E_ZIP: return "zes: not a valid ZIP archive or entry (end record, directory or local header)";
     case ZES_E_UNSUPPORTED: return "zes: unsupported ZIP feature (ZIP64, several disks, encryption, a method other than 0 or 8)";
+    case ZES_E_PNG: return "zes: not a valid PNG file (signature, chunk chain or header), or image data that does not fit its header";
     default: return "zes: unknown status";
   }
 }
@@ -5422,6 +5423,345 @@ int zes_zipwrite(const uint8_t* const* in, const uint64_t* in_len, const uint8_t
   if (total > cap) return ZES_E_NOSPACE;
   if ((rc = download(out, (const uint8_t*)g.gz_acc.p, total))) return rc;
   if (ent) memcpy(ent, z.data(), sizeof(zes_zip_entry) * (size_t)count);
+  return ZES_OK;
+}
+
+// ---- PNG images (include/zes.h: "PNG images"): the file rule, and batch decoding through it ----
+constexpr uint32_t PNG_IHDR = 0x49484452u, PNG_IDAT = 0x49444154u, PNG_PLTE = 0x504c5445u, PNG_IEND = 0x49454e44u, PNG_TRNS = 0x74524e53u;
+
+static uint32_t png_channels(uint32_t colour) { return colour == 2 ? 3u : colour == 4 ? 2u : colour == 6 ? 4u : 1u; }
+static uint64_t png_rowbytes(const ZesPngHead& h) { return ((uint64_t)h.width * (png_channels(h.colour) * h.depth) + 7) / 8; }
+
+// The file rule on p[0, c), stated once for the host forms (k_png_walk restates it for files in device memory): the verdict,
+// h filled as far as the walk got, and every chunk that passes the chain's tests handed to each().
+static int png_rule(const uint8_t* p, uint64_t c, ZesPngHead& h, const std::function<void(const ZesPngChunk&)>& each) {
+  memset(&h, 0, sizeof h);
+  static const uint8_t sig[8] = {0x89, 0x50, 0x4e, 0x47, 0x0d, 0x0a, 0x1a, 0x0a};
+  if (c < 8 || memcmp(p, sig, 8)) return ZES_E_PNG;
+  uint64_t pos = 8;
+  bool idat = false, closed = false, plte = false, trns = false;
+  const uint64_t steps = c / 12;  // a chunk takes 12 bytes at least
+  for (uint64_t s = 0; s < steps; s++) {
+    if (c - pos < 12) return ZES_E_PNG;  // (pos == c: the chain ends without IEND)
+    const uint32_t L = get_be32(p + pos), type = get_be32(p + pos + 4);
+    if (L > 0x7fffffffu) return ZES_E_PNG;
+    for (uint32_t b = 0; b < 4; b++) {
+      const uint32_t ch = (type >> (8 * b)) & 255u;
+      if (!((ch >= 'A' && ch <= 'Z') || (ch >= 'a' && ch <= 'z'))) return ZES_E_PNG;
+    }
+    if (L > c - pos - 12) return ZES_E_PNG;
+    const uint8_t* d = p + pos + 8;
+    each(ZesPngChunk{pos, L | (type == PNG_IDAT ? ZES_PNG_IDAT : 0u), get_be32(d + L)});
+    if (++h.nchunks == 1) {
+      if (type != PNG_IHDR || L != 13) return ZES_E_PNG;
+      h.width = get_be32(d);
+      h.height = get_be32(d + 4);
+      h.depth = d[8];
+      h.colour = d[9];
+      h.interlace = d[12];
+      if (h.width < 1 || h.width > 0x7fffffffu || h.height < 1 || h.height > 0x7fffffffu) return ZES_E_PNG;
+      const uint32_t dp = h.depth;
+      bool ok = false;
+      if (h.colour == 0) ok = dp == 1 || dp == 2 || dp == 4 || dp == 8 || dp == 16;
+      else if (h.colour == 3) ok = dp == 1 || dp == 2 || dp == 4 || dp == 8;
+      else if (h.colour == 2 || h.colour == 4 || h.colour == 6) ok = dp == 8 || dp == 16;
+      if (!ok || d[10] != 0 || d[11] != 0 || h.interlace > 1) return ZES_E_PNG;
+    } else if (type == PNG_IHDR) {
+      return ZES_E_PNG;
+    } else if (type == PNG_IDAT) {
+      if (closed || (h.colour == 3 && !plte)) return ZES_E_PNG;
+      idat = true;
+      h.idat_count++;
+      h.idat_bytes += L;
+    } else {
+      closed = idat;
+      if (type == PNG_PLTE) {
+        if (plte || idat || L % 3 || L < 3 || L > 768) return ZES_E_PNG;
+        plte = true;
+        h.plte_pos = pos + 8;
+        h.plte_len = L;
+      } else if (type == PNG_IEND) {
+        if (L != 0 || pos + 12 != c || !idat) return ZES_E_PNG;
+        return 1 + png_rowbytes(h) > 0xFFFFFFFFull / h.height ? ZES_E_UNSUPPORTED : ZES_OK;
+      } else if (!(type & 0x20000000u)) {
+        return ZES_E_UNSUPPORTED;  // a critical chunk this reader does not know
+      } else if (type == PNG_TRNS && !idat && !trns) {
+        trns = true;
+        h.trns_pos = pos + 8;
+        h.trns_len = L;
+      }
+    }
+    pos += 12ull + L;
+  }
+  return ZES_E_PNG;
+}
+
+// the caller's record of a file that passed the rule (h.status == ZES_OK); zeros for any other
+static void png_info_of(const ZesPngHead& h, zes_png_info* o) {
+  memset(o, 0, sizeof *o);
+  if (h.status != ZES_OK) return;
+  o->width = h.width, o->height = h.height;
+  o->depth = h.depth, o->colour = h.colour, o->interlace = h.interlace;
+  o->channels = (uint8_t)png_channels(h.colour);
+  o->bpp = (uint8_t)std::max<uint32_t>(1, o->channels * h.depth / 8);
+  o->rowbytes = png_rowbytes(h);
+  o->out_size = h.height * o->rowbytes;
+  o->idat_count = h.idat_count, o->idat_bytes = h.idat_bytes;
+  o->plte_pos = h.plte_pos, o->plte_len = h.plte_len;
+  o->trns_pos = h.trns_pos, o->trns_len = h.trns_len;
+}
+
+int zes_png_info_get(const uint8_t* in, uint64_t c, zes_png_info* info, uint32_t flags) {
+  if (!info || flags || (!in && c)) return ZES_E_ARG;
+  ZesPngHead h;
+  h.status = png_rule(in, c, h, [](const ZesPngChunk&) {});
+  png_info_of(h, info);
+  return h.status;
+}
+
+// One file of a png_decode_core batch: what the walk says about it, its chunks (when it passed the rule), where its first
+// byte lies in d_src and where its out_size bytes go in dst
+struct PngImg {
+  ZesPngHead h;
+  std::vector<ZesPngChunk> ch;
+  uint64_t src_at = 0, dst_off = 0;
+};
+
+// The share of the chunk table the first walk gives a file of n bytes: sized from the arguments alone
+static uint32_t png_tab_share(uint64_t n) { return (uint32_t)std::min<uint64_t>(n / 12, 16 + n / 4096); }
+
+// k_png_walk over the files d_src[in_off[i], + in_len[i]): heads and chunks of all of them into im.  The table goes through
+// g.gz_tab as files | heads | chunks; one launch and one read-back, and both once more with exact shares when a file that
+// passed the rule had more chunks than its share.
+static int png_walk_dev(const uint8_t* d_src, const uint64_t* in_off, const uint64_t* in_len, uint32_t count, std::vector<PngImg>& im) {
+  int rc;
+  std::vector<ZesPngFile> files(count);
+  for (uint32_t i = 0; i < count; i++) files[i] = ZesPngFile{in_off[i], in_len[i], 0u, png_tab_share(in_len[i])};
+  std::vector<uint8_t> back;
+  for (int round = 0; round < 2; round++) {
+    uint64_t total = 0;
+    for (ZesPngFile& f : files) {
+      if (total + f.tab_cap > 0xFFFFFFFFull) return ZES_E_ARG;
+      f.tab_base = (uint32_t)total;
+      total += f.tab_cap;
+    }
+    const size_t o_head = sizeof(ZesPngFile) * (size_t)count, o_tab = o_head + sizeof(ZesPngHead) * (size_t)count;
+    const size_t bytes = o_tab + sizeof(ZesPngChunk) * (size_t)total;
+    if ((rc = ensure(g.gz_tab, bytes))) return rc;
+    uint8_t* base = (uint8_t*)g.gz_tab.p;
+    HIPCHK(hipMemcpyAsync(base, files.data(), o_head, hipMemcpyHostToDevice, g.stream));
+    {
+      Timed t("k_png_walk");
+      hipLaunchKernelGGL(k_png_walk, dim3((count + 63) / 64), dim3(64), 0, g.stream, d_src, (const ZesPngFile*)base, count, (ZesPngHead*)(base + o_head),
+                         (ZesPngChunk*)(base + o_tab));
+    }
+    HIPCHK(hipGetLastError());
+    back.resize(bytes - o_head);
+    HIPCHK(hipMemcpyAsync(back.data(), base + o_head, bytes - o_head, hipMemcpyDeviceToHost, g.stream));
+    HIPCHK(hipStreamSynchronize(g.stream));
+    const ZesPngHead* heads = (const ZesPngHead*)back.data();
+    bool again = false;
+    for (uint32_t i = 0; i < count; i++) {
+      again = again || (heads[i].status == ZES_OK && heads[i].nchunks > files[i].tab_cap);
+      files[i].tab_cap = heads[i].status == ZES_OK ? heads[i].nchunks : 0u;
+    }
+    if (!again) {
+      const ZesPngChunk* tab = (const ZesPngChunk*)(back.data() + (o_tab - o_head));
+      for (uint32_t i = 0; i < count; i++) {
+        im[i].h = heads[i];
+        if (heads[i].status == ZES_OK) im[i].ch.assign(tab + files[i].tab_base, tab + files[i].tab_base + heads[i].nchunks);
+      }
+      return ZES_OK;
+    }
+  }
+  return ZES_E_DEVICE;  // (the second launch counts what the first one counted)
+}
+
+// The images of im whose status[k] is ZES_OK on entry (rule, interlace and capacity have passed them): steps 2 to 4 of
+// include/zes.h, every step one launch sequence for the batch.  status[k] becomes the image's status.
+static int png_decode_core(const uint8_t* d_src, const std::vector<PngImg>& im, uint8_t* dst, int32_t* status, uint32_t flags) {
+  int rc;
+  g.last_tier = 0;
+  const uint32_t n = (uint32_t)im.size();
+  // 2. chunk CRCs: type and data of every chunk
+  {
+    std::vector<ZesCrcSeg> segs;
+    for (uint32_t k = 0; k < n; k++)
+      if (status[k] == ZES_OK)
+        for (const ZesPngChunk& c : im[k].ch) segs.push_back(ZesCrcSeg{im[k].src_at + c.pos + 4, 4ull + (c.len & ~ZES_PNG_IDAT)});
+    if (segs.size() > 0x7fffffffull) return ZES_E_ARG;
+    std::vector<uint32_t> crc(segs.size());
+    if (!segs.empty() && (rc = crc32_batch_locked(d_src, segs.data(), (uint32_t)segs.size(), crc.data()))) return rc;
+    size_t q = 0;
+    for (uint32_t k = 0; k < n; k++)
+      if (status[k] == ZES_OK)
+        for (const ZesPngChunk& c : im[k].ch)
+          if (crc[q++] != c.crc) status[k] = ZES_E_CHECKSUM;
+  }
+  // 3. the zlib streams: gathered, decoded, their lengths and trailers checked
+  std::vector<uint32_t> who;
+  std::vector<InfJob> jobs;
+  std::vector<ZesGzSeg> segs;
+  std::vector<uint64_t> filtered;
+  uint64_t ipos = 0, opos = 0;
+  for (uint32_t k = 0; k < n; k++) {
+    if (status[k] != ZES_OK) continue;
+    const ZesPngHead& h = im[k].h;
+    const uint64_t F = h.height * (1 + png_rowbytes(h));
+    uint64_t at = ipos;
+    for (const ZesPngChunk& c : im[k].ch)
+      if ((c.len & ZES_PNG_IDAT) && (c.len & ~ZES_PNG_IDAT)) {
+        segs.push_back(ZesGzSeg{im[k].src_at + c.pos + 8, at, c.len & ~ZES_PNG_IDAT, 0u, 0u});
+        at += c.len & ~ZES_PNG_IDAT;
+      }
+    InfJob j{ipos, h.idat_bytes, opos, gz_slot_cap(F), 0, ZES_OK, 0};
+    j.want_end = true;
+    jobs.push_back(j);
+    who.push_back(k);
+    filtered.push_back(F);
+    ipos += gz_slot_in(h.idat_bytes);
+    opos += gz_slot_out(F);
+  }
+  if (jobs.empty()) return ZES_OK;
+  if ((rc = ensure(g.gz_bodies, ipos + 64)) || (rc = ensure(g.gz_outs, opos + 64))) return rc;
+  if ((rc = gz_gather(d_src, (uint8_t*)g.gz_bodies.p, segs))) return rc;
+  if ((rc = inflate_jobs((const uint8_t*)g.gz_bodies.p, (uint8_t*)g.gz_outs.p, jobs, nullptr, flags & ZES_F_PIECES))) return rc;
+  for (size_t q = 0; q < jobs.size(); q++)
+    if (jobs[q].status == ZES_E_NOSPACE || (jobs[q].status == ZES_OK && jobs[q].out_len != filtered[q])) jobs[q].status = ZES_E_PNG;
+  if ((rc = check_adler_jobs((const uint8_t*)g.gz_bodies.p, nullptr, (const uint8_t*)g.gz_outs.p, jobs))) return rc;
+  keep_times();
+  // 4. the filters
+  std::vector<ZesPngJob> uj;
+  std::vector<uint32_t> uw;
+  uint64_t bands = 0;
+  for (size_t q = 0; q < jobs.size(); q++) {
+    const uint32_t k = who[q];
+    status[k] = jobs[q].status;
+    if (status[k] != ZES_OK) continue;
+    const ZesPngHead& h = im[k].h;
+    const uint32_t depth_bits = png_channels(h.colour) * h.depth;
+    uj.push_back(ZesPngJob{jobs[q].out_off, im[k].dst_off, h.height, (uint32_t)png_rowbytes(h), std::max<uint32_t>(1, depth_bits / 8), (uint32_t)bands});
+    uw.push_back(k);
+    bands += (h.height + ZES_PNG_BAND - 1) / ZES_PNG_BAND;
+    if (bands > 0x7fffffffull) return ZES_E_ARG;
+  }
+  if (uj.empty()) return ZES_OK;
+  const size_t o_bad = sizeof(ZesPngJob) * uj.size();
+  if ((rc = ensure(g.gz_tab, o_bad + 4 * uj.size()))) return rc;
+  uint32_t* d_bad = (uint32_t*)((uint8_t*)g.gz_tab.p + o_bad);
+  HIPCHK(hipMemcpyAsync(g.gz_tab.p, uj.data(), o_bad, hipMemcpyHostToDevice, g.stream));
+  HIPCHK(hipMemsetAsync(d_bad, 0, 4 * uj.size(), g.stream));
+  {
+    Timed t("k_png_unfilter");
+    constexpr uint32_t per = ZES_PNG_UNF_THREADS / 64u;
+    hipLaunchKernelGGL(k_png_unfilter, dim3((uint32_t)((bands + per - 1) / per)), dim3(ZES_PNG_UNF_THREADS), 0, g.stream, (const uint8_t*)g.gz_outs.p, dst,
+                       (const ZesPngJob*)g.gz_tab.p, (uint32_t)uj.size(), (uint32_t)bands, d_bad);
+  }
+  HIPCHK(hipGetLastError());
+  std::vector<uint32_t> bad(uj.size());
+  HIPCHK(hipMemcpyAsync(bad.data(), d_bad, 4 * uj.size(), hipMemcpyDeviceToHost, g.stream));
+  HIPCHK(hipStreamSynchronize(g.stream));
+  for (size_t q = 0; q < uj.size(); q++)
+    if (bad[q]) status[uw[q]] = ZES_E_PNG;
+  return ZES_OK;
+}
+
+// zes_png_decode*: what both forms check before anything else
+static int png_decode_args(bool arrays, const uint64_t* out_len, const int32_t* status, uint32_t count, uint32_t flags) {
+  if (flags & ~ZES_F_PIECES) return ZES_E_ARG;
+  if (count && (!arrays || !out_len || !status)) return ZES_E_ARG;
+  return ZES_OK;
+}
+
+// Step 1 behind the walk, for image i: the rule's verdict, then interlace; the caller's records filled
+static void png_judge(const PngImg& m, uint32_t i, uint64_t* out_len, int32_t* status, zes_png_info* info, zes_png_info* mine) {
+  png_info_of(m.h, mine);
+  if (info) info[i] = *mine;
+  out_len[i] = 0;
+  status[i] = m.h.status != ZES_OK ? m.h.status : m.h.interlace ? ZES_E_UNSUPPORTED : ZES_OK;
+}
+
+int zes_png_decode_dev(const uint8_t* d_in, const uint64_t* in_off, const uint64_t* in_len, uint32_t count, uint8_t* d_out, const uint64_t* out_off,
+                       const uint64_t* out_cap, uint64_t* out_len, int32_t* status, zes_png_info* info, uint32_t flags) {
+  ROUTE_DEV(d_in, d_out);
+  if (const int arc = png_decode_args(in_off && in_len && out_off && out_cap, out_len, status, count, flags)) return arc;
+  for (uint32_t i = 0; i < count; i++)
+    if (in_len[i] && !d_in) return ZES_E_ARG;
+  if (!count) {
+    zip_read_none();
+    return ZES_OK;
+  }
+  LOCK_READY();
+  std::vector<PngImg> im(count);
+  if ((rc = png_walk_dev(d_in, in_off, in_len, count, im))) return call_done(rc, true);
+  bool null_out = false;
+  for (uint32_t i = 0; i < count; i++) {
+    zes_png_info mine;
+    png_judge(im[i], i, out_len, status, info, &mine);
+    im[i].src_at = in_off[i];
+    im[i].dst_off = out_off[i];
+    if (status[i] != ZES_OK) continue;
+    out_len[i] = mine.out_size;
+    if (out_cap[i] < mine.out_size) status[i] = ZES_E_NOSPACE;
+    else null_out = null_out || !d_out;
+  }
+  if (null_out) return call_done(ZES_E_ARG, true);
+  if ((rc = call_done(png_decode_core(d_in, im, d_out, status, flags), true))) return rc;
+  for (uint32_t i = 0; i < count; i++)
+    if (status[i] != ZES_OK && status[i] != ZES_E_NOSPACE) out_len[i] = 0;
+  return ZES_OK;
+}
+
+int zes_png_decode_alloc(const uint8_t* const* in, const uint64_t* in_len, uint32_t count, zes_alloc_fn alloc, void* user, uint64_t* out_len,
+                         int32_t* status, zes_png_info* info, uint32_t flags) {
+  UseDev ud(route_host());
+  if (const int arc = png_decode_args(in && in_len, out_len, status, count, flags)) return arc;
+  if (!alloc) return ZES_E_ARG;
+  for (uint32_t i = 0; i < count; i++)
+    if (in_len[i] && !in[i]) return ZES_E_ARG;
+  if (!count) {
+    zip_read_none();
+    return ZES_OK;
+  }
+  // the rule on the caller's memory: a batch in which no file passes touches no device
+  std::vector<PngImg> im(count);
+  std::vector<uint64_t> size(count, 0);
+  uint64_t tin = 0, tout = 0;
+  bool any = false;
+  for (uint32_t i = 0; i < count; i++) {
+    PngImg& m = im[i];
+    m.h.status = png_rule(in[i], in_len[i], m.h, [&](const ZesPngChunk& c) { m.ch.push_back(c); });
+    zes_png_info mine;
+    png_judge(m, i, out_len, status, info, &mine);
+    if (status[i] != ZES_OK) continue;
+    any = true;
+    size[i] = mine.out_size;
+    m.src_at = tin;
+    m.dst_off = tout;
+    tin += gz_up16(in_len[i]) + 16;
+    tout += gz_up16(mine.out_size) + 16;
+  }
+  if (!any) {
+    zip_read_none();
+    return ZES_OK;
+  }
+  LOCK_READY();
+  if ((rc = ensure(g.gz_in, tin + 64)) || (rc = ensure(g.gz_acc, tout + 64))) return rc;
+  for (uint32_t i = 0; i < count; i++)
+    if (status[i] == ZES_OK && (rc = upload((uint8_t*)g.gz_in.p + im[i].src_at, in[i], in_len[i]))) return rc;
+  if ((rc = call_done(png_decode_core((const uint8_t*)g.gz_in.p, im, (uint8_t*)g.gz_acc.p, status, flags), true))) return rc;
+  for (uint32_t i = 0; i < count; i++) {
+    if (status[i] != ZES_OK) continue;
+    uint8_t* to = alloc(user, i, size[i]);
+    if (!to) {
+      status[i] = ZES_E_ARG;
+      continue;
+    }
+    // (a short result is only enqueued: one synchronisation behind the loop serves them all)
+    if ((rc = download(to, (const uint8_t*)g.gz_acc.p + im[i].dst_off, size[i], nullptr, false))) return rc;
+    out_len[i] = size[i];
+  }
+  HIPCHK(hipStreamSynchronize(g.stream));
   return ZES_OK;
 }
 

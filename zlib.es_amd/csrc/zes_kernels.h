@@ -218,6 +218,38 @@ struct ZesZipPackRec {
   uint32_t pad2;
 };
 #define ZES_ZIP_PACK_SHARES 1024u  // workgroups that share one entry's body, at most (a share is whole 64 KiB pieces)
+// k_png_walk (zes_png.hip): one PNG file of a batch, and its share [tab_base, + tab_cap) of the chunk table
+struct ZesPngFile {
+  uint64_t in_off, in_len;
+  uint32_t tab_base, tab_cap;
+};
+// what the walk found in one file (the host's png_rule fills the same record): the IHDR fields, the counts, and the verdict
+// of the file rule (include/zes.h, "The file rule").  Positions are relative to the file's first byte
+struct ZesPngHead {
+  int32_t status;       // ZES_OK, ZES_E_PNG or ZES_E_UNSUPPORTED
+  uint32_t width, height;
+  uint8_t depth, colour, interlace, pad;
+  uint32_t nchunks;     // chunks the walk passed; those beyond tab_cap are counted and not stored
+  uint32_t idat_count;
+  uint32_t plte_len, trns_len;
+  uint64_t idat_bytes;
+  uint64_t plte_pos, trns_pos;  // the chunks' data (0 when absent)
+};
+struct ZesPngChunk {
+  uint64_t pos;    // the chunk's length field
+  uint32_t len;    // its data bytes | ZES_PNG_IDAT
+  uint32_t crc;    // the stored CRC field
+};
+#define ZES_PNG_IDAT 0x80000000u
+// k_png_unfilter (zes_png.hip): one image whose filtered scanlines stand in a scratch slot; its bands are the waves
+// [first_band, + ceil(height / 64)) of the launch
+struct ZesPngJob {
+  uint64_t src_off;   // the slot: height rows of 1 + rowbytes bytes
+  uint64_t dst_off;   // where the height * rowbytes result bytes go
+  uint32_t height, rowbytes, bpp, first_band;
+};
+#define ZES_PNG_BAND 64u          // rows of a band: a lane each
+#define ZES_PNG_UNF_THREADS 256u  // four independent waves to a workgroup
 
 // CRC-32 host arithmetic (zes_crc.hip): shift(s, k) = s * x^(8k) mod P; the kernel's table with npow powers
 uint32_t zes_crc_shift(uint32_t s, uint64_t k);
@@ -299,6 +331,9 @@ __global__ void k_gz_gather(const uint8_t*, uint8_t*, const ZesGzSeg*);
 __global__ void k_bgzf_pack(const uint8_t*, const uint8_t*, uint8_t*, const ZesBgzfRec*);
 __global__ void k_zip_stage(const uint8_t*, uint8_t*, uint8_t*, const ZesZipRec*, ZesZipVerdict*);
 __global__ void k_zip_pack(const uint8_t*, const uint8_t*, const uint8_t*, uint8_t*, const ZesZipPackRec*, uint32_t);
+// PNG reader (zes_png.hip)
+__global__ void k_png_walk(const uint8_t*, const ZesPngFile*, uint32_t, ZesPngHead*, ZesPngChunk*);
+__global__ void k_png_unfilter(const uint8_t*, uint8_t*, const ZesPngJob*, uint32_t, uint32_t, uint32_t*);
 __global__ void k_adler_blocks(const uint8_t*, const ZesBuf*, const ZesBlk*, unsigned long long*);
 __global__ void k_adler_seg(const uint8_t*, const ZesCrcSeg*, const uint2*, unsigned long long*);
 __global__ void k_layout(uint8_t*, const ZesBuf*, ZesBlk*, const unsigned long long*, ZesRes*);

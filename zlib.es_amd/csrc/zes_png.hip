@@ -1,0 +1,285 @@
+// zes_png.hip — device pieces of the PNG reader (zes_api.hip: png_decode_core; include/zes.h: "PNG images").
+//
+//   k_png_walk      one lane per file follows the chunk chain from byte 8 and judges the file by the file rule of
+//                   include/zes.h — the restatement of zes_api.hip's png_rule, which the host forms call.  It leaves a
+//                   ZesPngHead per file (the IHDR fields, the counts, where PLTE and tRNS lie, the verdict) and one
+//                   ZesPngChunk per chunk in the file's share of a table; chunks beyond the share are counted and not
+//                   stored, and the host then launches once more with the shares the first launch counted.  Bytes are read
+//                   one by one: a file and its chunks lie at any alignment, and the chain is serial anyway.
+//   k_png_unfilter  the scanline filters undone (PNG specification, 9.2), the batch in one launch.  Rows are cut into bands
+//                   of 64 and a wave is launched per (image, band).  A band is a restart when it is the image's first or
+//                   its first row's filter is None or Sub: such a row does not read the row above.  The wave of a restart
+//                   band decodes it and goes on through the bands behind it up to the next restart band or the image's
+//                   end; the wave of any other band reads that one filter byte and exits.  So every band has one owner,
+//                   found without a list, a queue, an atomic or a wait.
+//                   Inside a band lane j owns row r0 + j, one filter unit (bpp bytes) behind the lane above: at step t it
+//                   reconstructs unit t - j.  Left is its own last result; up is what lane j - 1 made one step ago, and
+//                   upper-left what it made two steps ago: one __shfl_up a step, the value of the step before kept in a
+//                   register.  Lane 0's row above is zeros for image row 0, and otherwise the last row of the band before,
+//                   which this same wave has stored: it reads it back from the output.
+//                   A lane reads its row (at any alignment in the slot: the stride is rowbytes + 1) as aligned dwords into
+//                   a shift register, the first one shifted past the bytes in front of the row — the slot is the call's own
+//                   scratch, padded on both sides, so a dword may reach over the row's ends.  It writes through a second
+//                   shift register: single bytes up to the output's first dword boundary, whole dwords from there, single
+//                   bytes for what is left at the row's end, so that no byte outside the row is written.
+#include "../../include/zes.h"
+#include "zes_common.h"
+#include "zes_kernels.h"
+
+#include <type_traits>
+
+namespace {
+__device__ __forceinline__ uint32_t png_be32(const uint8_t* p) { return (uint32_t)p[0] << 24 | (uint32_t)p[1] << 16 | (uint32_t)p[2] << 8 | (uint32_t)p[3]; }
+
+constexpr uint32_t PNG_IHDR = 0x49484452u, PNG_IDAT = 0x49444154u, PNG_PLTE = 0x504c5445u, PNG_IEND = 0x49454e44u, PNG_TRNS = 0x74524e53u;
+
+// The file rule on p[0, c): the verdict, h filled as far as the walk got.  (zes_api.hip: png_rule is the same, step by step.)
+__device__ int png_walk_file(const uint8_t* __restrict__ p, uint64_t c, ZesPngHead& h, ZesPngChunk* __restrict__ tab, uint32_t cap) {
+  if (c < 8 || png_be32(p) != 0x89504e47u || png_be32(p + 4) != 0x0d0a1a0au) return ZES_E_PNG;
+  uint64_t pos = 8;
+  uint32_t k = 0;
+  bool idat = false, closed = false, plte = false, trns = false;
+  const uint64_t steps = c / 12;  // a chunk takes 12 bytes at least
+  for (uint64_t s = 0; s < steps; s++) {
+    if (c - pos < 12) return ZES_E_PNG;  // (pos == c: the chain ends without IEND)
+    const uint32_t L = png_be32(p + pos), type = png_be32(p + pos + 4);
+    if (L > 0x7fffffffu) return ZES_E_PNG;
+    for (uint32_t b = 0; b < 4; b++)
+      if ((((type >> (8 * b)) & 0xDFu) - 'A') >= 26u || ((type >> (8 * b)) & 0x80u)) return ZES_E_PNG;
+    if (L > c - pos - 12) return ZES_E_PNG;
+    const uint8_t* d = p + pos + 8;
+    if (k < cap) {
+      ZesPngChunk r;
+      r.pos = pos;
+      r.len = L | (type == PNG_IDAT ? ZES_PNG_IDAT : 0u);
+      r.crc = png_be32(d + L);
+      tab[k] = r;
+    }
+    h.nchunks = ++k;
+    if (k == 1) {
+      if (type != PNG_IHDR || L != 13) return ZES_E_PNG;
+      h.width = png_be32(d);
+      h.height = png_be32(d + 4);
+      h.depth = d[8];
+      h.colour = d[9];
+      h.interlace = d[12];
+      if (h.width - 1 > 0x7ffffffeu || h.height - 1 > 0x7ffffffeu) return ZES_E_PNG;
+      const uint32_t dp = h.depth;
+      bool ok;
+      switch (h.colour) {
+        case 0: ok = dp == 1 || dp == 2 || dp == 4 || dp == 8 || dp == 16; break;
+        case 3: ok = dp == 1 || dp == 2 || dp == 4 || dp == 8; break;
+        case 2: case 4: case 6: ok = dp == 8 || dp == 16; break;
+        default: ok = false;
+      }
+      if (!ok || d[10] != 0 || d[11] != 0 || h.interlace > 1) return ZES_E_PNG;
+    } else if (type == PNG_IHDR) {
+      return ZES_E_PNG;
+    } else if (type == PNG_IDAT) {
+      if (closed || (h.colour == 3 && !plte)) return ZES_E_PNG;
+      idat = true;
+      h.idat_count++;
+      h.idat_bytes += L;
+    } else {
+      closed = idat;
+      if (type == PNG_PLTE) {
+        if (plte || idat || L % 3 || L < 3 || L > 768) return ZES_E_PNG;
+        plte = true;
+        h.plte_pos = pos + 8;
+        h.plte_len = L;
+      } else if (type == PNG_IEND) {
+        if (L != 0 || pos + 12 != c || !idat) return ZES_E_PNG;
+        const uint32_t ch = h.colour == 2 ? 3u : h.colour == 4 ? 2u : h.colour == 6 ? 4u : 1u;
+        const uint64_t rowbytes = ((uint64_t)h.width * (ch * h.depth) + 7) / 8;
+        return 1 + rowbytes > 0xFFFFFFFFull / h.height ? ZES_E_UNSUPPORTED : ZES_OK;
+      } else if (!(type & 0x20000000u)) {
+        return ZES_E_UNSUPPORTED;  // a critical chunk this reader does not know
+      } else if (type == PNG_TRNS && !idat && !trns) {
+        trns = true;
+        h.trns_pos = pos + 8;
+        h.trns_len = L;
+      }
+    }
+    pos += 12ull + L;
+  }
+  return ZES_E_PNG;
+}
+}  // namespace
+
+__global__ __launch_bounds__(64) void k_png_walk(const uint8_t* __restrict__ d_in, const ZesPngFile* __restrict__ files, uint32_t count,
+                                                ZesPngHead* __restrict__ heads, ZesPngChunk* __restrict__ tab) {
+  const uint32_t i = blockIdx.x * 64u + threadIdx.x;
+  if (i >= count) return;
+  const ZesPngFile f = files[i];
+  ZesPngHead h;
+  h.status = 0, h.width = h.height = 0, h.depth = h.colour = h.interlace = h.pad = 0;
+  h.nchunks = h.idat_count = h.plte_len = h.trns_len = 0;
+  h.idat_bytes = h.plte_pos = h.trns_pos = 0;
+  h.status = png_walk_file(d_in + f.in_off, f.in_len, h, tab + f.tab_base, f.tab_cap);
+  heads[i] = h;
+}
+
+namespace {
+// a filter unit in a register, and the shift registers that hold a row's bytes on their way in and out
+template <int BPP>
+struct PngUnit {
+  using T = typename std::conditional<(BPP <= 4), uint32_t, uint64_t>::type;
+  using W = typename std::conditional<(BPP <= 4), uint64_t, unsigned __int128>::type;
+  static constexpr T MASK = BPP == (int)sizeof(T) ? ~(T)0 : (((T)1 << (8 * (BPP % (int)sizeof(T)))) - 1);
+};
+
+// A row's bytes as aligned dwords: at most 3 + 4 bytes wait in front of a take of up to 4 (uint64_t), 7 + 4 in front of one
+// of 6 or 8 (128 bits).  The last dword read is the one that holds the row's last byte.
+template <int BPP>
+struct PngIn {
+  using U = PngUnit<BPP>;
+  const uint32_t* next;
+  typename U::W buf;
+  uint32_t avail;
+  __device__ __forceinline__ void open(const uint8_t* p) {
+    const uint32_t sh = (uint32_t)((uintptr_t)p & 3u);
+    next = reinterpret_cast<const uint32_t*>(p - sh);
+    buf = (typename U::W)(*next++ >> (8 * sh));
+    avail = 4 - sh;
+  }
+  __device__ __forceinline__ typename U::T take() {
+    while (avail < (uint32_t)BPP) {
+      buf |= (typename U::W)(*next++) << (8 * avail);
+      avail += 4;
+    }
+    const typename U::T v = (typename U::T)buf & U::MASK;
+    buf >>= 8 * BPP;
+    avail -= BPP;
+    return v;
+  }
+};
+
+// A row's results: bytes until the place is a dword boundary, dwords from there (at most 3 bytes wait behind a put), and
+// the bytes that are left at the row's end.  Only bytes of the row are ever stored.
+template <int BPP>
+struct PngOut {
+  using U = PngUnit<BPP>;
+  uint8_t* p;
+  typename U::W buf;
+  uint32_t n;
+  __device__ __forceinline__ void open(uint8_t* to) { p = to, buf = 0, n = 0; }
+  __device__ __forceinline__ void put(typename U::T v) {
+    buf |= (typename U::W)v << (8 * n);
+    n += BPP;
+    while (n) {
+      if (((uintptr_t)p & 3u) == 0) {
+        if (n < 4) break;
+        *reinterpret_cast<uint32_t*>(p) = (uint32_t)buf;
+        p += 4, buf >>= 32, n -= 4;
+      } else {
+        *p = (uint8_t)buf;
+        p += 1, buf >>= 8, n -= 1;
+      }
+    }
+  }
+  __device__ __forceinline__ void flush() {
+    for (; n; n--, buf >>= 8) *p++ = (uint8_t)buf;
+  }
+};
+
+// Recon(x) = Filt(x) + predictor, byte by byte (PNG specification, 9.2 and 9.4): a left, b up, c upper-left.  Every lane
+// computes every predictor it may need and selects by its own row's filter type, so rows of different types share the
+// steps; the Paeth arithmetic runs only when a row of the band asks for it.
+template <int BPP>
+__device__ __forceinline__ typename PngUnit<BPP>::T png_recon(typename PngUnit<BPP>::T raw, typename PngUnit<BPP>::T a, typename PngUnit<BPP>::T b,
+                                                               typename PngUnit<BPP>::T c, uint32_t ft, bool paeth) {
+  using T = typename PngUnit<BPP>::T;
+  T out = 0;
+#pragma unroll
+  for (int k = 0; k < BPP; k++) {
+    const int x = (int)((raw >> (8 * k)) & 255u), A = (int)((a >> (8 * k)) & 255u), B = (int)((b >> (8 * k)) & 255u), C = (int)((c >> (8 * k)) & 255u);
+    int pred = ft == 1 ? A : ft == 2 ? B : ft == 3 ? (A + B) >> 1 : 0;
+    if (paeth) {
+      const int pa = abs(B - C), pb = abs(A - C), pc = abs(A + B - 2 * C);
+      const int pp = (pa <= pb && pa <= pc) ? A : (pb <= pc ? B : C);  // ties: a, then b, then c
+      pred = ft == 4 ? pp : pred;
+    }
+    out |= (T)((uint32_t)(x + pred) & 255u) << (8 * k);
+  }
+  return out;
+}
+
+// One band: rows [r0, min(r0 + 64, height)), lane j the row r0 + j.  Called by a whole wave.
+template <int BPP>
+__device__ __forceinline__ void png_band(const uint8_t* __restrict__ src, uint8_t* dst, uint32_t r0, uint32_t height, uint32_t rowbytes, uint32_t lane,
+                                         uint32_t* __restrict__ bad) {
+  using T = typename PngUnit<BPP>::T;
+  const uint32_t npix = rowbytes / BPP;  // (rowbytes is a multiple of bpp: bpp is 1 below 8 bits a sample)
+  const uint32_t row = r0 + lane;
+  const bool live = row < height;
+  uint32_t ft = 0;
+  PngIn<BPP> in, up;
+  PngOut<BPP> out;
+  if (live) {
+    const uint8_t* s = src + (uint64_t)row * (rowbytes + 1ull);
+    ft = s[0];
+    in.open(s + 1);
+    out.open(dst + (uint64_t)row * rowbytes);
+  }
+  if (ft > 4) {  // not a filter type: the image is ZES_E_PNG, its range unspecified
+    *bad = 1u;
+    ft = 0;
+  }
+  // lane 0 of a restart band has filter None or Sub, or the image's row 0 above it: it reads no row (the last row of the
+  // band before is then another wave's, and may not be there yet)
+  const bool has_up = lane == 0 && r0 > 0 && ft >= 2;
+  if (has_up) up.open(dst + (uint64_t)(r0 - 1) * rowbytes);
+  const bool paeth = __ballot(ft == 4) != 0;
+  const uint32_t steps = npix + min(height - r0, ZES_PNG_BAND) - 1;
+  T res = 0, bl = 0;
+  for (uint32_t t = 0; t < steps; t++) {
+    T b = __shfl_up(res, 1);  // the lane above, one step ago: the unit above mine
+    if (lane == 0) b = 0;
+    const uint32_t pix = t - lane;
+    if (live && t >= lane && pix < npix) {
+      if (has_up) b = up.take();
+      res = png_recon<BPP>(in.take(), res, b, bl, ft, paeth);
+      out.put(res);
+    }
+    bl = b;  // the lane above, two steps ago by the next step: the unit above and to the left
+  }
+  if (live) out.flush();
+}
+}  // namespace
+
+__global__ __launch_bounds__(ZES_PNG_UNF_THREADS) void k_png_unfilter(const uint8_t* __restrict__ slots, uint8_t* dst, const ZesPngJob* __restrict__ jobs,
+                                                                    uint32_t njobs, uint32_t nbands, uint32_t* __restrict__ bad) {
+  const uint32_t lane = threadIdx.x & 63u;
+  const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(blockIdx.x * (ZES_PNG_UNF_THREADS / 64u) + threadIdx.x / 64u));
+  if (wave >= nbands) return;
+  uint32_t lo = 0, hi = njobs;  // the last image whose first band is not behind this one
+  while (hi - lo > 1) {
+    const uint32_t mid = (lo + hi) / 2;
+    if (jobs[mid].first_band <= wave) lo = mid;
+    else hi = mid;
+  }
+  const ZesPngJob j = jobs[lo];
+  const uint8_t* src = slots + j.src_off;
+  uint8_t* out = dst + j.dst_off;
+  const uint32_t nb = (j.height + ZES_PNG_BAND - 1) / ZES_PNG_BAND;
+  uint32_t band = wave - j.first_band;
+  auto restart = [&](uint32_t bnd) { return bnd == 0 || src[(uint64_t)bnd * ZES_PNG_BAND * (j.rowbytes + 1ull)] <= 1; };
+  if (!restart(band)) return;  // the wave of a restart band in front decodes this one
+  for (;;) {
+    const uint32_t r0 = band * ZES_PNG_BAND;
+    switch (j.bpp) {
+      case 1: png_band<1>(src, out, r0, j.height, j.rowbytes, lane, bad + lo); break;
+      case 2: png_band<2>(src, out, r0, j.height, j.rowbytes, lane, bad + lo); break;
+      case 3: png_band<3>(src, out, r0, j.height, j.rowbytes, lane, bad + lo); break;
+      case 4: png_band<4>(src, out, r0, j.height, j.rowbytes, lane, bad + lo); break;
+      case 6: png_band<6>(src, out, r0, j.height, j.rowbytes, lane, bad + lo); break;
+      default: png_band<8>(src, out, r0, j.height, j.rowbytes, lane, bad + lo); break;
+    }
+    if (++band >= nb || restart(band)) break;
+    // Lane 0 of the next band reads the row that lane 63 has just stored.  Writer and reader are lanes of one wave, so
+    // they sit on one compute unit and go through the same vector cache: a workgroup-scope fence makes the wave wait until
+    // its stores have left for that cache before a later load is issued, and keeps the compiler from moving either across
+    // it.  No other wave reads or writes these rows, so no wider scope is needed.
+    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
+  }
+}

@@ -1032,6 +1032,52 @@ napi_value ZipRead(napi_env env, napi_callback_info info) {
   return j.rc == 0 ? batch_results(env, &j) : throw_status(env, j.rc);
 }
 
+// ---- PNG images (include/zes.h: zes_png_info_get, zes_png_decode_alloc) ----
+// pngInfo(file): the file's zes_png_info record as 72 bytes; the façade makes the object.  The host form: no device is touched.
+napi_value PngInfo(napi_env env, napi_callback_info info) {
+  const Args a = get_args(env, info);
+  const Bytes in = need_bytes(env, a, 0, "pngInfo(file)", "file");
+  if (!in.ok) return nullptr;
+  zes_png_info rec;
+  const int rc = zes_png_info_get(in.p, in.n, &rec, ZES_F_DEFAULT);
+  if (rc) return throw_status(env, rc);
+  void* raw = nullptr;
+  napi_value v = new_u8(env, sizeof rec, &raw);
+  if (!v) return nullptr;
+  memcpy(raw, &rec, sizeof rec);
+  return v;
+}
+
+// pngDecodeBatch(files): the files decoded as one batch: { results, info } — per file the scanlines as a fresh Uint8Array or
+// the Error that says why not, as the batch forms answer, and the files' zes_png_info records back to back
+napi_value PngDecodeBatch(napi_env env, napi_callback_info info) {
+  static const char SIG[] = "pngDecodeBatch(files)";
+  const Args a = get_args(env, info);
+  bool is_arr = false;
+  uint32_t count = 0;
+  if (a.argc < 1 || napi_is_array(env, a.argv[0], &is_arr) != napi_ok || !is_arr || napi_get_array_length(env, a.argv[0], &count) != napi_ok)
+    return throw_type(env, std::string(SIG) + ": files must be an array of Uint8Array");
+  BatchJob j(count);
+  for (uint32_t i = 0; i < count; i++) {
+    napi_value e;
+    size_t n = 0;
+    if (napi_get_element(env, a.argv[0], i, &e) != napi_ok || !get_bytes(env, e, &j.in[i], &n))
+      return throw_type(env, std::string(SIG) + ": every element must be a Uint8Array");
+    j.in_len[i] = n;
+  }
+  std::vector<zes_png_info> recs((size_t)count + 1);
+  j.rc = zes_png_decode_alloc(j.in.data(), j.in_len.data(), count, batch_alloc, &j, j.out_len.data(), j.status.data(), recs.data(), ZES_F_DEFAULT);
+  if (j.rc) return throw_status(env, j.rc);
+  void* raw = nullptr;
+  napi_value res, vres = batch_results(env, &j), vinfo = new_u8(env, (size_t)count * sizeof(zes_png_info), &raw);
+  if (!vres || !vinfo) return nullptr;
+  if (count) memcpy(raw, recs.data(), (size_t)count * sizeof(zes_png_info));
+  if (napi_create_object(env, &res) != napi_ok) return nullptr;
+  napi_set_named_property(env, res, "results", vres);
+  napi_set_named_property(env, res, "info", vinfo);
+  return res;
+}
+
 // zip(names, datas): a ZIP archive of datas[i] under names[i], two arrays of Uint8Array of one length (the façade takes the
 // file objects apart and encodes string names): one call, the bounded result (include/zes.h: zes_zipwrite)
 napi_value Zip(napi_env env, napi_callback_info info) {
@@ -1111,6 +1157,8 @@ napi_value ModuleInit(napi_env env, napi_value exports) {
       {"zipIndex", swept<ZipIndex>},
       {"zipRead", swept<ZipRead>},
       {"zip", swept<Zip>},
+      {"pngInfo", swept<PngInfo>},
+      {"pngDecodeBatch", swept<PngDecodeBatch>},
       {"lastGunzipMembers", swept<LastGunzipMembers>},
       {"init", swept<Init>},
       {"initDevices", swept<InitDevices>},

@@ -28,6 +28,16 @@ export declare type ZipIndex = { entries: ZipEntry[], raw: Uint8Array };
 export declare function zipIndex(file: Uint8Array): ZipIndex;
 export declare function zipRead(file: Uint8Array, index: ZipIndex, sel?: number[] | Uint32Array): BatchResult[];
 export declare function zip(files: { name: string | Uint8Array, data: Uint8Array }[]): Uint8Array;
+/** PNG images, read only: the header's facts (no device is touched), and batch decoding to scanlines (samples as stored, filters undone). */
+export declare type PngInfo = {
+  width: number, height: number, depth: number, colourType: number, interlace: number, channels: number, bpp: number, rowBytes: number, size: number,
+  idatCount: number, idatBytes: number, paletteOffset: number, paletteLength: number, transparencyOffset: number, transparencyLength: number,
+};
+export declare type PngImage = { info: PngInfo, data: Uint8Array };
+export declare function pngInfo(file: Uint8Array): PngInfo;
+export declare function pngDecode(file: Uint8Array): PngImage;
+export declare type PngResult = PngImage | Error;
+export declare function pngDecodeBatch(files: Uint8Array[]): PngResult[];
 export declare function init(device: number): void;
 export declare function initDevices(n?: number): number;
 export declare function trim(): void;

@@ -178,6 +178,41 @@ function zip(files) {
 }
 
 /**
+ * Extra (not in the reference API): PNG images, reading.  `pngInfo` judges a file on the host (no device is touched, no CRC
+ * is checked) and returns what its header says: size, bit depth, colour type, interlace method, the filter unit `bpp`,
+ * `rowBytes`, the decoded `size` (height * rowBytes), and where the IDAT, PLTE and tRNS data lie.  `pngDecodeBatch` decodes
+ * files as one batch on the device: one launch checks every chunk's CRC-32, every IDAT stream goes through the inflate tiers
+ * in one call, and one launch undoes the scanline filters.  Element i of the result is `{ info, data }` or — instead of a
+ * throw — the `Error` that says why not.  `data` holds the scanlines as the file stores them: 16-bit samples big-endian,
+ * samples below 8 bits packed, palette indices as indices.  Interlaced files are listed by `pngInfo` and refused by the
+ * decoders.  `pngDecode` is the batch of one file and throws its Error.
+ */
+const pngInfoAt = (raw, at) => {  // one zes_png_info record (72 bytes, include/zes.h)
+  const v = new DataView(raw.buffer, raw.byteOffset + at, 72);
+  const big = (o) => Number(v.getBigUint64(o, true));
+  return {
+    width: v.getUint32(0, true), height: v.getUint32(4, true), depth: v.getUint8(8), colourType: v.getUint8(9), interlace: v.getUint8(10),
+    channels: v.getUint8(11), bpp: v.getUint8(12), rowBytes: big(16), size: big(24), idatCount: v.getUint32(32, true), idatBytes: big(40),
+    paletteOffset: big(48), paletteLength: v.getUint32(36, true), transparencyOffset: big(56), transparencyLength: v.getUint32(64, true),
+  };
+};
+
+function pngInfo(file) {
+  return pngInfoAt(addon.pngInfo(file), 0);
+}
+
+function pngDecodeBatch(files) {
+  const got = addon.pngDecodeBatch(files);
+  return got.results.map((r, i) => (r instanceof Error ? r : { info: pngInfoAt(got.info, 72 * i), data: r }));
+}
+
+function pngDecode(file) {
+  const got = pngDecodeBatch([file])[0];
+  if (got instanceof Error) throw got;
+  return got;
+}
+
+/**
  * Extra: how many members the last gunzip() of this thread decoded as one batch (a BGZF file: all of them, the
  * end-of-file marker included); 0 when the members went one after the other.
  */
@@ -230,6 +265,9 @@ exports.bgzfRead = bgzfRead;
 exports.zipIndex = zipIndex;
 exports.zipRead = zipRead;
 exports.zip = zip;
+exports.pngInfo = pngInfo;
+exports.pngDecodeBatch = pngDecodeBatch;
+exports.pngDecode = pngDecode;
 exports.lastGunzipMembers = lastGunzipMembers;
 exports.adler32 = adler32;
 exports.init = init;

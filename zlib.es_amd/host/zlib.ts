@@ -23,6 +23,12 @@ type ZipEntry = { nameBytes: Uint8Array, name: string, method: number, flags: nu
 type ZipIndex = { entries: ZipEntry[], raw: Uint8Array };
 type ZipSelection = number[] | Uint32Array;
 type ZipFile = { name: string | Uint8Array, data: Uint8Array };
+type PngInfo = {
+  width: number, height: number, depth: number, colourType: number, interlace: number, channels: number, bpp: number, rowBytes: number, size: number,
+  idatCount: number, idatBytes: number, paletteOffset: number, paletteLength: number, transparencyOffset: number, transparencyLength: number,
+};
+type PngImage = { info: PngInfo, data: Uint8Array };
+type PngResult = PngImage | Error;
 /**
  * Extra (not in the reference API): `verify: true` makes an inflate form check the stream's Adler-32 trailer against its
  * result; a trailer that is missing or does not match is the Error "zes: checksum mismatch".  The reference ignores the
@@ -182,6 +188,41 @@ export function zip(files: ZipFile[]): Uint8Array {
   if (!Array.isArray(files)) throw new TypeError('zip(files): files must be an array of { name, data }');
   const names = files.map((f) => (f && typeof f.name === 'string' ? new TextEncoder().encode(f.name) : f && f.name));
   return addon.zip(names, files.map((f) => f && f.data));
+}
+
+/**
+ * Extra (not in the reference API): PNG images, reading.  `pngInfo` judges a file on the host (no device is touched, no CRC
+ * is checked) and returns what its header says: size, bit depth, colour type, interlace method, the filter unit `bpp`,
+ * `rowBytes`, the decoded `size` (height * rowBytes), and where the IDAT, PLTE and tRNS data lie.  `pngDecodeBatch` decodes
+ * files as one batch on the device: one launch checks every chunk's CRC-32, every IDAT stream goes through the inflate tiers
+ * in one call, and one launch undoes the scanline filters.  Element i of the result is `{ info, data }` or — instead of a
+ * throw — the `Error` that says why not.  `data` holds the scanlines as the file stores them: 16-bit samples big-endian,
+ * samples below 8 bits packed, palette indices as indices.  Interlaced files are listed by `pngInfo` and refused by the
+ * decoders.  `pngDecode` is the batch of one file and throws its Error.
+ */
+const pngInfoAt = (raw, at) => {  // one zes_png_info record (72 bytes, include/zes.h)
+  const v = new DataView(raw.buffer, raw.byteOffset + at, 72);
+  const big = (o) => Number(v.getBigUint64(o, true));
+  return {
+    width: v.getUint32(0, true), height: v.getUint32(4, true), depth: v.getUint8(8), colourType: v.getUint8(9), interlace: v.getUint8(10),
+    channels: v.getUint8(11), bpp: v.getUint8(12), rowBytes: big(16), size: big(24), idatCount: v.getUint32(32, true), idatBytes: big(40),
+    paletteOffset: big(48), paletteLength: v.getUint32(36, true), transparencyOffset: big(56), transparencyLength: v.getUint32(64, true),
+  };
+};
+
+export function pngInfo(file: Uint8Array): PngInfo {
+  return pngInfoAt(addon.pngInfo(file), 0);
+}
+
+export function pngDecodeBatch(files: Uint8Array[]): PngResult[] {
+  const got = addon.pngDecodeBatch(files);
+  return got.results.map((r, i) => (r instanceof Error ? r : { info: pngInfoAt(got.info, 72 * i), data: r }));
+}
+
+export function pngDecode(file: Uint8Array): PngImage {
+  const got = pngDecodeBatch([file])[0];
+  if (got instanceof Error) throw got;
+  return got;
 }
 
 /**
