@@ -438,7 +438,7 @@ int zes_zipwrite(const uint8_t* const* in, const uint64_t* in_len, const uint8_t
 
 /* PNG images (PNG specification, second edition): the header of a file, and batch decoding of files to their scanlines.
  * The reader undoes the container, the zlib stream and the scanline filters and nothing else: samples stay as stored (16-bit
- * big-endian, sub-byte samples packed, palette indices as indices).  No Adam7 interlace, no APNG, no writer.
+ * big-endian, sub-byte samples packed, palette indices as indices).  No Adam7 interlace, no APNG.  The writer, zes_pngwrite* below, is the same in reverse.
  *
  * zes_png_info: what a decode call works from.  All values are little-endian host values; pad fields are 0.
  * The file rule.  A file in[0, c) is judged chunk by chunk from byte 8; the first failure in file order decides:
@@ -514,6 +514,66 @@ int zes_png_decode_dev(const uint8_t* d_in, const uint64_t* in_off, const uint64
                        const uint64_t* out_off, const uint64_t* out_cap, uint64_t* out_len, int32_t* status, zes_png_info* info, uint32_t flags);
 int zes_png_decode_alloc(const uint8_t* const* in, const uint64_t* in_len, uint32_t count, zes_alloc_fn alloc, void* user, uint64_t* out_len,
                          int32_t* status, zes_png_info* info, uint32_t flags);
+
+/* zes_pngwrite*: `count` images written as one batch, each to a PNG file of its own.  Image i is in_len[i] bytes of scanlines
+ * at d_in + in_off[i] (in[i], alloc form), exactly as zes_png_decode* writes them: no filter bytes, 16-bit samples big-endian,
+ * sub-byte samples packed, palette indices as indices; img[i] says what they are.  aux is host memory: image i's PLTE data,
+ * then its tRNS data, behind those of the images before it (as `names` in zes_zipwrite*).  img, in_off, in_len, out_off,
+ * out_cap, out_len and status are host arrays; the return value is non-zero only when the call as a whole could not run.
+ * The file is deterministic, the same inputs give the same bytes: signature; IHDR with compression 0, filter method 0,
+ * interlace 0; PLTE when plte_len != 0; tRNS when trns_len != 0; IDAT chunks of exactly 65536 data bytes, the last one
+ * shorter and never empty; IEND; nothing else.
+ *   zlib stream  over the F = height * (1 + rowbytes) filtered bytes.  It is what zes_deflate gives for them when the encoder
+ *                accepts the length (not = 1 mod 131072; F >= 2 always) and that stream is shorter than the stored form;
+ *                otherwise the stored form: 78 01, stored blocks of 65535 bytes, the last one shorter and final, the Adler-32
+ *   filter       0..4: that filter type on every row.  6: adaptive, every row takes the type whose filtered bytes have the
+ *                smallest sum of min(x, 256 - x) (libpng's heuristic; the sum exact in 64 bits, a tie to the lowest type
+ *                number, the row above row 0 zeros).  5: as 6, but a row r with r % 64 == 0 chooses between None and Sub only,
+ *                so that every band of zes_png_decode*'s unfilter step starts at a restart row and the bands of the file
+ *                decode in parallel.  Under 5 and 6 an image of colour type 3 or of a depth below 8 takes None on every row
+ * An image's status, decided in this order; an image with a status from step 1 or 2 costs no launch and has out_len[i] = 0:
+ *   1. ZES_E_ARG: a (colour, depth) pair outside the reader's table; width or height outside 1 .. 2^31 - 1; filter > 6; a
+ *      non-zero pad; in_len[i] != height * rowbytes; colour 3 with plte_len not a multiple of 3 in 3 .. 3 << depth;
+ *      plte_len != 0 for colour 0 or 4 (for colour 2 or 6: not a multiple of 3, or above 768); trns_len other than 0 or 2 for colour 0,
+ *      other than 0 or 6 for colour 2, not within 0 .. plte_len / 3 for colour 3, not 0 for colour 4 or 6
+ *   2. ZES_E_UNSUPPORTED: F > 0xFFFFFFFF
+ *   3. ZES_E_NOSPACE: the file does not fit out_cap[i], or d_out is NULL; out_len[i] is the size needed, the image is still
+ *      encoded and nothing of it is written
+ * For the whole call, ZES_E_ARG: a null array with count != 0, a null d_in / in[i] with a non-zero length, a null aux with
+ * PLTE or tRNS bytes to read, a null alloc, flag bits other than ZES_F_PIECES.  count == 0, and a batch in which no image
+ * passes steps 1 and 2, are ZES_OK without device work.
+ * zes_pngwrite_bound: cap[i] = the size of image i's file with the stored stream — exact when the image goes stored, and
+ * always enough — and 0 for an image that step 1 or 2 rejects (in_len taken as height * rowbytes).  It touches no device.
+ * The images go in groups, in order, as zes_zipwrite*'s entries do: up to 1024 of them whose encoder slots take up to 256 MiB
+ * (4 and 1 MiB under ZES_F_PIECES: same bytes), one image at least; the scratch (a filtered buffer and an encoder slot an
+ * image) is bounded by the group.  Launches per group:
+ *   k_png_filter  once: the filters chosen and applied, every row of every image of the group
+ *   the encoder   one batch encode over the filtered buffers (no CRC-32 launch over them); its read-back of the sizes is the
+ *                 group's one read-back
+ *   k_adler_seg   once, only in a group with lengths the encoder refuses: their Adler-32s, which the host finishes (so a group
+ *                 with such an image has this second read-back, and a group of nothing else this one alone)
+ *   k_png_pack    once: signature, IHDR / PLTE / tRNS, IDAT lengths and types, stream bytes or the stored form, IEND
+ *   k_crc32_seg   once: type and data of every chunk as they lie in the output, the sums left on the device
+ *   k_crc32_put   once: the chunk CRCs finished and stored
+ * (the last three only when an image of the group is written; aux goes up once per group).  No launch, copy or
+ * synchronisation per image.
+ * The device form takes d_in, every in_off, d_out and every out_off at any alignment, writes exactly out_len[i] bytes for an
+ * image at ZES_OK and no byte outside the ranges of the images that are written, and reads the input only inside the aligned
+ * 16-byte groups that hold it (zes_png_decode_dev's contract).  The alloc form stages the inputs (one upload per image), runs
+ * the same steps with the bound's room per image and calls alloc(user, i, out_len[i]) once per image that succeeds (NULL from
+ * alloc: that image is ZES_E_ARG).
+ * replaces: nothing (the reference has no PNG container) */
+typedef struct zes_pngw_image {  /* 16 bytes */
+  uint32_t width, height;
+  uint8_t depth, colour, filter, pad;   /* pad 0 */
+  uint16_t plte_len, trns_len;          /* bytes of PLTE / tRNS data in `aux` */
+} zes_pngw_image;
+int zes_pngwrite_bound(const zes_pngw_image* img, uint32_t count, uint64_t* cap /* count values */);
+int zes_pngwrite_dev(const uint8_t* d_in, const uint64_t* in_off, const uint64_t* in_len, const zes_pngw_image* img, const uint8_t* aux,
+                     uint32_t count, uint8_t* d_out, const uint64_t* out_off, const uint64_t* out_cap, uint64_t* out_len, int32_t* status,
+                     uint32_t flags);
+int zes_pngwrite(const uint8_t* const* in, const uint64_t* in_len, const zes_pngw_image* img, const uint8_t* aux, uint32_t count,
+                 zes_alloc_fn alloc, void* user, uint64_t* out_len, int32_t* status, uint32_t flags);
 
 /* Adler-32 of a buffer (standard value as an unsigned 32-bit).
  * replaces: `calcAdler32` src/adler32.ts:1-10 (byte extraction at src/zlib.ts:37-40). */

@@ -76,6 +76,13 @@ PNG_INFO = np.dtype([("width", "<u4"), ("height", "<u4"), ("depth", "u1"), ("col
                      ("plte_pos", "<u8"), ("trns_pos", "<u8"), ("trns_len", "<u4"), ("pad2", "<u4")])
 assert PNG_INFO.itemsize == 72
 
+# zes_pngw_image of include/zes.h: what the PNG writer is told about one image
+PNGW_IMAGE = np.dtype([("width", "<u4"), ("height", "<u4"), ("depth", "u1"), ("colour", "u1"), ("filter", "u1"), ("pad", "u1"), ("plte_len", "<u2"),
+                       ("trns_len", "<u2")])
+assert PNGW_IMAGE.itemsize == 16
+PNG_FILTER_BANDED = 5  # adaptive, rows 0, 64, 128, ... None or Sub: the reader's bands then decode in parallel
+PNG_FILTER_ADAPTIVE = 6
+
 ALLOC_FN = C.CFUNCTYPE(C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint64)  # zes_alloc_fn of include/zes.h
 
 
@@ -152,6 +159,10 @@ def lib():
         L.zes_png_decode_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                          C.c_void_p, C.c_uint32]
         L.zes_png_decode_alloc.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, ALLOC_FN, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32]
+        L.zes_pngwrite_bound.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p]
+        L.zes_pngwrite_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                       C.c_void_p, C.c_void_p, C.c_uint32]
+        L.zes_pngwrite.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, ALLOC_FN, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32]
         L.zes_gunzip_alloc.argtypes = [C.c_void_p, C.c_uint64, ALLOC_FN, C.c_void_p, u64p, C.c_uint32]
         L.zes_adler32.argtypes = [C.c_void_p, C.c_uint64, u32p]
         L.zes_adler32_dev.argtypes = [C.c_void_p, C.c_uint64, u32p]
@@ -655,6 +666,71 @@ def png_decode(data, flags=0):
     return got
 
 
+def png_bound(images):
+    """A capacity per image that always suffices for its PNG file, exact when its zlib stream goes stored, and 0 for a record
+    the writer rejects (zes_pngwrite_bound; no GPU needed).  ``images``: a PNGW_IMAGE array."""
+    img = np.ascontiguousarray(images, dtype=PNGW_IMAGE).reshape(-1)
+    cap = np.zeros(max(img.size, 1), dtype=np.uint64)
+    rc = lib().zes_pngwrite_bound(_ptr(img), img.size, cap.ctypes.data)
+    if rc:
+        _raise(rc)
+    return [int(x) for x in cap[: img.size]]
+
+
+def _png_item(rows, width=None, colour=None, depth=8, filter=PNG_FILTER_BANDED, palette=b"", trns=b""):
+    """(scanlines, PNGW_IMAGE fields, aux bytes) of one png_encode() argument list."""
+    a = rows if isinstance(rows, np.ndarray) else np.asarray(rows)
+    assert a.dtype == np.uint8 and a.ndim in (2, 3), "png_encode: rows is a uint8 array, height x rowbytes or height x width x channels"
+    height = a.shape[0]
+    if colour is None:
+        colour = {1: 0, 2: 4, 3: 2, 4: 6}[a.shape[2]] if a.ndim == 3 else (3 if len(palette) else 0)
+    channels = {0: 1, 2: 3, 3: 1, 4: 2, 6: 4}.get(colour, 1)
+    flat = np.ascontiguousarray(a).reshape(height, -1)
+    if width is None:
+        assert depth >= 8, "png_encode: `width` is needed below 8 bits a sample"
+        width = flat.shape[1] // (channels * depth // 8)
+    palette, trns = bytes(palette), bytes(trns)
+    assert len(palette) <= 65535 and len(trns) <= 65535
+    return flat.reshape(-1), (width, height, depth, colour, filter, 0, len(palette), len(trns)), palette + trns
+
+
+def png_encode_batch(items, flags=0):
+    """Images written as PNG files in one batch (zes_pngwrite): ``items`` is a list of dicts of png_encode()'s arguments; the
+    result has one uint8 array (the file) or one ZlibEsError per image (not raised, as with png_decode_batch)."""
+    parts = [_png_item(**it) for it in items]
+    cnt = len(parts)
+    img = np.zeros(max(cnt, 1), dtype=PNGW_IMAGE)
+    for i, (_, rec, _) in enumerate(parts):
+        img[i] = rec
+    aux = np.frombuffer(b"".join(x for _, _, x in parts), dtype=np.uint8)
+    got = {}
+
+    def alloc(_user, i, n):
+        got[i] = np.empty(max(int(n), 1), dtype=np.uint8)
+        return got[i].ctypes.data
+
+    ptrs = (C.c_void_p * max(cnt, 1))(*[d.ctypes.data if d.size else None for d, _, _ in parts])
+    ln = np.array([d.size for d, _, _ in parts], dtype=np.uint64)
+    out_len = np.zeros(max(cnt, 1), dtype=np.uint64)
+    status = np.zeros(max(cnt, 1), dtype=np.int32)
+    rc = lib().zes_pngwrite(ptrs, _ptr(ln), img.ctypes.data, _ptr(aux), cnt, ALLOC_FN(alloc), None, out_len.ctypes.data, status.ctypes.data, flags)
+    if rc:
+        _raise(rc)
+    return [got[i][: int(out_len[i])] if status[i] == 0 else ZlibEsError(int(status[i]), strerror(int(status[i]))) for i in range(cnt)]
+
+
+def png_encode(rows, width=None, colour=None, depth=8, filter=PNG_FILTER_BANDED, palette=b"", trns=b"", flags=0):
+    """One image as a PNG file (a uint8 array).  ``rows``: the scanlines as png_decode gives them, a uint8 array of ``height`` x
+    ``rowbytes`` (or height x width x channels of 8-bit samples: the colour type then follows from the channels); ``width`` is
+    needed below 8 bits a sample.  ``colour`` and ``depth`` as in IHDR; ``filter``: 0..4 that type on every row, 6 libpng's
+    adaptive choice, 5 (the default) the same with rows 0, 64, 128, ... None or Sub, which lets png_decode work on the file's
+    bands of 64 rows in parallel.  ``palette`` / ``trns``: the data of PLTE / tRNS.  An image that fails raises."""
+    got = png_encode_batch([dict(rows=rows, width=width, colour=colour, depth=depth, filter=filter, palette=palette, trns=trns)], flags)[0]
+    if isinstance(got, Exception):
+        raise got
+    return got
+
+
 def gunzip(data, flags=0):
     """gzip.decompress: every member, their outputs concatenated (zes_gunzip_alloc: one decode, an exact-size result)."""
     a = _as_u8(data)
@@ -961,6 +1037,51 @@ def png_decode_tensor(d_in, in_off, in_len, out=None, off=None, flags=0, cap=Non
     assert cap.size == cnt and all(int(o) + int(c) <= out.numel() for o, c in zip(off, cap)), "png_decode_tensor: a place reaches beyond `out`"
     call(out.data_ptr() if out.numel() else None, off, cap)
     return out, off, [int(x) for x in out_len[:cnt]], [int(x) for x in status[:cnt]], info[:cnt]
+
+
+def png_encode_tensor(d_in, in_off, in_len, images, aux=b"", out=None, off=None, cap=None, flags=0):
+    """Images in a 1-D uint8 CUDA tensor written as PNG files in one batch (zes_pngwrite_dev): image i's scanlines are
+    ``d_in[in_off[i] : in_off[i] + in_len[i]]`` and ``images[i]`` (a PNGW_IMAGE array) says what they are; ``aux`` holds every
+    image's PLTE then tRNS data, back to back.  Returns ``(out, off, out_len, status)``: file i is
+    ``out[off[i] : off[i] + out_len[i]]`` when ``status[i]`` is 0, and nothing else of ``out`` is written.  ``d_in``, ``out`` and
+    every offset may be any byte.  Without ``off`` the files are placed at 16-byte boundaries with png_bound()'s room each and
+    ``out`` is allocated when it is None.  ``cap``: the capacity of every file's place (default: png_bound(), or up to the end
+    of ``out`` with ``off``); a file that needs more is ZES_E_NOSPACE with its ``out_len`` the size needed."""
+    import torch
+
+    assert d_in.is_cuda and d_in.dtype == torch.uint8 and d_in.is_contiguous()
+    ioff = np.ascontiguousarray(in_off, dtype=np.uint64)
+    ilen = np.ascontiguousarray(in_len, dtype=np.uint64)
+    img = np.ascontiguousarray(images, dtype=PNGW_IMAGE).reshape(-1)
+    cnt = ilen.size
+    assert ioff.ndim == 1 and ioff.shape == ilen.shape and img.size == cnt, "png_encode_tensor: one offset, one length and one record per image"
+    ok = np.array(png_bound(img), dtype=np.uint64) != 0
+    assert all(int(o) + int(n) <= d_in.numel() for o, n, k in zip(ioff, ilen, ok) if k), "png_encode_tensor: an image reaches beyond `d_in`"
+    a = np.frombuffer(bytes(aux), dtype=np.uint8)
+    if off is None:
+        sizes = (np.array(png_bound(img), dtype=np.uint64) + np.uint64(15)) & ~np.uint64(15)
+        off = np.concatenate([np.zeros(1, dtype=np.uint64), np.cumsum(sizes, dtype=np.uint64)])[:cnt]
+        if out is None:
+            out = torch.empty(int(sizes.sum()), dtype=torch.uint8, device=d_in.device)
+        if cap is None:
+            cap = sizes
+    off = np.ascontiguousarray(off, dtype=np.uint64)
+    assert off.size == cnt, "png_encode_tensor: one offset per image"
+    if cap is None:
+        cap = np.array([max((out.numel() if out is not None else 0) - int(o), 0) for o in off], dtype=np.uint64)
+    cap = np.ascontiguousarray(cap, dtype=np.uint64)
+    if out is not None:
+        assert out.is_cuda and out.dtype == torch.uint8 and out.is_contiguous()
+        assert cap.size == cnt and all(int(o) + int(c) <= out.numel() for o, c in zip(off, cap)), "png_encode_tensor: a place reaches beyond `out`"
+    torch.cuda.current_stream(d_in.device).synchronize()
+    out_len = np.zeros(max(cnt, 1), dtype=np.uint64)
+    status = np.zeros(max(cnt, 1), dtype=np.int32)
+    rc = lib().zes_pngwrite_dev(d_in.data_ptr() if d_in.numel() else None, _ptr(ioff), _ptr(ilen), _ptr(img), _ptr(a), cnt,
+                                out.data_ptr() if out is not None and out.numel() else None, _ptr(off), _ptr(cap), out_len.ctypes.data,
+                                status.ctypes.data, flags)
+    if rc:
+        _raise(rc)
+    return out, off, [int(x) for x in out_len[:cnt]], [int(x) for x in status[:cnt]]
 
 
 def _batch_call(fn, d_in, in_off, in_len, d_out, out_off, out_cap, *extra):

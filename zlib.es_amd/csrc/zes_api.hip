@@ -18,6 +18,7 @@
 #include <functional>
 #include <future>
 #include <initializer_list>
+#include <deque>
 #include <map>
 #include <mutex>
 #include <string>
@@ -3926,15 +3927,17 @@ int zes_crc32(const uint8_t* in, uint64_t n, uint32_t* crc) {
 //   launch(...)        the kernel over `items` work items
 //   finish(a, end, w)  the buffer's checksum from its two words
 namespace {
+// The front half: the work list, the pool, the uploads and the launch.  *d_acc: the accumulator words on the device, two per
+// buffer, or null when no buffer has bytes (no launch).  `work` is read by an upload: it lives until the stream has passed it.
 template <class S>
-int seg_checksum_locked(S ck, const uint8_t* d, const ZesCrcSeg* segs, uint32_t count, uint32_t* out) {
+int seg_checksum_enqueue(S& ck, const uint8_t* d, const ZesCrcSeg* segs, uint32_t count, std::vector<uint2>& work, typename S::Word** d_acc) {
   using Word = typename S::Word;
   int rc;
-  std::vector<uint2> work;  // (buffer, chunk)
+  *d_acc = nullptr;
+  work.clear();  // (buffer, chunk)
   work.reserve(count);
   uint64_t maxlen = 0;
   for (uint32_t i = 0; i < count; i++) {
-    out[i] = S::EMPTY;
     if (!segs[i].len) continue;
     const uint64_t a = (uint64_t)(uintptr_t)d + segs[i].off, nch = S::chunks(a, a + segs[i].len);
     if (work.size() + nch >= (1ull << 31)) return ZES_E_ARG;
@@ -3954,8 +3957,21 @@ int seg_checksum_locked(S ck, const uint8_t* d, const ZesCrcSeg* segs, uint32_t 
     ck.launch((uint32_t)work.size(), d, (const ZesCrcSeg*)base, (const uint2*)(base + o_work), (Word*)(base + o_acc));
   }
   HIPCHK(hipGetLastError());
+  *d_acc = (Word*)(base + o_acc);
+  return ZES_OK;
+}
+
+template <class S>
+int seg_checksum_locked(S ck, const uint8_t* d, const ZesCrcSeg* segs, uint32_t count, uint32_t* out) {
+  using Word = typename S::Word;
+  int rc;
+  for (uint32_t i = 0; i < count; i++) out[i] = S::EMPTY;
+  std::vector<uint2> work;
+  Word* d_acc = nullptr;
+  if ((rc = seg_checksum_enqueue(ck, d, segs, count, work, &d_acc))) return rc;
+  if (!d_acc) return ZES_OK;
   std::vector<Word> acc(2 * (size_t)count);
-  HIPCHK(hipMemcpyAsync(acc.data(), base + o_acc, n_acc, hipMemcpyDeviceToHost, g.stream));
+  HIPCHK(hipMemcpyAsync(acc.data(), d_acc, sizeof(Word) * acc.size(), hipMemcpyDeviceToHost, g.stream));
   HIPCHK(hipStreamSynchronize(g.stream));
   for (uint32_t i = 0; i < count; i++) {
     if (!segs[i].len) continue;
@@ -3989,8 +4005,13 @@ struct CrcSeg {
     return zes_crc_mul(it->second, v);
   }
   uint32_t finish(uint64_t a, uint64_t end, const Word* w) {
+    const ZesCrcPut p = put(a, end, 0);
+    return zes_crc_mul(p.mul, w[0]) ^ w[1] ^ p.add;
+  }
+  // finish() for the device (k_crc32_put): the two constants, which depend on where the buffer lies and on its length alone
+  ZesCrcPut put(uint64_t a, uint64_t end, uint64_t dst) {
     const uint64_t last = end - std::max<uint64_t>(a, (a & ~(uint64_t)15) + (chunks(a, end) - 1) * CRC_CHUNK);
-    return shift(w[0], last) ^ w[1] ^ shift(0xFFFFFFFFu, end - a) ^ 0xFFFFFFFFu;
+    return ZesCrcPut{dst, shift(0x80000000u, last), shift(0xFFFFFFFFu, end - a) ^ 0xFFFFFFFFu};
   }
 };
 
@@ -4122,7 +4143,7 @@ static int call_done(int rc, bool clear) {
 // ---- A group of buffers encoded for a container: the step that bgzip_core (members) and zipwrite_groups (entries) share ----
 // The caller lays the group out: buffer k is d_in[in_off[k], + in_len[k]) and has the 16-byte aligned slot [o_off[k], + o_cap[k])
 // of g.gz_bodies, o_cap[k] == 0 for a buffer that the encoder is spared (the caller's rule).  encode() gives every buffer its
-// CRC-32 by one segmented launch and encodes the group by one deflate_batch_core call (none when the slots take no bytes: no
+// CRC-32 by one segmented launch (unless the caller has no use for them: crcs) and encodes the group by one deflate_batch_core call (none when the slots take no bytes: no
 // times of its own to keep); raw[k] is then the length of buffer k's raw stream, which starts at o_off[k] + 2 (78 9C in
 // front, the Adler-32 behind), and 0 for a spared buffer.
 // A result beyond the caller's capacity, by room(): every group is still encoded (the size needed is the answer), and from
@@ -4134,11 +4155,11 @@ struct EncGroup {
   std::vector<uint32_t> crc;
   bool fits = true;
   explicit EncGroup(size_t most) : o_off(most), o_cap(most), o_len(most), raw(most), status(most), csegs(most), crc(most) {}
-  int encode(const uint8_t* d_in, const uint64_t* in_off, const uint64_t* in_len, uint32_t cnt, uint64_t slots) {
+  int encode(const uint8_t* d_in, const uint64_t* in_off, const uint64_t* in_len, uint32_t cnt, uint64_t slots, bool crcs = true) {
     int rc;
     for (uint32_t k = 0; k < cnt; k++) csegs[k] = ZesCrcSeg{in_off[k], in_len[k]};
     if ((rc = ensure(g.gz_bodies, slots + 64))) return rc;
-    if ((rc = crc32_batch_locked(d_in, csegs.data(), cnt, crc.data()))) return rc;
+    if (crcs && (rc = crc32_batch_locked(d_in, csegs.data(), cnt, crc.data()))) return rc;
     if (slots) {
       if ((rc = deflate_batch_core(d_in, in_off, in_len, (uint8_t*)g.gz_bodies.p, o_off.data(), o_cap.data(), o_len.data(), status.data(), cnt))) return rc;
       keep_times();
@@ -5760,6 +5781,336 @@ int zes_png_decode_alloc(const uint8_t* const* in, const uint64_t* in_len, uint3
     // (a short result is only enqueued: one synchronisation behind the loop serves them all)
     if ((rc = download(to, (const uint8_t*)g.gz_acc.p + im[i].dst_off, size[i], nullptr, false))) return rc;
     out_len[i] = size[i];
+  }
+  HIPCHK(hipStreamSynchronize(g.stream));
+  return ZES_OK;
+}
+
+// ---- PNG writer (include/zes.h: "zes_pngwrite*"): filters by k_png_filter, zlib bodies by EncGroup, files by k_png_pack ----
+constexpr uint32_t PNGW_GROUP = ZIPW_GROUP, PNGW_GROUP_PIECES = ZIPW_GROUP_PIECES;  // a group: zipwrite_groups' limits
+constexpr uint64_t PNGW_GROUP_SLOTS = ZIPW_GROUP_SLOTS, PNGW_GROUP_SLOTS_PIECES = ZIPW_GROUP_SLOTS_PIECES;
+
+// What the arguments alone say about image i (steps 1 and 2 of include/zes.h), and its sizes
+struct PngwPlan {
+  int32_t status = ZES_OK;
+  uint32_t rowbytes = 0, bpp = 1, mode = 0, aux_off = 0;
+  uint64_t F = 0;  // the filtered bytes: height * (1 + rowbytes)
+};
+static uint64_t pngw_stored_len(uint64_t F) { return 2 + 5 * ((F + ZES_PNGW_BLOCK - 1) / ZES_PNGW_BLOCK) + F + 4; }
+// the file around a zlib stream of zlen bytes
+static uint64_t pngw_file_len(const zes_pngw_image& m, uint64_t zlen) {
+  return 8 + 25 + (m.plte_len ? 12ull + m.plte_len : 0) + (m.trns_len ? 12ull + m.trns_len : 0) + zlen + 12 * ((zlen + ZES_PNGW_IDAT - 1) / ZES_PNGW_IDAT) + 12;
+}
+static_assert(sizeof(zes_pngw_image) == 16, "zes_pngw_image is 16 bytes");
+static PngwPlan pngw_plan(const zes_pngw_image& m, uint64_t in_len) {
+  PngwPlan p;
+  p.status = ZES_E_ARG;
+  const uint32_t dp = m.depth;
+  bool ok;
+  switch (m.colour) {
+    case 0: ok = dp == 1 || dp == 2 || dp == 4 || dp == 8 || dp == 16; break;
+    case 3: ok = dp == 1 || dp == 2 || dp == 4 || dp == 8; break;
+    case 2: case 4: case 6: ok = dp == 8 || dp == 16; break;
+    default: ok = false;
+  }
+  if (!ok || m.width - 1 > 0x7ffffffeu || m.height - 1 > 0x7ffffffeu || m.filter > 6 || m.pad) return p;
+  const uint32_t bits = png_channels(m.colour) * dp;
+  const uint64_t rowbytes = ((uint64_t)m.width * bits + 7) / 8;
+  if ((unsigned __int128)in_len != (unsigned __int128)m.height * rowbytes) return p;
+  switch (m.colour) {
+    case 3: ok = m.plte_len % 3 == 0 && m.plte_len >= 3 && m.plte_len <= (3u << dp) && m.trns_len <= m.plte_len / 3; break;
+    case 0: ok = m.plte_len == 0 && (m.trns_len == 0 || m.trns_len == 2); break;
+    case 2: ok = m.trns_len == 0 || m.trns_len == 6; break;
+    case 4: ok = m.plte_len == 0 && m.trns_len == 0; break;
+    default: ok = m.trns_len == 0;
+  }
+  if (!ok || (m.colour != 3 && (m.plte_len % 3 || m.plte_len > 768))) return p;  // (a PLTE the reader's file rule would reject)
+  p.status = ZES_E_UNSUPPORTED;
+  if (1 + rowbytes > 0xFFFFFFFFull / m.height) return p;
+  p.status = ZES_OK;
+  p.rowbytes = (uint32_t)rowbytes;
+  p.bpp = std::max<uint32_t>(1, bits / 8);
+  p.F = m.height * (1 + rowbytes);
+  p.mode = (m.filter >= 5 && (m.colour == 3 || dp < 8)) ? 0u : m.filter;  // (adaptive: palette and sub-byte images take None)
+  return p;
+}
+
+// zes_pngwrite*: what both forms check before anything else, and the plans.  ZES_OK with *any == false: nothing to encode
+static int pngwrite_args(const std::function<bool(uint32_t)>& data, const uint64_t* in_len, const zes_pngw_image* img, const uint8_t* aux, uint32_t count,
+                         uint64_t* out_len, int32_t* status, uint32_t flags, std::vector<PngwPlan>& plan, bool* any) {
+  *any = false;
+  if (flags & ~ZES_F_PIECES) return ZES_E_ARG;
+  if (count && (!in_len || !img || !out_len || !status)) return ZES_E_ARG;
+  uint64_t naux = 0;
+  for (uint32_t i = 0; i < count; i++) {
+    if (in_len[i] && !data(i)) return ZES_E_ARG;
+    naux += (uint64_t)img[i].plte_len + img[i].trns_len;
+  }
+  if ((naux && !aux) || naux > 0xFFFFFFFFull) return ZES_E_ARG;
+  plan.resize(count);
+  naux = 0;
+  for (uint32_t i = 0; i < count; i++) {
+    plan[i] = pngw_plan(img[i], in_len[i]);
+    plan[i].aux_off = (uint32_t)naux;
+    naux += (uint64_t)img[i].plte_len + img[i].trns_len;
+    status[i] = plan[i].status;
+    out_len[i] = 0;
+    *any = *any || plan[i].status == ZES_OK;
+  }
+  return ZES_OK;
+}
+
+// The host memory that a call's asynchronous uploads read: the caller's, pngwrite_core's, as ZipwHost is zipwrite_core's
+struct PngwHost {
+  std::deque<std::vector<uint8_t>> blobs;
+  std::deque<std::vector<uint2>> work;
+  std::deque<std::vector<ZesCrcSeg>> segs;
+  uint8_t* blob(size_t n) {
+    blobs.emplace_back(n);
+    return blobs.back().data();
+  }
+};
+
+// The images whose status[i] is ZES_OK on entry, image i's scanlines at d_in + in_off[i], its file to d_out + out_off[i] when
+// it fits out_cap[i] (and d_out is there), else ZES_E_NOSPACE with the size needed.  Group by group as zipwrite_groups goes;
+// a group's launches, in order:
+//   k_png_filter   once: every row of the group's images into their scratch buffers (g.gz_outs)
+//   the encoder    EncGroup without its CRC-32 launch, the scratch buffers as its input: one deflate_batch_core call, whose
+//                  read-back is the group's (none when the encoder refuses every length)
+//   k_adler_seg    once, and only when the group has lengths that the encoder refuses (F = 1 mod 131072): their Adler-32s
+//                  (finished on the host, so this launch has a read-back of its own)
+//   k_png_pack     once: everything of the files but the chunk CRCs
+//   k_crc32_seg    once: type and data of every chunk as they lie in the output, the words left on the device
+//   k_crc32_put    once: the chunk CRCs finished and stored
+// The last three only when an image of the group is written.  g.gz_tab holds the filter's records and, behind the read-back,
+// aux | pack records | put records.
+static int pngwrite_groups(PngwHost& hm, const uint8_t* d_in, const uint64_t* in_off, const zes_pngw_image* img, const uint8_t* aux,
+                           const std::vector<PngwPlan>& plan, uint32_t count, uint8_t* d_out, const uint64_t* out_off, const uint64_t* out_cap,
+                           uint64_t* out_len, int32_t* status, uint32_t flags) {
+  int rc;
+  g.carry.clear();
+  g.last_tier = 0;
+  const uint32_t group = (flags & ZES_F_PIECES) ? PNGW_GROUP_PIECES : PNGW_GROUP;
+  const uint64_t group_slots = (flags & ZES_F_PIECES) ? PNGW_GROUP_SLOTS_PIECES : PNGW_GROUP_SLOTS;
+  std::vector<uint32_t> live;
+  for (uint32_t i = 0; i < count; i++)
+    if (status[i] == ZES_OK) live.push_back(i);
+  const uint32_t nlive = (uint32_t)live.size();
+  EncGroup eg(std::min(group, nlive));
+  std::vector<uint64_t> f_off(std::min(group, nlive)), f_len(std::min(group, nlive));
+  auto slot_of = [](uint64_t len) { return deflate_throws(len) ? 0ull : gz_up16(deflate_bound(len)); };
+  CrcSeg ck;
+  for (uint32_t e0 = 0; e0 < nlive;) {
+    // the group, its scratch buffers and encoder slots, the filter's records
+    uint32_t cnt = 0;
+    uint64_t slots = 0, fbytes = 0, units = 0;
+    while (e0 + cnt < nlive && cnt < group && (cnt == 0 || slots + slot_of(plan[live[e0 + cnt]].F) <= group_slots)) {
+      const PngwPlan& p = plan[live[e0 + cnt]];
+      eg.o_off[cnt] = slots;
+      eg.o_cap[cnt] = slot_of(p.F);
+      slots += eg.o_cap[cnt];
+      f_off[cnt] = fbytes;
+      f_len[cnt] = p.F;
+      fbytes += gz_up16(p.F) + 16;
+      cnt++;
+    }
+    ZesPngwJob* jobs = (ZesPngwJob*)hm.blob(sizeof(ZesPngwJob) * ((size_t)cnt + 1));
+    for (uint32_t k = 0; k < cnt; k++) {
+      const uint32_t i = live[e0 + k];
+      const PngwPlan& p = plan[i];
+      jobs[k] = ZesPngwJob{in_off[i], f_off[k], img[i].height, p.rowbytes, p.bpp, p.mode, (uint32_t)units, 0u};
+      units += (img[i].height + ZES_PNGW_RUN - 1) / ZES_PNGW_RUN;
+    }
+    if (units > 0x7fffffffull) return ZES_E_ARG;
+    jobs[cnt] = ZesPngwJob{0, 0, 0u, 0u, 0u, 0u, (uint32_t)units, 0u};
+    if ((rc = ensure(g.gz_outs, fbytes + 64)) || (rc = ensure(g.gz_tab, sizeof(ZesPngwJob) * ((size_t)cnt + 1)))) return rc;
+    uint8_t* filt = (uint8_t*)g.gz_outs.p;
+    HIPCHK(hipMemcpyAsync(g.gz_tab.p, jobs, sizeof(ZesPngwJob) * ((size_t)cnt + 1), hipMemcpyHostToDevice, g.stream));
+    {
+      Timed t("k_png_filter");
+      constexpr uint32_t per = ZES_PNGW_THREADS / 64u;
+      hipLaunchKernelGGL(k_png_filter, dim3((uint32_t)((units + per - 1) / per)), dim3(ZES_PNGW_THREADS), 0, g.stream, d_in, filt, (const ZesPngwJob*)g.gz_tab.p, cnt);
+    }
+    HIPCHK(hipGetLastError());
+    if ((rc = eg.encode(filt, f_off.data(), f_len.data(), cnt, slots, false))) return rc;
+    // the lengths the encoder refuses: their Adler-32s
+    std::vector<ZesCrcSeg> asegs;
+    for (uint32_t k = 0; k < cnt; k++)
+      if (!eg.o_cap[k]) asegs.push_back(ZesCrcSeg{f_off[k], f_len[k]});
+    std::vector<uint32_t> adler(asegs.size());
+    if (!asegs.empty() && (rc = adler32_batch_locked(filt, asegs.data(), (uint32_t)asegs.size(), adler.data()))) return rc;
+    // (the stream has been waited for: the filter's records in g.gz_tab are done with)
+    // stream or stored, the files' sizes and places
+    uint64_t naux = 0, wgs = 0;
+    uint32_t nrec = 0;
+    for (uint32_t k = 0; k < cnt; k++) naux += (uint64_t)img[live[e0 + k]].plte_len + img[live[e0 + k]].trns_len;
+    const size_t aux_pad = (size_t)gz_up16(naux);
+    uint8_t* haux = hm.blob(aux_pad + 16);
+    ZesPngwRec* recs = (ZesPngwRec*)hm.blob(sizeof(ZesPngwRec) * ((size_t)cnt + 1));
+    hm.segs.emplace_back();
+    std::vector<ZesCrcSeg>& csegs = hm.segs.back();
+    std::vector<ZesCrcPut> puts;
+    uint32_t aux_at = 0, refused = 0;
+    for (uint32_t k = 0; k < cnt; k++) {
+      const uint32_t i = live[e0 + k];
+      const PngwPlan& p = plan[i];
+      const zes_pngw_image& m = img[i];
+      const uint64_t stored_len = pngw_stored_len(p.F);
+      const bool stream = eg.o_cap[k] && eg.raw[k] + 6 < stored_len;
+      const uint64_t zlen = stream ? eg.raw[k] + 6 : stored_len;
+      const uint32_t my_adler = eg.o_cap[k] ? 0u : adler[refused++];
+      out_len[i] = pngw_file_len(m, zlen);
+      if (!d_out || out_len[i] > out_cap[i]) {
+        status[i] = ZES_E_NOSPACE;
+        continue;
+      }
+      ZesPngwRec& r = recs[nrec++];
+      memset(&r, 0, sizeof r);
+      r.src_off = stream ? eg.o_off[k] : f_off[k];
+      r.dst_off = out_off[i];
+      r.zlen = zlen;
+      r.adler_off = eg.o_cap[k] ? eg.o_off[k] + eg.raw[k] + 2 : ZES_PNGW_NO_SLOT;
+      r.flen = (uint32_t)p.F;
+      r.width = m.width, r.height = m.height;
+      r.aux_off = aux_at;
+      r.first_wg = (uint32_t)wgs;
+      r.adler = my_adler;
+      r.plte_len = m.plte_len, r.trns_len = m.trns_len;
+      r.depth = m.depth, r.colour = m.colour, r.stored = stream ? 0 : 1;
+      if (m.plte_len + m.trns_len) memcpy(haux + aux_at, aux + p.aux_off, (size_t)m.plte_len + m.trns_len);
+      aux_at += (uint32_t)m.plte_len + m.trns_len;
+      // the chunks as they will lie in the output: type and data of each, and the CRC field behind them
+      const uint64_t nidat = (zlen + ZES_PNGW_IDAT - 1) / ZES_PNGW_IDAT;
+      uint64_t at = out_off[i] + 8;
+      auto chunk = [&](uint64_t dlen) {
+        csegs.push_back(ZesCrcSeg{at + 4, 4 + dlen});
+        const uint64_t a = (uint64_t)(uintptr_t)d_out + at + 4;
+        puts.push_back(ck.put(a, a + 4 + dlen, at + 8 + dlen));
+        at += 12 + dlen;
+      };
+      chunk(13);
+      if (m.plte_len) chunk(m.plte_len);
+      if (m.trns_len) chunk(m.trns_len);
+      for (uint64_t c = 0; c < nidat; c++) chunk(std::min<uint64_t>(ZES_PNGW_IDAT, zlen - c * ZES_PNGW_IDAT));
+      chunk(0);
+      wgs += nidat;
+    }
+    if (!nrec) {
+      e0 += cnt;
+      continue;
+    }
+    if (wgs > 0x7fffffffull || csegs.size() > 0x7fffffffull) return ZES_E_ARG;
+    memset(&recs[nrec], 0, sizeof(ZesPngwRec));
+    recs[nrec].first_wg = (uint32_t)wgs;
+    const size_t o_recs = aux_pad, o_puts = o_recs + sizeof(ZesPngwRec) * ((size_t)nrec + 1), n_puts = sizeof(ZesCrcPut) * puts.size();
+    ZesCrcPut* hputs = (ZesCrcPut*)hm.blob(n_puts);
+    memcpy(hputs, puts.data(), n_puts);
+    if ((rc = ensure(g.gz_tab, o_puts + n_puts))) return rc;
+    uint8_t* tab = (uint8_t*)g.gz_tab.p;
+    if (aux_pad) HIPCHK(hipMemcpyAsync(tab, haux, aux_pad, hipMemcpyHostToDevice, g.stream));
+    HIPCHK(hipMemcpyAsync(tab + o_recs, recs, sizeof(ZesPngwRec) * ((size_t)nrec + 1), hipMemcpyHostToDevice, g.stream));
+    HIPCHK(hipMemcpyAsync(tab + o_puts, hputs, n_puts, hipMemcpyHostToDevice, g.stream));
+    {
+      Timed t("k_png_pack");
+      hipLaunchKernelGGL(k_png_pack, dim3((uint32_t)wgs), dim3(GZ_GATHER_THREADS), 0, g.stream, (const uint8_t*)filt, (const uint8_t*)g.gz_bodies.p, (const uint8_t*)tab,
+                         d_out, (const ZesPngwRec*)(tab + o_recs), nrec);
+    }
+    HIPCHK(hipGetLastError());
+    hm.work.emplace_back();
+    unsigned int* d_acc = nullptr;
+    rc = seg_checksum_enqueue(ck, d_out, csegs.data(), (uint32_t)csegs.size(), hm.work.back(), &d_acc);
+    if (rc || !d_acc) return rc ? rc : ZES_E_DEVICE;
+    {
+      Timed t("k_crc32_put");
+      hipLaunchKernelGGL(k_crc32_put, dim3((uint32_t)((puts.size() + 255) / 256)), dim3(256), 0, g.stream, (const unsigned int*)d_acc, (const ZesCrcPut*)(tab + o_puts),
+                         (uint32_t)puts.size(), d_out);
+    }
+    HIPCHK(hipGetLastError());
+    e0 += cnt;
+  }
+  HIPCHK(hipStreamSynchronize(g.stream));
+  return ZES_OK;
+}
+
+
+static int pngwrite_core(const uint8_t* d_in, const uint64_t* in_off, const zes_pngw_image* img, const uint8_t* aux, const std::vector<PngwPlan>& plan,
+                         uint32_t count, uint8_t* d_out, const uint64_t* out_off, const uint64_t* out_cap, uint64_t* out_len, int32_t* status, uint32_t flags) {
+  PngwHost hm;
+  const int rc = pngwrite_groups(hm, d_in, in_off, img, aux, plan, count, d_out, out_off, out_cap, out_len, status, flags);
+  // (a way out in the middle: what is under way may still read hm.  ZES_OK comes from behind the last synchronisation)
+  if (rc && hipStreamSynchronize(g.stream) != hipSuccess) (void)hipGetLastError();
+  return rc;
+}
+
+int zes_pngwrite_bound(const zes_pngw_image* img, uint32_t count, uint64_t* cap) {
+  if (count && (!img || !cap)) return ZES_E_ARG;
+  for (uint32_t i = 0; i < count; i++) {
+    const zes_pngw_image& m = img[i];
+    // (the scanlines' size is not an argument here: the one that fits the header)
+    const uint64_t rowbytes = ((uint64_t)m.width * (png_channels(m.colour) * m.depth) + 7) / 8;
+    const unsigned __int128 n = (unsigned __int128)m.height * rowbytes;
+    const PngwPlan p = n > 0xFFFFFFFFFFFFFFFFull ? PngwPlan{ZES_E_UNSUPPORTED} : pngw_plan(m, (uint64_t)n);
+    cap[i] = p.status == ZES_OK ? pngw_file_len(m, pngw_stored_len(p.F)) : 0;
+  }
+  return ZES_OK;
+}
+
+int zes_pngwrite_dev(const uint8_t* d_in, const uint64_t* in_off, const uint64_t* in_len, const zes_pngw_image* img, const uint8_t* aux, uint32_t count,
+                     uint8_t* d_out, const uint64_t* out_off, const uint64_t* out_cap, uint64_t* out_len, int32_t* status, uint32_t flags) {
+  ROUTE_DEV(d_in, d_out);
+  if (count && (!in_off || !out_off || !out_cap)) return ZES_E_ARG;
+  std::vector<PngwPlan> plan;
+  bool any = false;
+  if (const int arc = pngwrite_args([&](uint32_t) { return d_in != nullptr; }, in_len, img, aux, count, out_len, status, flags, plan, &any)) return arc;
+  if (!any) {
+    zip_read_none();
+    return ZES_OK;
+  }
+  LOCK_READY();
+  return call_done(pngwrite_core(d_in, in_off, img, aux, plan, count, d_out, out_off, out_cap, out_len, status, flags), true);
+}
+
+int zes_pngwrite(const uint8_t* const* in, const uint64_t* in_len, const zes_pngw_image* img, const uint8_t* aux, uint32_t count, zes_alloc_fn alloc,
+                 void* user, uint64_t* out_len, int32_t* status, uint32_t flags) {
+  UseDev ud(route_host());
+  if (count && (!in || !alloc)) return ZES_E_ARG;
+  std::vector<PngwPlan> plan;
+  bool any = false;
+  if (const int arc = pngwrite_args([&](uint32_t i) { return in[i] != nullptr; }, in_len, img, aux, count, out_len, status, flags, plan, &any)) return arc;
+  if (!any) {
+    zip_read_none();
+    return ZES_OK;
+  }
+  LOCK_READY();
+  // every image at a 16-byte boundary of g.gz_in, every file at one of g.gz_acc with the bound's room
+  std::vector<uint64_t> in_off(count, 0), out_off(count, 0), out_cap(count, 0);
+  uint64_t tin = 0, tout = 0;
+  for (uint32_t i = 0; i < count; i++) {
+    if (status[i] != ZES_OK) continue;
+    in_off[i] = tin;
+    tin += gz_up16(in_len[i]) + 16;
+    out_off[i] = tout;
+    out_cap[i] = pngw_file_len(img[i], pngw_stored_len(plan[i].F));
+    tout += gz_up16(out_cap[i]) + 16;
+  }
+  if ((rc = ensure(g.gz_in, tin + 64)) || (rc = ensure(g.gz_acc, tout + 64))) return rc;
+  for (uint32_t i = 0; i < count; i++)
+    if (status[i] == ZES_OK && (rc = upload((uint8_t*)g.gz_in.p + in_off[i], in[i], in_len[i]))) return rc;
+  rc = pngwrite_core((const uint8_t*)g.gz_in.p, in_off.data(), img, aux, plan, count, (uint8_t*)g.gz_acc.p, out_off.data(), out_cap.data(), out_len, status, flags);
+  if ((rc = call_done(rc, true))) return rc;
+  for (uint32_t i = 0; i < count; i++) {
+    if (status[i] != ZES_OK) {
+      out_len[i] = 0;
+      continue;
+    }
+    uint8_t* to = alloc(user, i, out_len[i]);
+    if (!to) {
+      status[i] = ZES_E_ARG;
+      out_len[i] = 0;
+      continue;
+    }
+    // (a short result is only enqueued: one synchronisation behind the loop serves them all)
+    if ((rc = download(to, (const uint8_t*)g.gz_acc.p + out_off[i], out_len[i], nullptr, false))) return rc;
   }
   HIPCHK(hipStreamSynchronize(g.stream));
   return ZES_OK;

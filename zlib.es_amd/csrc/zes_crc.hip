@@ -240,3 +240,17 @@ __global__ __launch_bounds__(CRC_THREADS) void k_crc32_seg(const uint8_t* __rest
     }
   }
 }
+
+// Buffer q of a k_crc32_seg launch finished on the device and stored, most significant byte first (a PNG chunk's CRC
+// field): what the host does with the two words in seg_checksum_locked, with the two constants that depend on the buffer's
+// length alone made there.  A thread per buffer.
+__global__ __launch_bounds__(256) void k_crc32_put(const unsigned int* __restrict__ acc, const ZesCrcPut* __restrict__ puts, uint32_t count,
+                                                  uint8_t* __restrict__ out) {
+  const uint32_t q = blockIdx.x * 256u + threadIdx.x;
+  if (q >= count) return;
+  const ZesCrcPut p = puts[q];
+  const uint32_t crc = crc_mulmod(p.mul, acc[2 * (size_t)q]) ^ acc[2 * (size_t)q + 1] ^ p.add;
+  uint8_t* d = out + p.dst;
+#pragma unroll
+  for (uint32_t k = 0; k < 4; k++) d[k] = (uint8_t)(crc >> (8 * (3 - k)));
+}

@@ -250,6 +250,47 @@ struct ZesPngJob {
 };
 #define ZES_PNG_BAND 64u          // rows of a band: a lane each
 #define ZES_PNG_UNF_THREADS 256u  // four independent waves to a workgroup
+// k_png_filter (zes_pngw.hip): one image of a PNG writer's group.  Its rows are cut into runs of ZES_PNGW_RUN, a wave each:
+// the waves [first_unit, next record's first_unit) of the launch.  The table has a closing record behind the last image:
+// only its first_unit counts, the launch's waves
+struct ZesPngwJob {
+  uint64_t src_off;   // the scanlines in the caller's input: height rows of rowbytes bytes, any alignment
+  uint64_t dst_off;   // the 16-byte aligned scratch buffer: height rows of 1 + rowbytes bytes
+  uint32_t height, rowbytes;
+  uint32_t bpp;       // the filter unit: 1, 2, 3, 4, 6 or 8
+  uint32_t mode;      // 0..4: that type on every row; ZES_PNGW_BANDED, ZES_PNGW_ADAPTIVE: the row's cheapest type
+  uint32_t first_unit;
+  uint32_t pad;
+};
+#define ZES_PNGW_BANDED 5u      // adaptive, but a row r with r % 64 == 0 chooses between None and Sub (k_png_unfilter's restart rows)
+#define ZES_PNGW_ADAPTIVE 6u
+#define ZES_PNGW_RUN 16u        // rows of a run: one wave goes through them in order, the row above still in the cache
+#define ZES_PNGW_THREADS 256u   // four independent waves to a workgroup
+// k_png_pack (zes_pngw.hip): one PNG file being written.  The file has a workgroup per IDAT chunk, [first_wg, next record's
+// first_wg); the table has a closing record as ZesZipPackRec's has
+struct ZesPngwRec {
+  uint64_t src_off;    // stream: the zlib stream's first byte (78 9C) in the slots; stored: the filtered bytes in the scratch
+  uint64_t dst_off;    // the signature's first byte in the output
+  uint64_t zlen;       // bytes of the zlib stream, the stored form's headers and trailer included
+  uint64_t adler_off;  // stored: where the Adler-32's four bytes stand in the slots (behind the encoder's stream), or
+                       // ZES_PNGW_NO_SLOT: `adler` holds it
+  uint32_t flen;       // stored: the filtered bytes
+  uint32_t width, height;
+  uint32_t aux_off;    // PLTE data, then tRNS data, in the device copy of the group's aux bytes
+  uint32_t first_wg;
+  uint32_t adler;
+  uint16_t plte_len, trns_len;
+  uint8_t depth, colour, stored, pad;
+};
+#define ZES_PNGW_NO_SLOT 0xFFFFFFFFFFFFFFFFull
+#define ZES_PNGW_IDAT 65536u   // data bytes of an IDAT chunk (the last one: what is left)
+#define ZES_PNGW_BLOCK 65535u  // bytes of a stored block (the last one: what is left)
+// k_crc32_put (zes_crc.hip): where buffer q of a k_crc32_seg launch has its CRC-32 stored, most significant byte first, and
+// what finishes it from the buffer's two accumulator words: mul * word 0 ^ word 1 ^ add
+struct ZesCrcPut {
+  uint64_t dst;
+  uint32_t mul, add;
+};
 
 // CRC-32 host arithmetic (zes_crc.hip): shift(s, k) = s * x^(8k) mod P; the kernel's table with npow powers
 uint32_t zes_crc_shift(uint32_t s, uint64_t k);
@@ -334,6 +375,10 @@ __global__ void k_zip_pack(const uint8_t*, const uint8_t*, const uint8_t*, uint8
 // PNG reader (zes_png.hip)
 __global__ void k_png_walk(const uint8_t*, const ZesPngFile*, uint32_t, ZesPngHead*, ZesPngChunk*);
 __global__ void k_png_unfilter(const uint8_t*, uint8_t*, const ZesPngJob*, uint32_t, uint32_t, uint32_t*);
+// PNG writer (zes_pngw.hip, zes_crc.hip)
+__global__ void k_png_filter(const uint8_t*, uint8_t*, const ZesPngwJob*, uint32_t);
+__global__ void k_png_pack(const uint8_t*, const uint8_t*, const uint8_t*, uint8_t*, const ZesPngwRec*, uint32_t);
+__global__ void k_crc32_put(const unsigned int*, const ZesCrcPut*, uint32_t, uint8_t*);
 __global__ void k_adler_blocks(const uint8_t*, const ZesBuf*, const ZesBlk*, unsigned long long*);
 __global__ void k_adler_seg(const uint8_t*, const ZesCrcSeg*, const uint2*, unsigned long long*);
 __global__ void k_layout(uint8_t*, const ZesBuf*, ZesBlk*, const unsigned long long*, ZesRes*);

@@ -1078,6 +1078,38 @@ napi_value PngDecodeBatch(napi_env env, napi_callback_info info) {
   return res;
 }
 
+// pngEncodeBatch(rows, records, aux): images written as PNG files in one batch (include/zes.h: zes_pngwrite) — rows[i] the
+// scanlines of image i, records its zes_pngw_image record (16 bytes each, back to back; the façade makes them) and aux every
+// image's PLTE then tRNS data.  Per image the file as a fresh Uint8Array or the Error that says why not.
+napi_value PngEncodeBatch(napi_env env, napi_callback_info info) {
+  static const char SIG[] = "pngEncodeBatch(rows, records, aux)";
+  const Args a = get_args(env, info);
+  bool is_arr = false;
+  uint32_t count = 0;
+  if (a.argc < 3 || napi_is_array(env, a.argv[0], &is_arr) != napi_ok || !is_arr || napi_get_array_length(env, a.argv[0], &count) != napi_ok)
+    return throw_type(env, std::string(SIG) + ": rows must be an array of Uint8Array");
+  const Bytes recs = need_bytes(env, a, 1, SIG, "records");
+  if (!recs.ok) return nullptr;
+  const Bytes aux = need_bytes(env, a, 2, SIG, "aux");
+  if (!aux.ok) return nullptr;
+  if (recs.n != (size_t)count * sizeof(zes_pngw_image)) return throw_type(env, std::string(SIG) + ": records must hold 16 bytes an image");
+  BatchJob j(count);
+  uint64_t naux = 0;
+  std::vector<zes_pngw_image> img((size_t)count + 1);
+  if (count) memcpy(img.data(), recs.p, recs.n);
+  for (uint32_t i = 0; i < count; i++) {
+    napi_value e;
+    size_t n = 0;
+    if (napi_get_element(env, a.argv[0], i, &e) != napi_ok || !get_bytes(env, e, &j.in[i], &n))
+      return throw_type(env, std::string(SIG) + ": every element of rows must be a Uint8Array");
+    j.in_len[i] = n;
+    naux += (uint64_t)img[i].plte_len + img[i].trns_len;
+  }
+  if (naux != aux.n) return throw_type(env, std::string(SIG) + ": aux must hold every image's PLTE and tRNS data");
+  j.rc = zes_pngwrite(j.in.data(), j.in_len.data(), img.data(), aux.p, count, batch_alloc, &j, j.out_len.data(), j.status.data(), ZES_F_DEFAULT);
+  return j.rc == 0 ? batch_results(env, &j) : throw_status(env, j.rc);
+}
+
 // zip(names, datas): a ZIP archive of datas[i] under names[i], two arrays of Uint8Array of one length (the façade takes the
 // file objects apart and encodes string names): one call, the bounded result (include/zes.h: zes_zipwrite)
 napi_value Zip(napi_env env, napi_callback_info info) {
@@ -1159,6 +1191,7 @@ napi_value ModuleInit(napi_env env, napi_value exports) {
       {"zip", swept<Zip>},
       {"pngInfo", swept<PngInfo>},
       {"pngDecodeBatch", swept<PngDecodeBatch>},
+      {"pngEncodeBatch", swept<PngEncodeBatch>},
       {"lastGunzipMembers", swept<LastGunzipMembers>},
       {"init", swept<Init>},
       {"initDevices", swept<InitDevices>},

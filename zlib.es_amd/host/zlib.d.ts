@@ -28,7 +28,7 @@ export declare type ZipIndex = { entries: ZipEntry[], raw: Uint8Array };
 export declare function zipIndex(file: Uint8Array): ZipIndex;
 export declare function zipRead(file: Uint8Array, index: ZipIndex, sel?: number[] | Uint32Array): BatchResult[];
 export declare function zip(files: { name: string | Uint8Array, data: Uint8Array }[]): Uint8Array;
-/** PNG images, read only: the header's facts (no device is touched), and batch decoding to scanlines (samples as stored, filters undone). */
+/** PNG images, reading: the header's facts (no device is touched), and batch decoding to scanlines (samples as stored, filters undone). */
 export declare type PngInfo = {
   width: number, height: number, depth: number, colourType: number, interlace: number, channels: number, bpp: number, rowBytes: number, size: number,
   idatCount: number, idatBytes: number, paletteOffset: number, paletteLength: number, transparencyOffset: number, transparencyLength: number,
@@ -38,6 +38,12 @@ export declare function pngInfo(file: Uint8Array): PngInfo;
 export declare function pngDecode(file: Uint8Array): PngImage;
 export declare type PngResult = PngImage | Error;
 export declare function pngDecodeBatch(files: Uint8Array[]): PngResult[];
+/** PNG images, writing: scanlines as pngDecode gives them to files, one batch on the device; filter 0..4 fixed, 6 adaptive, 5 (default) adaptive with restart rows. */
+export declare type PngSource = {
+  data: Uint8Array, width: number, height: number, colourType: number, depth?: number, filter?: number, palette?: Uint8Array, transparency?: Uint8Array,
+};
+export declare function pngEncode(image: PngSource): Uint8Array;
+export declare function pngEncodeBatch(images: PngSource[]): BatchResult[];
 export declare function init(device: number): void;
 export declare function initDevices(n?: number): number;
 export declare function trim(): void;

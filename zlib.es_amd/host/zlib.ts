@@ -29,6 +29,9 @@ type PngInfo = {
 };
 type PngImage = { info: PngInfo, data: Uint8Array };
 type PngResult = PngImage | Error;
+type PngSource = {
+  data: Uint8Array, width: number, height: number, colourType: number, depth?: number, filter?: number, palette?: Uint8Array, transparency?: Uint8Array,
+};
 /**
  * Extra (not in the reference API): `verify: true` makes an inflate form check the stream's Adler-32 trailer against its
  * result; a trailer that is missing or does not match is the Error "zes: checksum mismatch".  The reference ignores the
@@ -221,6 +224,49 @@ export function pngDecodeBatch(files: Uint8Array[]): PngResult[] {
 
 export function pngDecode(file: Uint8Array): PngImage {
   const got = pngDecodeBatch([file])[0];
+  if (got instanceof Error) throw got;
+  return got;
+}
+
+/**
+ * Extra (not in the reference API): PNG images, writing.  `pngEncodeBatch` writes images as PNG files in one batch on the
+ * device: one launch chooses and applies the scanline filters of every row of every image, one batch encode makes the zlib
+ * streams, one launch lays the files out and two more make the chunk CRCs.  An image is `{ data, width, height, colourType,
+ * depth = 8, filter = 5, palette, transparency }`: `data` the scanlines as `pngDecode` gives them (height * rowBytes bytes),
+ * `filter` 0..4 that type on every row, 6 libpng's adaptive choice, 5 the same with rows 0, 64, 128, ... None or Sub, which
+ * lets `pngDecode` work on the file's bands of 64 rows in parallel.  Element i of the result is the file or — instead of a
+ * throw — the `Error` that says why not.  The same images give the same bytes.  `pngEncode` is the batch of one image and
+ * throws its Error.
+ */
+export function pngEncodeBatch(images: PngSource[]): BatchResult[] {
+  if (!Array.isArray(images)) throw new TypeError('pngEncodeBatch(images): images must be an array of { data, width, height, colourType }');
+  const none = new Uint8Array(0);
+  const recs = new Uint8Array(16 * images.length);
+  const view = new DataView(recs.buffer);
+  const parts = [];
+  images.forEach((im, i) => {
+    if (!im || typeof im !== 'object') throw new TypeError('pngEncodeBatch(images): every image must be an object');
+    const plte = im.palette || none, trns = im.transparency || none;
+    if (!(plte instanceof Uint8Array) || !(trns instanceof Uint8Array) || plte.length > 65535 || trns.length > 65535)
+      throw new TypeError('pngEncodeBatch(images): palette and transparency must be Uint8Array of at most 65535 bytes');
+    for (const k of ['width', 'height', 'colourType'])
+      if (!Number.isInteger(im[k]) || im[k] < 0 || im[k] > 0xFFFFFFFF) throw new TypeError('pngEncodeBatch(images): ' + k + ' must be an unsigned integer');
+    view.setUint32(16 * i, im.width, true);
+    view.setUint32(16 * i + 4, im.height, true);
+    view.setUint8(16 * i + 8, im.depth === undefined ? 8 : im.depth);
+    view.setUint8(16 * i + 9, im.colourType);
+    view.setUint8(16 * i + 10, im.filter === undefined ? 5 : im.filter);
+    view.setUint16(16 * i + 12, plte.length, true);
+    view.setUint16(16 * i + 14, trns.length, true);
+    parts.push(plte, trns);
+  });
+  const aux = new Uint8Array(parts.reduce((n, p) => n + p.length, 0));
+  parts.reduce((at, p) => (aux.set(p, at), at + p.length), 0);
+  return addon.pngEncodeBatch(images.map((im) => im.data), recs, aux);
+}
+
+export function pngEncode(image: PngSource): Uint8Array {
+  const got = pngEncodeBatch([image])[0];
   if (got instanceof Error) throw got;
   return got;
 }
