@@ -1,4 +1,4 @@
-"""The checksum / gzip / BGZF / ZIP layer's launches: a case per seam of the layer, each at the smallest shape that reaches it, and
+"""The checksum / gzip / BGZF / ZIP / PNG layer's launches: a case per seam of the layer, each at the smallest shape that reaches it, and
 a runner that records what a call came to — status, result, and the launches per profiled name (zes_last_kernel_times).
 tests/test_gpu_container_launches.py compares the records with tests/golden/container_launches.json.
 
@@ -6,7 +6,8 @@ tests/test_gpu_container_launches.py compares the records with tests/golden/cont
 
 The launch counts are kept for this layer's kernels (LAYER); of a call's inflate and deflate kernels only the set of names.
 Every input of the checksum, gzip and BGZF cases is the library's own (its generators, its encoders); the ZIP archives are
-those of tests/_zip.py and tests/_zipwrite.py (CPython's bodies, the oracle's expected archive), built on the host.
+those of tests/_zip.py and tests/_zipwrite.py (CPython's bodies, the oracle's expected archive), built on the host, and the
+PNG files those of tests/_png.py.
 """
 import functools
 import gzip as pygzip
@@ -22,10 +23,12 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLDEN = os.path.join(ROOT, "tests", "golden", "container_launches.json")
 if os.path.join(ROOT, "tests") not in sys.path:  # (python -m tests._container_cases)
     sys.path.insert(0, os.path.join(ROOT, "tests"))
+import _png  # noqa: E402
 import _zip  # noqa: E402
 import _zipwrite  # noqa: E402
 
-LAYER = ("k_crc32", "k_crc32_seg", "k_adler", "k_adler_seg", "k_gz_walk", "k_gz_gather", "k_bgzf_mark", "k_bgzf_pack", "k_zip_stage", "k_zip_pack")
+LAYER = ("k_crc32", "k_crc32_seg", "k_adler", "k_adler_seg", "k_gz_walk", "k_gz_gather", "k_bgzf_mark", "k_bgzf_pack", "k_zip_stage", "k_zip_pack",
+         "k_png_walk", "k_png_unfilter", "k_png_filter", "k_png_pack", "k_crc32_put")
 CHUNK = 65280  # ZES_BGZF_CHUNK
 
 # (alignment, length) of the checksum cases' buffers: a start inside a 16-byte piece, a tail behind the last 16-byte boundary,
@@ -38,7 +41,8 @@ CASES = ["crc32 batch", "adler32 batch", "crc32 batch, every length 0", "adler32
          "inflate_batch checked",
          "zip_read_tensor standard", "zip_read standard", "zip_read_tensor failures", "zip_read failures", "zip_read_tensor stored only",
          "zip_read_tensor one rejected", "zip_read_tensor count 0", "zipwrite_tensor nine pieces", "zipwrite_tensor refused only", "zipwrite nine",
-         "bgzip_tensor 1 byte", "bgzf_read_tensor body damaged", "bgzf_read_tensor crc damaged", "gunzip_tensor bgzf crc damaged"]
+         "bgzip_tensor 1 byte", "bgzf_read_tensor body damaged", "bgzf_read_tensor crc damaged", "gunzip_tensor bgzf crc damaged",
+         "png_decode_tensor three", "png_decode three"]
 
 
 def _pkg():
@@ -252,10 +256,45 @@ def _checked(z, gpu, on_device):
                    bytes_equal=[host[o:o + len(p)].tobytes() == p for o, p in zip(out_off, plains)])
 
 
+@functools.lru_cache(maxsize=None)
+def png_three():
+    """Three small files of tests/_png.py: a good one, one whose zlib stream has a flipped Adler-32, another good one."""
+    a, b = _png.neighbours()
+    bad = [c for c in _png.damage() if c.name == "flipped Adler-32"]
+    assert len(bad) == 1 and bad[0].status == _png.ZES_E_CHECKSUM
+    return [a, bad[0], b]
+
+
+def _png_decode(z, gpu, on_device):
+    import torch
+
+    cases = png_three()
+    if on_device:
+        blobs = [np.frombuffer(c.blob, dtype=np.uint8) for c in cases]
+        in_off = np.cumsum([0] + [b.size + 3 for b in blobs])[:-1].tolist()  # (the second and third file off the 16-byte boundaries)
+        flat = np.zeros(in_off[-1] + blobs[-1].size, dtype=np.uint8)
+        for o, b in zip(in_off, blobs):
+            flat[o:o + b.size] = b
+        off = np.cumsum([0] + [len(c.want) + 5 for c in cases])[:-1].tolist()
+        out = torch.zeros(off[-1] + len(cases[-1].want), dtype=torch.uint8, device=gpu)
+        status, got, _ = _call(z, lambda: z.png_decode_tensor(_dev(flat, gpu, lead=1), in_off, [b.size for b in blobs], out=out, off=off))
+        host = got[0].cpu().numpy()
+        out_len, st = got[2], got[3]
+        datas = [host[o:o + n].tobytes() for o, n in zip(off, out_len)]
+    else:
+        status, res, _ = _call(z, lambda: z.png_decode_batch([c.blob for c in cases]))
+        st = [r.code if isinstance(r, z.ZlibEsError) else 0 for r in res]
+        datas = [b"" if s else r[1].tobytes() for r, s in zip(res, st)]
+        out_len = [len(d) for d in datas]
+    return _record(z, status, statuses=st, out_len=out_len, bytes_equal=[d == c.want if s == 0 else None for d, s, c in zip(datas, st, cases)])
+
+
 def run_case(z, gpu, name):
     """A case's record; profiling is on for the call and off again behind it."""
     z.set_profiling(True)
     try:
+        if name.split()[0] in ("png_decode_tensor", "png_decode"):
+            return _png_decode(z, gpu, name.startswith("png_decode_tensor"))
         if name.split()[0] in ("zip_read_tensor", "zip_read"):
             on_device = name.startswith("zip_read_tensor")
             if name.endswith("stored only"):
@@ -279,7 +318,7 @@ def run_case(z, gpu, name):
         if name == "bgzip_tensor":
             return _bgzip(z, gpu, 70000, 0)
         if name == "bgzip_tensor pieces":
-            return _bgzip(z, gpu, 4 * CHUNK + 1, z.ZES_F_PIECES)  # five members: two groups of BGZF_GROUP_PIECES
+            return _bgzip(z, gpu, 4 * CHUNK + 1, z.ZES_F_PIECES)  # five members: two groups of ENC_GROUP_PIECES
         if name.startswith("bgzf_index_tensor"):
             return _index(z, gpu, z.ZES_F_INDEX_WALK if name.endswith("walk") else 0)
         if name in ("bgzf_read_tensor", "bgzf_read"):

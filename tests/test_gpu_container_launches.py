@@ -1,4 +1,4 @@
-"""Which launches the checksum / gzip / BGZF / ZIP layer makes, pinned: every case of tests/_container_cases.py — status, result,
+"""Which launches the checksum / gzip / BGZF / ZIP / PNG layer makes, pinned: every case of tests/_container_cases.py — status, result,
 the launch count of each of the layer's kernels and the names of the inflate and deflate kernels beside them — against
 tests/golden/container_launches.json, which was recorded from the commits in front of the layer's two refactors (NOTES.md
 says which).  A driver that launched a gather twice, walked a file on the device that the host had walked already, or ran a
@@ -40,6 +40,12 @@ def facts(name, rec):
             assert rec["status"] == -21 and n.get("k_crc32_seg") == 1, rec
         return
     assert rec["status"] == 0, rec
+    if name.split()[0] in ("png_decode_tensor", "png_decode"):
+        # good, flipped Adler-32, good: one launch of each step for the batch, the walk only where the files are on the device
+        assert rec["statuses"] == [0, -21, 0] and rec["bytes_equal"] == [True, None, True] and rec["out_len"][1] == 0, rec
+        assert n.get("k_png_walk") == (1 if name.startswith("png_decode_tensor") else None), rec
+        assert n.get("k_crc32_seg") == 1 and n.get("k_adler_seg") == 1 and n.get("k_png_unfilter") == 1 and n.get("k_gz_gather", 0) >= 1 and rec["others"], rec
+        return
     if name.split()[0] in ("zip_read_tensor", "zip_read"):
         # every status is the one tests/_zip.py expects of the entry (entry_rule), the bytes are the entries' own
         assert all(rec["expected"]) and all(b for b, s in zip(rec["bytes_equal"], rec["statuses"]) if s == 0), rec

@@ -283,6 +283,22 @@ int ensure(DevBuf& b, size_t bytes) {
   return ZES_OK;
 }
 
+// up to the next 16-byte boundary: the places of a pooled buffer start at one
+uint64_t gz_up16(uint64_t v) { return (v + 15) & ~15ull; }
+
+// Host memory that a copy queued on the stream reads or writes outlives the stream's work on every way out: a function
+// that copies from or to memory of its own declares that memory first and a Drain BEHIND it (locals go in reverse order of
+// declaration: the guard's wait comes first, then the memory), and calls done() behind its own last synchronisation.  On any
+// other way out (HIPCHK, a helper's status) the guard lets the stream finish before the memory goes, and clears a HIP error
+// from that wait (the call's status is the one on its way already).
+struct Drain {
+  bool armed = true;
+  void done() { armed = false; }
+  ~Drain() {
+    if (armed && hipStreamSynchronize(g.stream) != hipSuccess) (void)hipGetLastError();
+  }
+};
+
 int init_locked(int device) {
   if (g.ready) {
     if (device >= 0 && device != g.device) return ZES_E_ARG;
@@ -1532,7 +1548,7 @@ int t1_publish(T1Group& t) {
   }
   if (segs.size() == 1) return cand_end_bit(segs[0].src_off / sizeof(ZesCandRes), &t.jobs[who[0]].end_bit);
   if (!segs.empty()) {
-    const size_t o_dst = (sizeof(ZesGzSeg) * segs.size() + 15) & ~(size_t)15;
+    const size_t o_dst = (size_t)gz_up16(sizeof(ZesGzSeg) * segs.size());
     for (size_t k = 0; k < segs.size(); k++) segs[k].dst_off = o_dst + 8 * k;
     if ((rc = ensure(g.crcseg, o_dst + 8 * segs.size()))) return rc;
     HIPCHK(hipMemcpyAsync(g.crcseg.p, segs.data(), sizeof(ZesGzSeg) * segs.size(), hipMemcpyHostToDevice, g.stream));
@@ -3428,25 +3444,75 @@ int zes_inflate_alloc(const uint8_t* in, uint64_t c, zes_alloc_fn alloc, void* u
 }
 
 // ---- batch over host pointers: one arena up, the device batch, results down ----
-// a buffer's slot in the arena that goes up: its bytes and 64 of slack behind them (as stage_in leaves), to a 16-byte boundary
-static uint64_t arena_slot(uint64_t len) { return (len + 64 + 15) & ~15ull; }
+// The trip of every form that takes host pointers, stated once (under the lock).  place() gives a piece of input its place in
+// the pool that goes up, room() gives an output its place in the pool that the batch writes: the bytes and `slack` more
+// behind them, from one 16-byte boundary to the next (16 for the container forms; 64, as stage_in leaves, for the plain
+// batch forms, whose streams the decoders read some way past).  up() grows the pools and sends the placed pieces.  hand_out()
+// takes every item still at ZES_OK to the caller's allocator, whose null answer is the item's ZES_E_ARG, and brings it down:
+// out_len[i] is its size then, and 0 for every other item.
+struct HostBatch {
+  DevBuf &in, &out;
+  const uint64_t slack;
+  uint64_t tin = 0, tout = 0;
+  struct Piece { uint64_t at; const uint8_t* p; uint64_t n; };  // (p null: the place alone)
+  std::vector<Piece> pieces;
+  HostBatch(DevBuf& in_, DevBuf& out_, uint64_t slack_ = 16) : in(in_), out(out_), slack(slack_) {}
+  uint64_t place(const uint8_t* p, uint64_t n) {
+    pieces.push_back(Piece{tin, p, n});
+    tin += gz_up16(n) + slack;
+    return pieces.back().at;
+  }
+  uint64_t room(uint64_t n) {
+    const uint64_t at = tout;
+    tout += gz_up16(n) + slack;
+    return at;
+  }
+  int up() {  // (a form that asked for no room lays its outputs out itself)
+    int rc;
+    if ((rc = ensure(in, tin + 64)) || (tout && (rc = ensure(out, tout + 64)))) return rc;
+    for (const Piece& q : pieces)
+      if (q.p && (rc = upload((uint8_t*)in.p + q.at, q.p, q.n))) return rc;
+    return ZES_OK;
+  }
+  const uint8_t* d_in() const { return (const uint8_t*)in.p; }
+  uint8_t* d_out() const { return (uint8_t*)out.p; }
+  int hand_out(uint32_t count, zes_alloc_fn alloc, void* user, int32_t* status, uint64_t* out_len, const std::function<uint64_t(uint32_t)>& size_of,
+               const std::function<uint64_t(uint32_t)>& off_of) {
+    int rc;
+    for (uint32_t i = 0; i < count; i++) {
+      if (status[i] != ZES_OK) {
+        out_len[i] = 0;
+        continue;
+      }
+      const uint64_t n = size_of(i);
+      uint8_t* to = alloc(user, i, n);
+      out_len[i] = to ? n : 0;
+      if (!to) {
+        status[i] = ZES_E_ARG;
+        continue;
+      }
+      // (a short result is only enqueued: one synchronisation behind the loop serves them all)
+      if ((rc = download(to, d_out() + off_of(i), n, nullptr, false))) return rc;
+    }
+    HIPCHK(hipStreamSynchronize(g.stream));
+    return ZES_OK;
+  }
+};
+
 static int deflate_batch_one(const uint8_t* const* in, const uint64_t* in_len, uint8_t* const* out, const uint64_t* out_cap,
                              uint64_t* out_len, int32_t* status, uint32_t count) {
   LOCK_READY();
+  HostBatch hb(g.st_in, g.st_out, 64);
   std::vector<uint64_t> in_off(count), o_off(count), o_cap(count), dl(count);
-  uint64_t tin = 0, tout = 0;
+  uint64_t tout = 0;
   for (uint32_t i = 0; i < count; i++) {
     if (!in[i] && in_len[i]) return ZES_E_ARG;
-    in_off[i] = tin;
-    tin += arena_slot(in_len[i]);
+    in_off[i] = hb.place(deflate_throws(in_len[i]) ? nullptr : in[i], in_len[i]);
     o_off[i] = tout;
     o_cap[i] = deflate_bound(in_len[i]);
-    tout += (o_cap[i] + 15) & ~15ull;
+    tout += gz_up16(o_cap[i]);
   }
-  if ((rc = ensure(g.st_in, tin + 64))) return rc;
-  if ((rc = ensure(g.st_out, tout + 64))) return rc;
-  for (uint32_t i = 0; i < count; i++)
-    if (!deflate_throws(in_len[i]) && (rc = upload((uint8_t*)g.st_in.p + in_off[i], in[i], in_len[i]))) return rc;
+  if ((rc = hb.up()) || (rc = ensure(g.st_out, tout + 64))) return rc;
   rc = deflate_batch_core((const uint8_t*)g.st_in.p, in_off.data(), in_len, (uint8_t*)g.st_out.p, o_off.data(), o_cap.data(), dl.data(), status, count);
   if (rc) return rc;
   for (uint32_t i = 0; i < count; i++) {
@@ -3464,23 +3530,20 @@ static int deflate_batch_one(const uint8_t* const* in, const uint64_t* in_len, u
 static int inflate_batch_alloc_one(const uint8_t* const* in, const uint64_t* in_len, zes_alloc_fn alloc, void* user, uint64_t* out_len,
                                    int32_t* status, uint32_t count, uint32_t flags) {
   LOCK_READY();
+  HostBatch hb(g.st_in, g.st_out, 64);
   std::vector<uint64_t> in_off(count), o_off(count), o_cap(count);
   std::vector<uint8_t> firsts(count);
   const bool check = (flags & ZES_F_CHECK_ADLER) != 0;
-  uint64_t tin = 0;
   for (uint32_t i = 0; i < count; i++) {
     if (!in[i] && in_len[i]) return ZES_E_ARG;
-    in_off[i] = tin;
-    tin += arena_slot(in_len[i]);
+    in_off[i] = hb.place(in[i], in_len[i]);
     firsts[i] = in_len[i] ? in[i][0] : 0;
     // first guess at the result size: a reference-made stream of c bytes rarely inflates beyond 4c; the retry below has exact sizes
     o_cap[i] = std::max<uint64_t>(in_len[i] * 4, 1 << 16);
     out_len[i] = 0;
     status[i] = ZES_OK;
   }
-  if ((rc = ensure(g.st_in, tin + 64))) return rc;
-  for (uint32_t i = 0; i < count; i++)
-    if ((rc = upload((uint8_t*)g.st_in.p + in_off[i], in[i], in_len[i]))) return rc;
+  if ((rc = hb.up())) return rc;
   std::vector<uint32_t> todo(count);
   for (uint32_t i = 0; i < count; i++) todo[i] = i;
   for (int attempt = 0; attempt < 8 && !todo.empty(); attempt++) {
@@ -3491,7 +3554,7 @@ static int inflate_batch_alloc_one(const uint8_t* const* in, const uint64_t* in_
     for (size_t k = 0; k < todo.size(); k++) {
       const uint32_t i = todo[k];
       o_off[i] = tout;
-      tout += (o_cap[i] + 15) & ~15ull;
+      tout += gz_up16(o_cap[i]);
       jobs[k] = InfJob{in_off[i], in_len[i], o_off[i], o_cap[i], 0, ZES_OK, 0};
       jobs[k].want_end = check;
       fb[k] = firsts[i];
@@ -4140,21 +4203,47 @@ static int call_done(int rc, bool clear) {
   return rc;
 }
 
-// ---- A group of buffers encoded for a container: the step that bgzip_core (members) and zipwrite_groups (entries) share ----
-// The caller lays the group out: buffer k is d_in[in_off[k], + in_len[k]) and has the 16-byte aligned slot [o_off[k], + o_cap[k])
-// of g.gz_bodies, o_cap[k] == 0 for a buffer that the encoder is spared (the caller's rule).  encode() gives every buffer its
+// ---- A group of buffers encoded for a container: the step that bgzip_core (members), zipwrite_core (entries) and
+// pngwrite_core (images) share ----
+// Buffer k of a group is d_in[in_off[k], + in_len[k]) and has the 16-byte aligned slot [o_off[k], + o_cap[k]) of g.gz_bodies,
+// o_cap[k] == 0 for a buffer that the encoder is spared; the slots take `slots` bytes.  form() lays a group out by the
+// writers' rule; bgzip_core, whose chunks have one fixed slot, fills the three itself.  encode() gives every buffer its
 // CRC-32 by one segmented launch (unless the caller has no use for them: crcs) and encodes the group by one deflate_batch_core call (none when the slots take no bytes: no
 // times of its own to keep); raw[k] is then the length of buffer k's raw stream, which starts at o_off[k] + 2 (78 9C in
 // front, the Adler-32 behind), and 0 for a spared buffer.
 // A result beyond the caller's capacity, by room(): every group is still encoded (the size needed is the answer), and from
 // the first group that does not fit whole nothing more is written.
+constexpr uint32_t ENC_GROUP = 1024;                     // buffers encoded at once: a block's scratch each, what zes_deflate_dev pools for 128 MiB ...
+constexpr uint32_t ENC_GROUP_PIECES = 4;                 // ... under ZES_F_PIECES
+constexpr uint64_t ENC_GROUP_SLOTS = 256ull << 20;       // ... and the bytes of their encoder slots (1024 buffers of up to 64 KiB take half of it)
+constexpr uint64_t ENC_GROUP_SLOTS_PIECES = 1ull << 20;  // ... under ZES_F_PIECES: two buffers of 300000 bytes do not share a group
+static_assert(ENC_GROUP <= DEFLATE_TABLE_BUFS && ENC_GROUP <= DEFLATE_DIRECT_BUFS, "a group's buffer table and results go through the page-locked area");
 struct EncGroup {
+  const uint32_t group;
+  const uint64_t group_slots;
   std::vector<uint64_t> o_off, o_cap, o_len, raw;
   std::vector<int32_t> status;
   std::vector<ZesCrcSeg> csegs;
   std::vector<uint32_t> crc;
   bool fits = true;
-  explicit EncGroup(size_t most) : o_off(most), o_cap(most), o_len(most), raw(most), status(most), csegs(most), crc(most) {}
+  // for a call of `items` buffers in all
+  EncGroup(uint32_t flags, uint64_t items)
+      : group((flags & ZES_F_PIECES) ? ENC_GROUP_PIECES : ENC_GROUP), group_slots((flags & ZES_F_PIECES) ? ENC_GROUP_SLOTS_PIECES : ENC_GROUP_SLOTS),
+        o_off((size_t)std::min<uint64_t>(group, items)), o_cap(o_off.size()), o_len(o_off.size()), raw(o_off.size()), status(o_off.size()),
+        csegs(o_off.size()), crc(o_off.size()) {}
+  // The next group of the buffers whose lengths are len[0, left): up to `group` of them whose encoder slots take up to
+  // group_slots bytes, and one at least; a length that the encoder refuses has no slot.  Returns how many it takes, and
+  // *slots: the bytes of their slots, for encode().
+  uint32_t form(const uint64_t* len, uint64_t left, uint64_t* slots) {
+    uint32_t cnt = 0;
+    for (*slots = 0; cnt < left && cnt < group; cnt++) {
+      const uint64_t slot = deflate_throws(len[cnt]) ? 0 : gz_up16(deflate_bound(len[cnt]));
+      if (cnt && *slots + slot > group_slots) break;
+      o_off[cnt] = *slots;
+      *slots += o_cap[cnt] = slot;
+    }
+    return cnt;
+  }
   int encode(const uint8_t* d_in, const uint64_t* in_off, const uint64_t* in_len, uint32_t cnt, uint64_t slots, bool crcs = true) {
     int rc;
     for (uint32_t k = 0; k < cnt; k++) csegs[k] = ZesCrcSeg{in_off[k], in_len[k]};
@@ -4175,20 +4264,17 @@ struct EncGroup {
 
 // ---- BGZF writer: the input in chunks of ZES_BGZF_CHUNK bytes, a gzip member each, and the end-of-file marker ----
 static const uint8_t kBgzfEof[28] = {0x1f, 0x8b, 8, 4, 0, 0, 0, 0, 0, 0xff, 6, 0, 'B', 'C', 2, 0, 0x1b, 0, 3, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-constexpr uint32_t BGZF_GROUP = 1024;       // members encoded at once: a block's scratch each, what zes_deflate_dev pools for 128 MiB
-constexpr uint32_t BGZF_GROUP_PIECES = 4;   // ... under ZES_F_PIECES
 constexpr uint64_t BGZF_MEMBER_MAX = ZES_BGZF_HLEN + 5 + ZES_BGZF_CHUNK + 8;  // a full chunk as a stored block: 65311
 constexpr uint64_t BGZF_N_MAX = 1ull << 62;  // (the bound of a longer input does not fit 64 bits)
 static_assert(BGZF_MEMBER_MAX <= 65536, "BSIZE has 16 bits");
-static_assert(BGZF_GROUP <= DEFLATE_TABLE_BUFS && BGZF_GROUP <= DEFLATE_DIRECT_BUFS, "a group's buffer table and results go through the page-locked area");
 static uint64_t bgzip_members(uint64_t n) { return (n + ZES_BGZF_CHUNK - 1) / ZES_BGZF_CHUNK + 1; }
 static uint64_t bgzip_bound(uint64_t n) {
   const uint64_t tail = n % ZES_BGZF_CHUNK;
   return n / ZES_BGZF_CHUNK * BGZF_MEMBER_MAX + (tail ? tail + ZES_BGZF_HLEN + 5 + 8 : 0) + sizeof kBgzfEof;
 }
 
-// The members of d_in[0, n) and the marker into d_out[0, cap), group by group (EncGroup): every chunk has a slot of its own
-// size class, a chunk of one byte, which the encoder refuses, is spared, and the call is made whenever the group has members.
+// The members of d_in[0, n) and the marker into d_out[0, cap), group by group (EncGroup, ENC_GROUP members or ENC_GROUP_PIECES):
+// every chunk has a slot of its own size class, a chunk of one byte, which the encoder refuses, is spared, and the call is made whenever the group has members.
 // The sizes come back, the host chooses stream or stored block per member and k_bgzf_pack puts the members in their places.
 // The marker is the last launch's last record.  A result beyond cap: EncGroup's rule.  member_off: null, or where every
 // member starts, the marker's last.
@@ -4196,12 +4282,12 @@ static int bgzip_core(const uint8_t* d_in, uint64_t n, uint8_t* d_out, uint64_t 
   int rc;
   g.carry.clear();
   const uint64_t nm = bgzip_members(n) - 1;  // (without the marker)
-  const uint64_t group = (flags & ZES_F_PIECES) ? BGZF_GROUP_PIECES : BGZF_GROUP;
-  const uint64_t slot = (deflate_bound(ZES_BGZF_CHUNK) + 15) & ~(uint64_t)15;
+  const uint64_t slot = gz_up16(deflate_bound(ZES_BGZF_CHUNK));
   std::vector<ZesBgzfRec> recs((size_t)nm + 1);  // (of the whole call: uploads read it until the last synchronisation)
-  const size_t gmax = (size_t)std::min(group, nm);
-  std::vector<uint64_t> in_off(gmax), in_len(gmax);
-  EncGroup eg(gmax);
+  EncGroup eg(flags, nm);
+  const uint64_t group = eg.group;
+  std::vector<uint64_t> in_off(eg.o_off.size()), in_len(eg.o_off.size());
+  Drain drain;  // (behind recs, eg and the group's tables)
   uint64_t total = 0;
   for (uint64_t m0 = 0;; m0 += group) {
     const uint32_t cnt = (uint32_t)std::min(group, nm - m0);
@@ -4241,6 +4327,7 @@ static int bgzip_core(const uint8_t* d_in, uint64_t n, uint8_t* d_out, uint64_t 
     if (last) break;
   }
   HIPCHK(hipStreamSynchronize(g.stream));
+  drain.done();
   if (member_off)
     for (uint64_t k = 0; k <= nm; k++) member_off[k] = recs[(size_t)k].dst_off;
   *out_len = total;
@@ -4469,7 +4556,6 @@ struct GzPart {
 // A body of `len` bytes stands in gz_bodies behind a 78 9C, in a slot of gz_slot_in(len) bytes (the decoders read whole 16-byte
 // groups, and some way past a stream's end); an output of m bytes that cannot be decoded in place gets gz_slot_out(m) bytes of
 // gz_outs, of which the job may write gz_slot_cap(m).
-static uint64_t gz_up16(uint64_t v) { return (v + 15) & ~15ull; }
 static uint64_t gz_slot_in(uint64_t len) { return gz_up16(2 + len) + 64; }
 static uint64_t gz_slot_cap(uint64_t m) { return std::max<uint64_t>(gz_up16(m), 16); }
 static uint64_t gz_slot_out(uint64_t m) { return gz_slot_cap(m) + 16; }
@@ -4889,7 +4975,7 @@ static int bgzf_read_args(const uint8_t* in, const uint64_t* coff, const uint64_
   return ZES_OK;
 }
 
-// a call that decodes nothing: zes_last_gunzip_members reports 0 after it.  (Not one helper with zip_read_none: this one is
+// a call that decodes nothing: zes_last_gunzip_members reports 0 after it.  (Not one helper with call_none: this one is
 // also the way out of a call whose plan failed, and leaves the times alone as every call does that ends in its checks.)
 static void bgzf_read_none() {
   std::lock_guard<std::mutex> lk(g_mu);
@@ -5069,9 +5155,9 @@ static int zip_read_args(const uint8_t* in, uint64_t c, const zes_zip_entry* ent
   return ZES_OK;
 }
 
-// a call with nothing to extract: no device work; the times and the tier of the call before do not stay (a successful call
-// that launches nothing reports no launch; bgzf_read_none says why the two differ)
-static void zip_read_none() {
+// a ZIP or PNG call with nothing to do: no device work; the times and the tier of the call before do not stay (a successful
+// call that launches nothing reports no launch; bgzf_read_none says why the two differ)
+static void call_none() {
   std::lock_guard<std::mutex> lk(g_mu);
   g.last_tier = 0;
   collect_times();
@@ -5103,6 +5189,8 @@ static int zip_read_core(const uint8_t* d_src, const std::vector<ZipPart>& ps, u
   if (!n) return ZES_OK;
   if ((rc = body_plan(bs, dst, 0, true))) return rc;
   std::vector<ZesZipRec> recs(n);
+  std::vector<ZesZipVerdict> verd(n);
+  Drain drain;  // (behind recs, which an upload reads, and verd, which the read-back writes)
   uint64_t longest = 0;
   for (uint32_t q = 0; q < n; q++) {
     const ZipPart& p = ps[st[q]];
@@ -5129,9 +5217,9 @@ static int zip_read_core(const uint8_t* d_src, const std::vector<ZipPart>& ps, u
                        d_verd);
   }
   HIPCHK(hipGetLastError());
-  std::vector<ZesZipVerdict> verd(n);
   HIPCHK(hipMemcpyAsync(verd.data(), d_verd, sizeof(ZesZipVerdict) * (size_t)n, hipMemcpyDeviceToHost, g.stream));
   HIPCHK(hipStreamSynchronize(g.stream));
+  drain.done();
   for (uint32_t q = 0; q < n; q++) bs[q].status = verd[q].status;
   rc = body_run(bs, dst, flags & ZES_F_PIECES, false, nullptr);
   for (uint32_t q = 0; q < n; q++) status[st[q]] = bs[q].status;
@@ -5144,7 +5232,7 @@ int zes_zip_read_dev(const uint8_t* d_in, uint64_t c, const zes_zip_entry* ent, 
   if (const int arc = zip_read_args(d_in, c, ent, nent, sel, count, out_len, status, flags)) return arc;
   if (count && !out_off) return ZES_E_ARG;
   if (!count) {
-    zip_read_none();
+    call_none();
     return ZES_OK;
   }
   std::vector<ZipPart> ps(count);
@@ -5168,59 +5256,33 @@ int zes_zip_read_alloc(const uint8_t* in, uint64_t c, const zes_zip_entry* ent, 
   if (const int arc = zip_read_args(in, c, ent, nent, sel, count, out_len, status, flags)) return arc;
   if (!alloc) return ZES_E_ARG;
   if (!count) {
-    zip_read_none();
+    call_none();
     return ZES_OK;
   }
   LOCK_READY();
   // only the selected entries' bytes cross to the device: header, name, extra field and body in one piece, the directory's
-  // copy of the name in another, each at a 16-byte boundary of g.gz_in
+  // copy of the name in another
+  HostBatch hb(g.gz_in, g.gz_acc);
   std::vector<ZipPart> ps(count);
-  std::vector<uint64_t> take(count, 0);
-  uint64_t tin = 0, tout = 0;
   for (uint32_t i = 0; i < count; i++) {
     const zes_zip_entry& z = ent[sel ? sel[i] : i];
     out_len[i] = 0;
     status[i] = zip_entry_alone(z, c);
-    ps[i] = ZipPart{z, 0, 0, 0, tout};
+    ps[i] = ZipPart{z, 0, 0, 0, 0};
     if (status[i]) continue;
     ps[i].limit = c - z.hdr_off;
-    take[i] = std::min<uint64_t>(ps[i].limit, 30ull + z.name_len + get_le16(in + z.hdr_off + 28) + z.csize);
-    ps[i].hdr_at = tin;
-    tin += ((take[i] + 15) & ~15ull) + 16;
-    ps[i].name_at = tin;
-    tin += (((uint64_t)z.name_len + 15) & ~15ull) + 16;
-    tout += (((uint64_t)z.usize + 15) & ~15ull) + 16;
+    ps[i].hdr_at = hb.place(in + z.hdr_off, std::min<uint64_t>(ps[i].limit, 30ull + z.name_len + get_le16(in + z.hdr_off + 28) + z.csize));
+    ps[i].name_at = hb.place(in + z.name_pos, z.name_len);
+    ps[i].dst_off = hb.room(z.usize);
   }
-  if ((rc = ensure(g.gz_in, tin + 64)) || (rc = ensure(g.gz_acc, tout + 64))) return rc;
-  for (uint32_t i = 0; i < count; i++) {
-    if (status[i]) continue;
-    if ((rc = upload((uint8_t*)g.gz_in.p + ps[i].hdr_at, in + ps[i].z.hdr_off, take[i]))) return rc;
-    if ((rc = upload((uint8_t*)g.gz_in.p + ps[i].name_at, in + ps[i].z.name_pos, ps[i].z.name_len))) return rc;
-  }
-  if ((rc = call_done(zip_read_core((const uint8_t*)g.gz_in.p, ps, (uint8_t*)g.gz_acc.p, status, flags), true))) return rc;
-  for (uint32_t i = 0; i < count; i++) {
-    if (status[i]) continue;
-    uint8_t* to = alloc(user, i, ps[i].z.usize);
-    if (!to) {
-      status[i] = ZES_E_ARG;
-      continue;
-    }
-    // (a short result is only enqueued: one synchronisation behind the loop serves them all)
-    if ((rc = download(to, (const uint8_t*)g.gz_acc.p + ps[i].dst_off, ps[i].z.usize, nullptr, false))) return rc;
-    out_len[i] = ps[i].z.usize;
-  }
-  HIPCHK(hipStreamSynchronize(g.stream));
-  return ZES_OK;
+  if ((rc = hb.up())) return rc;
+  if ((rc = call_done(zip_read_core(hb.d_in(), ps, hb.d_out(), status, flags), true))) return rc;
+  return hb.hand_out(count, alloc, user, status, out_len, [&](uint32_t i) { return (uint64_t)ps[i].z.usize; }, [&](uint32_t i) { return ps[i].dst_off; });
 }
 
 // ---- ZIP writer (include/zes.h: "zes_zipwrite*"): local headers, names and bodies by k_zip_pack, the directory by the host ----
-constexpr uint32_t ZIPW_GROUP = 1024;             // entries encoded at once ...
-constexpr uint32_t ZIPW_GROUP_PIECES = 4;         // ... under ZES_F_PIECES
-constexpr uint64_t ZIPW_GROUP_SLOTS = 256ull << 20;  // ... and the bytes of their encoder slots (1024 entries of up to 64 KiB take half of it)
-constexpr uint64_t ZIPW_GROUP_SLOTS_PIECES = 1ull << 20;  // ... under ZES_F_PIECES: two entries of 300000 bytes do not share a group
 constexpr uint32_t ZIPW_COUNT_MAX = 65534;        // (65535 is ZIP64's mark)
 constexpr uint64_t ZIPW_LEN_MAX = 0xFFFFFFFEull;  // (as is 0xFFFFFFFF in a size or an offset)
-static_assert(ZIPW_GROUP <= DEFLATE_TABLE_BUFS && ZIPW_GROUP <= DEFLATE_DIRECT_BUFS, "a group's buffer table and results go through the page-locked area");
 
 static uint64_t zipwrite_bound(const uint64_t* in_len, const uint16_t* name_len, uint32_t count) {
   uint64_t b = ZIP_END;
@@ -5257,52 +5319,38 @@ static int zipwrite_args(const std::function<bool(uint32_t)>& data, const uint64
 }
 
 // The archive of the entries d_in[in_off[i], + in_len[i]) into d_out[0, cap), group by group as bgzip_core goes: a group is
-// up to ZIPW_GROUP entries (ZIPW_GROUP_PIECES under ZES_F_PIECES) whose encoder slots take up to ZIPW_GROUP_SLOTS bytes (ZIPW_GROUP_SLOTS_PIECES),
-// and one entry at least.  The group goes through EncGroup (an entry that the encoder refuses is spared and has no slot, so
+// what EncGroup::form takes (an entry that the encoder refuses is spared and has no slot, so
 // a group of such entries makes no encoder call); the sizes come back, the host chooses the method (8 when the raw stream
 // is shorter than the entry, else 0) and the places, and one k_zip_pack launch writes the group's headers, names and bodies.
 // The directory and the end record are made here and go up in one copy behind the last group.  g.gz_tab holds the names
 // (uploaded once, padded to whole 16-byte groups) and behind them the group's records.  A result beyond cap: EncGroup's
 // rule, with the directory as one more group.  ent: null, or the records zes_zip_index lists for the result.
-// The host memory that the call's asynchronous uploads read (the padded names, every group's records, the directory) is the
-// caller's, zipwrite_core's, which lets the stream finish before it gives it up on any way out.
-struct ZipwHost {
-  std::vector<uint8_t> names, cd;
-  std::vector<ZesZipPackRec> recs;
-};
-static int zipwrite_groups(ZipwHost& hm, const uint8_t* d_in, const uint64_t* in_off, const uint64_t* in_len, const uint8_t* names, const uint16_t* name_len, uint32_t count,
+// The host memory that the call's asynchronous uploads read (the padded names, every group's records, the directory, the
+// encoder's tables) is declared in front of a Drain.  ZES_OK and ZES_E_NOSPACE come from behind the last synchronisation.
+static int zipwrite_core(const uint8_t* d_in, const uint64_t* in_off, const uint64_t* in_len, const uint8_t* names, const uint16_t* name_len, uint32_t count,
                          uint8_t* d_out, uint64_t cap, uint64_t* out_len, zes_zip_entry* ent, uint32_t flags) {
   int rc;
   g.carry.clear();
-  const uint32_t group = (flags & ZES_F_PIECES) ? ZIPW_GROUP_PIECES : ZIPW_GROUP;
-  const uint64_t group_slots = (flags & ZES_F_PIECES) ? ZIPW_GROUP_SLOTS_PIECES : ZIPW_GROUP_SLOTS;
+  std::vector<uint8_t> hnames, cd;
+  // (of the whole call: uploads read it until the last synchronisation.  A group has one entry at least and a closing record:
+  // at most `count` groups, whichever bound ends them)
+  std::vector<ZesZipPackRec> recs(2 * (size_t)count + 1);
+  EncGroup eg(flags, count);
+  Drain drain;  // (behind hnames, cd, recs and eg)
   std::vector<uint32_t> name_off((size_t)count + 1, 0);
   for (uint32_t i = 0; i < count; i++) name_off[i + 1] = name_off[i] + name_len[i];  // (65534 names of 65535 bytes fit 32 bits)
-  const size_t names_pad = ((size_t)name_off[count] + 15) & ~(size_t)15;
-  std::vector<uint8_t>& hnames = hm.names;
+  const size_t names_pad = (size_t)gz_up16(name_off[count]);
   hnames.assign(names_pad, 0);
   if (name_off[count]) memcpy(hnames.data(), names, name_off[count]);
-  if ((rc = ensure(g.gz_tab, names_pad + sizeof(ZesZipPackRec) * ((size_t)std::min(group, count) + 1)))) return rc;
+  if ((rc = ensure(g.gz_tab, names_pad + sizeof(ZesZipPackRec) * (eg.o_off.size() + 1)))) return rc;
   if (names_pad) HIPCHK(hipMemcpyAsync(g.gz_tab.p, hnames.data(), names_pad, hipMemcpyHostToDevice, g.stream));
   ZesZipPackRec* d_recs = (ZesZipPackRec*)((uint8_t*)g.gz_tab.p + names_pad);
   std::vector<zes_zip_entry> z(count);
-  // (of the whole call: uploads read it until the last synchronisation.  A group has one entry at least and a closing record:
-  // at most `count` groups, whichever bound ends them)
-  std::vector<ZesZipPackRec>& recs = hm.recs;
-  recs.resize(2 * (size_t)count + 1);
   size_t rpos = 0;
-  EncGroup eg(std::min(group, count));
-  auto slot_of = [](uint64_t len) { return deflate_throws(len) ? 0ull : gz_up16(deflate_bound(len)); };
   uint64_t total = 0;
   for (uint32_t e0 = 0; e0 < count;) {
-    uint32_t cnt = 0;
-    uint64_t slots = 0;
-    while (e0 + cnt < count && cnt < group && (cnt == 0 || slots + slot_of(in_len[e0 + cnt]) <= group_slots)) {
-      eg.o_off[cnt] = slots;
-      eg.o_cap[cnt] = slot_of(in_len[e0 + cnt]);
-      slots += eg.o_cap[cnt];
-      cnt++;
-    }
+    uint64_t slots;
+    const uint32_t cnt = eg.form(in_len + e0, count - e0, &slots);
     if ((rc = eg.encode(d_in, in_off + e0, in_len + e0, cnt, slots))) return rc;
     ZesZipPackRec* gr = &recs[rpos];
     uint32_t wgs = 0;
@@ -5353,8 +5401,6 @@ static int zipwrite_groups(ZipwHost& hm, const uint8_t* d_in, const uint64_t* in
   }
   // the directory and the end record
   const uint64_t cd_off = total;
-  std::vector<uint8_t>& cd = hm.cd;
-  cd.clear();
   cd.reserve((size_t)count * 46 + name_off[count] + ZIP_END);
   for (uint32_t i = 0; i < count; i++) {
     zes_zip_entry& t = z[i];
@@ -5382,19 +5428,11 @@ static int zipwrite_groups(ZipwHost& hm, const uint8_t* d_in, const uint64_t* in
   total += cd.size();
   if (eg.room(total, cap, d_out)) HIPCHK(hipMemcpyAsync(d_out + cd_off, cd.data(), cd.size(), hipMemcpyHostToDevice, g.stream));
   HIPCHK(hipStreamSynchronize(g.stream));
+  drain.done();
   *out_len = total;
   if (!eg.fits) return ZES_E_NOSPACE;
   if (ent && count) memcpy(ent, z.data(), sizeof(zes_zip_entry) * (size_t)count);
   return ZES_OK;
-}
-
-static int zipwrite_core(const uint8_t* d_in, const uint64_t* in_off, const uint64_t* in_len, const uint8_t* names, const uint16_t* name_len, uint32_t count,
-                         uint8_t* d_out, uint64_t cap, uint64_t* out_len, zes_zip_entry* ent, uint32_t flags) {
-  ZipwHost hm;
-  const int rc = zipwrite_groups(hm, d_in, in_off, in_len, names, name_len, count, d_out, cap, out_len, ent, flags);
-  // (a way out in the middle: what is under way may still read hm.  ZES_OK and ZES_E_NOSPACE come from behind the last synchronisation)
-  if (rc && rc != ZES_E_NOSPACE && hipStreamSynchronize(g.stream) != hipSuccess) (void)hipGetLastError();
-  return rc;
 }
 
 int zes_zipwrite_bound(const uint64_t* in_len, const uint16_t* name_len, uint32_t count, uint64_t* cap) {
@@ -5425,24 +5463,19 @@ int zes_zipwrite(const uint8_t* const* in, const uint64_t* in_len, const uint8_t
     return ZES_OK;
   }
   LOCK_READY();
-  // every entry at a 16-byte boundary of g.gz_in
+  HostBatch hb(g.gz_in, g.gz_acc);
   std::vector<uint64_t> in_off(count);
-  uint64_t tin = 0;
-  for (uint32_t i = 0; i < count; i++) {
-    in_off[i] = tin;
-    tin += gz_up16(in_len[i]);
-  }
+  for (uint32_t i = 0; i < count; i++) in_off[i] = hb.place(in[i], in_len[i]);
   const uint64_t bound = zipwrite_bound(in_len, name_len, count);
-  if ((rc = ensure(g.gz_in, tin + 64)) || (rc = ensure(g.gz_acc, bound + 64))) return rc;
-  for (uint32_t i = 0; i < count; i++)
-    if ((rc = upload((uint8_t*)g.gz_in.p + in_off[i], in[i], in_len[i]))) return rc;
+  hb.room(bound);  // (the archive: one place)
+  if ((rc = hb.up())) return rc;
   uint64_t total = 0;
   std::vector<zes_zip_entry> z(ent ? count : 0);
-  rc = zipwrite_core((const uint8_t*)g.gz_in.p, in_off.data(), in_len, names, name_len, count, (uint8_t*)g.gz_acc.p, bound, &total, ent ? z.data() : nullptr, flags);
+  rc = zipwrite_core(hb.d_in(), in_off.data(), in_len, names, name_len, count, hb.d_out(), bound, &total, ent ? z.data() : nullptr, flags);
   if ((rc = call_done(rc, true))) return rc;
   *out_len = total;
   if (total > cap) return ZES_E_NOSPACE;
-  if ((rc = download(out, (const uint8_t*)g.gz_acc.p, total))) return rc;
+  if ((rc = download(out, hb.d_out(), total))) return rc;
   if (ent) memcpy(ent, z.data(), sizeof(zes_zip_entry) * (size_t)count);
   return ZES_OK;
 }
@@ -5451,7 +5484,8 @@ int zes_zipwrite(const uint8_t* const* in, const uint64_t* in_len, const uint8_t
 constexpr uint32_t PNG_IHDR = 0x49484452u, PNG_IDAT = 0x49444154u, PNG_PLTE = 0x504c5445u, PNG_IEND = 0x49454e44u, PNG_TRNS = 0x74524e53u;
 
 static uint32_t png_channels(uint32_t colour) { return colour == 2 ? 3u : colour == 4 ? 2u : colour == 6 ? 4u : 1u; }
-static uint64_t png_rowbytes(const ZesPngHead& h) { return ((uint64_t)h.width * (png_channels(h.colour) * h.depth) + 7) / 8; }
+static uint64_t png_rowbytes(uint32_t width, uint32_t colour, uint32_t depth) { return ((uint64_t)width * (png_channels(colour) * depth) + 7) / 8; }
+static uint64_t png_rowbytes(const ZesPngHead& h) { return png_rowbytes(h.width, h.colour, h.depth); }
 
 // The file rule on p[0, c), stated once for the host forms (k_png_walk restates it for files in device memory): the verdict,
 // h filled as far as the walk got, and every chunk that passes the chain's tests handed to each().
@@ -5557,8 +5591,9 @@ static uint32_t png_tab_share(uint64_t n) { return (uint32_t)std::min<uint64_t>(
 static int png_walk_dev(const uint8_t* d_src, const uint64_t* in_off, const uint64_t* in_len, uint32_t count, std::vector<PngImg>& im) {
   int rc;
   std::vector<ZesPngFile> files(count);
-  for (uint32_t i = 0; i < count; i++) files[i] = ZesPngFile{in_off[i], in_len[i], 0u, png_tab_share(in_len[i])};
   std::vector<uint8_t> back;
+  Drain drain;  // (behind files, which an upload reads, and back, which the read-back writes)
+  for (uint32_t i = 0; i < count; i++) files[i] = ZesPngFile{in_off[i], in_len[i], 0u, png_tab_share(in_len[i])};
   for (int round = 0; round < 2; round++) {
     uint64_t total = 0;
     for (ZesPngFile& f : files) {
@@ -5592,6 +5627,7 @@ static int png_walk_dev(const uint8_t* d_src, const uint64_t* in_off, const uint
         im[i].h = heads[i];
         if (heads[i].status == ZES_OK) im[i].ch.assign(tab + files[i].tab_base, tab + files[i].tab_base + heads[i].nchunks);
       }
+      drain.done();  // (behind the round's synchronisation)
       return ZES_OK;
     }
   }
@@ -5604,15 +5640,21 @@ static int png_decode_core(const uint8_t* d_src, const std::vector<PngImg>& im, 
   int rc;
   g.last_tier = 0;
   const uint32_t n = (uint32_t)im.size();
+  // what copies queued on the stream read (step 2's segments through the checksum's upload, step 3's through gz_gather's,
+  // step 4's jobs) or write (step 4's read-back), and the guard behind them
+  std::vector<ZesCrcSeg> csegs;
+  std::vector<ZesGzSeg> segs;
+  std::vector<ZesPngJob> uj;
+  std::vector<uint32_t> bad;
+  Drain drain;
   // 2. chunk CRCs: type and data of every chunk
   {
-    std::vector<ZesCrcSeg> segs;
     for (uint32_t k = 0; k < n; k++)
       if (status[k] == ZES_OK)
-        for (const ZesPngChunk& c : im[k].ch) segs.push_back(ZesCrcSeg{im[k].src_at + c.pos + 4, 4ull + (c.len & ~ZES_PNG_IDAT)});
-    if (segs.size() > 0x7fffffffull) return ZES_E_ARG;
-    std::vector<uint32_t> crc(segs.size());
-    if (!segs.empty() && (rc = crc32_batch_locked(d_src, segs.data(), (uint32_t)segs.size(), crc.data()))) return rc;
+        for (const ZesPngChunk& c : im[k].ch) csegs.push_back(ZesCrcSeg{im[k].src_at + c.pos + 4, 4ull + (c.len & ~ZES_PNG_IDAT)});
+    if (csegs.size() > 0x7fffffffull) return ZES_E_ARG;
+    std::vector<uint32_t> crc(csegs.size());
+    if (!csegs.empty() && (rc = crc32_batch_locked(d_src, csegs.data(), (uint32_t)csegs.size(), crc.data()))) return rc;
     size_t q = 0;
     for (uint32_t k = 0; k < n; k++)
       if (status[k] == ZES_OK)
@@ -5622,7 +5664,6 @@ static int png_decode_core(const uint8_t* d_src, const std::vector<PngImg>& im, 
   // 3. the zlib streams: gathered, decoded, their lengths and trailers checked
   std::vector<uint32_t> who;
   std::vector<InfJob> jobs;
-  std::vector<ZesGzSeg> segs;
   std::vector<uint64_t> filtered;
   uint64_t ipos = 0, opos = 0;
   for (uint32_t k = 0; k < n; k++) {
@@ -5643,7 +5684,10 @@ static int png_decode_core(const uint8_t* d_src, const std::vector<PngImg>& im, 
     ipos += gz_slot_in(h.idat_bytes);
     opos += gz_slot_out(F);
   }
-  if (jobs.empty()) return ZES_OK;
+  if (jobs.empty()) {
+    drain.done();  // (step 2 ends in its read-back)
+    return ZES_OK;
+  }
   if ((rc = ensure(g.gz_bodies, ipos + 64)) || (rc = ensure(g.gz_outs, opos + 64))) return rc;
   if ((rc = gz_gather(d_src, (uint8_t*)g.gz_bodies.p, segs))) return rc;
   if ((rc = inflate_jobs((const uint8_t*)g.gz_bodies.p, (uint8_t*)g.gz_outs.p, jobs, nullptr, flags & ZES_F_PIECES))) return rc;
@@ -5652,7 +5696,6 @@ static int png_decode_core(const uint8_t* d_src, const std::vector<PngImg>& im, 
   if ((rc = check_adler_jobs((const uint8_t*)g.gz_bodies.p, nullptr, (const uint8_t*)g.gz_outs.p, jobs))) return rc;
   keep_times();
   // 4. the filters
-  std::vector<ZesPngJob> uj;
   std::vector<uint32_t> uw;
   uint64_t bands = 0;
   for (size_t q = 0; q < jobs.size(); q++) {
@@ -5666,7 +5709,10 @@ static int png_decode_core(const uint8_t* d_src, const std::vector<PngImg>& im, 
     bands += (h.height + ZES_PNG_BAND - 1) / ZES_PNG_BAND;
     if (bands > 0x7fffffffull) return ZES_E_ARG;
   }
-  if (uj.empty()) return ZES_OK;
+  if (uj.empty()) {
+    drain.done();  // (inflate_jobs has brought the jobs' results down: the stream is past segs)
+    return ZES_OK;
+  }
   const size_t o_bad = sizeof(ZesPngJob) * uj.size();
   if ((rc = ensure(g.gz_tab, o_bad + 4 * uj.size()))) return rc;
   uint32_t* d_bad = (uint32_t*)((uint8_t*)g.gz_tab.p + o_bad);
@@ -5679,9 +5725,10 @@ static int png_decode_core(const uint8_t* d_src, const std::vector<PngImg>& im, 
                        (const ZesPngJob*)g.gz_tab.p, (uint32_t)uj.size(), (uint32_t)bands, d_bad);
   }
   HIPCHK(hipGetLastError());
-  std::vector<uint32_t> bad(uj.size());
+  bad.resize(uj.size());
   HIPCHK(hipMemcpyAsync(bad.data(), d_bad, 4 * uj.size(), hipMemcpyDeviceToHost, g.stream));
   HIPCHK(hipStreamSynchronize(g.stream));
+  drain.done();
   for (size_t q = 0; q < uj.size(); q++)
     if (bad[q]) status[uw[q]] = ZES_E_PNG;
   return ZES_OK;
@@ -5709,7 +5756,7 @@ int zes_png_decode_dev(const uint8_t* d_in, const uint64_t* in_off, const uint64
   for (uint32_t i = 0; i < count; i++)
     if (in_len[i] && !d_in) return ZES_E_ARG;
   if (!count) {
-    zip_read_none();
+    call_none();
     return ZES_OK;
   }
   LOCK_READY();
@@ -5741,13 +5788,12 @@ int zes_png_decode_alloc(const uint8_t* const* in, const uint64_t* in_len, uint3
   for (uint32_t i = 0; i < count; i++)
     if (in_len[i] && !in[i]) return ZES_E_ARG;
   if (!count) {
-    zip_read_none();
+    call_none();
     return ZES_OK;
   }
   // the rule on the caller's memory: a batch in which no file passes touches no device
   std::vector<PngImg> im(count);
   std::vector<uint64_t> size(count, 0);
-  uint64_t tin = 0, tout = 0;
   bool any = false;
   for (uint32_t i = 0; i < count; i++) {
     PngImg& m = im[i];
@@ -5757,39 +5803,24 @@ int zes_png_decode_alloc(const uint8_t* const* in, const uint64_t* in_len, uint3
     if (status[i] != ZES_OK) continue;
     any = true;
     size[i] = mine.out_size;
-    m.src_at = tin;
-    m.dst_off = tout;
-    tin += gz_up16(in_len[i]) + 16;
-    tout += gz_up16(mine.out_size) + 16;
   }
   if (!any) {
-    zip_read_none();
+    call_none();
     return ZES_OK;
   }
   LOCK_READY();
-  if ((rc = ensure(g.gz_in, tin + 64)) || (rc = ensure(g.gz_acc, tout + 64))) return rc;
+  HostBatch hb(g.gz_in, g.gz_acc);
   for (uint32_t i = 0; i < count; i++)
-    if (status[i] == ZES_OK && (rc = upload((uint8_t*)g.gz_in.p + im[i].src_at, in[i], in_len[i]))) return rc;
-  if ((rc = call_done(png_decode_core((const uint8_t*)g.gz_in.p, im, (uint8_t*)g.gz_acc.p, status, flags), true))) return rc;
-  for (uint32_t i = 0; i < count; i++) {
-    if (status[i] != ZES_OK) continue;
-    uint8_t* to = alloc(user, i, size[i]);
-    if (!to) {
-      status[i] = ZES_E_ARG;
-      continue;
+    if (status[i] == ZES_OK) {
+      im[i].src_at = hb.place(in[i], in_len[i]);
+      im[i].dst_off = hb.room(size[i]);
     }
-    // (a short result is only enqueued: one synchronisation behind the loop serves them all)
-    if ((rc = download(to, (const uint8_t*)g.gz_acc.p + im[i].dst_off, size[i], nullptr, false))) return rc;
-    out_len[i] = size[i];
-  }
-  HIPCHK(hipStreamSynchronize(g.stream));
-  return ZES_OK;
+  if ((rc = hb.up())) return rc;
+  if ((rc = call_done(png_decode_core(hb.d_in(), im, hb.d_out(), status, flags), true))) return rc;
+  return hb.hand_out(count, alloc, user, status, out_len, [&](uint32_t i) { return size[i]; }, [&](uint32_t i) { return im[i].dst_off; });
 }
 
 // ---- PNG writer (include/zes.h: "zes_pngwrite*"): filters by k_png_filter, zlib bodies by EncGroup, files by k_png_pack ----
-constexpr uint32_t PNGW_GROUP = ZIPW_GROUP, PNGW_GROUP_PIECES = ZIPW_GROUP_PIECES;  // a group: zipwrite_groups' limits
-constexpr uint64_t PNGW_GROUP_SLOTS = ZIPW_GROUP_SLOTS, PNGW_GROUP_SLOTS_PIECES = ZIPW_GROUP_SLOTS_PIECES;
-
 // What the arguments alone say about image i (steps 1 and 2 of include/zes.h), and its sizes
 struct PngwPlan {
   int32_t status = ZES_OK;
@@ -5814,8 +5845,7 @@ static PngwPlan pngw_plan(const zes_pngw_image& m, uint64_t in_len) {
     default: ok = false;
   }
   if (!ok || m.width - 1 > 0x7ffffffeu || m.height - 1 > 0x7ffffffeu || m.filter > 6 || m.pad) return p;
-  const uint32_t bits = png_channels(m.colour) * dp;
-  const uint64_t rowbytes = ((uint64_t)m.width * bits + 7) / 8;
+  const uint64_t rowbytes = png_rowbytes(m.width, m.colour, dp);
   if ((unsigned __int128)in_len != (unsigned __int128)m.height * rowbytes) return p;
   switch (m.colour) {
     case 3: ok = m.plte_len % 3 == 0 && m.plte_len >= 3 && m.plte_len <= (3u << dp) && m.trns_len <= m.plte_len / 3; break;
@@ -5829,7 +5859,7 @@ static PngwPlan pngw_plan(const zes_pngw_image& m, uint64_t in_len) {
   if (1 + rowbytes > 0xFFFFFFFFull / m.height) return p;
   p.status = ZES_OK;
   p.rowbytes = (uint32_t)rowbytes;
-  p.bpp = std::max<uint32_t>(1, bits / 8);
+  p.bpp = std::max<uint32_t>(1, png_channels(m.colour) * dp / 8);
   p.F = m.height * (1 + rowbytes);
   p.mode = (m.filter >= 5 && (m.colour == 3 || dp < 8)) ? 0u : m.filter;  // (adaptive: palette and sub-byte images take None)
   return p;
@@ -5860,20 +5890,9 @@ static int pngwrite_args(const std::function<bool(uint32_t)>& data, const uint64
   return ZES_OK;
 }
 
-// The host memory that a call's asynchronous uploads read: the caller's, pngwrite_core's, as ZipwHost is zipwrite_core's
-struct PngwHost {
-  std::deque<std::vector<uint8_t>> blobs;
-  std::deque<std::vector<uint2>> work;
-  std::deque<std::vector<ZesCrcSeg>> segs;
-  uint8_t* blob(size_t n) {
-    blobs.emplace_back(n);
-    return blobs.back().data();
-  }
-};
-
 // The images whose status[i] is ZES_OK on entry, image i's scanlines at d_in + in_off[i], its file to d_out + out_off[i] when
-// it fits out_cap[i] (and d_out is there), else ZES_E_NOSPACE with the size needed.  Group by group as zipwrite_groups goes;
-// a group's launches, in order:
+// it fits out_cap[i] (and d_out is there), else ZES_E_NOSPACE with the size needed.  Group by group as zipwrite_core goes
+// (EncGroup::form over the filtered lengths); a group's launches, in order:
 //   k_png_filter   once: every row of the group's images into their scratch buffers (g.gz_outs)
 //   the encoder    EncGroup without its CRC-32 launch, the scratch buffers as its input: one deflate_batch_core call, whose
 //                  read-back is the group's (none when the encoder refuses every length)
@@ -5883,38 +5902,44 @@ struct PngwHost {
 //   k_crc32_seg    once: type and data of every chunk as they lie in the output, the words left on the device
 //   k_crc32_put    once: the chunk CRCs finished and stored
 // The last three only when an image of the group is written.  g.gz_tab holds the filter's records and, behind the read-back,
-// aux | pack records | put records.
-static int pngwrite_groups(PngwHost& hm, const uint8_t* d_in, const uint64_t* in_off, const zes_pngw_image* img, const uint8_t* aux,
-                           const std::vector<PngwPlan>& plan, uint32_t count, uint8_t* d_out, const uint64_t* out_off, const uint64_t* out_cap,
-                           uint64_t* out_len, int32_t* status, uint32_t flags) {
+// aux | pack records | put records.  Every group's records, which asynchronous uploads read, stay until the end of the call;
+// they and the encoder's and checksums' tables are declared in front of a Drain.
+static int pngwrite_core(const uint8_t* d_in, const uint64_t* in_off, const zes_pngw_image* img, const uint8_t* aux,
+                         const std::vector<PngwPlan>& plan, uint32_t count, uint8_t* d_out, const uint64_t* out_off, const uint64_t* out_cap,
+                         uint64_t* out_len, int32_t* status, uint32_t flags) {
   int rc;
   g.carry.clear();
   g.last_tier = 0;
-  const uint32_t group = (flags & ZES_F_PIECES) ? PNGW_GROUP_PIECES : PNGW_GROUP;
-  const uint64_t group_slots = (flags & ZES_F_PIECES) ? PNGW_GROUP_SLOTS_PIECES : PNGW_GROUP_SLOTS;
+  const uint32_t nlive = (uint32_t)std::count(status, status + count, (int32_t)ZES_OK);
+  std::deque<std::vector<uint8_t>> blobs;
+  std::deque<std::vector<uint2>> work;
+  std::deque<std::vector<ZesCrcSeg>> segs;
+  std::vector<ZesCrcSeg> asegs;  // a group's lengths that the encoder refuses
+  std::vector<uint64_t> flen;    // the live images' filtered lengths
+  EncGroup eg(flags, nlive);
+  std::vector<uint64_t> f_off(eg.o_off.size());
+  Drain drain;  // (behind everything above: uploads read it)
+  auto blob = [&](size_t n) {
+    blobs.emplace_back(n);
+    return blobs.back().data();
+  };
   std::vector<uint32_t> live;
   for (uint32_t i = 0; i < count; i++)
-    if (status[i] == ZES_OK) live.push_back(i);
-  const uint32_t nlive = (uint32_t)live.size();
-  EncGroup eg(std::min(group, nlive));
-  std::vector<uint64_t> f_off(std::min(group, nlive)), f_len(std::min(group, nlive));
-  auto slot_of = [](uint64_t len) { return deflate_throws(len) ? 0ull : gz_up16(deflate_bound(len)); };
+    if (status[i] == ZES_OK) {
+      live.push_back(i);
+      flen.push_back(plan[i].F);
+    }
   CrcSeg ck;
   for (uint32_t e0 = 0; e0 < nlive;) {
     // the group, its scratch buffers and encoder slots, the filter's records
-    uint32_t cnt = 0;
-    uint64_t slots = 0, fbytes = 0, units = 0;
-    while (e0 + cnt < nlive && cnt < group && (cnt == 0 || slots + slot_of(plan[live[e0 + cnt]].F) <= group_slots)) {
-      const PngwPlan& p = plan[live[e0 + cnt]];
-      eg.o_off[cnt] = slots;
-      eg.o_cap[cnt] = slot_of(p.F);
-      slots += eg.o_cap[cnt];
-      f_off[cnt] = fbytes;
-      f_len[cnt] = p.F;
-      fbytes += gz_up16(p.F) + 16;
-      cnt++;
+    const uint64_t* f_len = &flen[e0];
+    uint64_t slots, fbytes = 0, units = 0;
+    const uint32_t cnt = eg.form(f_len, nlive - e0, &slots);
+    for (uint32_t k = 0; k < cnt; k++) {
+      f_off[k] = fbytes;
+      fbytes += gz_up16(f_len[k]) + 16;
     }
-    ZesPngwJob* jobs = (ZesPngwJob*)hm.blob(sizeof(ZesPngwJob) * ((size_t)cnt + 1));
+    ZesPngwJob* jobs = (ZesPngwJob*)blob(sizeof(ZesPngwJob) * ((size_t)cnt + 1));
     for (uint32_t k = 0; k < cnt; k++) {
       const uint32_t i = live[e0 + k];
       const PngwPlan& p = plan[i];
@@ -5932,9 +5957,9 @@ static int pngwrite_groups(PngwHost& hm, const uint8_t* d_in, const uint64_t* in
       hipLaunchKernelGGL(k_png_filter, dim3((uint32_t)((units + per - 1) / per)), dim3(ZES_PNGW_THREADS), 0, g.stream, d_in, filt, (const ZesPngwJob*)g.gz_tab.p, cnt);
     }
     HIPCHK(hipGetLastError());
-    if ((rc = eg.encode(filt, f_off.data(), f_len.data(), cnt, slots, false))) return rc;
+    if ((rc = eg.encode(filt, f_off.data(), f_len, cnt, slots, false))) return rc;
     // the lengths the encoder refuses: their Adler-32s
-    std::vector<ZesCrcSeg> asegs;
+    asegs.clear();
     for (uint32_t k = 0; k < cnt; k++)
       if (!eg.o_cap[k]) asegs.push_back(ZesCrcSeg{f_off[k], f_len[k]});
     std::vector<uint32_t> adler(asegs.size());
@@ -5945,10 +5970,10 @@ static int pngwrite_groups(PngwHost& hm, const uint8_t* d_in, const uint64_t* in
     uint32_t nrec = 0;
     for (uint32_t k = 0; k < cnt; k++) naux += (uint64_t)img[live[e0 + k]].plte_len + img[live[e0 + k]].trns_len;
     const size_t aux_pad = (size_t)gz_up16(naux);
-    uint8_t* haux = hm.blob(aux_pad + 16);
-    ZesPngwRec* recs = (ZesPngwRec*)hm.blob(sizeof(ZesPngwRec) * ((size_t)cnt + 1));
-    hm.segs.emplace_back();
-    std::vector<ZesCrcSeg>& csegs = hm.segs.back();
+    uint8_t* haux = blob(aux_pad + 16);
+    ZesPngwRec* recs = (ZesPngwRec*)blob(sizeof(ZesPngwRec) * ((size_t)cnt + 1));
+    segs.emplace_back();
+    std::vector<ZesCrcSeg>& csegs = segs.back();
     std::vector<ZesCrcPut> puts;
     uint32_t aux_at = 0, refused = 0;
     for (uint32_t k = 0; k < cnt; k++) {
@@ -6003,7 +6028,7 @@ static int pngwrite_groups(PngwHost& hm, const uint8_t* d_in, const uint64_t* in
     memset(&recs[nrec], 0, sizeof(ZesPngwRec));
     recs[nrec].first_wg = (uint32_t)wgs;
     const size_t o_recs = aux_pad, o_puts = o_recs + sizeof(ZesPngwRec) * ((size_t)nrec + 1), n_puts = sizeof(ZesCrcPut) * puts.size();
-    ZesCrcPut* hputs = (ZesCrcPut*)hm.blob(n_puts);
+    ZesCrcPut* hputs = (ZesCrcPut*)blob(n_puts);
     memcpy(hputs, puts.data(), n_puts);
     if ((rc = ensure(g.gz_tab, o_puts + n_puts))) return rc;
     uint8_t* tab = (uint8_t*)g.gz_tab.p;
@@ -6016,9 +6041,9 @@ static int pngwrite_groups(PngwHost& hm, const uint8_t* d_in, const uint64_t* in
                          d_out, (const ZesPngwRec*)(tab + o_recs), nrec);
     }
     HIPCHK(hipGetLastError());
-    hm.work.emplace_back();
+    work.emplace_back();
     unsigned int* d_acc = nullptr;
-    rc = seg_checksum_enqueue(ck, d_out, csegs.data(), (uint32_t)csegs.size(), hm.work.back(), &d_acc);
+    rc = seg_checksum_enqueue(ck, d_out, csegs.data(), (uint32_t)csegs.size(), work.back(), &d_acc);
     if (rc || !d_acc) return rc ? rc : ZES_E_DEVICE;
     {
       Timed t("k_crc32_put");
@@ -6029,17 +6054,8 @@ static int pngwrite_groups(PngwHost& hm, const uint8_t* d_in, const uint64_t* in
     e0 += cnt;
   }
   HIPCHK(hipStreamSynchronize(g.stream));
+  drain.done();
   return ZES_OK;
-}
-
-
-static int pngwrite_core(const uint8_t* d_in, const uint64_t* in_off, const zes_pngw_image* img, const uint8_t* aux, const std::vector<PngwPlan>& plan,
-                         uint32_t count, uint8_t* d_out, const uint64_t* out_off, const uint64_t* out_cap, uint64_t* out_len, int32_t* status, uint32_t flags) {
-  PngwHost hm;
-  const int rc = pngwrite_groups(hm, d_in, in_off, img, aux, plan, count, d_out, out_off, out_cap, out_len, status, flags);
-  // (a way out in the middle: what is under way may still read hm.  ZES_OK comes from behind the last synchronisation)
-  if (rc && hipStreamSynchronize(g.stream) != hipSuccess) (void)hipGetLastError();
-  return rc;
 }
 
 int zes_pngwrite_bound(const zes_pngw_image* img, uint32_t count, uint64_t* cap) {
@@ -6047,8 +6063,7 @@ int zes_pngwrite_bound(const zes_pngw_image* img, uint32_t count, uint64_t* cap)
   for (uint32_t i = 0; i < count; i++) {
     const zes_pngw_image& m = img[i];
     // (the scanlines' size is not an argument here: the one that fits the header)
-    const uint64_t rowbytes = ((uint64_t)m.width * (png_channels(m.colour) * m.depth) + 7) / 8;
-    const unsigned __int128 n = (unsigned __int128)m.height * rowbytes;
+    const unsigned __int128 n = (unsigned __int128)m.height * png_rowbytes(m.width, m.colour, m.depth);
     const PngwPlan p = n > 0xFFFFFFFFFFFFFFFFull ? PngwPlan{ZES_E_UNSUPPORTED} : pngw_plan(m, (uint64_t)n);
     cap[i] = p.status == ZES_OK ? pngw_file_len(m, pngw_stored_len(p.F)) : 0;
   }
@@ -6063,7 +6078,7 @@ int zes_pngwrite_dev(const uint8_t* d_in, const uint64_t* in_off, const uint64_t
   bool any = false;
   if (const int arc = pngwrite_args([&](uint32_t) { return d_in != nullptr; }, in_len, img, aux, count, out_len, status, flags, plan, &any)) return arc;
   if (!any) {
-    zip_read_none();
+    call_none();
     return ZES_OK;
   }
   LOCK_READY();
@@ -6078,42 +6093,23 @@ int zes_pngwrite(const uint8_t* const* in, const uint64_t* in_len, const zes_png
   bool any = false;
   if (const int arc = pngwrite_args([&](uint32_t i) { return in[i] != nullptr; }, in_len, img, aux, count, out_len, status, flags, plan, &any)) return arc;
   if (!any) {
-    zip_read_none();
+    call_none();
     return ZES_OK;
   }
   LOCK_READY();
-  // every image at a 16-byte boundary of g.gz_in, every file at one of g.gz_acc with the bound's room
+  // every file gets the bound's room
+  HostBatch hb(g.gz_in, g.gz_acc);
   std::vector<uint64_t> in_off(count, 0), out_off(count, 0), out_cap(count, 0);
-  uint64_t tin = 0, tout = 0;
   for (uint32_t i = 0; i < count; i++) {
     if (status[i] != ZES_OK) continue;
-    in_off[i] = tin;
-    tin += gz_up16(in_len[i]) + 16;
-    out_off[i] = tout;
+    in_off[i] = hb.place(in[i], in_len[i]);
     out_cap[i] = pngw_file_len(img[i], pngw_stored_len(plan[i].F));
-    tout += gz_up16(out_cap[i]) + 16;
+    out_off[i] = hb.room(out_cap[i]);
   }
-  if ((rc = ensure(g.gz_in, tin + 64)) || (rc = ensure(g.gz_acc, tout + 64))) return rc;
-  for (uint32_t i = 0; i < count; i++)
-    if (status[i] == ZES_OK && (rc = upload((uint8_t*)g.gz_in.p + in_off[i], in[i], in_len[i]))) return rc;
-  rc = pngwrite_core((const uint8_t*)g.gz_in.p, in_off.data(), img, aux, plan, count, (uint8_t*)g.gz_acc.p, out_off.data(), out_cap.data(), out_len, status, flags);
+  if ((rc = hb.up())) return rc;
+  rc = pngwrite_core(hb.d_in(), in_off.data(), img, aux, plan, count, hb.d_out(), out_off.data(), out_cap.data(), out_len, status, flags);
   if ((rc = call_done(rc, true))) return rc;
-  for (uint32_t i = 0; i < count; i++) {
-    if (status[i] != ZES_OK) {
-      out_len[i] = 0;
-      continue;
-    }
-    uint8_t* to = alloc(user, i, out_len[i]);
-    if (!to) {
-      status[i] = ZES_E_ARG;
-      out_len[i] = 0;
-      continue;
-    }
-    // (a short result is only enqueued: one synchronisation behind the loop serves them all)
-    if ((rc = download(to, (const uint8_t*)g.gz_acc.p + out_off[i], out_len[i], nullptr, false))) return rc;
-  }
-  HIPCHK(hipStreamSynchronize(g.stream));
-  return ZES_OK;
+  return hb.hand_out(count, alloc, user, status, out_len, [&](uint32_t i) { return out_len[i]; }, [&](uint32_t i) { return out_off[i]; });
 }
 
 int zes_stage_lz77_dev(const uint8_t* d_in, uint64_t n, uint64_t start, uint32_t len, uint32_t* h_tokens, uint32_t* ntokens) {

@@ -1,4 +1,4 @@
-// zes_pngw.hip — device pieces of the PNG writer (zes_api.hip: pngwrite_groups; include/zes.h: "zes_pngwrite*").
+// zes_pngw.hip — device pieces of the PNG writer (zes_api.hip: pngwrite_core; include/zes.h: "zes_pngwrite*").
 //
 //   k_png_filter  the scanline filters applied (PNG specification, 9.2) and, for the adaptive modes, chosen: every row of
 //                 every image of a group in one launch.  A filtered row depends on raw rows only, so rows are independent:
