@@ -995,7 +995,7 @@ int deflate_batch_core(const uint8_t* d_in, const uint64_t* in_off, const uint64
                        (uint32_t*)g.codes.p, (uint32_t*)g.hdrs.p);
   }
   if (sort_dbg && (rc = phases_print(zes_huff_set_dbg, nblk, 7,
-                                     "zes huff steps (avg cycles over %u blocks): lit/len lengths %.0f distance lengths %.0f codes %.0f run-length coding %.0f its code %.0f header bits %.0f totals+out %.0f\n")))
+                                     "zes huff steps (avg cycles over %u blocks): rank sorts %.0f both alphabets' levels %.0f codes %.0f run-length coding %.0f its code %.0f header bits %.0f totals+out %.0f\n")))
     return rc;
   {
     HIPCHK(hipStreamWaitEvent(g.stream, g.ev_a1, 0));  // the checksums

@@ -2205,11 +2205,14 @@ __global__ __launch_bounds__(PARSE_THREADS, 8) void k_lz_parse_small(const uint8
 }
 
 // ------------------------------------------------------------------------------------------
-// k_huff: per block, 256 threads.
+// k_huff: per block, 384 threads = six wavefronts.
 // Package-merge restated as parallel merges: the reference's per-level
 // `sort(leaves ++ pairs(prev))` is a stable merge of two sorted runs (leaves first on ties), so
 // every item's slot is a binary-search rank; a code length is the number of levels whose
 // selected prefix still contains the leaf (the selected items of a level are a prefix of it).
+// The first five wavefronts hold the lit/len alphabet, a leaf and a package of every level per thread; the sixth holds
+// the distance alphabet, which walks its levels in the barrier rounds of the lit/len merge.  The code-length code is
+// built by the first wavefront alone, without barriers.
 // ------------------------------------------------------------------------------------------
 __device__ unsigned long long* g_huff_dbg = nullptr;  // ZES_DEBUG_PHASES: cycle stamps [g][8]
 void zes_huff_set_dbg(unsigned long long* p) { (void)hipMemcpyToSymbol(HIP_SYMBOL(g_huff_dbg), &p, sizeof p); }
@@ -2217,216 +2220,202 @@ void zes_huff_set_dbg(unsigned long long* p) { (void)hipMemcpyToSymbol(HIP_SYMBO
   do {                                                                                                   \
     if (g_huff_dbg && threadIdx.x == 0) g_huff_dbg[(size_t)blockIdx.x * 8 + (i)] = (unsigned long long)clock64(); \
   } while (0)
-#define HUFF_THREADS 256
-#define PM_MAXN 288
+#define HUFF_THREADS 384
+#define HUFF_WAVES (HUFF_THREADS / 64)
+#define PM_MAXN 320  // entries of the per-symbol arrays; the lit/len team's threads
+static_assert(HUFF_THREADS == HUFF_THREADS_HOST && HUFF_THREADS == PM_MAXN + 64, "the lit/len team and the distance wavefront");
+// Two alphabets lie side by side in the arrays of 320: slot 0 (288 entries: lit/len, later the code-length code) and
+// slot 288 (32 entries: distance), as in the histograms.
 struct HuffSmem {
-  uint32_t hist[320];           // working histogram of the current alphabet
-  uint32_t lw[PM_MAXN];         // leaf weights, ascending (count, symbol)
-  uint16_t lsym[PM_MAXN];       // symbol of sorted leaf i
-  uint32_t w[2][2 * PM_MAXN];   // merged weights of the previous / current level
-  uint32_t pk[PM_MAXN];         // packages of the current level
-  uint16_t leafpos[15][PM_MAXN];
-  uint32_t a_k[16];
-  uint8_t lens[320];            // [0..288) lit/len, [288..320) dist
+  uint32_t hist[320];              // counts: [0..288) lit/len, [288..320) distance
+  alignas(16) uint32_t key[320];   // rank sort: count - 1 per symbol
+  uint32_t lw[320];                // leaf weights, ascending (count, symbol)
+  uint16_t lsym[320];              // symbol of sorted leaf i
+  alignas(8) uint32_t w[2][640];   // merged weights of the previous / current level (a slot's entries start at twice its base)
+  uint16_t leafpos[15][320];
+  uint32_t pm_n[2];                // used symbols per slot
+  uint32_t a_k[2][16];
+  uint32_t top[3];                 // highest used lit/len symbol, highest used distance symbol, HCLEN
+  uint8_t lens[320];               // [0..288) lit/len, [288..320) dist
   uint8_t clens[32];
-  uint16_t codes[320];          // bit-reversed codes, same layout
+  uint16_t codes[320];             // bit-reversed codes, same layout
   uint16_t ccodes[32];
   uint8_t rl_sym[320];
   uint8_t rl_val[320];
-  uint32_t nrl;
   uint32_t hdr[ZES_HDR_WORDS];
   uint32_t hdr_bits;
   uint32_t total_bits;
-  uint32_t ccount[16], cfirst[16], crun[16];     // canonical codes: symbols per length, first code, symbols seen so far
-  uint16_t cwave[HUFF_THREADS / 64][16];         // canonical codes: symbols of each length per wave of the current pass
-  uint8_t cl[320];                               // lit/len lengths followed by the distance lengths (src/deflate.ts:81-97)
-  uint16_t run_tok[320];                         // run-length coding: tokens before the run that starts at this index
-  uint32_t wsum[HUFF_THREADS / 64];
-  unsigned long long starts[5];                  // run-length coding: bit i = a run starts at index i
+  uint32_t ccount[2][16], cfirst[2][16];  // canonical codes per slot: symbols per length, first code
+  uint16_t cwave[HUFF_WAVES][16];         // canonical codes: symbols of each length per wavefront
+  uint8_t cl[320];                        // lit/len lengths followed by the distance lengths (src/deflate.ts:81-97)
+  uint32_t wsum[HUFF_WAVES];
+  unsigned long long starts[5];           // run-length coding: bit i = a run starts at index i
 };
 
-__device__ static inline uint32_t lower_bound_u32(const uint32_t* a, uint32_t n, uint32_t v) {  // #{a[i] < v}
-  uint32_t lo = 0, hi = n;
-  while (lo < hi) {
-    uint32_t mid = (lo + hi) >> 1;
-    if (a[mid] < v) lo = mid + 1; else hi = mid;
-  }
-  return lo;
-}
-__device__ static inline uint32_t upper_bound_u32(const uint32_t* a, uint32_t n, uint32_t v) {  // #{a[i] <= v}
-  uint32_t lo = 0, hi = n;
-  while (lo < hi) {
-    uint32_t mid = (lo + hi) >> 1;
-    if (a[mid] <= v) lo = mid + 1; else hi = mid;
-  }
-  return lo;
+// The threads that build one alphabet: thread t < size holds symbol t, then leaf t and package t of every level.  `base` is the alphabet's slot.  A team of one wavefront (kWave) orders
+// its LDS traffic by waiting for its own requests; a wider one meets at the workgroup's barriers, the same number
+// whatever its alphabet holds, so two teams of a workgroup can run side by side.
+struct PmTeam {
+  uint32_t t, size, base;
+};
+template <bool kWave>
+__device__ __forceinline__ static void pm_sync() {
+  if (kWave) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+  else __syncthreads();
 }
 
-// Code lengths of alphabet hist[0..nsym) limited to L, into lens[0..nsym).  All threads call it.
+// Code lengths of the alphabet S.hist[T.base + (0..nsym)) limited to L, into lens[0..nsym) (nsym <= T.size).  All
+// threads of the team call it; `stamp` >= 0: the cycle stamp taken behind the rank sort.
 // A level of the package-merge is one round trip: every thread looks up the slots of its items of the level (a leaf
-// and a package, two of each for alphabets of more than 256 used symbols) side by side — leaf i goes behind the packages lighter than it, package j behind the leaves not heavier
-// (leaves precede packages on ties: src/huffman.ts:79-99) — by fixed-length binary searches whose loads overlap;
-// a package's weight is read as the sum of its two items of the level before, so there is no separate pass (and
+// and a package) side by side — leaf i goes behind the packages lighter than it, package j behind the leaves not heavier
+// (leaves precede packages on ties: src/huffman.ts:79-99) — by fixed-length binary searches whose loads overlap; a
+// package's weight is read as the sum of its two items of the level before, so there is no separate pass (and
 // barrier) that builds the packages.
-__device__ static void pm_lengths(HuffSmem& S, const uint32_t* hist, uint32_t nsym, uint32_t L, uint8_t* lens) {
-  const uint32_t tid = threadIdx.x, lane = tid & 63u;
-  __syncthreads();
-  // rank sort of the used symbols by (count, symbol)  — src/huffman.ts:67,79-85,95-99
-  uint32_t n = 0;
-  for (uint32_t s0 = 0; s0 < nsym; s0 += HUFF_THREADS) n += (uint32_t)__syncthreads_count(s0 + tid < nsym && hist[s0 + tid] != 0u);
-  for (uint32_t s = tid; s < nsym; s += HUFF_THREADS) {
-    lens[s] = 0;
-    const uint32_t c = hist[s];
-    if (c) {
-      uint32_t rank = 0;
-      for (uint32_t j = 0; j < nsym; j++) {
-        const uint32_t cj = hist[j];
-        rank += (cj != 0) && (cj < c || (cj == c && j < s));
-      }
-      S.lw[rank] = c;
-      S.lsym[rank] = (uint16_t)s;
+template <bool kWave>
+__device__ static void pm_lengths(HuffSmem& S, const PmTeam T, uint32_t nsym, uint32_t L, uint8_t* lens, int stamp) {
+  const uint32_t lane = threadIdx.x & 63u, b = T.base, a = b ? 1u : 0u;
+  const uint32_t i = T.t < T.size ? T.t : PM_MAXN;  // this thread's symbol, then its sorted leaf and its package
+  // sort keys: count - 1, so that an unused symbol's key is above every used one's
+  const uint32_t key = (i < nsym ? S.hist[b + i] : 0u) - 1u;
+  if (i < (b ? 32u : 288u)) S.key[b + i] = key;  // (the slot's entries behind nsym too: the walk below reads four at a load)
+  if (T.t == 0) S.pm_n[a] = 0;
+  if (i < nsym) lens[i] = 0;
+  pm_sync<kWave>();
+  // rank sort of the used symbols by (count, symbol)  — src/huffman.ts:67,79-85,95-99: the symbols below this thread's
+  // with a key not above its own, and the symbols above it with a key below.  Which of the two holds for a symbol is
+  // the same for all lanes of a wavefront but for the 64 symbols the wavefront itself holds.
+  const bool used = key != ~0u;
+  uint32_t rank = 0;
+  if (used) {
+    const uint32_t own = __builtin_amdgcn_readfirstlane(i & ~63u);
+    const uint4* k4 = reinterpret_cast<const uint4*>(S.key + b);
+    for (uint32_t q = 0; q < own >> 2; q++) {
+      const uint4 k = k4[q];
+      rank += (k.x <= key) + (k.y <= key) + (k.z <= key) + (k.w <= key);
     }
+    for (uint32_t q = own >> 2, qe = min(own + 64u, (nsym + 3u) & ~3u) >> 2; q < qe; q++) {
+      const uint4 k = k4[q];
+      const uint32_t j = 4u * q;
+      rank += (k.x < key || (k.x == key && j < i)) + (k.y < key || (k.y == key && j + 1u < i)) +
+              (k.z < key || (k.z == key && j + 2u < i)) + (k.w < key || (k.w == key && j + 3u < i));
+    }
+    for (uint32_t q = (own + 64u) >> 2, qe = (nsym + 3u) >> 2; q < qe; q++) {
+      const uint4 k = k4[q];
+      rank += (k.x < key) + (k.y < key) + (k.z < key) + (k.w < key);
+    }
+    // level 1: the sorted leaves; odd length drops the last item (src/huffman.ts:100-102)
+    S.lw[b + rank] = key + 1u;
+    S.lsym[b + rank] = (uint16_t)i;
+    S.w[0][2u * b + rank] = key + 1u;
+    S.leafpos[0][b + rank] = (uint16_t)rank;
   }
-  __syncthreads();
-  if (n == 0) return;  // empty table
-  if (n == 1) {        // src/huffman.ts:71-75
-    if (tid == 0) lens[S.lsym[0]] = 1;
-    __syncthreads();
-    return;
+  {
+    const uint32_t cnt = (uint32_t)__popcll(__ballot(used));
+    if (lane == 0 && cnt) atomicAdd(&S.pm_n[a], cnt);
   }
-  // level 1: the sorted leaves; odd length drops the last item (src/huffman.ts:100-102)
-  for (uint32_t i = tid; i < n; i += HUFF_THREADS) {
-    S.w[0][i] = S.lw[i];
-    S.leafpos[0][i] = (uint16_t)i;
-  }
+  pm_sync<kWave>();
+  const uint32_t n = S.pm_n[a];
+  if (stamp >= 0) USTAMP(stamp);
+  if (n == 1 && T.t == 0) lens[S.lsym[b]] = 1;  // src/huffman.ts:71-75
+  const bool merge = n >= 2u;                    // (neither an empty table nor a single symbol)
+  const bool mine = merge && i < n;              // (np < n: a thread without a leaf has no package either)
+  const uint32_t lv = mine ? S.lw[b + i] : 0u;
   uint32_t len_prev = n & ~1u;
   uint32_t sel = 0;
-  __syncthreads();
-  static_assert(PM_MAXN <= 2 * HUFF_THREADS && PM_MAXN < 512, "two items of either kind per thread, nine search steps");
-  const uint32_t st0 = 1u << (31u - (uint32_t)__builtin_clz(n));  // first search step: the largest power of two <= n (>= np)
-  const bool wide = n > HUFF_THREADS;                             // (uniform) a second leaf / package per thread
+  const uint32_t st0 = merge ? 1u << (31u - (uint32_t)__builtin_clz(n)) : 0u;  // first search step: the largest power of two <= n (>= np)
   for (uint32_t k = 1; k < L; k++) {
     const uint32_t np = len_prev >> 1;  // packages of this level: pairs of the level before (src/huffman.ts:87-94); 1 <= np < n
-    const uint2* wp2 = reinterpret_cast<const uint2*>(S.w[sel]);
-    uint32_t* wc = S.w[sel ^ 1];
-    // thread t: leaves t and t + 256, packages t and t + 256 (fixed roles: no selects inside the search)
-    const uint32_t i0 = min(tid, n - 1u), i1 = min(tid + HUFF_THREADS, n - 1u);
-    const uint32_t j0 = min(tid, np - 1u), j1 = min(tid + HUFF_THREADS, np - 1u);
-    const uint32_t lv0 = S.lw[i0], lv1 = S.lw[i1];
-    const uint2 pa = wp2[j0], pb = wp2[j1];
-    const uint32_t pv0 = pa.x + pa.y, pv1 = pb.x + pb.y;
-    uint32_t ll0 = 0, ll1 = 0, pl0 = 0, pl1 = 0;  // leaf: #{packages < lv}; package: #{leaves <= pv}
-    if (!wide) {
+    const uint2* wp2 = reinterpret_cast<const uint2*>(S.w[sel] + 2u * b);
+    uint32_t* wc = S.w[sel ^ 1] + 2u * b;
+    if (mine) {
+      // leaf i and package i (clamped; fixed roles: no selects inside the search)
+      const uint2 pa = wp2[min(i, np - 1u)];
+      const uint32_t pv = pa.x + pa.y;
+      uint32_t ll = 0, pl = 0;  // leaf: #{packages < lv}; package: #{leaves <= pv}
 #pragma unroll 1
       for (uint32_t st = st0; st; st >>= 1) {
-        const uint32_t ml = ll0 + st, mp = pl0 + st;
+        const uint32_t ml = ll + st, mp = pl + st;
         const uint2 x = wp2[min(ml, np) - 1u];
-        const uint32_t y = S.lw[min(mp, n) - 1u];
-        ll0 = (ml <= np && x.x + x.y < lv0) ? ml : ll0;
-        pl0 = (mp <= n && y <= pv0) ? mp : pl0;
+        const uint32_t y = S.lw[b + min(mp, n) - 1u];
+        ll = (ml <= np && x.x + x.y < lv) ? ml : ll;
+        pl = (mp <= n && y <= pv) ? mp : pl;
       }
-    } else {
-#pragma unroll 1
-      for (uint32_t st = st0; st; st >>= 1) {
-        const uint32_t ml0 = ll0 + st, ml1 = ll1 + st, mp0 = pl0 + st, mp1 = pl1 + st;
-        const uint2 x0 = wp2[min(ml0, np) - 1u], x1 = wp2[min(ml1, np) - 1u];
-        const uint32_t y0 = S.lw[min(mp0, n) - 1u], y1 = S.lw[min(mp1, n) - 1u];
-        ll0 = (ml0 <= np && x0.x + x0.y < lv0) ? ml0 : ll0;
-        ll1 = (ml1 <= np && x1.x + x1.y < lv1) ? ml1 : ll1;
-        pl0 = (mp0 <= n && y0 <= pv0) ? mp0 : pl0;
-        pl1 = (mp1 <= n && y1 <= pv1) ? mp1 : pl1;
-      }
-    }
-    if (tid < n) {
-      wc[tid + ll0] = lv0;
-      S.leafpos[k][tid] = (uint16_t)(tid + ll0);
-    }
-    if (tid < np) wc[tid + pl0] = pv0;
-    if (wide) {
-      if (tid + HUFF_THREADS < n) {
-        wc[tid + HUFF_THREADS + ll1] = lv1;
-        S.leafpos[k][tid + HUFF_THREADS] = (uint16_t)(tid + HUFF_THREADS + ll1);
-      }
-      if (tid + HUFF_THREADS < np) wc[tid + HUFF_THREADS + pl1] = pv1;
+      wc[i + ll] = lv;
+      S.leafpos[k][b + i] = (uint16_t)(i + ll);
+      if (i < np) wc[i + pl] = pv;
     }
     len_prev = (n + np) & ~1u;
     sel ^= 1;
-    __syncthreads();
+    pm_sync<kWave>();
   }
   // selected prefix per level, from the last level down (src/huffman.ts:106-115): a = #{i : leafpos[k][i] < m}, counted
-  // by the first wavefront (leaf positions ascend with i, so the leaves below m are a prefix)
-  if (tid < 64u) {
+  // by the team's first wavefront (leaf positions ascend with i, so the leaves below m are a prefix)
+  if (merge && T.t < 64u) {
     uint32_t m = len_prev;
     for (int k = (int)L - 1; k >= 0; k--) {
-      uint32_t a = 0;
+      uint32_t cnt = 0;
 #pragma unroll
-      for (uint32_t c = 0; c < (PM_MAXN + 63) / 64; c++) {
-        const uint32_t i = c * 64u + lane;
-        a += (uint32_t)__popcll(__ballot(i < n && S.leafpos[k][min(i, n - 1u)] < m));
+      for (uint32_t c0 = 0; c0 < PM_MAXN; c0 += 64u) {  // (clamped loads, all in flight together)
+        const uint32_t j = c0 + lane;
+        cnt += (uint32_t)__popcll(__ballot(j < n && S.leafpos[k][b + min(j, n - 1u)] < m));
       }
-      if (lane == 0) S.a_k[k] = a;
-      m = 2u * (m - a);
+      if (lane == 0) S.a_k[a][k] = cnt;
+      m = 2u * (m - cnt);
     }
   }
-  __syncthreads();
-  for (uint32_t i = tid; i < n; i += HUFF_THREADS) {
+  pm_sync<kWave>();
+  if (mine) {
     uint32_t l = 0;
-    for (uint32_t k = 0; k < L; k++) l += (S.a_k[k] > i);
-    lens[S.lsym[i]] = (uint8_t)l;
+    for (uint32_t k = 0; k < L; k++) l += (S.a_k[a][k] > i);
+    lens[S.lsym[b + i]] = (uint8_t)l;
   }
-  __syncthreads();
+  pm_sync<kWave>();
 }
 
 // canonical codes (src/huffman.ts:117-151), stored bit-reversed for LSB-first packing.  The code of a
 // symbol is the first code of its length plus its rank among the symbols of that length: counts per
-// length by LDS atomics, ranks from ballots (lower lanes) plus per-wave counts (earlier waves and passes).
-__device__ static void canon_codes(HuffSmem& S, const uint8_t* lens, uint32_t nsym, uint16_t* codes) {
-  const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
-  if (tid < 16) {
-    S.ccount[tid] = 0;
-    S.crun[tid] = 0;
-  }
-  __syncthreads();
-  for (uint32_t s = tid; s < nsym; s += HUFF_THREADS)
-    if (lens[s]) atomicAdd(&S.ccount[lens[s]], 1u);
-  __syncthreads();
-  if (tid == 0) {
-    uint32_t code = 0;
-    for (uint32_t l = 1; l < 16; l++) {
-      S.cfirst[l] = code;
-      code = (code + S.ccount[l]) << 1;
-    }
-  }
-  for (uint32_t s0 = 0; s0 < nsym; s0 += HUFF_THREADS) {  // uniform trip count
-    const uint32_t s = s0 + tid;
-    const uint32_t l = s < nsym ? lens[s] : 0u;
-    uint64_t same = ~0ull;
+// length by LDS atomics, ranks from ballots (lower lanes) plus per-wave counts (the team's earlier wavefronts).  The
+// team's thread t holds symbol t; teams and their synchronisation as in pm_lengths.
+template <bool kWave>
+__device__ static void canon_codes(HuffSmem& S, const PmTeam T, const uint8_t* lens, uint32_t nsym, uint16_t* codes) {
+  const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6, a = T.base ? 1u : 0u;
+  const uint32_t wave0 = wave - (T.t >> 6);  // the team's first wavefront
+  const bool sym = T.t < T.size && T.t < nsym;
+  if (T.t < 16) S.ccount[a][T.t] = 0;
+  if (lane < 16) S.cwave[wave][lane] = 0;
+  pm_sync<kWave>();
+  const uint32_t l = sym ? lens[T.t] : 0u;
+  uint64_t same = ~0ull;
 #pragma unroll
-    for (int bt = 0; bt < 4; bt++) {
-      const bool bit = (l >> bt) & 1u;
-      const uint64_t bal = __ballot(bit);
-      same &= bit ? bal : ~bal;
+  for (int bt = 0; bt < 4; bt++) {
+    const bool bit = (l >> bt) & 1u;
+    const uint64_t bal = __ballot(bit);
+    same &= bit ? bal : ~bal;
+  }
+  const uint32_t below = (uint32_t)__popcll(same & zes_lanemask_lt());
+  if (l && below == 0) {
+    S.cwave[wave][l] = (uint16_t)__popcll(same);
+    atomicAdd(&S.ccount[a][l], (uint32_t)__popcll(same));
+  }
+  pm_sync<kWave>();
+  if (T.t == 0) {
+    uint32_t code = 0;
+    for (uint32_t k = 1; k < 16; k++) {
+      S.cfirst[a][k] = code;
+      code = (code + S.ccount[a][k]) << 1;
     }
-    const uint32_t below = (uint32_t)__popcll(same & zes_lanemask_lt());
-    if (lane < 16) S.cwave[wave][lane] = 0;
-    __syncthreads();  // cfirst / crun of the previous pass visible, cwave cleared
-    if (l && below == 0) S.cwave[wave][l] = (uint16_t)__popcll(same);
-    __syncthreads();
+  }
+  pm_sync<kWave>();
+  if (sym) {
     uint32_t code = 0;
     if (l) {
-      uint32_t rank = S.crun[l] + below;
-      for (uint32_t w = 0; w < wave; w++) rank += S.cwave[w][l];
-      code = __brev(S.cfirst[l] + rank) >> (32u - l);
+      uint32_t rank = below;
+      for (uint32_t w = wave0; w < wave; w++) rank += S.cwave[w][l];
+      code = __brev(S.cfirst[a][l] + rank) >> (32u - l);
     }
-    if (s < nsym) codes[s] = (uint16_t)code;
-    __syncthreads();
-    if (tid < 16) {
-      uint32_t add = 0;
-      for (uint32_t w = 0; w < HUFF_THREADS / 64; w++) add += S.cwave[w][tid];
-      S.crun[tid] += add;
-    }
+    codes[T.t] = (uint16_t)code;
   }
-  __syncthreads();
+  pm_sync<kWave>();
 }
 
 // LSB-first bits at a known offset of S.hdr (zeroed beforehand), from any thread
@@ -2440,52 +2429,54 @@ __global__ __launch_bounds__(HUFF_THREADS) void k_huff(ZesBlk* __restrict__ blks
                                                        uint32_t* __restrict__ codes_out, uint32_t* __restrict__ hdr_out) {
   __shared__ HuffSmem S;
   const uint32_t g = blockIdx.x, tid = threadIdx.x;
+  const uint32_t lane = tid & 63u, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const uint32_t* hg = hists + (uint64_t)g * 320;
-  for (uint32_t i = tid; i < 320; i += HUFF_THREADS) S.hist[i] = hg[i];
+  if (tid < 320) {
+    S.hist[tid] = hg[tid];
+    S.lens[tid] = 0;
+    S.codes[tid] = 0;
+  }
   for (uint32_t i = tid; i < ZES_HDR_WORDS; i += HUFF_THREADS) S.hdr[i] = 0;
   if (tid == 0) S.total_bits = 0;
   __syncthreads();
 
   USTAMP(0);
-  pm_lengths(S, S.hist, 286, 15, S.lens);             // src/deflate.ts:78
-  USTAMP(1);
-  pm_lengths(S, S.hist + 288, 30, 15, S.lens + 288);  // src/deflate.ts:79
-  USTAMP(2);
-  canon_codes(S, S.lens, 286, S.codes);
-  canon_codes(S, S.lens + 288, 30, S.codes + 288);
+  {  // both alphabets' lengths (src/deflate.ts:78-79) and codes side by side, in the same barrier rounds
+    const bool ll = wave < PM_MAXN / 64u;
+    const PmTeam T = ll ? PmTeam{tid, PM_MAXN, 0u} : PmTeam{lane, 64u, 288u};
+    const uint32_t nsym = ll ? 286u : 30u;
+    pm_lengths<false>(S, T, nsym, 15, S.lens + T.base, 1);
+    USTAMP(2);
+    canon_codes<false>(S, T, S.lens + T.base, nsym, S.codes + T.base);
+  }
   USTAMP(3);
 
-  // code-length sequence + run-length coding (src/deflate.ts:81-139), one thread per run
-  const uint32_t lane = tid & 63u, wave = tid >> 6;
+  // code-length sequence + run-length coding (src/deflate.ts:81-139), one thread per run; index i on thread i
   if (tid == 0) {
-    S.a_k[0] = 256;  // highest used lit/len symbol (the end-of-block code is always used)
-    S.a_k[1] = 0;    // highest used distance symbol
-    S.nrl = 0;
+    S.top[0] = 256;  // highest used lit/len symbol (the end-of-block code is always used)
+    S.top[1] = 0;    // highest used distance symbol
   }
   __syncthreads();
-  if (tid < 29 && S.hist[257 + tid]) atomicMax(&S.a_k[0], 257u + tid);
-  if (tid < 30 && S.hist[288 + tid]) atomicMax(&S.a_k[1], tid);
+  if (tid < 29 && S.hist[257 + tid]) atomicMax(&S.top[0], 257u + tid);
+  if (tid < 30 && S.hist[288 + tid]) atomicMax(&S.top[1], tid);
   __syncthreads();
-  const uint32_t HLIT = S.a_k[0] + 1u, HDIST = S.a_k[1] + 1u, ncl = HLIT + HDIST;  // <= 316
-  for (uint32_t i = tid; i < ncl; i += HUFF_THREADS) S.cl[i] = i < HLIT ? S.lens[i] : S.lens[288 + i - HLIT];
+  const uint32_t HLIT = S.top[0] + 1u, HDIST = S.top[1] + 1u, ncl = HLIT + HDIST;  // <= 316
+  if (tid < ncl) S.cl[tid] = tid < HLIT ? S.lens[tid] : S.lens[288 + tid - HLIT];
   if (tid < 32) S.hist[tid] = 0;  // reused as the histogram of the run-length symbols
   __syncthreads();
   // a run = maximal stretch of equal lengths (it may cross the lit/len | distance border); the reference
   // cuts it into chunks of at most 138 (zeros) or 6 (other lengths): a chunk of 4 or more becomes one
   // repeat token (zeros) or the length plus a "repeat previous" token, a shorter one plain lengths
   // run starts as bit masks (320 indices = five 64-bit words, index ncl counts as a start)
-#pragma unroll
-  for (int q = 0; q < 2; q++) {
-    const uint32_t i = tid + q * HUFF_THREADS;
-    const bool st = i < 320u && (i >= ncl || i == 0 || S.cl[i] != S.cl[i - 1]);
+  {
+    const bool st = tid < 320u && (tid >= ncl || tid == 0 || S.cl[tid] != S.cl[tid - 1]);
     const uint64_t m = __ballot(st);
-    if (lane == 0 && (i >> 6) < 5u) S.starts[i >> 6] = m;
+    if (lane == 0 && wave < 5u) S.starts[wave] = m;
   }
   __syncthreads();
-  uint32_t mytok[2] = {0, 0}, myn[2] = {0, 0};
-#pragma unroll
-  for (int q = 0; q < 2; q++) {
-    const uint32_t i = tid + q * HUFF_THREADS;
+  uint32_t mytok = 0, myn = 0;
+  {
+    const uint32_t i = tid;
     if (i < ncl && (i == 0 || S.cl[i] != S.cl[i - 1])) {
       const uint32_t v = S.cl[i];
       // next start after i: first set bit above i in the masks
@@ -2502,15 +2493,14 @@ __global__ __launch_bounds__(HUFF_THREADS) void k_huff(ZesBlk* __restrict__ blks
       const uint32_t n = nxt - i;
       const uint32_t cap = v ? 6u : 138u, per = v ? 2u : 1u;
       const uint32_t m = n % cap;
-      myn[q] = n;
-      mytok[q] = (n / cap) * per + (m >= 4u ? per : m);
+      myn = n;
+      mytok = (n / cap) * per + (m >= 4u ? per : m);
     }
   }
-  // exclusive scan of the token counts in index order (thread t holds indices t and t + 256)
-  uint32_t pre[2];
-#pragma unroll
-  for (int q = 0; q < 2; q++) {
-    uint32_t incl = mytok[q];
+  // exclusive scan of the token counts in index order (the indices lie in the first five wavefronts)
+  uint32_t pre, nrl = 0;
+  {
+    uint32_t incl = mytok;
 #pragma unroll
     for (int d = 1; d < 64; d <<= 1) {
       const uint32_t t = __shfl_up(incl, d);
@@ -2518,19 +2508,18 @@ __global__ __launch_bounds__(HUFF_THREADS) void k_huff(ZesBlk* __restrict__ blks
     }
     if (lane == 63) S.wsum[wave] = incl;
     __syncthreads();
-    uint32_t base = S.nrl;  // tokens of the first 256 indices (0 in the first round)
-    for (uint32_t w = 0; w < wave; w++) base += S.wsum[w];
-    pre[q] = base + incl - mytok[q];
-    __syncthreads();
-    if (tid == HUFF_THREADS - 1) S.nrl = pre[q] + mytok[q];
-    __syncthreads();
+    uint32_t base = 0;
+    for (uint32_t w = 0; w < 5u; w++) {
+      if (w < wave) base += S.wsum[w];
+      nrl += S.wsum[w];
+    }
+    pre = base + incl - mytok;
   }
-#pragma unroll
-  for (int q = 0; q < 2; q++) {
-    if (myn[q]) {
-      const uint32_t v = S.cl[tid + q * HUFF_THREADS];
+  {
+    if (myn) {
+      const uint32_t v = S.cl[tid];
       const uint32_t cap = v ? 6u : 138u;
-      uint32_t pos = pre[q], rem = myn[q];
+      uint32_t pos = pre, rem = myn;
       while (rem) {
         const uint32_t r = min(rem, cap);
         if (r >= 4u) {
@@ -2558,41 +2547,39 @@ __global__ __launch_bounds__(HUFF_THREADS) void k_huff(ZesBlk* __restrict__ blks
     }
   }
   __syncthreads();
-  const uint32_t nrl = S.nrl;
-  for (uint32_t i = tid; i < nrl; i += HUFF_THREADS) atomicAdd(&S.hist[S.rl_sym[i]], 1u);
+  if (tid < nrl) atomicAdd(&S.hist[S.rl_sym[tid]], 1u);  // (a token per index at the most)
   __syncthreads();
   USTAMP(4);
-  pm_lengths(S, S.hist, 19, 7, S.clens);  // src/deflate.ts:141
-  canon_codes(S, S.clens, 19, S.ccodes);
+  // the code-length code (src/deflate.ts:141) and HCLEN, 1 + the last index in transmission order whose symbol is used,
+  // by the first wavefront
+  if (wave == 0) {
+    const PmTeam T{lane, 64u, 0u};
+    pm_lengths<true>(S, T, 19, 7, S.clens, -1);
+    canon_codes<true>(S, T, S.clens, 19, S.ccodes);
+    const uint64_t used = __ballot(lane < 19 && S.clens[kClOrder[min(lane, 18u)]]);
+    if (lane == 0) S.top[2] = max(4u, 64u - (uint32_t)__builtin_clzll(used | 1ull));
+  }
+  __syncthreads();
   USTAMP(5);
 
   // header bits (src/deflate.ts:143-181): fixed fields, the code-length code, then the coded run-length tokens,
-  // each token ORed in at its bit offset (exclusive scan of the token bit counts)
-  if (tid == 0) S.a_k[2] = 4;  // HCLEN: 1 + last index in transmission order whose symbol is used
-  __syncthreads();
-  if (tid < 19 && S.clens[kClOrder[tid]]) atomicMax(&S.a_k[2], tid + 1u);
-  __syncthreads();
-  const uint32_t HCLEN = S.a_k[2];
+  // each token (token i on thread i) ORed in at its bit offset (exclusive scan of the token bit counts)
+  const uint32_t HCLEN = S.top[2];
   if (tid == 0) atomicOr(&S.hdr[0], (HLIT - 257u) | ((HDIST - 1u) << 5) | (((HCLEN - 4u) & 15u) << 10));
   if (tid < HCLEN) {
     uint32_t bp = 14u + 3u * tid;
     hdr_or(S, bp, S.clens[kClOrder[tid]], 3);  // src/deflate.ts:158-165
   }
-  uint32_t tv[2] = {0, 0}, tb[2] = {0, 0};
-#pragma unroll
-  for (int q = 0; q < 2; q++) {  // thread t holds tokens 2t and 2t + 1
-    const uint32_t i = 2u * tid + (uint32_t)q;
-    if (i < nrl) {
-      const uint32_t sy = S.rl_sym[i], cl = S.clens[sy];
-      const uint32_t xb = sy == 18u ? 7u : sy == 17u ? 3u : sy == 16u ? 2u : 0u;
-      const uint32_t xv = sy == 18u ? S.rl_val[i] - 11u : (sy == 17u || sy == 16u) ? S.rl_val[i] - 3u : 0u;
-      tv[q] = (uint32_t)S.ccodes[sy] | (xv << cl);
-      tb[q] = cl + xb;
-    }
+  uint32_t tv = 0, tb = 0;
+  if (tid < nrl) {
+    const uint32_t sy = S.rl_sym[tid], cl = S.clens[sy];
+    const uint32_t xb = sy == 18u ? 7u : sy == 17u ? 3u : sy == 16u ? 2u : 0u;
+    const uint32_t xv = sy == 18u ? S.rl_val[tid] - 11u : (sy == 17u || sy == 16u) ? S.rl_val[tid] - 3u : 0u;
+    tv = (uint32_t)S.ccodes[sy] | (xv << cl);
+    tb = cl + xb;
   }
   {
-    const uint32_t mine = tb[0] + tb[1];
-    uint32_t incl = mine;
+    uint32_t incl = tb;
 #pragma unroll
     for (int d = 1; d < 64; d <<= 1) {
       const uint32_t t = __shfl_up(incl, d);
@@ -2601,47 +2588,44 @@ __global__ __launch_bounds__(HUFF_THREADS) void k_huff(ZesBlk* __restrict__ blks
     if (lane == 63) S.wsum[wave] = incl;
     __syncthreads();
     uint32_t base = 14u + 3u * HCLEN, total = 0;
-    for (uint32_t w = 0; w < HUFF_THREADS / 64; w++) {
+    for (uint32_t w = 0; w < 5u; w++) {
       if (w < wave) base += S.wsum[w];
       total += S.wsum[w];
     }
-    uint32_t bp = base + incl - mine;
-    if (tb[0]) hdr_or(S, bp, tv[0], tb[0]);
-    bp += tb[0];
-    if (tb[1]) hdr_or(S, bp, tv[1], tb[1]);
+    if (tb) hdr_or(S, base + incl - tb, tv, tb);
     if (tid == 0) S.hdr_bits = 14u + 3u * HCLEN + total;
   }
   __syncthreads();
   USTAMP(6);
   // block bit count straight from the histograms
   uint32_t part = 0;
-  for (uint32_t s = tid; s < 286; s += HUFF_THREADS) {
-    uint32_t xb = (s >= 257) ? kLenXbits[s - 257] : 0u;
-    part += hg[s] * ((uint32_t)S.lens[s] + xb);
-  }
+  if (tid < 286) part = hg[tid] * ((uint32_t)S.lens[tid] + (tid >= 257 ? kLenXbits[tid - 257] : 0u));
   if (tid < 30) part += hg[288 + tid] * ((uint32_t)S.lens[288 + tid] + kDistXbits[tid]);
-  atomicAdd(&S.total_bits, part);
+  if (tid < 320) atomicAdd(&S.total_bits, part);
   __syncthreads();
   if (tid == 0) {
     blks[g].hdr_bits = S.hdr_bits;
     blks[g].bits = 3u + S.hdr_bits + S.total_bits;
   }
   uint32_t* cg = codes_out + (uint64_t)g * 320;
-  for (uint32_t i = tid; i < 320; i += HUFF_THREADS) cg[i] = (uint32_t)S.codes[i] | ((uint32_t)S.lens[i] << 16);
+  if (tid < 320) cg[tid] = (uint32_t)S.codes[tid] | ((uint32_t)S.lens[tid] << 16);
   uint32_t* hd = hdr_out + (uint64_t)g * ZES_HDR_WORDS;
   for (uint32_t i = tid; i < ZES_HDR_WORDS; i += HUFF_THREADS) hd[i] = S.hdr[i];
   USTAMP(7);
 }
 
-// stage-level entry for tests: lengths only
+// stage-level entry for tests: lengths only.  An alphabet of up to 64 symbols goes to one wavefront, as the code-length
+// code does in k_huff; a larger one to the lit/len team.
 __global__ __launch_bounds__(HUFF_THREADS) void k_huff_lengths_only(const uint32_t* __restrict__ hist, uint32_t nsym, uint32_t L,
                                                                     uint8_t* __restrict__ lens_out) {
   __shared__ HuffSmem S;
-  const uint32_t tid = threadIdx.x;
-  for (uint32_t i = tid; i < 320; i += HUFF_THREADS) S.hist[i] = i < nsym ? hist[i] : 0u;
+  const uint32_t tid = threadIdx.x, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  if (tid < 320) S.hist[tid] = tid < nsym ? hist[tid] : 0u;
   __syncthreads();
-  pm_lengths(S, S.hist, nsym, L, S.lens);
-  for (uint32_t i = tid; i < nsym; i += HUFF_THREADS) lens_out[i] = S.lens[i];
+  if (nsym > 64u) pm_lengths<false>(S, PmTeam{tid, PM_MAXN, 0u}, nsym, L, S.lens, -1);
+  else if (wave == 0) pm_lengths<true>(S, PmTeam{tid, 64u, 0u}, nsym, L, S.lens, -1);
+  __syncthreads();
+  if (tid < nsym) lens_out[tid] = S.lens[tid];
 }
 
 // ------------------------------------------------------------------------------------------

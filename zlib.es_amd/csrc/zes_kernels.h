@@ -30,7 +30,7 @@
 #define ZES_ROUTE_WALK3 32u            // phase 3 walked the true chain
 #define PARSE_THREADS 1024
 #define EMIT_THREADS 1024
-#define HUFF_THREADS_HOST 256
+#define HUFF_THREADS_HOST 384
 #define ADLER_THREADS 256
 #define ADLER_CHUNK 65536u
 // k_crc32 (zes_crc.hip): a workgroup per 64 KiB chunk, 16 pieces of 16 bytes per thread, 4096 bytes apart; the table
