@@ -981,7 +981,7 @@ int deflate_batch_core(const uint8_t* d_in, const uint64_t* in_off, const uint64
   rc = launch_lz77(d_in, nblk, use_index, nbuf > 1 && nblk > 256, sort_dbg, [&]() -> int {
     if (!sort_dbg) return ZES_OK;
     return phases_print(zes_sort_set_dbg, nblk, 7,
-                        "zes sort steps (avg cycles over %u blocks): zero %.0f count %.0f flag %.0f compact %.0f stage %.0f three passes %.0f sd/inv %.0f\n");
+                        "zes sort steps (avg cycles over %u blocks): zero %.0f count %.0f flags %.0f level 2 + compact %.0f stage %.0f three passes %.0f sd/inv %.0f\n");
   });
   if (rc) return rc;
   if (sort_dbg) {  // (the parser's stamps: armed inside launch_lz77, in front of its two parse launches)

@@ -104,6 +104,19 @@ __device__ __forceinline__ static uint4 sort_ld16(const uint8_t* __restrict__ sr
   return make_uint4(t[0], t[1], t[2], t[3]);
 }
 
+// the 3-byte key at position p of the block, from memory: the two aligned words that hold it (the second one is
+// fetched only where the key reaches into it, so no word without a byte of the block is touched).  srcw: the block's
+// start rounded down to a word, mis: the bytes it was rounded by (a uniform base and a 32-bit offset per lane)
+__device__ __forceinline__ static uint32_t sort_key_at(const uint32_t* __restrict__ srcw, uint32_t mis, uint32_t p) {
+  const uint32_t o = p + mis, s = o & 3u;
+  return __builtin_amdgcn_alignbyte(srcw[(o >> 2) + (s >= 2u ? 1u : 0u)], srcw[o >> 2], s) & 0xffffffu;
+}
+
+// second filter level: list words (two 16-bit entries each) a thread holds in registers, and the list that fits
+#define SORT_LIST_WORDS 16u
+#define SORT_LIST_CAP (SORT_THREADS * SORT_LIST_WORDS * 2u)
+static_assert(SORT_LIST_CAP * 4u <= ZES_BLK, "the final list of positions, one word each, lives in the block area");
+
 __global__ __launch_bounds__(SORT_THREADS) void k_lz_sort(const uint8_t* __restrict__ d_in, const ZesBuf* __restrict__ bufs,
                                                           const ZesBlk* __restrict__ blks, uint32_t* idx_a,
                                                           uint32_t* __restrict__ idx_b, uint32_t* inv_all, uint16_t* __restrict__ sd_all,
@@ -140,6 +153,8 @@ __global__ __launch_bounds__(SORT_THREADS) void k_lz_sort(const uint8_t* __restr
   __syncthreads();
   SSTAMP(1);
   const bool aligned = (((uintptr_t)src) & 15u) == 0;
+  const uint32_t mis4 = (uint32_t)((uintptr_t)src & 3u);
+  const uint32_t* srcw = reinterpret_cast<const uint32_t*>(src - mis4);
   const uint32_t p0 = tid * SORT_OWN;  // this thread's positions: [p0, p0 + 128) below cnt
   // pass 1: count every key (saturating at two: bit 0 = seen, bit 1 = seen again)
   uint32_t samp[SORT_OWN / 16];  // hash of the first key of each 16-position chunk: the survivor rate is sampled on these
@@ -277,8 +292,273 @@ __global__ __launch_bounds__(SORT_THREADS) void k_lz_sort(const uint8_t* __restr
       cur = nxt;
     }
   }
+  SSTAMP(3);
+  // Second level.  The first one leaves a fifth of the positions on incompressible data, spread evenly: a walk over all
+  // 128 positions of every thread issues an LDS instruction per position and wave whenever one lane of 64 needs it, that
+  // is always.  So the kept positions are listed first, in position order: 16-bit entries in the dead counter table
+  // (an entry at or behind index `nlo` lies in the block's upper half), from there two entries a word into registers,
+  // with the lanes of a wave on neighbouring words and the waves on consecutive shares of the list.  Both passes of the
+  // second level then run over the registers, a lane's key fetched from the input at its position, and the verdicts are
+  // ranked inside the wave: list order is position order.  The list fits the registers for up to SORT_LIST_CAP
+  // positions, a quarter of a full block; a block on this route that keeps more (its sampled positions are unlike the
+  // rest) walks all positions as before.
+  bool listed = false;
+  uint32_t n1 = 0, nlo = 0, at1 = 0;  // the first level's survivors: all, those below position 65536, those in front of this thread's
   if (two) {  // uniform
-    __syncthreads();  // every thread is done with the first level's counters
+    const uint32_t mine1 = (uint32_t)(__popc(f0) + __popc(f1) + __popc(f2) + __popc(f3));
+    uint32_t incl1 = mine1;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+      const uint32_t t = __shfl_up(incl1, d);
+      if ((int)lane >= d) incl1 += t;
+    }
+    if (lane == 63) S.wsum[wave] = incl1;
+    __syncthreads();  // also: every thread is done with the first level's counters
+    at1 = incl1 - mine1;
+#pragma unroll
+    for (uint32_t w = 0; w < SORT_WAVES; w++) {
+      const uint32_t v = S.wsum[w];
+      at1 += w < wave ? v : 0u;
+      nlo += w < SORT_WAVES / 2u ? v : 0u;  // the threads of the lower eight waves own the positions below 65536
+      n1 += v;
+    }
+    listed = n1 <= SORT_LIST_CAP;
+  }
+  if (listed) {  // uniform
+    uint32_t e[SORT_LIST_WORDS];
+    {
+      uint16_t* l16 = reinterpret_cast<uint16_t*>(S.in);
+      uint32_t o = at1;
+#pragma unroll
+      for (uint32_t w = 0; w < 4; w++) {
+        uint32_t f = w == 0u ? f0 : w == 1u ? f1 : w == 2u ? f2 : f3;
+        while (f) {
+          l16[o++] = (uint16_t)(p0 + 32u * w + (uint32_t)__builtin_ctz(f));
+          f &= f - 1u;
+        }
+      }
+    }
+    __syncthreads();
+    const uint32_t nwords = (n1 + 1u) >> 1;
+    const uint32_t wshare = (nwords + SORT_WAVES - 1u) / SORT_WAVES;  // words of the list per wave: at most 64 * SORT_LIST_WORDS
+#pragma unroll
+    for (uint32_t j = 0; j < SORT_LIST_WORDS; j++) e[j] = tbl[min(wave * wshare + 64u * j + lane, nwords ? nwords - 1u : 0u)];
+    // entry k of word j: its position (0 where the list has no such entry) and whether it is there
+#define SORT_LIST_ENTRY(j, k, pos, valid)                                              \
+  const uint32_t li_ = 2u * (wave * wshare + 64u * (j) + lane) + (k);                  \
+  const bool valid = 64u * (j) + lane < wshare && li_ < n1;                            \
+  const uint32_t pos = valid ? ((e[j] >> (16u * (k))) & 0xffffu) + (li_ >= nlo ? 65536u : 0u) : 0u
+    // Every entry's second hash, kept in registers for both passes (~0: no entry).  The loads are unconditional, with
+    // position 0 where there is no entry, and half of them in flight together: two memory latencies for the whole list.  (Fetched
+    // again in each pass, four words a step, the two passes and the compaction took 77k cycles a block on random data.)
+    uint32_t hh[2u * SORT_LIST_WORDS];
+#pragma unroll
+    for (uint32_t q0 = 0; q0 < 2u * SORT_LIST_WORDS; q0 += SORT_LIST_WORDS) {  // (two halves: all 64 words at once do not fit the registers)
+#pragma unroll
+      for (uint32_t q = q0; q < q0 + SORT_LIST_WORDS; q++) {
+        SORT_LIST_ENTRY(q >> 1, q & 1u, pos, valid);
+        const uint32_t key = sort_key_at(srcw, mis4, pos);
+        hh[q] = valid ? sort_hash2(key) : ~0u;
+      }
+#pragma unroll
+      for (uint32_t q = q0; q < q0 + SORT_LIST_WORDS; q += 4u) asm volatile("" : "+v"(hh[q]), "+v"(hh[q + 1u]), "+v"(hh[q + 2u]), "+v"(hh[q + 3u]));
+    }
+    __syncthreads();  // every thread has its words of the list
+    {
+      uint4* t4 = reinterpret_cast<uint4*>(S.in);
+      for (uint32_t i = tid; i < ZES_BLK / 16; i += SORT_THREADS) t4[i] = make_uint4(0, 0, 0, 0);
+    }
+    __syncthreads();
+    // level 2, count.  Eight returning adds in a row, then the eight second ones: no branch between them, a lane without
+    // an entry ORs nothing into a word of its own.
+#pragma unroll
+    for (uint32_t g8 = 0; g8 < 2u * SORT_LIST_WORDS; g8 += 8u) {
+      if (32u * g8 < wshare) {  // uniform: word g8 / 2 is in some lane's share
+        uint32_t old[8];
+#pragma unroll
+        for (uint32_t q = 0; q < 8; q++) {
+          const bool valid = hh[g8 + q] != ~0u;
+          const uint32_t h = valid ? hh[g8 + q] : tid * 16u, sh = (h & 15u) * 2u;
+          old[q] = atomicOr(&tbl[h >> 4], valid ? 1u << sh : 0u);
+        }
+#pragma unroll
+        for (uint32_t q = 0; q < 8; q++) {
+          const bool valid = hh[g8 + q] != ~0u;
+          const uint32_t h = valid ? hh[g8 + q] : tid * 16u, sh = (h & 15u) * 2u;
+          atomicOr(&tbl[h >> 4], (valid && ((old[q] >> sh) & 3u) == 1u) ? 2u << sh : 0u);
+        }
+      }
+    }
+    __syncthreads();
+    // level 2, flags: one verdict bit per entry
+    uint32_t vb = 0;
+#pragma unroll
+    for (uint32_t q = 0; q < 2u * SORT_LIST_WORDS; q++) {
+      const bool valid = hh[q] != ~0u;
+      const uint32_t h = valid ? hh[q] : 0u;
+      const uint32_t keep = (tbl[h >> 4] >> ((h & 15u) * 2u + 1u)) & 1u;
+      vb |= (valid ? keep : 0u) << q;
+    }
+    // ranks: the wave's total, the waves' totals, then entry by entry inside the wave
+    uint32_t wtot = (uint32_t)__popc(vb);
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) wtot += __shfl_xor(wtot, d);
+    if (lane == 0) S.wsum[wave] = wtot;
+    __syncthreads();  // also: every thread is done with the second level's counters
+    uint32_t run = 0;
+    ns = 0;
+#pragma unroll
+    for (uint32_t w = 0; w < SORT_WAVES; w++) {
+      const uint32_t v = S.wsum[w];
+      run += w < wave ? v : 0u;
+      ns += v;
+    }
+    uint32_t* fin = reinterpret_cast<uint32_t*>(S.in);  // the final list: at most SORT_LIST_CAP words
+#pragma unroll
+    for (uint32_t j = 0; j < SORT_LIST_WORDS; j++) {
+      if (64u * j < wshare) {  // uniform
+        const uint32_t b0 = (vb >> (2u * j)) & 1u, b1 = (vb >> (2u * j + 1u)) & 1u;
+        const uint64_t m0 = __ballot(b0), m1 = __ballot(b1);
+        const uint32_t at = run + (uint32_t)__popcll(m0 & zes_lanemask_lt()) + (uint32_t)__popcll(m1 & zes_lanemask_lt());
+        if (b0) {
+          SORT_LIST_ENTRY(j, 0u, pos, valid);
+          (void)valid;
+          fin[at] = pos;
+        }
+        if (b1) {
+          SORT_LIST_ENTRY(j, 1u, pos, valid);
+          (void)valid;
+          fin[at + b0] = pos;
+        }
+        run += (uint32_t)__popcll(m0) + (uint32_t)__popcll(m1);
+      }
+    }
+#undef SORT_LIST_ENTRY
+    __syncthreads();
+    // A list of at most one tile, from a block the eager match finder takes (it needs the sorted positions and nothing
+    // else), is sorted where it stands: keys and positions in registers in the tile's layout (wave w holds elements
+    // [512 w, 512 w + 512) in eight rounds of 64), three stable passes with the rank rule of the passes below, each
+    // scattering into LDS, and the sorted positions leave once.  No staged block, no trip through idx_a / idx_b.
+#ifdef NO_LAZY
+    const bool lazy_l = false;
+#else
+    const bool lazy_l = inv_all != nullptr && ns * 2u >= cnt;
+#endif
+    if (ns != 0u && ns <= SORT_TILE && !lazy_l) {  // uniform
+      static_assert(SORT_TILE * 8u <= ZES_BLK, "a tile's keys and positions fit the block area");
+      uint32_t* lkey = reinterpret_cast<uint32_t*>(S.in);       // [SORT_TILE] (the final list stands here until it is in registers)
+      uint32_t* lpos = lkey + SORT_TILE;                        // [SORT_TILE]
+      const uint32_t i0 = wave * (SORT_TILE / SORT_WAVES) + lane;
+      uint32_t kk[SORT_ROUNDS], pp[SORT_ROUNDS], rk[SORT_ROUNDS];
+#pragma unroll
+      for (uint32_t r = 0; r < SORT_ROUNDS; r++) pp[r] = fin[min(i0 + 64u * r, ns - 1u)];
+#pragma unroll
+      for (uint32_t r = 0; r < SORT_ROUNDS; r++) kk[r] = sort_key_at(srcw, mis4, pp[r]);
+#pragma unroll
+      for (uint32_t r = 0; r < SORT_ROUNDS; r++) {
+        if (i0 + 64u * r < ns) {
+          atomicAdd(&sub[0][(kk[r] >> 16) & 255u], 1u);
+          atomicAdd(&sub[1][(kk[r] >> 8) & 255u], 1u);
+          atomicAdd(&sub[2][kk[r] & 255u], 1u);
+        }
+      }
+      if (tid == 0) A[ZES_BLK - 1] = ns;
+      __syncthreads();  // the list is in registers, the histogram copies are complete
+      SSTAMP(4);
+      if (tid < 3 * 256) {
+        const uint32_t* hs = reinterpret_cast<const uint32_t*>(&S.whist[0][0][0]);
+        (&S.hist[0][0])[tid] = hs[tid] + hs[768 + tid] + hs[1536 + tid] + hs[2304 + tid];
+      }
+      __syncthreads();
+      // every pass's exclusive digit offsets, in place, by one wave each; every wave's counter row
+      if (wave < 3u) {
+        uint32_t c[4];
+        uint32_t sum = 0;
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+          c[k] = S.hist[wave][lane * 4 + k];
+          sum += c[k];
+        }
+        uint32_t in2 = sum;
+#pragma unroll
+        for (int d = 1; d < 64; d <<= 1) {
+          const uint32_t t = __shfl_up(in2, d);
+          if ((int)lane >= d) in2 += t;
+        }
+        uint32_t run2 = in2 - sum;
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+          S.hist[wave][lane * 4 + k] = run2;
+          run2 += c[k];
+        }
+      }
+      uint32_t* wrow = reinterpret_cast<uint32_t*>(&S.whist[0][wave][0]);
+      wrow[lane] = 0;  // (the rows lie in the area of the histogram copies: folded above, behind the barrier)
+      wrow[lane + 64u] = 0;
+      __syncthreads();
+      SSTAMP(5);
+      for (uint32_t pass = 0; pass < 3u; pass++) {
+        const uint32_t dsh = 16u - 8u * pass;  // least significant key byte first: the byte at offset 2
+        if (pass) {
+#pragma unroll
+          for (uint32_t r = 0; r < SORT_ROUNDS; r++) {
+            const uint32_t i = min(i0 + 64u * r, ns - 1u);
+            kk[r] = lkey[i];
+            pp[r] = lpos[i];
+          }
+        }
+#pragma unroll
+        for (uint32_t r = 0; r < SORT_ROUNDS; r++) {
+          const uint32_t d = (kk[r] >> dsh) & 255u, sh = 16u * (d & 1u);
+          const uint32_t old = (i0 + 64u * r < ns) ? atomicAdd(&wrow[d >> 1], 1u << sh) : 0u;
+          rk[r] = (old >> sh) & 0xffffu;
+        }
+        __syncthreads();  // counts visible; every element of the last pass's arrays is in registers
+        if (tid < 256) {
+          uint32_t o = 0;
+#pragma unroll
+          for (int w = 0; w < SORT_WAVES; w++) {
+            const uint32_t c = S.whist[0][w][tid];
+            S.whist[0][w][tid] = (uint16_t)o;  // offset of wave w inside the run of digit tid
+            o += c;
+          }
+        }
+        __syncthreads();  // offsets visible
+#pragma unroll
+        for (uint32_t r = 0; r < SORT_ROUNDS; r++) {
+          const uint32_t d = (kk[r] >> dsh) & 255u;
+          const uint32_t dst = S.hist[pass][d] + S.whist[0][wave][d] + rk[r];
+          if (i0 + 64u * r < ns) {
+            lkey[dst] = kk[r];
+            lpos[dst] = pp[r];
+          }
+        }
+        wrow[lane] = 0;  // this wave's own row, behind its own last reads of it
+        wrow[lane + 64u] = 0;
+        __syncthreads();
+      }
+      SSTAMP(6);
+      for (uint32_t i = tid; i < ns; i += SORT_THREADS) A[i] = lpos[i];
+      SSTAMP(7);
+      return;
+    }
+    // the list leaves for B with coalesced stores; its digit histograms (four copies picked by lane, as above)
+    for (uint32_t i = tid; i < ns; i += SORT_THREADS) {
+      const uint32_t pos = fin[i];
+      const uint32_t key = sort_key_at(srcw, mis4, pos);
+      B[i] = pos;
+      atomicAdd(&sub[0][(key >> 16) & 255u], 1u);
+      atomicAdd(&sub[1][(key >> 8) & 255u], 1u);
+      atomicAdd(&sub[2][key & 255u], 1u);
+    }
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the list is in memory before another wave reads it back
+    __syncthreads();
+    if (tid < 3 * 256) {
+      const uint32_t* hs = reinterpret_cast<const uint32_t*>(&S.whist[0][0][0]);
+      (&S.hist[0][0])[tid] = hs[tid] + hs[768 + tid] + hs[1536 + tid] + hs[2304 + tid];
+    }
+  } else {
+  if (two) {  // uniform
     {
       uint4* t4 = reinterpret_cast<uint4*>(S.in);
       for (uint32_t i = tid; i < ZES_BLK / 16; i += SORT_THREADS) t4[i] = make_uint4(0, 0, 0, 0);
@@ -343,7 +623,6 @@ __global__ __launch_bounds__(SORT_THREADS) void k_lz_sort(const uint8_t* __restr
       f3 = g3;
     }
   }
-  SSTAMP(3);
   // ordered compaction into B.  Exclusive scan of the per-thread counts; then the flag words and
   // their running totals go to LDS (the counter table is dead by then) so that the list can be
   // written with neighbouring lanes on neighbouring positions: coalesced stores.
@@ -402,7 +681,10 @@ __global__ __launch_bounds__(SORT_THREADS) void k_lz_sort(const uint8_t* __restr
       if ((w >> (p & 31u)) & 1u) B[fpre[p >> 5] + (uint32_t)__popc(w & ((1u << (p & 31u)) - 1u))] = p;
     }
   }
-  }  // !dense
+  }  // !listed
+  } else {  // dense
+    SSTAMP(3);
+  }
   __syncthreads();  // flag words (or, dense, the counter table) read before the block is staged over them
   SSTAMP(4);
   // Blocks that keep most of their positions (text, periodic data) go to the lazy match finder, which
