@@ -575,6 +575,64 @@ int zes_pngwrite_dev(const uint8_t* d_in, const uint64_t* in_off, const uint64_t
 int zes_pngwrite(const uint8_t* const* in, const uint64_t* in_len, const zes_pngw_image* img, const uint8_t* aux, uint32_t count,
                  zes_alloc_fn alloc, void* user, uint64_t* out_len, int32_t* status, uint32_t flags);
 
+/* zes_pngpix*: PNG files decoded to pixels, width * height * 4 bytes of R, G, B, A an image, row by row from the top, as one
+ * batch on the device: what a texture or an image tensor takes.  No Adam7 interlace, no gamma, no colour management, no
+ * output format other than 8-bit RGBA.
+ * The conversion rule.  A stored sample s of depth d becomes 8 bits: d = 1: s * 255; 2: s * 85; 4: s * 17; 8: s; 16: s >> 8
+ * (the high byte: libpng's strip_16).  Per colour type:
+ *   0 (grey)        R = G = B = the 8-bit grey, A = 255.  With a tRNS of 2 bytes, A = 0 exactly where the stored sample, at its
+ *                   full depth before the reduction, equals the big-endian key (all 16 bits of it: a key above the depth's
+ *                   range matches nothing)
+ *   2 (RGB)         R, G, B reduced, A = 255.  With a tRNS of 6 bytes, A = 0 where all three stored samples equal the three
+ *                   keys at full depth (all 16 bits at depth 16)
+ *   3 (palette)     index i gives PLTE entry i; A = tRNS[i] for i < trns_len, else 255.  An index at or beyond plte_len / 3
+ *                   gives (0, 0, 0, 255), as PIL and browsers do: decided here so that a pixel needs no status and the call no
+ *                   read-back for one
+ *   4 (grey, alpha) the grey replicated, A the alpha sample reduced
+ *   6 (RGBA)        all four samples reduced; at depth 8 a copy
+ * A tRNS whose length does not fit the colour type — other than 2 for colour 0, other than 6 for colour 2, above
+ * plte_len / 3 for colour 3, any for colours 4 and 6 — is ignored as if the file had none: the file rule lets such files
+ * through, and these calls do not refuse them.
+ *
+ * zes_pngpix_dev / zes_pngpix_alloc take the arguments of zes_png_decode_dev / zes_png_decode_alloc, fill the same
+ * zes_png_info, and answer the same statuses from the same steps 1 to 4 in the same order (flags: ZES_F_PIECES only), with
+ * these differences:
+ *   size    the size of image i is width * height * 4: what out_len[i] reports (on ZES_OK and ZES_E_NOSPACE), what out_cap[i]
+ *           is compared with and what alloc is asked for.  A call whose capacities are all 0 is the sizing pass and costs the
+ *           walk alone
+ *   step 4  writes the unfiltered scanlines into pooled scratch, a 16-byte aligned and padded slot an image (zes_trim,
+ *           zes_pool_bytes and zes_stage_poison cover it), not into the caller's memory
+ *   step 5  one k_png_expand launch for the batch writes the pixels of the images still at ZES_OK.  PLTE and tRNS are read on
+ *           the device from the file bytes at plte_pos / trns_pos, at any alignment (step 2 has checked their CRCs)
+ * An image with a status costs no later launch for itself; there is no launch, copy or synchronisation per image.  A call
+ * over one file launches the kernels that a call over many files of the same kind launches (in step 3 the block-parallel
+ * tier follows a single stream's block chain with its chain kernel as it follows a batch's, where the decode calls let
+ * the host follow it).
+ * The device form writes image i to d_out + out_off[i] at any alignment: exactly width * height * 4 bytes for an image at
+ * ZES_OK and no byte outside the ranges of the images that reach step 5, which must not overlap.  Stores are 16 bytes wide
+ * from the first 16-byte boundary of a row's output, whole pixels in front of it and at the row's end; an output that is
+ * not 4-byte aligned is stored byte by byte (slower, the same bytes).
+ *
+ * zes_pngpix_expand_dev is step 5 alone, over scanlines that lie in device memory already (kept from zes_png_decode_dev,
+ * say): image i is in_len[i] bytes at d_in + in_off[i], described by img[i] and the aux bytes exactly as zes_pngwrite_dev
+ * takes them; the filter field is ignored.  Statuses:
+ *   per image   ZES_E_ARG and ZES_E_UNSUPPORTED by steps 1 and 2 of zes_pngwrite* (one check serves both), out_len[i] = 0;
+ *               ZES_E_NOSPACE when out_cap[i] < width * height * 4 or d_out is NULL, out_len[i] the size needed
+ *   whole call  ZES_E_ARG as for zes_pngwrite_dev (flag bits other than ZES_F_PIECES, which changes nothing here)
+ *   count == 0, and a batch with nothing to write, are ZES_OK without device work
+ * It costs one upload (the job table and the aux bytes of the images that are written) and one launch, and reads nothing
+ * back: a status can only come from the host's checks.  d_in, d_out and every offset may have any alignment; exactly
+ * width * height * 4 bytes are written for an image at ZES_OK and none outside those ranges; the input is read only inside
+ * the aligned 16-byte groups that hold it (zes_pngwrite_dev's rule for its input).
+ * replaces: nothing (the reference has no PNG container) */
+int zes_pngpix_dev(const uint8_t* d_in, const uint64_t* in_off, const uint64_t* in_len, uint32_t count, uint8_t* d_out,
+                   const uint64_t* out_off, const uint64_t* out_cap, uint64_t* out_len, int32_t* status, zes_png_info* info, uint32_t flags);
+int zes_pngpix_alloc(const uint8_t* const* in, const uint64_t* in_len, uint32_t count, zes_alloc_fn alloc, void* user, uint64_t* out_len,
+                     int32_t* status, zes_png_info* info, uint32_t flags);
+int zes_pngpix_expand_dev(const uint8_t* d_in, const uint64_t* in_off, const uint64_t* in_len, const zes_pngw_image* img, const uint8_t* aux,
+                          uint32_t count, uint8_t* d_out, const uint64_t* out_off, const uint64_t* out_cap, uint64_t* out_len, int32_t* status,
+                          uint32_t flags);
+
 /* Adler-32 of a buffer (standard value as an unsigned 32-bit).
  * replaces: `calcAdler32` src/adler32.ts:1-10 (byte extraction at src/zlib.ts:37-40). */
 int zes_adler32(const uint8_t* in, uint64_t n, uint32_t* adler);

@@ -163,6 +163,9 @@ def lib():
         L.zes_pngwrite_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p,
                                        C.c_void_p, C.c_void_p, C.c_uint32]
         L.zes_pngwrite.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, ALLOC_FN, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32]
+        L.zes_pngpix_dev.argtypes = L.zes_png_decode_dev.argtypes
+        L.zes_pngpix_alloc.argtypes = L.zes_png_decode_alloc.argtypes
+        L.zes_pngpix_expand_dev.argtypes = L.zes_pngwrite_dev.argtypes
         L.zes_gunzip_alloc.argtypes = [C.c_void_p, C.c_uint64, ALLOC_FN, C.c_void_p, u64p, C.c_uint32]
         L.zes_adler32.argtypes = [C.c_void_p, C.c_uint64, u32p]
         L.zes_adler32_dev.argtypes = [C.c_void_p, C.c_uint64, u32p]
@@ -634,10 +637,9 @@ def png_info(data):
     return info[0]
 
 
-def png_decode_batch(buffers, flags=0):
-    """PNG files decoded as one batch (zes_png_decode_alloc): a list with one ``(info, scanlines)`` pair or one ZlibEsError
-    per file (not raised, as with zip_read).  ``scanlines`` is a uint8 array of ``height`` x ``rowbytes``: the samples as the
-    file stores them (16-bit big-endian, sub-byte samples packed, palette indices), the filters undone."""
+def _png_batch(pix, buffers, flags):
+    """png_decode_batch (zes_png_decode_alloc) and, with ``pix``, png_pixels_batch (zes_pngpix_alloc): one call, the results
+    shaped per image."""
     arrs = [_as_u8(b) for b in buffers]
     cnt = len(arrs)
     got = {}
@@ -651,16 +653,41 @@ def png_decode_batch(buffers, flags=0):
     out_len = np.zeros(max(cnt, 1), dtype=np.uint64)
     status = np.zeros(max(cnt, 1), dtype=np.int32)
     info = np.zeros(max(cnt, 1), dtype=PNG_INFO)
-    rc = lib().zes_png_decode_alloc(ptrs, _ptr(ln), cnt, ALLOC_FN(alloc), None, out_len.ctypes.data, status.ctypes.data, info.ctypes.data, flags)
+    fn = lib().zes_pngpix_alloc if pix else lib().zes_png_decode_alloc
+    rc = fn(ptrs, _ptr(ln), cnt, ALLOC_FN(alloc), None, out_len.ctypes.data, status.ctypes.data, info.ctypes.data, flags)
     if rc:
         _raise(rc)
-    return [(info[i], got[i][: int(out_len[i])].reshape(int(info[i]["height"]), int(info[i]["rowbytes"]))) if status[i] == 0
+    shape = lambda r: (int(r["height"]), int(r["width"]), 4) if pix else (int(r["height"]), int(r["rowbytes"]))
+    return [(info[i], got[i][: int(out_len[i])].reshape(shape(info[i]))) if status[i] == 0
             else ZlibEsError(int(status[i]), strerror(int(status[i]))) for i in range(cnt)]
+
+
+def png_decode_batch(buffers, flags=0):
+    """PNG files decoded as one batch (zes_png_decode_alloc): a list with one ``(info, scanlines)`` pair or one ZlibEsError
+    per file (not raised, as with zip_read).  ``scanlines`` is a uint8 array of ``height`` x ``rowbytes``: the samples as the
+    file stores them (16-bit big-endian, sub-byte samples packed, palette indices), the filters undone."""
+    return _png_batch(False, buffers, flags)
 
 
 def png_decode(data, flags=0):
     """One PNG file decoded: ``(info, scanlines)`` as png_decode_batch gives them; a file that fails raises."""
     got = png_decode_batch([data], flags)[0]
+    if isinstance(got, Exception):
+        raise got
+    return got
+
+
+def png_pixels_batch(buffers, flags=0):
+    """PNG files decoded to pixels as one batch (zes_pngpix_alloc): a list with one ``(info, rgba)`` pair or one ZlibEsError
+    per file (not raised, as with png_decode_batch).  ``rgba`` is a uint8 array of ``height`` x ``width`` x 4: R, G, B, A by
+    the conversion rule of include/zes.h (sub-byte samples scaled, 16-bit samples cut to their high byte, the palette looked
+    up, tRNS applied)."""
+    return _png_batch(True, buffers, flags)
+
+
+def png_pixels(data, flags=0):
+    """One PNG file decoded to pixels: ``(info, rgba)`` as png_pixels_batch gives them; a file that fails raises."""
+    got = png_pixels_batch([data], flags)[0]
     if isinstance(got, Exception):
         raise got
     return got
@@ -999,6 +1026,11 @@ def png_decode_tensor(d_in, in_off, in_len, out=None, off=None, flags=0, cap=Non
     first and the images are packed at 16-byte boundaries from the start of ``out``, which is allocated when it is None.
     ``cap``: the capacity of every image's place (default: up to the end of ``out``); an image that needs more is
     ZES_E_NOSPACE with its ``out_len`` the size needed."""
+    return _png_tensor(False, d_in, in_off, in_len, out, off, flags, cap)
+
+
+def _png_tensor(_pix, d_in, in_off, in_len, out, off, flags, cap):
+    """png_decode_tensor and, with ``_pix``, png_pixels_tensor: the same arguments, sizing pass and placement."""
     import torch
 
     assert d_in.is_cuda and d_in.dtype == torch.uint8 and d_in.is_contiguous()
@@ -1014,8 +1046,8 @@ def png_decode_tensor(d_in, in_off, in_len, out=None, off=None, flags=0, cap=Non
     src = d_in.data_ptr() if d_in.numel() else None
 
     def call(dst, o, c):
-        rc = lib().zes_png_decode_dev(src, _ptr(ioff), _ptr(ilen), cnt, dst, _ptr(o), _ptr(c), out_len.ctypes.data, status.ctypes.data,
-                                      info.ctypes.data, flags)
+        fn = lib().zes_pngpix_dev if _pix else lib().zes_png_decode_dev
+        rc = fn(src, _ptr(ioff), _ptr(ilen), cnt, dst, _ptr(o), _ptr(c), out_len.ctypes.data, status.ctypes.data, info.ctypes.data, flags)
         if rc:
             _raise(rc)
 
@@ -1037,6 +1069,13 @@ def png_decode_tensor(d_in, in_off, in_len, out=None, off=None, flags=0, cap=Non
     assert cap.size == cnt and all(int(o) + int(c) <= out.numel() for o, c in zip(off, cap)), "png_decode_tensor: a place reaches beyond `out`"
     call(out.data_ptr() if out.numel() else None, off, cap)
     return out, off, [int(x) for x in out_len[:cnt]], [int(x) for x in status[:cnt]], info[:cnt]
+
+
+def png_pixels_tensor(d_in, in_off, in_len, out=None, off=None, flags=0, cap=None):
+    """PNG files in a 1-D uint8 CUDA tensor decoded to pixels as one batch (zes_pngpix_dev): png_decode_tensor's arguments and
+    result, ``(out, off, out_len, status, info)``, with image i's ``width * height * 4`` bytes of R, G, B, A at
+    ``out[off[i] : off[i] + out_len[i]]`` (the conversion rule of include/zes.h)."""
+    return _png_tensor(True, d_in, in_off, in_len, out, off, flags, cap)
 
 
 def png_encode_tensor(d_in, in_off, in_len, images, aux=b"", out=None, off=None, cap=None, flags=0):
@@ -1079,6 +1118,53 @@ def png_encode_tensor(d_in, in_off, in_len, images, aux=b"", out=None, off=None,
     rc = lib().zes_pngwrite_dev(d_in.data_ptr() if d_in.numel() else None, _ptr(ioff), _ptr(ilen), _ptr(img), _ptr(a), cnt,
                                 out.data_ptr() if out is not None and out.numel() else None, _ptr(off), _ptr(cap), out_len.ctypes.data,
                                 status.ctypes.data, flags)
+    if rc:
+        _raise(rc)
+    return out, off, [int(x) for x in out_len[:cnt]], [int(x) for x in status[:cnt]]
+
+
+def png_expand_tensor(d_in, in_off, in_len, images, aux=b"", out=None, off=None, cap=None):
+    """Scanlines in a 1-D uint8 CUDA tensor turned into pixels in one launch (zes_pngpix_expand_dev): png_encode_tensor's
+    arguments — image i's scanlines are ``d_in[in_off[i] : in_off[i] + in_len[i]]`` as png_decode_tensor leaves them,
+    ``images[i]`` (a PNGW_IMAGE array, its ``filter`` ignored) says what they are, ``aux`` holds every image's PLTE then tRNS
+    data.  Returns ``(out, off, out_len, status)``: image i's ``width * height * 4`` bytes of R, G, B, A are
+    ``out[off[i] : off[i] + out_len[i]]`` when ``status[i]`` is 0, and nothing else of ``out`` is written.  Without ``off`` the
+    images are packed at 16-byte boundaries and ``out`` is allocated when it is None; ``cap`` as in png_encode_tensor."""
+    import torch
+
+    assert d_in.is_cuda and d_in.dtype == torch.uint8 and d_in.is_contiguous()
+    ioff = np.ascontiguousarray(in_off, dtype=np.uint64)
+    ilen = np.ascontiguousarray(in_len, dtype=np.uint64)
+    img = np.ascontiguousarray(images, dtype=PNGW_IMAGE).reshape(-1)
+    cnt = ilen.size
+    assert ioff.ndim == 1 and ioff.shape == ilen.shape and img.size == cnt, "png_expand_tensor: one offset, one length and one record per image"
+    plain = img.copy()
+    plain["filter"] = 0
+    ok = np.array(png_bound(plain), dtype=np.uint64) != 0  # (the writer's rule on the records: the call's own check)
+    assert all(int(o) + int(n) <= d_in.numel() for o, n, k in zip(ioff, ilen, ok) if k), "png_expand_tensor: an image reaches beyond `d_in`"
+    a = np.frombuffer(bytes(aux), dtype=np.uint8)
+    if off is None:
+        sizes = np.where(ok, img["width"].astype(np.uint64) * img["height"].astype(np.uint64) * np.uint64(4), np.uint64(0)).astype(np.uint64)
+        sizes = (sizes + np.uint64(15)) & ~np.uint64(15)
+        off = np.concatenate([np.zeros(1, dtype=np.uint64), np.cumsum(sizes, dtype=np.uint64)])[:cnt]
+        if out is None:
+            out = torch.empty(int(sizes.sum()), dtype=torch.uint8, device=d_in.device)
+        if cap is None:
+            cap = sizes
+    off = np.ascontiguousarray(off, dtype=np.uint64)
+    assert off.size == cnt, "png_expand_tensor: one offset per image"
+    if cap is None:
+        cap = np.array([max((out.numel() if out is not None else 0) - int(o), 0) for o in off], dtype=np.uint64)
+    cap = np.ascontiguousarray(cap, dtype=np.uint64)
+    if out is not None:
+        assert out.is_cuda and out.dtype == torch.uint8 and out.is_contiguous()
+        assert cap.size == cnt and all(int(o) + int(c) <= out.numel() for o, c in zip(off, cap)), "png_expand_tensor: a place reaches beyond `out`"
+    torch.cuda.current_stream(d_in.device).synchronize()
+    out_len = np.zeros(max(cnt, 1), dtype=np.uint64)
+    status = np.zeros(max(cnt, 1), dtype=np.int32)
+    rc = lib().zes_pngpix_expand_dev(d_in.data_ptr() if d_in.numel() else None, _ptr(ioff), _ptr(ilen), _ptr(img), _ptr(a), cnt,
+                                     out.data_ptr() if out is not None and out.numel() else None, _ptr(off), _ptr(cap), out_len.ctypes.data,
+                                     status.ctypes.data, 0)
     if rc:
         _raise(rc)
     return out, off, [int(x) for x in out_len[:cnt]], [int(x) for x in status[:cnt]]

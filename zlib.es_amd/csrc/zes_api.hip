@@ -161,7 +161,9 @@ static_assert(disjoint({PIN_SPAN(t2.search), PIN_SPAN(t2.ncand), PIN_SPAN(t2.nsu
   /* group's encoder slots, gz_tab for its member records */                                                                      \
   X(crctab) X(crcacc) X(gz_in) X(gz_acc) X(gz_stage) X(gz_bodies) X(gz_outs) X(gz_tab) X(crcseg)                                  \
   /* seg_checksum_locked's segs | work | acc for the Adler-32; the gathered trailers of a checked inflate batch */                \
-  X(adlerseg)
+  X(adlerseg)                                                                                                                     \
+  /* zes_pngpix*: the unfiltered scanlines of a batch, a padded slot an image, on their way to k_png_expand */                    \
+  X(png_lines)
 
 // The survivor list of the block-start search as the block-parallel tier's scan left it in a pool (one buffer): the
 // segment-parallel tier's search of the same stream starts from it instead of scanning again.  The note holds until it
@@ -210,6 +212,7 @@ struct Ctx {
   std::vector<std::pair<std::string, KTime>> carry;  // times collected in the middle of a call (a nested inflate_jobs) that its last collect_times puts in front of its own
   std::vector<std::string> name_pool;
   int last_tier = 0;
+  bool device_chain = false;  // the block-parallel tier follows a single buffer's chain with k_inf_chain too, not on the host (pngpix_core)
   int last_members = 0;  // members the member-parallel gzip reader decoded in the last gunzip call (0: the serial path answered)
   uint32_t route[ZES_ROUTE_WORDS] = {0};  // zes_stage_lz77_dev's last block: what its kernels did (zes_stage_lz77_route)
   SurvList sv;  // (of `surv`)
@@ -1349,7 +1352,7 @@ int t1_decode(T1Group& t) {
   // a 0.8 ms call).  Only a chain that needs the slots moved (false candidates between the blocks) still runs that kernel,
   // for its map.
   ZesParMirror mir{};
-  if (t.one && t.work <= MIRROR_ITEMS && g.mirror_dev && g.pinned_dev) {
+  if (t.one && !g.device_chain && t.work <= MIRROR_ITEMS && g.mirror_dev && g.pinned_dev) {
     mir.cres_host = g.mirror_dev->cres;
     mir.start_host = g.mirror_dev->start;
     mir.counters = t.counters;
@@ -5749,8 +5752,84 @@ static void png_judge(const PngImg& m, uint32_t i, uint64_t* out_len, int32_t* s
   status[i] = m.h.status != ZES_OK ? m.h.status : m.h.interlace ? ZES_E_UNSUPPORTED : ZES_OK;
 }
 
-int zes_png_decode_dev(const uint8_t* d_in, const uint64_t* in_off, const uint64_t* in_len, uint32_t count, uint8_t* d_out, const uint64_t* out_off,
-                       const uint64_t* out_cap, uint64_t* out_len, int32_t* status, zes_png_info* info, uint32_t flags) {
+// ---- step 5 of zes_pngpix* (include/zes.h: "The conversion rule"), which zes_pngpix_expand_dev runs alone ----
+// What k_png_expand is told about one image, and the tiles it takes behind *tiles.  The rule's reading of tRNS: a length that
+// does not fit the colour type counts as none
+static ZesPngxJob pngx_job(uint32_t width, uint32_t height, uint32_t colour, uint32_t depth, uint32_t plte_len, uint64_t trns_len, uint64_t* tiles) {
+  ZesPngxJob j;
+  memset(&j, 0, sizeof j);
+  j.width = width, j.height = height, j.rowbytes = (uint32_t)png_rowbytes(width, colour, depth);
+  j.depth = (uint8_t)depth, j.colour = (uint8_t)colour;
+  j.plte_len = colour == 3 ? (uint16_t)std::min<uint32_t>(plte_len, 768) : 0;
+  const bool fits = colour == 0 ? trns_len == 2 : colour == 2 ? trns_len == 6 : colour == 3 && trns_len <= plte_len / 3;
+  j.trns_len = fits ? (uint16_t)trns_len : 0;
+  j.tile_rows = std::min(height, std::max(1u, ZES_PNGX_TILE_PIXELS / width));
+  j.first_tile = (uint32_t)*tiles;
+  *tiles += (height + j.tile_rows - 1) / j.tile_rows;
+  return j;
+}
+static_assert(sizeof(ZesPngxJob) == 64, "ZesPngxJob is 64 bytes");
+static uint64_t png_pix_size(uint32_t width, uint32_t height) { return 4ull * width * height; }
+
+// One k_png_expand launch over `table`: njobs records and, behind them, the PLTE and tRNS bytes that came from the host (none
+// when d_aux is given: the jobs then point into those bytes, the files).  One upload into g.gz_tab, one launch; the
+// synchronisation ends the call's device work.  `table` is the caller's and outlives this function.
+static int pngx_run(const uint8_t* d_lines, const uint8_t* d_aux, uint8_t* d_out, const std::vector<uint8_t>& table, uint32_t njobs, uint64_t tiles) {
+  int rc;
+  if (tiles > 0x7fffffffull) return ZES_E_ARG;
+  if ((rc = ensure(g.gz_tab, table.size() + 16))) return rc;
+  Drain drain;
+  HIPCHK(hipMemcpyAsync(g.gz_tab.p, table.data(), table.size(), hipMemcpyHostToDevice, g.stream));
+  {
+    Timed t("k_png_expand");
+    hipLaunchKernelGGL(k_png_expand, dim3((uint32_t)tiles), dim3(ZES_PNGX_THREADS), 0, g.stream, d_lines,
+                       d_aux ? d_aux : (const uint8_t*)g.gz_tab.p + sizeof(ZesPngxJob) * (size_t)njobs, d_out, (const ZesPngxJob*)g.gz_tab.p, njobs);
+  }
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipStreamSynchronize(g.stream));
+  drain.done();
+  return ZES_OK;
+}
+
+// Steps 2 to 5 of zes_pngpix* for the images whose status[k] is ZES_OK on entry, im[k].dst_off the place of their pixels in
+// dst: png_decode_core with a padded slot of g.png_lines as every image's place, then the pixels of those that came through
+static int pngpix_core(const uint8_t* d_src, std::vector<PngImg>& im, uint8_t* dst, int32_t* status, uint32_t flags) {
+  int rc;
+  const uint32_t n = (uint32_t)im.size();
+  std::vector<uint64_t> pix_off(n);
+  uint64_t at = 0;
+  for (uint32_t k = 0; k < n; k++) {
+    pix_off[k] = im[k].dst_off;
+    if (status[k] != ZES_OK) continue;
+    im[k].dst_off = at;
+    at += gz_up16(im[k].h.height * png_rowbytes(im[k].h)) + 16;
+  }
+  if (at && (rc = ensure(g.png_lines, at + 64))) return rc;
+  // The pixel forms launch the same kernels for one image as for many: a single stream's block chain is followed by
+  // k_inf_chain as a batch's is, not on the host (a kernel of about 11 us; the design point is a batch)
+  g.device_chain = true;
+  rc = png_decode_core(d_src, im, (uint8_t*)g.png_lines.p, status, flags);
+  g.device_chain = false;
+  if (rc) return rc;
+  std::vector<uint8_t> table;
+  uint64_t tiles = 0;
+  uint32_t njobs = 0;
+  for (uint32_t k = 0; k < n; k++) {
+    if (status[k] != ZES_OK) continue;
+    const ZesPngHead& h = im[k].h;
+    ZesPngxJob j = pngx_job(h.width, h.height, h.colour, h.depth, h.plte_len, h.trns_len, &tiles);
+    j.src_off = im[k].dst_off, j.dst_off = pix_off[k];
+    j.plte_off = im[k].src_at + h.plte_pos, j.trns_off = im[k].src_at + h.trns_pos;
+    table.insert(table.end(), (const uint8_t*)&j, (const uint8_t*)&j + sizeof j);
+    njobs++;
+  }
+  return njobs ? pngx_run((const uint8_t*)g.png_lines.p, d_src, dst, table, njobs, tiles) : ZES_OK;
+}
+
+// The device forms: zes_png_decode_dev, and with `pix` zes_pngpix_dev — the same steps and statuses, the size an image needs
+// and the core behind step 1 apart
+static int png_dev_form(bool pix, const uint8_t* d_in, const uint64_t* in_off, const uint64_t* in_len, uint32_t count, uint8_t* d_out,
+                        const uint64_t* out_off, const uint64_t* out_cap, uint64_t* out_len, int32_t* status, zes_png_info* info, uint32_t flags) {
   ROUTE_DEV(d_in, d_out);
   if (const int arc = png_decode_args(in_off && in_len && out_off && out_cap, out_len, status, count, flags)) return arc;
   for (uint32_t i = 0; i < count; i++)
@@ -5769,19 +5848,20 @@ int zes_png_decode_dev(const uint8_t* d_in, const uint64_t* in_off, const uint64
     im[i].src_at = in_off[i];
     im[i].dst_off = out_off[i];
     if (status[i] != ZES_OK) continue;
-    out_len[i] = mine.out_size;
-    if (out_cap[i] < mine.out_size) status[i] = ZES_E_NOSPACE;
+    out_len[i] = pix ? png_pix_size(mine.width, mine.height) : mine.out_size;
+    if (out_cap[i] < out_len[i]) status[i] = ZES_E_NOSPACE;
     else null_out = null_out || !d_out;
   }
   if (null_out) return call_done(ZES_E_ARG, true);
-  if ((rc = call_done(png_decode_core(d_in, im, d_out, status, flags), true))) return rc;
+  if ((rc = call_done(pix ? pngpix_core(d_in, im, d_out, status, flags) : png_decode_core(d_in, im, d_out, status, flags), true))) return rc;
   for (uint32_t i = 0; i < count; i++)
     if (status[i] != ZES_OK && status[i] != ZES_E_NOSPACE) out_len[i] = 0;
   return ZES_OK;
 }
 
-int zes_png_decode_alloc(const uint8_t* const* in, const uint64_t* in_len, uint32_t count, zes_alloc_fn alloc, void* user, uint64_t* out_len,
-                         int32_t* status, zes_png_info* info, uint32_t flags) {
+// The alloc forms: zes_png_decode_alloc, and with `pix` zes_pngpix_alloc
+static int png_alloc_form(bool pix, const uint8_t* const* in, const uint64_t* in_len, uint32_t count, zes_alloc_fn alloc, void* user, uint64_t* out_len,
+                          int32_t* status, zes_png_info* info, uint32_t flags) {
   UseDev ud(route_host());
   if (const int arc = png_decode_args(in && in_len, out_len, status, count, flags)) return arc;
   if (!alloc) return ZES_E_ARG;
@@ -5802,7 +5882,7 @@ int zes_png_decode_alloc(const uint8_t* const* in, const uint64_t* in_len, uint3
     png_judge(m, i, out_len, status, info, &mine);
     if (status[i] != ZES_OK) continue;
     any = true;
-    size[i] = mine.out_size;
+    size[i] = pix ? png_pix_size(mine.width, mine.height) : mine.out_size;
   }
   if (!any) {
     call_none();
@@ -5810,14 +5890,32 @@ int zes_png_decode_alloc(const uint8_t* const* in, const uint64_t* in_len, uint3
   }
   LOCK_READY();
   HostBatch hb(g.gz_in, g.gz_acc);
+  std::vector<uint64_t> place(count, 0);
   for (uint32_t i = 0; i < count; i++)
     if (status[i] == ZES_OK) {
       im[i].src_at = hb.place(in[i], in_len[i]);
-      im[i].dst_off = hb.room(size[i]);
+      im[i].dst_off = place[i] = hb.room(size[i]);
     }
   if ((rc = hb.up())) return rc;
-  if ((rc = call_done(png_decode_core(hb.d_in(), im, hb.d_out(), status, flags), true))) return rc;
-  return hb.hand_out(count, alloc, user, status, out_len, [&](uint32_t i) { return size[i]; }, [&](uint32_t i) { return im[i].dst_off; });
+  if ((rc = call_done(pix ? pngpix_core(hb.d_in(), im, hb.d_out(), status, flags) : png_decode_core(hb.d_in(), im, hb.d_out(), status, flags), true))) return rc;
+  return hb.hand_out(count, alloc, user, status, out_len, [&](uint32_t i) { return size[i]; }, [&](uint32_t i) { return place[i]; });
+}
+
+int zes_png_decode_dev(const uint8_t* d_in, const uint64_t* in_off, const uint64_t* in_len, uint32_t count, uint8_t* d_out, const uint64_t* out_off,
+                       const uint64_t* out_cap, uint64_t* out_len, int32_t* status, zes_png_info* info, uint32_t flags) {
+  return png_dev_form(false, d_in, in_off, in_len, count, d_out, out_off, out_cap, out_len, status, info, flags);
+}
+int zes_png_decode_alloc(const uint8_t* const* in, const uint64_t* in_len, uint32_t count, zes_alloc_fn alloc, void* user, uint64_t* out_len,
+                         int32_t* status, zes_png_info* info, uint32_t flags) {
+  return png_alloc_form(false, in, in_len, count, alloc, user, out_len, status, info, flags);
+}
+int zes_pngpix_dev(const uint8_t* d_in, const uint64_t* in_off, const uint64_t* in_len, uint32_t count, uint8_t* d_out, const uint64_t* out_off,
+                   const uint64_t* out_cap, uint64_t* out_len, int32_t* status, zes_png_info* info, uint32_t flags) {
+  return png_dev_form(true, d_in, in_off, in_len, count, d_out, out_off, out_cap, out_len, status, info, flags);
+}
+int zes_pngpix_alloc(const uint8_t* const* in, const uint64_t* in_len, uint32_t count, zes_alloc_fn alloc, void* user, uint64_t* out_len,
+                     int32_t* status, zes_png_info* info, uint32_t flags) {
+  return png_alloc_form(true, in, in_len, count, alloc, user, out_len, status, info, flags);
 }
 
 // ---- PNG writer (include/zes.h: "zes_pngwrite*"): filters by k_png_filter, zlib bodies by EncGroup, files by k_png_pack ----
@@ -6110,6 +6208,47 @@ int zes_pngwrite(const uint8_t* const* in, const uint64_t* in_len, const zes_png
   rc = pngwrite_core(hb.d_in(), in_off.data(), img, aux, plan, count, hb.d_out(), out_off.data(), out_cap.data(), out_len, status, flags);
   if ((rc = call_done(rc, true))) return rc;
   return hb.hand_out(count, alloc, user, status, out_len, [&](uint32_t i) { return out_len[i]; }, [&](uint32_t i) { return out_off[i]; });
+}
+
+// zes_pngpix_expand_dev: k_png_expand alone, over scanlines in device memory that the writer's records describe.  The checks
+// are the writer's (pngwrite_args, with the filter field, which says nothing here, taken as 0); the job table and the aux
+// bytes go up in one copy and nothing comes back: every status is the host's.
+int zes_pngpix_expand_dev(const uint8_t* d_in, const uint64_t* in_off, const uint64_t* in_len, const zes_pngw_image* img, const uint8_t* aux, uint32_t count,
+                          uint8_t* d_out, const uint64_t* out_off, const uint64_t* out_cap, uint64_t* out_len, int32_t* status, uint32_t flags) {
+  ROUTE_DEV(d_in, d_out);
+  if (count && (!in_off || !out_off || !out_cap || !img)) return ZES_E_ARG;
+  std::vector<zes_pngw_image> plain(img, img + count);
+  for (zes_pngw_image& m : plain) m.filter = 0;
+  std::vector<PngwPlan> plan;
+  bool any = false;
+  if (const int arc = pngwrite_args([&](uint32_t) { return d_in != nullptr; }, in_len, plain.data(), aux, count, out_len, status, flags, plan, &any)) return arc;
+  std::vector<uint8_t> table, bytes;
+  uint64_t tiles = 0;
+  uint32_t njobs = 0;
+  for (uint32_t i = 0; i < count; i++) {
+    if (status[i] != ZES_OK) continue;
+    const zes_pngw_image& m = plain[i];
+    out_len[i] = png_pix_size(m.width, m.height);
+    if (!d_out || out_cap[i] < out_len[i]) {
+      status[i] = ZES_E_NOSPACE;
+      continue;
+    }
+    ZesPngxJob j = pngx_job(m.width, m.height, m.colour, m.depth, m.plte_len, m.trns_len, &tiles);
+    j.src_off = in_off[i], j.dst_off = out_off[i];
+    j.plte_off = bytes.size(), j.trns_off = bytes.size() + m.plte_len;
+    bytes.insert(bytes.end(), aux + plan[i].aux_off, aux + plan[i].aux_off + m.plte_len + m.trns_len);
+    table.insert(table.end(), (const uint8_t*)&j, (const uint8_t*)&j + sizeof j);
+    njobs++;
+  }
+  if (!njobs) {
+    call_none();
+    return ZES_OK;
+  }
+  table.insert(table.end(), bytes.begin(), bytes.end());
+  LOCK_READY();
+  g.carry.clear();
+  g.last_tier = 0;
+  return call_done(pngx_run(d_in, nullptr, d_out, table, njobs, tiles), true);
 }
 
 int zes_stage_lz77_dev(const uint8_t* d_in, uint64_t n, uint64_t start, uint32_t len, uint32_t* h_tokens, uint32_t* ntokens) {

@@ -250,6 +250,21 @@ struct ZesPngJob {
 };
 #define ZES_PNG_BAND 64u          // rows of a band: a lane each
 #define ZES_PNG_UNF_THREADS 256u  // four independent waves to a workgroup
+// k_png_expand (zes_png.hip): one image whose scanlines (no filter bytes) become 8-bit RGBA pixels.  Its rows are cut into
+// tiles of tile_rows, a workgroup each: the workgroups [first_tile, + ceil(height / tile_rows)) of the launch
+struct ZesPngxJob {   // 64 bytes
+  uint64_t src_off;   // the scanlines: height rows of rowbytes bytes, any alignment
+  uint64_t dst_off;   // where the width * height * 4 result bytes go, any alignment
+  uint64_t plte_off, trns_off;  // PLTE and tRNS data in the kernel's `aux` bytes, any alignment
+  uint32_t width, height, rowbytes, first_tile;
+  uint32_t tile_rows;
+  uint16_t plte_len;  // colour 3: bytes of PLTE data, at most 768
+  uint16_t trns_len;  // bytes of tRNS data that count: 2 (colour 0), 6 (colour 2), up to plte_len / 3 (colour 3), else 0
+  uint8_t depth, colour, pad[2];
+  uint32_t pad2;
+};
+#define ZES_PNGX_THREADS 256u
+#define ZES_PNGX_TILE_PIXELS 8192u  // about what a tile holds: 32 KiB of output a workgroup
 // k_png_filter (zes_pngw.hip): one image of a PNG writer's group.  Its rows are cut into runs of ZES_PNGW_RUN, a wave each:
 // the waves [first_unit, next record's first_unit) of the launch.  The table has a closing record behind the last image:
 // only its first_unit counts, the launch's waves
@@ -375,6 +390,7 @@ __global__ void k_zip_pack(const uint8_t*, const uint8_t*, const uint8_t*, uint8
 // PNG reader (zes_png.hip)
 __global__ void k_png_walk(const uint8_t*, const ZesPngFile*, uint32_t, ZesPngHead*, ZesPngChunk*);
 __global__ void k_png_unfilter(const uint8_t*, uint8_t*, const ZesPngJob*, uint32_t, uint32_t, uint32_t*);
+__global__ void k_png_expand(const uint8_t*, const uint8_t*, uint8_t*, const ZesPngxJob*, uint32_t);
 // PNG writer (zes_pngw.hip, zes_crc.hip)
 __global__ void k_png_filter(const uint8_t*, uint8_t*, const ZesPngwJob*, uint32_t);
 __global__ void k_png_pack(const uint8_t*, const uint8_t*, const uint8_t*, uint8_t*, const ZesPngwRec*, uint32_t);

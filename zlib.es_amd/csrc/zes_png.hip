@@ -22,6 +22,10 @@
 //                   scratch, padded on both sides, so a dword may reach over the row's ends.  It writes through a second
 //                   shift register: single bytes up to the output's first dword boundary, whole dwords from there, single
 //                   bytes for what is left at the row's end, so that no byte outside the row is written.
+//   k_png_expand    the scanlines of the batch turned into 8-bit RGBA pixels by the conversion rule of include/zes.h, in one
+//                   launch: a streaming kernel, a workgroup per (image, tile of rows), a lane four pixels a step — source
+//                   bytes fetched as aligned 16-byte groups and shifted into place, results stored as 16-byte groups from
+//                   the first 16-byte boundary of a row's output.  It stands at the end of this file.
 #include "../../include/zes.h"
 #include "zes_common.h"
 #include "zes_kernels.h"
@@ -282,4 +286,169 @@ __global__ __launch_bounds__(ZES_PNG_UNF_THREADS) void k_png_unfilter(const uint
     // it.  No other wave reads or writes these rows, so no wider scope is needed.
     __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
   }
+}
+
+// ---- k_png_expand: scanlines to 8-bit RGBA (include/zes.h: "The conversion rule") ----
+namespace {
+constexpr int pngx_channels(int colour) { return colour == 2 ? 3 : colour == 4 ? 2 : colour == 6 ? 4 : 1; }
+
+// The nb <= NB bytes at `a` (any alignment) as little-endian dwords w[0 .. ceil(NB / 4)): read as the aligned 16-byte groups
+// that hold them and nothing else, then moved down by a's place in its group — whole dwords by selection, the bytes left
+// by a funnel shift.  Bytes behind the nb are zeros or whatever stands in the last group read.
+template <int NB>
+__device__ __forceinline__ void pngx_load(const uint8_t* a, uint32_t nb, uint32_t (&w)[(NB + 3) / 4]) {
+  constexpr int NQ = (NB + 30) / 16, NW = (NB + 3) / 4;
+  const uint32_t off = (uint32_t)((uintptr_t)a & 15u);
+  const uint4* q = reinterpret_cast<const uint4*>(a - off);
+  uint32_t d[4 * NQ + 1];
+#pragma unroll
+  for (int k = 0; k < NQ; k++) {
+    uint4 v = make_uint4(0u, 0u, 0u, 0u);
+    if (16u * k < off + nb) v = q[k];
+    d[4 * k] = v.x, d[4 * k + 1] = v.y, d[4 * k + 2] = v.z, d[4 * k + 3] = v.w;
+  }
+  d[4 * NQ] = 0u;
+  const uint32_t dsh = off >> 2, bsh = 8u * (off & 3u);
+  uint32_t t[NW + 1];
+#pragma unroll
+  for (int k = 0; k <= NW; k++) t[k] = dsh == 0 ? d[k] : dsh == 1 ? d[k + 1] : dsh == 2 ? d[k + 2] : d[k + 3];
+#pragma unroll
+  for (int k = 0; k < NW; k++) w[k] = (uint32_t)((((uint64_t)t[k + 1] << 32) | t[k]) >> bsh);
+}
+
+template <int NW>
+__device__ __forceinline__ uint32_t pngx_byte(const uint32_t (&w)[NW], int i) { return (w[i >> 2] >> (8 * (i & 3))) & 255u; }
+
+// sample i (counted in samples from the window's first byte) of depth 8 or 16 at its full depth, and any sample as 8 bits
+template <int DEPTH, int NW>
+__device__ __forceinline__ uint32_t pngx_sample(const uint32_t (&w)[NW], int i) {
+  if (DEPTH == 16) return pngx_byte(w, 2 * i) << 8 | pngx_byte(w, 2 * i + 1);
+  return pngx_byte(w, i);
+}
+template <int DEPTH>
+__device__ __forceinline__ uint32_t pngx_to8(uint32_t s) {
+  return DEPTH == 1 ? s * 255u : DEPTH == 2 ? s * 85u : DEPTH == 4 ? s * 17u : DEPTH == 8 ? s : s >> 8;
+}
+
+// A tile: rows [r0, r1) of one image.  A row's pixels go in groups: the 1 to 4 pixels in front of the first 16-byte boundary
+// of the row's output are group 0, then four pixels a group.  So a whole group behind group 0 is one aligned 16-byte store;
+// group 0 and the row's last group store whole pixels (dwords).  An output that is not 4-byte aligned takes the slow path:
+// the same groups, every pixel stored as four single bytes.
+// A row has at most G groups (one fewer where its boundary falls late: the slot is then empty).  The tile's rows * G slots
+// are taken by the threads in order, ZES_PNGX_THREADS a step: consecutive lanes have consecutive groups of a row, a narrow
+// image keeps every lane busy, and a thread finds its next slot by two additions — the one division by G a tile is by a
+// value the workgroup shares.
+template <int COLOUR, int DEPTH>
+__device__ __forceinline__ void pngx_tile(const uint8_t* __restrict__ src, uint8_t* __restrict__ dst, const ZesPngxJob& j, uint32_t r0, uint32_t r1,
+                                          const uint32_t* pal, bool keyed, uint32_t k0, uint32_t k1, uint32_t k2) {
+  constexpr int CH = pngx_channels(COLOUR), BITS = CH * DEPTH;
+  constexpr int NB = BITS >= 8 ? BITS / 2 : BITS == 4 ? 3 : 2;  // bytes that four pixels touch at most
+  constexpr int NW = (NB + 3) / 4;
+  const uint32_t G = 1u + (j.width + 2u) / 4u, dr = ZES_PNGX_THREADS / G, dg = ZES_PNGX_THREADS % G;
+  const bool words = ((uintptr_t)dst & 3u) == 0;
+  uint32_t row = r0 + threadIdx.x / G, g = threadIdx.x % G;
+  for (; row < r1; g += dg, row += dr + (g >= G ? 1u : 0u), g -= (g >= G ? G : 0u)) {
+    const uint8_t* s = src + (uint64_t)row * j.rowbytes;
+    uint8_t* o = dst + (uint64_t)row * j.width * 4ull;
+    uint32_t first = 4u;
+    if (words) {
+      first = ((16u - (uint32_t)((uintptr_t)o & 15u)) & 15u) >> 2;
+      if (first == 0) first = 4u;
+    }
+    const uint32_t p0 = g ? first + 4u * (g - 1u) : 0u;
+    if (p0 < j.width) {
+      const uint32_t p1 = min(j.width, first + 4u * g), n = p1 - p0;
+      const uint64_t bit0 = (uint64_t)p0 * BITS, byte0 = bit0 >> 3;
+      uint32_t w[NW];
+      pngx_load<NB>(s + byte0, (uint32_t)((((uint64_t)p1 * BITS + 7u) >> 3) - byte0), w);
+      uint32_t px[4];
+#pragma unroll
+      for (int k = 0; k < 4; k++) {
+        uint32_t c[4];
+        if (BITS < 8) {  // one sample a pixel, the first one of a byte in its high bits
+          const uint32_t bit = (uint32_t)(bit0 & 7u) + k * DEPTH;
+          c[0] = (w[0] >> (8u * (bit >> 3) + 8u - DEPTH - (bit & 7u))) & ((1u << DEPTH) - 1u);
+        } else {
+#pragma unroll
+          for (int q = 0; q < CH; q++) c[q] = pngx_sample<DEPTH>(w, k * CH + q);
+        }
+        if (COLOUR == 3) {
+          px[k] = pal[c[0]];
+        } else if (COLOUR == 0) {
+          px[k] = pngx_to8<DEPTH>(c[0]) * 0x010101u | ((keyed && c[0] == k0) ? 0u : 0xFF000000u);
+        } else if (COLOUR == 2) {
+          px[k] = pngx_to8<DEPTH>(c[0]) | pngx_to8<DEPTH>(c[1]) << 8 | pngx_to8<DEPTH>(c[2]) << 16 |
+                  ((keyed && c[0] == k0 && c[1] == k1 && c[2] == k2) ? 0u : 0xFF000000u);
+        } else if (COLOUR == 4) {
+          px[k] = pngx_to8<DEPTH>(c[0]) * 0x010101u | pngx_to8<DEPTH>(c[1]) << 24;
+        } else {
+          px[k] = pngx_to8<DEPTH>(c[0]) | pngx_to8<DEPTH>(c[1]) << 8 | pngx_to8<DEPTH>(c[2]) << 16 | pngx_to8<DEPTH>(c[3]) << 24;
+        }
+      }
+      uint8_t* to = o + 4ull * p0;
+      if (n == 4u && words && ((uintptr_t)to & 15u) == 0) {
+        *reinterpret_cast<uint4*>(to) = make_uint4(px[0], px[1], px[2], px[3]);
+      } else if (words) {
+#pragma unroll
+        for (int k = 0; k < 4; k++)
+          if ((uint32_t)k < n) reinterpret_cast<uint32_t*>(to)[k] = px[k];
+      } else {
+#pragma unroll
+        for (int k = 0; k < 4; k++)
+          if ((uint32_t)k < n) {
+            to[4 * k] = (uint8_t)px[k], to[4 * k + 1] = (uint8_t)(px[k] >> 8);
+            to[4 * k + 2] = (uint8_t)(px[k] >> 16), to[4 * k + 3] = (uint8_t)(px[k] >> 24);
+          }
+      }
+    }
+  }
+}
+}  // namespace
+
+// A workgroup per (image, tile of rows); the tile's image by a binary search of the job table, as k_png_unfilter finds its
+// band.  Colour type 3: the workgroup first builds the 256-entry RGBA table in LDS from the PLTE and tRNS bytes (read one
+// by one: they lie at any byte of a file), entries behind the palette (0, 0, 0, 255); a pixel is then one LDS dword.
+// Colour types 0 and 2: the tRNS key, compared with the stored samples at their full depth.  `aux` holds PLTE and tRNS.
+__global__ __launch_bounds__(ZES_PNGX_THREADS) void k_png_expand(const uint8_t* __restrict__ lines, const uint8_t* __restrict__ aux, uint8_t* __restrict__ dst,
+                                                                const ZesPngxJob* __restrict__ jobs, uint32_t njobs) {
+  __shared__ uint32_t pal[256];
+  const uint32_t tile = blockIdx.x;
+  uint32_t lo = 0, hi = njobs;  // the last image whose first tile is not behind this one
+  while (hi - lo > 1) {
+    const uint32_t mid = (lo + hi) / 2;
+    if (jobs[mid].first_tile <= tile) lo = mid;
+    else hi = mid;
+  }
+  const ZesPngxJob j = jobs[lo];
+  const uint32_t r0 = (tile - j.first_tile) * j.tile_rows, r1 = min(j.height, r0 + j.tile_rows);  // (tile_rows * tiles < 2^32: the host's rule)
+  if (r0 >= j.height) return;
+  const uint8_t* src = lines + j.src_off;
+  uint8_t* out = dst + j.dst_off;
+  uint32_t k0 = 0, k1 = 0, k2 = 0;
+  bool keyed = false;
+  if (j.colour == 3) {
+    const uint8_t *P = aux + j.plte_off, *T = aux + j.trns_off;
+    const uint32_t i = threadIdx.x, entries = min((uint32_t)j.plte_len / 3u, 256u);
+    uint32_t e = 0xFF000000u;
+    if (i < entries) e = (uint32_t)P[3 * i] | (uint32_t)P[3 * i + 1] << 8 | (uint32_t)P[3 * i + 2] << 16 | (i < j.trns_len ? (uint32_t)T[i] : 255u) << 24;
+    pal[i] = e;
+    __syncthreads();
+  } else if (j.colour == 0 && j.trns_len == 2) {
+    const uint8_t* T = aux + j.trns_off;
+    keyed = true, k0 = (uint32_t)T[0] << 8 | T[1];
+  } else if (j.colour == 2 && j.trns_len == 6) {
+    const uint8_t* T = aux + j.trns_off;
+    keyed = true, k0 = (uint32_t)T[0] << 8 | T[1], k1 = (uint32_t)T[2] << 8 | T[3], k2 = (uint32_t)T[4] << 8 | T[5];
+  }
+#define PNGX_CASE(C, D) \
+  case (C) * 32 + (D): pngx_tile<C, D>(src, out, j, r0, r1, pal, keyed, k0, k1, k2); break;
+  switch (j.colour * 32u + j.depth) {
+    PNGX_CASE(0, 1) PNGX_CASE(0, 2) PNGX_CASE(0, 4) PNGX_CASE(0, 8) PNGX_CASE(0, 16)
+    PNGX_CASE(2, 8) PNGX_CASE(2, 16)
+    PNGX_CASE(3, 1) PNGX_CASE(3, 2) PNGX_CASE(3, 4) PNGX_CASE(3, 8)
+    PNGX_CASE(4, 8) PNGX_CASE(4, 16)
+    PNGX_CASE(6, 8) PNGX_CASE(6, 16)
+    default: break;  // (the host passes no other pair)
+  }
+#undef PNGX_CASE
 }

@@ -1032,7 +1032,7 @@ napi_value ZipRead(napi_env env, napi_callback_info info) {
   return j.rc == 0 ? batch_results(env, &j) : throw_status(env, j.rc);
 }
 
-// ---- PNG images (include/zes.h: zes_png_info_get, zes_png_decode_alloc) ----
+// ---- PNG images (include/zes.h: zes_png_info_get, zes_png_decode_alloc, zes_pngpix_alloc) ----
 // pngInfo(file): the file's zes_png_info record as 72 bytes; the façade makes the object.  The host form: no device is touched.
 napi_value PngInfo(napi_env env, napi_callback_info info) {
   const Args a = get_args(env, info);
@@ -1048,10 +1048,11 @@ napi_value PngInfo(napi_env env, napi_callback_info info) {
   return v;
 }
 
-// pngDecodeBatch(files): the files decoded as one batch: { results, info } — per file the scanlines as a fresh Uint8Array or
-// the Error that says why not, as the batch forms answer, and the files' zes_png_info records back to back
-napi_value PngDecodeBatch(napi_env env, napi_callback_info info) {
-  static const char SIG[] = "pngDecodeBatch(files)";
+// pngDecodeBatch(files) and pngPixelsBatch(files): the files decoded as one batch: { results, info } — per file the scanlines
+// (the pixels: width * height * 4 bytes of R, G, B, A) as a fresh Uint8Array or the Error that says why not, as the batch
+// forms answer, and the files' zes_png_info records back to back.  The two differ in the entry point alone
+using PngBatchFn = int (*)(const uint8_t* const*, const uint64_t*, uint32_t, zes_alloc_fn, void*, uint64_t*, int32_t*, zes_png_info*, uint32_t);
+napi_value png_batch(napi_env env, napi_callback_info info, const char* SIG, PngBatchFn fn) {
   const Args a = get_args(env, info);
   bool is_arr = false;
   uint32_t count = 0;
@@ -1066,7 +1067,7 @@ napi_value PngDecodeBatch(napi_env env, napi_callback_info info) {
     j.in_len[i] = n;
   }
   std::vector<zes_png_info> recs((size_t)count + 1);
-  j.rc = zes_png_decode_alloc(j.in.data(), j.in_len.data(), count, batch_alloc, &j, j.out_len.data(), j.status.data(), recs.data(), ZES_F_DEFAULT);
+  j.rc = fn(j.in.data(), j.in_len.data(), count, batch_alloc, &j, j.out_len.data(), j.status.data(), recs.data(), ZES_F_DEFAULT);
   if (j.rc) return throw_status(env, j.rc);
   void* raw = nullptr;
   napi_value res, vres = batch_results(env, &j), vinfo = new_u8(env, (size_t)count * sizeof(zes_png_info), &raw);
@@ -1077,6 +1078,8 @@ napi_value PngDecodeBatch(napi_env env, napi_callback_info info) {
   napi_set_named_property(env, res, "info", vinfo);
   return res;
 }
+napi_value PngDecodeBatch(napi_env env, napi_callback_info info) { return png_batch(env, info, "pngDecodeBatch(files)", zes_png_decode_alloc); }
+napi_value PngPixelsBatch(napi_env env, napi_callback_info info) { return png_batch(env, info, "pngPixelsBatch(files)", zes_pngpix_alloc); }
 
 // pngEncodeBatch(rows, records, aux): images written as PNG files in one batch (include/zes.h: zes_pngwrite) — rows[i] the
 // scanlines of image i, records its zes_pngw_image record (16 bytes each, back to back; the façade makes them) and aux every
@@ -1191,6 +1194,7 @@ napi_value ModuleInit(napi_env env, napi_value exports) {
       {"zip", swept<Zip>},
       {"pngInfo", swept<PngInfo>},
       {"pngDecodeBatch", swept<PngDecodeBatch>},
+      {"pngPixelsBatch", swept<PngPixelsBatch>},
       {"pngEncodeBatch", swept<PngEncodeBatch>},
       {"lastGunzipMembers", swept<LastGunzipMembers>},
       {"init", swept<Init>},

@@ -229,6 +229,26 @@ export function pngDecode(file: Uint8Array): PngImage {
 }
 
 /**
+ * Extra (not in the reference API): PNG images as pixels.  `pngPixelsBatch` decodes files as `pngDecodeBatch` does and goes
+ * one step further on the device: one more launch turns every image's scanlines into `width * height * 4` bytes of R, G, B,
+ * A, row by row from the top — samples below 8 bits scaled to 0..255, 16-bit samples cut to their high byte, grey
+ * replicated, palette indices looked up (an index beyond the palette is opaque black), tRNS applied as alpha (a tRNS whose
+ * length does not fit the colour type is ignored).  Element i of the result is `{ info, data }` — `info` as `pngInfo` gives
+ * it, `data` the pixels — or the `Error` that says why not.  No gamma, no colour management, no interlaced files.
+ * `pngPixels` is the batch of one file and throws its Error.
+ */
+export function pngPixelsBatch(files: Uint8Array[]): PngResult[] {
+  const got = addon.pngPixelsBatch(files);
+  return got.results.map((r, i) => (r instanceof Error ? r : { info: pngInfoAt(got.info, 72 * i), data: r }));
+}
+
+export function pngPixels(file: Uint8Array): PngImage {
+  const got = pngPixelsBatch([file])[0];
+  if (got instanceof Error) throw got;
+  return got;
+}
+
+/**
  * Extra (not in the reference API): PNG images, writing.  `pngEncodeBatch` writes images as PNG files in one batch on the
  * device: one launch chooses and applies the scanline filters of every row of every image, one batch encode makes the zlib
  * streams, one launch lays the files out and two more make the chunk CRCs.  An image is `{ data, width, height, colourType,
