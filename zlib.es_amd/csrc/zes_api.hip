@@ -1006,11 +1006,16 @@ int deflate_batch_core(const uint8_t* d_in, const uint64_t* in_off, const uint64
     // (the results go straight into the page-locked read-back area when they fit it: no copy command behind the kernels)
     hipLaunchKernelGGL(k_layout, dim3(nbuf), dim3(256), 0, g.stream, d_out, dbufs, dblks, adler, res_direct ? res_direct : (ZesRes*)g.res.p);
   }
+  if (sort_dbg && (rc = phases_arm(zes_emit_set_dbg, nblk))) return rc;
   {
     Timed t("k_emit");
     hipLaunchKernelGGL(k_emit, dim3(nblk), dim3(EMIT_THREADS), 0, g.stream, d_out, dbufs, dblks, (uint32_t*)g.idx_a.p,
                        (const uint32_t*)g.codes.p, (const uint32_t*)g.hdrs.p);
   }
+  // (this kernel's stamps 2 .. 6 are no clocks but the first wave's cycles in each step, summed over the block's tiles)
+  if (sort_dbg && (rc = phases_print(zes_emit_set_dbg, nblk, 1,
+                                     "zes emit steps (avg cycles over %u blocks, first wave): whole %.0f = header copy %.0f build %.0f scan %.0f stage %.0f flush %.0f\n")))
+    return rc;
   HIPCHK(hipGetLastError());
   ZesRes* r = g.pinned->def.res;
   if (nbuf > DEFLATE_DIRECT_BUFS) {

@@ -3216,21 +3216,32 @@ __global__ __launch_bounds__(256) void k_layout(uint8_t* __restrict__ d_out, con
 }
 
 // ------------------------------------------------------------------------------------------
-// k_emit: one workgroup per block.  Items (3 block bits, header words, tokens, EOB) get their
-// bit offsets from a workgroup scan; bits are OR-ed into an LDS staging window and leave as
-// whole dwords.  Only the first and last dword of a block (shared with its neighbours) use
-// global atomics.
+// k_emit: one workgroup per block.  The three block bits and the header bits are a shifted copy
+// of k_huff's header words; the tokens and EOB get their bit offsets from a workgroup scan, a
+// tile of 8192 at a time; bits are OR-ed into an LDS staging window and leave as whole dwords.
+// Only the first and last dword of a block (shared with its neighbours) use global atomics.
+//
+// A wave owns a contiguous run of 512 tokens of the tile, a lane two groups of four in it, 256
+// tokens apart: each group is one aligned 16-byte load, a load instruction of the wave 1 KiB.
+// A group in which no lane of the wave holds a match (and none lies behind the block's last
+// token) is packed before the scan into one piece of at most 60 bits with 32-bit arithmetic.
+// The other groups are built item by item, the match computation of a slot only in a wave that
+// holds a match there, its table entries read from LDS; where every lane's four items fit 64
+// bits they become one piece as well, else they are packed into 64-bit pieces behind the scan.
+// The staging window is zero whenever a tile begins (word 0: the bits carried over): the flush
+// clears each word it takes, so a tile costs two barriers.
 // ------------------------------------------------------------------------------------------
-#ifndef EMIT_ITEMS
-#define EMIT_ITEMS 4  // tokens per thread per tile (a multiple of 4: 16-byte loads)
-#endif
-#define EMIT_TILE (EMIT_THREADS * EMIT_ITEMS)
-#define EMIT_STAGE_WORDS (EMIT_TILE * 48 / 32 + 8)
+#define EMIT_GROUPS 2                              // groups of four tokens per thread per tile
+#define EMIT_WAVE_RUN (64 * 4 * EMIT_GROUPS)       // W: tokens of a tile that one wave owns (tests/_emit_cases.py: EMIT_WAVE_RUN)
+#define EMIT_TILE (EMIT_THREADS * 4 * EMIT_GROUPS) // T: tokens per tile (tests/_emit_cases.py: EMIT_TILE)
+#define EMIT_STAGE_WORDS (EMIT_TILE * 48 / 32 + 8) // an item has at most 48 bits; + the carried dword, rounded up to 16 bytes
+static_assert(EMIT_STAGE_WORDS % 4 == 0, "the window is cleared 16 bytes at a time");
+#define EMIT_LEN_TAB 320   // behind the block's 320 codes: kLenBase | kLenXbits << 16, then kDistBase | kDistXbits << 16,
+#define EMIT_DIST_TAB 349  // so that a match reads its four table entries from LDS, two words, and waits for no global load
 struct EmitSmem {
-  uint32_t codes[320];
-  uint32_t stage[EMIT_STAGE_WORDS];
+  uint32_t codes[320 + 29 + 30];
+  alignas(16) uint32_t stage[EMIT_STAGE_WORDS];
   uint32_t wsum[EMIT_THREADS / 64];
-  uint32_t carry;
 };
 
 __device__ static inline void stage_or(uint32_t* stage, uint32_t rel_bit, uint64_t v, uint32_t nbits) {
@@ -3245,156 +3256,248 @@ __device__ static inline void stage_or(uint32_t* stage, uint32_t rel_bit, uint64
 // (vmcnt(0)), which here would hold each tile until its flush stores and the next tile's token loads have landed.
 __device__ __forceinline__ static void emit_lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
+// ZES_DEBUG_PHASES: [g][8] = clock at entry, clock at exit, then the first wave's cycles in each step summed over the
+// block's tiles (header copy, build, scan, stage, flush).  The sums are wave-uniform: they live in scalar registers.
+__device__ unsigned long long* g_emit_dbg = nullptr;
+void zes_emit_set_dbg(unsigned long long* p) { (void)hipMemcpyToSymbol(HIP_SYMBOL(g_emit_dbg), &p, sizeof p); }
+#define EMIT_STAMP(i)                                        \
+  do {                                                       \
+    if (stamped) {                                           \
+      const unsigned long long now_ = (unsigned long long)clock64(); \
+      st_acc[i] += now_ - st_last;                           \
+      st_last = now_;                                        \
+    }                                                        \
+  } while (0)
+
+// inclusive add scans by DPP (as wave_scan_add of zes_inflate.hip): over the rows of 16 lanes, and over the 64 lanes
+template <int CTRL, int ROWS>
+__device__ __forceinline__ static uint32_t emit_dpp(uint32_t x) {
+  return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, CTRL, ROWS, 0xf, false);
+}
+__device__ __forceinline__ static uint32_t emit_row_scan(uint32_t x) {
+  x += emit_dpp<0x111, 0xf>(x);
+  x += emit_dpp<0x112, 0xf>(x);
+  x += emit_dpp<0x114, 0xf>(x);
+  x += emit_dpp<0x118, 0xf>(x);
+  return x;
+}
+__device__ __forceinline__ static uint32_t emit_wave_scan(uint32_t x) {
+  x = emit_row_scan(x);
+  x += emit_dpp<0x142, 0xa>(x);  // row_bcast:15 into rows 1 and 3
+  x += emit_dpp<0x143, 0xc>(x);  // row_bcast:31 into rows 2 and 3
+  return x;
+}
+__device__ __forceinline__ static uint32_t emit_readlane(uint32_t x, uint32_t l) { return (uint32_t)__builtin_amdgcn_readlane((int)x, (int)l); }
+
+// The four items of a lane's group at tokens ti0 .. ti0 + 3, as (value, bits), the bit counts a byte each in nbp.  The
+// match computation of a slot runs only in a wave that holds a match there.  TAIL: the group may reach the block's
+// last token: EOB (src/deflate.ts:222-226) is the item behind it, and nothing comes behind EOB.
+template <bool TAIL>
+__device__ __forceinline__ static void emit_items(const uint32_t* codes, const uint32_t (&tv)[4], uint32_t ti0, uint32_t ntok, uint64_t (&val)[4],
+                                                  uint32_t& nbp, uint32_t& sum) {
+#pragma unroll
+  for (int k = 0; k < 4; k++) {
+    uint32_t t = tv[k];
+    if (TAIL && ti0 + k >= ntok) t = 256u;
+    const bool m = (t & ZES_TOK_MATCH) != 0u;
+    const uint32_t c = codes[m ? 256u : t];  // literal (src/deflate.ts:212-219) or EOB
+    uint64_t v = c & 0xffffu;
+    uint32_t b = c >> 16;
+    if (__ballot(m) != 0ull) {
+      if (m) {  // src/deflate.ts:187-211
+        const uint32_t len = zes_tok_len(t), dist = zes_tok_dist(t);
+        const uint32_t lc = zes_len_code(len), dc = zes_dist_code(dist);
+        const uint32_t cl = codes[257 + lc], cd = codes[288 + dc];
+        const uint32_t tl = codes[EMIT_LEN_TAB + lc], td = codes[EMIT_DIST_TAB + dc];  // base | extra bits << 16
+        const uint32_t ll = cl >> 16, dl = cd >> 16;
+        v = (uint64_t)(cl & 0xffffu);
+        b = ll;
+        v |= (uint64_t)(len - (tl & 0xffffu)) << b;
+        b += tl >> 16;
+        v |= (uint64_t)(cd & 0xffffu) << b;
+        b += dl;
+        v |= (uint64_t)(dist - (td & 0xffffu)) << b;
+        b += td >> 16;
+      }
+    }
+    if (TAIL && ti0 + k > ntok) {
+      v = 0;
+      b = 0;
+    }
+    val[k] = v;
+    nbp |= b << (8 * k);
+    sum += b;
+  }
+}
+
 __global__ __launch_bounds__(EMIT_THREADS, 8) void k_emit(uint8_t* __restrict__ d_out, const ZesBuf* __restrict__ bufs,
                                                        const ZesBlk* __restrict__ blks, const uint32_t* __restrict__ tok_in,
                                                        const uint32_t* __restrict__ codes_in, const uint32_t* __restrict__ hdr_in) {
   __shared__ EmitSmem S;
-  const uint32_t g = blockIdx.x, tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+  const uint32_t g = blockIdx.x, tid = threadIdx.x, lane = tid & 63u;
+  const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(tid >> 6));  // (uniform: a scalar register)
   const ZesBlk bk = blks[g];
   const ZesBuf bf = bufs[bk.buf];
   uint32_t* out32 = reinterpret_cast<uint32_t*>(d_out + bf.out_off);
   const uint32_t* tk = tok_in + (uint64_t)g * ZES_BLK;
   const uint32_t* hd = hdr_in + (uint64_t)g * ZES_HDR_WORDS;
+  unsigned long long* const dbg = g_emit_dbg;
+  const bool stamped = dbg != nullptr && wave == 0;
+  unsigned long long st_acc[5] = {0, 0, 0, 0, 0}, st_first = stamped ? (unsigned long long)clock64() : 0ull, st_last = st_first;
+  // the first tile's tokens: on their way during the header copy (the loads of a tile are issued unconditionally, a
+  // tile ahead, and the barriers below do not wait for them; behind the block's list they are clamped into it)
+  static_assert(EMIT_TILE <= ZES_BLK, "the first tile lies inside the block's token list");
+  const uint32_t run0 = wave * EMIT_WAVE_RUN + lane * 4u;  // my first group in a tile; group h lies 256 * h tokens on
+  uint4 pre[EMIT_GROUPS];
+#pragma unroll
+  for (int h = 0; h < EMIT_GROUPS; h++) pre[h] = *reinterpret_cast<const uint4*>(tk + run0 + 256u * h);
   for (uint32_t i = tid; i < 320; i += EMIT_THREADS) S.codes[i] = codes_in[(uint64_t)g * 320 + i];
-  if (tid == 0) S.carry = 0;
+  if (tid >= 512u && tid < 512u + 29u) S.codes[EMIT_LEN_TAB + tid - 512u] = kLenBase[tid - 512u] | ((uint32_t)kLenXbits[tid - 512u] << 16);
+  if (tid >= 576u && tid < 576u + 30u) S.codes[EMIT_DIST_TAB + tid - 576u] = kDistBase[tid - 576u] | ((uint32_t)kDistXbits[tid - 576u] << 16);
+  for (uint32_t i = tid; i < EMIT_STAGE_WORDS / 4; i += EMIT_THREADS) reinterpret_cast<uint4*>(S.stage)[i] = make_uint4(0, 0, 0, 0);
   const uint64_t blk_first_dw = bk.bit_off >> 5;
   const uint64_t blk_last_dw = (bk.bit_off + bk.bits - 1) >> 5;
   const bool is_final = (bk.blk + 1 == bf.nblk) && !(bf.flags & ZES_BUF_NOTFINAL);
-  const uint32_t nhdr_items = 1 + ((bk.hdr_bits + 31u) >> 5);  // block bits + header words
-  // item space: the first tile holds only the header items, token i is item EMIT_TILE + i, so that a
-  // thread's four tokens are one aligned 16-byte load (issued unconditionally: no wait under a branch)
-  const uint32_t nitems = EMIT_TILE + bk.ntok + 1;             // + EOB
-  static_assert(1 + ZES_HDR_WORDS <= EMIT_TILE, "header items fit the first tile");
-  uint64_t cur_bit = bk.bit_off;                               // uniform
+  const uint32_t ntok = bk.ntok;
   __syncthreads();
 
-  // tokens of the tile in hand (the first tile holds header items only; tile 1 starts at token 0)
-  uint4 pre[EMIT_ITEMS / 4];
-#pragma unroll
-  for (int k4 = 0; k4 < EMIT_ITEMS / 4; k4++) pre[k4] = make_uint4(0, 0, 0, 0);
-  for (uint32_t t0 = 0; t0 < nitems; t0 += EMIT_TILE) {
-    // 1. each thread builds its (value, nbits) items
-    uint64_t val[EMIT_ITEMS];
-    uint32_t nb[EMIT_ITEMS];
-    uint32_t mysum = 0;
-    uint32_t tv4[EMIT_ITEMS];
-#pragma unroll
-    for (int k4 = 0; k4 < EMIT_ITEMS / 4; k4++) {
-      tv4[4 * k4 + 0] = pre[k4].x;
-      tv4[4 * k4 + 1] = pre[k4].y;
-      tv4[4 * k4 + 2] = pre[k4].z;
-      tv4[4 * k4 + 3] = pre[k4].w;
+  // 0. BFINAL + BTYPE=2 (src/deflate.ts:21-28) and the header bits: k_huff's words shifted by three bits and by the
+  // block's position inside its first dword, one output dword a thread; the trailing partial dword is carried into
+  // the first tile through word 0 of the window
+  {
+    const uint32_t head = (uint32_t)(bk.bit_off & 31u), hb = bk.hdr_bits, nhw = (hb + 31u) >> 5;
+    const uint32_t nout = (head + 3u + hb + 31u) >> 5, nfull = (head + 3u + hb) >> 5;
+    auto hword = [&](uint32_t i) -> uint32_t {  // header word i without what lies behind hdr_bits; 0 outside (i = -1 too)
+      if (i >= nhw) return 0u;
+      uint32_t w = hd[i];
+      if (i == nhw - 1u && (hb & 31u)) w &= (1u << (hb & 31u)) - 1u;
+      return w;
+    };
+    auto cword = [&](uint32_t i) -> uint32_t {  // dword i of: three block bits, then the header bits
+      uint32_t w = (hword(i) << 3) | (hword(i - 1u) >> 29);
+      if (i == 0) w |= (is_final ? 1u : 0u) | (2u << 1);
+      return w;
+    };
+    for (uint32_t j = tid; j < nout; j += EMIT_THREADS) {
+      const uint32_t c1 = cword(j), c0 = cword(j - 1u);
+      const uint32_t w = head ? (c1 << head) | (c0 >> (32u - head)) : c1;
+      if (j < nfull) {
+        const uint64_t gw = blk_first_dw + j;
+        if (gw == blk_first_dw || gw == blk_last_dw) atomicOr(&out32[gw], w);
+        else out32[gw] = w;
+      } else {
+        S.stage[0] = w;
+      }
     }
-    {  // the next tile's tokens: on their way while this tile is worked on (the barriers below do not wait for them)
-      const uint32_t ti0 = t0 + tid * EMIT_ITEMS;  // first token of this thread in tile t0 + EMIT_TILE
-      const uint4* qp = reinterpret_cast<const uint4*>(tk + min(ti0, ZES_BLK - EMIT_ITEMS));
+  }
+  uint64_t cur_bit = bk.bit_off + 3u + bk.hdr_bits;  // uniform
+  EMIT_STAMP(0);
+
+  // tokens 0 .. ntok - 1 and EOB as item ntok
+  for (uint32_t t0 = 0; t0 <= ntok; t0 += EMIT_TILE) {
+    uint4 q[EMIT_GROUPS];
 #pragma unroll
-      for (int k4 = 0; k4 < EMIT_ITEMS / 4; k4++) pre[k4] = qp[k4];
-    }
+    for (int h = 0; h < EMIT_GROUPS; h++) q[h] = pre[h];
 #pragma unroll
-    for (int k = 0; k < EMIT_ITEMS; k++) {
-      const uint32_t it = t0 + tid * EMIT_ITEMS + k;
-      uint64_t v = 0;
-      uint32_t b = 0;
-      if (it < EMIT_TILE) {
-        if (it == 0) {  // BFINAL + BTYPE=2 (src/deflate.ts:21-28)
-          v = (is_final ? 1u : 0u) | (2u << 1);
-          b = 3;
-        } else if (it < nhdr_items) {
-          const uint32_t wi = it - 1;
-          v = hd[wi];
-          b = min(32u, bk.hdr_bits - wi * 32u);
-        }
-      } else if (it < nitems) {
-        if (it == nitems - 1) {  // EOB (src/deflate.ts:222-226)
-          const uint32_t c = S.codes[256];
-          v = c & 0xffffu;
-          b = c >> 16;
-        } else {
-          const uint32_t tv = tv4[k];
-          if (tv & ZES_TOK_MATCH) {  // src/deflate.ts:187-211
-            const uint32_t len = zes_tok_len(tv), dist = zes_tok_dist(tv);
-            const uint32_t lc = zes_len_code(len), dc = zes_dist_code(dist);
-            const uint32_t cl = S.codes[257 + lc], cd = S.codes[288 + dc];
-            const uint32_t ll = cl >> 16, dl = cd >> 16;
-            const uint32_t lx = kLenXbits[lc], dx = kDistXbits[dc];
-            v = (uint64_t)(cl & 0xffffu);
-            b = ll;
-            v |= (uint64_t)(len - kLenBase[lc]) << b;
-            b += lx;
-            v |= (uint64_t)(cd & 0xffffu) << b;
-            b += dl;
-            v |= (uint64_t)(dist - kDistBase[dc]) << b;
-            b += dx;
-          } else {  // literal (src/deflate.ts:212-219)
-            const uint32_t c = S.codes[tv];
-            v = c & 0xffffu;
-            b = c >> 16;
+    for (int h = 0; h < EMIT_GROUPS; h++)
+      pre[h] = *reinterpret_cast<const uint4*>(tk + min(t0 + EMIT_TILE + run0 + 256u * h, ZES_BLK - 4u));
+    // 1. each group becomes one piece (literals only) or four (value, nbits) items; nbp: the bit counts, a byte each
+    uint64_t val[EMIT_GROUPS][4];
+    uint32_t nbp[EMIT_GROUPS], sum[EMIT_GROUPS];
+    bool one[EMIT_GROUPS];  // (uniform) every lane's group is a single piece in val[h][0], nbp[h] its bit count
+#pragma unroll
+    for (int h = 0; h < EMIT_GROUPS; h++) {
+      const uint32_t ws = t0 + wave * EMIT_WAVE_RUN + 256u * h;  // the wave's first token of this group (uniform)
+      const uint32_t tv[4] = {q[h].x, q[h].y, q[h].z, q[h].w};
+      const bool full = ws + 256u <= ntok;  // all of the wave's 256 are tokens of the block
+      one[h] = full && __ballot(((tv[0] | tv[1] | tv[2] | tv[3]) & ZES_TOK_MATCH) != 0u) == 0ull;
+      val[h][1] = val[h][2] = val[h][3] = 0;
+      if (one[h]) {  // four literals (src/deflate.ts:212-219): two pairs of at most 30 bits, then one 64-bit shift
+        const uint32_t c0 = S.codes[tv[0]], c1 = S.codes[tv[1]], c2 = S.codes[tv[2]], c3 = S.codes[tv[3]];
+        const uint32_t p01 = (c0 & 0xffffu) | ((c1 & 0xffffu) << (c0 >> 16)), n01 = (c0 >> 16) + (c1 >> 16);
+        const uint32_t p23 = (c2 & 0xffffu) | ((c3 & 0xffffu) << (c2 >> 16)), n23 = (c2 >> 16) + (c3 >> 16);
+        val[h][0] = (uint64_t)p01 | ((uint64_t)p23 << n01);
+        sum[h] = nbp[h] = n01 + n23;
+      } else {
+        val[h][0] = 0;
+        sum[h] = nbp[h] = 0;
+        if (ws <= ntok) {  // (a group wholly behind EOB has nothing)
+          if (full) emit_items<false>(S.codes, tv, ws + lane * 4u, ntok, val[h], nbp[h], sum[h]);
+          else emit_items<true>(S.codes, tv, ws + lane * 4u, ntok, val[h], nbp[h], sum[h]);
+          if (__ballot(sum[h] > 64u) == 0ull) {  // three literals and a common match: one piece in every lane after all
+            const uint32_t n0 = nbp[h] & 0xffu, n1 = n0 + ((nbp[h] >> 8) & 0xffu), n2 = n1 + ((nbp[h] >> 16) & 0xffu);
+            val[h][0] |= (val[h][1] << (n0 & 63u)) | (val[h][2] << (n1 & 63u)) | (val[h][3] << (n2 & 63u));  // (an item without bits is 0)
+            nbp[h] = sum[h];
+            one[h] = true;
           }
         }
       }
-      val[k] = v;
-      nb[k] = b;
-      mysum += b;
     }
-    // 2. workgroup exclusive scan of mysum
-    uint32_t incl = mysum;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-      const uint32_t t = __shfl_up(incl, d);
-      if ((int)lane >= d) incl += t;
-    }
-    if (lane == 63) S.wsum[wave] = incl;
-    emit_lds_barrier();  // also: previous tile's flush finished reading stage/carry
-    uint32_t wbase = 0, tile_bits = 0;
-#pragma unroll
-    for (uint32_t w = 0; w < EMIT_THREADS / 64; w++) {
-      const uint32_t s = S.wsum[w];
-      if (w < wave) wbase += s;
-      tile_bits += s;
-    }
-    uint32_t rel = wbase + incl - mysum;  // bit offset of my first item inside the tile
-    // 3. zero the staging window, seed it with the carried partial dword
+    EMIT_STAMP(1);
+    // 2. exclusive scan over the workgroup.  A lane's two sums (at most 192 each, 12288 over a wave) share one word for
+    // the wave scan; the sixteen wave totals are scanned by every wave inside one row of lanes.
+    static_assert(EMIT_GROUPS == 2, "two 16-bit sums a word");
+    const uint32_t incl = emit_wave_scan(sum[0] | (sum[1] << 16));
+    const uint32_t tot = emit_readlane(incl, 63), tot0 = tot & 0xffffu;
+    if (lane == 0) S.wsum[wave] = tot0 + (tot >> 16);
+    emit_lds_barrier();  // also: the previous tile's flush has taken and cleared its words
+    const uint32_t wtot = S.wsum[lane & 15u];
+    const uint32_t wincl = emit_row_scan(wtot);
+    const uint32_t tile_bits = emit_readlane(wincl, 15), wbase = emit_readlane(wincl - wtot, wave);
     const uint32_t head = (uint32_t)(cur_bit & 31u);
-    const uint32_t nwords = (head + tile_bits + 31u) >> 5;
-    for (uint32_t i = tid; i < nwords + 1; i += EMIT_THREADS) S.stage[i] = (i == 0) ? S.carry : 0u;
-    emit_lds_barrier();
-    // 4. OR the items in.  A thread's items are consecutive in the stream: they are gathered into 64-bit pieces first
-    // (seven 9-bit literals make one), so that the staging window sees two or three LDS atomics per piece instead of
-    // one or two per item — the atomics, with their bank conflicts, are what this step costs.
-    rel += head;
-    {
-      uint64_t acc = 0;
-      uint32_t accn = 0, accpos = rel;
+    const uint32_t rel[EMIT_GROUPS] = {head + wbase + (incl & 0xffffu) - sum[0], head + wbase + tot0 + (incl >> 16) - sum[1]};
+    EMIT_STAMP(2);
+    // 3. OR the pieces in.  The items of a group are consecutive in the stream: they are gathered into 64-bit pieces
+    // first, so that the window sees two or three LDS atomics per piece instead of one or two per item.
 #pragma unroll
-      for (int k = 0; k < EMIT_ITEMS; k++) {
-        if (accn + nb[k] > 64u) {
-          stage_or(S.stage, accpos, acc, accn);
-          accpos += accn;
-          acc = 0;
-          accn = 0;
+    for (int h = 0; h < EMIT_GROUPS; h++) {
+      if (one[h]) {
+        stage_or(S.stage, rel[h], val[h][0], nbp[h]);  // (a lane behind EOB ORs nothing into a word of the window)
+      } else if (nbp[h]) {
+        uint64_t acc = 0;
+        uint32_t accn = 0, accpos = rel[h];
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+          const uint32_t nb = (nbp[h] >> (8 * k)) & 0xffu;
+          if (accn + nb > 64u) {
+            stage_or(S.stage, accpos, acc, accn);
+            accpos += accn;
+            acc = 0;
+            accn = 0;
+          }
+          acc |= val[h][k] << accn;  // (an item has at most 48 bits; accn + nb <= 64 here)
+          accn += nb;
         }
-        acc |= val[k] << accn;  // (an item has at most 48 bits; accn + nb[k] <= 64 here)
-        accn += nb[k];
+        if (accn) stage_or(S.stage, accpos, acc, accn);
       }
-      if (accn) stage_or(S.stage, accpos, acc, accn);
     }
     emit_lds_barrier();
-    // 5. flush complete dwords; the trailing partial dword is carried into the next tile
+    EMIT_STAMP(3);
+    // 4. flush complete dwords, each cleared behind its read; the trailing partial dword moves to word 0 for the next tile
     const uint64_t first_dw = cur_bit >> 5;
     const uint32_t end_bits = head + tile_bits;
-    const bool last_tile = (t0 + EMIT_TILE >= nitems);
-    const uint32_t ncomplete = last_tile ? nwords : (end_bits >> 5);
+    const bool last_tile = t0 + EMIT_TILE > ntok;
+    const uint32_t ncomplete = last_tile ? (end_bits + 31u) >> 5 : end_bits >> 5;
     for (uint32_t i = tid; i < ncomplete; i += EMIT_THREADS) {
       const uint64_t gw = first_dw + i;
       const uint32_t w = S.stage[i];
+      S.stage[i] = 0;
       if (gw == blk_first_dw || gw == blk_last_dw) atomicOr(&out32[gw], w);
       else out32[gw] = w;
     }
-    const uint32_t carry_next = (!last_tile && (end_bits & 31u)) ? S.stage[end_bits >> 5] : 0u;
-    emit_lds_barrier();
-    if (tid == 0) S.carry = carry_next;
+    if (tid == 0 && !last_tile && ncomplete) {  // (behind this thread's own clearing of word 0; nobody else touches these two)
+      const uint32_t c = S.stage[ncomplete];
+      S.stage[ncomplete] = 0;
+      S.stage[0] = c;
+    }
     cur_bit += tile_bits;
+    EMIT_STAMP(4);
+  }
+  if (stamped && tid == 0) {
+    unsigned long long* d = dbg + (size_t)g * 8;
+    d[0] = st_first;
+    d[1] = (unsigned long long)clock64();
+    for (int i = 0; i < 5; i++) d[2 + i] = st_acc[i];
   }
 }
 
