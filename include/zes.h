@@ -47,7 +47,7 @@ typedef enum zes_status {
   ZES_E_UNSUPPORTED = -23,  /* zes_zip_*: a valid archive or entry that uses something this reader does not implement: ZIP64, several
                                disks, encryption, a method other than 0 (stored) or 8 (DEFLATE); zes_png_*: a valid file with a
                                critical chunk this reader does not know, filtered data of more than 0xFFFFFFFF bytes, or (the
-                               decode calls) Adam7 interlace */
+                               decode calls without ZES_F_PNG_INTERLACED) Adam7 interlace */
   ZES_E_PNG = -24           /* zes_png_*: not a PNG file this reader accepts, or image data that does not fit its header */
 } zes_status;
 
@@ -80,6 +80,9 @@ typedef enum zes_status {
                                   testing aid, same results */
 #define ZES_F_INDEX_WALK 64u    /* zes_bgzf_index_dev: find the members with k_gz_walk's serial chain instead of the
                                   parallel finder: testing aid and the baseline of the measurement; same results */
+#define ZES_F_PNG_INTERLACED 128u /* zes_png_decode_dev, zes_png_decode_alloc, zes_pngpix_dev, zes_pngpix_alloc: decode files of
+                                  interlace method 1 (Adam7) too, instead of answering ZES_E_UNSUPPORTED for them ("Interlaced
+                                  images" below).  Files of interlace method 0 decode as without the flag */
 #define ZES_F_LOOSE_CANDIDATES 2u /* block-start search without the reference's run-length-coding rules: more false
                                   * candidates reach the block decoder (testing aid for that path; same results) */
 
@@ -438,7 +441,7 @@ int zes_zipwrite(const uint8_t* const* in, const uint64_t* in_len, const uint8_t
 
 /* PNG images (PNG specification, second edition): the header of a file, and batch decoding of files to their scanlines.
  * The reader undoes the container, the zlib stream and the scanline filters and nothing else: samples stay as stored (16-bit
- * big-endian, sub-byte samples packed, palette indices as indices).  No Adam7 interlace, no APNG.  The writer, zes_pngwrite* below, is the same in reverse.
+ * big-endian, sub-byte samples packed, palette indices as indices).  Adam7 interlace is refused without ZES_F_PNG_INTERLACED ("Interlaced images" below); no APNG.  The writer, zes_pngwrite* below, is the same in reverse.
  *
  * zes_png_info: what a decode call works from.  All values are little-endian host values; pad fields are 0.
  * The file rule.  A file in[0, c) is judged chunk by chunk from byte 8; the first failure in file order decides:
@@ -456,7 +459,7 @@ int zes_zipwrite(const uint8_t* const* in, const uint64_t* in_len, const uint8_t
  *   size        behind a sound chain: the filtered size F = height * (1 + rowbytes) > 0xFFFFFFFF is ZES_E_UNSUPPORTED
  * zes_png_info_get applies the rule to the caller's memory on the host and touches no device, so it checks no CRC.  It
  * answers ZES_OK for an interlaced file and reports the method (as zes_zip_index lists entries it cannot extract); the
- * decode calls answer ZES_E_UNSUPPORTED for one.  With a status the record is all zeros.  ZES_E_ARG: a null info, a null in
+ * decode calls answer ZES_E_UNSUPPORTED for one unless ZES_F_PNG_INTERLACED is set.  With a status the record is all zeros.  ZES_E_ARG: a null info, a null in
  * with c != 0, any flag bit.
  * replaces: nothing (the reference has no PNG container) */
 typedef struct zes_png_info {   /* 72 bytes */
@@ -481,11 +484,11 @@ int zes_png_info_get(const uint8_t* in, uint64_t c, zes_png_info* info, uint32_t
  * when info is not NULL (zeros for a file the rule rejects); the return value is non-zero only when the call as a whole could
  * not run.  in_off, in_len, out_off, out_cap, out_len, status and info are host arrays.
  *   ZES_E_ARG   a null array with count != 0, a null d_in / in[i] with a non-zero length, a null d_out while an image has
- *               bytes to write, flag bits other than ZES_F_PIECES (passed on to the inflate tiers)
+ *               bytes to write, flag bits other than ZES_F_PIECES (passed on to the inflate tiers) and ZES_F_PNG_INTERLACED
  *   count == 0  ZES_OK, no device work; zes_last_kernel_times then reports no launch and zes_last_inflate_tier 0
  * An image's status, decided in this order; an image with a status costs no later launch for itself:
  *   1. the file rule above (device form: k_png_walk, one lane a file, which also lists every chunk; alloc form: the host's
- *      function), then interlace 1: ZES_E_UNSUPPORTED, then (device form) out_cap[i] < out_size: ZES_E_NOSPACE.  A call whose
+ *      function), then interlace 1: ZES_E_UNSUPPORTED (without ZES_F_PNG_INTERLACED; with it: "Interlaced images"), then (device form) out_cap[i] < out_size: ZES_E_NOSPACE.  A call whose
  *      capacities are all 0 is the sizing pass and costs the walk alone.
  *   2. chunk CRCs: one segmented CRC-32 launch over type and data of every chunk of every image still at ZES_OK; any
  *      mismatch, ancillary chunks included, is ZES_E_CHECKSUM
@@ -509,6 +512,36 @@ int zes_png_info_get(const uint8_t* in, uint64_t c, zes_png_info* info, uint32_t
  * Known limit: the filters of Up, Average and Paeth rows depend on the row above, so an image is unfiltered by one wave from
  * each row of filter None or Sub that starts a band of 64 rows (and from row 0) to the next such row.  An image without such
  * rows is unfiltered by a single wave: the design point is a batch of images, not one large image.
+ *
+ * Interlaced images.  With ZES_F_PNG_INTERLACED in flags (zes_png_decode_dev, zes_png_decode_alloc, zes_pngpix_dev and
+ * zes_pngpix_alloc take it, alone or with ZES_F_PIECES; no other call does) a file of interlace method 1 (Adam7) is decoded
+ * too; without the flag, and for every file of interlace method 0 with it, statuses, bytes and launches are what they are
+ * above.  Pass p = 1..7 of a width x height image holds the pixels (x0 + k * dx, y0 + m * dy):
+ *            pass   1  2  3  4  5  6  7
+ *            x0     0  4  0  2  0  1  0
+ *            y0     0  0  4  0  2  0  1
+ *            dx     8  8  4  4  2  2  1
+ *            dy     8  8  8  4  4  2  2
+ * It has pw = ceil((width - x0) / dx) pixels a row and ph = ceil((height - y0) / dy) rows, each 0 when the difference is not
+ * positive.  A pass with pw == 0 or ph == 0 has no byte in the stream, not even filter bytes; any other one has ph rows of
+ * 1 + ceil(pw * channels * depth / 8) bytes, filtered as an image of its own: the row above its row 0 is zeros, the filter
+ * unit is the image's bpp.  The passes stand back to back; Fi, the interlaced filtered size, is the sum of their bytes.  The
+ * steps above apply with these differences:
+ *   1. Fi > 0xFFFFFFFF (computed in 64 bits: Fi can exceed the F of the file rule) is ZES_E_UNSUPPORTED, in the alloc forms on
+ *      the host as the rule is.  out_size, out_len and zes_png_info are unchanged: the result is height * rowbytes bytes (the
+ *      pixel forms: width * height * 4)
+ *   3. the stream must inflate to exactly Fi bytes, else ZES_E_PNG
+ *   4. the same single k_png_unfilter launch, an interlaced image's passes being up to seven images of it, unfiltered into
+ *      pooled scratch; a filter byte above 4 in any pass makes the image ZES_E_PNG
+ *   4b. one k_png_deinterlace launch for the batch, only when an interlaced image is still at ZES_OK (the tiles of an
+ *      interlaced image that step 4 made ZES_E_PNG are then part of that launch and exit at once, writing nothing: the
+ *      launch is the batch's, and its table went up before step 4), gathers the passes into
+ *      the scanlines exactly as a non-interlaced file of the same pixels decodes: 16-bit samples big-endian, sub-byte samples
+ *      packed from the high bits, palette indices as indices.  The pad bits behind a row's last pixel (depths below 8) are
+ *      zeros: the pad bits of the pass rows in the file may hold anything and do not reach the output
+ * The contracts above stay: no launch, copy or synchronisation per image or per pass; exactly out_size bytes an image, no byte
+ * outside the ranges of the images that reach the last step, at any alignment.  Scratch grows by a slot for the unfiltered
+ * passes of every interlaced image.  Writing interlaced files is out of scope (zes_pngwrite* writes interlace 0).
  * replaces: nothing (the reference has no PNG container) */
 int zes_png_decode_dev(const uint8_t* d_in, const uint64_t* in_off, const uint64_t* in_len, uint32_t count, uint8_t* d_out,
                        const uint64_t* out_off, const uint64_t* out_cap, uint64_t* out_len, int32_t* status, zes_png_info* info, uint32_t flags);
@@ -576,8 +609,8 @@ int zes_pngwrite(const uint8_t* const* in, const uint64_t* in_len, const zes_png
                  zes_alloc_fn alloc, void* user, uint64_t* out_len, int32_t* status, uint32_t flags);
 
 /* zes_pngpix*: PNG files decoded to pixels, width * height * 4 bytes of R, G, B, A an image, row by row from the top, as one
- * batch on the device: what a texture or an image tensor takes.  No Adam7 interlace, no gamma, no colour management, no
- * output format other than 8-bit RGBA.
+ * batch on the device: what a texture or an image tensor takes.  Adam7 interlace is refused without ZES_F_PNG_INTERLACED;
+ * no gamma, no colour management, no output format other than 8-bit RGBA.
  * The conversion rule.  A stored sample s of depth d becomes 8 bits: d = 1: s * 255; 2: s * 85; 4: s * 17; 8: s; 16: s >> 8
  * (the high byte: libpng's strip_16).  Per colour type:
  *   0 (grey)        R = G = B = the 8-bit grey, A = 255.  With a tRNS of 2 bytes, A = 0 exactly where the stored sample, at its
@@ -595,13 +628,15 @@ int zes_pngwrite(const uint8_t* const* in, const uint64_t* in_len, const zes_png
  * through, and these calls do not refuse them.
  *
  * zes_pngpix_dev / zes_pngpix_alloc take the arguments of zes_png_decode_dev / zes_png_decode_alloc, fill the same
- * zes_png_info, and answer the same statuses from the same steps 1 to 4 in the same order (flags: ZES_F_PIECES only), with
- * these differences:
+ * zes_png_info, and answer the same statuses from the same steps 1 to 4 in the same order (flags: ZES_F_PIECES and ZES_F_PNG_INTERLACED only),
+ * with these differences:
  *   size    the size of image i is width * height * 4: what out_len[i] reports (on ZES_OK and ZES_E_NOSPACE), what out_cap[i]
  *           is compared with and what alloc is asked for.  A call whose capacities are all 0 is the sizing pass and costs the
  *           walk alone
  *   step 4  writes the unfiltered scanlines into pooled scratch, a 16-byte aligned and padded slot an image (zes_trim,
- *           zes_pool_bytes and zes_stage_poison cover it), not into the caller's memory
+ *           zes_pool_bytes and zes_stage_poison cover it), not into the caller's memory; step 4b (ZES_F_PNG_INTERLACED) writes
+ *           an interlaced image's scanlines into the same kind of slot, and step 5 runs over plain and deinterlaced images
+ *           together
  *   step 5  one k_png_expand launch for the batch writes the pixels of the images still at ZES_OK.  PLTE and tRNS are read on
  *           the device from the file bytes at plte_pos / trns_pos, at any alignment (step 2 has checked their CRCs)
  * An image with a status costs no later launch for itself; there is no launch, copy or synchronisation per image.  A call

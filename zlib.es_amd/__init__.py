@@ -48,6 +48,7 @@ ZES_E_UNSUPPORTED = -23  # zes_zip_*: ZIP64, several disks, encryption, a method
 ZES_E_PNG = -24  # zes_png_*: not a PNG file this reader accepts, or image data that does not fit its header
 ZES_F_GZIP_SERIAL = 32  # zes_gunzip*: the members one after the other even where they could go as one batch (testing aid)
 ZES_F_INDEX_WALK = 64  # zes_bgzf_index_dev: the members by k_gz_walk's serial chain instead of the parallel finder (testing aid, baseline)
+ZES_F_PNG_INTERLACED = 128  # zes_png_decode*, zes_pngpix_dev, zes_pngpix_alloc: Adam7-interlaced files decode too (without it: ZES_E_UNSUPPORTED)
 ZES_F_CHECK_ADLER = 16  # zes_inflate*, the batch forms included: the Adler-32 trailer behind the stream must be there and match
 
 GEN_KINDS = {"xorshift": 0, "lowent4k": 1, "itext": 2}
@@ -665,12 +666,15 @@ def _png_batch(pix, buffers, flags):
 def png_decode_batch(buffers, flags=0):
     """PNG files decoded as one batch (zes_png_decode_alloc): a list with one ``(info, scanlines)`` pair or one ZlibEsError
     per file (not raised, as with zip_read).  ``scanlines`` is a uint8 array of ``height`` x ``rowbytes``: the samples as the
-    file stores them (16-bit big-endian, sub-byte samples packed, palette indices), the filters undone."""
+    file stores them (16-bit big-endian, sub-byte samples packed, palette indices), the filters undone.  An Adam7-interlaced
+    file is ZlibEsError(ZES_E_UNSUPPORTED) unless ``flags`` has ZES_F_PNG_INTERLACED; with it, its scanlines are those of a
+    non-interlaced file of the same pixels."""
     return _png_batch(False, buffers, flags)
 
 
 def png_decode(data, flags=0):
-    """One PNG file decoded: ``(info, scanlines)`` as png_decode_batch gives them; a file that fails raises."""
+    """One PNG file decoded: ``(info, scanlines)`` as png_decode_batch gives them; a file that fails raises.  ``flags``:
+    ZES_F_PNG_INTERLACED to take an Adam7-interlaced file."""
     got = png_decode_batch([data], flags)[0]
     if isinstance(got, Exception):
         raise got
@@ -681,12 +685,13 @@ def png_pixels_batch(buffers, flags=0):
     """PNG files decoded to pixels as one batch (zes_pngpix_alloc): a list with one ``(info, rgba)`` pair or one ZlibEsError
     per file (not raised, as with png_decode_batch).  ``rgba`` is a uint8 array of ``height`` x ``width`` x 4: R, G, B, A by
     the conversion rule of include/zes.h (sub-byte samples scaled, 16-bit samples cut to their high byte, the palette looked
-    up, tRNS applied)."""
+    up, tRNS applied).  ``flags``: ZES_F_PNG_INTERLACED to take Adam7-interlaced files too, as png_decode_batch does."""
     return _png_batch(True, buffers, flags)
 
 
 def png_pixels(data, flags=0):
-    """One PNG file decoded to pixels: ``(info, rgba)`` as png_pixels_batch gives them; a file that fails raises."""
+    """One PNG file decoded to pixels: ``(info, rgba)`` as png_pixels_batch gives them; a file that fails raises.  ``flags``:
+    ZES_F_PNG_INTERLACED to take an Adam7-interlaced file."""
     got = png_pixels_batch([data], flags)[0]
     if isinstance(got, Exception):
         raise got
@@ -1025,7 +1030,8 @@ def png_decode_tensor(d_in, in_off, in_len, out=None, off=None, flags=0, cap=Non
     array.  ``d_in``, ``out`` and every offset may be any byte.  Without ``off`` a sizing pass (the chunk walk alone) comes
     first and the images are packed at 16-byte boundaries from the start of ``out``, which is allocated when it is None.
     ``cap``: the capacity of every image's place (default: up to the end of ``out``); an image that needs more is
-    ZES_E_NOSPACE with its ``out_len`` the size needed."""
+    ZES_E_NOSPACE with its ``out_len`` the size needed.  ``flags``: ZES_F_PNG_INTERLACED to take Adam7-interlaced files too
+    (ZES_E_UNSUPPORTED without it); their sizes and scanlines are those of non-interlaced files of the same pixels."""
     return _png_tensor(False, d_in, in_off, in_len, out, off, flags, cap)
 
 
@@ -1074,7 +1080,8 @@ def _png_tensor(_pix, d_in, in_off, in_len, out, off, flags, cap):
 def png_pixels_tensor(d_in, in_off, in_len, out=None, off=None, flags=0, cap=None):
     """PNG files in a 1-D uint8 CUDA tensor decoded to pixels as one batch (zes_pngpix_dev): png_decode_tensor's arguments and
     result, ``(out, off, out_len, status, info)``, with image i's ``width * height * 4`` bytes of R, G, B, A at
-    ``out[off[i] : off[i] + out_len[i]]`` (the conversion rule of include/zes.h)."""
+    ``out[off[i] : off[i] + out_len[i]]`` (the conversion rule of include/zes.h).  ``flags``: ZES_F_PNG_INTERLACED as in
+    png_decode_tensor."""
     return _png_tensor(True, d_in, in_off, in_len, out, off, flags, cap)
 
 

@@ -162,8 +162,10 @@ static_assert(disjoint({PIN_SPAN(t2.search), PIN_SPAN(t2.ncand), PIN_SPAN(t2.nsu
   X(crctab) X(crcacc) X(gz_in) X(gz_acc) X(gz_stage) X(gz_bodies) X(gz_outs) X(gz_tab) X(crcseg)                                  \
   /* seg_checksum_locked's segs | work | acc for the Adler-32; the gathered trailers of a checked inflate batch */                \
   X(adlerseg)                                                                                                                     \
-  /* zes_pngpix*: the unfiltered scanlines of a batch, a padded slot an image, on their way to k_png_expand */                    \
-  X(png_lines)
+  /* zes_pngpix*: the unfiltered scanlines of a batch, a padded slot an image, on their way to k_png_expand; */                   \
+  /* ZES_F_PNG_INTERLACED: the unfiltered passes of a batch's Adam7 images, a padded slot an image, on their way to */            \
+  /* k_png_deinterlace */                                                                                                         \
+  X(png_lines) X(png_passes)
 
 // The survivor list of the block-start search as the block-parallel tier's scan left it in a pool (one buffer): the
 // segment-parallel tier's search of the same stream starts from it instead of scanning again.  The note holds until it
@@ -5582,6 +5584,33 @@ int zes_png_info_get(const uint8_t* in, uint64_t c, zes_png_info* info, uint32_t
   return h.status;
 }
 
+// An Adam7 image's seven passes (include/zes.h: "Interlaced images"): pass p + 1 has ph[p] rows of prb[p] bytes behind a filter
+// byte each (both 0 for a pass without pixels, which has no byte in the stream); Fi is what the stream inflates to.  Where
+// the unfiltered passes stand in the image's slot of g.png_passes: off[p], each on a 16-byte boundary; the slot is padded
+struct PngPasses {
+  uint32_t ph[7];
+  uint64_t prb[7], off[7];
+  uint64_t Fi, slot;
+};
+static PngPasses png_passes_of(const ZesPngHead& h) {
+  static const uint8_t x0[7] = {0, 4, 0, 2, 0, 1, 0}, y0[7] = {0, 0, 4, 0, 2, 0, 1}, sx[7] = {3, 3, 2, 2, 1, 1, 0}, sy[7] = {3, 3, 3, 2, 2, 1, 1};
+  const uint64_t bits = png_channels(h.colour) * h.depth;
+  PngPasses a;
+  a.Fi = a.slot = 0;
+  for (int p = 0; p < 7; p++) {
+    uint64_t pw = h.width > x0[p] ? ((uint64_t)(h.width - x0[p]) + (1u << sx[p]) - 1) >> sx[p] : 0;
+    uint64_t ph = h.height > y0[p] ? ((uint64_t)(h.height - y0[p]) + (1u << sy[p]) - 1) >> sy[p] : 0;
+    if (!pw || !ph) pw = ph = 0;
+    a.ph[p] = (uint32_t)ph;
+    a.prb[p] = (pw * bits + 7) / 8;
+    a.off[p] = a.slot;
+    a.Fi += ph * (1 + a.prb[p]);  // (at most the file rule's F a pass: no overflow)
+    a.slot += gz_up16(ph * a.prb[p]);
+  }
+  a.slot += 16;
+  return a;
+}
+
 // One file of a png_decode_core batch: what the walk says about it, its chunks (when it passed the rule), where its first
 // byte lies in d_src and where its out_size bytes go in dst
 struct PngImg {
@@ -5643,8 +5672,11 @@ static int png_walk_dev(const uint8_t* d_src, const uint64_t* in_off, const uint
 }
 
 // The images of im whose status[k] is ZES_OK on entry (rule, interlace and capacity have passed them): steps 2 to 4 of
-// include/zes.h, every step one launch sequence for the batch.  status[k] becomes the image's status.
-static int png_decode_core(const uint8_t* d_src, const std::vector<PngImg>& im, uint8_t* dst, int32_t* status, uint32_t flags) {
+// include/zes.h, every step one launch sequence for the batch.  status[k] becomes the image's status.  An interlaced image
+// (it is here only under ZES_F_PNG_INTERLACED) takes the same steps with its seven passes as seven images of step 4, which go
+// to a slot of g.png_passes, and step 4b behind it: k_png_deinterlace from there to the image's place.  `more`: the caller
+// launches on g.stream behind this and synchronises there (pngpix_core), so step 4b, which brings nothing back, does not.
+static int png_decode_core(const uint8_t* d_src, const std::vector<PngImg>& im, uint8_t* dst, int32_t* status, uint32_t flags, bool more = false) {
   int rc;
   g.last_tier = 0;
   const uint32_t n = (uint32_t)im.size();
@@ -5653,6 +5685,8 @@ static int png_decode_core(const uint8_t* d_src, const std::vector<PngImg>& im, 
   std::vector<ZesCrcSeg> csegs;
   std::vector<ZesGzSeg> segs;
   std::vector<ZesPngJob> uj;
+  std::vector<ZesPngDeintJob> dj;
+  std::vector<uint8_t> table;
   std::vector<uint32_t> bad;
   Drain drain;
   // 2. chunk CRCs: type and data of every chunk
@@ -5677,7 +5711,7 @@ static int png_decode_core(const uint8_t* d_src, const std::vector<PngImg>& im, 
   for (uint32_t k = 0; k < n; k++) {
     if (status[k] != ZES_OK) continue;
     const ZesPngHead& h = im[k].h;
-    const uint64_t F = h.height * (1 + png_rowbytes(h));
+    const uint64_t F = h.interlace ? png_passes_of(h).Fi : h.height * (1 + png_rowbytes(h));
     uint64_t at = ipos;
     for (const ZesPngChunk& c : im[k].ch)
       if ((c.len & ZES_PNG_IDAT) && (c.len & ~ZES_PNG_IDAT)) {
@@ -5704,57 +5738,103 @@ static int png_decode_core(const uint8_t* d_src, const std::vector<PngImg>& im, 
   if ((rc = check_adler_jobs((const uint8_t*)g.gz_bodies.p, nullptr, (const uint8_t*)g.gz_outs.p, jobs))) return rc;
   keep_times();
   // 4. the filters
-  std::vector<uint32_t> uw;
-  uint64_t bands = 0;
+  std::vector<uint32_t> uw, dw;
+  uint64_t bands = 0, tiles = 0, pass_at = 0;
   for (size_t q = 0; q < jobs.size(); q++) {
     const uint32_t k = who[q];
     status[k] = jobs[q].status;
     if (status[k] != ZES_OK) continue;
     const ZesPngHead& h = im[k].h;
-    const uint32_t depth_bits = png_channels(h.colour) * h.depth;
-    uj.push_back(ZesPngJob{jobs[q].out_off, im[k].dst_off, h.height, (uint32_t)png_rowbytes(h), std::max<uint32_t>(1, depth_bits / 8), (uint32_t)bands});
-    uw.push_back(k);
-    bands += (h.height + ZES_PNG_BAND - 1) / ZES_PNG_BAND;
-    if (bands > 0x7fffffffull) return ZES_E_ARG;
+    const uint32_t depth_bits = png_channels(h.colour) * h.depth, bpp = std::max<uint32_t>(1, depth_bits / 8);
+    if (!h.interlace) {
+      uj.push_back(ZesPngJob{jobs[q].out_off, im[k].dst_off, h.height, (uint32_t)png_rowbytes(h), bpp, (uint32_t)bands});
+      uw.push_back(k);
+      bands += (h.height + ZES_PNG_BAND - 1) / ZES_PNG_BAND;
+    } else {  // a job per pass that has pixels, and the record of step 4b
+      const PngPasses a = png_passes_of(h);
+      ZesPngDeintJob d;
+      memset(&d, 0, sizeof d);
+      d.src_off = pass_at, d.dst_off = im[k].dst_off;
+      d.width = h.width, d.height = h.height, d.rowbytes = (uint32_t)png_rowbytes(h), d.bits = depth_bits;
+      d.tile_rows = std::min(h.height, std::max(1u, ZES_PNGD_TILE_BYTES / d.rowbytes));
+      d.first_tile = (uint32_t)tiles;
+      d.ujob0 = (uint32_t)uj.size();
+      uint64_t from = jobs[q].out_off;
+      for (int p = 0; p < 7; p++) {
+        d.pass_off16[p] = (uint32_t)(a.off[p] / 16);
+        if (!a.ph[p]) continue;
+        uj.push_back(ZesPngJob{from, pass_at + a.off[p], a.ph[p], (uint32_t)a.prb[p], bpp | ZES_PNG_TO_PASSES, (uint32_t)bands});
+        uw.push_back(k);
+        bands += (a.ph[p] + ZES_PNG_BAND - 1) / ZES_PNG_BAND;
+        from += a.ph[p] * (1 + a.prb[p]);
+      }
+      d.ujobs = (uint32_t)uj.size() - d.ujob0;
+      dj.push_back(d);
+      dw.push_back(k);
+      tiles += (h.height + d.tile_rows - 1) / d.tile_rows;
+      pass_at += a.slot;
+    }
+    if (bands > 0x7fffffffull || tiles > 0x7fffffffull || uj.size() > 0x7fffffffull) return ZES_E_ARG;
   }
   if (uj.empty()) {
     drain.done();  // (inflate_jobs has brought the jobs' results down: the stream is past segs)
     return ZES_OK;
   }
-  const size_t o_bad = sizeof(ZesPngJob) * uj.size();
+  // one table, one upload: the unfilter jobs, the deinterlace jobs behind them, then the jobs' `bad` words
+  const size_t o_dj = sizeof(ZesPngJob) * uj.size(), o_bad = o_dj + sizeof(ZesPngDeintJob) * dj.size();
+  table.resize(o_bad);
+  memcpy(table.data(), uj.data(), o_dj);
+  if (!dj.empty()) memcpy(table.data() + o_dj, dj.data(), o_bad - o_dj);
   if ((rc = ensure(g.gz_tab, o_bad + 4 * uj.size()))) return rc;
+  if (pass_at && (rc = ensure(g.png_passes, pass_at + 64))) return rc;
   uint32_t* d_bad = (uint32_t*)((uint8_t*)g.gz_tab.p + o_bad);
-  HIPCHK(hipMemcpyAsync(g.gz_tab.p, uj.data(), o_bad, hipMemcpyHostToDevice, g.stream));
+  HIPCHK(hipMemcpyAsync(g.gz_tab.p, table.data(), o_bad, hipMemcpyHostToDevice, g.stream));
   HIPCHK(hipMemsetAsync(d_bad, 0, 4 * uj.size(), g.stream));
   {
     Timed t("k_png_unfilter");
     constexpr uint32_t per = ZES_PNG_UNF_THREADS / 64u;
     hipLaunchKernelGGL(k_png_unfilter, dim3((uint32_t)((bands + per - 1) / per)), dim3(ZES_PNG_UNF_THREADS), 0, g.stream, (const uint8_t*)g.gz_outs.p, dst,
-                       (const ZesPngJob*)g.gz_tab.p, (uint32_t)uj.size(), (uint32_t)bands, d_bad);
+                       (uint8_t*)g.png_passes.p, (const ZesPngJob*)g.gz_tab.p, (uint32_t)uj.size(), (uint32_t)bands, d_bad);
   }
   HIPCHK(hipGetLastError());
   bad.resize(uj.size());
   HIPCHK(hipMemcpyAsync(bad.data(), d_bad, 4 * uj.size(), hipMemcpyDeviceToHost, g.stream));
   HIPCHK(hipStreamSynchronize(g.stream));
-  drain.done();
+  drain.done();  // (the table has gone up and the words have come down: nothing queued reads or writes host memory now)
   for (size_t q = 0; q < uj.size(); q++)
     if (bad[q]) status[uw[q]] = ZES_E_PNG;
+  // 4b. the passes of the interlaced images gathered into scanlines: the table is already there, and the tiles of an image
+  // that has a `bad` word set are launched with the others and exit on reading it
+  bool gather = false;
+  for (const uint32_t k : dw) gather = gather || status[k] == ZES_OK;
+  if (gather) {
+    {
+      Timed t("k_png_deinterlace");
+      hipLaunchKernelGGL(k_png_deinterlace, dim3((uint32_t)tiles), dim3(ZES_PNGD_THREADS), 0, g.stream, (const uint8_t*)g.png_passes.p, dst,
+                         (const ZesPngDeintJob*)((const uint8_t*)g.gz_tab.p + o_dj), (uint32_t)dj.size(), (const uint32_t*)d_bad);
+    }
+    HIPCHK(hipGetLastError());
+    if (!more) HIPCHK(hipStreamSynchronize(g.stream));
+  }
   return ZES_OK;
 }
+static_assert(sizeof(ZesPngJob) == 32 && sizeof(ZesPngDeintJob) == 80, "the step-4 table: 8-byte aligned records back to back");
 
 // zes_png_decode*: what both forms check before anything else
 static int png_decode_args(bool arrays, const uint64_t* out_len, const int32_t* status, uint32_t count, uint32_t flags) {
-  if (flags & ~ZES_F_PIECES) return ZES_E_ARG;
+  if (flags & ~(ZES_F_PIECES | ZES_F_PNG_INTERLACED)) return ZES_E_ARG;
   if (count && (!arrays || !out_len || !status)) return ZES_E_ARG;
   return ZES_OK;
 }
 
-// Step 1 behind the walk, for image i: the rule's verdict, then interlace; the caller's records filled
-static void png_judge(const PngImg& m, uint32_t i, uint64_t* out_len, int32_t* status, zes_png_info* info, zes_png_info* mine) {
+// Step 1 behind the walk, for image i: the rule's verdict, then interlace (refused without ZES_F_PNG_INTERLACED; with it, the
+// seven passes' filtered size has the bound the rule sets for a plain image's); the caller's records filled
+static void png_judge(const PngImg& m, uint32_t i, uint64_t* out_len, int32_t* status, zes_png_info* info, zes_png_info* mine, uint32_t flags) {
   png_info_of(m.h, mine);
   if (info) info[i] = *mine;
   out_len[i] = 0;
-  status[i] = m.h.status != ZES_OK ? m.h.status : m.h.interlace ? ZES_E_UNSUPPORTED : ZES_OK;
+  status[i] = m.h.status;
+  if (status[i] == ZES_OK && m.h.interlace && (!(flags & ZES_F_PNG_INTERLACED) || png_passes_of(m.h).Fi > 0xFFFFFFFFull)) status[i] = ZES_E_UNSUPPORTED;
 }
 
 // ---- step 5 of zes_pngpix* (include/zes.h: "The conversion rule"), which zes_pngpix_expand_dev runs alone ----
@@ -5813,7 +5893,7 @@ static int pngpix_core(const uint8_t* d_src, std::vector<PngImg>& im, uint8_t* d
   // The pixel forms launch the same kernels for one image as for many: a single stream's block chain is followed by
   // k_inf_chain as a batch's is, not on the host (a kernel of about 11 us; the design point is a batch)
   g.device_chain = true;
-  rc = png_decode_core(d_src, im, (uint8_t*)g.png_lines.p, status, flags);
+  rc = png_decode_core(d_src, im, (uint8_t*)g.png_lines.p, status, flags, true);  // (an image at ZES_OK behind it: pngx_run synchronises)
   g.device_chain = false;
   if (rc) return rc;
   std::vector<uint8_t> table;
@@ -5849,7 +5929,7 @@ static int png_dev_form(bool pix, const uint8_t* d_in, const uint64_t* in_off, c
   bool null_out = false;
   for (uint32_t i = 0; i < count; i++) {
     zes_png_info mine;
-    png_judge(im[i], i, out_len, status, info, &mine);
+    png_judge(im[i], i, out_len, status, info, &mine, flags);
     im[i].src_at = in_off[i];
     im[i].dst_off = out_off[i];
     if (status[i] != ZES_OK) continue;
@@ -5884,7 +5964,7 @@ static int png_alloc_form(bool pix, const uint8_t* const* in, const uint64_t* in
     PngImg& m = im[i];
     m.h.status = png_rule(in[i], in_len[i], m.h, [&](const ZesPngChunk& c) { m.ch.push_back(c); });
     zes_png_info mine;
-    png_judge(m, i, out_len, status, info, &mine);
+    png_judge(m, i, out_len, status, info, &mine, flags);
     if (status[i] != ZES_OK) continue;
     any = true;
     size[i] = pix ? png_pix_size(mine.width, mine.height) : mine.out_size;

@@ -250,6 +250,23 @@ struct ZesPngJob {
 };
 #define ZES_PNG_BAND 64u          // rows of a band: a lane each
 #define ZES_PNG_UNF_THREADS 256u  // four independent waves to a workgroup
+#define ZES_PNG_TO_PASSES 0x80000000u  // in ZesPngJob::bpp: a pass of an interlaced image, dst_off counts in the kernel's `passes`
+// k_png_deinterlace (zes_png.hip): one Adam7 image whose seven unfiltered passes stand in a slot of `passes`; pass p begins
+// at 16 * pass_off16[p - 1] of the slot, its rows packed (no filter bytes).  Its output rows are cut into tiles of tile_rows,
+// a workgroup each: the workgroups [first_tile, + ceil(height / tile_rows)) of the launch.  The image's passes were the
+// unfilter jobs [ujob0, + ujobs) of the same call: the kernel leaves an image alone when one of their `bad` words is set
+struct ZesPngDeintJob {  // 80 bytes
+  uint64_t src_off;   // the slot, 16-byte aligned
+  uint64_t dst_off;   // where the height * rowbytes result bytes go, any alignment
+  uint32_t width, height, rowbytes;
+  uint32_t bits;      // of a pixel: 1, 2, 4, 8, 16, 24, 32, 48, 64
+  uint32_t first_tile, tile_rows;
+  uint32_t ujob0, ujobs;
+  uint32_t pass_off16[7];
+  uint32_t pad;
+};
+#define ZES_PNGD_THREADS 256u
+#define ZES_PNGD_TILE_BYTES 32768u  // about what a tile writes
 // k_png_expand (zes_png.hip): one image whose scanlines (no filter bytes) become 8-bit RGBA pixels.  Its rows are cut into
 // tiles of tile_rows, a workgroup each: the workgroups [first_tile, + ceil(height / tile_rows)) of the launch
 struct ZesPngxJob {   // 64 bytes
@@ -390,7 +407,8 @@ __global__ void k_zip_stage(const uint8_t*, uint8_t*, uint8_t*, const ZesZipRec*
 __global__ void k_zip_pack(const uint8_t*, const uint8_t*, const uint8_t*, uint8_t*, const ZesZipPackRec*, uint32_t);
 // PNG reader (zes_png.hip)
 __global__ void k_png_walk(const uint8_t*, const ZesPngFile*, uint32_t, ZesPngHead*, ZesPngChunk*);
-__global__ void k_png_unfilter(const uint8_t*, uint8_t*, const ZesPngJob*, uint32_t, uint32_t, uint32_t*);
+__global__ void k_png_unfilter(const uint8_t*, uint8_t*, uint8_t*, const ZesPngJob*, uint32_t, uint32_t, uint32_t*);
+__global__ void k_png_deinterlace(const uint8_t*, uint8_t*, const ZesPngDeintJob*, uint32_t, const uint32_t*);
 __global__ void k_png_expand(const uint8_t*, const uint8_t*, uint8_t*, const ZesPngxJob*, uint32_t);
 // PNG writer (zes_pngw.hip, zes_crc.hip)
 __global__ void k_png_filter(const uint8_t*, uint8_t*, const ZesPngwJob*, uint32_t);

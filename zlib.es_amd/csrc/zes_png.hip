@@ -25,7 +25,11 @@
 //   k_png_expand    the scanlines of the batch turned into 8-bit RGBA pixels by the conversion rule of include/zes.h, in one
 //                   launch: a streaming kernel, a workgroup per (image, tile of rows), a lane four pixels a step — source
 //                   bytes fetched as aligned 16-byte groups and shifted into place, results stored as 16-byte groups from
-//                   the first 16-byte boundary of a row's output.  It stands at the end of this file.
+//                   the first 16-byte boundary of a row's output.  It stands behind the unfilter kernel.
+//   k_png_deinterlace  ZES_F_PNG_INTERLACED: the seven Adam7 passes of an image, which k_png_unfilter has unfiltered as images
+//                   of their own into a scratch slot, gathered into the image's scanlines in one launch for the batch: a
+//                   gather driven by the output, a workgroup per (image, tile of output rows), every output byte stored
+//                   once as part of a 16-byte group, a dword or (at a row's ends) a byte.  It stands at the end of this file.
 #include "../../include/zes.h"
 #include "zes_common.h"
 #include "zes_kernels.h"
@@ -251,8 +255,9 @@ __device__ __forceinline__ void png_band(const uint8_t* __restrict__ src, uint8_
 }
 }  // namespace
 
-__global__ __launch_bounds__(ZES_PNG_UNF_THREADS) void k_png_unfilter(const uint8_t* __restrict__ slots, uint8_t* dst, const ZesPngJob* __restrict__ jobs,
-                                                                    uint32_t njobs, uint32_t nbands, uint32_t* __restrict__ bad) {
+__global__ __launch_bounds__(ZES_PNG_UNF_THREADS) void k_png_unfilter(const uint8_t* __restrict__ slots, uint8_t* dst, uint8_t* passes,
+                                                                    const ZesPngJob* __restrict__ jobs, uint32_t njobs, uint32_t nbands,
+                                                                    uint32_t* __restrict__ bad) {
   const uint32_t lane = threadIdx.x & 63u;
   const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(blockIdx.x * (ZES_PNG_UNF_THREADS / 64u) + threadIdx.x / 64u));
   if (wave >= nbands) return;
@@ -262,9 +267,10 @@ __global__ __launch_bounds__(ZES_PNG_UNF_THREADS) void k_png_unfilter(const uint
     if (jobs[mid].first_band <= wave) lo = mid;
     else hi = mid;
   }
-  const ZesPngJob j = jobs[lo];
+  ZesPngJob j = jobs[lo];
   const uint8_t* src = slots + j.src_off;
-  uint8_t* out = dst + j.dst_off;
+  uint8_t* out = ((j.bpp & ZES_PNG_TO_PASSES) ? passes : dst) + j.dst_off;  // (a pass of an Adam7 image is an image of its own)
+  j.bpp &= ~ZES_PNG_TO_PASSES;
   const uint32_t nb = (j.height + ZES_PNG_BAND - 1) / ZES_PNG_BAND;
   uint32_t band = wave - j.first_band;
   auto restart = [&](uint32_t bnd) { return bnd == 0 || src[(uint64_t)bnd * ZES_PNG_BAND * (j.rowbytes + 1ull)] <= 1; };
@@ -451,4 +457,186 @@ __global__ __launch_bounds__(ZES_PNGX_THREADS) void k_png_expand(const uint8_t* 
     default: break;  // (the host passes no other pair)
   }
 #undef PNGX_CASE
+}
+
+// ---- k_png_deinterlace: the seven Adam7 passes gathered back into scanlines (include/zes.h: "Interlaced images") ----
+namespace {
+// Pass p = 1..7 holds the pixels (x0 + k * dx, y0 + m * dy); dx = 1 << sx, dy = 1 << sy, and x0 < dx, y0 < dy, so the
+// pixel (x, y) of pass p is its pixel x >> sx of its row y >> sy.  A nibble a pass, pass 1 lowest.
+constexpr uint32_t PNGD_SX = 0x0112233u, PNGD_SY = 0x1122333u, PNGD_X0 = 0x0102040u;
+struct PngdPass {
+  const uint8_t* base;  // its unfiltered rows, 16-byte aligned
+  uint32_t prb;         // bytes of one of them
+  uint32_t pad;
+};
+// the pass of a pixel of an even row (an odd row is pass 7 from end to end)
+__device__ __forceinline__ uint32_t pngd_pass(uint32_t x, uint32_t y) {
+  return (x & 1u) ? 6u : (y & 2u) ? 5u : (x & 2u) ? 4u : (y & 4u) ? 3u : (x & 4u) ? 2u : 1u;
+}
+// where pixel (x, y), y even, begins in its pass, for pixels of B whole bytes
+template <int B>
+__device__ __forceinline__ const uint8_t* pngd_at(const PngdPass* ps, uint32_t x, uint32_t y) {
+  const uint32_t p = pngd_pass(x, y), q = 4u * (p - 1u);
+  return ps[p].base + (uint64_t)(y >> ((PNGD_SY >> q) & 7u)) * ps[p].prb + (uint64_t)(x >> ((PNGD_SX >> q) & 7u)) * B;
+}
+// output byte o of the even row y, at depths below 8: 8 / D pixels from up to four passes, the first one in the high
+// bits; the places behind the row's last pixel stay zeros
+template <int D>
+__device__ __forceinline__ uint32_t pngd_sub(const PngdPass* ps, uint32_t width, uint32_t y, uint32_t o) {
+  constexpr uint32_t PPB = 8 / D;
+  uint32_t v = 0;
+#pragma unroll
+  for (uint32_t k = 0; k < PPB; k++) {
+    const uint32_t x = o * PPB + k;
+    if (x < width) {
+      const uint32_t p = pngd_pass(x, y), q = 4u * (p - 1u);
+      const uint64_t bit = (uint64_t)(x >> ((PNGD_SX >> q) & 7u)) * D;
+      const uint32_t byte = ps[p].base[(uint64_t)(y >> ((PNGD_SY >> q) & 7u)) * ps[p].prb + (bit >> 3)];
+      v |= ((byte >> (8u - D - (uint32_t)(bit & 7u))) & ((1u << D) - 1u)) << (8u - D - k * D);
+    }
+  }
+  return v;
+}
+// The output bytes [wo, wo + 4) of the even row y as a little-endian dword; those outside [0, rb) are zeros.  Pixels of 2,
+// 4 and 8 bytes are fetched whole where the dword begins on one (a pass begins on a 16-byte boundary and its rows are
+// whole pixels, so such a pixel is aligned to its own size, 4 at most); everything else goes byte by byte.
+template <int BITS>
+__device__ __forceinline__ uint32_t pngd_word(const PngdPass* ps, uint32_t width, uint32_t rb, uint32_t y, int64_t wo) {
+  if ((BITS == 32 || BITS == 64) && wo >= 0 && (wo & 3) == 0) {  // (rb is a multiple of 4: the dword ends inside the row)
+    const uint32_t x = (uint32_t)((uint64_t)wo / (BITS / 8));
+    return *reinterpret_cast<const uint32_t*>(pngd_at<BITS / 8>(ps, x, y) + ((uint64_t)wo % (BITS / 8)));
+  }
+  if (BITS == 16 && wo >= 0 && (wo & 1) == 0) {
+    const uint32_t x = (uint32_t)((uint64_t)wo / 2);
+    uint32_t v = *reinterpret_cast<const uint16_t*>(pngd_at<2>(ps, x, y));
+    if (wo + 2 < (int64_t)rb) v |= (uint32_t)*reinterpret_cast<const uint16_t*>(pngd_at<2>(ps, x + 1u, y)) << 16;
+    return v;
+  }
+  uint32_t v = 0;
+#pragma unroll
+  for (int b = 0; b < 4; b++) {
+    const int64_t o = wo + b;
+    if (o >= 0 && o < (int64_t)rb) {
+      uint32_t byte;
+      if (BITS < 8) {
+        byte = pngd_sub<(BITS < 8 ? BITS : 1)>(ps, width, y, (uint32_t)o);
+      } else {
+        constexpr uint32_t B = BITS < 8 ? 1 : BITS / 8;
+        byte = pngd_at<(int)B>(ps, (uint32_t)o / B, y)[(uint32_t)o % B];
+      }
+      v |= byte << (8 * b);
+    }
+  }
+  return v;
+}
+// the aligned dword at `a`, of which only bytes inside [lo, hi) are read: the others count as zeros
+__device__ __forceinline__ uint32_t pngd_ldw(const uint8_t* a, const uint8_t* lo, const uint8_t* hi) {
+  if (a >= lo && a + 4 <= hi) return *reinterpret_cast<const uint32_t*>(a);
+  uint32_t v = 0;
+#pragma unroll
+  for (int b = 0; b < 4; b++)
+    if (a + b >= lo && a + b < hi) v |= (uint32_t)a[b] << (8 * b);
+  return v;
+}
+
+// A tile: output rows [r0, r1) of one image.  A row's output is cut at the 16-byte boundaries of its addresses into units:
+// a thread makes a unit's four dwords in registers and stores them as one 16-byte group; the unit in front of the row's
+// first boundary and the one that holds its end store their whole dwords and, around those, single bytes.  So every byte of
+// the row is stored once, and none outside it.  The tile's rows * G unit slots are taken by the threads in order, as
+// k_png_expand takes its groups: consecutive lanes have consecutive units of a row.
+// An odd row is row y / 2 of pass 7 as it stands: a dword of it is two aligned dwords of the pass and a funnel shift, no
+// arithmetic per pixel.  Its last byte loses the pad bits of the file (depths below 8).
+template <int BITS>
+__device__ __forceinline__ void pngd_tile(const PngdPass* ps, uint8_t* dst, const ZesPngDeintJob& j, uint32_t r0, uint32_t r1) {
+  const uint32_t rb = j.rowbytes;
+  const uint32_t G = rb / 16u + 2u, dr = ZES_PNGD_THREADS / G, dg = ZES_PNGD_THREADS % G;
+  const uint8_t *p7lo = ps[7].base, *p7hi = p7lo + (uint64_t)(j.height >> 1) * rb;
+  const uint32_t used = (uint32_t)((((uint64_t)j.width * BITS - 1u) & 7u) + 1u);  // bits of a row's last byte that are pixels
+  const uint32_t padmask = ~(((0xFFu >> used) & 0xFFu) << 24);                    // (for a dword whose top byte is that one)
+  uint32_t row = r0 + threadIdx.x / G, g = threadIdx.x % G;
+  for (; row < r1; g += dg, row += dr + (g >= G ? 1u : 0u), g -= (g >= G ? G : 0u)) {
+    uint8_t* o = dst + (uint64_t)row * rb;
+    const int64_t u0 = 16ll * g - (int64_t)((uintptr_t)o & 15u);  // the unit's first byte, counted from the row's
+    if (u0 >= (int64_t)rb) continue;
+    const bool odd = (row & 1u) != 0;
+    const uint8_t* s7 = p7lo + (uint64_t)(row >> 1) * rb;
+    uint32_t w[4];
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+      const int64_t wo = u0 + 4 * k;
+      w[k] = 0;
+      if (wo > -4 && wo < (int64_t)rb) {
+        if (odd) {
+          const uint8_t* s = s7 + wo;
+          const uint32_t sh = (uint32_t)((uintptr_t)s & 3u);
+          const uint32_t a = pngd_ldw(s - sh, p7lo, p7hi);
+          const uint32_t b = sh ? pngd_ldw(s - sh + 4, p7lo, p7hi) : 0u;
+          w[k] = (uint32_t)((((uint64_t)b << 32) | a) >> (8u * sh));
+          const int64_t last = (int64_t)rb - 1 - wo;  // the row's last byte, counted from this dword's first
+          if (BITS < 8 && last >= 0 && last < 4) w[k] &= padmask >> (8 * (3 - (int)last));
+        } else {
+          w[k] = pngd_word<BITS>(ps, j.width, rb, row, wo);
+        }
+      }
+    }
+    uint8_t* to = o + u0;
+    if (u0 >= 0 && u0 + 16 <= (int64_t)rb) {
+      *reinterpret_cast<uint4*>(to) = make_uint4(w[0], w[1], w[2], w[3]);
+    } else {
+#pragma unroll
+      for (int k = 0; k < 4; k++) {
+        const int64_t wo = u0 + 4 * k;
+        if (wo >= 0 && wo + 4 <= (int64_t)rb) {
+          *reinterpret_cast<uint32_t*>(to + 4 * k) = w[k];
+        } else {
+#pragma unroll
+          for (int b = 0; b < 4; b++)
+            if (wo + b >= 0 && wo + b < (int64_t)rb) to[4 * k + b] = (uint8_t)(w[k] >> (8 * b));
+        }
+      }
+    }
+  }
+}
+}  // namespace
+
+// A workgroup per (image, tile of output rows); the tile's image by a binary search of the job table, as k_png_expand finds
+// its tile.  The seven passes' places and row sizes go to LDS once a workgroup: a pixel's pass is then an index.
+__global__ __launch_bounds__(ZES_PNGD_THREADS) void k_png_deinterlace(const uint8_t* __restrict__ passes, uint8_t* __restrict__ dst,
+                                                                     const ZesPngDeintJob* __restrict__ jobs, uint32_t njobs,
+                                                                     const uint32_t* __restrict__ bad) {
+  __shared__ PngdPass ps[8];
+  const uint32_t tile = blockIdx.x;
+  uint32_t lo = 0, hi = njobs;  // the last image whose first tile is not behind this one
+  while (hi - lo > 1) {
+    const uint32_t mid = (lo + hi) / 2;
+    if (jobs[mid].first_tile <= tile) lo = mid;
+    else hi = mid;
+  }
+  const ZesPngDeintJob j = jobs[lo];
+  const uint32_t r0 = (tile - j.first_tile) * j.tile_rows, r1 = min(j.height, r0 + j.tile_rows);  // (tile_rows * tiles < 2^32: the host's rule)
+  if (r0 >= j.height) return;
+  for (uint32_t q = 0; q < j.ujobs; q++)
+    if (bad[j.ujob0 + q]) return;  // a filter byte above 4 in one of its passes: ZES_E_PNG, nothing of it is written
+  if (threadIdx.x < 7u) {
+    const uint32_t q = 4u * threadIdx.x, sx = (PNGD_SX >> q) & 7u, x0 = (PNGD_X0 >> q) & 7u;
+    const uint64_t pw = j.width > x0 ? ((uint64_t)(j.width - x0) + (1u << sx) - 1u) >> sx : 0u;
+    PngdPass p;
+    p.base = passes + j.src_off + 16ull * j.pass_off16[threadIdx.x];
+    p.prb = (uint32_t)((pw * j.bits + 7u) >> 3);
+    p.pad = 0;
+    ps[threadIdx.x + 1u] = p;
+  }
+  __syncthreads();
+  uint8_t* out = dst + j.dst_off;
+  switch (j.bits) {
+    case 1: pngd_tile<1>(ps, out, j, r0, r1); break;
+    case 2: pngd_tile<2>(ps, out, j, r0, r1); break;
+    case 4: pngd_tile<4>(ps, out, j, r0, r1); break;
+    case 8: pngd_tile<8>(ps, out, j, r0, r1); break;
+    case 16: pngd_tile<16>(ps, out, j, r0, r1); break;
+    case 24: pngd_tile<24>(ps, out, j, r0, r1); break;
+    case 32: pngd_tile<32>(ps, out, j, r0, r1); break;
+    case 48: pngd_tile<48>(ps, out, j, r0, r1); break;
+    default: pngd_tile<64>(ps, out, j, r0, r1); break;
+  }
 }

@@ -1048,9 +1048,11 @@ napi_value PngInfo(napi_env env, napi_callback_info info) {
   return v;
 }
 
-// pngDecodeBatch(files) and pngPixelsBatch(files): the files decoded as one batch: { results, info } — per file the scanlines
+// pngDecodeBatch(files[, options]) and pngPixelsBatch(files[, options]): the files decoded as one batch: { results, info } — per file the scanlines
 // (the pixels: width * height * 4 bytes of R, G, B, A) as a fresh Uint8Array or the Error that says why not, as the batch
-// forms answer, and the files' zes_png_info records back to back.  The two differ in the entry point alone
+// forms answer, and the files' zes_png_info records back to back.  The two differ in the entry point alone.  options,
+// { interlaced?: boolean }: ZES_F_PNG_INTERLACED when interlaced is true (Adam7 files decode too); anything but an object or
+// undefined in its place, an array included, is a TypeError
 using PngBatchFn = int (*)(const uint8_t* const*, const uint64_t*, uint32_t, zes_alloc_fn, void*, uint64_t*, int32_t*, zes_png_info*, uint32_t);
 napi_value png_batch(napi_env env, napi_callback_info info, const char* SIG, PngBatchFn fn) {
   const Args a = get_args(env, info);
@@ -1066,8 +1068,20 @@ napi_value png_batch(napi_env env, napi_callback_info info, const char* SIG, Png
       return throw_type(env, std::string(SIG) + ": every element must be a Uint8Array");
     j.in_len[i] = n;
   }
+  uint32_t flags = ZES_F_DEFAULT;
+  napi_valuetype vt = napi_undefined;
+  if (a.argc > 1 && (napi_typeof(env, a.argv[1], &vt) != napi_ok || vt != napi_undefined)) {
+    napi_value v;
+    bool on = false;
+    bool opt_arr = false;
+    if (vt != napi_object || napi_is_array(env, a.argv[1], &opt_arr) != napi_ok || opt_arr)
+      return throw_type(env, std::string(SIG) + ": options must be an object { interlaced?: boolean }");
+    if (napi_get_named_property(env, a.argv[1], "interlaced", &v) == napi_ok && napi_typeof(env, v, &vt) == napi_ok && vt == napi_boolean &&
+        napi_get_value_bool(env, v, &on) == napi_ok && on)
+      flags |= ZES_F_PNG_INTERLACED;
+  }
   std::vector<zes_png_info> recs((size_t)count + 1);
-  j.rc = fn(j.in.data(), j.in_len.data(), count, batch_alloc, &j, j.out_len.data(), j.status.data(), recs.data(), ZES_F_DEFAULT);
+  j.rc = fn(j.in.data(), j.in_len.data(), count, batch_alloc, &j, j.out_len.data(), j.status.data(), recs.data(), flags);
   if (j.rc) return throw_status(env, j.rc);
   void* raw = nullptr;
   napi_value res, vres = batch_results(env, &j), vinfo = new_u8(env, (size_t)count * sizeof(zes_png_info), &raw);

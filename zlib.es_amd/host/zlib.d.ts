@@ -35,12 +35,14 @@ export declare type PngInfo = {
 };
 export declare type PngImage = { info: PngInfo, data: Uint8Array };
 export declare function pngInfo(file: Uint8Array): PngInfo;
-export declare function pngDecode(file: Uint8Array): PngImage;
+/** `interlaced: true` lets Adam7-interlaced files decode too (refused otherwise); the result is that of a non-interlaced file of the same pixels. */
+export declare type PngOptions = { interlaced?: boolean };
+export declare function pngDecode(file: Uint8Array, options?: PngOptions): PngImage;
 export declare type PngResult = PngImage | Error;
-export declare function pngDecodeBatch(files: Uint8Array[]): PngResult[];
+export declare function pngDecodeBatch(files: Uint8Array[], options?: PngOptions): PngResult[];
 /** PNG images as pixels: `data` is width * height * 4 bytes of R, G, B, A (sub-byte samples scaled, 16-bit samples cut to the high byte, palette and tRNS applied). */
-export declare function pngPixels(file: Uint8Array): PngImage;
-export declare function pngPixelsBatch(files: Uint8Array[]): PngResult[];
+export declare function pngPixels(file: Uint8Array, options?: PngOptions): PngImage;
+export declare function pngPixelsBatch(files: Uint8Array[], options?: PngOptions): PngResult[];
 /** PNG images, writing: scanlines as pngDecode gives them to files, one batch on the device; filter 0..4 fixed, 6 adaptive, 5 (default) adaptive with restart rows. */
 export declare type PngSource = {
   data: Uint8Array, width: number, height: number, colourType: number, depth?: number, filter?: number, palette?: Uint8Array, transparency?: Uint8Array,

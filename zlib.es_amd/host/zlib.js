@@ -184,8 +184,12 @@ function zip(files) {
  * files as one batch on the device: one launch checks every chunk's CRC-32, every IDAT stream goes through the inflate tiers
  * in one call, and one launch undoes the scanline filters.  Element i of the result is `{ info, data }` or — instead of a
  * throw — the `Error` that says why not.  `data` holds the scanlines as the file stores them: 16-bit samples big-endian,
- * samples below 8 bits packed, palette indices as indices.  Interlaced files are listed by `pngInfo` and refused by the
- * decoders.  `pngDecode` is the batch of one file and throws its Error.
+ * samples below 8 bits packed, palette indices as indices.  Interlaced (Adam7) files are listed by `pngInfo` and refused by
+ * the decoders without `{ interlaced: true }` as the second argument (ZES_F_PNG_INTERLACED); with it they decode to the
+ * scanlines of a non-interlaced file of the same pixels.  `pngDecode` is the batch of one file and throws its Error.
+ * (The option is written `...options` and read as `options[0]`, as `inflate` writes its own: strip_types.py erases a
+ * rest parameter's type but not the `?` of an optional one, and `.length` stays 1.  zlib.d.ts declares one optional
+ * argument, `options?: PngOptions`; arguments behind it are not looked at.)
  */
 const pngInfoAt = (raw, at) => {  // one zes_png_info record (72 bytes, include/zes.h)
   const v = new DataView(raw.buffer, raw.byteOffset + at, 72);
@@ -201,13 +205,13 @@ function pngInfo(file) {
   return pngInfoAt(addon.pngInfo(file), 0);
 }
 
-function pngDecodeBatch(files) {
-  const got = addon.pngDecodeBatch(files);
+function pngDecodeBatch(files, ...options) {
+  const got = addon.pngDecodeBatch(files, options[0]);
   return got.results.map((r, i) => (r instanceof Error ? r : { info: pngInfoAt(got.info, 72 * i), data: r }));
 }
 
-function pngDecode(file) {
-  const got = pngDecodeBatch([file])[0];
+function pngDecode(file, ...options) {
+  const got = pngDecodeBatch([file], options[0])[0];
   if (got instanceof Error) throw got;
   return got;
 }
@@ -218,16 +222,17 @@ function pngDecode(file) {
  * A, row by row from the top — samples below 8 bits scaled to 0..255, 16-bit samples cut to their high byte, grey
  * replicated, palette indices looked up (an index beyond the palette is opaque black), tRNS applied as alpha (a tRNS whose
  * length does not fit the colour type is ignored).  Element i of the result is `{ info, data }` — `info` as `pngInfo` gives
- * it, `data` the pixels — or the `Error` that says why not.  No gamma, no colour management, no interlaced files.
+ * it, `data` the pixels — or the `Error` that says why not.  No gamma, no colour management; interlaced files are refused
+ * without `{ interlaced: true }` as the second argument (ZES_F_PNG_INTERLACED), as `pngDecodeBatch` refuses them.
  * `pngPixels` is the batch of one file and throws its Error.
  */
-function pngPixelsBatch(files) {
-  const got = addon.pngPixelsBatch(files);
+function pngPixelsBatch(files, ...options) {
+  const got = addon.pngPixelsBatch(files, options[0]);
   return got.results.map((r, i) => (r instanceof Error ? r : { info: pngInfoAt(got.info, 72 * i), data: r }));
 }
 
-function pngPixels(file) {
-  const got = pngPixelsBatch([file])[0];
+function pngPixels(file, ...options) {
+  const got = pngPixelsBatch([file], options[0])[0];
   if (got instanceof Error) throw got;
   return got;
 }
