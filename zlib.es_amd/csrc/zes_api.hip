@@ -812,6 +812,9 @@ int phases_print(PhaseSetter set, uint32_t nblk, int ran, const char* fmt) {
 // route[0..2], and the word the launch left in idx_b's last slot to route[3] (first sort) and route[4] (k_lz_index).
 template <class F>
 int launch_lz77(const uint8_t* d_in, uint32_t grid, bool use_index, bool heaviest_first, bool phases, F after_index, uint32_t* route = nullptr) {
+  // in the pipeline a block parsed from its match list goes on in the position form (zes_kernels.h: ZES_POS_WORDS); the
+  // stage entry hands tokens to the host and asks for the list
+  const uint32_t list_form = route ? 1u : 0u;
   int rc;
   const ZesBuf* dbufs = (const ZesBuf*)g.bufs.p;
   ZesBlk* dblks = (ZesBlk*)g.blks.p;
@@ -873,7 +876,7 @@ int launch_lz77(const uint8_t* d_in, uint32_t grid, bool use_index, bool heavies
     // two launches over all blocks: the blocks with a chain mask or a short match list run two to a compute unit
     // (k_lz_parse_small), the others need the exit maps' 128 KiB; each kernel leaves the other's blocks at once
     hipLaunchKernelGGL(k_lz_parse_small, dim3(grid), dim3(PARSE_THREADS), 0, g.stream, d_in, dbufs, dblks, idx_b, idx_a, (uint32_t*)g.hists.p,
-                       (const uint32_t*)g.tmask.p, (const uint32_t*)g.mlist.p);
+                       (const uint32_t*)g.tmask.p, (const uint32_t*)g.mlist.p, list_form);
   }
   {
     Timed t("k_lz_parse");
@@ -1012,7 +1015,7 @@ int deflate_batch_core(const uint8_t* d_in, const uint64_t* in_off, const uint64
   {
     Timed t("k_emit");
     hipLaunchKernelGGL(k_emit, dim3(nblk), dim3(EMIT_THREADS), 0, g.stream, d_out, dbufs, dblks, (uint32_t*)g.idx_a.p,
-                       (const uint32_t*)g.codes.p, (const uint32_t*)g.hdrs.p);
+                       (const uint32_t*)g.codes.p, (const uint32_t*)g.hdrs.p, d_in, (const uint32_t*)g.idx_b.p, (const uint32_t*)g.mlist.p);
   }
   // (this kernel's stamps 2 .. 6 are no clocks but the first wave's cycles in each step, summed over the block's tiles)
   if (sort_dbg && (rc = phases_print(zes_emit_set_dbg, nblk, 1,

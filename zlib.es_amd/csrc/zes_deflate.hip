@@ -2140,7 +2140,8 @@ template <bool SMALL>
 __device__ __forceinline__ static void parse_body(ParseSmemT<SMALL>& S, const uint8_t* __restrict__ d_in, const ZesBuf* __restrict__ bufs,
                                                   ZesBlk* __restrict__ blks, const uint32_t* __restrict__ match_in,
                                                   uint32_t* __restrict__ tok_out, uint32_t* __restrict__ hists,
-                                                  const uint32_t* __restrict__ tmask_all, const uint32_t* __restrict__ mlist_all) {
+                                                  const uint32_t* __restrict__ tmask_all, const uint32_t* __restrict__ mlist_all,
+                                                  uint32_t list_form) {
   const uint32_t g = blockIdx.x, tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
   const ZesBlk bk = blks[g];
   const ZesBuf bf = bufs[bk.buf];
@@ -2376,6 +2377,10 @@ __device__ __forceinline__ static void parse_body(ParseSmemT<SMALL>& S, const ui
   PSTAMP(4);
   }  // (neither mask nor list: the chain is searched)
   unsigned long long mymask[2] = {0ull, 0ull};  // thread t owns chunks 2t, 2t+1 for the scan
+  // A block parsed from its match list leaves no token list in the pipeline (position form, zes_kernels.h): of D2 it needs
+  // the token count alone, of D3 the histograms.
+  bool posform = false;
+  if constexpr (SMALL) posform = fewmatches && list_form == 0u;
   // ---- D2: token offsets = exclusive scan of the per-chunk counts ----
   uint32_t cnt2[2];
 #pragma unroll
@@ -2401,14 +2406,64 @@ __device__ __forceinline__ static void parse_body(ParseSmemT<SMALL>& S, const ui
     total += sm;
   }
   const uint32_t ex = wbase + incl - mysum;
-  if (tid * 2 < PARSE_CHUNKS) S.u.d.cpre[tid * 2] = ex;
-  if (tid * 2 + 1 < PARSE_CHUNKS) S.u.d.cpre[tid * 2 + 1] = ex + cnt2[0];
-  __syncthreads();
+  if (!posform) {  // (uniform)
+    if (tid * 2 < PARSE_CHUNKS) S.u.d.cpre[tid * 2] = ex;
+    if (tid * 2 + 1 < PARSE_CHUNKS) S.u.d.cpre[tid * 2 + 1] = ex + cnt2[0];
+    __syncthreads();
+  }
 
   PSTAMP(5);
   // ---- D3: tokens + histograms ----
+  // The position form: the block's tokens are the input bytes on the chain and the match words k_lz_match left at the
+  // taken starts, so the two bit maps go out, 32 KiB for 512, and k_emit reads the rest where it lies.  What remains
+  // here is the histograms: the taken matches from the sorted list, the literals four positions a lane from one aligned
+  // word of input.
+  if (posform) {
+    if constexpr (SMALL) {
+      const uint32_t* ch32 = reinterpret_cast<const uint32_t*>(S.u.d.mask);
+      for (uint32_t i = tid; i < ZES_BLK / 32u; i += PARSE_THREADS) reinterpret_cast<uint2*>(to)[i] = make_uint2(ch32[i], S.mstart[i]);
+      for (uint32_t i = tid; i < nml; i += PARSE_THREADS) {
+        if (!S.acc[i]) continue;
+        const uint32_t p = S.srt[i] & 0x1FFFFu, m = mi[p];
+        if (m & ZES_TOK_MATCH) {
+          atomicAdd(&S.lh[257u + zes_len_code(zes_tok_len(m))], 1u);
+          atomicAdd(&S.dh[zes_dist_code(zes_tok_dist(m))], 1u);
+        } else {
+          atomicAdd(&S.lh[src[p]], 1u);
+        }
+      }
+      // the block may begin at any byte: whole words from the word its first byte lies in, shifted; no word without a
+      // byte of the block is touched
+      const uint32_t mis = (uint32_t)(reinterpret_cast<uintptr_t>(src) & 3u);
+      const uint32_t* srcw = reinterpret_cast<const uint32_t*>(src - mis);
+      const uint32_t lastw = (mis + T - 1u) >> 2, nw = (T + 3u) >> 2;
+      for (uint32_t w0 = 0; w0 < nw; w0 += 4u * PARSE_THREADS) {
+        uint32_t lo[4], hi[4];
+#pragma unroll
+        for (uint32_t k = 0; k < 4; k++) lo[k] = srcw[min(w0 + k * PARSE_THREADS + tid, lastw)];
+        if (mis) {  // (uniform)
+#pragma unroll
+          for (uint32_t k = 0; k < 4; k++) hi[k] = srcw[min(w0 + k * PARSE_THREADS + tid + 1u, lastw)];
+        } else {
+#pragma unroll
+          for (uint32_t k = 0; k < 4; k++) hi[k] = 0;
+        }
+#pragma unroll
+        for (uint32_t k = 0; k < 4; k++) {
+          const uint32_t w = w0 + k * PARSE_THREADS + tid;
+          if (w >= nw) continue;
+          const uint32_t v = __builtin_amdgcn_alignbyte(hi[k], lo[k], mis), sh = (w & 7u) * 4u;
+          const uint32_t lit = (ch32[w >> 3] & ~S.mstart[w >> 3]) >> sh;  // on the chain and no match: a literal
+          if (lit & 1u) atomicAdd(&S.lh[v & 0xffu], 1u);
+          if (lit & 2u) atomicAdd(&S.lh[(v >> 8) & 0xffu], 1u);
+          if (lit & 4u) atomicAdd(&S.lh[(v >> 16) & 0xffu], 1u);
+          if (lit & 8u) atomicAdd(&S.lh[v >> 24], 1u);
+        }
+      }
+    }
+  }
   constexpr uint32_t DB = SMALL ? 4u : PARSE_BATCH;  // chunks per batch of loads
-  for (uint32_t cb = c_lo; cb < c_hi; cb += DB) {
+  for (uint32_t cb = c_lo; cb < c_hi && !posform; cb += DB) {
     uint32_t mw[DB], by[DB];
     unsigned long long mks[DB];
     bool ism[DB];
@@ -2474,16 +2529,17 @@ __global__ __launch_bounds__(PARSE_THREADS) void k_lz_parse(const uint8_t* __res
                                                             uint32_t* __restrict__ tok_out, uint32_t* __restrict__ hists,
                                                             const uint32_t* __restrict__ tmask_all, const uint32_t* __restrict__ mlist_all) {
   __shared__ __align__(16) ParseSmemT<false> S;
-  parse_body<false>(S, d_in, bufs, blks, match_in, tok_out, hists, tmask_all, mlist_all);
+  parse_body<false>(S, d_in, bufs, blks, match_in, tok_out, hists, tmask_all, mlist_all, 1u);
 }
-// the blocks with a chain mask or a short match list: two workgroups per compute unit
+// the blocks with a chain mask or a short match list: two workgroups per compute unit.  list_form: a block parsed from its
+// match list gets its token list as every other block does (the stage entry, which hands the tokens to the host)
 __global__ __launch_bounds__(PARSE_THREADS, 8) void k_lz_parse_small(const uint8_t* __restrict__ d_in, const ZesBuf* __restrict__ bufs,
                                                                      ZesBlk* __restrict__ blks, const uint32_t* __restrict__ match_in,
                                                                      uint32_t* __restrict__ tok_out, uint32_t* __restrict__ hists,
                                                                      const uint32_t* __restrict__ tmask_all,
-                                                                     const uint32_t* __restrict__ mlist_all) {
+                                                                     const uint32_t* __restrict__ mlist_all, uint32_t list_form) {
   __shared__ __align__(16) ParseSmemT<true> S;
-  parse_body<true>(S, d_in, bufs, blks, match_in, tok_out, hists, tmask_all, mlist_all);
+  parse_body<true>(S, d_in, bufs, blks, match_in, tok_out, hists, tmask_all, mlist_all, list_form);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -3291,10 +3347,11 @@ __device__ __forceinline__ static uint32_t emit_readlane(uint32_t x, uint32_t l)
 
 // The four items of a lane's group at tokens ti0 .. ti0 + 3, as (value, bits), the bit counts a byte each in nbp.  The
 // match computation of a slot runs only in a wave that holds a match there.  TAIL: the group may reach the block's
-// last token: EOB (src/deflate.ts:222-226) is the item behind it, and nothing comes behind EOB.
+// last token: EOB (src/deflate.ts:222-226) is the item behind it, and nothing comes behind EOB.  none: a bit per slot whose
+// item has no bits at all (the position form: a position that is not on the chain).
 template <bool TAIL>
-__device__ __forceinline__ static void emit_items(const uint32_t* codes, const uint32_t (&tv)[4], uint32_t ti0, uint32_t ntok, uint64_t (&val)[4],
-                                                  uint32_t& nbp, uint32_t& sum) {
+__device__ __forceinline__ static void emit_items(const uint32_t* codes, const uint32_t (&tv)[4], uint32_t ti0, uint32_t ntok, uint32_t none,
+                                                  uint64_t (&val)[4], uint32_t& nbp, uint32_t& sum) {
 #pragma unroll
   for (int k = 0; k < 4; k++) {
     uint32_t t = tv[k];
@@ -3320,7 +3377,7 @@ __device__ __forceinline__ static void emit_items(const uint32_t* codes, const u
         b += td >> 16;
       }
     }
-    if (TAIL && ti0 + k > ntok) {
+    if ((TAIL && ti0 + k > ntok) || ((none >> k) & 1u)) {
       v = 0;
       b = 0;
     }
@@ -3330,14 +3387,22 @@ __device__ __forceinline__ static void emit_items(const uint32_t* codes, const u
   }
 }
 
-__global__ __launch_bounds__(EMIT_THREADS, 8) void k_emit(uint8_t* __restrict__ d_out, const ZesBuf* __restrict__ bufs,
-                                                       const ZesBlk* __restrict__ blks, const uint32_t* __restrict__ tok_in,
-                                                       const uint32_t* __restrict__ codes_in, const uint32_t* __restrict__ hdr_in) {
-  __shared__ EmitSmem S;
+// POS: the front end of a block in the position form (zes_kernels.h: ZES_POS_WORDS).  A tile is 8192 positions, the loop runs
+// to the block's length with EOB as the item behind the last position, and a lane's group is four consecutive positions:
+// one aligned word of input (two, shifted, where the block begins inside a word), the nibble of each bit map, and the
+// match word of the group's first taken start.  A position on the chain is the literal of its byte or, at a taken start,
+// the match; a position inside a match is an item without bits.  The input and the match words are requested a tile
+// ahead, the bit maps two (a match word's address comes out of them), all of it unconditionally with clamped addresses.
+// A wave's group with every position on the chain and no start is the token form's one literal piece, from the same
+// arithmetic; everything behind the build step is the token form's.  MIS: the block begins inside a word (a body of its
+// own: a second word's load under a branch, uniform as it is, makes the loop wait for the loads it has just issued).
+template <bool POS, bool MIS>
+__device__ __forceinline__ static void emit_body(EmitSmem& S, uint8_t* __restrict__ d_out, const ZesBlk bk, const ZesBuf bf,
+                                                 const uint32_t* __restrict__ tok_in, const uint32_t* __restrict__ codes_in,
+                                                 const uint32_t* __restrict__ hdr_in, const uint8_t* __restrict__ d_in,
+                                                 const uint32_t* __restrict__ match_in) {
   const uint32_t g = blockIdx.x, tid = threadIdx.x, lane = tid & 63u;
   const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(tid >> 6));  // (uniform: a scalar register)
-  const ZesBlk bk = blks[g];
-  const ZesBuf bf = bufs[bk.buf];
   uint32_t* out32 = reinterpret_cast<uint32_t*>(d_out + bf.out_off);
   const uint32_t* tk = tok_in + (uint64_t)g * ZES_BLK;
   const uint32_t* hd = hdr_in + (uint64_t)g * ZES_HDR_WORDS;
@@ -3349,8 +3414,37 @@ __global__ __launch_bounds__(EMIT_THREADS, 8) void k_emit(uint8_t* __restrict__ 
   static_assert(EMIT_TILE <= ZES_BLK, "the first tile lies inside the block's token list");
   const uint32_t run0 = wave * EMIT_WAVE_RUN + lane * 4u;  // my first group in a tile; group h lies 256 * h tokens on
   uint4 pre[EMIT_GROUPS];
+  // the position form: the input from the word the block's first byte lies in (no word without a byte of the block is
+  // touched), the block's match words, and what is on its way: the next tile's input words, nibbles (chain | starts << 4,
+  // a byte a group) and match words, and the bit map words of the tile behind it
+  const uint8_t* src = d_in + bf.in_off + (uint64_t)bk.blk * ZES_BLK;
+  const uint32_t mis = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(reinterpret_cast<uintptr_t>(src) & 3u));
+  const uint32_t* srcw = reinterpret_cast<const uint32_t*>(src - mis);
+  const uint32_t lastw = (mis + bk.len - 1u) >> 2;
+  const uint32_t* mi = match_in + (uint64_t)g * ZES_BLK;
+  uint32_t pin_lo[EMIT_GROUPS], pin_hi[EMIT_GROUPS], pmw[EMIT_GROUPS], pnb = 0;
+  uint2 pbm[EMIT_GROUPS];
+  auto ld_bm = [&](uint32_t p) -> uint2 { return reinterpret_cast<const uint2*>(tk)[min(p, ZES_BLK - 4u) >> 5]; };
+  auto nibbles = [&](uint2 b, uint32_t p) -> uint32_t { return ((b.x >> (p & 28u)) & 15u) | (((b.y >> (p & 28u)) & 15u) << 4); };
+  auto ld_in = [&](uint32_t p, uint32_t& lo, uint32_t& hi) {
+    lo = srcw[min(p >> 2, lastw)];
+    hi = 0;
+    if constexpr (MIS) hi = srcw[min((p >> 2) + 1u, lastw)];
+  };
+  auto ld_mw = [&](uint32_t p, uint32_t nb) -> uint32_t {  // the match word of the first start in the nibble pair (none: any word)
+    const uint32_t s = nb >> 4;
+    return mi[s ? min(p + (uint32_t)__ffs((int)s) - 1u, ZES_BLK - 1u) : lane];
+  };
+  if constexpr (POS) {
 #pragma unroll
-  for (int h = 0; h < EMIT_GROUPS; h++) pre[h] = *reinterpret_cast<const uint4*>(tk + run0 + 256u * h);
+    for (int h = 0; h < EMIT_GROUPS; h++) {
+      pbm[h] = ld_bm(run0 + 256u * h);
+      ld_in(run0 + 256u * h, pin_lo[h], pin_hi[h]);
+    }
+  } else {
+#pragma unroll
+    for (int h = 0; h < EMIT_GROUPS; h++) pre[h] = *reinterpret_cast<const uint4*>(tk + run0 + 256u * h);
+  }
   for (uint32_t i = tid; i < 320; i += EMIT_THREADS) S.codes[i] = codes_in[(uint64_t)g * 320 + i];
   if (tid >= 512u && tid < 512u + 29u) S.codes[EMIT_LEN_TAB + tid - 512u] = kLenBase[tid - 512u] | ((uint32_t)kLenXbits[tid - 512u] << 16);
   if (tid >= 576u && tid < 576u + 30u) S.codes[EMIT_DIST_TAB + tid - 576u] = kDistBase[tid - 576u] | ((uint32_t)kDistXbits[tid - 576u] << 16);
@@ -3393,14 +3487,42 @@ __global__ __launch_bounds__(EMIT_THREADS, 8) void k_emit(uint8_t* __restrict__ 
   uint64_t cur_bit = bk.bit_off + 3u + bk.hdr_bits;  // uniform
   EMIT_STAMP(0);
 
-  // tokens 0 .. ntok - 1 and EOB as item ntok
-  for (uint32_t t0 = 0; t0 <= ntok; t0 += EMIT_TILE) {
+  if constexpr (POS) {  // the first tile's nibbles are here by now: its match words, and the second tile's bit map words
+#pragma unroll
+    for (int h = 0; h < EMIT_GROUPS; h++) {
+      const uint32_t p = run0 + 256u * h;
+      const uint32_t nb = nibbles(pbm[h], p);
+      pnb |= nb << (8 * h);
+      pmw[h] = ld_mw(p, nb);
+      pbm[h] = ld_bm(EMIT_TILE + p);
+    }
+  }
+  // tokens 0 .. ntok - 1 and EOB as item ntok; the position form: positions 0 .. len - 1 and EOB as item len
+  const uint32_t nitem = POS ? bk.len : ntok;
+  for (uint32_t t0 = 0; t0 <= nitem; t0 += EMIT_TILE) {
     uint4 q[EMIT_GROUPS];
+    uint32_t qnb = 0;
+    if constexpr (POS) {  // q: the group's input word, shifted into place, and its match word
+      qnb = pnb;
+      pnb = 0;
 #pragma unroll
-    for (int h = 0; h < EMIT_GROUPS; h++) q[h] = pre[h];
+      for (int h = 0; h < EMIT_GROUPS; h++) {
+        q[h].x = MIS ? __builtin_amdgcn_alignbyte(pin_hi[h], pin_lo[h], mis) : pin_lo[h];
+        q[h].y = pmw[h];
+        const uint32_t p = t0 + EMIT_TILE + run0 + 256u * h;
+        const uint32_t nb = nibbles(pbm[h], p);
+        pnb |= nb << (8 * h);
+        ld_in(p, pin_lo[h], pin_hi[h]);
+        pmw[h] = ld_mw(p, nb);
+        pbm[h] = ld_bm(p + EMIT_TILE);
+      }
+    } else {
 #pragma unroll
-    for (int h = 0; h < EMIT_GROUPS; h++)
-      pre[h] = *reinterpret_cast<const uint4*>(tk + min(t0 + EMIT_TILE + run0 + 256u * h, ZES_BLK - 4u));
+      for (int h = 0; h < EMIT_GROUPS; h++) q[h] = pre[h];
+#pragma unroll
+      for (int h = 0; h < EMIT_GROUPS; h++)
+        pre[h] = *reinterpret_cast<const uint4*>(tk + min(t0 + EMIT_TILE + run0 + 256u * h, ZES_BLK - 4u));
+    }
     // 1. each group becomes one piece (literals only) or four (value, nbits) items; nbp: the bit counts, a byte each
     uint64_t val[EMIT_GROUPS][4];
     uint32_t nbp[EMIT_GROUPS], sum[EMIT_GROUPS];
@@ -3408,9 +3530,43 @@ __global__ __launch_bounds__(EMIT_THREADS, 8) void k_emit(uint8_t* __restrict__ 
 #pragma unroll
     for (int h = 0; h < EMIT_GROUPS; h++) {
       const uint32_t ws = t0 + wave * EMIT_WAVE_RUN + 256u * h;  // the wave's first token of this group (uniform)
-      const uint32_t tv[4] = {q[h].x, q[h].y, q[h].z, q[h].w};
-      const bool full = ws + 256u <= ntok;  // all of the wave's 256 are tokens of the block
-      one[h] = full && __ballot(((tv[0] | tv[1] | tv[2] | tv[3]) & ZES_TOK_MATCH) != 0u) == 0ull;
+      const bool full = ws + 256u <= nitem;  // all of the wave's 256 are tokens of the block
+      uint32_t tv[4], none = 0;
+      if constexpr (POS) {
+        const uint32_t nb = (qnb >> (8 * h)) & 0xffu;
+        tv[0] = q[h].x & 0xffu;
+        tv[1] = (q[h].x >> 8) & 0xffu;
+        tv[2] = (q[h].x >> 16) & 0xffu;
+        tv[3] = q[h].x >> 24;
+        one[h] = full && __ballot(nb != 15u) == 0ull;  // every position on the chain, no start
+        if (!one[h] && ws <= nitem) {
+          const uint32_t p0 = ws + lane * 4u;
+          const int left = (int)nitem - (int)p0;  // positions of the block from p0 on; slot `left` is EOB, nothing behind it
+          const uint32_t in_blk = left >= 4 ? 15u : left <= 0 ? 0u : (1u << left) - 1u;
+          const uint32_t chain = nb & in_blk, starts = (nb >> 4) & chain;
+          none = ~chain & 15u;
+          if ((uint32_t)left < 4u) none &= ~(1u << left);
+          const uint32_t more = starts & (starts - 1u);  // a second start: behind a match of three bytes at the group's first position
+#pragma unroll
+          for (int k = 0; k < 4; k++) {
+            // (a start whose word holds no match stays the literal of its byte, as in k_lz_parse's token pass)
+            if ((starts & ~more & (1u << k)) && (q[h].y & ZES_TOK_MATCH)) tv[k] = q[h].y;
+            if (k == left) tv[k] = 256u;
+          }
+          if (__ballot(more != 0u) != 0ull) {  // (rare; the load and its wait stay inside this branch)
+            const uint32_t mw2 = mi[more ? min(p0 + (uint32_t)__ffs((int)more) - 1u, ZES_BLK - 1u) : lane];
+#pragma unroll
+            for (int k = 0; k < 4; k++)
+              if ((more & (1u << k)) && (mw2 & ZES_TOK_MATCH)) tv[k] = mw2;
+          }
+        }
+      } else {
+        tv[0] = q[h].x;
+        tv[1] = q[h].y;
+        tv[2] = q[h].z;
+        tv[3] = q[h].w;
+        one[h] = full && __ballot(((tv[0] | tv[1] | tv[2] | tv[3]) & ZES_TOK_MATCH) != 0u) == 0ull;
+      }
       val[h][1] = val[h][2] = val[h][3] = 0;
       if (one[h]) {  // four literals (src/deflate.ts:212-219): two pairs of at most 30 bits, then one 64-bit shift
         const uint32_t c0 = S.codes[tv[0]], c1 = S.codes[tv[1]], c2 = S.codes[tv[2]], c3 = S.codes[tv[3]];
@@ -3421,9 +3577,9 @@ __global__ __launch_bounds__(EMIT_THREADS, 8) void k_emit(uint8_t* __restrict__ 
       } else {
         val[h][0] = 0;
         sum[h] = nbp[h] = 0;
-        if (ws <= ntok) {  // (a group wholly behind EOB has nothing)
-          if (full) emit_items<false>(S.codes, tv, ws + lane * 4u, ntok, val[h], nbp[h], sum[h]);
-          else emit_items<true>(S.codes, tv, ws + lane * 4u, ntok, val[h], nbp[h], sum[h]);
+        if (ws <= nitem) {  // (a group wholly behind EOB has nothing)
+          if (POS || full) emit_items<false>(S.codes, tv, ws + lane * 4u, ntok, none, val[h], nbp[h], sum[h]);  // (the position form has its tail in tv and none)
+          else emit_items<true>(S.codes, tv, ws + lane * 4u, ntok, 0u, val[h], nbp[h], sum[h]);
           if (__ballot(sum[h] > 64u) == 0ull) {  // three literals and a common match: one piece in every lane after all
             const uint32_t n0 = nbp[h] & 0xffu, n1 = n0 + ((nbp[h] >> 8) & 0xffu), n2 = n1 + ((nbp[h] >> 16) & 0xffu);
             val[h][0] |= (val[h][1] << (n0 & 63u)) | (val[h][2] << (n1 & 63u)) | (val[h][3] << (n2 & 63u));  // (an item without bits is 0)
@@ -3476,7 +3632,7 @@ __global__ __launch_bounds__(EMIT_THREADS, 8) void k_emit(uint8_t* __restrict__ 
     // 4. flush complete dwords, each cleared behind its read; the trailing partial dword moves to word 0 for the next tile
     const uint64_t first_dw = cur_bit >> 5;
     const uint32_t end_bits = head + tile_bits;
-    const bool last_tile = t0 + EMIT_TILE > ntok;
+    const bool last_tile = t0 + EMIT_TILE > nitem;
     const uint32_t ncomplete = last_tile ? (end_bits + 31u) >> 5 : end_bits >> 5;
     for (uint32_t i = tid; i < ncomplete; i += EMIT_THREADS) {
       const uint64_t gw = first_dw + i;
@@ -3498,6 +3654,26 @@ __global__ __launch_bounds__(EMIT_THREADS, 8) void k_emit(uint8_t* __restrict__ 
     d[0] = st_first;
     d[1] = (unsigned long long)clock64();
     for (int i = 0; i < 5; i++) d[2 + i] = st_acc[i];
+  }
+}
+
+// The front end is chosen per workgroup: a block that k_lz_parse_small parsed from its match list is in the position form
+// (the head word of its list says so, as it told the two parse kernels which of them the block belongs to; it is loaded
+// beside the block's record, not in front of it: one memory latency at the head of a workgroup, not two)
+__global__ __launch_bounds__(EMIT_THREADS, 8) void k_emit(uint8_t* __restrict__ d_out, const ZesBuf* __restrict__ bufs,
+                                                       const ZesBlk* __restrict__ blks, const uint32_t* __restrict__ tok_in,
+                                                       const uint32_t* __restrict__ codes_in, const uint32_t* __restrict__ hdr_in,
+                                                       const uint8_t* __restrict__ d_in, const uint32_t* __restrict__ match_in,
+                                                       const uint32_t* __restrict__ mlist_all) {
+  __shared__ EmitSmem S;
+  const uint32_t nml = mlist_all[(uint64_t)blockIdx.x * ZES_MLIST_WORDS];
+  const ZesBlk bk = blks[blockIdx.x];
+  const ZesBuf bf = bufs[bk.buf];
+  if (nml <= ZES_MLIST_CAP) {
+    if ((reinterpret_cast<uintptr_t>(d_in) + bf.in_off) & 3u) emit_body<true, true>(S, d_out, bk, bf, tok_in, codes_in, hdr_in, d_in, match_in);
+    else emit_body<true, false>(S, d_out, bk, bf, tok_in, codes_in, hdr_in, d_in, match_in);
+  } else {
+    emit_body<false, false>(S, d_out, bk, bf, tok_in, codes_in, hdr_in, d_in, match_in);
   }
 }
 

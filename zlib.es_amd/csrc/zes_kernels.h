@@ -48,6 +48,11 @@
 // k_lz_match -> k_lz_parse, per block: [0] = matches found (all ones: a block of k_lz_match_lazy), [1..] the first ZES_MLIST_CAP of them as position | (length - 3) << 17
 #define ZES_MLIST_CAP 4095u
 #define ZES_MLIST_WORDS 4096u
+// k_lz_parse_small -> k_emit, a block parsed from its match list in the pipeline (head word of the list <= ZES_MLIST_CAP):
+// the position form.  No token list: the block's row of the token area begins with a pair of words per 32 positions, a
+// bit each: [2 i] the position is on the greedy chain, [2 i + 1] a taken match starts there.  A chain position's token is
+// the input byte, a taken start's the match word k_lz_match left at the position
+#define ZES_POS_WORDS (2u * (131072u / 32u))
 #define PAR_THREADS 1024
 #define PAR_WAVES (PAR_THREADS / 64)
 #define INF_SCAN_THREADS 256
@@ -391,7 +396,7 @@ __global__ void k_lz_match_lazy(const uint8_t*, const ZesBuf*, const ZesBlk*, co
 __global__ void k_lz_order(const uint32_t*, uint32_t, uint32_t*);
 __global__ void k_lz_match(const uint8_t*, const ZesBuf*, const ZesBlk*, const uint32_t*, uint32_t*, uint32_t*);
 __global__ void k_lz_parse(const uint8_t*, const ZesBuf*, ZesBlk*, const uint32_t*, uint32_t*, uint32_t*, const uint32_t*, const uint32_t*);
-__global__ void k_lz_parse_small(const uint8_t*, const ZesBuf*, ZesBlk*, const uint32_t*, uint32_t*, uint32_t*, const uint32_t*, const uint32_t*);
+__global__ void k_lz_parse_small(const uint8_t*, const ZesBuf*, ZesBlk*, const uint32_t*, uint32_t*, uint32_t*, const uint32_t*, const uint32_t*, uint32_t);
 __global__ void k_huff(ZesBlk*, const uint32_t*, uint32_t*, uint32_t*);
 __global__ void k_huff_lengths_only(const uint32_t*, uint32_t, uint32_t, uint8_t*);
 __global__ void k_selftest_lds_order(unsigned long long*, uint32_t, uint32_t);
@@ -417,7 +422,8 @@ __global__ void k_crc32_put(const unsigned int*, const ZesCrcPut*, uint32_t, uin
 __global__ void k_adler_blocks(const uint8_t*, const ZesBuf*, const ZesBlk*, unsigned long long*);
 __global__ void k_adler_seg(const uint8_t*, const ZesCrcSeg*, const uint2*, unsigned long long*);
 __global__ void k_layout(uint8_t*, const ZesBuf*, ZesBlk*, const unsigned long long*, ZesRes*);
-__global__ void k_emit(uint8_t*, const ZesBuf*, const ZesBlk*, const uint32_t*, const uint32_t*, const uint32_t*);
+__global__ void k_emit(uint8_t*, const ZesBuf*, const ZesBlk*, const uint32_t*, const uint32_t*, const uint32_t*, const uint8_t*, const uint32_t*,
+                       const uint32_t*);
 __global__ void k_zero_u64(unsigned long long*, uint32_t);
 __global__ void k_bits_place(uint32_t*, uint64_t, const uint32_t*, uint64_t);
 #endif
