@@ -270,6 +270,69 @@ int zes_gunzip(const uint8_t* in, uint64_t c, uint8_t* out, uint64_t cap, uint64
 int zes_gunzip_dev(const uint8_t* d_in, uint64_t c, uint8_t* d_out, uint64_t cap, uint64_t* out_len, uint32_t flags);
 int zes_gunzip_alloc(const uint8_t* in, uint64_t c, zes_alloc_fn alloc, void* user, uint64_t* out_len, uint32_t flags);
 
+/* zes_gzip_batch*: many independent buffers, one gzip file each, in one call whose launches, copies and synchronisations do
+ * not grow with the number of files.  File i is one member:
+ *   header   zes_gzip's: 1f 8b 08 00 00 00 00 00 00 ff
+ *   body     the bytes of zes_deflate_raw when the encoder accepts the length (not 0, 1 or 1 mod 131072) and that stream is
+ *            shorter than the stored form; otherwise the stored form: blocks of 65535 bytes, 00 | LEN | NLEN | the bytes,
+ *            BFINAL (01) on the last one; length 0 is the one block 01 00 00 ff ff.  So every length below 2^32 writes, and
+ *            where the stream is kept the file is byte for byte zes_gzip's.  The same inputs give the same bytes
+ *   trailer  the CRC-32 of the input, then ISIZE, both little-endian
+ * in_off, in_len, out_off, out_cap, out_len and status are host arrays of `count` values.  The return value is non-zero only
+ * when the call as a whole could not run; count == 0 is ZES_OK without device work.
+ *   status[i]  ZES_OK: out_len[i] bytes written
+ *              ZES_E_UNSUPPORTED: in_len[i] >= 2^32 (ISIZE stays exact), decided before any launch; out_len[i] = 0
+ *              ZES_E_NOSPACE (device form): out_cap[i] is too small or d_out is null; the file is still encoded, out_len[i] is
+ *              the size needed and nothing of it is written — a call with every capacity 0 is a sizing pass
+ *              ZES_E_ARG (host form): alloc returned NULL for the file
+ *   ZES_E_ARG for the whole call: a null array with count != 0, a null d_in / in[i] with a non-zero length, a null alloc,
+ *              flag bits other than ZES_F_PIECES
+ * zes_gzip_batch_bound: cap[i] = 18 + n + 5 * max(1, ceil(n / 65535)), exact when the file is stored and always enough (0 for
+ * a length of 2^32 and more); it touches no device.
+ * The device form takes d_in, d_out and every offset at ANY alignment, writes exactly out_len[i] bytes for a file at ZES_OK
+ * and no byte outside the ranges [out_off[i], out_off[i] + out_cap[i]), which must not overlap, and reads the input only
+ * inside the aligned 16-byte groups that hold it.  The host form calls alloc(user, i, n) once per file at ZES_OK, behind the
+ * device work.  Everything runs on one context.
+ * Launches: the files are encoded in groups (1024 files whose encoder slots take up to 256 MiB; ZES_F_PIECES: 4 and 1 MiB —
+ * same bytes); a group costs one segmented CRC-32 launch, one batch encode with its one read-back of the sizes, and one
+ * k_gz_pack launch that writes headers, bodies and trailers.  Nothing is launched per file.
+ * replaces: nothing (the reference has no gzip container); the bodies are `deflate` of src/deflate.ts:14-39 per buffer. */
+int zes_gzip_batch_bound(const uint64_t* in_len, uint32_t count, uint64_t* cap /* count values */);
+int zes_gzip_batch_dev(const uint8_t* d_in, const uint64_t* in_off, const uint64_t* in_len, uint32_t count, uint8_t* d_out,
+                       const uint64_t* out_off, const uint64_t* out_cap, uint64_t* out_len, int32_t* status, uint32_t flags);
+int zes_gzip_batch(const uint8_t* const* in, const uint64_t* in_len, uint32_t count, zes_alloc_fn alloc, void* user,
+                   uint64_t* out_len, int32_t* status, uint32_t flags);
+
+/* zes_gunzip_batch*: many independent gzip files decoded in one call.  status[i], out_len[i] and the bytes are exactly what
+ * zes_gunzip_dev (zes_gunzip_alloc) gives for file i alone with out_cap[i] as its capacity, for every file, good or bad: the
+ * batch is a route, not a second rule.  Arrays, return value and count == 0 as for zes_gzip_batch*.
+ *   1. One k_gz_heads launch (the host forms: the same rule on the caller's memory) judges every file a candidate or not; it
+ *      never gives a status.  A candidate has in_len >= 18, starts 1f 8b 08, has FLG bits 5-7 and FHCRC clear, a header
+ *      (FEXTRA, FNAME, FCOMMENT walked by RFC 1952) that ends within 256 bytes and at least 8 bytes before the file's end,
+ *      no subfield 'B','C' of SLEN 2 that states a member size below in_len (a BGZF file keeps its member-parallel route
+ *      through step 3), and an ISIZE (the file's last 4 bytes) of at most out_cap[i] (device form) and at most 1032 times
+ *      the body's length (a lying trailer cannot grow the scratch).
+ *   2. The candidates' bodies [hlen, in_len - 8) go as one batch: one gather, one pass through the inflate tiers, one
+ *      segmented CRC-32 launch.  A candidate is done when its stream ends in the body's last byte, its output is exactly
+ *      ISIZE bytes and the CRC-32 matches: zes_gunzip's checks for a single-member file.
+ *   3. Every other file — no candidate, or a candidate that step 2 did not pass: two members, padding, a corrupt body, a
+ *      wrong trailer — goes through zes_gunzip_dev's path, in order; that path decides its status, size and bytes.
+ *      ZES_F_GZIP_SERIAL sends every file this way (testing aid, yardstick).
+ * flags: ZES_F_PIECES, ZES_F_GZIP_SERIAL; others are ZES_E_ARG for the whole call, as are a null array with count != 0, a null
+ * d_in / in[i] with a non-zero length, a null d_out with a non-zero capacity and a null alloc.
+ * The device form takes d_in, d_out and every offset at ANY alignment, writes exactly out_len[i] bytes for a file at ZES_OK
+ * and no byte outside the ranges [out_off[i], out_off[i] + out_cap[i]), which must not overlap (a file that fails may leave
+ * bytes inside its own range), and reads the input only inside the aligned 16-byte groups that hold it.
+ * zes_gunzip_batch_alloc verifies every file first, then calls alloc(user, i, n) once per file at ZES_OK, in order, and
+ * never for a failed one; NULL from alloc is that file's ZES_E_ARG.  Everything runs on one context.
+ * zes_last_gunzip_batch: how many files of this thread's last zes_gunzip_batch* call finished in step 2 and in step 3.
+ * replaces: nothing (the reference has no gzip container). */
+int zes_gunzip_batch_dev(const uint8_t* d_in, const uint64_t* in_off, const uint64_t* in_len, uint32_t count, uint8_t* d_out,
+                         const uint64_t* out_off, const uint64_t* out_cap, uint64_t* out_len, int32_t* status, uint32_t flags);
+int zes_gunzip_batch_alloc(const uint8_t* const* in, const uint64_t* in_len, uint32_t count, zes_alloc_fn alloc, void* user,
+                           uint64_t* out_len, int32_t* status, uint32_t flags);
+int zes_last_gunzip_batch(uint32_t* batched, uint32_t* serial);   /* files of the last batch call by route */
+
 /* BGZF random access: the member index of a BGZF file, and reads of any range of its uncompressed data that decode only
  * the members holding that range (what htslib does with a .gzi index).
  *

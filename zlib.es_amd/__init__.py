@@ -168,6 +168,13 @@ def lib():
         L.zes_pngpix_alloc.argtypes = L.zes_png_decode_alloc.argtypes
         L.zes_pngpix_expand_dev.argtypes = L.zes_pngwrite_dev.argtypes
         L.zes_gunzip_alloc.argtypes = [C.c_void_p, C.c_uint64, ALLOC_FN, C.c_void_p, u64p, C.c_uint32]
+        L.zes_gzip_batch_bound.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p]
+        for name in ("zes_gzip_batch_dev", "zes_gunzip_batch_dev"):
+            getattr(L, name).argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                         C.c_uint32]
+        for name in ("zes_gzip_batch", "zes_gunzip_batch_alloc"):
+            getattr(L, name).argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, ALLOC_FN, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32]
+        L.zes_last_gunzip_batch.argtypes = [u32p, u32p]
         L.zes_adler32.argtypes = [C.c_void_p, C.c_uint64, u32p]
         L.zes_adler32_dev.argtypes = [C.c_void_p, C.c_uint64, u32p]
         L.zes_adler32_batch_dev.argtypes = [C.c_void_p, u64p, u64p, u32p, C.c_uint32]
@@ -779,6 +786,56 @@ def gunzip(data, flags=0):
     return got[0][: n.value]
 
 
+def gzip_batch_bound(lens):
+    """zes_gzip_batch_bound: the room that file i of gzip_batch_tensor needs at most, ``18 + n + 5 * max(1, ceil(n / 65535))``."""
+    ln = np.ascontiguousarray(lens, dtype=np.uint64).reshape(-1)
+    cap = np.zeros(max(ln.size, 1), dtype=np.uint64)
+    rc = lib().zes_gzip_batch_bound(_ptr(ln), ln.size, cap.ctypes.data)
+    if rc:
+        _raise(rc)
+    return [int(x) for x in cap[: ln.size]]
+
+
+def _host_batch(fn, buffers, flags):
+    """zes_gzip_batch / zes_gunzip_batch_alloc over a list of buffers: one uint8 array or one ZlibEsError (not raised) per buffer."""
+    arrs = [_as_u8(b) for b in buffers]
+    cnt = len(arrs)
+    got = {}
+
+    def alloc(_user, i, n):
+        got[i] = np.empty(max(int(n), 1), dtype=np.uint8)
+        return got[i].ctypes.data
+
+    ptrs = (C.c_void_p * max(cnt, 1))(*[a.ctypes.data if a.size else None for a in arrs])
+    ln = np.array([a.size for a in arrs], dtype=np.uint64)
+    out_len = np.zeros(max(cnt, 1), dtype=np.uint64)
+    status = np.zeros(max(cnt, 1), dtype=np.int32)
+    rc = fn(ptrs, _ptr(ln), cnt, ALLOC_FN(alloc), None, out_len.ctypes.data, status.ctypes.data, flags)
+    if rc:
+        _raise(rc)
+    return [got[i][: int(out_len[i])] if status[i] == 0 else ZlibEsError(int(status[i]), strerror(int(status[i]))) for i in range(cnt)]
+
+
+def gzip_batch(buffers, flags=0):
+    """Independent buffers written as one gzip file each in one batch (zes_gzip_batch): the result has one uint8 array (the
+    file: gzip()'s bytes, or the stored form where that is shorter or the encoder refuses the length) or one ZlibEsError per
+    buffer (not raised).  ``flags``: ZES_F_PIECES for groups of four (same bytes)."""
+    return _host_batch(lib().zes_gzip_batch, buffers, flags)
+
+
+def gunzip_batch(buffers, flags=0):
+    """Independent gzip files decoded in one batch (zes_gunzip_batch_alloc): per file what gunzip() gives for it alone, a uint8
+    array or the ZlibEsError (not raised).  ``flags``: ZES_F_PIECES, ZES_F_GZIP_SERIAL (every file on the per-file route)."""
+    return _host_batch(lib().zes_gunzip_batch_alloc, buffers, flags)
+
+
+def last_gunzip_batch():
+    """``(batched, serial)``: the files of the last gunzip batch call that finished as one batch and on the per-file route."""
+    a, b = C.c_uint32(), C.c_uint32()
+    lib().zes_last_gunzip_batch(C.byref(a), C.byref(b))
+    return a.value, b.value
+
+
 def adler32(data):
     a = _as_u8(data)
     out = C.c_uint32()
@@ -927,6 +984,75 @@ def gunzip_tensor(t, out, flags=0):
     rc = lib().zes_gunzip_dev(t.data_ptr(), t.numel(), out.data_ptr(), out.numel(), C.byref(n), flags)
     _raise_need(rc, n)
     return out[: n.value]
+
+
+def _gz_batch_tensor(fn, who, bound, d_in, in_off, in_len, out, off, cap, flags):
+    """gzip_batch_tensor and gunzip_batch_tensor: the same arguments and placement; ``bound()``: every item's room when ``off``
+    is not given."""
+    import torch
+
+    assert d_in.is_cuda and d_in.dtype == torch.uint8 and d_in.is_contiguous()
+    ioff = np.ascontiguousarray(in_off, dtype=np.uint64)
+    ilen = np.ascontiguousarray(in_len, dtype=np.uint64)
+    cnt = ilen.size
+    assert ioff.ndim == 1 and ioff.shape == ilen.shape, "%s: one offset and one length per file" % who
+    assert all(int(o) + int(n) <= d_in.numel() for o, n in zip(ioff, ilen)), "%s: a file reaches beyond `d_in`" % who
+    torch.cuda.current_stream(d_in.device).synchronize()
+    out_len = np.zeros(max(cnt, 1), dtype=np.uint64)
+    status = np.zeros(max(cnt, 1), dtype=np.int32)
+    src = d_in.data_ptr() if d_in.numel() else None
+
+    def call(dst, o, c):
+        rc = fn(src, _ptr(ioff), _ptr(ilen), cnt, dst, _ptr(o), _ptr(c), out_len.ctypes.data, status.ctypes.data, flags)
+        if rc:
+            _raise(rc)
+
+    if off is None:
+        sizes = (np.array(bound(call, cnt, status, out_len), dtype=np.uint64).reshape(-1)[:cnt] + np.uint64(15)) & ~np.uint64(15)
+        off = np.concatenate([np.zeros(1, dtype=np.uint64), np.cumsum(sizes, dtype=np.uint64)])[:cnt]
+        if out is None:
+            out = torch.empty(int(sizes.sum()), dtype=torch.uint8, device=d_in.device)
+        if cap is None:
+            cap = sizes
+    off = np.ascontiguousarray(off, dtype=np.uint64)
+    assert off.size == cnt, "%s: one offset per file" % who
+    if cap is None:
+        cap = np.array([max((out.numel() if out is not None else 0) - int(o), 0) for o in off], dtype=np.uint64)
+    cap = np.ascontiguousarray(cap, dtype=np.uint64)
+    assert cap.size == cnt, "%s: one capacity per file" % who
+    if out is not None:
+        assert out.is_cuda and out.dtype == torch.uint8 and out.is_contiguous()
+        assert all(int(o) + int(c) <= out.numel() for o, c in zip(off, cap)), "%s: a place reaches beyond `out`" % who
+    call(out.data_ptr() if out is not None and out.numel() else None, off, cap)
+    return out, off, [int(x) for x in out_len[:cnt]], [int(x) for x in status[:cnt]]
+
+
+def gzip_batch_tensor(d_in, in_off, in_len, out=None, off=None, cap=None, flags=0):
+    """Buffers in a 1-D uint8 CUDA tensor written as one gzip file each in one batch (zes_gzip_batch_dev): buffer i is
+    ``d_in[in_off[i] : in_off[i] + in_len[i]]``.  Returns ``(out, off, out_len, status)``: file i is
+    ``out[off[i] : off[i] + out_len[i]]`` when ``status[i]`` is 0, and nothing else of ``out`` is written.  ``d_in``, ``out`` and
+    every offset may be any byte.  Without ``off`` the files are placed at 16-byte boundaries with gzip_batch_bound()'s room
+    each and ``out`` is allocated when it is None.  ``cap``: the capacity of every file's place (default: the bound, or up to
+    the end of ``out`` with ``off``); a file that needs more is ZES_E_NOSPACE with its ``out_len`` the size needed, so a call
+    with ``out=None`` and zero capacities is a sizing pass."""
+    return _gz_batch_tensor(lib().zes_gzip_batch_dev, "gzip_batch_tensor", lambda call, cnt, status, out_len: gzip_batch_bound(in_len), d_in, in_off,
+                            in_len, out, off, cap, flags)
+
+
+def gunzip_batch_tensor(d_in, in_off, in_len, out=None, off=None, cap=None, flags=0):
+    """gzip files in a 1-D uint8 CUDA tensor decoded in one batch (zes_gunzip_batch_dev): file i is
+    ``d_in[in_off[i] : in_off[i] + in_len[i]]``.  Returns ``(out, off, out_len, status)``: per file what gunzip_tensor gives for
+    it alone with ``cap[i]`` as its capacity; output i is ``out[off[i] : off[i] + out_len[i]]`` when ``status[i]`` is 0.  ``d_in``,
+    ``out`` and every offset may be any byte.  Without ``off`` a sizing pass comes first and the outputs are packed at 16-byte
+    boundaries from the start of ``out``, which is allocated when it is None.  ``cap``: as in gzip_batch_tensor.  ``flags``:
+    ZES_F_PIECES, ZES_F_GZIP_SERIAL (every file on the per-file route)."""
+
+    def sizes(call, cnt, status, out_len):
+        zeros = np.zeros(max(cnt, 1), dtype=np.uint64)
+        call(None, zeros, zeros)
+        return np.where(status[:cnt] == ZES_E_NOSPACE, out_len[:cnt], 0)
+
+    return _gz_batch_tensor(lib().zes_gunzip_batch_dev, "gunzip_batch_tensor", sizes, d_in, in_off, in_len, out, off, cap, flags)
 
 
 def bgzf_index_tensor(t, flags=0):

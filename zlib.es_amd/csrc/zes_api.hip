@@ -6,6 +6,7 @@
 #include "../../include/zes.h"
 #include "zes_kernels.h"
 #include "zes_chain.h"
+#include "zes_gzbatch.h"
 
 #include <algorithm>
 #include <atomic>
@@ -165,7 +166,9 @@ static_assert(disjoint({PIN_SPAN(t2.search), PIN_SPAN(t2.ncand), PIN_SPAN(t2.nsu
   /* zes_pngpix*: the unfiltered scanlines of a batch, a padded slot an image, on their way to k_png_expand; */                   \
   /* ZES_F_PNG_INTERLACED: the unfiltered passes of a batch's Adam7 images, a padded slot an image, on their way to */            \
   /* k_png_deinterlace */                                                                                                         \
-  X(png_lines) X(png_passes)
+  X(png_lines) X(png_passes)                                                                                                      \
+  /* zes_gunzip_batch*: the output of a file on the per-file route that cannot be decoded in its place */                         \
+  X(gz_batch)
 
 // The survivor list of the block-start search as the block-parallel tier's scan left it in a pool (one buffer): the
 // segment-parallel tier's search of the same stream starts from it instead of scanning again.  The note holds until it
@@ -216,6 +219,7 @@ struct Ctx {
   int last_tier = 0;
   bool device_chain = false;  // the block-parallel tier follows a single buffer's chain with k_inf_chain too, not on the host (pngpix_core)
   int last_members = 0;  // members the member-parallel gzip reader decoded in the last gunzip call (0: the serial path answered)
+  uint32_t last_gzb[2] = {0, 0};  // files of the last zes_gunzip_batch* call that finished as one batch / on the per-file route
   uint32_t route[ZES_ROUTE_WORDS] = {0};  // zes_stage_lz77_dev's last block: what its kernels did (zes_stage_lz77_route)
   SurvList sv;  // (of `surv`)
   char arch[64] = {0};
@@ -6339,6 +6343,388 @@ int zes_pngpix_expand_dev(const uint8_t* d_in, const uint64_t* in_off, const uin
   return call_done(pngx_run(d_in, nullptr, d_out, table, njobs, tiles), true);
 }
 
+// ---- gzip files as one batch (include/zes.h: "zes_gzip_batch*", "zes_gunzip_batch*") ----
+constexpr uint64_t GZB_LEN_MAX = 0xFFFFFFFFull;  // (ISIZE is exact up to here)
+static uint64_t gzip_batch_cap(uint64_t n) { return 18 + zes_gz_stored_len(n); }
+
+// What both writer forms decide from the arguments alone (`data(i)`: file i's bytes are there): ZES_E_ARG, then every file's
+// status, ZES_E_UNSUPPORTED for a length that ISIZE cannot state.  *any: a file is left to encode
+static int gzip_batch_args(const std::function<bool(uint32_t)>& data, const uint64_t* in_len, uint32_t count, uint64_t* out_len, int32_t* status,
+                           uint32_t flags, bool* any) {
+  *any = false;
+  if (flags & ~ZES_F_PIECES) return ZES_E_ARG;
+  if (count && (!in_len || !out_len || !status)) return ZES_E_ARG;
+  for (uint32_t i = 0; i < count; i++)
+    if (in_len[i] && !data(i)) return ZES_E_ARG;
+  for (uint32_t i = 0; i < count; i++) {
+    status[i] = in_len[i] > GZB_LEN_MAX ? ZES_E_UNSUPPORTED : ZES_OK;
+    out_len[i] = 0;
+    *any = *any || status[i] == ZES_OK;
+  }
+  return ZES_OK;
+}
+
+// The files whose status[i] is ZES_OK on entry, file i's bytes at d_in + in_off[i], its gzip file to d_out + out_off[i] when it
+// fits out_cap[i] (and d_out is there), else ZES_E_NOSPACE with the size needed.  Group by group as zipwrite_core goes
+// (EncGroup::form over the lengths): EncGroup::encode with its one CRC-32 launch, whose read-back is the group's, the host
+// chooses stream or stored form per file, and one k_gz_pack launch writes the group's files.  g.gz_tab holds the group's
+// records; every group's records, which asynchronous uploads read, stay until the end of the call, in front of a Drain.
+static int gzip_batch_core(const uint8_t* d_in, const uint64_t* in_off, const uint64_t* in_len, uint32_t count, uint8_t* d_out, const uint64_t* out_off,
+                           const uint64_t* out_cap, uint64_t* out_len, int32_t* status, uint32_t flags) {
+  int rc;
+  g.carry.clear();
+  g.last_tier = 0;
+  std::vector<uint32_t> live;
+  std::vector<uint64_t> l_off, l_len;
+  for (uint32_t i = 0; i < count; i++)
+    if (status[i] == ZES_OK) {
+      live.push_back(i);
+      l_off.push_back(in_off[i]);
+      l_len.push_back(in_len[i]);
+    }
+  const uint32_t nlive = (uint32_t)live.size();
+  std::deque<std::vector<ZesGzPackRec>> tables;
+  EncGroup eg(flags, nlive);
+  Drain drain;  // (behind the tables and eg)
+  for (uint32_t e0 = 0; e0 < nlive;) {
+    uint64_t slots;
+    const uint32_t cnt = eg.form(&l_len[e0], nlive - e0, &slots);
+    if ((rc = eg.encode(d_in, &l_off[e0], &l_len[e0], cnt, slots))) return rc;
+    tables.emplace_back();
+    std::vector<ZesGzPackRec>& recs = tables.back();
+    uint64_t wgs = 0;
+    for (uint32_t k = 0; k < cnt; k++) {
+      const uint32_t i = live[e0 + k];
+      const uint64_t len = l_len[e0 + k], stored_len = zes_gz_stored_len(len);
+      const bool stream = eg.o_cap[k] && eg.raw[k] < stored_len;
+      const uint64_t body = stream ? eg.raw[k] : stored_len;
+      out_len[i] = 18 + body;
+      if (!d_out || out_len[i] > out_cap[i]) {
+        status[i] = ZES_E_NOSPACE;
+        continue;
+      }
+      ZesGzPackRec r;
+      memset(&r, 0, sizeof r);
+      r.src_off = stream ? eg.o_off[k] + 2 : l_off[e0 + k];
+      r.dst_off = out_off[i];
+      r.body_len = body;
+      r.len = (uint32_t)len;
+      r.crc = eg.crc[k];
+      r.first_wg = (uint32_t)wgs;
+      r.stored = stream ? 0u : 1u;
+      recs.push_back(r);
+      wgs += std::min<uint64_t>(std::max<uint64_t>((body + GZ_GATHER_PIECE - 1) / GZ_GATHER_PIECE, 1), ZES_GZ_PACK_SHARES);
+    }
+    e0 += cnt;
+    if (recs.empty()) continue;
+    if (wgs > 0x7fffffffull) return ZES_E_ARG;
+    const uint32_t nrec = (uint32_t)recs.size();
+    ZesGzPackRec end;
+    memset(&end, 0, sizeof end);
+    end.first_wg = (uint32_t)wgs;
+    recs.push_back(end);
+    if ((rc = ensure(g.gz_tab, sizeof(ZesGzPackRec) * recs.size()))) return rc;
+    HIPCHK(hipMemcpyAsync(g.gz_tab.p, recs.data(), sizeof(ZesGzPackRec) * recs.size(), hipMemcpyHostToDevice, g.stream));
+    {
+      Timed t("k_gz_pack");
+      hipLaunchKernelGGL(k_gz_pack, dim3((uint32_t)wgs), dim3(GZ_GATHER_THREADS), 0, g.stream, d_in, (const uint8_t*)g.gz_bodies.p, d_out,
+                         (const ZesGzPackRec*)g.gz_tab.p, nrec);
+    }
+    HIPCHK(hipGetLastError());
+  }
+  HIPCHK(hipStreamSynchronize(g.stream));
+  drain.done();
+  return ZES_OK;
+}
+
+int zes_gzip_batch_bound(const uint64_t* in_len, uint32_t count, uint64_t* cap) {
+  if (count && (!in_len || !cap)) return ZES_E_ARG;
+  for (uint32_t i = 0; i < count; i++) cap[i] = in_len[i] > GZB_LEN_MAX ? 0 : gzip_batch_cap(in_len[i]);
+  return ZES_OK;
+}
+
+int zes_gzip_batch_dev(const uint8_t* d_in, const uint64_t* in_off, const uint64_t* in_len, uint32_t count, uint8_t* d_out, const uint64_t* out_off,
+                       const uint64_t* out_cap, uint64_t* out_len, int32_t* status, uint32_t flags) {
+  ROUTE_DEV(d_in, d_out);
+  if (count && (!in_off || !out_off || !out_cap)) return ZES_E_ARG;
+  bool any = false;
+  if (const int arc = gzip_batch_args([&](uint32_t) { return d_in != nullptr; }, in_len, count, out_len, status, flags, &any)) return arc;
+  if (!any) {
+    call_none();
+    return ZES_OK;
+  }
+  LOCK_READY();
+  return call_done(gzip_batch_core(d_in, in_off, in_len, count, d_out, out_off, out_cap, out_len, status, flags), true);
+}
+
+int zes_gzip_batch(const uint8_t* const* in, const uint64_t* in_len, uint32_t count, zes_alloc_fn alloc, void* user, uint64_t* out_len, int32_t* status,
+                   uint32_t flags) {
+  UseDev ud(route_host());
+  if (!alloc || (count && !in)) return ZES_E_ARG;
+  bool any = false;
+  if (const int arc = gzip_batch_args([&](uint32_t i) { return in[i] != nullptr; }, in_len, count, out_len, status, flags, &any)) return arc;
+  if (!any) {
+    call_none();
+    return ZES_OK;
+  }
+  LOCK_READY();
+  // every file gets the bound's room
+  HostBatch hb(g.gz_in, g.gz_acc);
+  std::vector<uint64_t> in_off(count, 0), out_off(count, 0), out_cap(count, 0);
+  for (uint32_t i = 0; i < count; i++) {
+    if (status[i] != ZES_OK) continue;
+    in_off[i] = hb.place(in[i], in_len[i]);
+    out_cap[i] = gzip_batch_cap(in_len[i]);
+    out_off[i] = hb.room(out_cap[i]);
+  }
+  if ((rc = hb.up())) return rc;
+  rc = gzip_batch_core(hb.d_in(), in_off.data(), in_len, count, hb.d_out(), out_off.data(), out_cap.data(), out_len, status, flags);
+  if ((rc = call_done(rc, true))) return rc;
+  return hb.hand_out(count, alloc, user, status, out_len, [&](uint32_t i) { return out_len[i]; }, [&](uint32_t i) { return out_off[i]; });
+}
+
+// the first min(len, ZES_GZ_HLEN_MAX) bytes of a file in host memory, for zes_gz_candidate
+struct GzHostBytes {
+  const uint8_t* h;
+  uint32_t avail;
+  uint32_t byte(uint32_t i) const { return h[i]; }
+  uint32_t nul_from(uint32_t p) const {
+    while (p < avail && h[p]) p++;
+    return p;
+  }
+};
+
+// One file of a gunzip batch: where it lies in the source and in the caller's memory (host forms), what k_gz_heads or the
+// host rule says of it, where its output goes and how much room that has
+struct GzbFile {
+  uint64_t off, len;
+  const uint8_t* h;
+  ZesGzHead head;
+  uint64_t dst_off, cap;
+};
+
+// Step 1 of the device form: one k_gz_heads launch over every file, one read-back of the records
+static int gzb_heads_dev(const uint8_t* d_src, std::vector<GzbFile>& fs) {
+  int rc;
+  const uint32_t n = (uint32_t)fs.size();
+  std::vector<ZesGzFile> tab(n);
+  std::vector<ZesGzHead> heads(n);
+  Drain drain;  // (behind tab, which an upload reads, and heads, which the read-back writes)
+  for (uint32_t i = 0; i < n; i++) tab[i] = ZesGzFile{fs[i].off, fs[i].len, fs[i].cap};
+  const size_t o_heads = sizeof(ZesGzFile) * (size_t)n;
+  if ((rc = ensure(g.gz_tab, o_heads + sizeof(ZesGzHead) * (size_t)n))) return rc;
+  ZesGzHead* d_heads = (ZesGzHead*)((uint8_t*)g.gz_tab.p + o_heads);
+  HIPCHK(hipMemcpyAsync(g.gz_tab.p, tab.data(), o_heads, hipMemcpyHostToDevice, g.stream));
+  {
+    constexpr uint32_t per = ZES_GZ_HEADS_THREADS / 64u;
+    Timed t("k_gz_heads");
+    hipLaunchKernelGGL(k_gz_heads, dim3((n + per - 1) / per), dim3(ZES_GZ_HEADS_THREADS), 0, g.stream, d_src, (const ZesGzFile*)g.gz_tab.p, d_heads, n);
+  }
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipMemcpyAsync(heads.data(), d_heads, sizeof(ZesGzHead) * (size_t)n, hipMemcpyDeviceToHost, g.stream));
+  HIPCHK(hipStreamSynchronize(g.stream));
+  drain.done();
+  for (uint32_t i = 0; i < n; i++) fs[i].head = heads[i];
+  return ZES_OK;
+}
+
+// Step 2: the candidates as one batch on the plan of the gzip members (body_plan, one k_gz_gather of the bodies, body_run
+// per part): done[i] for a candidate that comes back ZES_OK, whose head.isize bytes then stand at dst + dst_off.  A candidate
+// with a status has decided nothing: it is the per-file route's.
+static int gzb_batch(const uint8_t* d_src, const std::vector<GzbFile>& fs, uint8_t* dst, uint32_t flags, std::vector<uint8_t>& done) {
+  int rc;
+  std::vector<uint32_t> ids;
+  std::vector<BodyPart> bs;
+  for (uint32_t i = 0; i < fs.size(); i++)
+    if (fs[i].head.candidate) {
+      const ZesGzHead& h = fs[i].head;
+      ids.push_back(i);
+      bs.push_back(BodyPart{fs[i].len - h.hlen - 8, h.isize, h.crc, fs[i].dst_off, 0u, h.isize, true, ZES_OK});
+    }
+  if (ids.empty()) return ZES_OK;
+  if ((rc = body_plan(bs, dst, 0, true))) return rc;
+  std::vector<ZesGzSeg> segs;
+  for (size_t k = 0; k < ids.size(); k++) segs.push_back(ZesGzSeg{fs[ids[k]].off + fs[ids[k]].head.hlen, bs[k].islot + 2, bs[k].len, 1u, 0u});
+  Drain drain;  // (behind segs, which gz_gather's upload reads)
+  if ((rc = gz_gather(d_src, (uint8_t*)g.gz_bodies.p, segs))) return rc;
+  if ((rc = body_run(bs, dst, flags & ZES_F_PIECES, false, nullptr))) return rc;
+  HIPCHK(hipStreamSynchronize(g.stream));
+  drain.done();
+  for (size_t k = 0; k < ids.size(); k++) done[ids[k]] = bs[k].status == ZES_OK;
+  return ZES_OK;
+}
+
+// Step 3, one file: what zes_gunzip_dev does with it alone (gunzip_any), into d_to with capacity cap.  d_to is at a 16-byte
+// boundary, and the decoders' whole 16-byte groups have room behind cap.
+static int gzb_one(const GzbFile& f, const uint8_t* d_src, uint8_t* d_to, uint64_t cap, uint64_t* out_len, uint32_t flags) {
+  *out_len = 0;
+  if (f.len == 0) return ZES_E_GZIP;
+  GzSrc S{f.h, d_src + f.off, f.len};
+  uint64_t hlen = 0;
+  int rc = f.h ? gz_header(f.h, f.len, f.len, &hlen) : S.header(0, &hlen);
+  if (rc) return rc;
+  rc = gunzip_any(S, hlen, true, d_to, cap, out_len, flags & ZES_F_PIECES);
+  if (rc && rc != ZES_E_NOSPACE) {
+    *out_len = 0;
+    (void)hipGetLastError();
+  }
+  return rc;
+}
+
+// The same through g.gz_batch (the decoders write whole 16-byte groups, a file's place may begin and end at any byte): the
+// scratch has min(cap, a guess) bytes first and the size needed when the answer is that this was too little; the verdict is
+// the one for `cap`.
+static int gzb_one_scratch(const GzbFile& f, const uint8_t* d_src, uint64_t cap, uint64_t* out_len, uint32_t flags) {
+  int rc;
+  uint64_t room = std::min<uint64_t>(cap, std::max<uint64_t>(4 * f.len, 65536));
+  for (;;) {
+    if ((rc = ensure(g.gz_batch, gz_up16(room) + 64))) return rc;
+    rc = gzb_one(f, d_src, (uint8_t*)g.gz_batch.p, room, out_len, flags);
+    if (rc != ZES_E_NOSPACE || *out_len > cap || *out_len <= room) return rc;
+    room = *out_len;
+  }
+}
+
+// a gunzip batch of no files: no device work, and nothing of the call before stays
+static void gzb_none() {
+  call_none();
+  std::lock_guard<std::mutex> lk(g_mu);
+  g.last_members = 0;
+  g.last_gzb[0] = g.last_gzb[1] = 0;
+}
+
+static int gunzip_batch_args(const std::function<bool(uint32_t)>& data, const uint64_t* in_len, uint32_t count, uint64_t* out_len, int32_t* status,
+                             uint32_t flags) {
+  if (flags & ~(ZES_F_PIECES | ZES_F_GZIP_SERIAL)) return ZES_E_ARG;
+  if (count && (!in_len || !out_len || !status)) return ZES_E_ARG;
+  for (uint32_t i = 0; i < count; i++)
+    if (in_len[i] && !data(i)) return ZES_E_ARG;
+  return ZES_OK;
+}
+
+int zes_gunzip_batch_dev(const uint8_t* d_in, const uint64_t* in_off, const uint64_t* in_len, uint32_t count, uint8_t* d_out, const uint64_t* out_off,
+                         const uint64_t* out_cap, uint64_t* out_len, int32_t* status, uint32_t flags) {
+  ROUTE_DEV(d_in, d_out);
+  if (count && (!in_off || !out_off || !out_cap)) return ZES_E_ARG;
+  if (const int arc = gunzip_batch_args([&](uint32_t) { return d_in != nullptr; }, in_len, count, out_len, status, flags)) return arc;
+  for (uint32_t i = 0; i < count; i++)
+    if (out_cap[i] && !d_out) return ZES_E_ARG;
+  if (!count) {
+    gzb_none();
+    return ZES_OK;
+  }
+  LOCK_READY();
+  g.carry.clear();
+  g.last_tier = 0;
+  g.last_members = 0;
+  g.last_gzb[0] = g.last_gzb[1] = 0;
+  std::vector<GzbFile> fs(count);
+  for (uint32_t i = 0; i < count; i++) {
+    fs[i] = GzbFile{in_off[i], in_len[i], nullptr, ZesGzHead{0, 0, 0, 0}, out_off[i], out_cap[i]};
+    out_len[i] = 0;
+    status[i] = ZES_OK;
+  }
+  std::vector<uint8_t> done(count, 0);
+  if (!(flags & ZES_F_GZIP_SERIAL)) {
+    if ((rc = gzb_heads_dev(d_in, fs)) || (rc = gzb_batch(d_in, fs, d_out, flags, done))) return call_done(rc, true);
+  }
+  std::vector<ZesGzSeg> seg(1);
+  Drain drain;  // (behind seg, which gz_gather's upload reads)
+  for (uint32_t i = 0; i < count; i++) {
+    if (done[i]) {
+      out_len[i] = fs[i].head.isize;
+      g.last_gzb[0]++;
+      continue;
+    }
+    g.last_gzb[1]++;
+    uint64_t n = 0;
+    rc = gzb_one_scratch(fs[i], d_in, out_cap[i], &n, flags);
+    if (rc == ZES_OK && n) {  // (n <= out_cap[i]: exactly the result's bytes go to their place)
+      seg[0] = ZesGzSeg{0, out_off[i], n, 0u, 0u};
+      int grc = gz_gather((const uint8_t*)g.gz_batch.p, d_out, seg);
+      if (!grc && hipStreamSynchronize(g.stream) != hipSuccess) grc = ZES_E_DEVICE;
+      if (grc) return call_done(grc, true);
+    }
+    if (rc == ZES_E_DEVICE) return call_done(rc, true);
+    status[i] = rc;
+    out_len[i] = n;
+  }
+  drain.done();
+  return call_done(ZES_OK, false);
+}
+
+int zes_gunzip_batch_alloc(const uint8_t* const* in, const uint64_t* in_len, uint32_t count, zes_alloc_fn alloc, void* user, uint64_t* out_len,
+                           int32_t* status, uint32_t flags) {
+  UseDev ud(route_host());
+  if (!alloc || (count && !in)) return ZES_E_ARG;
+  if (const int arc = gunzip_batch_args([&](uint32_t i) { return in[i] != nullptr; }, in_len, count, out_len, status, flags)) return arc;
+  if (!count) {
+    gzb_none();
+    return ZES_OK;
+  }
+  LOCK_READY();
+  g.carry.clear();
+  g.last_tier = 0;
+  g.last_members = 0;
+  g.last_gzb[0] = g.last_gzb[1] = 0;
+  // step 1 on the host; a candidate's output gets its place at once, the others' sizes are known behind their own decode
+  HostBatch hb(g.gz_in, g.gz_acc);
+  std::vector<GzbFile> fs(count);
+  for (uint32_t i = 0; i < count; i++) {
+    const uint64_t len = in_len[i];
+    GzbFile& f = fs[i];
+    f = GzbFile{hb.place(in[i], len), len, in[i], ZesGzHead{0, 0, 0, 0}, 0, 0};
+    out_len[i] = 0;
+    status[i] = ZES_OK;
+    if (len >= 8) f.head.crc = get_le32(in[i] + len - 8), f.head.isize = get_le32(in[i] + len - 4);
+    if (!(flags & ZES_F_GZIP_SERIAL)) {
+      const GzHostBytes a{in[i], (uint32_t)std::min<uint64_t>(len, ZES_GZ_HLEN_MAX)};
+      f.head.candidate = zes_gz_candidate(a, len, ZES_GZB_NO_CAP, f.head.isize, &f.head.hlen) ? 1u : 0u;
+    }
+    if (f.head.candidate) f.dst_off = hb.room(f.head.isize);
+  }
+  if ((rc = hb.up())) return rc;
+  std::vector<uint8_t> done(count, 0);
+  if ((rc = gzb_batch(hb.d_in(), fs, hb.d_out(), flags, done))) return call_done(rc, true);
+  // the per-file route: every result waits in host memory until all files have their verdict
+  std::vector<std::vector<uint8_t>> kept(count);
+  for (uint32_t i = 0; i < count; i++) {
+    if (done[i]) {
+      out_len[i] = fs[i].head.isize;
+      g.last_gzb[0]++;
+      continue;
+    }
+    g.last_gzb[1]++;
+    uint64_t n = 0;
+    rc = gzb_one_scratch(fs[i], hb.d_in(), ZES_GZB_NO_CAP & ~15ull, &n, flags);
+    if (rc == ZES_E_DEVICE) return call_done(rc, true);
+    status[i] = rc;
+    out_len[i] = rc == ZES_OK ? n : 0;
+    if (rc == ZES_OK && n) {
+      kept[i].resize(n);
+      if ((rc = download(kept[i].data(), (const uint8_t*)g.gz_batch.p, n))) return call_done(rc, true);
+    }
+  }
+  if ((rc = call_done(ZES_OK, false))) return rc;
+  for (uint32_t i = 0; i < count; i++) {
+    if (status[i] != ZES_OK) continue;
+    const uint64_t n = out_len[i];
+    uint8_t* to = alloc(user, i, n);
+    if (!to) {
+      status[i] = ZES_E_ARG;
+      out_len[i] = 0;
+      continue;
+    }
+    if (done[i]) {
+      if ((rc = download(to, hb.d_out() + fs[i].dst_off, n, nullptr, false))) return rc;
+    } else if (n) {
+      memcpy(to, kept[i].data(), n);
+    }
+  }
+  HIPCHK(hipStreamSynchronize(g.stream));
+  return ZES_OK;
+}
+
 int zes_stage_lz77_dev(const uint8_t* d_in, uint64_t n, uint64_t start, uint32_t len, uint32_t* h_tokens, uint32_t* ntokens) {
   ROUTE_DEV(d_in);
   if (!h_tokens || !ntokens || len < 2 || len > ZES_BLK || start + len > n || (start % ZES_BLK)) return ZES_E_ARG;
@@ -6548,6 +6934,14 @@ int zes_last_gunzip_members(void) {
   UseDev ud(t_last);
   std::lock_guard<std::mutex> lk(g_mu);
   return g.last_members;
+}
+
+int zes_last_gunzip_batch(uint32_t* batched, uint32_t* serial) {
+  UseDev ud(t_last);
+  std::lock_guard<std::mutex> lk(g_mu);
+  if (batched) *batched = g.last_gzb[0];
+  if (serial) *serial = g.last_gzb[1];
+  return ZES_OK;
 }
 
 int zes_set_profiling(int on) {

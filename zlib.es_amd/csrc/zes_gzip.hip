@@ -38,10 +38,28 @@
 //                copy of the names); all of them copy the body as shares of gz_copy — the encoder's stream out of its scratch
 //                slot, or the caller's bytes.  Entries meet at any byte: only the entry's own bytes are written, each by one
 //                workgroup, and the input is read only inside the aligned 16-byte groups that hold the entry's bytes.
+//
+// Independent gzip files as one batch (zes_api.hip: gzip_batch_core for the writer; zes_gunzip_batch_dev and
+// zes_gunzip_batch_alloc over gzb_heads_dev, gzb_batch and gzb_one_scratch for the reader):
+//   k_gz_heads   a wavefront per file of a gunzip batch, as k_gz_walk reads a member: the 64 lanes fetch the file's first 256
+//                bytes side by side, lane l bytes 4l .. 4l + 3 into one register by four byte loads (a file starts at any
+//                byte), each tested against the file's end; the header is
+//                parsed from the lanes' registers with uniform lane reads, the NULs that end FNAME and FCOMMENT are found by
+//                ballot; eight lanes fetch the trailer.  One record {candidate, hlen, crc, isize} per file by the rule of
+//                zes_gzbatch.h (zes_gz_candidate), which the host forms apply to the caller's memory.  No byte outside the
+//                file is read.
+//   k_gz_pack    the files of a gzip batch being written, over a flat list of workgroups as in k_zip_pack: a file has as many
+//                as its body has 64 KiB pieces (one at least, ZES_GZ_PACK_SHARES at most), found by bisection.  The file's
+//                first workgroup writes the 10 header bytes and the 8 trailer bytes; all of them copy the body as shares of
+//                gz_copy: the encoder's stream out of its slot, or the stored form, whose blocks (five header bytes, then up
+//                to 65535 bytes out of the caller's input) are dealt out to the workgroups in turn.  Files meet at any byte:
+//                only the file's own bytes are written, each by one workgroup, and the input is read only inside the
+//                aligned 16-byte groups that hold the file's bytes.
 #include "../../include/zes.h"
 #include "zes_common.h"
 #include "zes_kernels.h"
 #include "zes_copy.h"
+#include "zes_gzbatch.h"
 
 __global__ __launch_bounds__(64) void k_gz_walk(const uint8_t* __restrict__ d_in, uint64_t c, ZesGzWalk* __restrict__ head,
                                                ZesGzMember* __restrict__ tab, uint32_t cap) {
@@ -257,4 +275,88 @@ __global__ __launch_bounds__(GZ_GATHER_THREADS) void k_zip_pack(const uint8_t* _
     gz_copy(names + r.name_off, h + 30, r.name_len, tid, 0, 1);
   }
   gz_copy((r.method == 8 ? slots : in) + r.src_off, h + 30 + r.name_len, r.csize, tid, y, ny);
+}
+
+namespace {
+// the first a.avail bytes of a file as a wavefront holds them: lane l has bytes 4l .. 4l + 3 in w (0 behind the file's end)
+struct GzWaveBytes {
+  uint32_t w, lane, avail;
+  __device__ __forceinline__ uint32_t byte(uint32_t i) const {
+    return ((uint32_t)__builtin_amdgcn_readlane((int)w, (int)(i >> 2)) >> (8 * (i & 3u))) & 255u;
+  }
+  __device__ __forceinline__ uint32_t nul_from(uint32_t p) const {
+    uint32_t m = 0;
+#pragma unroll
+    for (uint32_t b = 0; b < 4; b++) {
+      const uint32_t q = lane * 4 + b;
+      if (q >= p && q < avail && ((w >> (8 * b)) & 255u) == 0) m |= 1u << b;
+    }
+    const unsigned long long hit = __ballot(m != 0);
+    if (!hit) return avail;
+    const uint32_t l = (uint32_t)__ffsll((long long)hit) - 1;
+    const uint32_t lm = (uint32_t)__builtin_amdgcn_readlane((int)m, (int)l);
+    return l * 4 + (uint32_t)__ffs((int)lm) - 1;
+  }
+};
+}  // namespace
+
+__global__ __launch_bounds__(ZES_GZ_HEADS_THREADS) void k_gz_heads(const uint8_t* __restrict__ d_in, const ZesGzFile* __restrict__ files,
+                                                                  ZesGzHead* __restrict__ heads, uint32_t count) {
+  const uint32_t lane = threadIdx.x & 63u;
+  const uint32_t f = (uint32_t)__builtin_amdgcn_readfirstlane((int)(blockIdx.x * (ZES_GZ_HEADS_THREADS / 64u) + threadIdx.x / 64u));
+  if (f >= count) return;
+  const ZesGzFile F = files[f];
+  const uint8_t* p = d_in + F.off;
+  uint32_t w = 0;
+#pragma unroll
+  for (uint32_t b = 0; b < 4; b++) {
+    const uint64_t o = (uint64_t)lane * 4 + b;
+    if (o < F.len) w |= (uint32_t)p[o] << (8 * b);
+  }
+  const uint32_t tb = (lane < 8 && F.len >= 8) ? p[F.len - 8 + lane] : 0u;
+  uint32_t t[2] = {0, 0};
+#pragma unroll
+  for (uint32_t k = 0; k < 8; k++) t[k >> 2] |= (uint32_t)__builtin_amdgcn_readlane((int)tb, (int)k) << (8 * (k & 3u));
+  const GzWaveBytes a{w, lane, (uint32_t)min(F.len, (uint64_t)ZES_GZ_HLEN_MAX)};
+  uint32_t hlen = 0;
+  const bool cand = zes_gz_candidate(a, F.len, F.cap, t[1], &hlen);
+  if (lane == 0) heads[f] = ZesGzHead{cand ? 1u : 0u, hlen, t[0], t[1]};
+}
+
+__global__ __launch_bounds__(GZ_GATHER_THREADS) void k_gz_pack(const uint8_t* __restrict__ in, const uint8_t* __restrict__ slots,
+                                                              uint8_t* __restrict__ out, const ZesGzPackRec* __restrict__ recs, uint32_t count) {
+  // the last record whose first workgroup is not behind this one (recs[count] closes the table: no workgroup is its own)
+  uint32_t lo = 0, hi = count;
+  while (hi - lo > 1) {
+    const uint32_t mid = (lo + hi) / 2;
+    if (recs[mid].first_wg <= blockIdx.x) lo = mid; else hi = mid;
+  }
+  const ZesGzPackRec r = recs[lo];
+  const uint32_t y = blockIdx.x - r.first_wg, ny = recs[lo + 1].first_wg - r.first_wg;
+  const uint32_t tid = threadIdx.x;
+  uint8_t* m = out + r.dst_off;
+  if (y == 0) {
+    if (tid < 10) m[tid] = tid == 0 ? 0x1f : tid == 1 ? 0x8b : tid == 2 ? 8 : tid == 9 ? 0xff : 0;  // FLG 0, MTIME 0, XFL 0, OS 255
+    if (tid >= 32 && tid < 40) {
+      const uint32_t k = tid - 32;
+      m[10 + r.body_len + k] = (uint8_t)((k < 4 ? r.crc : r.len) >> (8 * (k & 3u)));
+    }
+  }
+  uint8_t* body = m + 10;
+  if (!r.stored) {
+    gz_copy(slots + r.src_off, body, r.body_len, tid, y, ny);
+    return;
+  }
+  // the stored form: per block of ZES_GZ_STORED_BLOCK bytes final, LEN, NLEN, the bytes; block b is workgroup b mod ny's
+  const uint32_t nb = (uint32_t)zes_gz_stored_blocks(r.len);
+  for (uint32_t b = y; b < nb; b += ny) {
+    const uint32_t at = b * ZES_GZ_STORED_BLOCK;  // (below 2^32 with len)
+    const uint32_t len = min(ZES_GZ_STORED_BLOCK, r.len - at);
+    uint8_t* blk = body + (uint64_t)b * (5ull + ZES_GZ_STORED_BLOCK);
+    if (tid >= 64 && tid < 69) {
+      const uint32_t k = tid - 64, v = len | (~len << 16);
+      blk[k] = k ? (uint8_t)(v >> (8 * (k - 1))) : (uint8_t)(b + 1 == nb ? 1 : 0);
+    }
+    gz_copy(in + r.src_off + at, blk + 5, len, tid, 0, 1);
+  }
 }

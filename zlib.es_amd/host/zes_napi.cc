@@ -1127,6 +1127,30 @@ napi_value PngEncodeBatch(napi_env env, napi_callback_info info) {
   return j.rc == 0 ? batch_results(env, &j) : throw_status(env, j.rc);
 }
 
+// gzipBatch(inputs) and gunzipBatch(files): independent buffers written as one gzip file each, and independent gzip files
+// decoded, as one batch (include/zes.h: zes_gzip_batch, zes_gunzip_batch_alloc): per item a fresh Uint8Array or the Error that
+// says why not, as the batch forms answer.  The two differ in the entry point alone.
+using GzBatchFn = int (*)(const uint8_t* const*, const uint64_t*, uint32_t, zes_alloc_fn, void*, uint64_t*, int32_t*, uint32_t);
+napi_value gz_batch(napi_env env, napi_callback_info info, const char* SIG, GzBatchFn fn) {
+  const Args a = get_args(env, info);
+  bool is_arr = false;
+  uint32_t count = 0;
+  if (a.argc < 1 || napi_is_array(env, a.argv[0], &is_arr) != napi_ok || !is_arr || napi_get_array_length(env, a.argv[0], &count) != napi_ok)
+    return throw_type(env, std::string(SIG) + ": the argument must be an array of Uint8Array");
+  BatchJob j(count);
+  for (uint32_t i = 0; i < count; i++) {
+    napi_value e;
+    size_t n = 0;
+    if (napi_get_element(env, a.argv[0], i, &e) != napi_ok || !get_bytes(env, e, &j.in[i], &n))
+      return throw_type(env, std::string(SIG) + ": every element must be a Uint8Array");
+    j.in_len[i] = n;
+  }
+  j.rc = fn(j.in.data(), j.in_len.data(), count, batch_alloc, &j, j.out_len.data(), j.status.data(), ZES_F_DEFAULT);
+  return j.rc == 0 ? batch_results(env, &j) : throw_status(env, j.rc);
+}
+napi_value GzipBatch(napi_env env, napi_callback_info info) { return gz_batch(env, info, "gzipBatch(inputs)", zes_gzip_batch); }
+napi_value GunzipBatch(napi_env env, napi_callback_info info) { return gz_batch(env, info, "gunzipBatch(files)", zes_gunzip_batch_alloc); }
+
 // zip(names, datas): a ZIP archive of datas[i] under names[i], two arrays of Uint8Array of one length (the façade takes the
 // file objects apart and encodes string names): one call, the bounded result (include/zes.h: zes_zipwrite)
 napi_value Zip(napi_env env, napi_callback_info info) {
@@ -1199,6 +1223,8 @@ napi_value ModuleInit(napi_env env, napi_value exports) {
       {"adler32", swept<Adler32>},
       {"gzip", swept<Gzip>},
       {"gunzip", swept<Gunzip>},
+      {"gzipBatch", swept<GzipBatch>},
+      {"gunzipBatch", swept<GunzipBatch>},
       {"bgzip", swept<Bgzip>},
       {"bgzipIndex", swept<BgzipIndex>},
       {"bgzfIndex", swept<BgzfIndex>},

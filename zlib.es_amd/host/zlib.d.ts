@@ -17,6 +17,9 @@ export declare function allocPinned(n: number): Uint8Array;
 export declare function adler32(input: Uint8Array): number;
 export declare function gzip(input: Uint8Array): Uint8Array;
 export declare function gunzip(input: Uint8Array): Uint8Array;
+/** Many independent gzip files in one batch: per item the file (the output) or the Error that says why not; every input length writes. */
+export declare function gzipBatch(inputs: Uint8Array[]): BatchResult[];
+export declare function gunzipBatch(files: Uint8Array[]): BatchResult[];
 export declare function lastGunzipMembers(): number;
 export declare function bgzip(input: Uint8Array): Uint8Array;
 export declare function bgzipIndex(input: Uint8Array): { data: Uint8Array, offsets: number[] };

@@ -104,6 +104,20 @@ function gunzip(input) {
 }
 
 /**
+ * Extra (not in the reference API): many independent gzip files in one call.  `gzipBatch` writes every input as one gzip file
+ * (gzip()'s bytes, or stored blocks where those are shorter or the encoder refuses the length: every length writes) and
+ * `gunzipBatch` decodes every file as gunzip() would alone; the device work does not grow with the number of items.  Element
+ * i of the result is the file (the output) or — the call does not throw — the `Error` that says why not.
+ */
+function gzipBatch(inputs) {
+  return addon.gzipBatch(inputs);
+}
+
+function gunzipBatch(files) {
+  return addon.gunzipBatch(files);
+}
+
+/**
  * Extra (not in the reference API): BGZF files, the blocked gzip of bgzip / htslib.  `bgzip` writes one gzip member per
  * 65280-byte chunk of the input, each stating its own size, and the 28-byte end-of-file marker: a file htslib can index
  * and gunzip() decodes as one batch.  Every input length is valid.  `bgzipIndex` also returns the byte position of every
@@ -326,6 +340,8 @@ exports.inflateBatchAsync = inflateBatchAsync;
 exports.allocPinned = allocPinned;
 exports.gzip = gzip;
 exports.gunzip = gunzip;
+exports.gzipBatch = gzipBatch;
+exports.gunzipBatch = gunzipBatch;
 exports.bgzip = bgzip;
 exports.bgzipIndex = bgzipIndex;
 exports.bgzfIndex = bgzfIndex;

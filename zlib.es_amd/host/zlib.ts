@@ -121,6 +121,20 @@ export function gunzip(input: Uint8Array): Uint8Array {
 }
 
 /**
+ * Extra (not in the reference API): many independent gzip files in one call.  `gzipBatch` writes every input as one gzip file
+ * (gzip()'s bytes, or stored blocks where those are shorter or the encoder refuses the length: every length writes) and
+ * `gunzipBatch` decodes every file as gunzip() would alone; the device work does not grow with the number of items.  Element
+ * i of the result is the file (the output) or — the call does not throw — the `Error` that says why not.
+ */
+export function gzipBatch(inputs: Uint8Array[]): BatchResult[] {
+  return addon.gzipBatch(inputs);
+}
+
+export function gunzipBatch(files: Uint8Array[]): BatchResult[] {
+  return addon.gunzipBatch(files);
+}
+
+/**
  * Extra (not in the reference API): BGZF files, the blocked gzip of bgzip / htslib.  `bgzip` writes one gzip member per
  * 65280-byte chunk of the input, each stating its own size, and the 28-byte end-of-file marker: a file htslib can index
  * and gunzip() decodes as one batch.  Every input length is valid.  `bgzipIndex` also returns the byte position of every
