@@ -48,7 +48,8 @@ typedef enum zes_status {
                                disks, encryption, a method other than 0 (stored) or 8 (DEFLATE); zes_png_*: a valid file with a
                                critical chunk this reader does not know, filtered data of more than 0xFFFFFFFF bytes, or (the
                                decode calls without ZES_F_PNG_INTERLACED) Adam7 interlace */
-  ZES_E_PNG = -24           /* zes_png_*: not a PNG file this reader accepts, or image data that does not fit its header */
+  ZES_E_PNG = -24,          /* zes_png_*: not a PNG file this reader accepts, or image data that does not fit its header */
+  ZES_E_TIFF = -25          /* zes_tiff_*: not a TIFF file this reader accepts, or image data that does not fit its directory */
 } zes_status;
 
 /* Geometry of the reference format (src/const.ts:7). */
@@ -730,6 +731,105 @@ int zes_pngpix_alloc(const uint8_t* const* in, const uint64_t* in_len, uint32_t 
 int zes_pngpix_expand_dev(const uint8_t* d_in, const uint64_t* in_off, const uint64_t* in_len, const zes_pngw_image* img, const uint8_t* aux,
                           uint32_t count, uint8_t* d_out, const uint64_t* out_off, const uint64_t* out_cap, uint64_t* out_len, int32_t* status,
                           uint32_t flags);
+
+/* TIFF images (TIFF 6.0; Compression 8 and 32946 of TIFF Technical Note 2): the index of one image of a file, and a rectangle
+ * of that image decoded as one batch.  Reading is all there is: no TIFF writer.  The tiles or strips of an image ("segments")
+ * are independent zlib streams that state their own sizes, as BGZF members are, and Predictor 2 chains within a row, never
+ * across rows: every row of every segment is independent work, and a rectangle needs only the segments it touches.
+ *
+ * zes_tiff_image: what a read call works from.  All values are little-endian host values; there are no pad fields.
+ * The file rule (one host function, used by both index forms), the first failure in this order deciding; all arithmetic in
+ * 64 bits:
+ *   header      c >= 8 and the bytes are 49 49 2a 00 or 4d 4d 00 2a, else ZES_E_TIFF; 49 49 2b 00 / 4d 4d 00 2b (BigTIFF):
+ *               ZES_E_UNSUPPORTED
+ *   chain       every directory lies at an offset o >= 8 with o + 2 + 12 n + 4 <= c (n its entry count), else ZES_E_TIFF; more
+ *               than 65536 hops: ZES_E_TIFF; the chain ends at a next-offset of 0.  *dirs = the chain's length; dir >= *dirs:
+ *               ZES_E_ARG (with *dirs filled)
+ *   entries     of directory `dir`, in file order, need not be sorted; the first occurrence of a tag counts.  A tag the reader
+ *               uses (256-259, 262, 266, 273, 277-279, 284, 317, 322-325, 338, 339) must be SHORT (3) or LONG (4) with a count
+ *               >= 1, its values inline when count * size <= 4, else at an offset with offset + count * size <= c; else
+ *               ZES_E_TIFF.  Other tags are not looked at
+ *   geometry    ImageWidth and ImageLength present and >= 1; either StripOffsets and StripByteCounts (RowsPerStrip >= 1 when
+ *               present), or TileWidth, TileLength, TileOffsets and TileByteCounts (both dimensions non-zero multiples of 16);
+ *               both kinds, neither, or a missing partner: ZES_E_TIFF.  Both arrays hold exactly across * down values and every
+ *               segment has off + len <= c, else ZES_E_TIFF
+ *   defaults    SamplesPerPixel 1, Compression 1, Predictor 1, PlanarConfiguration 1, FillOrder 1, SampleFormat 1,
+ *               RowsPerStrip the height, BitsPerSample one value of 1 (a bilevel file: unsupported below); Photometric and
+ *               ExtraSamples are reported as 0 when absent
+ *   kinds       SamplesPerPixel 0 or a BitsPerSample count != SamplesPerPixel: ZES_E_TIFF.  Then ZES_E_UNSUPPORTED for: unequal
+ *               bit depths or one outside {8, 16, 32}; more than 4 samples; PlanarConfiguration other than 1 with more than one
+ *               sample; FillOrder other than 1; Compression other than 1 (none), 8 and 32946 (both zlib); Predictor 3;
+ *               Predictor 2 with Compression 1 (libtiff ignores the tag there, other readers apply it: the file is ambiguous);
+ *               a segment of more than 0xFFFFFFFF decoded bytes; more than 2^31 - 1 segments.  A Predictor other than 1, 2 and
+ *               3: ZES_E_TIFF
+ * With any status but ZES_E_NOSPACE the record is all zeros.  compression, predictor, photometric, sample_format (its first
+ * value) and extra_samples (its first value) are reported; the last three are not interpreted: palette, colour and orientation
+ * are the caller's.
+ *
+ * zes_tiff_index applies the rule to the caller's memory on the host and touches no device.  seg_off and seg_len receive the
+ * across * down file positions and byte counts, row-major in segment order; *segments = across * down.  cap < *segments:
+ * ZES_E_NOSPACE with *segments, *dirs and *img filled (cap == 0 is the sizing call; seg_off and seg_len may be null then).
+ * ZES_E_ARG: a null img, segments or dirs, a null `in` with c != 0, null arrays with cap != 0, flags != 0.
+ * zes_tiff_index_dev is the same for a file in device memory: it brings down the 8 header bytes, of every directory on the
+ * chain its count and its next-offset, the entries of directory `dir`, the values that do not lie inline in their entries
+ * (the two arrays; BitsPerSample and SampleFormat of an image of 3 or 4 samples; in a file that gives another tag the reader
+ * uses more than 4 bytes of values, the first of them) - never pixel data - and judges them with the same host function: at
+ * most 1 + 2 * dirs + 1 + 16 copies (1 + 2 * dirs + 1 + 4 for a file whose scalar tags have one value), each followed by a
+ * synchronisation.
+ *
+ * zes_tiff_read_dev / zes_tiff_read_alloc decode the rectangle rect = {x, y, w, h} of the image (NULL: the whole image) to
+ * h rows of w * spp * bits / 8 bytes, dense, row by row from the top.  Samples of 16 and 32 bits are written little-endian
+ * whatever the file's byte order, so that a view of the result as int16 or float32 works.  Decided in this order:
+ *   1. ZES_E_ARG: null arrays, a null d_in / in with c != 0, a record the rule could not have produced (across, down and
+ *      out_size are computed again from the other fields), an empty rectangle or one that leaves the image, flag bits other
+ *      than ZES_F_PIECES (passed on to the inflate tiers), a segment with off + len > c.  Then (device form) cap below the
+ *      rectangle's size: ZES_E_NOSPACE with *out_len set; a null d_out: ZES_E_ARG
+ *   2. the segments the rectangle touches are chosen on the host.  A segment's decoded size E is seg_w * seg_h * spp * bits / 8
+ *      for a tile (a tile is always whole: edge tiles are padded) and rows * width * spp * bits / 8 for a strip of `rows` rows
+ *   3. Compression 1: seg_len < E is the segment's ZES_E_TIFF, bytes beyond E are ignored.  The bytes are read where they
+ *      lie in the file: no copy is made
+ *   4. Compression 8 and 32946: the touched segments are decoded as one batch into pooled scratch (the tiers of
+ *      zes_inflate_batch_dev).  A stream keeps its inflate status; a result that is not exactly E bytes, one that would
+ *      outgrow its slot included, is ZES_E_TIFF; the Adler-32 is always checked (one segmented launch): a wrong or missing one
+ *      is ZES_E_CHECKSUM
+ *   5. one k_tiff_place launch for the call, the only thing that writes d_out: Predictor 2 undone (within every segment row,
+ *      from the segment's column 0 on, sample k becomes the sum of samples k, k - spp, k - 2 spp, ... modulo 2^bits; the
+ *      samples of a big-endian file are swapped first), the samples made little-endian, tile padding and everything outside the
+ *      rectangle dropped, every row put at its place at the rectangle's pitch.  The segments that failed are not part of it
+ * The call returns ZES_OK when every touched segment is ZES_OK, else the status of the first failing one in segment order; the
+ * pixels of the good segments are still written (device form), a failed segment's pixels are unspecified, and no byte outside
+ * [d_out, d_out + the rectangle's size) is ever written, at any alignment of d_out.  seg_status (may be null): across * down
+ * values, ZES_OK for a segment that was decoded or not touched, else its status.  There is no launch, copy or synchronisation
+ * per segment.  *out_len = the rectangle's size (0 with ZES_E_ARG).  The kernels may read the aligned 16-byte groups that
+ * hold a segment.
+ * zes_tiff_read_alloc is the host form: it indexes directory `dir` on the host (the rule's statuses first, with *img zeros),
+ * uploads only the segments the rectangle touches, runs steps 3 to 5 and, when the call is ZES_OK, calls alloc(user, 0, size)
+ * once and brings the pixels down (a null answer: ZES_E_ARG).  img may be null.
+ * zes_last_tiff_read: the touched segments of this thread's last zes_tiff_read_* call and the bytes that call uploaded (0 for
+ * the device form): what a test of "only the touched segments go up" reads.
+ * replaces: nothing (the reference has no TIFF container) */
+typedef struct zes_tiff_image {  /* 48 bytes */
+  uint32_t width, height;
+  uint32_t seg_w, seg_h;   /* tile width and length; strips: width, and RowsPerStrip clamped to height */
+  uint32_t across, down;   /* segments per row and per column */
+  uint16_t bits;           /* 8, 16 or 32 */
+  uint16_t spp;            /* 1..4 */
+  uint16_t compression, predictor, photometric, sample_format, extra_samples;
+  uint8_t big_endian, tiled;
+  uint64_t out_size;       /* width * height * spp * bits / 8 */
+} zes_tiff_image;
+typedef struct zes_tiff_rect {
+  uint32_t x, y, w, h;
+} zes_tiff_rect;
+int zes_tiff_index(const uint8_t* in, uint64_t c, uint32_t dir, zes_tiff_image* img, uint64_t* seg_off, uint64_t* seg_len, uint64_t cap,
+                   uint64_t* segments, uint32_t* dirs, uint32_t flags);
+int zes_tiff_index_dev(const uint8_t* d_in, uint64_t c, uint32_t dir, zes_tiff_image* img, uint64_t* seg_off, uint64_t* seg_len, uint64_t cap,
+                       uint64_t* segments, uint32_t* dirs, uint32_t flags);
+int zes_tiff_read_dev(const uint8_t* d_in, uint64_t c, const zes_tiff_image* img, const uint64_t* seg_off, const uint64_t* seg_len,
+                      const zes_tiff_rect* rect, uint8_t* d_out, uint64_t cap, uint64_t* out_len, int32_t* seg_status, uint32_t flags);
+int zes_tiff_read_alloc(const uint8_t* in, uint64_t c, uint32_t dir, const zes_tiff_rect* rect, zes_alloc_fn alloc, void* user, uint64_t* out_len,
+                        zes_tiff_image* img, uint32_t flags);
+int zes_last_tiff_read(uint32_t* segments, uint64_t* bytes_up);
 
 /* Adler-32 of a buffer (standard value as an unsigned 32-bit).
  * replaces: `calcAdler32` src/adler32.ts:1-10 (byte extraction at src/zlib.ts:37-40). */

@@ -46,6 +46,7 @@ ZES_E_CHECKSUM = -21  # a trailer does not match: gzip CRC-32 / ISIZE / FHCRC, z
 ZES_E_ZIP = -22  # zes_zip_*: not a ZIP archive this reader accepts, or an entry whose local header or sizes do not fit its directory record
 ZES_E_UNSUPPORTED = -23  # zes_zip_*: ZIP64, several disks, encryption, a method other than 0 or 8
 ZES_E_PNG = -24  # zes_png_*: not a PNG file this reader accepts, or image data that does not fit its header
+ZES_E_TIFF = -25  # zes_tiff_*: not a TIFF file this reader accepts, or image data that does not fit its directory
 ZES_F_GZIP_SERIAL = 32  # zes_gunzip*: the members one after the other even where they could go as one batch (testing aid)
 ZES_F_INDEX_WALK = 64  # zes_bgzf_index_dev: the members by k_gz_walk's serial chain instead of the parallel finder (testing aid, baseline)
 ZES_F_PNG_INTERLACED = 128  # zes_png_decode*, zes_pngpix_dev, zes_pngpix_alloc: Adam7-interlaced files decode too (without it: ZES_E_UNSUPPORTED)
@@ -83,6 +84,12 @@ PNGW_IMAGE = np.dtype([("width", "<u4"), ("height", "<u4"), ("depth", "u1"), ("c
 assert PNGW_IMAGE.itemsize == 16
 PNG_FILTER_BANDED = 5  # adaptive, rows 0, 64, 128, ... None or Sub: the reader's bands then decode in parallel
 PNG_FILTER_ADAPTIVE = 6
+
+# zes_tiff_image of include/zes.h: what the TIFF reader says about one image of a file
+TIFF_IMAGE = np.dtype([("width", "<u4"), ("height", "<u4"), ("seg_w", "<u4"), ("seg_h", "<u4"), ("across", "<u4"), ("down", "<u4"), ("bits", "<u2"),
+                       ("spp", "<u2"), ("compression", "<u2"), ("predictor", "<u2"), ("photometric", "<u2"), ("sample_format", "<u2"),
+                       ("extra_samples", "<u2"), ("big_endian", "u1"), ("tiled", "u1"), ("out_size", "<u8")])
+assert TIFF_IMAGE.itemsize == 48
 
 ALLOC_FN = C.CFUNCTYPE(C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint64)  # zes_alloc_fn of include/zes.h
 
@@ -167,6 +174,12 @@ def lib():
         L.zes_pngpix_dev.argtypes = L.zes_png_decode_dev.argtypes
         L.zes_pngpix_alloc.argtypes = L.zes_png_decode_alloc.argtypes
         L.zes_pngpix_expand_dev.argtypes = L.zes_pngwrite_dev.argtypes
+        for name in ("zes_tiff_index", "zes_tiff_index_dev"):
+            getattr(L, name).argtypes = [C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, u64p, u32p, C.c_uint32]
+        L.zes_tiff_read_dev.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, u64p, C.c_void_p,
+                                        C.c_uint32]
+        L.zes_tiff_read_alloc.argtypes = [C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, ALLOC_FN, C.c_void_p, u64p, C.c_void_p, C.c_uint32]
+        L.zes_last_tiff_read.argtypes = [u32p, C.c_void_p]
         L.zes_gunzip_alloc.argtypes = [C.c_void_p, C.c_uint64, ALLOC_FN, C.c_void_p, u64p, C.c_uint32]
         L.zes_gzip_batch_bound.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p]
         for name in ("zes_gzip_batch_dev", "zes_gunzip_batch_dev"):
@@ -1401,6 +1414,129 @@ def last_gunzip_members():
     """Members the member-parallel path decoded in this thread's last gunzip call (0: the member-by-member path answered),
     or the members the last bgzf_read decoded."""
     return int(lib().zes_last_gunzip_members())
+
+
+# ---- TIFF reader (include/zes.h: "zes_tiff_*") -------------------------------------------------
+def _tiff_dict(img, dirs):
+    d = {k: int(img[k]) for k in TIFF_IMAGE.names}
+    d["dirs"] = int(dirs)
+    return d
+
+
+def _tiff_index(fn, ptr, size, dir):
+    """Both index forms: the sizing call, then the arrays.  (record, seg_off, seg_len, dirs)."""
+    img = np.zeros(1, dtype=TIFF_IMAGE)
+    nseg, dirs = C.c_uint64(), C.c_uint32()
+    rc = fn(ptr, size, int(dir), img.ctypes.data, None, None, 0, C.byref(nseg), C.byref(dirs), 0)
+    if rc not in (ZES_OK, ZES_E_NOSPACE):
+        err = ZlibEsError(rc, strerror(rc))
+        err.dirs = dirs.value
+        raise err
+    off, ln = np.zeros(nseg.value, dtype=np.uint64), np.zeros(nseg.value, dtype=np.uint64)
+    rc = fn(ptr, size, int(dir), img.ctypes.data, _ptr(off), _ptr(ln), off.size, C.byref(nseg), C.byref(dirs), 0)
+    if rc:
+        _raise(rc)
+    return img[0].copy(), off, ln, dirs.value
+
+
+def tiff_index(data, dir=0):
+    """The index of directory ``dir`` of a TIFF file (zes_tiff_index; no GPU needed): ``(info, seg_off, seg_len)`` — the
+    record as tiff_info gives it, and the file positions and byte counts of its tiles or strips in row-major order."""
+    a = _as_u8(data)
+    img, off, ln, dirs = _tiff_index(lib().zes_tiff_index, _ptr(a), a.size, dir)
+    return _tiff_dict(img, dirs), off, ln
+
+
+def tiff_info(data, dir=0):
+    """What the TIFF reader says about directory ``dir`` of a file (no GPU needed): the zes_tiff_image record as a dict —
+    width, height, seg_w, seg_h, across, down, bits, spp, compression, predictor, photometric, sample_format, extra_samples,
+    big_endian, tiled, out_size — plus ``dirs``, the length of the file's directory chain.  A file the rule refuses raises
+    (``.dirs`` on the error when the chain was walked)."""
+    return tiff_index(data, dir)[0]
+
+
+def _tiff_rect(rect):
+    if rect is None:
+        return None, None
+    r = (C.c_uint32 * 4)(*[int(v) for v in rect])
+    return r, C.cast(r, C.c_void_p)
+
+
+def tiff_dtype(info):
+    """The numpy dtype of an image's samples: from ``bits`` and ``sample_format`` (2: signed, 3 at 32 bits: float32, else
+    unsigned), little-endian as the reader writes them."""
+    bits, fmt = int(info["bits"]), int(info["sample_format"])
+    if fmt == 3 and bits == 32:
+        return np.dtype("<f4")
+    return np.dtype("<%s%d" % ("i" if fmt == 2 else "u", bits // 8))
+
+
+def tiff_read(data, dir=0, rect=None, flags=0):
+    """A rectangle ``(x, y, w, h)`` of directory ``dir`` of a TIFF file (None: the whole image) as a numpy array of shape
+    ``(h, w, spp)`` (zes_tiff_read_alloc: only the tiles or strips under the rectangle are uploaded and decoded).  The dtype
+    is tiff_dtype()'s.  A file the rule refuses, or a touched segment that fails, raises."""
+    a = _as_u8(data)
+    got = []
+
+    def alloc(_user, _index, n):
+        got.append(np.empty(max(int(n), 1), dtype=np.uint8))
+        return got[0].ctypes.data
+
+    img = np.zeros(1, dtype=TIFF_IMAGE)
+    n = C.c_uint64()
+    keep, r = _tiff_rect(rect)
+    rc = lib().zes_tiff_read_alloc(_ptr(a), a.size, int(dir), r, ALLOC_FN(alloc), None, C.byref(n), img.ctypes.data, flags)
+    if rc:
+        _raise(rc)
+    info = img[0]
+    w, h = (int(info["width"]), int(info["height"])) if rect is None else (int(rect[2]), int(rect[3]))
+    return got[0][: n.value].view(tiff_dtype(info)).reshape(h, w, int(info["spp"]))
+
+
+def last_tiff_read():
+    """``(segments, bytes_up)``: the segments the last tiff_read call's rectangle touched and the bytes it uploaded."""
+    a, b = C.c_uint32(), C.c_uint64()
+    lib().zes_last_tiff_read(C.byref(a), C.byref(b))
+    return a.value, b.value
+
+
+def tiff_index_tensor(t, dir=0):
+    """tiff_index for a file in a 1-D uint8 CUDA tensor (zes_tiff_index_dev: only the header, the directories and the two
+    arrays come down).  The result is what tiff_read_tensor takes as ``index``."""
+    assert t.is_cuda and t.dtype.itemsize == 1 and t.dim() == 1 and t.is_contiguous(), "tiff_index_tensor: a 1-D uint8 CUDA tensor"
+    img, off, ln, dirs = _tiff_index(lib().zes_tiff_index_dev, t.data_ptr() if t.numel() else None, t.numel(), dir)
+    return _tiff_dict(img, dirs), off, ln
+
+
+def tiff_read_tensor(t, index, rect=None, out=None, flags=0):
+    """A rectangle of an indexed image decoded on the device (zes_tiff_read_dev): ``(pixels, seg_status, status)``.
+    ``pixels`` is a uint8 tensor of shape ``(h, w, spp * bits / 8)`` — a view of ``out`` (a 1-D uint8 CUDA tensor, any
+    alignment) when that is given — samples little-endian; ``seg_status`` has one status per segment (0 for one that was
+    decoded or not touched) and ``status`` is the call's: 0, or the first failing segment's (the good segments' pixels are
+    written all the same).  Anything else the call refuses raises."""
+    import torch
+
+    info, off, ln = index
+    assert t.is_cuda and t.dtype.itemsize == 1 and t.dim() == 1 and t.is_contiguous(), "tiff_read_tensor: a 1-D uint8 CUDA tensor"
+    img = np.zeros(1, dtype=TIFF_IMAGE)
+    for k in TIFF_IMAGE.names:
+        img[0][k] = info[k]
+    w, h = (int(info["width"]), int(info["height"])) if rect is None else (int(rect[2]), int(rect[3]))
+    ps = int(info["spp"]) * int(info["bits"]) // 8
+    if out is None:
+        out = torch.empty(max(w * h * ps, 1), dtype=torch.uint8, device=t.device)
+    assert out.is_cuda and out.dtype == torch.uint8 and out.dim() == 1 and out.is_contiguous(), "tiff_read_tensor: `out` is a 1-D uint8 CUDA tensor"
+    off, ln = np.ascontiguousarray(off, dtype=np.uint64), np.ascontiguousarray(ln, dtype=np.uint64)
+    nseg = int(info["across"]) * int(info["down"])
+    assert off.size == nseg and ln.size == nseg, "tiff_read_tensor: one offset and one length per segment"
+    st = np.zeros(max(nseg, 1), dtype=np.int32)
+    n = C.c_uint64()
+    keep, r = _tiff_rect(rect)
+    rc = lib().zes_tiff_read_dev(t.data_ptr() if t.numel() else None, t.numel(), img.ctypes.data, _ptr(off), _ptr(ln), r, out.data_ptr(), out.numel(),
+                                 C.byref(n), st.ctypes.data, flags)
+    if rc in (ZES_E_ARG, ZES_E_DEVICE, ZES_E_NOSPACE):
+        _raise_need(rc, n)
+    return out[: n.value].view(h, w, ps), st[:nseg], rc
 
 
 def set_profiling(on):

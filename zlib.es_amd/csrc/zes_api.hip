@@ -219,6 +219,8 @@ struct Ctx {
   int last_tier = 0;
   bool device_chain = false;  // the block-parallel tier follows a single buffer's chain with k_inf_chain too, not on the host (pngpix_core)
   int last_members = 0;  // members the member-parallel gzip reader decoded in the last gunzip call (0: the serial path answered)
+  uint32_t last_tiff_segs = 0;  // the last zes_tiff_read_* call: the segments its rectangle touched, the bytes it uploaded (zes_last_tiff_read)
+  uint64_t last_tiff_up = 0;
   uint32_t last_gzb[2] = {0, 0};  // files of the last zes_gunzip_batch* call that finished as one batch / on the per-file route
   uint32_t route[ZES_ROUTE_WORDS] = {0};  // zes_stage_lz77_dev's last block: what its kernels did (zes_stage_lz77_route)
   SurvList sv;  // (of `surv`)
@@ -2944,6 +2946,7 @@ const char* zes_strerror(int status) {
     case ZES_E_ZIP: return "zes: not a valid ZIP archive or entry (end record, directory or local header)";
     case ZES_E_UNSUPPORTED: return "zes: unsupported ZIP feature (ZIP64, several disks, encryption, a method other than 0 or 8)";
     case ZES_E_PNG: return "zes: not a valid PNG file (signature, chunk chain or header), or image data that does not fit its header";
+    case ZES_E_TIFF: return "zes: not a valid TIFF file (header, directory chain or tags), or image data that does not fit its directory";
     default: return "zes: unknown status";
   }
 }
@@ -6008,6 +6011,424 @@ int zes_pngpix_dev(const uint8_t* d_in, const uint64_t* in_off, const uint64_t* 
 int zes_pngpix_alloc(const uint8_t* const* in, const uint64_t* in_len, uint32_t count, zes_alloc_fn alloc, void* user, uint64_t* out_len,
                      int32_t* status, zes_png_info* info, uint32_t flags) {
   return png_alloc_form(true, in, in_len, count, alloc, user, out_len, status, info, flags);
+}
+
+// ---- TIFF reader (include/zes.h: "zes_tiff_*"): the file rule on the host, the touched segments through inflate_jobs as one
+// batch, the pixels by k_tiff_place ----
+// What the rule says about one directory of a file: the record, the segment arrays, the chain's length
+struct TiffIndex {
+  zes_tiff_image im;
+  std::vector<uint64_t> off, len;
+  uint32_t dirs = 0;
+};
+// fetch(pos, len): the file's bytes [pos, pos + len), which the rule has checked to lie inside the file, valid until the rule
+// returns; null when they cannot be had (the device form's copy failed: *frc says how)
+using TiffFetch = std::function<const uint8_t*(uint64_t, uint64_t)>;
+
+static uint64_t tiff_ps(const zes_tiff_image& m) { return (uint64_t)m.spp * (m.bits / 8u); }
+static uint64_t tiff_ceil(uint64_t a, uint64_t b) { return (a + b - 1) / b; }
+// the rows of the segments of segment row sy, and the decoded size of one of them (step 2 of include/zes.h)
+static uint32_t tiff_seg_rows(const zes_tiff_image& m, uint32_t sy) {
+  return m.tiled ? m.seg_h : (uint32_t)std::min<uint64_t>(m.seg_h, m.height - (uint64_t)sy * m.seg_h);
+}
+static uint64_t tiff_seg_size(const zes_tiff_image& m, uint32_t sy) { return (uint64_t)m.seg_w * tiff_seg_rows(m, sy) * tiff_ps(m); }
+
+// The file rule of include/zes.h on a file of c bytes, directory `dir`: the verdict; x.dirs is filled once the chain has been
+// walked, the rest of x with ZES_OK only
+static int tiff_rule(uint64_t c, uint32_t dir, const TiffFetch& fetch, const int* frc, TiffIndex& x) {
+  memset(&x.im, 0, sizeof x.im);
+  x.off.clear();
+  x.len.clear();
+  x.dirs = 0;
+  // header
+  if (c < 8) return ZES_E_TIFF;
+  const uint8_t* h = fetch(0, 8);
+  if (!h) return *frc;
+  if (!((h[0] == 0x49 && h[1] == 0x49) || (h[0] == 0x4d && h[1] == 0x4d))) return ZES_E_TIFF;
+  const bool be = h[0] == 0x4d;
+  auto u16 = [be](const uint8_t* p) { return be ? (uint32_t)p[0] << 8 | p[1] : (uint32_t)p[1] << 8 | p[0]; };
+  auto u32 = [be](const uint8_t* p) {
+    return be ? (uint32_t)p[0] << 24 | (uint32_t)p[1] << 16 | (uint32_t)p[2] << 8 | p[3] : (uint32_t)p[3] << 24 | (uint32_t)p[2] << 16 | (uint32_t)p[1] << 8 | p[0];
+  };
+  if (u16(h + 2) == 43) return ZES_E_UNSUPPORTED;
+  if (u16(h + 2) != 42) return ZES_E_TIFF;
+  // chain
+  uint64_t o = u32(h + 4), at = 0;
+  uint32_t n_at = 0, dirs = 0;
+  while (o) {
+    if (dirs >= 65536 || o < 8 || o + 2 > c) return ZES_E_TIFF;
+    const uint8_t* p = fetch(o, 2);
+    if (!p) return *frc;
+    const uint32_t n = u16(p);
+    if (o + 2 + 12ull * n + 4 > c) return ZES_E_TIFF;
+    if (dirs == dir) at = o, n_at = n;
+    if (!(p = fetch(o + 2 + 12ull * n, 4))) return *frc;
+    o = u32(p);
+    dirs++;
+  }
+  x.dirs = dirs;
+  if (dir >= dirs) return ZES_E_ARG;
+  // entries
+  struct Tag {
+    uint32_t id;
+    bool have = false;
+    uint32_t type = 0, count = 0;
+    uint64_t pos = 0;
+    explicit Tag(uint32_t i) : id(i) {}
+  };
+  Tag t_w(256), t_h(257), t_bits(258), t_comp(259), t_photo(262), t_fill(266), t_soff(273), t_spp(277), t_rps(278), t_slen(279), t_planar(284), t_pred(317),
+      t_tw(322), t_tl(323), t_toff(324), t_tlen(325), t_extra(338), t_fmt(339);
+  Tag* const used[] = {&t_w, &t_h, &t_bits, &t_comp, &t_photo, &t_fill, &t_soff, &t_spp, &t_rps, &t_slen, &t_planar, &t_pred, &t_tw, &t_tl, &t_toff, &t_tlen,
+                       &t_extra, &t_fmt};
+  const uint8_t* ents = n_at ? fetch(at + 2, 12ull * n_at) : h;
+  if (!ents) return *frc;
+  for (uint32_t i = 0; i < n_at; i++) {
+    const uint8_t* e = ents + 12ull * i;
+    const uint32_t id = u16(e);
+    for (Tag* t : used) {
+      if (t->id != id || t->have) continue;
+      t->type = u16(e + 2), t->count = u32(e + 4);
+      if ((t->type != 3 && t->type != 4) || !t->count) return ZES_E_TIFF;
+      const uint64_t bytes = (uint64_t)t->count * (t->type == 3 ? 2 : 4);
+      t->pos = at + 2 + 12ull * i + 8;
+      if (bytes > 4) {
+        t->pos = u32(e + 8);
+        if (t->pos + bytes > c) return ZES_E_TIFF;
+      }
+      t->have = true;
+    }
+  }
+  // values k0 .. k0 + n - 1 of a tag that is there (inline ones out of the entries, the others by one fetch)
+  bool lost = false;
+  auto values = [&](const Tag& t, uint64_t k0, uint64_t n, std::vector<uint64_t>& v) {
+    const uint32_t size = t.type == 3 ? 2 : 4;
+    const bool inl = (uint64_t)t.count * size <= 4;
+    const uint8_t* p = inl ? ents + (t.pos - (at + 2)) + k0 * size : fetch(t.pos + k0 * size, n * size);
+    if (!p) {
+      lost = true;
+      return;
+    }
+    v.resize(n);
+    for (uint64_t k = 0; k < n; k++) v[k] = size == 2 ? u16(p + 2 * k) : u32(p + 4 * k);
+  };
+  auto first = [&](const Tag& t, uint64_t absent) -> uint64_t {
+    if (!t.have) return absent;
+    std::vector<uint64_t> v;
+    values(t, 0, 1, v);
+    return lost ? 0 : v[0];
+  };
+  // geometry
+  if (!t_w.have || !t_h.have) return ZES_E_TIFF;
+  const uint64_t W = first(t_w, 0), H = first(t_h, 0);
+  if (lost) return *frc;
+  if (!W || !H) return ZES_E_TIFF;
+  const bool strips = t_soff.have || t_slen.have, tiles = t_tw.have || t_tl.have || t_toff.have || t_tlen.have;
+  if (strips == tiles) return ZES_E_TIFF;
+  if (strips ? !(t_soff.have && t_slen.have) : !(t_tw.have && t_tl.have && t_toff.have && t_tlen.have)) return ZES_E_TIFF;
+  uint64_t sw, sh;
+  if (tiles) {
+    sw = first(t_tw, 0), sh = first(t_tl, 0);
+    if (lost) return *frc;
+    if (!sw || !sh || sw % 16 || sh % 16) return ZES_E_TIFF;
+  } else {
+    sw = W, sh = first(t_rps, H);
+    if (lost) return *frc;
+    if (!sh) return ZES_E_TIFF;
+    sh = std::min(sh, H);
+  }
+  const uint64_t across = tiff_ceil(W, sw), down = tiff_ceil(H, sh), nseg = across * down;
+  const Tag &t_off = tiles ? t_toff : t_soff, &t_len = tiles ? t_tlen : t_slen;
+  if (t_off.count != nseg || t_len.count != nseg) return ZES_E_TIFF;
+  values(t_off, 0, nseg, x.off);
+  if (!lost) values(t_len, 0, nseg, x.len);
+  if (lost) return *frc;
+  for (uint64_t k = 0; k < nseg; k++)
+    if (x.off[k] + x.len[k] > c) return ZES_E_TIFF;
+  // defaults and kinds
+  const uint64_t spp = first(t_spp, 1), comp = first(t_comp, 1), pred = first(t_pred, 1), planar = first(t_planar, 1), fill = first(t_fill, 1);
+  const uint64_t fmt = first(t_fmt, 1), photo = first(t_photo, 0), extra = first(t_extra, 0);
+  if (lost) return *frc;
+  if (!spp || (t_bits.have ? t_bits.count : 1u) != spp) return ZES_E_TIFF;
+  std::vector<uint64_t> bits(1, 1);
+  if (t_bits.have) values(t_bits, 0, spp, bits);
+  if (lost) return *frc;
+  for (uint64_t b : bits)
+    if (b != bits[0]) return ZES_E_UNSUPPORTED;
+  if (bits[0] != 8 && bits[0] != 16 && bits[0] != 32) return ZES_E_UNSUPPORTED;
+  if (spp > 4) return ZES_E_UNSUPPORTED;
+  if (planar != 1 && spp > 1) return ZES_E_UNSUPPORTED;
+  if (fill != 1) return ZES_E_UNSUPPORTED;
+  if (comp != 1 && comp != 8 && comp != 32946) return ZES_E_UNSUPPORTED;
+  if (pred == 3) return ZES_E_UNSUPPORTED;
+  if (pred == 2 && comp == 1) return ZES_E_UNSUPPORTED;
+  if (sw * sh > 0xFFFFFFFFull / (spp * (bits[0] / 8))) return ZES_E_UNSUPPORTED;  // (sw, sh < 2^32: the product fits; times the pixel's bytes it might not)
+  if (nseg > 0x7fffffffull) return ZES_E_UNSUPPORTED;
+  if (pred != 1 && pred != 2) return ZES_E_TIFF;
+  zes_tiff_image& m = x.im;
+  m.width = (uint32_t)W, m.height = (uint32_t)H, m.seg_w = (uint32_t)sw, m.seg_h = (uint32_t)sh, m.across = (uint32_t)across, m.down = (uint32_t)down;
+  m.bits = (uint16_t)bits[0], m.spp = (uint16_t)spp, m.compression = (uint16_t)comp, m.predictor = (uint16_t)pred, m.photometric = (uint16_t)photo;
+  m.sample_format = (uint16_t)fmt, m.extra_samples = (uint16_t)extra;
+  m.big_endian = be, m.tiled = tiles;
+  m.out_size = W * H * spp * (bits[0] / 8);
+  return ZES_OK;
+}
+static_assert(sizeof(zes_tiff_image) == 48 && offsetof(zes_tiff_image, out_size) == 40, "zes_tiff_image is 48 bytes without pad fields");
+
+static int tiff_index_args(const uint8_t* in, uint64_t c, zes_tiff_image* img, const uint64_t* seg_off, const uint64_t* seg_len, uint64_t cap,
+                           uint64_t* segments, uint32_t* dirs, uint32_t flags) {
+  if (!img || !segments || !dirs || (!in && c) || flags || (cap && (!seg_off || !seg_len))) return ZES_E_ARG;
+  memset(img, 0, sizeof *img);
+  *segments = 0;
+  *dirs = 0;
+  return ZES_OK;
+}
+
+static int tiff_index_out(int rrc, const TiffIndex& x, zes_tiff_image* img, uint64_t* seg_off, uint64_t* seg_len, uint64_t cap, uint64_t* segments,
+                          uint32_t* dirs) {
+  *dirs = x.dirs;
+  if (rrc) return rrc;
+  *img = x.im;
+  *segments = x.off.size();
+  if (cap < x.off.size()) return ZES_E_NOSPACE;
+  memcpy(seg_off, x.off.data(), 8 * x.off.size());
+  memcpy(seg_len, x.len.data(), 8 * x.len.size());
+  return ZES_OK;
+}
+
+int zes_tiff_index(const uint8_t* in, uint64_t c, uint32_t dir, zes_tiff_image* img, uint64_t* seg_off, uint64_t* seg_len, uint64_t cap,
+                   uint64_t* segments, uint32_t* dirs, uint32_t flags) {
+  if (const int arc = tiff_index_args(in, c, img, seg_off, seg_len, cap, segments, dirs, flags)) return arc;
+  TiffIndex x;
+  const int frc = ZES_OK;
+  const int rrc = tiff_rule(c, dir, [&](uint64_t pos, uint64_t) { return in + pos; }, &frc, x);
+  return tiff_index_out(rrc, x, img, seg_off, seg_len, cap, segments, dirs);
+}
+
+int zes_tiff_index_dev(const uint8_t* d_in, uint64_t c, uint32_t dir, zes_tiff_image* img, uint64_t* seg_off, uint64_t* seg_len, uint64_t cap,
+                       uint64_t* segments, uint32_t* dirs, uint32_t flags) {
+  ROUTE_DEV(d_in);
+  if (const int arc = tiff_index_args(d_in, c, img, seg_off, seg_len, cap, segments, dirs, flags)) return arc;
+  if (c < 8) return ZES_E_TIFF;
+  LOCK_READY();
+  std::deque<std::vector<uint8_t>> kept;  // (every piece stays until the rule returns)
+  int frc = ZES_OK;
+  auto fetch = [&](uint64_t pos, uint64_t len) -> const uint8_t* {
+    kept.emplace_back(len + 1);
+    if (len && (hipMemcpyAsync(kept.back().data(), d_in + pos, len, hipMemcpyDeviceToHost, g.stream) != hipSuccess || hipStreamSynchronize(g.stream) != hipSuccess)) {
+      (void)hipGetLastError();
+      frc = ZES_E_DEVICE;
+      return nullptr;
+    }
+    return kept.back().data();
+  };
+  TiffIndex x;
+  const int rrc = tiff_rule(c, dir, fetch, &frc, x);
+  return tiff_index_out(rrc, x, img, seg_off, seg_len, cap, segments, dirs);
+}
+
+// One segment that the rectangle touches: its place in the arrays, where its bytes lie in d_src, its decoded size, its first
+// pixel's place in the image and its rows; then its status, and where its decoded bytes lie in k_tiff_place's source
+struct TiffSeg {
+  uint32_t idx;
+  uint64_t at, len, E;
+  uint32_t x0, y0, rows;
+  int32_t status = ZES_OK;
+  uint64_t src_off = 0;
+};
+
+// a record the rule could have produced (step 1 of include/zes.h)
+static bool tiff_record_ok(const zes_tiff_image& m) {
+  if (!m.width || !m.height || !m.seg_w || !m.seg_h || m.big_endian > 1 || m.tiled > 1) return false;
+  if ((m.bits != 8 && m.bits != 16 && m.bits != 32) || m.spp < 1 || m.spp > 4) return false;
+  if ((m.compression != 1 && m.compression != 8 && m.compression != 32946) || (m.predictor != 1 && m.predictor != 2)) return false;
+  if (m.predictor == 2 && m.compression == 1) return false;
+  if (m.tiled ? (m.seg_w % 16 || m.seg_h % 16) : (m.seg_w != m.width || m.seg_h > m.height)) return false;
+  if (m.across != tiff_ceil(m.width, m.seg_w) || m.down != tiff_ceil(m.height, m.seg_h)) return false;
+  if ((uint64_t)m.across * m.down > 0x7fffffffull || (uint64_t)m.seg_w * m.seg_h > 0xFFFFFFFFull / tiff_ps(m)) return false;
+  return m.out_size == (uint64_t)m.width * m.height * tiff_ps(m);
+}
+
+// the rectangle of a call (null: the whole image), or false for an empty one or one that leaves the image
+static bool tiff_rect_of(const zes_tiff_image& m, const zes_tiff_rect* rect, zes_tiff_rect* r) {
+  *r = rect ? *rect : zes_tiff_rect{0, 0, m.width, m.height};
+  return r->w && r->h && (uint64_t)r->x + r->w <= m.width && (uint64_t)r->y + r->h <= m.height;
+}
+
+// the segments under the rectangle, in segment order; seg(k) = (file position, length) of segment k
+static void tiff_touched(const zes_tiff_image& m, const zes_tiff_rect& r, const std::function<std::pair<uint64_t, uint64_t>(uint32_t)>& seg,
+                         std::vector<TiffSeg>& ts) {
+  const uint32_t sx0 = r.x / m.seg_w, sx1 = (r.x + r.w - 1) / m.seg_w, sy0 = r.y / m.seg_h, sy1 = (r.y + r.h - 1) / m.seg_h;
+  for (uint32_t sy = sy0; sy <= sy1; sy++)
+    for (uint32_t sx = sx0; sx <= sx1; sx++) {
+      TiffSeg t;
+      t.idx = sy * m.across + sx;
+      const std::pair<uint64_t, uint64_t> ol = seg(t.idx);
+      t.at = ol.first, t.len = ol.second;
+      t.E = tiff_seg_size(m, sy);
+      t.x0 = sx * m.seg_w, t.y0 = sy * m.seg_h, t.rows = tiff_seg_rows(m, sy);
+      ts.push_back(t);
+    }
+}
+
+// Steps 3 to 5 of include/zes.h for the touched segments ts, whose bytes lie at d_src + at: the rectangle r of image m to dst.
+// Every segment's status is left in ts; the return value is the call's own (a device error, scratch that could not grow).
+static int tiff_read_core(const uint8_t* d_src, const zes_tiff_image& m, std::vector<TiffSeg>& ts, const zes_tiff_rect& r, uint8_t* dst, uint32_t flags) {
+  int rc;
+  g.last_tier = 0;
+  // what copies queued on the stream read (the gather's segments, the kernel's jobs), and the guard behind them
+  std::vector<ZesGzSeg> segs;
+  std::vector<ZesTiffJob> tj;
+  Drain drain;
+  const uint8_t* src = d_src;
+  if (m.compression != 1) {  // 4. the zlib streams: gathered, decoded, their lengths and trailers checked
+    std::vector<InfJob> jobs;
+    uint64_t ipos = 0, opos = 0;
+    for (const TiffSeg& t : ts) {
+      if (t.len) segs.push_back(ZesGzSeg{t.at, ipos, t.len, 0u, 0u});
+      InfJob j{ipos, t.len, opos, gz_slot_cap(t.E), 0, ZES_OK, 0};
+      j.want_end = true;
+      jobs.push_back(j);
+      ipos += gz_slot_in(t.len);
+      opos += gz_slot_out(t.E);
+    }
+    if ((rc = ensure(g.gz_bodies, ipos + 64)) || (rc = ensure(g.gz_outs, opos + 64))) return rc;
+    if ((rc = gz_gather(d_src, (uint8_t*)g.gz_bodies.p, segs))) return rc;
+    // the same kernels for four segments as for many: a single stream's block chain is followed on the device too
+    g.device_chain = true;
+    rc = inflate_jobs((const uint8_t*)g.gz_bodies.p, (uint8_t*)g.gz_outs.p, jobs, nullptr, flags & ZES_F_PIECES);
+    g.device_chain = false;
+    if (rc) return rc;
+    for (size_t q = 0; q < jobs.size(); q++)
+      if (jobs[q].status == ZES_E_NOSPACE || (jobs[q].status == ZES_OK && jobs[q].out_len != ts[q].E)) jobs[q].status = ZES_E_TIFF;
+    if ((rc = check_adler_jobs((const uint8_t*)g.gz_bodies.p, nullptr, (const uint8_t*)g.gz_outs.p, jobs))) return rc;
+    keep_times();
+    for (size_t q = 0; q < jobs.size(); q++) ts[q].status = jobs[q].status, ts[q].src_off = jobs[q].out_off;
+    src = (const uint8_t*)g.gz_outs.p;
+  } else {  // 3. read where they lie
+    for (TiffSeg& t : ts) t.status = t.len < t.E ? ZES_E_TIFF : ZES_OK, t.src_off = t.at;
+  }
+  // 5. the pixels
+  const uint32_t ps = (uint32_t)tiff_ps(m), run = ps % 3 ? 16u : 48u;
+  ZesTiffCall call;
+  memset(&call, 0, sizeof call);
+  call.pitch = (uint64_t)r.w * ps;
+  call.rx = r.x, call.ry = r.y;
+  call.seg_rowbytes = m.seg_w * ps;  // (at most a segment's decoded size: 32 bits)
+  while (call.lanes_log2 < 6 && ((uint64_t)run << call.lanes_log2) < call.seg_rowbytes) call.lanes_log2++;
+  const uint32_t side = 64u >> call.lanes_log2;
+  call.unit_rows = side * (uint32_t)std::min<uint64_t>(4, std::max<uint64_t>(1, 4096 / ((uint64_t)call.seg_rowbytes * side)));
+  call.bps = m.bits / 8u, call.spp = m.spp, call.predictor = m.predictor, call.big_endian = m.big_endian;
+  uint64_t units = 0;
+  for (const TiffSeg& t : ts) {
+    if (t.status != ZES_OK) continue;
+    ZesTiffJob j;
+    memset(&j, 0, sizeof j);
+    j.src_off = t.src_off, j.x0 = t.x0, j.y0 = t.y0;
+    j.row_lo = std::max(r.y, t.y0) - t.y0, j.row_hi = (uint32_t)std::min<uint64_t>((uint64_t)r.y + r.h, (uint64_t)t.y0 + t.rows) - t.y0;
+    j.col_lo = std::max(r.x, t.x0) - t.x0, j.col_hi = (uint32_t)std::min<uint64_t>((uint64_t)r.x + r.w, (uint64_t)t.x0 + m.seg_w) - t.x0;
+    j.first_unit = (uint32_t)units;
+    units += tiff_ceil(j.row_hi - j.row_lo, call.unit_rows);
+    if (units > 0x7fffffffull) return ZES_E_ARG;
+    tj.push_back(j);
+  }
+  if (tj.empty()) {
+    drain.done();  // (inflate_jobs and check_adler_jobs have brought their results down: the stream is past segs)
+    return ZES_OK;
+  }
+  call.njobs = (uint32_t)tj.size();
+  ZesTiffJob closing;
+  memset(&closing, 0, sizeof closing);
+  closing.first_unit = (uint32_t)units;
+  tj.push_back(closing);
+  if ((rc = ensure(g.gz_tab, sizeof(ZesTiffJob) * tj.size()))) return rc;
+  HIPCHK(hipMemcpyAsync(g.gz_tab.p, tj.data(), sizeof(ZesTiffJob) * tj.size(), hipMemcpyHostToDevice, g.stream));
+  {
+    Timed t("k_tiff_place");
+    constexpr uint32_t per = ZES_TIFF_THREADS / 64u;
+    hipLaunchKernelGGL(k_tiff_place, dim3((uint32_t)((units + per - 1) / per)), dim3(ZES_TIFF_THREADS), 0, g.stream, src, dst, (const ZesTiffJob*)g.gz_tab.p, call);
+  }
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipStreamSynchronize(g.stream));
+  drain.done();
+  return ZES_OK;
+}
+static_assert(sizeof(ZesTiffJob) == 40, "ZesTiffJob: 8-byte aligned records back to back");
+
+// the call's status from its segments', and the caller's seg_status filled
+static int tiff_verdict(const zes_tiff_image& m, const std::vector<TiffSeg>& ts, int32_t* seg_status) {
+  int worst = ZES_OK;
+  if (seg_status)
+    for (uint64_t k = 0; k < (uint64_t)m.across * m.down; k++) seg_status[k] = ZES_OK;
+  for (const TiffSeg& t : ts) {
+    if (seg_status) seg_status[t.idx] = t.status;
+    if (!worst) worst = t.status;
+  }
+  return worst;
+}
+
+int zes_tiff_read_dev(const uint8_t* d_in, uint64_t c, const zes_tiff_image* img, const uint64_t* seg_off, const uint64_t* seg_len,
+                      const zes_tiff_rect* rect, uint8_t* d_out, uint64_t cap, uint64_t* out_len, int32_t* seg_status, uint32_t flags) {
+  ROUTE_DEV(d_in, d_out);
+  if (!out_len) return ZES_E_ARG;
+  *out_len = 0;
+  zes_tiff_rect r;
+  if (!img || !seg_off || !seg_len || (!d_in && c) || (flags & ~ZES_F_PIECES) || !tiff_record_ok(*img) || !tiff_rect_of(*img, rect, &r)) return ZES_E_ARG;
+  std::vector<TiffSeg> ts;
+  tiff_touched(*img, r, [&](uint32_t k) { return std::make_pair(seg_off[k], seg_len[k]); }, ts);
+  for (const TiffSeg& t : ts)
+    if (t.at > c || t.len > c - t.at) return ZES_E_ARG;
+  *out_len = (uint64_t)r.w * r.h * tiff_ps(*img);
+  if (cap < *out_len) return ZES_E_NOSPACE;
+  if (!d_out) {
+    *out_len = 0;
+    return ZES_E_ARG;
+  }
+  LOCK_READY();
+  g.last_tiff_segs = (uint32_t)ts.size(), g.last_tiff_up = 0;
+  if ((rc = call_done(tiff_read_core(d_in, *img, ts, r, d_out, flags), true))) return rc;
+  return tiff_verdict(*img, ts, seg_status);
+}
+
+int zes_tiff_read_alloc(const uint8_t* in, uint64_t c, uint32_t dir, const zes_tiff_rect* rect, zes_alloc_fn alloc, void* user, uint64_t* out_len,
+                        zes_tiff_image* img, uint32_t flags) {
+  UseDev ud(route_host());
+  if (!out_len || !alloc || (!in && c) || (flags & ~ZES_F_PIECES)) return ZES_E_ARG;
+  *out_len = 0;
+  if (img) memset(img, 0, sizeof *img);
+  TiffIndex x;
+  const int frc = ZES_OK;
+  if (const int rrc = tiff_rule(c, dir, [&](uint64_t pos, uint64_t) { return in + pos; }, &frc, x)) return rrc;
+  if (img) *img = x.im;
+  zes_tiff_rect r;
+  if (!tiff_rect_of(x.im, rect, &r)) return ZES_E_ARG;
+  std::vector<TiffSeg> ts;
+  tiff_touched(x.im, r, [&](uint32_t k) { return std::make_pair(x.off[k], x.len[k]); }, ts);
+  const uint64_t size = (uint64_t)r.w * r.h * tiff_ps(x.im);
+  LOCK_READY();
+  HostBatch hb(g.gz_in, g.gz_acc);
+  uint64_t up = 0;
+  for (TiffSeg& t : ts) {
+    up += t.len;
+    t.at = hb.place(in + t.at, t.len);
+  }
+  const uint64_t place = hb.room(size);
+  g.last_tiff_segs = (uint32_t)ts.size(), g.last_tiff_up = up;
+  if ((rc = hb.up())) return rc;
+  if ((rc = call_done(tiff_read_core(hb.d_in(), x.im, ts, r, hb.d_out() + place, flags), true))) return rc;
+  if ((rc = tiff_verdict(x.im, ts, nullptr))) return rc;
+  uint8_t* to = alloc(user, 0, size);
+  if (!to) return ZES_E_ARG;
+  if ((rc = download(to, hb.d_out() + place, size))) return rc;
+  *out_len = size;
+  return ZES_OK;
+}
+
+int zes_last_tiff_read(uint32_t* segments, uint64_t* bytes_up) {
+  UseDev ud(t_last);
+  std::lock_guard<std::mutex> lk(g_mu);
+  if (segments) *segments = g.last_tiff_segs;
+  if (bytes_up) *bytes_up = g.last_tiff_up;
+  return ZES_OK;
 }
 
 // ---- PNG writer (include/zes.h: "zes_pngwrite*"): filters by k_png_filter, zlib bodies by EncGroup, files by k_png_pack ----

@@ -322,6 +322,30 @@ struct ZesPngwRec {
 #define ZES_PNGW_NO_SLOT 0xFFFFFFFFFFFFFFFFull
 #define ZES_PNGW_IDAT 65536u   // data bytes of an IDAT chunk (the last one: what is left)
 #define ZES_PNGW_BLOCK 65535u  // bytes of a stored block (the last one: what is left)
+// k_tiff_place (zes_tiff.hip): what is the same for every segment of a call, and one touched segment.  A segment's rows
+// [row_lo, row_hi) - those the rectangle reaches - are cut into units of unit_rows rows, a wave each: the waves
+// [first_unit, next record's first_unit) of the launch.  The table has a closing record behind the last segment: only its
+// first_unit counts, the launch's waves
+struct ZesTiffCall {
+  uint64_t pitch;         // bytes of a row of the rectangle: rw * spp * bps
+  uint32_t rx, ry;        // the rectangle's first column and row in the image
+  uint32_t seg_rowbytes;  // bytes of a segment's row where it lies: seg_w * spp * bps
+  uint32_t lanes_log2;    // a row is taken by 2^lanes_log2 lanes at a time, so a wave takes 64 >> lanes_log2 rows side by side
+  uint32_t unit_rows;     // rows of a unit: a multiple of 64 >> lanes_log2
+  uint32_t bps, spp;      // bytes a sample (1, 2, 4), samples a pixel (1..4)
+  uint32_t predictor;     // 1 or 2
+  uint32_t big_endian;
+  uint32_t njobs;
+};
+struct ZesTiffJob {
+  uint64_t src_off;       // the segment's decoded bytes: 16-byte aligned in the scratch; anywhere in the file (Compression 1)
+  uint32_t x0, y0;        // the image column and row of the segment's first pixel
+  uint32_t row_lo, row_hi;  // the segment's rows that lie inside the rectangle
+  uint32_t col_lo, col_hi;  // the segment's columns that lie inside the rectangle (the predictor still starts at column 0)
+  uint32_t first_unit;
+  uint32_t pad;
+};
+#define ZES_TIFF_THREADS 256u   // four independent waves to a workgroup
 // k_crc32_put (zes_crc.hip): where buffer q of a k_crc32_seg launch has its CRC-32 stored, most significant byte first, and
 // what finishes it from the buffer's two accumulator words: mul * word 0 ^ word 1 ^ add
 struct ZesCrcPut {
@@ -415,6 +439,8 @@ __global__ void k_png_walk(const uint8_t*, const ZesPngFile*, uint32_t, ZesPngHe
 __global__ void k_png_unfilter(const uint8_t*, uint8_t*, uint8_t*, const ZesPngJob*, uint32_t, uint32_t, uint32_t*);
 __global__ void k_png_deinterlace(const uint8_t*, uint8_t*, const ZesPngDeintJob*, uint32_t, const uint32_t*);
 __global__ void k_png_expand(const uint8_t*, const uint8_t*, uint8_t*, const ZesPngxJob*, uint32_t);
+// TIFF reader (zes_tiff.hip)
+__global__ void k_tiff_place(const uint8_t*, uint8_t*, const ZesTiffJob*, ZesTiffCall);
 // PNG writer (zes_pngw.hip, zes_crc.hip)
 __global__ void k_png_filter(const uint8_t*, uint8_t*, const ZesPngwJob*, uint32_t);
 __global__ void k_png_pack(const uint8_t*, const uint8_t*, const uint8_t*, uint8_t*, const ZesPngwRec*, uint32_t);

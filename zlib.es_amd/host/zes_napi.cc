@@ -1127,6 +1127,76 @@ napi_value PngEncodeBatch(napi_env env, napi_callback_info info) {
   return j.rc == 0 ? batch_results(env, &j) : throw_status(env, j.rc);
 }
 
+// ---- TIFF images (include/zes.h: zes_tiff_index, zes_tiff_read_alloc) ----
+// the optional directory number at argument k: undefined counts as 0
+bool tiff_dir(napi_env env, const Args& a, size_t k, uint32_t* dir) {
+  *dir = 0;
+  napi_valuetype vt = napi_undefined;
+  if (a.argc <= k || napi_typeof(env, a.argv[k], &vt) != napi_ok || vt == napi_undefined) return true;
+  uint64_t d = 0;
+  if (!get_safe_uint(env, a.argv[k], &d) || d > 0xFFFFFFFFull) return false;
+  *dir = (uint32_t)d;
+  return true;
+}
+// a zes_tiff_image record and the chain's length behind it as 52 bytes; the façade makes the object
+napi_value tiff_record(napi_env env, const zes_tiff_image& rec, uint32_t dirs) {
+  void* raw = nullptr;
+  napi_value v = new_u8(env, sizeof rec + 4, &raw);
+  if (!v) return nullptr;
+  memcpy(raw, &rec, sizeof rec);
+  memcpy(static_cast<uint8_t*>(raw) + sizeof rec, &dirs, 4);
+  return v;
+}
+// tiffInfo(file[, dir]): what the file rule says about directory dir.  The host form: no device is touched.
+napi_value TiffInfo(napi_env env, napi_callback_info info) {
+  static const char SIG[] = "tiffInfo(file[, dir])";
+  const Args a = get_args(env, info);
+  const Bytes in = need_bytes(env, a, 0, SIG, "file");
+  if (!in.ok) return nullptr;
+  uint32_t dir = 0, dirs = 0;
+  if (!tiff_dir(env, a, 1, &dir)) return throw_type(env, std::string(SIG) + ": dir must be a non-negative integer below 2^32");
+  zes_tiff_image rec;
+  uint64_t nseg = 0;
+  const int rc = zes_tiff_index(in.p, in.n, dir, &rec, nullptr, nullptr, 0, &nseg, &dirs, ZES_F_DEFAULT);  // (the sizing call: ZES_E_NOSPACE on a valid file)
+  if (rc != ZES_E_NOSPACE) return throw_status(env, rc ? rc : ZES_E_ARG);
+  return tiff_record(env, rec, dirs);
+}
+// tiffRead(file, dir, rect): a rectangle (a Uint32Array of x, y, w, h; undefined: the whole image) of directory dir decoded
+// by zes_tiff_read_alloc, through the batch forms' marshalling as a batch of one: { results: [pixels], info }
+napi_value TiffRead(napi_env env, napi_callback_info info) {
+  static const char SIG[] = "tiffRead(file, dir, rect)";
+  const Args a = get_args(env, info);
+  const Bytes in = need_bytes(env, a, 0, SIG, "file");
+  if (!in.ok) return nullptr;
+  uint32_t dir = 0;
+  if (!tiff_dir(env, a, 1, &dir)) return throw_type(env, std::string(SIG) + ": dir must be a non-negative integer below 2^32");
+  zes_tiff_rect rect;
+  bool have_rect = false;
+  napi_valuetype vt = napi_undefined;
+  if (a.argc > 2 && napi_typeof(env, a.argv[2], &vt) == napi_ok && vt != napi_undefined) {
+    napi_typedarray_type type;
+    void* p = nullptr;
+    size_t len = 0, off = 0;
+    napi_value ab;
+    bool is_ta = false;
+    if (napi_is_typedarray(env, a.argv[2], &is_ta) != napi_ok || !is_ta || napi_get_typedarray_info(env, a.argv[2], &type, &len, &p, &ab, &off) != napi_ok ||
+        type != napi_uint32_array || len != 4)
+      return throw_type(env, std::string(SIG) + ": rect must be a Uint32Array of x, y, w, h");
+    memcpy(&rect, p, sizeof rect);
+    have_rect = true;
+  }
+  BatchJob j(1);
+  zes_tiff_image rec;
+  j.rc = zes_tiff_read_alloc(in.p, in.n, dir, have_rect ? &rect : nullptr, batch_alloc, &j, j.out_len.data(), &rec, ZES_F_DEFAULT);
+  if (j.rc) return throw_status(env, j.rc);
+  napi_value res, vres = batch_results(env, &j), vinfo = tiff_record(env, rec, 0);
+  if (!vres || !vinfo) return nullptr;
+  if (napi_create_object(env, &res) != napi_ok) return nullptr;
+  napi_set_named_property(env, res, "results", vres);
+  napi_set_named_property(env, res, "info", vinfo);
+  return res;
+}
+
 // gzipBatch(inputs) and gunzipBatch(files): independent buffers written as one gzip file each, and independent gzip files
 // decoded, as one batch (include/zes.h: zes_gzip_batch, zes_gunzip_batch_alloc): per item a fresh Uint8Array or the Error that
 // says why not, as the batch forms answer.  The two differ in the entry point alone.
@@ -1236,6 +1306,8 @@ napi_value ModuleInit(napi_env env, napi_value exports) {
       {"pngDecodeBatch", swept<PngDecodeBatch>},
       {"pngPixelsBatch", swept<PngPixelsBatch>},
       {"pngEncodeBatch", swept<PngEncodeBatch>},
+      {"tiffInfo", swept<TiffInfo>},
+      {"tiffRead", swept<TiffRead>},
       {"lastGunzipMembers", swept<LastGunzipMembers>},
       {"init", swept<Init>},
       {"initDevices", swept<InitDevices>},

@@ -52,6 +52,16 @@ export declare type PngSource = {
 };
 export declare function pngEncode(image: PngSource): Uint8Array;
 export declare function pngEncodeBatch(images: PngSource[]): BatchResult[];
+/** TIFF images, reading: a directory's geometry on the host, and a rectangle of it decoded on the device (uncompressed and zlib-compressed tiles or strips, Predictor 2 undone, samples little-endian). */
+export declare type TiffInfo = {
+  width: number, height: number, segmentWidth: number, segmentHeight: number, across: number, down: number, bits: number, samples: number,
+  compression: number, predictor: number, photometric: number, sampleFormat: number, extraSamples: number, bigEndian: boolean, tiled: boolean,
+  size: number, dirs: number };
+export declare type TiffRect = { x: number, y: number, w: number, h: number };
+export declare type TiffOptions = { dir?: number, rect?: TiffRect };
+export declare type TiffImage = { width: number, height: number, samples: number, bits: number, data: Uint8Array };
+export declare function tiffInfo(file: Uint8Array, dir?: number): TiffInfo;
+export declare function tiffRead(file: Uint8Array, options?: TiffOptions): TiffImage;
 export declare function init(device: number): void;
 export declare function initDevices(n?: number): number;
 export declare function trim(): void;

@@ -295,6 +295,47 @@ function pngEncode(image) {
 }
 
 /**
+ * Extra (not in the reference API): TIFF images, reading.  `tiffInfo` judges directory `dir` (default 0) of a file on the host
+ * (no device is touched) and returns its geometry: size, the tiles' or strips' size (`segmentWidth`, `segmentHeight`) and
+ * count (`across`, `down`), `bits` (8, 16 or 32) and `samples` (1..4) a pixel, the Compression, Predictor, Photometric,
+ * SampleFormat and ExtraSamples tags as the file states them, the decoded `size` and `dirs`, the length of the file's directory
+ * chain.  `tiffRead` decodes a rectangle `{ x, y, w, h }` of that image (default: the whole image) on the device: only the
+ * tiles or strips under the rectangle are uploaded, they go through the inflate tiers as one batch, and one launch undoes
+ * Predictor 2, drops tile padding and puts the rows in place.  `data` holds `height` rows of `width * samples * bits / 8`
+ * bytes, samples of 16 and 32 bits little-endian whatever the file's byte order.  Uncompressed and zlib-compressed
+ * (Compression 8, 32946) files are read; anything else, and a tile or strip that fails, throws the Error that says why.
+ * (`...dir` and `...options` are read as `dir[0]` and `options[0]`, as `pngDecode` reads its own.)
+ */
+const tiffInfoOf = (raw) => {  // a zes_tiff_image record (48 bytes, include/zes.h) and the chain's length
+  const v = new DataView(raw.buffer, raw.byteOffset, 52);
+  const u32 = (o) => v.getUint32(o, true), u16 = (o) => v.getUint16(o, true);
+  return {
+    width: u32(0), height: u32(4), segmentWidth: u32(8), segmentHeight: u32(12), across: u32(16), down: u32(20), bits: u16(24), samples: u16(26),
+    compression: u16(28), predictor: u16(30), photometric: u16(32), sampleFormat: u16(34), extraSamples: u16(36), bigEndian: v.getUint8(38) !== 0,
+    tiled: v.getUint8(39) !== 0, size: Number(v.getBigUint64(40, true)), dirs: u32(48),
+  };
+};
+
+function tiffInfo(file, ...dir) {
+  return tiffInfoOf(addon.tiffInfo(file, dir[0]));
+}
+
+function tiffRead(file, ...options) {
+  const o = options[0];
+  if (o !== undefined && (o === null || typeof o !== 'object' || Array.isArray(o))) throw new TypeError('tiffRead(file, options): options must be an object { dir?, rect? }');
+  let rect;
+  if (o && o.rect !== undefined) {
+    const r = o.rect;
+    if (!r || typeof r !== 'object' || ![r.x, r.y, r.w, r.h].every((k) => Number.isInteger(k) && k >= 0 && k <= 0xFFFFFFFF))
+      throw new TypeError('tiffRead(file, options): rect must be { x, y, w, h } of unsigned integers');
+    rect = Uint32Array.of(r.x, r.y, r.w, r.h);
+  }
+  const got = addon.tiffRead(file, o ? o.dir : undefined, rect);
+  const info = tiffInfoOf(got.info);
+  return { width: rect ? rect[2] : info.width, height: rect ? rect[3] : info.height, samples: info.samples, bits: info.bits, data: got.results[0] };
+}
+
+/**
  * Extra: how many members the last gunzip() of this thread decoded as one batch (a BGZF file: all of them, the
  * end-of-file marker included); 0 when the members went one after the other.
  */
@@ -356,6 +397,8 @@ exports.pngPixelsBatch = pngPixelsBatch;
 exports.pngPixels = pngPixels;
 exports.pngEncodeBatch = pngEncodeBatch;
 exports.pngEncode = pngEncode;
+exports.tiffInfo = tiffInfo;
+exports.tiffRead = tiffRead;
 exports.lastGunzipMembers = lastGunzipMembers;
 exports.adler32 = adler32;
 exports.init = init;
