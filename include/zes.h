@@ -733,7 +733,7 @@ int zes_pngpix_expand_dev(const uint8_t* d_in, const uint64_t* in_off, const uin
                           uint32_t flags);
 
 /* TIFF images (TIFF 6.0; Compression 8 and 32946 of TIFF Technical Note 2): the index of one image of a file, and a rectangle
- * of that image decoded as one batch.  Reading is all there is: no TIFF writer.  The tiles or strips of an image ("segments")
+ * of that image decoded as one batch (zes_tiffwrite*, below, is the other direction).  The tiles or strips of an image ("segments")
  * are independent zlib streams that state their own sizes, as BGZF members are, and Predictor 2 chains within a row, never
  * across rows: every row of every segment is independent work, and a rectangle needs only the segments it touches.
  *
@@ -830,6 +830,71 @@ int zes_tiff_read_dev(const uint8_t* d_in, uint64_t c, const zes_tiff_image* img
 int zes_tiff_read_alloc(const uint8_t* in, uint64_t c, uint32_t dir, const zes_tiff_rect* rect, zes_alloc_fn alloc, void* user, uint64_t* out_len,
                         zes_tiff_image* img, uint32_t flags);
 int zes_last_tiff_read(uint32_t* segments, uint64_t* bytes_up);
+
+/* zes_tiffwrite*: one image written to one classic TIFF file with one directory, its tiles or strips encoded as one batch.
+ * The input is what zes_tiff_read_* writes for the whole image: height rows of width * spp * bits / 8 bytes, dense, row by row
+ * from the top, samples of 16 and 32 bits little-endian whatever byte order the file gets.  The record is the reader's own
+ * zes_tiff_image, so index -> read -> write round-trips: a record that zes_tiff_index produced for a file this writer accepts
+ * writes a file whose index is that record again.
+ * The file, byte for byte (the same input gives the same bytes):
+ *   header      8 bytes: 49 49 2a 00 or 4d 4d 00 2a by big_endian, and the directory's offset
+ *   segments    from offset 8 on in row-major segment order, each at an even offset: one zero pad byte follows a segment of
+ *               odd length.  A segment's decoded bytes: a tile is always whole, columns right of the image and rows below it
+ *               are zeros; a strip holds min(seg_h, height - y0) rows of the image's width.  Under Predictor 2 every sample
+ *               from the segment's second pixel on has the sample spp places before it subtracted, modulo 2^bits, from the
+ *               segment's column 0 through the pad pixels too, on host-order values; the samples are then put in the file's
+ *               byte order.  Compression 1: those bytes as they are.  Compression 8 and 32946: what zes_deflate gives for
+ *               them when the encoder accepts the length (not 1, not 1 mod 131072) and the stream is shorter than the stored
+ *               form; otherwise the stored form of zes_pngwrite*: 78 01, stored blocks of 65535 bytes, the Adler-32.  The
+ *               Compression tag holds the value the record gave
+ *   arrays      behind the segments the values that do not fit an entry, each array at an even offset, in this order:
+ *               BitsPerSample when spp >= 3; ExtraSamples when its count is 3; SampleFormat when it is written and spp >= 3;
+ *               the offsets when there are at least 2 segments; the byte counts likewise
+ *   directory   at an even offset behind them, with a next-offset of 0.  Entries sorted by tag: 256, 257 (LONG); 258 (SHORT
+ *               x spp); 259; 262; 273 or 324, 278 or 322 / 323, 279 or 325 (all LONG); 277; 284 = 1; 317 only when the
+ *               predictor is 2; 338 only when spp exceeds the photometric's base (1 for Photometric 0 and 1, 3 for 2):
+ *               spp - base values, each extra_samples; 339 only when sample_format != 1: spp values; nothing else.  Tags
+ *               without a type here are SHORT.  Values that fit 4 bytes lie in their entry
+ * Statuses, the first that applies:
+ *   1. ZES_E_ARG: a null img or out_len; a null d_in / in with n != 0; a null alloc; flag bits other than ZES_F_PIECES; a
+ *      record that step 1 of zes_tiff_read_* rejects (one function serves both; across, down and out_size are computed again
+ *      from the other fields); n != out_size; big_endian or tiled above 1; bits not 8, 16 or 32; spp outside 1..4; tile
+ *      dimensions that are not non-zero multiples of 16; compression not 1, 8 or 32946; predictor not 1 or 2; photometric not
+ *      0, 1 or 2; spp below the photometric's base; extra_samples above 2, or non-zero when spp equals the base;
+ *      sample_format not 1, 2 or 3, or 3 at a depth other than 32
+ *   2. ZES_E_UNSUPPORTED, the reader's own lines, so that the writer never makes a file the reader refuses: Predictor 2 with
+ *      Compression 1; a segment of more than 0xFFFFFFFF decoded bytes; more than 2^31 - 1 segments; and a bound above
+ *      0xFFFFFFFF (classic TIFF offsets have 32 bits; BigTIFF is not written)
+ *   3. ZES_E_NOSPACE, device form only: cap below the file's size, or a null d_out.  *out_len is the size needed (cap == 0
+ *      with a null d_out is the sizing call); every group is still encoded; no byte outside [d_out, d_out + cap) is written,
+ *      the bytes inside are unspecified
+ * On ZES_OK exactly *out_len bytes are written, at any alignment of d_out.  The input is read only inside the aligned 16-byte
+ * groups that hold it.  seg_off / seg_len (null, or across * down values each): the positions and byte counts of the segments
+ * as written, what zes_tiff_index would give for the file.
+ * zes_tiffwrite_bound: *cap = the file's size with every segment in the stored form (Compression 1: as it is) - exact when
+ * all segments go stored, and always enough; *segments (may be null) = across * down.  Statuses 1 and 2 as above with n taken
+ * as out_size; a null cap is ZES_E_ARG.  It touches no device.
+ * The segments go in groups, in order, as zes_pngwrite*'s images do: up to 1024 of them whose encoder slots take up to 256 MiB
+ * (4 and 1 MiB under ZES_F_PIECES: same bytes).  Launches per group:
+ *   k_tiff_cut    once: every segment of the group cut out of the image into a 16-byte aligned slot of pooled scratch
+ *                 (zes_trim, zes_pool_bytes and zes_stage_poison cover it): Predictor 2 applied, pad columns and rows stored
+ *                 as zeros, samples in the file's byte order
+ *   the encoder   one batch encode over the slots (no CRC-32 launch); its read-back of the sizes is the group's one
+ *                 read-back.  Compression 1 skips it
+ *   k_adler_seg   once, only in a group with lengths the encoder refuses (only strips have them: a tile is a multiple of 256
+ *                 bytes): their Adler-32s, finished on the host (a second read-back).  A segment that goes stored because its
+ *                 stream was longer takes the Adler-32 the encoder left behind the stream
+ *   k_tiff_pack   once: the group's segments at their file positions with their pad bytes, as stream or stored form; in the
+ *                 last group also the arrays, the directory and the header, which go up once as one host-built blob
+ * No launch, copy or synchronisation per segment; Compression 1 takes the same path through the scratch.
+ * zes_tiffwrite is the host form: it stages the input, runs the same steps with the bound's room, calls alloc(user, 0, size)
+ * once and brings the bytes down (a null answer: ZES_E_ARG).
+ * replaces: nothing (the reference has no TIFF container) */
+int zes_tiffwrite_bound(const zes_tiff_image* img, uint64_t* cap, uint64_t* segments);
+int zes_tiffwrite_dev(const uint8_t* d_in, uint64_t n, const zes_tiff_image* img, uint8_t* d_out, uint64_t cap, uint64_t* out_len,
+                      uint64_t* seg_off, uint64_t* seg_len, uint32_t flags);
+int zes_tiffwrite(const uint8_t* in, uint64_t n, const zes_tiff_image* img, zes_alloc_fn alloc, void* user, uint64_t* out_len,
+                  uint32_t flags);
 
 /* Adler-32 of a buffer (standard value as an unsigned 32-bit).
  * replaces: `calcAdler32` src/adler32.ts:1-10 (byte extraction at src/zlib.ts:37-40). */

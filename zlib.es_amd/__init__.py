@@ -180,6 +180,9 @@ def lib():
                                         C.c_uint32]
         L.zes_tiff_read_alloc.argtypes = [C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, ALLOC_FN, C.c_void_p, u64p, C.c_void_p, C.c_uint32]
         L.zes_last_tiff_read.argtypes = [u32p, C.c_void_p]
+        L.zes_tiffwrite_bound.argtypes = [C.c_void_p, u64p, u64p]
+        L.zes_tiffwrite_dev.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, u64p, C.c_void_p, C.c_void_p, C.c_uint32]
+        L.zes_tiffwrite.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, ALLOC_FN, C.c_void_p, u64p, C.c_uint32]
         L.zes_gunzip_alloc.argtypes = [C.c_void_p, C.c_uint64, ALLOC_FN, C.c_void_p, u64p, C.c_uint32]
         L.zes_gzip_batch_bound.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p]
         for name in ("zes_gzip_batch_dev", "zes_gunzip_batch_dev"):
@@ -1537,6 +1540,91 @@ def tiff_read_tensor(t, index, rect=None, out=None, flags=0):
     if rc in (ZES_E_ARG, ZES_E_DEVICE, ZES_E_NOSPACE):
         _raise_need(rc, n)
     return out[: n.value].view(h, w, ps), st[:nseg], rc
+
+
+# ---- TIFF writer (include/zes.h: "zes_tiffwrite*") ---------------------------------------------
+def tiff_image(width, height, bits=8, spp=1, tile=None, rows=None, compression=8, predictor=2, photometric=None, sample_format=1, extra_samples=None,
+               big_endian=False):
+    """A consistent zes_tiff_image record (a dict, as tiff_info gives it without ``dirs``) for tiff_write: ``tile=(w, h)`` for
+    tiles, else strips of ``rows`` rows (default: one strip).  photometric defaults to 2 (RGB) from 3 samples on, else 1;
+    extra_samples to 2 (unassociated alpha) when there are samples beyond the photometric's.  Nothing is checked here: the
+    write call does that."""
+    width, height, spp = int(width), int(height), int(spp)
+    assert tile is None or rows is None, "tiff_image: tiles or strips, not both"
+    if tile is not None:
+        seg_w, seg_h, tiled = int(tile[0]), int(tile[1]), 1
+    else:
+        seg_w, seg_h, tiled = width, min(int(rows), height) if rows is not None else height, 0
+    if photometric is None:
+        photometric = 2 if spp >= 3 else 1
+    base = 3 if photometric == 2 else 1
+    if extra_samples is None:
+        extra_samples = 2 if spp > base else 0
+    return dict(width=width, height=height, seg_w=seg_w, seg_h=seg_h, across=-(-width // seg_w) if seg_w else 0, down=-(-height // seg_h) if seg_h else 0,
+                bits=int(bits), spp=spp, compression=int(compression), predictor=int(predictor), photometric=int(photometric),
+                sample_format=int(sample_format), extra_samples=int(extra_samples), big_endian=int(bool(big_endian)), tiled=tiled,
+                out_size=width * height * spp * (int(bits) // 8))
+
+
+def _tiff_record(record):
+    img = np.zeros(1, dtype=TIFF_IMAGE)
+    for k in TIFF_IMAGE.names:
+        img[0][k] = record[k]
+    return img
+
+
+def tiff_bound(record):
+    """``(cap, segments)``: a capacity that always suffices for the file tiff_write makes of ``record`` - exact when every
+    segment goes stored - and the number of its segments (zes_tiffwrite_bound; no GPU needed)."""
+    img = _tiff_record(record)
+    cap, nseg = C.c_uint64(), C.c_uint64()
+    rc = lib().zes_tiffwrite_bound(img.ctypes.data, C.byref(cap), C.byref(nseg))
+    if rc:
+        _raise(rc)
+    return cap.value, nseg.value
+
+
+def tiff_write(pixels, record, flags=0):
+    """The TIFF file of one image as ``bytes`` (zes_tiffwrite).  ``pixels``: what tiff_read gives for the whole image - an
+    array of ``record["out_size"]`` bytes in all, rows from the top, samples little-endian - and ``record`` a tiff_image() or a
+    tiff_info() of a file this writer accepts."""
+    a = pixels if isinstance(pixels, np.ndarray) else np.frombuffer(bytes(pixels), dtype=np.uint8)
+    a = np.ascontiguousarray(a).reshape(-1).view(np.uint8)
+    img = _tiff_record(record)
+    got = []
+
+    def alloc(_user, _index, n):
+        got.append(np.empty(max(int(n), 1), dtype=np.uint8))
+        return got[0].ctypes.data
+
+    n = C.c_uint64()
+    rc = lib().zes_tiffwrite(_ptr(a), a.size, img.ctypes.data, ALLOC_FN(alloc), None, C.byref(n), flags)
+    if rc:
+        _raise(rc)
+    return got[0][: n.value].tobytes()
+
+
+def tiff_write_tensor(t, record, out=None, flags=0):
+    """The TIFF file of an image that lies in a 1-D uint8 CUDA tensor, written on the device (zes_tiffwrite_dev):
+    ``(file, seg_off, seg_len)`` - the file a uint8 tensor (a view of ``out``, a 1-D uint8 CUDA tensor at any alignment, when
+    that is given; else a tensor of tiff_bound()'s size is made) and the positions and byte counts of its segments, what
+    tiff_index would give for it.  A capacity below the file's size raises with ``.need``."""
+    import torch
+
+    assert t.is_cuda and t.dtype.itemsize == 1 and t.dim() == 1 and t.is_contiguous(), "tiff_write_tensor: a 1-D uint8 CUDA tensor"
+    img = _tiff_record(record)
+    bound, nseg = tiff_bound(record)  # (raises for a record the writer refuses, before anything is sized by it)
+    if out is None:
+        out = torch.empty(bound, dtype=torch.uint8, device=t.device)
+    assert out.is_cuda and out.dtype == torch.uint8 and out.dim() == 1 and out.is_contiguous(), "tiff_write_tensor: `out` is a 1-D uint8 CUDA tensor"
+    off, ln = np.zeros(nseg, dtype=np.uint64), np.zeros(nseg, dtype=np.uint64)
+    n = C.c_uint64()
+    torch.cuda.current_stream(t.device).synchronize()  # the library runs on its own stream
+    rc = lib().zes_tiffwrite_dev(t.data_ptr() if t.numel() else None, t.numel(), img.ctypes.data, out.data_ptr() if out.numel() else None, out.numel(),
+                                 C.byref(n), off.ctypes.data, ln.ctypes.data, flags)
+    if rc:
+        _raise_need(rc, n)
+    return out[: n.value], off, ln
 
 
 def set_profiling(on):

@@ -6236,17 +6236,21 @@ struct TiffSeg {
   uint64_t src_off = 0;
 };
 
-// a record the rule could have produced (step 1 of include/zes.h)
-static bool tiff_record_ok(const zes_tiff_image& m) {
-  if (!m.width || !m.height || !m.seg_w || !m.seg_h || m.big_endian > 1 || m.tiled > 1) return false;
-  if ((m.bits != 8 && m.bits != 16 && m.bits != 32) || m.spp < 1 || m.spp > 4) return false;
-  if ((m.compression != 1 && m.compression != 8 && m.compression != 32946) || (m.predictor != 1 && m.predictor != 2)) return false;
-  if (m.predictor == 2 && m.compression == 1) return false;
-  if (m.tiled ? (m.seg_w % 16 || m.seg_h % 16) : (m.seg_w != m.width || m.seg_h > m.height)) return false;
-  if (m.across != tiff_ceil(m.width, m.seg_w) || m.down != tiff_ceil(m.height, m.seg_h)) return false;
-  if ((uint64_t)m.across * m.down > 0x7fffffffull || (uint64_t)m.seg_w * m.seg_h > 0xFFFFFFFFull / tiff_ps(m)) return false;
-  return m.out_size == (uint64_t)m.width * m.height * tiff_ps(m);
+// A record the rule could have produced (step 1 of include/zes.h): ZES_OK, or what is wrong with it - ZES_E_ARG for values no
+// file gives the record, then ZES_E_UNSUPPORTED for the kinds the rule refuses.  The reader turns both down alike
+// (tiff_record_ok); the writer answers them as they are.
+static int tiff_record_status(const zes_tiff_image& m) {
+  if (!m.width || !m.height || !m.seg_w || !m.seg_h || m.big_endian > 1 || m.tiled > 1) return ZES_E_ARG;
+  if ((m.bits != 8 && m.bits != 16 && m.bits != 32) || m.spp < 1 || m.spp > 4) return ZES_E_ARG;
+  if ((m.compression != 1 && m.compression != 8 && m.compression != 32946) || (m.predictor != 1 && m.predictor != 2)) return ZES_E_ARG;
+  if (m.tiled ? (m.seg_w % 16 || m.seg_h % 16) : (m.seg_w != m.width || m.seg_h > m.height)) return ZES_E_ARG;
+  if (m.across != tiff_ceil(m.width, m.seg_w) || m.down != tiff_ceil(m.height, m.seg_h)) return ZES_E_ARG;
+  if ((unsigned __int128)m.out_size != (unsigned __int128)m.width * m.height * tiff_ps(m)) return ZES_E_ARG;
+  if (m.predictor == 2 && m.compression == 1) return ZES_E_UNSUPPORTED;
+  if ((uint64_t)m.across * m.down > 0x7fffffffull || (uint64_t)m.seg_w * m.seg_h > 0xFFFFFFFFull / tiff_ps(m)) return ZES_E_UNSUPPORTED;
+  return ZES_OK;
 }
+static bool tiff_record_ok(const zes_tiff_image& m) { return tiff_record_status(m) == ZES_OK; }
 
 // the rectangle of a call (null: the whole image), or false for an empty one or one that leaves the image
 static bool tiff_rect_of(const zes_tiff_image& m, const zes_tiff_rect* rect, zes_tiff_rect* r) {
@@ -6762,6 +6766,291 @@ int zes_pngpix_expand_dev(const uint8_t* d_in, const uint64_t* in_off, const uin
   g.carry.clear();
   g.last_tier = 0;
   return call_done(pngx_run(d_in, nullptr, d_out, table, njobs, tiles), true);
+}
+
+// ---- TIFF writer (include/zes.h: "zes_tiffwrite*"): segments by k_tiff_cut, zlib streams by EncGroup, the file by k_tiff_pack ----
+// What the record alone says (statuses 1 and 2 of include/zes.h), and the sizes that follow from it
+struct TiffwPlan {
+  uint32_t base = 1;      // the photometric's samples: what spp exceeds are extra samples
+  uint32_t entries = 0;   // of the directory
+  uint64_t nseg = 0;
+  uint64_t tail = 0;      // bytes of the out-of-line arrays and the directory
+  uint64_t bound = 0;     // the file with every segment in the stored form
+};
+static uint64_t tiffw_stored_len(const zes_tiff_image& m, uint64_t E) { return m.compression == 1 ? E : pngw_stored_len(E); }
+static uint64_t tiffw_even(uint64_t v) { return v + (v & 1); }
+static int tiffw_plan(const zes_tiff_image& m, uint64_t n, TiffwPlan* p) {
+  const int st = tiff_record_status(m);
+  if (st == ZES_E_ARG || n != m.out_size) return ZES_E_ARG;
+  if (m.photometric > 2) return ZES_E_ARG;
+  p->base = m.photometric == 2 ? 3u : 1u;
+  if (m.spp < p->base || m.extra_samples > 2 || (m.spp == p->base && m.extra_samples)) return ZES_E_ARG;
+  if (m.sample_format < 1 || m.sample_format > 3 || (m.sample_format == 3 && m.bits != 32)) return ZES_E_ARG;
+  if (st) return st;
+  p->nseg = (uint64_t)m.across * m.down;
+  const bool fmt = m.sample_format != 1;
+  p->entries = (m.tiled ? 11u : 10u) + (m.predictor == 2 ? 1u : 0u) + (m.spp > p->base ? 1u : 0u) + (fmt ? 1u : 0u);
+  // (every array has an even size: none needs a pad byte in front of the next)
+  p->tail = (m.spp >= 3 ? 2ull * m.spp : 0) + (m.spp - p->base == 3 ? 6ull : 0) + (fmt && m.spp >= 3 ? 2ull * m.spp : 0) + (p->nseg >= 2 ? 8 * p->nseg : 0) + 2 +
+            12ull * p->entries + 4;
+  // the segments: every row of them alike but the last row of strips
+  const unsigned __int128 full = (unsigned __int128)(p->nseg - m.across) * tiffw_even(tiffw_stored_len(m, tiff_seg_size(m, 0)));
+  const unsigned __int128 bound = 8 + full + (unsigned __int128)m.across * tiffw_even(tiffw_stored_len(m, tiff_seg_size(m, m.down - 1))) + p->tail;
+  if (bound > 0xFFFFFFFFull) return ZES_E_UNSUPPORTED;
+  p->bound = (uint64_t)bound;
+  return ZES_OK;
+}
+
+// The out-of-line arrays and the directory as they lie at the even file position `at`, the segments at off[k] with len[k] bytes
+static void tiffw_tail(const zes_tiff_image& m, const TiffwPlan& p, const uint64_t* off, const uint64_t* len, uint64_t at, std::vector<uint8_t>& b) {
+  const bool be = m.big_endian != 0;
+  auto p16 = [&](uint32_t v) {
+    b.push_back((uint8_t)(be ? v >> 8 : v));
+    b.push_back((uint8_t)(be ? v : v >> 8));
+  };
+  auto p32 = [&](uint32_t v) {
+    for (int k = 0; k < 4; k++) b.push_back((uint8_t)(v >> (8 * (be ? 3 - k : k))));
+  };
+  struct Ent {
+    uint32_t tag, type;  // 3: SHORT, 4: LONG
+    std::vector<uint32_t> vals;
+    uint32_t pos = 0;    // of values that do not fit the entry
+  };
+  std::vector<Ent> ents;
+  auto add = [&](uint32_t tag, uint32_t type, std::vector<uint32_t> vals) { ents.push_back(Ent{tag, type, std::move(vals), 0u}); };
+  std::vector<uint32_t> voff((size_t)p.nseg), vlen((size_t)p.nseg);
+  for (uint64_t k = 0; k < p.nseg; k++) voff[(size_t)k] = (uint32_t)off[k], vlen[(size_t)k] = (uint32_t)len[k];
+  add(256, 4, {m.width});
+  add(257, 4, {m.height});
+  add(258, 3, std::vector<uint32_t>(m.spp, m.bits));
+  add(259, 3, {m.compression});
+  add(262, 3, {m.photometric});
+  if (!m.tiled) add(273, 4, voff);
+  add(277, 3, {m.spp});
+  if (!m.tiled) add(278, 4, {m.seg_h}), add(279, 4, vlen);
+  add(284, 3, {1u});
+  if (m.predictor == 2) add(317, 3, {2u});
+  if (m.tiled) add(322, 4, {m.seg_w}), add(323, 4, {m.seg_h}), add(324, 4, voff), add(325, 4, vlen);
+  if (m.spp > p.base) add(338, 3, std::vector<uint32_t>(m.spp - p.base, m.extra_samples));
+  if (m.sample_format != 1) add(339, 3, std::vector<uint32_t>(m.spp, m.sample_format));
+  auto put = [&](const Ent& e) {
+    for (uint32_t v : e.vals) e.type == 3 ? p16(v) : p32(v);
+  };
+  auto size_of = [](const Ent& e) { return (uint64_t)e.vals.size() * (e.type == 3 ? 2u : 4u); };
+  const uint32_t order[5] = {258u, 338u, 339u, m.tiled ? 324u : 273u, m.tiled ? 325u : 279u};
+  for (uint32_t tag : order)
+    for (Ent& e : ents)
+      if (e.tag == tag && size_of(e) > 4) {
+        e.pos = (uint32_t)(at + b.size());
+        put(e);
+      }
+  p16((uint32_t)ents.size());
+  for (const Ent& e : ents) {
+    p16(e.tag), p16(e.type), p32((uint32_t)e.vals.size());
+    if (size_of(e) > 4) {
+      p32(e.pos);
+    } else {
+      const size_t before = b.size();
+      put(e);
+      b.resize(before + 4, 0);
+    }
+  }
+  p32(0);  // no next directory
+}
+
+// The image at d_in (m.out_size bytes, any alignment) written as the file of include/zes.h to d_out[0, cap).  Group by group as
+// pngwrite_core goes (EncGroup::form over the segments' decoded lengths); a group's launches, in order:
+//   k_tiff_cut     once: every segment of the group into its scratch slot (g.gz_outs)
+//   the encoder    EncGroup without its CRC-32 launch, the slots as its input: one deflate_batch_core call, whose read-back is the
+//                  group's (none for Compression 1, and none when the encoder refuses every length)
+//   k_adler_seg    once, and only when the group has lengths that the encoder refuses (1, or 1 mod 131072): their Adler-32s
+//   k_tiff_pack    once: the segments at their file positions; in the last group also the tail and the header, a host-built blob
+// g.gz_tab holds the cut's records, the pack's records and the blob side by side.  Every group's tables, which asynchronous
+// uploads read, stay until the end of the call, in front of a Drain.  A result beyond cap: EncGroup::room's rule.
+static int tiffwrite_core(const uint8_t* d_in, const zes_tiff_image& m, const TiffwPlan& p, uint8_t* d_out, uint64_t cap, uint64_t* out_len,
+                          uint64_t* seg_off, uint64_t* seg_len, uint32_t flags) {
+  int rc;
+  g.carry.clear();
+  g.last_tier = 0;
+  const bool zl = m.compression != 1;
+  const uint32_t ps = (uint32_t)tiff_ps(m), run = ps % 3 ? 16u : 48u;
+  std::deque<std::vector<uint8_t>> blobs;
+  std::vector<ZesCrcSeg> asegs;                                   // a group's lengths that the encoder refuses
+  std::vector<uint64_t> off((size_t)p.nseg), len((size_t)p.nseg);  // the segments as written
+  EncGroup eg(flags, p.nseg);
+  std::vector<uint64_t> c_off(eg.o_off.size()), c_len(eg.o_off.size());
+  Drain drain;  // (behind everything above: uploads read it)
+  auto blob = [&](size_t n) {
+    blobs.emplace_back(n);
+    return blobs.back().data();
+  };
+  ZesTiffCall call;
+  memset(&call, 0, sizeof call);
+  call.pitch = (uint64_t)m.width * ps;
+  call.seg_rowbytes = m.seg_w * ps;
+  while (call.lanes_log2 < 6 && ((uint64_t)run << call.lanes_log2) < call.seg_rowbytes) call.lanes_log2++;
+  const uint32_t side = 64u >> call.lanes_log2;
+  call.unit_rows = side * (uint32_t)std::min<uint64_t>(4, std::max<uint64_t>(1, 4096 / ((uint64_t)call.seg_rowbytes * side)));
+  call.bps = m.bits / 8u, call.spp = m.spp, call.predictor = m.predictor, call.big_endian = m.big_endian;
+  uint64_t total = 8;
+  for (uint64_t e0 = 0; e0 < p.nseg;) {
+    // the group, its scratch slots and encoder slots, the cut's records
+    const uint64_t win = std::min<uint64_t>(eg.group, p.nseg - e0);
+    for (uint64_t k = 0; k < win; k++) c_len[(size_t)k] = tiff_seg_size(m, (uint32_t)((e0 + k) / m.across));
+    uint64_t slots, cbytes = 0, units = 0;
+    const uint32_t cnt = eg.form(c_len.data(), win, &slots);
+    const bool last = e0 + cnt == p.nseg;
+    ZesTiffCutJob* jobs = (ZesTiffCutJob*)blob(sizeof(ZesTiffCutJob) * ((size_t)cnt + 1));
+    for (uint32_t k = 0; k < cnt; k++) {
+      const uint32_t sy = (uint32_t)((e0 + k) / m.across), sx = (uint32_t)((e0 + k) % m.across);
+      c_off[k] = cbytes;
+      cbytes += gz_up16(c_len[k]) + 16;
+      ZesTiffCutJob& j = jobs[k];
+      j.dst_off = c_off[k];
+      j.x0 = sx * m.seg_w, j.y0 = sy * m.seg_h;
+      j.live_rows = tiff_seg_rows(m, sy);
+      j.rows = m.tiled ? m.seg_h : j.live_rows;
+      j.live_rows = std::min(j.live_rows, m.height - j.y0);
+      j.cols = std::min(m.seg_w, m.width - j.x0);
+      j.first_unit = (uint32_t)units;
+      units += tiff_ceil(j.rows, call.unit_rows);
+    }
+    if (units > 0x7fffffffull) return ZES_E_ARG;
+    memset(&jobs[cnt], 0, sizeof(ZesTiffCutJob));
+    jobs[cnt].first_unit = (uint32_t)units;
+    const size_t n_jobs = sizeof(ZesTiffCutJob) * ((size_t)cnt + 1), o_recs = (size_t)gz_up16(n_jobs);
+    const size_t o_blob = o_recs + (size_t)gz_up16(sizeof(ZesTiffPackRec) * ((size_t)cnt + 3)), o_head = (size_t)gz_up16(p.tail);
+    if ((rc = ensure(g.gz_outs, cbytes + 64)) || (rc = ensure(g.gz_tab, o_blob + o_head + 16 + 64))) return rc;
+    uint8_t* cut = (uint8_t*)g.gz_outs.p;
+    uint8_t* tab = (uint8_t*)g.gz_tab.p;
+    HIPCHK(hipMemcpyAsync(tab, jobs, n_jobs, hipMemcpyHostToDevice, g.stream));
+    call.njobs = cnt;
+    {
+      Timed t("k_tiff_cut");
+      constexpr uint32_t per = ZES_TIFF_THREADS / 64u;
+      hipLaunchKernelGGL(k_tiff_cut, dim3((uint32_t)((units + per - 1) / per)), dim3(ZES_TIFF_THREADS), 0, g.stream, d_in, cut, (const ZesTiffCutJob*)tab, call);
+    }
+    HIPCHK(hipGetLastError());
+    std::vector<uint32_t> adler;
+    if (zl) {
+      if ((rc = eg.encode(cut, c_off.data(), c_len.data(), cnt, slots, false))) return rc;
+      // the lengths the encoder refuses: their Adler-32s
+      asegs.clear();
+      for (uint32_t k = 0; k < cnt; k++)
+        if (!eg.o_cap[k]) asegs.push_back(ZesCrcSeg{c_off[k], c_len[k]});
+      adler.resize(asegs.size());
+      if (!asegs.empty() && (rc = adler32_batch_locked(cut, asegs.data(), (uint32_t)asegs.size(), adler.data()))) return rc;
+    }
+    // stream, stored or as it is; the segments' places
+    ZesTiffPackRec* recs = (ZesTiffPackRec*)blob(sizeof(ZesTiffPackRec) * ((size_t)cnt + 3));
+    memset(recs, 0, sizeof(ZesTiffPackRec) * ((size_t)cnt + 3));
+    uint64_t wgs = 0;
+    uint32_t nrec = 0, refused = 0;
+    for (uint32_t k = 0; k < cnt; k++) {
+      const uint64_t E = c_len[k], stored_len = tiffw_stored_len(m, E);
+      const bool stream = zl && eg.o_cap[k] && eg.raw[k] + 6 < stored_len;
+      ZesTiffPackRec& r = recs[nrec++];
+      r.kind = !zl ? ZES_TIFFW_RAW : stream ? ZES_TIFFW_STREAM : ZES_TIFFW_STORED;
+      r.src_off = stream ? eg.o_off[k] : c_off[k];
+      r.dst_off = total;
+      r.adler_off = ZES_PNGW_NO_SLOT;
+      if (zl && !stream) {
+        if (eg.o_cap[k]) r.adler_off = eg.o_off[k] + eg.raw[k] + 2;
+        else r.adler = adler[refused++];
+      }
+      r.len = (uint32_t)(stream ? eg.raw[k] + 6 : E);
+      r.first_wg = (uint32_t)wgs;
+      wgs += r.kind == ZES_TIFFW_STORED ? tiff_ceil(E, ZES_PNGW_BLOCK) : std::max<uint64_t>(1, tiff_ceil(r.len, ZES_TIFFW_PIECE));
+      off[(size_t)(e0 + k)] = total;
+      len[(size_t)(e0 + k)] = stream ? eg.raw[k] + 6 : stored_len;
+      total += tiffw_even(len[(size_t)(e0 + k)]);
+    }
+    uint8_t* hblob = nullptr;
+    if (last) {  // the tail behind the last segment, and the header, which states where the tail's directory lies
+      std::vector<uint8_t> tail;
+      tiffw_tail(m, p, off.data(), len.data(), total, tail);
+      if (tail.size() != p.tail) return ZES_E_DEVICE;  // (the plan's arithmetic and the builder disagree: a bug)
+      hblob = blob(o_head + 16);
+      memcpy(hblob, tail.data(), tail.size());
+      const uint32_t dir = (uint32_t)(total + p.tail - (2 + 12ull * p.entries + 4));
+      const uint8_t head[8] = {(uint8_t)(m.big_endian ? 0x4d : 0x49), (uint8_t)(m.big_endian ? 0x4d : 0x49), (uint8_t)(m.big_endian ? 0 : 42),
+                               (uint8_t)(m.big_endian ? 42 : 0),      (uint8_t)(dir >> (m.big_endian ? 24 : 0)), (uint8_t)(dir >> (m.big_endian ? 16 : 8)),
+                               (uint8_t)(dir >> (m.big_endian ? 8 : 16)), (uint8_t)(dir >> (m.big_endian ? 0 : 24))};
+      memcpy(hblob + o_head, head, 8);
+      for (int q = 0; q < 2; q++) {
+        ZesTiffPackRec& r = recs[nrec++];
+        r.kind = ZES_TIFFW_BLOB;
+        r.src_off = q ? o_head : 0;
+        r.dst_off = q ? 0 : total;
+        r.adler_off = ZES_PNGW_NO_SLOT;
+        r.len = q ? 8u : (uint32_t)p.tail;
+        r.first_wg = (uint32_t)wgs;
+        wgs += std::max<uint64_t>(1, tiff_ceil(r.len, ZES_TIFFW_PIECE));
+      }
+      total += p.tail;
+    }
+    if (wgs > 0x7fffffffull) return ZES_E_ARG;
+    recs[nrec].first_wg = (uint32_t)wgs;
+    if (eg.room(total, cap, d_out)) {
+      HIPCHK(hipMemcpyAsync(tab + o_recs, recs, sizeof(ZesTiffPackRec) * ((size_t)nrec + 1), hipMemcpyHostToDevice, g.stream));
+      if (hblob) HIPCHK(hipMemcpyAsync(tab + o_blob, hblob, o_head + 16, hipMemcpyHostToDevice, g.stream));
+      Timed t("k_tiff_pack");
+      hipLaunchKernelGGL(k_tiff_pack, dim3((uint32_t)wgs), dim3(GZ_GATHER_THREADS), 0, g.stream, (const uint8_t*)cut, (const uint8_t*)g.gz_bodies.p,
+                         (const uint8_t*)(tab + o_blob), d_out, (const ZesTiffPackRec*)(tab + o_recs), nrec);
+    }
+    HIPCHK(hipGetLastError());
+    e0 += cnt;
+  }
+  HIPCHK(hipStreamSynchronize(g.stream));
+  drain.done();
+  for (uint64_t k = 0; k < p.nseg; k++) {
+    if (seg_off) seg_off[k] = off[(size_t)k];
+    if (seg_len) seg_len[k] = len[(size_t)k];
+  }
+  *out_len = total;
+  return eg.fits ? ZES_OK : ZES_E_NOSPACE;
+}
+static_assert(sizeof(ZesTiffCutJob) == 32 && sizeof(ZesTiffPackRec) == 40, "the writer's records: 8-byte aligned, back to back");
+
+int zes_tiffwrite_bound(const zes_tiff_image* img, uint64_t* cap, uint64_t* segments) {
+  if (!img || !cap) return ZES_E_ARG;
+  *cap = 0;
+  if (segments) *segments = 0;
+  TiffwPlan p;
+  if (const int prc = tiffw_plan(*img, img->out_size, &p)) return prc;
+  *cap = p.bound;
+  if (segments) *segments = p.nseg;
+  return ZES_OK;
+}
+
+int zes_tiffwrite_dev(const uint8_t* d_in, uint64_t n, const zes_tiff_image* img, uint8_t* d_out, uint64_t cap, uint64_t* out_len, uint64_t* seg_off,
+                      uint64_t* seg_len, uint32_t flags) {
+  ROUTE_DEV(d_in, d_out);
+  if (!img || !out_len || (!d_in && n) || (flags & ~ZES_F_PIECES)) return ZES_E_ARG;
+  *out_len = 0;
+  TiffwPlan p;
+  if (const int prc = tiffw_plan(*img, n, &p)) return prc;
+  LOCK_READY();
+  return call_done(tiffwrite_core(d_in, *img, p, d_out, cap, out_len, seg_off, seg_len, flags), true);
+}
+
+int zes_tiffwrite(const uint8_t* in, uint64_t n, const zes_tiff_image* img, zes_alloc_fn alloc, void* user, uint64_t* out_len, uint32_t flags) {
+  UseDev ud(route_host());
+  if (!img || !out_len || !alloc || (!in && n) || (flags & ~ZES_F_PIECES)) return ZES_E_ARG;
+  *out_len = 0;
+  TiffwPlan p;
+  if (const int prc = tiffw_plan(*img, n, &p)) return prc;
+  LOCK_READY();
+  HostBatch hb(g.gz_in, g.gz_acc);
+  const uint64_t in_at = hb.place(in, n), out_at = hb.room(p.bound);
+  if ((rc = hb.up())) return rc;
+  uint64_t total = 0;
+  if ((rc = call_done(tiffwrite_core(hb.d_in() + in_at, *img, p, hb.d_out() + out_at, p.bound, &total, nullptr, nullptr, flags), true))) return rc;
+  uint8_t* to = alloc(user, 0, total);
+  if (!to) return ZES_E_ARG;
+  if ((rc = download(to, hb.d_out() + out_at, total))) return rc;
+  *out_len = total;
+  return ZES_OK;
 }
 
 // ---- gzip files as one batch (include/zes.h: "zes_gzip_batch*", "zes_gunzip_batch*") ----

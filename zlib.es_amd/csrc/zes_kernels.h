@@ -346,6 +346,36 @@ struct ZesTiffJob {
   uint32_t pad;
 };
 #define ZES_TIFF_THREADS 256u   // four independent waves to a workgroup
+// k_tiff_cut (zes_tiff.hip): one segment of a TIFF writer's group, cut out of the caller's image into its scratch slot.  What
+// is the same for every segment travels as a ZesTiffCall (pitch: a row of the image; rx, ry: 0).  The segment's rows are cut
+// into units of unit_rows rows, a wave each, as k_tiff_place's are; the table has a closing record
+struct ZesTiffCutJob {
+  uint64_t dst_off;       // the segment's 16-byte aligned slot in the scratch: rows * seg_rowbytes bytes, every one written
+  uint32_t x0, y0;        // the image column and row of the segment's first pixel
+  uint32_t rows;          // rows of the segment as the file holds it (a tile: seg_h; a strip: its rows of the image)
+  uint32_t live_rows;     // ... of which these lie in the image; the rest are zeros
+  uint32_t cols;          // the segment's columns that lie in the image; the rest are zeros
+  uint32_t first_unit;
+};
+// k_tiff_pack (zes_tiff.hip): one range of the file being written.  A record has the workgroups [first_wg, next record's
+// first_wg): one per ZES_TIFFW_PIECE bytes of a stream, of a segment as it is or of a blob, one per stored block of the
+// stored form; the table has a closing record as ZesZipPackRec's has
+struct ZesTiffPackRec {
+  uint64_t src_off;    // STREAM: the zlib stream's first byte (78 9C) in the slots; STORED, RAW: the segment's bytes in the
+                       // scratch; BLOB: the bytes in the device copy of the call's host-built blob
+  uint64_t dst_off;    // the range's first byte in the file
+  uint64_t adler_off;  // STORED: where the Adler-32's four bytes stand in the slots (behind the encoder's stream), or
+                       // ZES_PNGW_NO_SLOT: `adler` holds it
+  uint32_t len;        // STREAM: the stream's bytes; STORED, RAW: the segment's decoded bytes; BLOB: its bytes
+  uint32_t first_wg;
+  uint32_t adler;
+  uint32_t kind;
+};
+#define ZES_TIFFW_STREAM 0u
+#define ZES_TIFFW_STORED 1u     // 78 01, stored blocks of ZES_PNGW_BLOCK bytes, the Adler-32: zes_pngwrite*'s stored form
+#define ZES_TIFFW_RAW 2u        // Compression 1
+#define ZES_TIFFW_BLOB 3u       // the tail (out-of-line arrays and directory) and the header; no pad byte behind it
+#define ZES_TIFFW_PIECE 65536u
 // k_crc32_put (zes_crc.hip): where buffer q of a k_crc32_seg launch has its CRC-32 stored, most significant byte first, and
 // what finishes it from the buffer's two accumulator words: mul * word 0 ^ word 1 ^ add
 struct ZesCrcPut {
@@ -441,6 +471,9 @@ __global__ void k_png_deinterlace(const uint8_t*, uint8_t*, const ZesPngDeintJob
 __global__ void k_png_expand(const uint8_t*, const uint8_t*, uint8_t*, const ZesPngxJob*, uint32_t);
 // TIFF reader (zes_tiff.hip)
 __global__ void k_tiff_place(const uint8_t*, uint8_t*, const ZesTiffJob*, ZesTiffCall);
+// TIFF writer (zes_tiff.hip)
+__global__ void k_tiff_cut(const uint8_t*, uint8_t*, const ZesTiffCutJob*, ZesTiffCall);
+__global__ void k_tiff_pack(const uint8_t*, const uint8_t*, const uint8_t*, uint8_t*, const ZesTiffPackRec*, uint32_t);
 // PNG writer (zes_pngw.hip, zes_crc.hip)
 __global__ void k_png_filter(const uint8_t*, uint8_t*, const ZesPngwJob*, uint32_t);
 __global__ void k_png_pack(const uint8_t*, const uint8_t*, const uint8_t*, uint8_t*, const ZesPngwRec*, uint32_t);

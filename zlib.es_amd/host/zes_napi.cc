@@ -1197,6 +1197,23 @@ napi_value TiffRead(napi_env env, napi_callback_info info) {
   return res;
 }
 
+// tiffWrite(pixels, record): one image written as a TIFF file by zes_tiffwrite, through the batch forms' marshalling as a batch
+// of one.  record: the 48 bytes of a zes_tiff_image (the façade packs its info object)
+napi_value TiffWrite(napi_env env, napi_callback_info info) {
+  static const char SIG[] = "tiffWrite(pixels, record)";
+  const Args a = get_args(env, info);
+  const Bytes in = need_bytes(env, a, 0, SIG, "pixels");
+  if (!in.ok) return nullptr;
+  const Bytes r = need_bytes(env, a, 1, SIG, "record");
+  if (!r.ok) return nullptr;
+  if (r.n != sizeof(zes_tiff_image)) return throw_type(env, std::string(SIG) + ": record must hold the 48 bytes of a zes_tiff_image");
+  zes_tiff_image rec;
+  memcpy(&rec, r.p, sizeof rec);
+  BatchJob j(1);
+  j.rc = zes_tiffwrite(in.p, in.n, &rec, batch_alloc, &j, j.out_len.data(), ZES_F_DEFAULT);
+  return j.rc == 0 ? batch_results(env, &j) : throw_status(env, j.rc);
+}
+
 // gzipBatch(inputs) and gunzipBatch(files): independent buffers written as one gzip file each, and independent gzip files
 // decoded, as one batch (include/zes.h: zes_gzip_batch, zes_gunzip_batch_alloc): per item a fresh Uint8Array or the Error that
 // says why not, as the batch forms answer.  The two differ in the entry point alone.
@@ -1308,6 +1325,7 @@ napi_value ModuleInit(napi_env env, napi_value exports) {
       {"pngEncodeBatch", swept<PngEncodeBatch>},
       {"tiffInfo", swept<TiffInfo>},
       {"tiffRead", swept<TiffRead>},
+      {"tiffWrite", swept<TiffWrite>},
       {"lastGunzipMembers", swept<LastGunzipMembers>},
       {"init", swept<Init>},
       {"initDevices", swept<InitDevices>},

@@ -62,6 +62,9 @@ export declare type TiffOptions = { dir?: number, rect?: TiffRect };
 export declare type TiffImage = { width: number, height: number, samples: number, bits: number, data: Uint8Array };
 export declare function tiffInfo(file: Uint8Array, dir?: number): TiffInfo;
 export declare function tiffRead(file: Uint8Array, options?: TiffOptions): TiffImage;
+/** TIFF images, writing: one image to one classic TIFF file; `info` as tiffInfo gives it (across, down, size and dirs optional), so that info -> read -> write round-trips. */
+export declare type TiffRecord = Omit<TiffInfo, 'across' | 'down' | 'size' | 'dirs'> & { across?: number, down?: number, size?: number, dirs?: number };
+export declare function tiffWrite(pixels: Uint8Array, info: TiffRecord): Uint8Array;
 export declare function init(device: number): void;
 export declare function initDevices(n?: number): number;
 export declare function trim(): void;

@@ -37,6 +37,7 @@ type TiffInfo = {
 type TiffRect = { x: number, y: number, w: number, h: number };
 type TiffOptions = { dir?: number, rect?: TiffRect };
 type TiffImage = { width: number, height: number, samples: number, bits: number, data: Uint8Array };
+type TiffRecord = Omit<TiffInfo, 'across' | 'down' | 'size' | 'dirs'> & { across?: number, down?: number, size?: number, dirs?: number };
 type PngSource = {
   data: Uint8Array, width: number, height: number, colourType: number, depth?: number, filter?: number, palette?: Uint8Array, transparency?: Uint8Array,
 };
@@ -357,6 +358,33 @@ export function tiffRead(file: Uint8Array, ...options: TiffOptions[]): TiffImage
   const got = addon.tiffRead(file, o ? o.dir : undefined, rect);
   const info = tiffInfoOf(got.info);
   return { width: rect ? rect[2] : info.width, height: rect ? rect[3] : info.height, samples: info.samples, bits: info.bits, data: got.results[0] };
+}
+
+/**
+ * Extra (not in the reference API): TIFF images, writing.  `tiffWrite` writes one image to one classic TIFF file with one
+ * directory: `pixels` is what `tiffRead` gives for the whole image (`height` rows of `width * samples * bits / 8` bytes, samples
+ * little-endian whatever `bigEndian` says) and `info` what `tiffInfo` gives (`dirs` is ignored; `across`, `down` and `size` are
+ * computed when they are absent), so that info -> read -> write round-trips.  The tiles or strips are cut, differenced under
+ * Predictor 2 and encoded as one batch on the device; a record the writer refuses throws the Error that says why.
+ */
+export function tiffWrite(pixels: Uint8Array, info: TiffRecord): Uint8Array {
+  if (info === null || typeof info !== 'object' || Array.isArray(info)) throw new TypeError('tiffWrite(pixels, info): info must be an object as tiffInfo gives it');
+  const n = (k, dflt) => {
+    const x = info[k] === undefined ? dflt : info[k];
+    if (!Number.isInteger(x) || x < 0) throw new TypeError('tiffWrite(pixels, info): info.' + k + ' must be a non-negative integer');
+    return x;
+  };
+  const raw = new Uint8Array(48);
+  const v = new DataView(raw.buffer);
+  const width = n('width'), height = n('height'), sw = n('segmentWidth'), sh = n('segmentHeight'), bits = n('bits'), samples = n('samples');
+  const put32 = (o, x) => v.setUint32(o, x > 0xFFFFFFFF ? 0xFFFFFFFF : x, true), put16 = (o, x) => v.setUint16(o, x > 0xFFFF ? 0xFFFF : x, true);
+  put32(0, width); put32(4, height); put32(8, sw); put32(12, sh);
+  put32(16, n('across', sw ? Math.ceil(width / sw) : 0)); put32(20, n('down', sh ? Math.ceil(height / sh) : 0));
+  put16(24, bits); put16(26, samples); put16(28, n('compression', 8)); put16(30, n('predictor', 1)); put16(32, n('photometric', samples >= 3 ? 2 : 1));
+  put16(34, n('sampleFormat', 1)); put16(36, n('extraSamples', 0));
+  v.setUint8(38, info.bigEndian ? 1 : 0); v.setUint8(39, info.tiled ? 1 : 0);
+  v.setBigUint64(40, BigInt(n('size', width * height * samples * Math.floor(bits / 8))), true);
+  return addon.tiffWrite(pixels, raw)[0];
 }
 
 /**
